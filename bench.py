@@ -4,10 +4,17 @@
 A "step" is one pass of the hot path over the whole batch: driver (fast, on device) -> LiDAR sweep written
 to HBM -> integrate -> lap progress, for every env.  All inputs are resident in HBM before the timed region;
 the K timed steps run as ONE persistent launch (the state stays in LDS between steps).  A launch of few steps is far shorter than
-the clock differences between boxes, so `--repeats` such launches are timed one by one (default: enough of them for about 20 ms of
-kernel time) and the MEDIAN launch is what `value` and `ms_per_step` report (`repeats`, best and worst are in the line).
+the clock differences between boxes, so `--repeats` such launches can be timed one by one and the MEDIAN launch is what `value` and
+`ms_per_step` report (`repeats`, best and worst are in the line).  A plain run times exactly ONE launch of K steps; under `--full`
+the default is enough launches for about 20 ms of kernel time.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+`--full` adds what the headline does not need: the CPU oracle's rate on the same workload (`cpu_baseline`, about 14 s of CPU work,
+N = 1 only; `--no-cpu-baseline` leaves it out) and the repeated launches above.  `--dump-outputs DIR` writes, after the timed
+launches, the state a caller of the timed path reads back (LiDAR scans, poses, controls, race progress, snapshots, metrics record)
+as DIR/<name>.npy in float32 / float64 (DIR/<name>_rank<r>.npy for N > 1); the inputs are seeded, so two builds can be compared
+array for array.
 
 N > 1: one process per GPU.  Launched by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
 --gpus N` (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env), or, when no launcher set WORLD_SIZE, bench.py starts
@@ -135,6 +142,17 @@ def cpu_baseline(track, n_rays, policy, cars, seed, budget_s=14.0, lidar_mode="r
                       + f" -- oracle/ftgp_oracle.c (the CPU restatement, OpenMP over envs); host has {host_cpus} logical CPUs, this process may use {share}"}
 
 
+def dump_outputs(env, out_dir, suffix):
+    """What a caller of the timed path reads back after its last step, as float32 / float64 .npy files (< 64 MB at the headline
+    shape: the scans are 4096 x 1080 float32; the integer race state converts to float64 exactly)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"lidar": env.lidar(), "pose": env.pose(), "ctrl": env.ctrl(), "snapshot": env.snapshot(),
+              "progress": env.progress().astype(np.float64), "race_steps": env.race_steps().astype(np.float64),
+              "winners": env.winners().astype(np.float64), "metrics": env.metrics_local()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def launch_ranks(n, argv, script=None, poll_s=0.2):
     """No launcher set WORLD_SIZE: start the N ranks ourselves (one child per GPU).  Returns 0 only if every rank exits 0; as soon
     as one rank fails the others are stopped (they would wait for it in the rendezvous until their timeout) and its code is
@@ -181,9 +199,14 @@ def main():
     ap.add_argument("--track", default="track")
     ap.add_argument("--policy", default="fast")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=0, help="timed launches of K steps each, timed one by one; the median is reported "
-                                                           "(0 = as many as make about 20 ms of kernel time, at most 31)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed launches of K steps each, timed one by one; the median is reported "
+                                                              "(0 = as many as make about 20 ms of kernel time, at most 31; default: 1, "
+                                                              "or 0 under --full)")
     ap.add_argument("--lidar", default="rangefinder", choices=("rangefinder", "fakelidar"))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed launches, write the state the timed path leaves (DIR/<name>.npy, float32 / float64)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline and "
+                                                        "repeated launches (see the module docstring)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -263,7 +286,7 @@ def main():
         if rdzv is not None:
             rdzv.barrier()
 
-    repeats = args.repeats
+    repeats = args.repeats if args.repeats is not None else (0 if args.full else 1)
     if repeats <= 0:           # a launch of few steps is shorter than anything a wall clock compares across boxes: time several
         repeats = max(1, min(31, int(20.0 / max(args.steps * 0.03 * args.cars, 1e-3) + 0.999)))
         repeats += 1 - repeats % 2                                   # odd: the median is a launch that happened
@@ -368,9 +391,13 @@ def main():
                          "kernel_ms_max": [float(x) for x in per_rank[:, 2]], "wall_ms_median": [float(x) for x in per_rank[:, 3]],
                          "kernel_ms_spread_over_ranks": float(per_rank[:, 0].max() / max(per_rank[:, 0].min(), 1e-12))},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(env, args.dump_outputs, "" if world == 1 else "_rank0")
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(track, args.rays, args.policy, args.cars, seed, lidar_mode=args.lidar)
         print(json.dumps(out), flush=True)
+    elif args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, f"_rank{rank}")
     exchange.close()
     if rdzv_x is not None:
         rdzv_x.close()

@@ -6,7 +6,7 @@ Run once in the build container (needs /root/reference; never runs on the GPU bo
 
 Fixtures (data only -- inputs and the reference's outputs):
   g1_drivers.npz   nidc / fast / lobotomy / drivers.template process_lidar on seeded scans, R in {36, 90, 1080}
-  g2_fakelidar.npz ft_grandprix.raycast.fakelidar on each track's EDT from on-track origins, R in {36, 1080}
+  g2_fakelidar_<track>.npz  ft_grandprix.raycast.fakelidar on each track's EDT from on-track origins, R in {36, 1080}
   g3_chunk.json    ft_grandprix.chunk.chunk() metadata.json for the 4 tracks + SHA-256 of the chunk pixels
   g4_math.npz      custom.quaternion_to_euler / euler_to_quaternion / quaternion_to_angle, VehicleState
                    lap_completion / absolute_completion truth table, ordinal()
@@ -21,6 +21,9 @@ Fixtures (data only -- inputs and the reference's outputs):
                    on scipy's distance transform (recipe of custom.py:1149-1153 / raycast.py:24-27) from car poses mapped to pixels with the
                    expressions of custom.py:1382-1384, fan = the rangefinders' (SURVEY.md 8a-3), ranges scaled as custom.py:1392-1393;
                    plus the SHA-256 of each track's distance transform
+  g9_reference_drivers.npz / .json  the reference's nidc / fast / drivers.template objects driving closed loops through the host
+                   path (ft_grandprix_amd.sim) on the CPU oracle: template/cars/cars.json (the roster itself is stored) for 250 steps,
+                   nidc and fast alone for 300, the template driver for 50 (every value it returned, and its arity)
 
 custom.py imports mujoco / dearpygui / empy / svg.path, which are not installed; they are replaced by
 MagicMock entries in sys.modules for the import only -- none of the functions
@@ -112,8 +115,8 @@ def gen_g2():
     from scipy.ndimage import distance_transform_edt
     from ft_grandprix_amd.track import load_track_from_template
     rng = np.random.default_rng(7)
-    data = {}
     for name in ("track", "circle", "small-circle", "inkscape"):
+        data = {}
         t = load_track_from_template(os.path.join(REF, "template"), name)
         dt = distance_transform_edt(~t.wall_mask())
         # on-track origins: the centre-line samples mapped back to pixels, plus jitter
@@ -133,7 +136,7 @@ def gen_g2():
             data[f"{name}_{R}_scan"] = scan
             data[f"{name}_{R}_points"] = pts
         data[f"{name}_origins"] = np.stack([ox, oy], axis=1)
-    np.savez_compressed(os.path.join(HERE, "g2_fakelidar.npz"), **data)
+        np.savez_compressed(os.path.join(HERE, f"g2_fakelidar_{name}.npz"), **data)       # one file per track: each under 1 MiB
     print("g2: ok")
 
 
@@ -379,9 +382,63 @@ def gen_g8():
     print("g8: ok")
 
 
+# ----------------------------------------------------------------------------- G9
+G9_ROSTER_STEPS, G9_LOOP_STEPS, G9_TEMPLATE_STEPS = 250, 300, 50
+
+
+def gen_g9():
+    """The reference's OWN driver objects in closed loops through the host path (ft_grandprix_amd.sim.Simulator, one process_lidar
+    call per car and step), with the CPU oracle as the world: template/cars/cars.json on `track` (2 envs x 3 cars, 90 rays), nidc /
+    fast alone (3 envs, 90 rays, spawn_mode 1, seed 9), drivers.template on `small-circle`.  The tests drive the device policies
+    (K5, the restatement) on the same worlds and compare."""
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    from helpers import load_oracle
+    from ft_grandprix_amd.sim import Simulator
+    from ft_grandprix_amd.track import load_track
+    oracle = load_oracle()
+    data, meta = {}, {}
+    roster = Simulator.load_roster(os.path.join(REF, "template", "cars", "cars.json"))
+    sim = Simulator(load_track("track"), roster, n_envs=2, n_rays=90, lib=oracle)
+    meta["roster"] = roster
+    meta["roster_modules"] = [type(vs.driver).__module__ for vs in sim.vehicle_states[:3]]
+    with np.errstate(all="ignore"):
+        sim.drive(G9_ROSTER_STEPS)
+    data.update(roster_progress=sim.env.progress(), roster_pose=sim.env.pose(), roster_ctrl=sim.env.ctrl(),
+                roster_laps=np.array([vs.laps for vs in sim.vehicle_states]))
+    sim.close()
+    meta["loop_modules"] = {}
+    for name, policy in (("ft_grandprix.nidc", "nidc"), ("file://ft_grandprix/fast.py", "fast")):
+        sim = Simulator(load_track("track"), [{"driver": name, "name": "ref"}], n_envs=3, n_rays=90, lib=oracle, spawn_mode=1, seed=9)
+        meta["loop_modules"][name] = type(sim.vehicle_states[0].driver).__module__
+        with np.errstate(all="ignore"):
+            sim.drive(G9_LOOP_STEPS)
+        data.update({f"loop_{policy}_progress": sim.env.progress(), f"loop_{policy}_pose": sim.env.pose(),
+                     f"loop_{policy}_lidar": sim.env.lidar()})
+        sim.close()
+    sim = Simulator(load_track("small-circle"), [{"driver": "drivers.template", "name": "t"}], n_envs=1, n_rays=36, lib=oracle)
+    drv = sim.vehicle_states[0].driver
+    meta["template"] = {"v2": sim.vehicle_states[0].v2, "module": type(drv).__module__, "returns": []}
+    call = drv.process_lidar
+    def recording(*args):
+        out = call(*args)
+        meta["template"]["returns"].append([float(x) for x in out])
+        return out
+    drv.process_lidar = recording
+    sim.drive(G9_TEMPLATE_STEPS)
+    data.update(template_ctrl=sim.env.ctrl(), template_steps=sim.env.steps())
+    sim.close()
+    np.savez_compressed(os.path.join(HERE, "g9_reference_drivers.npz"), **data)
+    with open(os.path.join(HERE, "g9_reference_drivers.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+    print("g9: ok")
+
+
 if __name__ == "__main__":
     if "--only-g8" in sys.argv:
         gen_g8()
+        raise SystemExit(0)
+    if "--only-g9" in sys.argv:
+        gen_g9()
         raise SystemExit(0)
     gen_g6()
     gen_g7()

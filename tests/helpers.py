@@ -37,6 +37,11 @@ def golden(name):
     return os.path.join(GOLDEN, name)
 
 
+def g2_fakelidar(track):
+    """Fixture G2 of one track (stored one file per track: <track>_origins, <track>_<R>_angles / _scan / _points)."""
+    return np.load(golden(f"g2_fakelidar_{track}.npz"))
+
+
 def oracle_policy(lib, policy, scan_f32, last_steer=0.0):
     import ctypes as C
     s = np.ascontiguousarray(scan_f32, dtype=np.float32)
@@ -101,7 +106,7 @@ def k2_minus_fakelidar_square_pixels(lib, name, R):
     K2 ray j of a car with world yaw psi has -(psi + pi + 2 pi j / R) (mushr.em.xml:112-117, y up): the same ray for psi = -yaw_g."""
     import dataclasses
     from ft_grandprix_amd.track import load_track
-    g = np.load(golden("g2_fakelidar.npz"))
+    g = g2_fakelidar(name)
     t = load_track(name)
     s = 40.0 / t.width
     sq = dataclasses.replace(t, px_size_x=s, px_size_y=s)
@@ -119,7 +124,7 @@ def k2_minus_fakelidar_along_k2_rays(lib, name, R, seed=11):
     from scipy.ndimage import distance_transform_edt
     from ft_grandprix_amd import capi
     from ft_grandprix_amd.track import load_track
-    g = np.load(golden("g2_fakelidar.npz"))
+    g = g2_fakelidar(name)
     t = load_track(name)
     origins = g[f"{name}_origins"]
     yaw = np.random.default_rng(seed).uniform(-np.pi, np.pi, len(origins))

@@ -18,7 +18,7 @@ import pytest
 
 from ft_grandprix_amd import capi
 from ft_grandprix_amd.track import load_track
-from tests.helpers import golden
+from tests.helpers import g2_fakelidar, golden
 
 TRACKS = ["track", "circle", "small-circle", "inkscape"]
 MAP = 40.0            # 20 * scale, custom.py:1155,1382
@@ -71,7 +71,7 @@ def preimage(target, scale, size):
 def check_g2_through_step(lib, name, n_origins=8):
     """G2 ray k has the image-frame direction (cos a_k, sin a_k).  With the car at yaw 0 the mode's direction is (bx, -by) of the
     fan entry, so fan = (cos a, -sin a) reproduces it exactly (negation is exact; 1 * b - 0 * b' == b)."""
-    g = np.load(golden("g2_fakelidar.npz"))
+    g = g2_fakelidar(name)
     t = load_track(name)
     origins = g[f"{name}_origins"][:n_origins]
     exact = 0

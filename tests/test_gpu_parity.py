@@ -9,7 +9,7 @@ import pytest
 
 from ft_grandprix_amd import capi
 from ft_grandprix_amd.track import load_track
-from tests.helpers import golden
+from tests.helpers import g2_fakelidar, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -647,12 +647,12 @@ def test_metrics_exchange_in_two_halves_beside_the_next_launch(product, with_com
 
 
 def test_bench_repeats_median_and_overlap_fields(product):
-    """The bench line of a short launch: several launches timed one by one, the median reported, `repeats` in the line, the
-    roofline's `bound` derived from the committed counters with both fractions side by side."""
+    """The bench line of a short launch under --full: several launches timed one by one, the median reported, `repeats` in the line,
+    the roofline's `bound` derived from the committed counters with both fractions side by side."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -673,11 +673,40 @@ def test_bench_repeats_median_and_overlap_fields(product):
     assert d["metrics_allgather"]["sum_steps"] == 4096 * (5 + 20 * d["repeats"])       # the record collected last is the last launch's
 
 
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_what_they_computed(product, tmp_path):
+    """A plain bench run: ONE launch of exactly --steps steps, no CPU baseline; --dump-outputs writes the state after the last timed
+    step as float32 / float64 arrays, the same from run to run (seeded inputs) and equal to a rollout of warmup + steps steps."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "7", "--warmup", "3", "--envs-per-gpu", "256",
+                            "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["repeats"] == 1 and d["steps"] == 7 and "cpu_baseline" not in d and d["ms_per_step"] > 0
+        assert d["metrics_allgather"]["sum_steps"] == 256 * (3 + 7)
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert {"lidar", "pose", "ctrl", "progress"} <= set(a) and a.keys() == b.keys()
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    with capi.Env(product, load_track("track"), n_envs=256, n_rays=1080, spawn_mode=1, seed=1234) as e:
+        e.rollout("fast", 3); e.rollout("fast", 7)
+        np.testing.assert_array_equal(a["lidar"], e.lidar())
+        np.testing.assert_array_equal(a["pose"], e.pose())
+        np.testing.assert_array_equal(a["progress"], e.progress())
+
+
 @pytest.mark.parametrize("name", ["track", "circle", "small-circle", "inkscape"])
 def test_g2_fakelidar_on_gpu_bit_exact(product, name):
     """Row a3: the fakelidar-compat kernel against the outputs of the reference's own raycast.fakelidar (fixture G2)."""
     from scipy.ndimage import distance_transform_edt
-    gld = np.load(golden("g2_fakelidar.npz"))
+    gld = g2_fakelidar(name)
     t = load_track(name)
     dt = distance_transform_edt(~t.wall_mask())
     origins = gld[f"{name}_origins"]

@@ -41,8 +41,8 @@ def test_the_comparison_is_sensitive_to_ray_order_and_orientation(oracle):
     """The same K2 sweep against the goldens taken the other way round, a quarter turn off, or just one degree (3 rays) off:
     the every-ray bound fails by tens to hundreds of pixels, i.e. the test above does pin index 0, the sense of rotation and
     the frame."""
-    from tests.helpers import golden
-    scan = np.load(golden("g2_fakelidar.npz"))["track_1080_scan"]
+    from tests.helpers import g2_fakelidar
+    scan = g2_fakelidar("track")["track_1080_scan"]
     k2_px = k2_minus_fakelidar_square_pixels(oracle, "track", 1080) + scan
     for wrong, gross in ((scan[:, ::-1], True), (np.roll(scan, 270, axis=1), True), (np.roll(scan, 3, axis=1), False), (np.roll(scan, -3, axis=1), False)):
         e = k2_px - wrong

@@ -2,7 +2,6 @@
 reference builds one Driver() per roster entry and calls them one by one (custom.py:1097-1104,1398-1411; template/cars/cars.json is
 nidc, fast, nidc).  Pins: the drivers themselves are pinned by G1 (reference-run controls); here the DISPATCH is checked -- per-car
 launches against single-driver launches, host Python drivers against the device, GPU against oracle."""
-import os
 import sys
 
 import numpy as np
@@ -54,33 +53,27 @@ def test_per_car_needs_a_roster_and_bundled_drivers(oracle):
         assert (ctrl[0::2] == 0).all() and (ctrl[1::2, 0] > 0).all()
 
 
-REF = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_reference_roster_with_its_own_drivers_against_one_device_rollout(oracle):
     """template/cars/cars.json -- nidc, fast, nidc -- driven by the reference's OWN driver objects, one per car, step by step
-    (sim.Simulator, the host path) against ONE rollout("roster"): the closed loops stay together (the Python drivers see binary64
-    copies of the binary32 scans; the restated K5 agrees to rounding, as in test_unmodified_reference_drivers_close_the_loop)."""
+    (sim.Simulator, the host path; recorded in fixture G9) against ONE rollout("roster"): the closed loops stay together (the Python
+    drivers saw binary64 copies of the binary32 scans; the restated K5 agrees to rounding, as in
+    test_unmodified_reference_drivers_close_the_loop)."""
+    import json
     from ft_grandprix_amd.sim import Simulator
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    roster = Simulator.load_roster(os.path.join(REF, "template", "cars", "cars.json"))
-    t = load_track("track")
-    host = Simulator(t, roster, n_envs=2, n_rays=90, lib=oracle)
-    dev = Simulator(t, roster, n_envs=2, n_rays=90, lib=oracle)
+    from tests.helpers import golden
+    meta = json.load(open(golden("g9_reference_drivers.json")))
+    host = np.load(golden("g9_reference_drivers.npz"))
+    assert meta["roster_modules"] == ["ft_grandprix.nidc", "ft_grandprix.fast", "ft_grandprix.nidc"]
+    dev = Simulator(load_track("track"), meta["roster"], n_envs=2, n_rays=90, lib=oracle)
     try:
-        assert host.roster_policies() == ROSTER
-        assert [type(vs.driver).__module__ for vs in host.vehicle_states[:3]] == ["ft_grandprix.nidc", "ft_grandprix.fast", "ft_grandprix.nidc"]
-        with np.errstate(all="ignore"):
-            host.drive(250)
+        assert dev.roster_policies() == ROSTER
         dev.rollout("roster", 250)
-        np.testing.assert_array_equal(host.env.progress(), dev.env.progress())
-        np.testing.assert_allclose(host.env.pose(), dev.env.pose(), rtol=0, atol=1e-6)
-        np.testing.assert_allclose(host.env.ctrl(), dev.env.ctrl(), rtol=0, atol=1e-6)
-        assert [vs.laps for vs in host.vehicle_states] == [vs.laps for vs in dev.vehicle_states]
+        np.testing.assert_array_equal(host["roster_progress"], dev.env.progress())
+        np.testing.assert_allclose(host["roster_pose"], dev.env.pose(), rtol=0, atol=1e-6)
+        np.testing.assert_allclose(host["roster_ctrl"], dev.env.ctrl(), rtol=0, atol=1e-6)
+        assert list(host["roster_laps"]) == [vs.laps for vs in dev.vehicle_states]
     finally:
-        host.close(); dev.close()
+        dev.close()
 
 
 def test_roster_of_python_only_drivers_is_not_taken_to_the_device(oracle):

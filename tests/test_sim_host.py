@@ -1,10 +1,9 @@
 """Host-side driver surface (ft_grandprix_amd.sim) on CPU, with the oracle standing in for the device library.
 
-When the reference checkout is present (/root/reference, never on the GPU box) its OWN nidc / fast / template
-drivers are loaded unmodified through roster strings and driven for a few hundred steps; the closed-loop result must
-agree with the oracle's restated drivers (K5) run on the same worlds."""
+The reference's OWN nidc / fast / template drivers, loaded unmodified through roster strings and driven for a few hundred steps,
+are recorded in fixture G9 (tests/golden/make_golden.py); the closed-loop result must agree with the oracle's restated drivers
+(K5) run on the same worlds."""
 import json
-import os
 import sys
 
 import numpy as np
@@ -13,9 +12,12 @@ import pytest
 from ft_grandprix_amd import capi
 from ft_grandprix_amd.sim import Simulator, LobotomyDriver, resolve_driver_path, VehicleStateSnapshot
 from ft_grandprix_amd.track import load_track
+from tests.helpers import golden
 
-REF = "/root/reference"
-have_ref = os.path.isdir(os.path.join(REF, "ft_grandprix"))
+
+def g9():
+    """Fixture G9: the reference's own drivers in closed loops on the host path (tests/golden/make_golden.py)."""
+    return json.load(open(golden("g9_reference_drivers.json"))), np.load(golden("g9_reference_drivers.npz"))
 
 
 def test_roster_path_resolution_matches_reference_rules():
@@ -46,34 +48,41 @@ def test_import_failure_falls_back_to_null_driver_and_arity_is_sniffed(oracle):
     sim.close()
 
 
-@pytest.mark.skipif(not have_ref, reason="reference checkout not present")
 @pytest.mark.parametrize("name,policy", [("ft_grandprix.nidc", "nidc"), ("file://ft_grandprix/fast.py", "fast")])
 def test_unmodified_reference_drivers_close_the_loop(oracle, name, policy):
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
+    """The reference's own driver, named by roster string, drove the host path for 300 steps (fixture G9); the oracle's restated
+    driver drives the same world in one rollout."""
+    meta, ref = g9()
+    assert meta["loop_modules"][name] == resolve_driver_path(name) == "ft_grandprix." + policy
     t = load_track("track")
-    cars = [{"driver": name, "name": "ref"}]
-    sim = Simulator(t, cars, n_envs=3, n_rays=90, lib=oracle, spawn_mode=1, seed=9)
-    assert type(sim.vehicle_states[0].driver).__module__.startswith("ft_grandprix.")
     with capi.Env(oracle, t, n_envs=3, n_rays=90, spawn_mode=1, seed=9) as dev:
-        with np.errstate(all="ignore"):
-            sim.drive(300)
         dev.rollout(policy, 300)
-        # the Python drivers see float64 copies of the f32 scan; the restated K5 agrees to rounding, so the closed loops stay together
-        np.testing.assert_array_equal(sim.env.progress(), dev.progress())
-        np.testing.assert_allclose(sim.env.pose(), dev.pose(), rtol=0, atol=1e-6)
-        np.testing.assert_allclose(sim.env.lidar(), dev.lidar(), rtol=0, atol=1e-4)
-    sim.close()
+        # the Python drivers saw float64 copies of the f32 scan; the restated K5 agrees to rounding, so the closed loops stay together
+        np.testing.assert_array_equal(ref[f"loop_{policy}_progress"], dev.progress())
+        np.testing.assert_allclose(ref[f"loop_{policy}_pose"], dev.pose(), rtol=0, atol=1e-6)
+        np.testing.assert_allclose(ref[f"loop_{policy}_lidar"], dev.lidar(), rtol=0, atol=1e-4)
 
 
-@pytest.mark.skipif(not have_ref, reason="reference checkout not present")
 def test_reference_template_driver_runs_unmodified(oracle):
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    sim = Simulator(load_track("small-circle"), [{"driver": "drivers.template", "name": "t"}], n_envs=1, n_rays=36, lib=oracle)
+    """drivers.template (process_lidar(ranges, state), fixture G9: its arity and every value it returned) through the host path: a
+    driver of that signature returning those values is called with the snapshot and its controls reach the car."""
+    import types
+    meta, ref = g9()
+    rec = meta["template"]
+    assert rec["module"] == "drivers.template" and rec["v2"] and len(rec["returns"]) == 50
+    returns = iter(rec["returns"])
+
+    class Template:
+        def process_lidar(self, ranges, state):
+            assert isinstance(state, VehicleStateSnapshot)
+            return tuple(next(returns))
+    m = types.ModuleType("ftgp_g9_template"); m.Driver = Template; sys.modules["ftgp_g9_template"] = m
+    sim = Simulator(load_track("small-circle"), [{"driver": "ftgp_g9_template", "name": "t"}], n_envs=1, n_rays=36, lib=oracle)
     assert sim.vehicle_states[0].v2
     sim.drive(50)
+    np.testing.assert_array_equal(sim.env.ctrl(), ref["template_ctrl"])
     np.testing.assert_array_equal(sim.env.ctrl(), 0.0)
+    np.testing.assert_array_equal(sim.env.steps(), ref["template_steps"])
     np.testing.assert_array_equal(sim.env.steps(), [50])
     sim.close()
 

@@ -2,7 +2,7 @@
 """One GPU-box visit that produces the judged evidence for a build (run it through gpurun, then copy gpurun_out/profile/* to
 profiles/roundN/):   python3 tools/collect_profile.py [steps] [envs] [policy] [cars] [track] [tag]   (default: the headline; a tag
 other than "latest" names the files sq_<tag>.json, ... and leaves the files bench.py reads alone)
-  bench.json                       python bench.py (the driver's line, with cpu_baseline)
+  bench.json                       python bench.py --full (the driver's line, with cpu_baseline)
   kernel_stats.csv                 rocprofv3 --kernel-trace --stats of the same bench command (average duration per kernel)
   sq_latest.json                   SQ counters of the step kernel, three --pmc passes (own runs, kernel-trace only)
   traffic_latest.json              FETCH_SIZE / WRITE_SIZE of the step kernel, separate --pmc passes (guide: KB; FETCH x2 on gfx950)
@@ -107,13 +107,13 @@ for name in (f"sq_{TAG}.json", f"traffic_{TAG}.json"):
 # 4. the bench line + kernel stats of the same command
 cfg = ["--envs-per-gpu", str(ENVS), "--policy", POLICY, "--cars", str(CARS), "--track", TRACK]
 SUFFIX = "" if TAG == "latest" else "_" + TAG
-run(["python3", "bench.py", "--steps", str(STEPS), "--warmup", "50", *cfg] + ([] if TAG == "latest" else ["--no-cpu-baseline"]), f"{OUT}/bench{SUFFIX}.log", 600)
+run(["python3", "bench.py", "--full", "--steps", str(STEPS), "--warmup", "50", *cfg] + ([] if TAG == "latest" else ["--no-cpu-baseline"]), f"{OUT}/bench{SUFFIX}.log", 600)
 line = [l for l in open(f"{OUT}/bench{SUFFIX}.log").read().splitlines() if l.startswith("{")][-1]
 open(f"{OUT}/bench{SUFFIX}.json", "w").write(line + "\n")
 open(f"{OUT}/bench{SUFFIX}.json.sha", "w").write(sha() + "\n")
 shutil.rmtree(f"{OUT}/raw_stats", ignore_errors=True)
 run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", f"{OUT}/raw_stats", "--",
-     "python3", "bench.py", "--steps", str(STEPS), "--warmup", "50", "--no-cpu-baseline", *cfg], f"{OUT}/raw_stats.log", 600)
+     "python3", "bench.py", "--full", "--steps", str(STEPS), "--warmup", "50", "--no-cpu-baseline", *cfg], f"{OUT}/raw_stats.log", 600)
 shutil.copy(glob.glob(f"{OUT}/raw_stats/**/*kernel_stats.csv", recursive=True)[0], f"{OUT}/kernel_stats{SUFFIX}.csv")
 open(f"{OUT}/kernel_stats{SUFFIX}.csv.sha", "w").write(sha() + "\n")
 

@@ -5,11 +5,12 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out; export TMPDIR=/tmp
 tag=${1:-now}; out=gpurun_out/fakelidar_$tag.log
+dir=${out%/*}; pre=${out%.log}
 export FTGP_PROF_LIDAR=fakelidar
 STEPS=${FAKE_STEPS:-100}
 echo "# kernel_source_sha=$(python3 tools/evidence.py sha) $(date '+%Y-%m-%d %H:%M:%S') fakelidar_evidence $tag: 4096 envs x 1080 rays, track, fast, FAKELIDAR mode" > $out
-timeout -k 10 300 python3 bench.py --lidar fakelidar --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/fakelidar_${tag}_bench20.json 2>> $out || { echo "bench20 failed" >> $out; tail -5 $out; exit 1; }
-timeout -k 10 300 python3 bench.py --lidar fakelidar --steps $STEPS --warmup 20 > gpurun_out/fakelidar_${tag}_bench.json 2>> $out || { echo "bench failed" >> $out; tail -5 $out; exit 1; }
+timeout -k 10 300 python3 bench.py --full --lidar fakelidar --steps 20 --warmup 5 --no-cpu-baseline > ${pre}_bench20.json 2>> $out || { echo "bench20 failed" >> $out; tail -5 $out; exit 1; }
+timeout -k 10 300 python3 bench.py --full --lidar fakelidar --steps $STEPS --warmup 20 > ${pre}_bench.json 2>> $out || { echo "bench failed" >> $out; tail -5 $out; exit 1; }
 python3 - $tag >> $out <<'PY'
 import json, sys
 for f in ("bench20", "bench"):
@@ -18,7 +19,7 @@ for f in ("bench20", "bench"):
     print(f"{f}: {j['value']:.4g} env-steps/s, {j['ms_per_step'] * 1e3:.2f} us/step wall, kernel {r['kernel_ms_per_launch'] * 1e3 / j['steps']:.2f} us/step, frac {r['frac']:.4f}, {r['kernel'][:60]}")
 PY
 rm -rf gpurun_out/fk_stats
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/fk_stats -- python3 bench.py --lidar fakelidar --steps $STEPS --warmup 20 --no-cpu-baseline > gpurun_out/fk_stats.log 2>&1 || { tail -5 gpurun_out/fk_stats.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $dir/fk_stats -- python3 bench.py --full --lidar fakelidar --steps $STEPS --warmup 20 --no-cpu-baseline > $dir/fk_stats.log 2>&1 || { tail -5 $dir/fk_stats.log; exit 1; }
 cp $(find gpurun_out/fk_stats -name '*kernel_stats.csv' | head -1) gpurun_out/fakelidar_${tag}_kernel_stats.csv
 echo "kernel stats (rocprofv3 --kernel-trace --stats of the $STEPS-step bench command):" >> $out; head -4 gpurun_out/fakelidar_${tag}_kernel_stats.csv >> $out
 CASE="4096 1080 fast $STEPS"

@@ -28,7 +28,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = soak ]; then
     tail -18 gpurun_out/soak.log
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-    run bench20 500 python bench.py --steps 20 --warmup 5
+    run bench20 500 python bench.py --full --steps 20 --warmup 5
     tail -1 gpurun_out/bench20.log | cut -c1-400
 fi
 exit 0
