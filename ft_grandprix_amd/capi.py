@@ -76,7 +76,17 @@ API_SYMBOLS = (
     "get_steps", "set_pose", "policy_eval", "eval_progress", "metrics_local", "comm_unique_id", "comm_init", "metrics_allgather",
     "metrics_allgather_begin", "metrics_allgather_end", "get_distance_field",
     "last_kernel_ms", "kernel_name", "fakelidar", "selftest", "build_info", "get_race_steps",
+    "device_io_config", "step_device",
 )
+
+
+class FtgpDeviceIoConfig(C.Structure):
+    _fields_ = [("roster", C.c_void_p), ("max_episode_steps", C.c_int64), ("action_repeat", C.c_int32), ("auto_reset", C.c_int32)]
+
+
+class FtgpDeviceStep(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("action", C.c_void_p), ("obs", C.c_void_p), ("reward", C.c_void_p),
+                ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("final_obs", C.c_void_p)]
 
 
 class FtgpError(RuntimeError):
@@ -145,6 +155,8 @@ class CLib:
             "kernel_name": (C.c_char_p, [vp]),
             "selftest": (i32, [i32, C.POINTER(C.c_int64)]),
             "build_info": (C.c_char_p, []),
+            "device_io_config": (i32, [vp, C.POINTER(FtgpDeviceIoConfig)]),
+            "step_device": (i32, [vp, C.POINTER(FtgpDeviceStep)]),
         }
         for name, (res, args) in sigs.items():
             if name == "fakelidar" and self.prefix != "ftgp_":
@@ -275,6 +287,26 @@ class Env:
         if p.shape != (self.cars_per_env,):
             raise ValueError(f"one policy per car of an env: expected {self.cars_per_env}, got {p.shape}")
         self._call("set_car_policies", _ptr(p))
+
+    # -- device I/O (include/ftgp.h: ftgp_device_io_config / ftgp_step_device); ft_grandprix_amd.vec wraps it on torch tensors
+    def device_io_config(self, roster=None, max_episode_steps: int = 0, action_repeat: int = 1, auto_reset: bool = True):
+        """roster: one entry per car slot ("host"/"agent" = external, or a bundled driver), None = every slot external."""
+        cfg = FtgpDeviceIoConfig()
+        r = None
+        if roster is not None:
+            r = np.array([POLICY_HOST if x == "agent" else POLICY_BY_NAME[x] if isinstance(x, str) else int(x) for x in roster],
+                         dtype=np.int32)
+            if r.shape != (self.cars_per_env,):
+                raise ValueError(f"one roster entry per car of an env: expected {self.cars_per_env}, got {r.shape}")
+            cfg.roster = r.ctypes.data
+        cfg.max_episode_steps, cfg.action_repeat, cfg.auto_reset = int(max_episode_steps), int(action_repeat), int(bool(auto_reset))
+        self._call("device_io_config", C.byref(cfg))
+
+    def step_device(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0):
+        """One ftgp_step_device call on integer device addresses (and an integer hipStream_t, 0 = the null stream); only enqueues."""
+        io = FtgpDeviceStep(stream or None, action or None, obs or None, reward or None, terminated or None, truncated or None,
+                            final_obs or None)
+        self._call("step_device", C.byref(io))
 
     # -- read-backs
     def lidar(self) -> np.ndarray:

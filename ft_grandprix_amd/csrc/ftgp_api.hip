@@ -103,6 +103,17 @@ struct FtgpEnv {
     std::vector<int32_t> h_prog; std::vector<double> h_core;
     bool rows_valid = false;          // h_prog / h_core mirror the device state (cleared by every call that changes it)
     bool multi = false;
+    // device I/O (ftgp_device_io_config / ftgp_step_device)
+    bool io_ready = false;
+    DeviceIoArgs io{};                // the episode rules and the slot table; the buffers are filled in per call
+    int io_repeat = 1;
+    int32_t* h_tables = nullptr;      // pinned [2][FTGP_MAX_CARS_PER_BLOCK]: the user's roster (mirror of P.car_policy), the device-io slot table
+    int table_on_device = 0;          // which of the two the params block holds (-1: neither); only a FTGP_POLICY_PER_CAR launch reads it
+    int32_t* d_prev_abs = nullptr;
+    hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
+    struct Checked { const void* p; size_t bytes; };
+    Checked io_checked[32] = {};      // device buffers found valid (hipPointerGetAttributes), replaced round robin
+    int io_checked_next = 0;
     // comm
     void* comm = nullptr; int rank = 0, world = 1;
 };
@@ -252,16 +263,31 @@ void collect_slot(const FtgpEnv* e, int slot, double* out)
     memcpy(out, v, sizeof v);
 }
 
-int launch_steps(FtgpEnv* e, int policy, int n_steps)
+// The params block holds the slot table of the next FTGP_POLICY_PER_CAR launch: 0 = the user's roster, 1 = the device-io table.  A
+// stream-ordered copy from pinned memory when it is the other one.
+int use_table(FtgpEnv* e, int which)
+{
+    if (e->table_on_device == which) return 0;
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(e->d_params) + offsetof(DeviceParams, car_policy), e->h_tables + which * FTGP_MAX_CARS_PER_BLOCK,
+                           sizeof e->P.car_policy, hipMemcpyHostToDevice, e->stream));
+    e->table_on_device = which;
+    return 0;
+}
+
+// device_io: the launch of ftgp_step_device (the device-io slot table; checked by ftgp_device_io_config)
+int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
 {
     e->rows_valid = false;
     if (n_steps < 0) return fail(FTGP_ERR_ARG, "n_steps < 0%s");
-    if (policy == FTGP_POLICY_PER_CAR && !e->P.car_policy[0]) return fail(FTGP_ERR_STATE, "FTGP_POLICY_PER_CAR without ftgp_set_car_policies%s");
-    if (uses_disparity_driver(e, policy)) {
-        if (e->P.n_rays < 8) return fail(FTGP_ERR_ARG, "nidc/fast need n_rays >= 8 (they drop len/8 rays from each end)%s");
-        if (e->P.n_rays - 2 * e->P.eighth > FTGP_WAVE * FTGP_WAVE) return fail(FTGP_ERR_ARG, "the device drivers handle at most 4096 samples in the front window%s");
+    if (!device_io) {
+        if (policy == FTGP_POLICY_PER_CAR && !e->P.car_policy[0]) return fail(FTGP_ERR_STATE, "FTGP_POLICY_PER_CAR without ftgp_set_car_policies%s");
+        if (uses_disparity_driver(e, policy)) {
+            if (e->P.n_rays < 8) return fail(FTGP_ERR_ARG, "nidc/fast need n_rays >= 8 (they drop len/8 rays from each end)%s");
+            if (e->P.n_rays - 2 * e->P.eighth > FTGP_WAVE * FTGP_WAVE) return fail(FTGP_ERR_ARG, "the device drivers handle at most 4096 samples in the front window%s");
+        }
     }
     HIP_TRY(hipSetDevice(e->device));
+    if (policy == FTGP_POLICY_PER_CAR && n_steps > 0 && e->h_tables) if (int rc = use_table(e, device_io ? 1 : 0)) return rc;
     const int cpb = e->P.cars_per_block;
     const int blocks = (e->P.n_cars + cpb - 1) / cpb;
     const int slot = e->cur_slot ^ 1;
@@ -316,6 +342,30 @@ int sync_rows_to_host(FtgpEnv* e)
     HIP_TRY(hipMemcpyAsync(e->h_core.data(), e->d_core, sizeof(double) * e->h_core.size(), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->rows_valid = true;
+    return 0;
+}
+
+// A buffer of ftgp_step_device: `bytes` of device memory on the handle's device from p on (hipPointerGetAttributes, and the extent of the
+// allocation from hipMemGetAddressRange).  Buffers found valid are remembered, so that the steady state asks the runtime nothing.
+int check_device_buffer(FtgpEnv* e, const void* p, size_t bytes, const char* name)
+{
+    if (!p) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is NULL", name);
+    for (const FtgpEnv::Checked& c : e->io_checked) if (c.p == p && c.bytes >= bytes) return 0;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is not device memory", name);
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != e->device) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is not device memory on the handle's device", name);
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FTGP_ERR_ARG, "ftgp_step_device: the allocation of %s is unknown to the runtime", name);
+    }
+    const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
+    if (q < b || q - b + bytes > size) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is smaller than the layout needs", name);
+    e->io_checked[e->io_checked_next] = { p, bytes };
+    e->io_checked_next = (e->io_checked_next + 1) % (int)(sizeof e->io_checked / sizeof e->io_checked[0]);
     return 0;
 }
 
@@ -406,6 +456,10 @@ int ftgp_destroy(FtgpEnv* e)
     if (e->h_metrics) (void)hipHostFree(e->h_metrics);
     if (e->h_gather) (void)hipHostFree(e->h_gather);
     if (e->h_wg_metrics) (void)hipHostFree(e->h_wg_metrics);
+    if (e->h_tables) (void)hipHostFree(e->h_tables);
+    if (e->d_prev_abs) (void)hipFree(e->d_prev_abs);
+    if (e->ev_io_in) (void)hipEventDestroy(e->ev_io_in);
+    if (e->ev_io_out) (void)hipEventDestroy(e->ev_io_out);
     if (e->ev_gather) (void)hipEventDestroy(e->ev_gather);
     if (e->ev_start) (void)hipEventDestroy(e->ev_start);
     for (hipEvent_t ev : e->ev_stop) if (ev) (void)hipEventDestroy(ev);
@@ -844,6 +898,78 @@ int ftgp_set_car_policies(FtgpEnv* e, const int32_t* policies)
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));           // no launch is reading the block while it changes
     HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(e->d_params) + offsetof(DeviceParams, car_policy), e->P.car_policy, sizeof e->P.car_policy, hipMemcpyHostToDevice));
+    if (e->h_tables) memcpy(e->h_tables, e->P.car_policy, sizeof e->P.car_policy);    // (no copy from it is pending: the stream is idle)
+    e->table_on_device = 0;
+    return 0;
+}
+
+int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
+{
+    if (!e || !cfg) return fail(FTGP_ERR_ARG, "null argument%s");
+    if (cfg->action_repeat < 1) return fail(FTGP_ERR_ARG, "device_io_config: action_repeat >= 1%s");
+    const int cpe = e->P.cars_per_env;
+    int32_t slot[FTGP_PAIR_STRIDE];
+    int n_ext = 0; bool disparity = false;
+    for (int k = 0; k < cpe; ++k) {
+        slot[k] = cfg->roster ? cfg->roster[k] : FTGP_POLICY_HOST;
+        if (slot[k] < FTGP_POLICY_HOST || slot[k] > FTGP_POLICY_RANDOM) return fail(FTGP_ERR_ARG, "device_io_config: host / lobotomy / nidc / fast / random only%s");
+        n_ext += slot[k] == FTGP_POLICY_HOST;
+        disparity = disparity || slot[k] == FTGP_POLICY_NIDC || slot[k] == FTGP_POLICY_FAST;
+    }
+    if (n_ext == 0) return fail(FTGP_ERR_ARG, "device_io_config: at least one slot must be external (FTGP_POLICY_HOST)%s");
+    if (disparity && e->P.n_rays < 8) return fail(FTGP_ERR_ARG, "nidc/fast need n_rays >= 8%s");
+    if (disparity && e->P.n_rays - 2 * e->P.eighth > FTGP_WAVE * FTGP_WAVE) return fail(FTGP_ERR_ARG, "the device drivers handle at most 4096 samples in the front window%s");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));           // no copy from the pinned tables is pending while they change
+    if (!e->h_tables) {
+        HIP_TRY(hipHostMalloc(&e->h_tables, sizeof(int32_t) * 2 * FTGP_MAX_CARS_PER_BLOCK, hipHostMallocDefault));
+        memcpy(e->h_tables, e->P.car_policy, sizeof e->P.car_policy);
+        e->table_on_device = 0;
+    }
+    if (!e->d_prev_abs) HIP_TRY(hipMalloc(&e->d_prev_abs, sizeof(int32_t) * (size_t)e->P.n_cars));
+    if (!e->ev_io_in) HIP_TRY(hipEventCreateWithFlags(&e->ev_io_in, hipEventDisableTiming));
+    if (!e->ev_io_out) HIP_TRY(hipEventCreateWithFlags(&e->ev_io_out, hipEventDisableTiming));
+    // a workgroup holds whole envs, so its car slot c runs entry c % cars_per_env (as ftgp_set_car_policies)
+    for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->h_tables[FTGP_MAX_CARS_PER_BLOCK + c] = slot[c % cpe];
+    if (e->table_on_device == 1) e->table_on_device = -1;
+    DeviceIoArgs& A = e->io;
+    A = DeviceIoArgs{};
+    A.max_episode_steps = cfg->max_episode_steps; A.n_ext = n_ext; A.auto_reset = cfg->auto_reset ? 1 : 0;
+    for (int k = 0, i = 0; k < FTGP_PAIR_STRIDE; ++k) A.ext_index[k] = (k < cpe && slot[k] == FTGP_POLICY_HOST) ? i++ : -1;
+    A.prev_abs = e->d_prev_abs;
+    e->io_repeat = cfg->action_repeat;
+    e->io_ready = true;
+    return 0;
+}
+
+int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io)
+{
+    if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
+    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
+    HIP_TRY(hipSetDevice(e->device));
+    DeviceIoArgs A = e->io;
+    const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)e->P.n_rays;
+    if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
+    if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
+    if (int rc = check_device_buffer(e, io->reward, sizeof(float) * rows, "reward")) return rc;
+    if (int rc = check_device_buffer(e, io->terminated, n_envs, "terminated")) return rc;
+    if (int rc = check_device_buffer(e, io->truncated, n_envs, "truncated")) return rc;
+    if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
+    A.action = io->action; A.obs = io->obs; A.reward = io->reward; A.terminated = io->terminated; A.truncated = io->truncated; A.final_obs = io->final_obs;
+    A.vec4 = e->P.n_rays % 4 == 0 && (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
+    hipStream_t caller = (hipStream_t)io->stream;
+    HIP_TRY(hipEventRecord(e->ev_io_in, caller));
+    HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_io_in, 0));
+    const unsigned car_blocks = (unsigned)((e->P.n_cars + 255) / 256);
+    hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream, e->P, A);
+    HIP_TRY(hipGetLastError());
+    if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, e->io_repeat, true)) return rc;
+    hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream, e->P, A);
+    HIP_TRY(hipGetLastError());
+    e->rows_valid = false;
+    if (A.auto_reset) e->launch_metrics_valid = false;     // the launch's record describes the state before the resets
+    HIP_TRY(hipEventRecord(e->ev_io_out, e->stream));
+    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out, 0));
     return 0;
 }
 

@@ -1774,12 +1774,11 @@ __device__ __forceinline__ void progress_lane(const DeviceParams& P, CarCore& s,
     race_store(r, &s);
 }
 
-__global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ env_mask)
+// car ci back at its spawn pose with a cleared race state; car 0 of the env also zeroes the env's steps (ftgp_reset_kernel,
+// ftgp_io_finish_kernel)
+__device__ __forceinline__ void reset_car(const DeviceParams& P, int ci)
 {
-    const int ci = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ci >= P.n_cars) return;
     const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
-    if (env_mask && !env_mask[env]) return;
     CarCore s;
     memset(&s, 0, sizeof s);
     const int p = (P.spawn_mode == 0) ? (car + 5) * 2 : (int)((10 + 7 * (long)(P.env_base + env) + 2 * car) % 98);   // custom.py:1112
@@ -1800,6 +1799,14 @@ __global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ en
     for (int k = 0; k < FTGP_MAX_LAP_TIMES; ++k) P.cars[ci].times[k] = 0.0;
     progress_lane(P, s, 0, P.cars[ci].times);
     static_cast<CarCore&>(P.cars[ci]) = s;
+}
+
+__global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ env_mask)
+{
+    const int ci = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ci >= P.n_cars) return;
+    if (env_mask && !env_mask[ci / P.cars_per_env]) return;
+    reset_car(P, ci);
 }
 
 // sensordata = 0 after mj_resetData (custom.py:1092): coalesced zero fill of the reset envs' scans
@@ -1837,6 +1844,97 @@ __global__ void ftgp_set_pose_kernel(DeviceParams P, const double* __restrict__ 
     const double n = sqrt(o[3] * o[3] + o[6] * o[6]);
     CarState& s = P.cars[ci];
     s.x = o[0]; s.y = o[1]; s.qw = o[3] / n; s.qz = o[6] / n; s.vx = o[7]; s.vy = o[8]; s.wz = o[12];
+}
+
+// =============================================================================================
+// Device I/O (ftgp_step_device): the caller's actions in, observations / rewards / episode ends out, all in device memory.
+// A call is: ftgp_io_ingest_kernel -> ftgp_step_kernel<.., ROSTER> (action_repeat steps) -> ftgp_io_finish_kernel.
+// =============================================================================================
+struct DeviceIoArgs {
+    const float* action;          // [n_envs][n_ext][2] (speed, steering_angle)
+    float* obs;                   // [n_envs][n_ext][n_rays]
+    float* reward;                // [n_envs][n_ext]
+    uint8_t* terminated;          // [n_envs]
+    uint8_t* truncated;           // [n_envs]
+    float* final_obs;             // [n_envs][n_ext][n_rays] or null
+    int32_t* prev_abs;            // [n_cars] absolute_completion before the call's steps
+    int64_t max_episode_steps;    // <= 0: never truncate
+    int32_t n_ext, auto_reset;
+    int32_t vec4;                 // n_rays % 4 == 0 and obs / final_obs 16-byte aligned: rows move as float4
+    int32_t ext_index[FTGP_PAIR_STRIDE];   // car slot -> its index among the env's external cars, -1 = a bundled driver
+};
+
+// custom.py:132-143, as ftgp_get_progress column 3 reports it
+__device__ __forceinline__ int32_t absolute_completion(const CarCore& a)
+{
+    return a.laps * 100 + (a.good_start ? a.completion : -(100 - a.completion));
+}
+
+// One car per lane: external cars take the caller's action -- (0, 0) once finished, the null driver of custom.py:1441-1447 --
+// and every car's absolute_completion is kept for the reward.
+__global__ void ftgp_io_ingest_kernel(DeviceParams P, DeviceIoArgs A)
+{
+    const int ci = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ci >= P.n_cars) return;
+    CarState& s = P.cars[ci];
+    A.prev_abs[ci] = absolute_completion(s);
+    const int k = A.ext_index[ci % P.cars_per_env];
+    if (k < 0) return;
+    const float* a = A.action + 2 * ((size_t)(ci / P.cars_per_env) * A.n_ext + k);
+    const bool fin = s.finished != 0;
+    s.u_speed = fin ? 0.0 : (double)a[0];
+    s.u_steer = fin ? 0.0 : (double)a[1];
+}
+
+// One workgroup per env, after the steps: rewards, episode ends, and the observations.  An env that ended with auto_reset on
+// hands its scans to final_obs, gets obs rows of zeros and is reset exactly as ftgp_reset resets it (reset_car, ranges 0).
+#define FTGP_IO_THREADS 256
+__global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_kernel(DeviceParams P, DeviceIoArgs A)
+{
+    __shared__ int ended;
+    const int env = blockIdx.x, cpe = P.cars_per_env, ci0 = env * cpe, t = threadIdx.x;
+    if (t == 0) {
+        bool all_finished = true;
+        for (int c = 0; c < cpe; ++c)
+            if (A.ext_index[c] >= 0 && !P.cars[ci0 + c].finished) all_finished = false;
+        const bool trunc = !all_finished && A.max_episode_steps > 0 && P.steps[env] >= A.max_episode_steps;
+        A.terminated[env] = all_finished ? 1 : 0;
+        A.truncated[env] = trunc ? 1 : 0;
+        ended = (all_finished || trunc) ? 1 : 0;
+    }
+    if (t < cpe && A.ext_index[t] >= 0)
+        A.reward[(size_t)env * A.n_ext + A.ext_index[t]] = (float)(absolute_completion(P.cars[ci0 + t]) - A.prev_abs[ci0 + t]);
+    __syncthreads();
+    const bool reset = A.auto_reset && ended;
+    const int R = P.n_rays;
+    for (int c = 0; c < cpe; ++c) {
+        const int k = A.ext_index[c];
+        float* src = P.ranges + (size_t)(ci0 + c) * P.ranges_stride;
+        if (k >= 0) {
+            const size_t row = ((size_t)env * A.n_ext + k) * R;
+            float* obs = A.obs + row;
+            float* fin = A.final_obs ? A.final_obs + row : nullptr;
+            if (A.vec4) {
+                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int j = t; j < R / 4; j += FTGP_IO_THREADS) {
+                    const float4 v = reinterpret_cast<const float4*>(src)[j];
+                    if (!reset) { reinterpret_cast<float4*>(obs)[j] = v; continue; }
+                    if (fin) reinterpret_cast<float4*>(fin)[j] = v;
+                    reinterpret_cast<float4*>(obs)[j] = z;
+                }
+            } else {
+                for (int j = t; j < R; j += FTGP_IO_THREADS) {
+                    const float v = src[j];
+                    if (!reset) { obs[j] = v; continue; }
+                    if (fin) fin[j] = v;
+                    obs[j] = 0.0f;
+                }
+            }
+        }
+        __syncthreads();      // the row has been read before it is zeroed
+        if (reset) for (int j = t; j < P.ranges_stride; j += FTGP_IO_THREADS) src[j] = 0.0f;
+    }
+    if (reset && t < cpe) reset_car(P, ci0 + t);      // (the records were read before the first barrier)
 }
 
 // Packed read-back rows, one car per lane: the host copies 3 small arrays instead of the whole state records.

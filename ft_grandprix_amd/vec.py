@@ -1,0 +1,158 @@
+"""A vectorised environment stepped from torch tensors on the GPU (include/ftgp.h: ftgp_device_io_config / ftgp_step_device).
+
+For drivers that live on the device -- a learned driver, an MLP over the scan, anything written with torch ops -- the host path
+(``set_ctrl`` + ``step`` + ``get_lidar``, with a synchronisation each) caps the rate far below what the kernels reach.  Here a step
+only enqueues work: the actions are read, the worlds stepped, rewards / episode ends computed and ended envs reset on the device,
+ordered on torch's current stream.
+
+One HIP runtime per process.  torch ships its own ``libamdhip64.so``; ``libftgp.so`` resolves its HIP runtime to whichever copy is
+already mapped.  Imported after torch, it shares torch's; loaded first, torch then maps a second runtime, and torch's streams and
+pointers mean nothing to the library.  This module imports torch before it loads the library, and ``DeviceVecEnv`` refuses to run
+in a process that holds two runtimes (``check_single_hip_runtime``).  torch is imported here only; the rest of the package is numpy.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch  # first: the library must bind to torch's HIP runtime (see above)
+
+from . import capi
+from .track import Track, load_track
+
+RUNTIME_ERROR = "libftgp.so was loaded before torch in this process; start a fresh process"
+ROSTER_NAMES = ("agent", "host", "lobotomy", "nidc", "fast", "random")
+
+
+def mapped_hip_runtimes(maps_text: str | None = None) -> dict:
+    """{"libamdhip64": [paths], "libhsa-runtime64": [paths]}: the HIP and HSA runtime files mapped into this process."""
+    if maps_text is None:
+        with open("/proc/self/maps") as f:
+            maps_text = f.read()
+    out = {"libamdhip64": set(), "libhsa-runtime64": set()}
+    for line in maps_text.splitlines():
+        parts = line.split(None, 5)
+        if len(parts) < 6:
+            continue
+        path = parts[5].strip()
+        base = path.rsplit("/", 1)[-1]
+        for name in out:
+            if base.startswith(name + ".so"):
+                out[name].add(path)
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def check_single_hip_runtime(maps_text: str | None = None) -> None:
+    """Raise RuntimeError when more than one HIP or HSA runtime is mapped (libftgp.so was loaded before torch).
+
+    One exception: under rocprofv3 the profiler's own library (librocprofiler-sdk) maps the HSA runtime it was built against beside
+    torch's; with a single HIP runtime that second HSA file is the profiler's, not a second runtime of the process's HIP calls."""
+    if maps_text is None:
+        with open("/proc/self/maps") as f:
+            maps_text = f.read()
+    rt = mapped_hip_runtimes(maps_text)
+    profiler = "librocprofiler-sdk" in maps_text
+    for name, paths in rt.items():
+        if name == "libhsa-runtime64" and profiler and len(rt["libamdhip64"]) == 1:
+            continue
+        if len(paths) > 1:
+            raise RuntimeError(f"{RUNTIME_ERROR} (two copies of {name} are mapped: {', '.join(paths)})")
+
+
+class DeviceVecEnv:
+    """``n_envs`` worlds of ``cars_per_env`` cars each, stepped from torch tensors on ``cuda:device_id``.
+
+    roster: one entry per car slot -- "agent" (driven by the caller's actions) or a bundled device driver ("lobotomy", "nidc",
+    "fast", "random"); None = every slot an agent.  ``n_agents`` = the number of "agent" slots.
+
+    ``step(actions)`` takes float32 [n_envs, n_agents, 2] = (speed, steering_angle) and returns (obs, reward, terminated,
+    truncated, info): obs float32 [n_envs, n_agents, n_rays], reward float32 [n_envs, n_agents] = the change of the car's
+    absolute completion, terminated / truncated bool [n_envs], info["final_obs"] = the obs of the envs that ended in the call,
+    before their reset (other rows hold older values).  The returned tensors are the env's own buffers: the next ``step`` or
+    ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
+    synchronises the host.
+    """
+
+    def __init__(self, track, n_envs: int = 4096, n_rays: int = 1080, cars_per_env: int = 1, roster=None,
+                 max_episode_steps: int = 3000, action_repeat: int = 1, auto_reset: bool = True, device_id: int = 0, **env_kwargs):
+        n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
+        if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
+            raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
+        if int(action_repeat) < 1:
+            raise ValueError("action_repeat >= 1")
+        roster = ["agent"] * cars_per_env if roster is None else list(roster)
+        if len(roster) != cars_per_env:
+            raise ValueError(f"one roster entry per car of an env: expected {cars_per_env}, got {len(roster)}")
+        bad = [r for r in roster if r not in ROSTER_NAMES]
+        if bad:
+            raise ValueError(f"unknown roster entries {bad}: use one of {ROSTER_NAMES}")
+        roster = ["agent" if r == "host" else r for r in roster]
+        if "agent" not in roster:
+            raise ValueError('the roster needs at least one "agent" slot')
+        if "lidar_mode" in env_kwargs and env_kwargs["lidar_mode"] not in capi.LIDAR_BY_NAME and env_kwargs["lidar_mode"] not in (0, 1):
+            raise ValueError(f"unknown lidar_mode {env_kwargs['lidar_mode']!r}")
+        self.track = load_track(track) if isinstance(track, str) else track
+        if not isinstance(self.track, Track):
+            raise ValueError("track: a Track or the name of a bundled track")
+        self.n_envs, self.n_rays, self.cars_per_env, self.roster = n_envs, n_rays, cars_per_env, roster
+        self.n_agents = roster.count("agent")
+        self.max_episode_steps, self.action_repeat, self.auto_reset = int(max_episode_steps), int(action_repeat), bool(auto_reset)
+
+        lib = capi.load()
+        check_single_hip_runtime()                   # before any torch GPU call
+        self.device = torch.device("cuda", int(device_id))
+        self.env = capi.Env(lib, self.track, n_envs=n_envs, cars_per_env=cars_per_env, n_rays=n_rays, device_id=int(device_id),
+                            **env_kwargs)
+        self.env.device_io_config(roster, self.max_episode_steps, self.action_repeat, self.auto_reset)
+        z = dict(device=self.device)
+        self.obs = torch.zeros((n_envs, self.n_agents, n_rays), dtype=torch.float32, **z)
+        self.final_obs = torch.zeros_like(self.obs)
+        self.reward = torch.zeros((n_envs, self.n_agents), dtype=torch.float32, **z)
+        self.terminated = torch.zeros(n_envs, dtype=torch.bool, **z)     # one byte each: the library writes 0 / 1
+        self.truncated = torch.zeros(n_envs, dtype=torch.bool, **z)
+        self._shape = torch.Size((n_envs, self.n_agents, 2))
+        # the call's argument block, built once: a step fills in the action and the stream (the host side of a step is what bounds a
+        # one-step call, so it does no more than that)
+        self._io = capi.FtgpDeviceStep(None, None, self.obs.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
+                                       self.truncated.data_ptr(), self.final_obs.data_ptr())
+        self._io_ref = ctypes.byref(self._io)
+        self._step_device = lib.fn("step_device")
+
+    def reset(self):
+        """Reset every env (synchronous ftgp_reset); obs = the scans right after a reset, all zeros (custom.py:1092)."""
+        self.env.reset()
+        with torch.cuda.device(self.device):
+            self.obs.zero_()
+        return self.obs
+
+    def _check_actions(self, actions):
+        if not isinstance(actions, torch.Tensor):
+            raise ValueError("actions: a torch tensor")
+        if actions.device != self.device:
+            raise ValueError(f"actions are on {actions.device}, the env on {self.device}")
+        if actions.dtype != torch.float32:
+            raise ValueError(f"actions: float32, got {actions.dtype}")
+        if actions.shape != self._shape:
+            raise ValueError(f"actions: shape {tuple(self._shape)}, got {tuple(actions.shape)}")
+        if not actions.is_contiguous():
+            raise ValueError("actions: a contiguous tensor")
+
+    def step(self, actions):
+        self._check_actions(actions)
+        self._io.action = actions.data_ptr()
+        self._io.stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._step_device(self.env.h, self._io_ref)      # Env.step_device, without rebuilding the argument block
+        if rc:
+            self.env.lib.check(rc)
+        return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
+
+    def close(self):
+        if getattr(self, "env", None) is not None:
+            torch.cuda.current_stream(self.device).synchronize()
+            self.env.close()
+            self.env = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

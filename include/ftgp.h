@@ -215,6 +215,59 @@ int ftgp_rollout(FtgpEnv *env, int policy, int n_steps);
  */
 int ftgp_set_car_policies(FtgpEnv *env, const int32_t *policies);
 
+/*
+ * Device I/O: a vectorised environment stepped from device buffers, for drivers that live on the GPU (a learned driver, any batched
+ * policy over the scan), with rewards, episode ends and auto-reset on the device.  The reference steps one world with one Python
+ * driver call per car (custom.py:1398-1426); nothing there batches, so the rules below are this library's own, built from the
+ * reference's pieces as cited.
+ *
+ * ftgp_device_io_config sets the slot table and the episode rules (it may synchronise; call it once, or between phases):
+ *   roster             int32[cars_per_env] (host) or NULL (= every slot external).  FTGP_POLICY_HOST marks an external slot, driven by
+ *                      the caller's actions; the other slots take FTGP_POLICY_LOBOTOMY / NIDC / FAST / RANDOM, the bundled drivers on the
+ *                      device (template/cars/cars.json races nidc, fast, nidc).  At least one slot must be external.  This table is kept
+ *                      apart from ftgp_set_car_policies' roster: ftgp_rollout(FTGP_POLICY_PER_CAR) and ftgp_policy_eval behave as if the
+ *                      device path had never run.
+ *   max_episode_steps  truncation: env steps since the env's last reset >= this; <= 0 = never
+ *   action_repeat      physics steps per ftgp_step_device call, >= 1
+ *   auto_reset         non-zero: envs that end in a call are reset at the end of that call
+ * n_ext below = the number of external slots.
+ */
+typedef struct FtgpDeviceIoConfig {
+    const int32_t *roster;
+    int64_t max_episode_steps;
+    int32_t action_repeat;
+    int32_t auto_reset;
+} FtgpDeviceIoConfig;
+int ftgp_device_io_config(FtgpEnv *env, const FtgpDeviceIoConfig *cfg);
+
+/*
+ * One call of ftgp_step_device (it only enqueues work and never blocks the host):
+ *   1. the handle's stream waits for `stream` (an event recorded there); at the end `stream` waits for the handle's stream;
+ *   2. external car i of env e takes ctrl = ((double)action[e][i][0], (double)action[e][i][1]) -- (0, 0) once it has finished, the
+ *      reference's null driver (custom.py:1441-1447); every car's absolute_completion (ftgp_get_progress column 3) is noted;
+ *   3. action_repeat steps of ftgp_rollout(FTGP_POLICY_PER_CAR) with the device-io slot table: external slots keep their controls
+ *      (a finished car gets (0, 0) at every step), the other slots run their bundled drivers;
+ *   4. reward[e][i] = absolute_completion after - before (an integer, exact in float32); terminated[e] = every external car of e has
+ *      finished (custom.py:1367-1370); truncated[e] = not terminated, max_episode_steps > 0 and the env's steps >= max_episode_steps;
+ *      with auto_reset, an env that ended has its obs rows copied to final_obs (if given) and is reset exactly as ftgp_reset(mask)
+ *      resets it (spawn, ranges 0, steps 0, progress at the spawn pose);
+ *   5. obs[e][i] = the ranges of external car i of env e as ftgp_get_lidar lays them out -- all zeros for an env just reset
+ *      (custom.py:1092).
+ * Every buffer is device memory on the handle's device, laid out densely as below; a host pointer is FTGP_ERR_ARG before anything is
+ * enqueued.  Before ftgp_device_io_config: FTGP_ERR_STATE.  ftgp_last_kernel_ms reports the step kernel of the call.
+ */
+typedef struct FtgpDeviceStep {
+    void *stream;                 /* hipStream_t the buffers are ordered on (e.g. torch's current stream); NULL = the null stream */
+    const float *action;          /* float32[n_envs][n_ext][2] = (speed, steering_angle), external slots in slot order */
+    float *obs;                   /* float32[n_envs][n_ext][n_rays] */
+    float *reward;                /* float32[n_envs][n_ext] */
+    uint8_t *terminated;          /* uint8[n_envs] */
+    uint8_t *truncated;           /* uint8[n_envs] */
+    float *final_obs;             /* optional float32[n_envs][n_ext][n_rays]: rows of envs reset in this call get the pre-reset obs;
+                                     other rows are left as they were */
+} FtgpDeviceStep;
+int ftgp_step_device(FtgpEnv *env, const FtgpDeviceStep *io);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).
