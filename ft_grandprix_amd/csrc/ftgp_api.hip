@@ -8,7 +8,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -33,6 +35,25 @@ int fail(int code, const char* fmt, const char* a = "")
             return FTGP_ERR_HIP;                                                                   \
         }                                                                                          \
     } while (0)
+
+// ---- HIP resources, freed by their owners ------------------------------------------------------
+struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
+struct HostFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+struct EventFree { void operator()(hipEvent_t ev) const { (void)hipEventDestroy(ev); } };
+struct StreamFree { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+template <class T> using DevBuf = std::unique_ptr<T, DevFree>;       // hipMalloc
+template <class T> using HostBuf = std::unique_ptr<T, HostFree>;     // hipHostMalloc
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventFree>;
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamFree>;
+
+template <class T> hipError_t dev_alloc(DevBuf<T>& b, size_t bytes) { void* p = nullptr; hipError_t r = hipMalloc(&p, bytes); b.reset(static_cast<T*>(p)); return r; }
+template <class T> hipError_t dev_upload(DevBuf<T>& b, const void* src, size_t bytes)      // hipMalloc, then a copy from the host
+{ hipError_t r = dev_alloc(b, bytes); return r != hipSuccess ? r : hipMemcpy(b.get(), src, bytes, hipMemcpyHostToDevice); }
+template <class T> hipError_t dev_zeros(DevBuf<T>& b, size_t bytes, hipStream_t s)           // hipMalloc, then zeroed in stream order
+{ hipError_t r = dev_alloc(b, bytes); return r != hipSuccess ? r : hipMemsetAsync(b.get(), 0, bytes, s); }
+template <class T> hipError_t host_alloc(HostBuf<T>& b, size_t bytes, unsigned flags) { void* p = nullptr; hipError_t r = hipHostMalloc(&p, bytes, flags); b.reset(static_cast<T*>(p)); return r; }
+hipError_t make_event(Event& ev, unsigned flags) { hipEvent_t p = nullptr; hipError_t r = hipEventCreateWithFlags(&p, flags); ev.reset(p); return r; }
+hipError_t make_stream(Stream& s) { hipStream_t p = nullptr; hipError_t r = hipStreamCreateWithFlags(&p, hipStreamNonBlocking); s.reset(p); return r; }
 
 // ---- RCCL, loaded lazily so that single-GPU use never touches it ------------------------------
 struct Id128 { char internal[128]; };   // == ncclUniqueId (rccl.h:43)
@@ -67,30 +88,30 @@ int load_rccl()
 
 }  // namespace
 
+// The members free themselves in reverse order of declaration, the streams last; ftgp_destroy synchronises both streams first.
 struct FtgpEnv {
     DeviceParams P{};
-    FtgpConfig cfg{};
     int device = 0;
-    hipStream_t stream = nullptr, side = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop[2] = { nullptr, nullptr }, ev_metrics = nullptr, ev_gather = nullptr;      // ev_stop: one per metrics slot
+    Stream stream, side;
+    Event ev_start, ev_stop[2], ev_metrics, ev_gather;      // ev_stop: one per metrics slot
     bool timed = false;
     bool ext_launch = true;      // FTGP_LAUNCH_PLAIN=1 switches it off (tools/launch_host.sh)
     bool last_roster = false;    // the newest launch ran the ROSTER instantiation
     // device buffers
-    uint16_t* d_field = nullptr; uint32_t* d_bits = nullptr; uint32_t* d_nearbits = nullptr;
-    double* d_path = nullptr; double* d_spawn = nullptr; float* d_ray = nullptr; float* d_cover = nullptr; void* d_veh = nullptr; unsigned char* d_stage = nullptr; DeviceParams* d_params = nullptr;
-    CarState* d_cars = nullptr; float* d_ranges = nullptr; int64_t* d_steps = nullptr;
-    uint8_t* d_env_mask = nullptr; uint8_t* d_car_mask = nullptr; double* d_ctrl = nullptr; double* d_pose = nullptr;
-    double* d_metrics = nullptr; double* d_gather = nullptr; double* d_wg_metrics = nullptr; unsigned int* d_wg_ticket = nullptr;
-    double* d_edt = nullptr; double* d_fan = nullptr;      // FTGP_LIDAR_FAKELIDAR: distance transform, binary64 fan
+    DevBuf<uint16_t> d_field; DevBuf<uint32_t> d_bits, d_nearbits;
+    DevBuf<double> d_path, d_spawn; DevBuf<float> d_ray, d_cover; DevBuf<void> d_veh; DevBuf<unsigned char> d_stage; DevBuf<DeviceParams> d_params;
+    DevBuf<CarState> d_cars; DevBuf<float> d_ranges; DevBuf<int64_t> d_steps;
+    DevBuf<uint8_t> d_env_mask, d_car_mask; DevBuf<double> d_ctrl, d_pose;
+    DevBuf<double> d_metrics, d_gather, d_wg_metrics; DevBuf<unsigned int> d_wg_ticket;
+    DevBuf<double> d_edt, d_fan;      // FTGP_LIDAR_FAKELIDAR: distance transform, binary64 fan
     // This rank's metrics record lives in two slots (device memory for RCCL, pinned host memory for the caller) that successive
     // launches alternate between, so that the exchange of launch k's record can run beside launch k + 1.
     int cur_slot = 0;                    // slot of the most recent step launch (or of the record ftgp_metrics_kernel refreshed)
     bool launch_metrics_valid = false;   // slot cur_slot of d_metrics / h_metrics still describes the state (no reset / set_pose / ... since)
-    double* h_metrics = nullptr;      // pinned [2][FTGP_METRIC_DOUBLES]: THIS rank's records only (the gathered ones land in h_gather)
+    HostBuf<double> h_metrics;        // pinned [2][FTGP_METRIC_DOUBLES]: THIS rank's records only (the gathered ones land in h_gather)
     double* h_metrics_dev = nullptr;  // the same buffer as the device sees it: the step kernel's epilogue writes straight into it
-    double* h_gather = nullptr;       // pinned [world][FTGP_METRIC_DOUBLES]: landing buffer of the all-gather
-    double* h_wg_metrics = nullptr;   // pinned [2][workgroups][FTGP_METRIC_DOUBLES]: the workgroups' partial records of a launch (one rank, no communicator:
+    HostBuf<double> h_gather;         // pinned [world][FTGP_METRIC_DOUBLES]: landing buffer of the all-gather
+    HostBuf<double> h_wg_metrics;     // pinned [2][workgroups][FTGP_METRIC_DOUBLES]: the workgroups' partial records of a launch (one rank, no communicator:
                                       // nothing on the device needs the launch's record, the host adds the partial records up -- collect_slot())
     int n_blocks = 0;                 // workgroups of a step launch
     bool slot_partial[2] = { false, false };   // the record of that slot's launch is in h_wg_metrics (partial records), not in h_metrics
@@ -99,7 +120,7 @@ struct FtgpEnv {
     hipEvent_t gather_event = nullptr;   // what its _end waits for: ev_gather (side stream / metrics kernel) or the slot's own ev_stop
     bool gather_held = false;         // one rank: the record was copied to `held` because a later launch was about to reuse its slot
     double held[FTGP_METRIC_DOUBLES] = { 0 };
-    int32_t* d_prog = nullptr; double* d_core = nullptr;
+    DevBuf<int32_t> d_prog; DevBuf<double> d_core;
     std::vector<int32_t> h_prog; std::vector<double> h_core;
     bool rows_valid = false;          // h_prog / h_core mirror the device state (cleared by every call that changes it)
     bool multi = false;
@@ -107,10 +128,10 @@ struct FtgpEnv {
     bool io_ready = false;
     DeviceIoArgs io{};                // the episode rules and the slot table; the buffers are filled in per call
     int io_repeat = 1;
-    int32_t* h_tables = nullptr;      // pinned [2][FTGP_MAX_CARS_PER_BLOCK]: the user's roster (mirror of P.car_policy), the device-io slot table
+    HostBuf<int32_t> h_tables;        // pinned [2][FTGP_MAX_CARS_PER_BLOCK]: the user's roster (mirror of P.car_policy), the device-io slot table
     int table_on_device = 0;          // which of the two the params block holds (-1: neither); only a FTGP_POLICY_PER_CAR launch reads it
-    int32_t* d_prev_abs = nullptr;
-    hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
+    DevBuf<int32_t> d_prev_abs;
+    Event ev_io_in, ev_io_out;
     struct Checked { const void* p; size_t bytes; };
     Checked io_checked[32] = {};      // device buffers found valid (hipPointerGetAttributes), replaced round robin
     int io_checked_next = 0;
@@ -235,6 +256,275 @@ int lds_layout(DeviceParams& P, int cpb, int wpb)
     return o;
 }
 
+// the device probe of the entries that open a device: there is one (no CPU fallback) and `id` names it; it is made current
+int open_device(int id)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FTGP_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback%s");
+    if (id < 0 || id >= ndev) return fail(FTGP_ERR_ARG, "device_id out of range%s");
+    HIP_TRY(hipSetDevice(id));
+    return 0;
+}
+
+// Direction sectors of the box field: more slope slices mean fewer march iterations and a larger field.  A large batch is bound by
+// throughput and by what of the field its cars keep in the 4-MiB L2s (16 sectors: 32 bytes per pixel); a small one by the latency of
+// its longest rays (64 sectors); 16384 cars (config 5) do best with 8.  Measured: profiles/round4/ab_sectors.log.  Results do not depend on the choice.
+int sector_count(const FtgpConfig& cfg)
+{
+    const long cars_total = (long)cfg.n_envs * cfg.cars_per_env;
+    int n_sectors = cars_total >= 8192 ? 8 : cars_total >= 2048 ? 16 : 64;
+    if (const char* sv = getenv("FTGP_SECTORS_RT")) { const int c = atoi(sv); if (c == 8 || c == 16 || c == 32 || c == 64) n_sectors = c; }
+    return n_sectors;
+}
+
+// ftgp_create, step 1: the checks of the configuration (no device call)
+int validate(const FtgpConfig& cfg)
+{
+    if (cfg.abi_version != FTGP_ABI_VERSION) return fail(FTGP_ERR_ARG, "abi version mismatch%s");
+    if (cfg.n_envs < 1 || cfg.cars_per_env < 1 || cfg.cars_per_env > 8 || cfg.n_rays < 1) return fail(FTGP_ERR_ARG, "bad n_envs / cars_per_env / n_rays%s");
+    if (cfg.spawn_mode == 0 && (cfg.cars_per_env + 4) * 2 + 1 >= FTGP_PATH_POINTS) return fail(FTGP_ERR_ARG, "too many cars for the reference spawn rule%s");
+    const FtgpTrack& t = cfg.track;
+    if (t.width < 1 || t.height < 1 || !t.bits || !t.path || t.words_per_row < (t.width + 31) / 32) return fail(FTGP_ERR_ARG, "bad track%s");
+    if (t.width > 8192 || t.height > 8192) return fail(FTGP_ERR_ARG, "images above 8192 pixels are not supported%s");
+    // the march addresses the field with a 32-bit byte offset
+    if ((uint64_t)ftgp_plane256(t.width, t.height) * 256u * (uint64_t)sector_count(cfg) > 0xFFFFFFFFull)
+        return fail(FTGP_ERR_ARG, "track image too large: the sector box field (2 bytes per pixel and direction sector) must stay below 4 GiB%s");
+    if (cfg.env_base < 0) return fail(FTGP_ERR_ARG, "env_base < 0%s");
+    if (cfg.lidar_mode != FTGP_LIDAR_RANGEFINDER && cfg.lidar_mode != FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_ARG, "unknown lidar_mode%s");
+    if (!(cfg.dt > 0.0) || !(t.px_size_x > 0.0) || !(t.px_size_y > 0.0)) return fail(FTGP_ERR_ARG, "bad dt / pixel size%s");
+    const FtgpVehicle& v = cfg.vehicle;
+    if (!(v.contact_radius > 0.0) || !(v.mass > 0.0) || !(v.izz > 0.0) || (v.kind != FTGP_VEHICLE_MUSHR && v.kind != FTGP_VEHICLE_TRICYCLE))
+        return fail(FTGP_ERR_ARG, "bad vehicle%s");
+    if (cfg.bubble_wrap && !(v.softener_radius > 0.0)) return fail(FTGP_ERR_ARG, "bubble_wrap needs vehicle.softener_radius > 0%s");
+    return 0;
+}
+
+// ftgp_create, step 2: the plan -- everything that fixes what the step kernel does; host arithmetic only (no HIP call)
+struct Plan {
+    DeviceParams P = DeviceParams();  // value-initialised (padding bytes zero: the block is uploaded as it lies); every pointer null
+    HostTables tab;                   // bitmaps and run lengths of the track (build_tables)
+    std::vector<float> ray;           // [n_rays][2] binary32 fan, zero-padded to 16 bytes (DeviceParams::ray_dir)
+    std::vector<double> fan;          // [n_rays][2] binary64 fan (FAKELIDAR: DeviceParams::fan_dirs)
+    std::vector<double> spawn;        // [FTGP_PATH_POINTS][4] x, y, qw, qz
+    std::vector<float> cover;         // cover-count thresholds of nidc, then of fast, cover_kmax + 1 each (+ padding)
+    std::vector<unsigned char> veh;   // the VehLds image, padded to 16 bytes
+    std::vector<int32_t> tasks;       // [2][cars_per_block * tasks_per_car][4] the sweep's task tables (DeviceParams::task_tab)
+};
+
+// workgroup shape: whole envs, at most 16 cars (K1 / K3 run on the lanes of one wave), two workgroups per CU
+// (<= 80 KiB of LDS each) so that 8 waves per SIMD hide the latency of the field loads
+int plan_shape(DeviceParams& P)
+{
+    const int unit = P.cars_per_env;
+    int wpb = 16;
+    if (const char* sv = getenv("FTGP_WAVES_PER_BLOCK")) { const int c = atoi(sv); if (c >= 1 && c <= 16) wpb = c; }
+    int want = (FTGP_MAX_CARS_PER_BLOCK / unit) * unit;
+    // small batches: fewer cars per workgroup so that every CU gets work.  Up to four envs per CU a batch runs best as ONE workgroup per CU
+    // (its step is the driver -> dynamics latency chain plus one sweep task per wave: a second workgroup on the CU only competes for issue
+    // slots -- 1024 envs: 9.1 us per step with 256 workgroups of 4, 9.8 with 512 of 2; 512 envs: 8.8 / 9.0); larger batches take two
+    // workgroups per CU (1536 envs: 10.7 us with 512 workgroups of 3, 13.9 with 256 of 6) -- profiles/round5/config2_shapes.log
+    const int n_units = P.n_cars / unit;
+    const int n_cu = P.n_cu > 0 ? P.n_cu : 256;
+    const int per_cu = (n_units + n_cu - 1) / n_cu;
+    const int spread = (per_cu <= 4 ? std::max(1, per_cu) : std::max(1, n_units / (2 * n_cu))) * unit;
+    int cpb = std::min(want, spread);
+    if (const char* sv = getenv("FTGP_CARS_PER_BLOCK")) { const int c = atoi(sv); if (c >= unit && c <= FTGP_MAX_CARS_PER_BLOCK) cpb = (c / unit) * unit; }
+    int lds_cap = 80 * 1024;
+    if (const char* sv = getenv("FTGP_LDS_CAP_KB")) { const int c = atoi(sv); if (c >= 16 && c <= 160) lds_cap = c * 1024; }
+    while (cpb > unit && lds_layout(P, cpb, wpb) > lds_cap) cpb -= unit;
+    if (lds_layout(P, cpb, wpb) > 160 * 1024) {
+        snprintf(g_err, sizeof g_err, "one env of %d car(s) with a %d-ray scan does not fit the 160 KiB LDS", unit, P.n_rays);
+        return FTGP_ERR_ARG;
+    }
+    if (getenv("FTGP_VERBOSE"))
+        fprintf(stderr, "ftgp_create: %d cars x %d waves per workgroup, %d B of LDS (cap %d)\n", cpb, wpb, lds_layout(P, cpb, wpb), lds_cap);
+    return 0;
+}
+
+// the fan: binary32 ray table (zero-padded to 16 bytes) and binary64 directions
+void plan_fan(const FtgpConfig& cfg, std::vector<float>& ray, std::vector<double>& fan)
+{
+    const int R = cfg.n_rays;
+    ray.assign((size_t)pad16(sizeof(float) * 2 * (size_t)R) / sizeof(float), 0.0f);
+    fan.assign(2 * (size_t)R, 0.0);
+    for (int j = 0; j < R; ++j) {
+        // mushr.em.xml:112-117: phi_j = radians(360/R*j - 90); the ray (+z of the site) is (sin phi, -cos phi, 0)
+        const double phi = ((360.0 / (double)R) * (double)j - 90.0) * (M_PI / 180.0);
+        fan[2 * (size_t)j] = cfg.fan_dirs ? cfg.fan_dirs[2 * (size_t)j] : sin(phi);
+        fan[2 * (size_t)j + 1] = cfg.fan_dirs ? cfg.fan_dirs[2 * (size_t)j + 1] : -cos(phi);
+        ray[2 * (size_t)j] = (float)fan[2 * (size_t)j]; ray[2 * (size_t)j + 1] = (float)fan[2 * (size_t)j + 1];
+        // The rangefinders' own fan is point-symmetric: site j + n/2 looks exactly opposite to site j.  The BINARY32 table says so to the last
+        // bit (its second half is the negated first half -- the roundings of libm's sin / cos of phi + pi need not be), which is what lets the
+        // sweep derive a ray from its opposite; a caller's fan_dirs is taken as it comes.  The binary64 fan of FAKELIDAR mode is libm's value
+        // for every site, as include/ftgp.h says for fan_dirs == NULL (round 4 negated it too: a last-bit difference from the documented fan).
+        if (!cfg.fan_dirs && R % 2 == 0 && j >= R / 2) {
+            ray[2 * (size_t)j] = -ray[2 * (size_t)(j - R / 2)]; ray[2 * (size_t)j + 1] = -ray[2 * (size_t)(j - R / 2) + 1];
+        }
+    }
+}
+
+// the sweep's work list (lidar_groups): draw g -> (kidx = g / cars_per_block, car slot = g % cars_per_block), task = group_order[kidx]
+void plan_task_order(const FtgpConfig& cfg, const std::vector<float>& ray, DeviceParams& P)
+{
+    const int R = cfg.n_rays, halfR = R / 2;
+    bool sym = R % 2 == 0 && !getenv("FTGP_NO_PAIRS");
+    for (int j = 0; sym && j < halfR; ++j)
+        sym = ray[2 * (size_t)(j + halfR)] == -ray[2 * (size_t)j] && ray[2 * (size_t)(j + halfR) + 1] == -ray[2 * (size_t)j + 1] &&
+              std::signbit(ray[2 * (size_t)(j + halfR)]) != std::signbit(ray[2 * (size_t)j]) && std::signbit(ray[2 * (size_t)(j + halfR) + 1]) != std::signbit(ray[2 * (size_t)j + 1]);
+    std::vector<int> tasks;
+    if (!sym) for (int j0 = 0; j0 < R; j0 += FTGP_WAVE) tasks.push_back(j0);
+    else {
+        int j0 = 0;
+        for (; j0 + FTGP_WAVE <= halfR; j0 += FTGP_WAVE) tasks.push_back(j0 | (1 << 16));
+        if (j0 < halfR) tasks.push_back(j0 | ((halfR - j0 <= FTGP_WAVE / 2 ? 2 : 1) << 16));
+    }
+    // expected march length of a task ~ how far its rays look along the car's axis: |cos| of the angle between the group's middle ray
+    // and the axis (ray 0 looks backwards, ray n/2 ahead); ties keep index order
+    std::vector<std::pair<double, int>> key;
+    for (int t : tasks) {
+        const double mid = std::min((double)R - 1.0, (double)(t & 0xffff) + 31.5);
+        key.push_back({ getenv("FTGP_GROUP_ORDER_PLAIN") ? 0.0 : -fabs(cos(2.0 * M_PI * mid / (double)R)), t });
+    }
+    std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
+    // the cheapest pairs -- the last tasks a sweep draws -- go out as two single groups each: the waves then end a sweep within ONE short
+    // group of each other, not within two (the set-up shared inside a pair is worth less than that at the very end)
+    int tail = 2;
+    if (const char* sv = getenv("FTGP_PAIR_TAIL")) tail = atoi(sv);
+    std::vector<int> order;
+    for (size_t k = 0; k < key.size(); ++k) {
+        const int t = key[k].second;
+        if ((t >> 16) == 1 && (int)(key.size() - k) <= tail) { order.push_back(t & 0xffff); order.push_back((t & 0xffff) + halfR); }
+        else order.push_back(t);
+    }
+    P.tasks_per_car = (int)order.size();
+    for (size_t k = 0; k < order.size(); ++k) P.group_order[k] = order[k];
+    // mate_masks(): a ray of a group lies within 32 spacings of the rangefinders' uniform fan of the group's middle ray; + 1.2 degrees for the
+    // slack in the rays' own test (acos 0.9999 = 0.81 degrees) and rounding.  A caller's fan has no such bound: every mate is looked at.
+    const double gamma = 32.0 * (2.0 * M_PI / (double)R) + 0.021;
+    if (cfg.fan_dirs || gamma >= 1.5) { P.group_cg = -2.0f; P.group_sg = 0.0f; }
+    else { P.group_cg = (float)cos(gamma); P.group_sg = (float)sin(gamma); }
+    if (getenv("FTGP_VERBOSE")) fprintf(stderr, "ftgp_create: %d sweep tasks per car (%s)\n", P.tasks_per_car, sym ? "pairs of opposite ray groups" : "single groups");
+}
+
+// the sweep's task tables (DeviceParams::task_tab): draw g is task g / cars_per_block of car slot g % cars_per_block, with everything the
+// draw and the delivery need precomputed
+int plan_task_table(const DeviceParams& P, std::vector<int32_t>& tt)
+{
+    const int cpb = P.cars_per_block, ntasks = cpb * P.tasks_per_car, R = P.n_rays, halfR = R / 2;
+    if (P.tasks_per_car > 256 || R > 0x4000) return fail(FTGP_ERR_ARG, "internal: the task table's fields are too narrow for this fan%s");
+    tt.assign(2 * 4 * (size_t)ntasks, 0);
+    auto wclass = [&](int first, int lim) {          // rays first .. min(first + 63, lim - 1) against the window [eighth, R - eighth)
+        const int last = std::min(first + FTGP_WAVE, lim) - 1, lo = P.eighth, hi = R - P.eighth;
+        if (last < lo || first >= hi || lo >= hi) return 0;
+        return (first >= lo && last < hi) ? 1 : 2;
+    };
+    for (int g = 0; g < ntasks; ++g) {
+        const int kidx = g / cpb, c = g % cpb, ent = P.group_order[kidx], j0 = ent & 0xffff, kind = ent >> 16;
+        const int w0 = kind == 2 ? 2 : wclass(j0, kind == 1 ? halfR : R), w1 = kind == 1 ? wclass(j0 + halfR, R) : 0;
+        const uint32_t plain = (uint32_t)j0 | (uint32_t)kind << 14 | (uint32_t)c << 16;
+        int32_t* a = &tt[4 * (size_t)g];
+        int32_t* b = &tt[4 * (size_t)(ntasks + g)];
+        a[0] = (int32_t)(plain | (uint32_t)w0 << 20 | (uint32_t)w1 << 22 | (uint32_t)(j0 == 0 ? 1 : 0) << 24);
+        b[0] = (int32_t)plain;
+        a[1] = b[1] = c * (int)sizeof(LidarFrame) | kidx << 16;
+        a[2] = b[2] = c * P.ranges_stride * 4;
+        a[3] = b[3] = 4 * (c * P.win_floats + (P.eighth & 3) - P.eighth);
+    }
+    return 0;
+}
+
+// the VehLds image: the vehicle constants as the step kernel stages them into LDS
+void plan_vehicle(const DeviceParams& P, std::vector<unsigned char>& img)
+{
+    const FtgpVehicle& v = P.veh;
+    img.assign((size_t)pad16(sizeof(VehLds)), 0);
+    VehLds vl; memset(&vl, 0, sizeof vl);
+    vl.v = P.veh; for (int i = 0; i < 4; ++i) vl.wheel_load[i] = P.wheel_load[i];
+    // every part of a car that a ray can see (chassis box, LiDAR puck) lies within rmax of the car's origin; 10 % margin
+    const double cx = std::max(fabs(v.box_xmin), fabs(v.box_xmax)), cy = std::max(fabs(v.box_ymin), fabs(v.box_ymax));
+    const double rmax = std::max(sqrt(cx * cx + cy * cy), sqrt(v.lidar_x * v.lidar_x + v.lidar_y * v.lidar_y) + v.lidar_ring_radius);
+    vl.cull_radius = (float)(1.1 * rmax);
+    {   // the puck inside the box with at least 1e-3 to spare on every side (MuSHR: 0.016, tricycle: 0.0175): coordinates in a mate's frame are below the
+        // map's 40 units, so binary32 rounding of the two tests is below 1e-5 -- the circle can never come out ahead of the box
+        const double m = 1e-3, r = v.lidar_ring_radius;
+        vl.puck_in_box = (v.lidar_x - r >= v.box_xmin + m && v.lidar_x + r <= v.box_xmax - m && v.lidar_y - r >= v.box_ymin + m && v.lidar_y + r <= v.box_ymax - m &&
+                          !getenv("FTGP_PUCK_TEST")) ? 1 : 0;
+    }
+    vl.box_xmin_f = (float)v.box_xmin; vl.box_xmax_f = (float)v.box_xmax; vl.box_ymin_f = (float)v.box_ymin; vl.box_ymax_f = (float)v.box_ymax;
+    vl.lidar_x_f = (float)v.lidar_x; vl.lidar_y_f = (float)v.lidar_y; vl.ring_radius_f = (float)v.lidar_ring_radius;
+    memcpy(img.data(), &vl, sizeof vl);
+}
+
+// n_cu: compute units of the device (the workgroup shape depends on it)
+int plan_create(const FtgpConfig& cfg, int n_cu, Plan& pl)
+{
+    const FtgpTrack& t = cfg.track;
+    const FtgpVehicle& v = cfg.vehicle;
+    DeviceParams& P = pl.P;
+    P.n_envs = cfg.n_envs; P.cars_per_env = cfg.cars_per_env; P.n_cars = cfg.n_envs * cfg.cars_per_env;
+    P.n_rays = cfg.n_rays; P.lap_target = cfg.lap_target; P.spawn_mode = cfg.spawn_mode; P.env_base = cfg.env_base;
+    P.ranges_stride = (cfg.n_rays + 31) & ~31;      // rows start on 128-B boundaries
+    P.seed = cfg.seed; P.dt = cfg.dt;
+    P.rpp = (2 * M_PI) / (double)cfg.n_rays;
+    P.two_over_rpp = (float)(2.0 / P.rpp);
+    P.bubble_wrap = cfg.bubble_wrap ? 1 : 0;        // cfg.naive_flatten: accepted, no effect on a planar model (custom.py:1338-1339)
+    P.lidar_mode = cfg.lidar_mode;
+    P.map_size = cfg.map_size > 0.0 ? cfg.map_size : 40.0;                     // 20 * scale, custom.py:1155,1382
+    P.width = t.width; P.height = t.height; P.words_per_row = t.words_per_row; P.fstride = t.width + 2;
+    P.plane256 = ftgp_plane256(t.width, t.height);
+    // a ray's sector is always found among all FTGP_SECTORS; the table says which plane serves it
+    P.n_sectors = sector_count(cfg); P.slice_factor = FTGP_SLICE_FACTOR(FTGP_SLOPE_SLICES);
+    P.n_planes = ftgp_sector_table(P.sector_tab, P.n_sectors, t.width + 2, P.plane256);
+    P.px_size_x = t.px_size_x; P.px_size_y = t.px_size_y; P.origin_x = t.origin_x; P.origin_y = t.origin_y;
+    P.inv_px_x = 1.0 / t.px_size_x; P.inv_px_y = 1.0 / t.px_size_y;
+    P.inv_px_x_f = (float)P.inv_px_x; P.inv_px_y_f = (float)P.inv_px_y;
+    P.veh = cfg.vehicle;
+    {   // static wheel loads from the wheelbase split
+        const double wtot = v.mass * v.gravity;
+        if (v.kind == FTGP_VEHICLE_TRICYCLE) {       // two driven wheels behind the origin, the caster (wheel 2) in front
+            const double a_f = v.wheel_x[2], a_r = -0.5 * (v.wheel_x[0] + v.wheel_x[1]);
+            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_f / (a_f + a_r)));
+            P.wheel_load[2] = wtot * (a_r / (a_f + a_r)); P.wheel_load[3] = 0.0;
+        } else {
+            const double a_f = 0.5 * (v.wheel_x[0] + v.wheel_x[1]), a_r = -0.5 * (v.wheel_x[2] + v.wheel_x[3]);
+            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_r / (a_f + a_r)));
+            P.wheel_load[2] = P.wheel_load[3] = 0.5 * (wtot * (a_f / (a_f + a_r)));
+        }
+    }
+    {   // chessboard reach of the largest wall-contact window
+        const double rmax = std::max(v.contact_radius, cfg.bubble_wrap ? v.softener_radius : 0.0);
+        P.contact_reach = std::max((int)ceil(rmax * P.inv_px_x), (int)ceil(rmax * P.inv_px_y));
+    }
+    P.eighth = (int)((double)cfg.n_rays / 8.0);                    // nidc.py:18
+    // the largest cover count any positive sample can produce (that of the smallest positive float), over both drivers
+    const double tiny = (double)1.401298464e-45f;
+    P.cover_kmax = std::max(1, std::max(cover_count_host(0.24, P.rpp, tiny), cover_count_host(0.12, P.rpp, tiny)));
+    P.win_floats = ((P.eighth & 3) + (cfg.n_rays - 2 * P.eighth) + 1 + 3) & ~3;       // window at float (eighth % 4), ranges[0] in the last float
+    P.snap_eps = ftgp_snap_eps(t.width, t.height);
+    P.n_cu = n_cu;
+    P.edge_margin = (float)(v.lidar_ring_radius * std::max(P.inv_px_x, P.inv_px_y) * 1.001 + 2.0);
+    if ((cfg.n_rays + FTGP_WAVE - 1) / FTGP_WAVE > FTGP_MAX_GROUPS) return fail(FTGP_ERR_ARG, "n_rays above 16384 is not supported%s");
+    if (int rc = plan_shape(P)) return rc;
+    build_tables(t, P.contact_reach, pl.tab);
+    plan_fan(cfg, pl.ray, pl.fan);
+    plan_task_order(cfg, pl.ray, P);
+    if (int rc = plan_task_table(P, pl.tasks)) return rc;
+    pl.spawn.assign(4 * FTGP_PATH_POINTS, 0.0);
+    for (int p = 0; p < FTGP_PATH_POINTS; ++p) {      // position_vehicles (custom.py:1240-1245) + euler_to_quaternion([angle, 0, 0]) (custom.py:81-87)
+        const int p1 = (p + 1) % FTGP_PATH_POINTS;
+        const double ang = atan2(t.path[2 * p1 + 1] - t.path[2 * p + 1], t.path[2 * p1] - t.path[2 * p]);
+        pl.spawn[4 * p] = t.path[2 * p]; pl.spawn[4 * p + 1] = t.path[2 * p + 1]; pl.spawn[4 * p + 2] = cos(ang / 2); pl.spawn[4 * p + 3] = sin(ang / 2);
+    }
+    {   // cover-count thresholds: nidc (car_width 0.12, nidc.py:5) then fast (0.06, fast.py:4), each padded to the staged size
+        const size_t stride = (size_t)P.cover_kmax + 1, padded = (size_t)pad16(sizeof(float) * stride) / sizeof(float);
+        pl.cover.assign(stride + padded + 4, 0.0f);
+        build_cover_table(0.12, cfg.n_rays, P.cover_kmax, pl.cover.data());
+        build_cover_table(0.06, cfg.n_rays, P.cover_kmax, pl.cover.data() + stride);
+    }
+    plan_vehicle(P, pl.veh);
+    return 0;
+}
+
 // Waiting for an event of a launch is a blocked wait.  Polling hipEventQuery instead was measured (tools/launch_host.sh, round 4): 7 us
 // SLOWER per launch -- every query takes the runtime's locks and walks the stream's command list.
 hipError_t wait_event(const FtgpEnv*, hipEvent_t ev) { return hipEventSynchronize(ev); }
@@ -248,14 +538,35 @@ bool uses_disparity_driver(const FtgpEnv* e, int policy)
     return false;
 }
 
+// what the device drivers nidc and fast need of the scan
+int check_disparity_shape(const DeviceParams& P)
+{
+    if (P.n_rays < 8) return fail(FTGP_ERR_ARG, "nidc/fast need n_rays >= 8 (they drop len/8 rays from each end)%s");
+    if (P.n_rays - 2 * P.eighth > FTGP_WAVE * FTGP_WAVE) return fail(FTGP_ERR_ARG, "the device drivers handle at most 4096 samples in the front window%s");
+    return 0;
+}
+
+// The six instantiations of ftgp_step_kernel<MULTI, FAKE, ROSTER>.  FAKELIDAR always runs the roster one.
+struct StepKernel { void (*fn)(const DeviceParams*, int, int, int); const char* name; };
+const StepKernel kStepKernels[2][3] = {      // [multi][0: single driver, 1: roster, 2: FAKELIDAR]
+    { { ftgp_step_kernel<false, false, false>, "ftgp_step_kernel<false, false, false>" },
+      { ftgp_step_kernel<false, false, true>, "ftgp_step_kernel<false, false, true>" },
+      { ftgp_step_kernel<false, true, true>, "ftgp_step_kernel<false, true, true>" } },
+    { { ftgp_step_kernel<true, false, false>, "ftgp_step_kernel<true, false, false>" },
+      { ftgp_step_kernel<true, false, true>, "ftgp_step_kernel<true, false, true>" },
+      { ftgp_step_kernel<true, true, true>, "ftgp_step_kernel<true, true, true>" } },
+};
+
+const StepKernel& step_kernel(const FtgpEnv* e, bool roster) { return kStepKernels[e->multi][e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR ? 2 : roster ? 1 : 0]; }
+
 // This rank's record of the launch (or metrics kernel) that wrote `slot`, once its event has been waited for: the record itself, or the
 // sum of the workgroups' partial records (sums of integers, a minimum and a maximum: exact in any order -- bit-identical to what the
 // step kernel's last workgroup or ftgp_metrics_kernel compute on the device).
 void collect_slot(const FtgpEnv* e, int slot, double* out)
 {
-    if (!e->slot_partial[slot]) { memcpy(out, e->h_metrics + (size_t)slot * FTGP_METRIC_DOUBLES, sizeof(double) * FTGP_METRIC_DOUBLES); return; }
+    if (!e->slot_partial[slot]) { memcpy(out, e->h_metrics.get() + (size_t)slot * FTGP_METRIC_DOUBLES, sizeof(double) * FTGP_METRIC_DOUBLES); return; }
     double v[FTGP_METRIC_DOUBLES] = { 0, 0, 0, 0, 0, 0, INFINITY, -INFINITY };
-    const double* r = e->h_wg_metrics + (size_t)slot * e->n_blocks * FTGP_METRIC_DOUBLES;
+    const double* r = e->h_wg_metrics.get() + (size_t)slot * e->n_blocks * FTGP_METRIC_DOUBLES;
     for (int b = 0; b < e->n_blocks; ++b, r += FTGP_METRIC_DOUBLES) {
         for (int q = 0; q < 6; ++q) v[q] += r[q];
         v[6] = fmin(v[6], r[6]); v[7] = fmax(v[7], r[7]);
@@ -268,8 +579,8 @@ void collect_slot(const FtgpEnv* e, int slot, double* out)
 int use_table(FtgpEnv* e, int which)
 {
     if (e->table_on_device == which) return 0;
-    HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(e->d_params) + offsetof(DeviceParams, car_policy), e->h_tables + which * FTGP_MAX_CARS_PER_BLOCK,
-                           sizeof e->P.car_policy, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(e->d_params.get()) + offsetof(DeviceParams, car_policy), e->h_tables.get() + which * FTGP_MAX_CARS_PER_BLOCK,
+                           sizeof e->P.car_policy, hipMemcpyHostToDevice, e->stream.get()));
     e->table_on_device = which;
     return 0;
 }
@@ -281,10 +592,7 @@ int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
     if (n_steps < 0) return fail(FTGP_ERR_ARG, "n_steps < 0%s");
     if (!device_io) {
         if (policy == FTGP_POLICY_PER_CAR && !e->P.car_policy[0]) return fail(FTGP_ERR_STATE, "FTGP_POLICY_PER_CAR without ftgp_set_car_policies%s");
-        if (uses_disparity_driver(e, policy)) {
-            if (e->P.n_rays < 8) return fail(FTGP_ERR_ARG, "nidc/fast need n_rays >= 8 (they drop len/8 rays from each end)%s");
-            if (e->P.n_rays - 2 * e->P.eighth > FTGP_WAVE * FTGP_WAVE) return fail(FTGP_ERR_ARG, "the device drivers handle at most 4096 samples in the front window%s");
-        }
+        if (uses_disparity_driver(e, policy)) if (int rc = check_disparity_shape(e->P)) return rc;
     }
     HIP_TRY(hipSetDevice(e->device));
     if (policy == FTGP_POLICY_PER_CAR && n_steps > 0 && e->h_tables) if (int rc = use_table(e, device_io ? 1 : 0)) return rc;
@@ -294,7 +602,7 @@ int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
     // an exchange that is still reading this launch's slot (begin without end, two launches ago) goes first: over RCCL on the device (the
     // side stream's event); with one rank the "exchange" is the record in pinned memory, which is put aside before the slot is reused
     if (n_steps > 0 && e->gather_open && e->gather_slot == slot) {
-        if (e->comm) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_gather, 0));
+        if (e->comm) HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_gather.get(), 0));
         else if (!e->gather_held) {
             HIP_TRY(wait_event(e, e->gather_event));
             collect_slot(e, slot, e->held);
@@ -304,27 +612,23 @@ int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
     // The launch's two events ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL): no marker packet before and after it,
     // and their difference is the kernel's time alone.  FTGP_LAUNCH_PLAIN=1: hipEventRecord on either side instead.
     const bool ext = e->ext_launch && n_steps > 0;
-    if (!ext) HIP_TRY(hipEventRecord(e->ev_start, e->stream));
+    if (!ext) HIP_TRY(hipEventRecord(e->ev_start.get(), e->stream.get()));
     if (n_steps > 0) {
         const dim3 grid(blocks), block(e->P.waves_per_block * FTGP_WAVE);
         const uint32_t lds = (uint32_t)e->P.lds_bytes;
-        const bool fake = e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR;
-        hipEvent_t ev0 = ext ? e->ev_start : nullptr, ev1 = ext ? e->ev_stop[slot] : nullptr;
+        hipEvent_t ev0 = ext ? e->ev_start.get() : nullptr, ev1 = ext ? e->ev_stop[slot].get() : nullptr;
         const bool roster = policy == FTGP_POLICY_PER_CAR;
         e->last_roster = roster;
         // one rank and no communicator: the workgroups' partial records go straight to pinned host memory (bit 1 of the slot argument)
         const bool partial = e->h_wg_metrics != nullptr && e->comm == nullptr && e->d_wg_metrics != nullptr;
         const int slot_arg = slot | (partial ? 2 : 0);
         e->slot_partial[slot] = partial;
-#define FTGP_LAUNCH(M, F, R) hipExtLaunchKernelGGL((ftgp_step_kernel<M, F, R>), grid, block, lds, e->stream, ev0, ev1, 0, e->d_params, policy, n_steps, slot_arg)
-        if (e->multi) { if (fake) FTGP_LAUNCH(true, true, true); else if (roster) FTGP_LAUNCH(true, false, true); else FTGP_LAUNCH(true, false, false); }
-        else          { if (fake) FTGP_LAUNCH(false, true, true); else if (roster) FTGP_LAUNCH(false, false, true); else FTGP_LAUNCH(false, false, false); }
-#undef FTGP_LAUNCH
+        hipExtLaunchKernelGGL(step_kernel(e, roster).fn, grid, block, lds, e->stream.get(), ev0, ev1, 0, e->d_params.get(), policy, n_steps, slot_arg);
         HIP_TRY(hipGetLastError());
         e->cur_slot = slot;
         e->launch_metrics_valid = e->d_wg_metrics != nullptr;
     }
-    if (!ext) HIP_TRY(hipEventRecord(e->ev_stop[e->cur_slot], e->stream));
+    if (!ext) HIP_TRY(hipEventRecord(e->ev_stop[e->cur_slot].get(), e->stream.get()));
     e->timed = true;
     return 0;
 }
@@ -336,11 +640,11 @@ int sync_rows_to_host(FtgpEnv* e)
     HIP_TRY(hipSetDevice(e->device));
     const size_t n = (size_t)e->P.n_cars;
     e->h_prog.resize(n * FTGP_PROGRESS_INTS); e->h_core.resize(n * kCoreDoubles);
-    hipLaunchKernelGGL(ftgp_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->P, e->d_prog, e->d_core);
+    hipLaunchKernelGGL(ftgp_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream.get(), e->P, e->d_prog.get(), e->d_core.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(e->h_prog.data(), e->d_prog, sizeof(int32_t) * e->h_prog.size(), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_core.data(), e->d_core, sizeof(double) * e->h_core.size(), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(e->h_prog.data(), e->d_prog.get(), sizeof(int32_t) * e->h_prog.size(), hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipMemcpyAsync(e->h_core.data(), e->d_core.get(), sizeof(double) * e->h_core.size(), hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     e->rows_valid = true;
     return 0;
 }
@@ -366,6 +670,89 @@ int check_device_buffer(FtgpEnv* e, const void* p, size_t bytes, const char* nam
     if (q < b || q - b + bytes > size) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is smaller than the layout needs", name);
     e->io_checked[e->io_checked_next] = { p, bytes };
     e->io_checked_next = (e->io_checked_next + 1) % (int)(sizeof e->io_checked / sizeof e->io_checked[0]);
+    return 0;
+}
+
+// ftgp_create, step 3: the upload -- allocate, copy, search the box field (or the distance transform), write the images
+int upload(FtgpEnv* e, const FtgpTrack& t, const Plan& pl)
+{
+    memcpy(&e->P, &pl.P, sizeof e->P);          // as it lies, padding included
+    DeviceParams& P = e->P;
+    hipStream_t s = e->stream.get();
+    const size_t plane = (size_t)t.width * t.height, n_cars = (size_t)P.n_cars;
+    if (P.lidar_mode == FTGP_LIDAR_FAKELIDAR) {
+        // The distance transform of custom.py:1149-1153 / raycast.py:24-27 (scipy.ndimage.distance_transform_edt of the non-wall
+        // mask) without scipy, exact: the squared distance is the minimum over the columns x' of (x - x')^2 + g(x', y)^2 with g the
+        // vertical distance to the nearest wall of column x' -- the run lengths above -- in integers; one correctly rounded sqrt.
+        DevBuf<uint16_t> d_runy;
+        HIP_TRY(dev_upload(d_runy, pl.tab.runy.data(), 2 * plane * sizeof(uint16_t)));
+        HIP_TRY(dev_alloc(e->d_edt, plane * sizeof(double)));
+        HIP_TRY(dev_upload(e->d_fan, pl.fan.data(), pl.fan.size() * sizeof(double)));
+        hipLaunchKernelGGL(ftgp_edt_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, d_runy.get(), t.width, t.height, e->d_edt.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        P.edt = e->d_edt.get(); P.fan_dirs = e->d_fan.get();
+    } else {   // sector box field: upload the run lengths, search the boxes on the device
+        const size_t plane_cells = (size_t)P.plane256 * 128;
+        DevBuf<uint16_t> d_runx, d_runy;
+        HIP_TRY(dev_alloc(e->d_field, plane_cells * (size_t)P.n_planes * sizeof(uint16_t)));
+        HIP_TRY(dev_upload(d_runx, pl.tab.runx.data(), 2 * plane * sizeof(uint16_t)));
+        HIP_TRY(dev_upload(d_runy, pl.tab.runy.data(), 2 * plane * sizeof(uint16_t)));
+        hipLaunchKernelGGL(ftgp_box_field_kernel, dim3((unsigned)((plane_cells * P.n_sectors + 255) / 256)), dim3(256), 0, s, d_runx.get(), d_runy.get(), t.width, t.height, P.n_sectors, e->d_field.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        P.field = e->d_field.get();
+    }
+    const size_t sz_bits = sizeof(uint32_t) * (size_t)t.height * t.words_per_row, sz_path = sizeof(double) * 2 * FTGP_PATH_POINTS;
+    HIP_TRY(dev_upload(e->d_veh, pl.veh.data(), pl.veh.size()));
+    HIP_TRY(dev_upload(e->d_bits, pl.tab.bits.data(), sz_bits));
+    HIP_TRY(dev_upload(e->d_nearbits, pl.tab.nearbits.data(), sz_bits));
+    HIP_TRY(dev_upload(e->d_path, t.path, sz_path));
+    HIP_TRY(dev_upload(e->d_ray, pl.ray.data(), sizeof(float) * pl.ray.size()));
+    HIP_TRY(dev_upload(e->d_spawn, pl.spawn.data(), sizeof(double) * pl.spawn.size()));
+    HIP_TRY(dev_upload(e->d_cover, pl.cover.data(), sizeof(float) * pl.cover.size()));
+    // zeroed on the handle's own stream: a non-blocking stream is not ordered against the null stream, and ftgp_reset() runs on it
+    HIP_TRY(dev_zeros(e->d_cars, sizeof(CarState) * n_cars, s)); HIP_TRY(dev_zeros(e->d_ranges, sizeof(float) * n_cars * P.ranges_stride, s));
+    HIP_TRY(dev_zeros(e->d_steps, sizeof(int64_t) * (size_t)P.n_envs, s)); HIP_TRY(dev_alloc(e->d_env_mask, (size_t)P.n_envs)); HIP_TRY(dev_alloc(e->d_car_mask, n_cars));
+    HIP_TRY(dev_alloc(e->d_ctrl, sizeof(double) * 2 * n_cars)); HIP_TRY(dev_alloc(e->d_pose, sizeof(double) * FTGP_POSE_DOUBLES * n_cars));
+    HIP_TRY(dev_alloc(e->d_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2));
+    HIP_TRY(host_alloc(e->h_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2, hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void**)&e->h_metrics_dev, e->h_metrics.get(), 0));
+    if (!getenv("FTGP_NO_FUSED_METRICS")) {          // (diagnostic switch: tests compare the fused record with ftgp_metrics_kernel's)
+        const size_t blocks = (n_cars + (size_t)P.cars_per_block - 1) / (size_t)P.cars_per_block;
+        HIP_TRY(dev_alloc(e->d_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * blocks));
+        HIP_TRY(dev_zeros(e->d_wg_ticket, sizeof(unsigned int), s));
+        P.wg_metrics = e->d_wg_metrics.get(); P.wg_ticket = e->d_wg_ticket.get(); P.metrics_dev = e->d_metrics.get(); P.metrics_host = e->h_metrics_dev;
+        e->n_blocks = (int)blocks;
+        if (!getenv("FTGP_NO_HOST_SUM")) {           // (diagnostic switch: the device-side hand-off of the record also with one rank)
+            HIP_TRY(host_alloc(e->h_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2 * blocks, hipHostMallocMapped));
+            HIP_TRY(hipHostGetDevicePointer((void**)&P.wg_metrics_host, e->h_wg_metrics.get(), 0));
+        }
+    }
+    HIP_TRY(dev_alloc(e->d_prog, sizeof(int32_t) * FTGP_PROGRESS_INTS * n_cars)); HIP_TRY(dev_alloc(e->d_core, sizeof(double) * kCoreDoubles * n_cars));
+    P.bits = e->d_bits.get(); P.nearbits = e->d_nearbits.get(); P.path = e->d_path.get(); P.spawn = e->d_spawn.get(); P.veh_dev = e->d_veh.get();
+    P.ray_dir = e->d_ray.get(); P.cover_thr = e->d_cover.get(); P.cars = e->d_cars.get(); P.ranges = e->d_ranges.get(); P.steps = e->d_steps.get();
+    {   // the staging image: the LDS bytes [off_params, off_cars) as every workgroup wants them, then both drivers' cover tables
+        const size_t head = (size_t)(P.off_cars - P.off_params), cover = (size_t)P.stage_cover, stride = (size_t)P.cover_kmax + 1;
+        std::vector<unsigned char> simg(head + 2 * cover, 0);
+        memcpy(simg.data(), &P, offsetof(DeviceParams, veh));      // every pointer of the head is set by now
+        memcpy(simg.data() + (P.off_veh - P.off_params), pl.veh.data(), pl.veh.size());
+        memcpy(simg.data() + (P.off_path - P.off_params), t.path, sz_path);
+        memcpy(simg.data() + (P.off_ray - P.off_params), pl.ray.data(), sizeof(float) * pl.ray.size());
+        memcpy(simg.data() + head, pl.cover.data(), sizeof(float) * stride);
+        memcpy(simg.data() + head + cover, pl.cover.data() + stride, sizeof(float) * stride);
+        HIP_TRY(dev_upload(e->d_stage, simg.data(), simg.size()));
+        P.stage_img = e->d_stage.get();
+    }
+    {   // device image of the parameter block, and behind it the sweep's task tables
+        const size_t head = (size_t)pad16(sizeof(DeviceParams));
+        std::vector<unsigned char> pimg(head + sizeof(int32_t) * pl.tasks.size() + 16, 0);
+        HIP_TRY(dev_alloc(e->d_params, pimg.size()));
+        P.task_tab = reinterpret_cast<const int32_t*>(reinterpret_cast<unsigned char*>(e->d_params.get()) + head);
+        memcpy(pimg.data(), &P, sizeof(DeviceParams));
+        memcpy(pimg.data() + head, pl.tasks.data(), sizeof(int32_t) * pl.tasks.size());
+        HIP_TRY(hipMemcpy(e->d_params.get(), pimg.data(), pimg.size(), hipMemcpyHostToDevice));
+    }
     return 0;
 }
 
@@ -446,26 +833,9 @@ int ftgp_destroy(FtgpEnv* e)
 {
     if (!e) return 0;
     (void)hipSetDevice(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    if (e->side) (void)hipStreamSynchronize(e->side);
+    if (e->stream) (void)hipStreamSynchronize(e->stream.get());
+    if (e->side) (void)hipStreamSynchronize(e->side.get());
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
-    void* bufs[] = { e->d_field, e->d_bits, e->d_nearbits, e->d_cover, e->d_stage, e->d_params, e->d_veh, e->d_path, e->d_spawn, e->d_ray, e->d_cars, e->d_ranges,
-                     e->d_steps, e->d_env_mask, e->d_car_mask, e->d_ctrl, e->d_pose, e->d_metrics, e->d_gather, e->d_prog, e->d_core, e->d_wg_metrics, e->d_wg_ticket,
-                     e->d_edt, e->d_fan };
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    if (e->h_metrics) (void)hipHostFree(e->h_metrics);
-    if (e->h_gather) (void)hipHostFree(e->h_gather);
-    if (e->h_wg_metrics) (void)hipHostFree(e->h_wg_metrics);
-    if (e->h_tables) (void)hipHostFree(e->h_tables);
-    if (e->d_prev_abs) (void)hipFree(e->d_prev_abs);
-    if (e->ev_io_in) (void)hipEventDestroy(e->ev_io_in);
-    if (e->ev_io_out) (void)hipEventDestroy(e->ev_io_out);
-    if (e->ev_gather) (void)hipEventDestroy(e->ev_gather);
-    if (e->ev_start) (void)hipEventDestroy(e->ev_start);
-    for (hipEvent_t ev : e->ev_stop) if (ev) (void)hipEventDestroy(ev);
-    if (e->ev_metrics) (void)hipEventDestroy(e->ev_metrics);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    if (e->side) (void)hipStreamDestroy(e->side);
     delete e;
     return 0;
 }
@@ -474,369 +844,23 @@ int ftgp_create(const FtgpConfig* cfg, FtgpEnv** out)
 {
     if (!cfg || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     *out = nullptr;
-    if (cfg->abi_version != FTGP_ABI_VERSION) return fail(FTGP_ERR_ARG, "abi version mismatch%s");
-    if (cfg->n_envs < 1 || cfg->cars_per_env < 1 || cfg->cars_per_env > 8 || cfg->n_rays < 1)
-        return fail(FTGP_ERR_ARG, "bad n_envs / cars_per_env / n_rays%s");
-    if (cfg->spawn_mode == 0 && (cfg->cars_per_env + 4) * 2 + 1 >= FTGP_PATH_POINTS)
-        return fail(FTGP_ERR_ARG, "too many cars for the reference spawn rule%s");
-    const FtgpTrack& t = cfg->track;
-    if (t.width < 1 || t.height < 1 || !t.bits || !t.path || t.words_per_row < (t.width + 31) / 32)
-        return fail(FTGP_ERR_ARG, "bad track%s");
-    if (t.width > 8192 || t.height > 8192) return fail(FTGP_ERR_ARG, "images above 8192 pixels are not supported%s");
-    // Direction sectors of the box field: more slope slices mean fewer march iterations and a larger field.  A large batch is bound by
-    // throughput and by what of the field its cars keep in the 4-MiB L2s (16 sectors: 32 bytes per pixel); a small one by the latency of
-    // its longest rays (64 sectors); 16384 cars (config 5) do best with 8.  Measured: profiles/round4/ab_sectors.log.  Results do not depend on the choice.
-    const long cars_total = (long)cfg->n_envs * cfg->cars_per_env;
-    int n_sectors = cars_total >= 8192 ? 8 : cars_total >= 2048 ? 16 : 64;
-    if (const char* sv = getenv("FTGP_SECTORS_RT")) { const int c = atoi(sv); if (c == 8 || c == 16 || c == 32 || c == 64) n_sectors = c; }
-    const int n_planes = n_sectors;
-    // the march addresses the field with a 32-bit byte offset
-    if ((uint64_t)ftgp_plane256(t.width, t.height) * 256u * (uint64_t)n_planes > 0xFFFFFFFFull)
-        return fail(FTGP_ERR_ARG, "track image too large: the sector box field (2 bytes per pixel and direction sector) must stay below 4 GiB%s");
-    if (cfg->env_base < 0) return fail(FTGP_ERR_ARG, "env_base < 0%s");
-    if (cfg->lidar_mode != FTGP_LIDAR_RANGEFINDER && cfg->lidar_mode != FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_ARG, "unknown lidar_mode%s");
-    if (!(cfg->dt > 0.0) || !(t.px_size_x > 0.0) || !(t.px_size_y > 0.0)) return fail(FTGP_ERR_ARG, "bad dt / pixel size%s");
-    const FtgpVehicle& v = cfg->vehicle;
-    if (!(v.contact_radius > 0.0) || !(v.mass > 0.0) || !(v.izz > 0.0) || (v.kind != FTGP_VEHICLE_MUSHR && v.kind != FTGP_VEHICLE_TRICYCLE))
-        return fail(FTGP_ERR_ARG, "bad vehicle%s");
-    if (cfg->bubble_wrap && !(v.softener_radius > 0.0)) return fail(FTGP_ERR_ARG, "bubble_wrap needs vehicle.softener_radius > 0%s");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(FTGP_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback%s");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(FTGP_ERR_ARG, "device_id out of range%s");
-
-    FtgpEnv* e = new FtgpEnv();
-    e->ext_launch = !getenv("FTGP_LAUNCH_PLAIN");
-    e->cfg = *cfg;
-    e->device = cfg->device_id;
-#define CREATE_TRY(expr)                                                                           \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            snprintf(g_err, sizeof g_err, "%s failed: %s", #expr, hipGetErrorString(e_));          \
-            ftgp_destroy(e);                                                                       \
-            return FTGP_ERR_HIP;                                                                   \
-        }                                                                                          \
-    } while (0)
-    CREATE_TRY(hipSetDevice(e->device));
+    if (int rc = validate(*cfg)) return rc;
+    if (int rc = open_device(cfg->device_id)) return rc;
     // FTGP_WAIT_SPIN=1: the host waits for a launch by spinning instead of blocking on the interrupt (hipDeviceScheduleSpin: a CPU core per
     // waiting handle for a shorter wake-up; measured: tools/launch_host.sh).  Best effort: a device that is already active keeps its flags.
     if (const char* sv = getenv("FTGP_WAIT_SPIN")) { if (atoi(sv) == 1) (void)hipSetDeviceFlags(hipDeviceScheduleSpin); (void)hipGetLastError(); }
-    CREATE_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    CREATE_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreate(&e->ev_start));
-    CREATE_TRY(hipEventCreate(&e->ev_stop[0]));
-    CREATE_TRY(hipEventCreate(&e->ev_stop[1]));
-    CREATE_TRY(hipEventCreateWithFlags(&e->ev_metrics, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&e->ev_gather, hipEventDisableTiming));
-
-    DeviceParams& P = e->P;
-    P.n_envs = cfg->n_envs; P.cars_per_env = cfg->cars_per_env; P.n_cars = cfg->n_envs * cfg->cars_per_env;
-    P.n_rays = cfg->n_rays; P.lap_target = cfg->lap_target; P.spawn_mode = cfg->spawn_mode; P.env_base = cfg->env_base;
-    P.ranges_stride = (cfg->n_rays + 31) & ~31;      // rows start on 128-B boundaries
-    P.seed = cfg->seed; P.dt = cfg->dt;
-    P.rpp = (2 * M_PI) / (double)cfg->n_rays;
-    P.two_over_rpp = (float)(2.0 / P.rpp);
-    P.bubble_wrap = cfg->bubble_wrap ? 1 : 0;        // cfg->naive_flatten: accepted, no effect on a planar model (custom.py:1338-1339)
-    P.lidar_mode = cfg->lidar_mode;
-    P.map_size = cfg->map_size > 0.0 ? cfg->map_size : 40.0;                     // 20 * scale, custom.py:1155,1382
-    P.width = t.width; P.height = t.height; P.words_per_row = t.words_per_row; P.fstride = t.width + 2;
-    P.plane256 = ftgp_plane256(t.width, t.height);
-    // a ray's sector is always found among all FTGP_SECTORS; the table says which plane serves it
-    P.n_sectors = n_sectors; P.slice_factor = FTGP_SLICE_FACTOR(FTGP_SLOPE_SLICES);
-    P.n_planes = ftgp_sector_table(P.sector_tab, n_sectors, t.width + 2, P.plane256);
-    P.px_size_x = t.px_size_x; P.px_size_y = t.px_size_y; P.origin_x = t.origin_x; P.origin_y = t.origin_y;
-    P.inv_px_x = 1.0 / t.px_size_x; P.inv_px_y = 1.0 / t.px_size_y;
-    P.inv_px_x_f = (float)P.inv_px_x; P.inv_px_y_f = (float)P.inv_px_y;
-    P.veh = cfg->vehicle;
-    {   // static wheel loads from the wheelbase split
-        const double wtot = v.mass * v.gravity;
-        if (v.kind == FTGP_VEHICLE_TRICYCLE) {       // two driven wheels behind the origin, the caster (wheel 2) in front
-            const double a_f = v.wheel_x[2], a_r = -0.5 * (v.wheel_x[0] + v.wheel_x[1]);
-            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_f / (a_f + a_r)));
-            P.wheel_load[2] = wtot * (a_r / (a_f + a_r)); P.wheel_load[3] = 0.0;
-        } else {
-            const double a_f = 0.5 * (v.wheel_x[0] + v.wheel_x[1]), a_r = -0.5 * (v.wheel_x[2] + v.wheel_x[3]);
-            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_r / (a_f + a_r)));
-            P.wheel_load[2] = P.wheel_load[3] = 0.5 * (wtot * (a_f / (a_f + a_r)));
-        }
-    }
-    e->multi = cfg->cars_per_env > 1;
-    {   // chessboard reach of the largest wall-contact window
-        const double rmax = std::max(v.contact_radius, cfg->bubble_wrap ? v.softener_radius : 0.0);
-        P.contact_reach = std::max((int)ceil(rmax * P.inv_px_x), (int)ceil(rmax * P.inv_px_y));
-    }
-    P.eighth = (int)((double)cfg->n_rays / 8.0);                    // nidc.py:18
-    {   // the largest cover count any positive sample can produce (that of the smallest positive float), over both drivers
-        const double rpp = (2 * M_PI) / (double)cfg->n_rays;
-        const float tiny = 1.401298464e-45f;
-        P.cover_kmax = std::max(1, std::max(cover_count_host(0.24, rpp, (double)tiny), cover_count_host(0.12, rpp, (double)tiny)));
-    }
-    P.win_floats = ((P.eighth & 3) + (cfg->n_rays - 2 * P.eighth) + 1 + 3) & ~3;       // window at float (eighth % 4), ranges[0] in the last float
-    P.snap_eps = ftgp_snap_eps(t.width, t.height);
-    { hipDeviceProp_t prop; CREATE_TRY(hipGetDeviceProperties(&prop, e->device)); P.n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; }
-    P.edge_margin = (float)(v.lidar_ring_radius * std::max(P.inv_px_x, P.inv_px_y) * 1.001 + 2.0);
-    if ((cfg->n_rays + FTGP_WAVE - 1) / FTGP_WAVE > FTGP_MAX_GROUPS) { ftgp_destroy(e); return fail(FTGP_ERR_ARG, "n_rays above 16384 is not supported%s"); }
-
-    // workgroup shape: whole envs, at most 16 cars (K1 / K3 run on the lanes of one wave), two workgroups per CU
-    // (<= 80 KiB of LDS each) so that 8 waves per SIMD hide the latency of the field loads
-    {
-        const int unit = cfg->cars_per_env;
-        int wpb = 16;
-        if (const char* sv = getenv("FTGP_WAVES_PER_BLOCK")) { const int c = atoi(sv); if (c >= 1 && c <= 16) wpb = c; }
-        int want = (FTGP_MAX_CARS_PER_BLOCK / unit) * unit;
-        // small batches: fewer cars per workgroup so that every CU gets work.  Up to four envs per CU a batch runs best as ONE workgroup per CU
-        // (its step is the driver -> dynamics latency chain plus one sweep task per wave: a second workgroup on the CU only competes for issue
-        // slots -- 1024 envs: 9.1 us per step with 256 workgroups of 4, 9.8 with 512 of 2; 512 envs: 8.8 / 9.0); larger batches take two
-        // workgroups per CU (1536 envs: 10.7 us with 512 workgroups of 3, 13.9 with 256 of 6) -- profiles/round5/config2_shapes.log
-        const int n_units = P.n_cars / unit;
-        const int n_cu = P.n_cu > 0 ? P.n_cu : 256;
-        const int per_cu = (n_units + n_cu - 1) / n_cu;
-        const int spread = (per_cu <= 4 ? std::max(1, per_cu) : std::max(1, n_units / (2 * n_cu))) * unit;
-        int cpb = std::min(want, spread);
-        if (const char* sv = getenv("FTGP_CARS_PER_BLOCK")) { const int c = atoi(sv); if (c >= unit && c <= FTGP_MAX_CARS_PER_BLOCK) cpb = (c / unit) * unit; }
-        int lds_cap = 80 * 1024;
-        if (const char* sv = getenv("FTGP_LDS_CAP_KB")) { const int c = atoi(sv); if (c >= 16 && c <= 160) lds_cap = c * 1024; }
-        while (cpb > unit && lds_layout(P, cpb, wpb) > lds_cap) cpb -= unit;
-        if (lds_layout(P, cpb, wpb) > 160 * 1024) {
-            snprintf(g_err, sizeof g_err, "one env of %d car(s) with a %d-ray scan does not fit the 160 KiB LDS", unit, P.n_rays);
-            ftgp_destroy(e);
-            return FTGP_ERR_ARG;
-        }
-        if (getenv("FTGP_VERBOSE"))
-            fprintf(stderr, "ftgp_create: %d cars x %d waves per workgroup, %d B of LDS (cap %d)\n", cpb, wpb, lds_layout(P, cpb, wpb), lds_cap);
-    }
-#define FTGP_BIG_LDS(M, F, R) CREATE_TRY(hipFuncSetAttribute((const void*)ftgp_step_kernel<M, F, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-    FTGP_BIG_LDS(false, false, false); FTGP_BIG_LDS(true, false, false); FTGP_BIG_LDS(false, false, true); FTGP_BIG_LDS(true, false, true);
-    FTGP_BIG_LDS(false, true, true); FTGP_BIG_LDS(true, true, true);
-#undef FTGP_BIG_LDS
-
-    // host-side tables
-    HostTables tab;
-    build_tables(t, P.contact_reach, tab);
-    std::vector<float> ray(2 * (size_t)cfg->n_rays + 4, 0.0f);
-    std::vector<double> fan(2 * (size_t)cfg->n_rays, 0.0);
-    for (int j = 0; j < cfg->n_rays; ++j) {
-        // mushr.em.xml:112-117: phi_j = radians(360/R*j - 90); the ray (+z of the site) is (sin phi, -cos phi, 0)
-        const double phi = ((360.0 / (double)cfg->n_rays) * (double)j - 90.0) * (M_PI / 180.0);
-        fan[2 * (size_t)j] = cfg->fan_dirs ? cfg->fan_dirs[2 * (size_t)j] : sin(phi);
-        fan[2 * (size_t)j + 1] = cfg->fan_dirs ? cfg->fan_dirs[2 * (size_t)j + 1] : -cos(phi);
-        ray[2 * (size_t)j] = (float)fan[2 * (size_t)j]; ray[2 * (size_t)j + 1] = (float)fan[2 * (size_t)j + 1];
-        // The rangefinders' own fan is point-symmetric: site j + n/2 looks exactly opposite to site j.  The BINARY32 table says so to the last
-        // bit (its second half is the negated first half -- the roundings of libm's sin / cos of phi + pi need not be), which is what lets the
-        // sweep derive a ray from its opposite; a caller's fan_dirs is taken as it comes.  The binary64 fan of FAKELIDAR mode is libm's value
-        // for every site, as include/ftgp.h says for fan_dirs == NULL (round 4 negated it too: a last-bit difference from the documented fan).
-        if (!cfg->fan_dirs && cfg->n_rays % 2 == 0 && j >= cfg->n_rays / 2) {
-            ray[2 * (size_t)j] = -ray[2 * (size_t)(j - cfg->n_rays / 2)]; ray[2 * (size_t)j + 1] = -ray[2 * (size_t)(j - cfg->n_rays / 2) + 1];
-        }
-    }
-    {   // the sweep's work list (lidar_groups): draw g -> (kidx = g / cars_per_block, car slot = g % cars_per_block), task = group_order[kidx]
-        const int R = cfg->n_rays, halfR = R / 2;
-        bool sym = R % 2 == 0 && !getenv("FTGP_NO_PAIRS");
-        for (int j = 0; sym && j < halfR; ++j)
-            sym = ray[2 * (size_t)(j + halfR)] == -ray[2 * (size_t)j] && ray[2 * (size_t)(j + halfR) + 1] == -ray[2 * (size_t)j + 1] &&
-                  std::signbit(ray[2 * (size_t)(j + halfR)]) != std::signbit(ray[2 * (size_t)j]) && std::signbit(ray[2 * (size_t)(j + halfR) + 1]) != std::signbit(ray[2 * (size_t)j + 1]);
-        std::vector<int> tasks;
-        if (!sym) for (int j0 = 0; j0 < R; j0 += FTGP_WAVE) tasks.push_back(j0);
-        else {
-            int j0 = 0;
-            for (; j0 + FTGP_WAVE <= halfR; j0 += FTGP_WAVE) tasks.push_back(j0 | (1 << 16));
-            if (j0 < halfR) tasks.push_back(j0 | ((halfR - j0 <= FTGP_WAVE / 2 ? 2 : 1) << 16));
-        }
-        P.tasks_per_car = (int)tasks.size();
-        // expected march length of a task ~ how far its rays look along the car's axis: |cos| of the angle between the group's middle ray
-        // and the axis (ray 0 looks backwards, ray n/2 ahead); ties keep index order
-        std::vector<std::pair<double, int>> key;
-        for (int t : tasks) {
-            const double mid = std::min((double)R - 1.0, (double)(t & 0xffff) + 31.5);
-            key.push_back({ getenv("FTGP_GROUP_ORDER_PLAIN") ? 0.0 : -fabs(cos(2.0 * M_PI * mid / (double)R)), t });
-        }
-        std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
-        // the cheapest pairs -- the last tasks a sweep draws -- go out as two single groups each: the waves then end a sweep within ONE short
-        // group of each other, not within two (the set-up shared inside a pair is worth less than that at the very end)
-        int tail = 2;
-        if (const char* sv = getenv("FTGP_PAIR_TAIL")) tail = atoi(sv);
-        std::vector<int> order;
-        for (size_t k = 0; k < key.size(); ++k) {
-            const int t = key[k].second;
-            if ((t >> 16) == 1 && (int)(key.size() - k) <= tail) { order.push_back(t & 0xffff); order.push_back((t & 0xffff) + halfR); }
-            else order.push_back(t);
-        }
-        P.tasks_per_car = (int)order.size();
-        for (size_t k = 0; k < order.size(); ++k) P.group_order[k] = order[k];
-        // mate_masks(): a ray of a group lies within 32 spacings of the rangefinders' uniform fan of the group's middle ray; + 1.2 degrees for the
-        // slack in the rays' own test (acos 0.9999 = 0.81 degrees) and rounding.  A caller's fan has no such bound: every mate is looked at.
-        const double gamma = 32.0 * (2.0 * M_PI / (double)R) + 0.021;
-        if (cfg->fan_dirs || gamma >= 1.5) { P.group_cg = -2.0f; P.group_sg = 0.0f; }
-        else { P.group_cg = (float)cos(gamma); P.group_sg = (float)sin(gamma); }
-        if (getenv("FTGP_VERBOSE")) fprintf(stderr, "ftgp_create: %d sweep tasks per car (%s)\n", P.tasks_per_car, sym ? "pairs of opposite ray groups" : "single groups");
-    }
-    std::vector<double> spawn(4 * FTGP_PATH_POINTS);
-    for (int p = 0; p < FTGP_PATH_POINTS; ++p) {
-        // position_vehicles (custom.py:1240-1245) + euler_to_quaternion([angle, 0, 0]) (custom.py:81-87)
-        const int p1 = (p + 1) % FTGP_PATH_POINTS;
-        const double ang = atan2(t.path[2 * p1 + 1] - t.path[2 * p + 1], t.path[2 * p1] - t.path[2 * p]);
-        spawn[4 * p] = t.path[2 * p]; spawn[4 * p + 1] = t.path[2 * p + 1];
-        spawn[4 * p + 2] = cos(ang / 2); spawn[4 * p + 3] = sin(ang / 2);
-    }
-
-    if (cfg->lidar_mode == FTGP_LIDAR_FAKELIDAR) {
-        // The distance transform of custom.py:1149-1153 / raycast.py:24-27 (scipy.ndimage.distance_transform_edt of the non-wall
-        // mask) without scipy, exact: the squared distance is the minimum over the columns x' of (x - x')^2 + g(x', y)^2 with g the
-        // vertical distance to the nearest wall of column x' -- the run lengths above -- in integers; one correctly rounded sqrt.
-        const size_t plane = (size_t)t.width * t.height;
-        uint16_t* d_runy = nullptr;
-        CREATE_TRY(hipMalloc(&d_runy, 2 * plane * sizeof(uint16_t)));
-        CREATE_TRY(hipMalloc(&e->d_edt, plane * sizeof(double)));
-        CREATE_TRY(hipMalloc(&e->d_fan, fan.size() * sizeof(double)));
-        CREATE_TRY(hipMemcpy(d_runy, tab.runy.data(), 2 * plane * sizeof(uint16_t), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMemcpy(e->d_fan, fan.data(), fan.size() * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(ftgp_edt_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, e->stream, d_runy, t.width, t.height, e->d_edt);
-        CREATE_TRY(hipGetLastError());
-        CREATE_TRY(hipStreamSynchronize(e->stream));
-        (void)hipFree(d_runy);
-        P.edt = e->d_edt; P.fan_dirs = e->d_fan;
-    } else {   // sector box field: upload the run lengths, search the boxes on the device
-        const size_t plane = (size_t)t.width * t.height;
-        const size_t plane_cells = (size_t)P.plane256 * 128;
-        const size_t cells = plane_cells * (size_t)P.n_planes;
-        uint16_t* d_runx = nullptr; uint16_t* d_runy = nullptr;
-        CREATE_TRY(hipMalloc(&e->d_field, cells * sizeof(uint16_t)));
-        CREATE_TRY(hipMalloc(&d_runx, 2 * plane * sizeof(uint16_t)));
-        CREATE_TRY(hipMalloc(&d_runy, 2 * plane * sizeof(uint16_t)));
-        CREATE_TRY(hipMemcpy(d_runx, tab.runx.data(), 2 * plane * sizeof(uint16_t), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMemcpy(d_runy, tab.runy.data(), 2 * plane * sizeof(uint16_t), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(ftgp_box_field_kernel, dim3((unsigned)((plane_cells * (size_t)P.n_sectors + 255) / 256)), dim3(256), 0, e->stream, d_runx, d_runy, t.width, t.height, P.n_sectors, e->d_field);
-        CREATE_TRY(hipGetLastError());
-        CREATE_TRY(hipStreamSynchronize(e->stream));
-        (void)hipFree(d_runx); (void)hipFree(d_runy);
-        P.field = e->d_field;
-    }
-    {
-        std::vector<unsigned char> vimg((size_t)pad16(sizeof(VehLds)), 0);
-        VehLds vl; memset(&vl, 0, sizeof vl);
-        vl.v = P.veh; for (int i = 0; i < 4; ++i) vl.wheel_load[i] = P.wheel_load[i];
-        // every part of a car that a ray can see (chassis box, LiDAR puck) lies within rmax of the car's origin; 10 % margin
-        const double cx = std::max(fabs(v.box_xmin), fabs(v.box_xmax)), cy = std::max(fabs(v.box_ymin), fabs(v.box_ymax));
-        const double rmax = std::max(sqrt(cx * cx + cy * cy), sqrt(v.lidar_x * v.lidar_x + v.lidar_y * v.lidar_y) + v.lidar_ring_radius);
-        vl.cull_radius = (float)(1.1 * rmax);
-        {   // the puck inside the box with at least 1e-3 to spare on every side (MuSHR: 0.016, tricycle: 0.0175): coordinates in a mate's frame are below the
-            // map's 40 units, so binary32 rounding of the two tests is below 1e-5 -- the circle can never come out ahead of the box
-            const double m = 1e-3, r = v.lidar_ring_radius;
-            vl.puck_in_box = (v.lidar_x - r >= v.box_xmin + m && v.lidar_x + r <= v.box_xmax - m && v.lidar_y - r >= v.box_ymin + m && v.lidar_y + r <= v.box_ymax - m &&
-                              !getenv("FTGP_PUCK_TEST")) ? 1 : 0;
-        }
-        vl.box_xmin_f = (float)v.box_xmin; vl.box_xmax_f = (float)v.box_xmax; vl.box_ymin_f = (float)v.box_ymin; vl.box_ymax_f = (float)v.box_ymax;
-        vl.lidar_x_f = (float)v.lidar_x; vl.lidar_y_f = (float)v.lidar_y; vl.ring_radius_f = (float)v.lidar_ring_radius;
-        memcpy(vimg.data(), &vl, sizeof vl);
-        CREATE_TRY(hipMalloc(&e->d_veh, vimg.size()));
-        CREATE_TRY(hipMemcpy(e->d_veh, vimg.data(), vimg.size(), hipMemcpyHostToDevice));
-        P.veh_dev = e->d_veh;
-    }
-    const size_t sz_bits = sizeof(uint32_t) * (size_t)t.height * t.words_per_row;
-    const size_t sz_path = (size_t)pad16(sizeof(double) * 2 * FTGP_PATH_POINTS), sz_ray = (size_t)pad16(sizeof(float) * 2 * (size_t)cfg->n_rays);
-    const size_t n_cars = (size_t)P.n_cars;
-    CREATE_TRY(hipMalloc(&e->d_bits, sz_bits));
-    CREATE_TRY(hipMalloc(&e->d_nearbits, sz_bits));
-    CREATE_TRY(hipMalloc(&e->d_path, sz_path));
-    CREATE_TRY(hipMalloc(&e->d_ray, sz_ray));
-    CREATE_TRY(hipMalloc(&e->d_spawn, sizeof(double) * 4 * FTGP_PATH_POINTS));
-    {   // cover-count thresholds: nidc (car_width 0.12, nidc.py:5) then fast (0.06, fast.py:4), each padded to the staged size
-        const size_t stride = (size_t)P.cover_kmax + 1, padded = (size_t)pad16(sizeof(float) * stride) / sizeof(float);
-        std::vector<float> thr(stride + padded + 4, 0.0f);
-        build_cover_table(0.12, cfg->n_rays, P.cover_kmax, thr.data());
-        build_cover_table(0.06, cfg->n_rays, P.cover_kmax, thr.data() + stride);
-        CREATE_TRY(hipMalloc(&e->d_cover, sizeof(float) * thr.size()));
-        CREATE_TRY(hipMemcpy(e->d_cover, thr.data(), sizeof(float) * thr.size(), hipMemcpyHostToDevice));
-        P.cover_thr = e->d_cover;
-    }
-    CREATE_TRY(hipMalloc(&e->d_cars, sizeof(CarState) * n_cars));
-    CREATE_TRY(hipMalloc(&e->d_ranges, sizeof(float) * n_cars * P.ranges_stride));
-    CREATE_TRY(hipMalloc(&e->d_steps, sizeof(int64_t) * (size_t)P.n_envs));
-    CREATE_TRY(hipMalloc(&e->d_env_mask, (size_t)P.n_envs));
-    CREATE_TRY(hipMalloc(&e->d_car_mask, n_cars));
-    CREATE_TRY(hipMalloc(&e->d_ctrl, sizeof(double) * 2 * n_cars));
-    CREATE_TRY(hipMalloc(&e->d_pose, sizeof(double) * FTGP_POSE_DOUBLES * n_cars));
-    CREATE_TRY(hipMalloc(&e->d_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2));
-    CREATE_TRY(hipHostMalloc(&e->h_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2, hipHostMallocMapped));
-    CREATE_TRY(hipHostGetDevicePointer((void**)&e->h_metrics_dev, e->h_metrics, 0));
-    if (!getenv("FTGP_NO_FUSED_METRICS")) {          // (diagnostic switch: tests compare the fused record with ftgp_metrics_kernel's)
-        const size_t blocks = (n_cars + (size_t)P.cars_per_block - 1) / (size_t)P.cars_per_block;
-        CREATE_TRY(hipMalloc(&e->d_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * blocks));
-        CREATE_TRY(hipMalloc(&e->d_wg_ticket, sizeof(unsigned int)));
-        CREATE_TRY(hipMemsetAsync(e->d_wg_ticket, 0, sizeof(unsigned int), e->stream));
-        P.wg_metrics = e->d_wg_metrics; P.wg_ticket = e->d_wg_ticket; P.metrics_dev = e->d_metrics; P.metrics_host = e->h_metrics_dev;
-        e->n_blocks = (int)blocks;
-        if (!getenv("FTGP_NO_HOST_SUM")) {           // (diagnostic switch: the device-side hand-off of the record also with one rank)
-            CREATE_TRY(hipHostMalloc(&e->h_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2 * blocks, hipHostMallocMapped));
-            CREATE_TRY(hipHostGetDevicePointer((void**)&P.wg_metrics_host, e->h_wg_metrics, 0));
-        }
-    }
-    CREATE_TRY(hipMalloc(&e->d_prog, sizeof(int32_t) * FTGP_PROGRESS_INTS * n_cars));
-    CREATE_TRY(hipMalloc(&e->d_core, sizeof(double) * kCoreDoubles * n_cars));
-    CREATE_TRY(hipMemcpy(e->d_bits, tab.bits.data(), sz_bits, hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(e->d_nearbits, tab.nearbits.data(), sz_bits, hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemsetAsync(e->d_path, 0, sz_path, e->stream));
-    CREATE_TRY(hipStreamSynchronize(e->stream));
-    CREATE_TRY(hipMemcpy(e->d_path, t.path, sizeof(double) * 2 * FTGP_PATH_POINTS, hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(e->d_spawn, spawn.data(), sizeof(double) * spawn.size(), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemsetAsync(e->d_ray, 0, sz_ray, e->stream));
-    CREATE_TRY(hipStreamSynchronize(e->stream));
-    CREATE_TRY(hipMemcpy(e->d_ray, ray.data(), sizeof(float) * 2 * (size_t)cfg->n_rays, hipMemcpyHostToDevice));
-    // on the handle's own stream: a non-blocking stream is not ordered against the null stream, and ftgp_reset() below runs on it
-    CREATE_TRY(hipMemsetAsync(e->d_cars, 0, sizeof(CarState) * n_cars, e->stream));
-    CREATE_TRY(hipMemsetAsync(e->d_ranges, 0, sizeof(float) * n_cars * P.ranges_stride, e->stream));
-    CREATE_TRY(hipMemsetAsync(e->d_steps, 0, sizeof(int64_t) * (size_t)P.n_envs, e->stream));
-    P.bits = e->d_bits; P.nearbits = e->d_nearbits; P.path = e->d_path; P.spawn = e->d_spawn;
-    P.ray_dir = e->d_ray; P.cars = e->d_cars; P.ranges = e->d_ranges; P.steps = e->d_steps;
-    {   // the staging image: the LDS bytes [off_params, off_cars) as every workgroup wants them, then both drivers' cover tables
-        const size_t head = (size_t)(P.off_cars - P.off_params), cover = (size_t)P.stage_cover;
-        std::vector<unsigned char> simg(head + 2 * cover, 0);
-        CREATE_TRY(hipMalloc(&e->d_stage, simg.size()));
-        P.stage_img = e->d_stage;
-        memcpy(simg.data() + (P.off_params - P.off_params), &P, offsetof(DeviceParams, veh));
-        CREATE_TRY(hipMemcpy(simg.data() + (P.off_veh - P.off_params), e->d_veh, (size_t)pad16(sizeof(VehLds)), hipMemcpyDeviceToHost));
-        memcpy(simg.data() + (P.off_path - P.off_params), t.path, sizeof(double) * 2 * FTGP_PATH_POINTS);
-        memcpy(simg.data() + (P.off_ray - P.off_params), ray.data(), sizeof(float) * 2 * (size_t)cfg->n_rays);
-        const size_t stride = (size_t)P.cover_kmax + 1;
-        CREATE_TRY(hipMemcpy(simg.data() + head, e->d_cover, std::min(cover, sizeof(float) * stride), hipMemcpyDeviceToHost));
-        CREATE_TRY(hipMemcpy(simg.data() + head + cover, e->d_cover + stride, std::min(cover, sizeof(float) * stride), hipMemcpyDeviceToHost));
-        CREATE_TRY(hipMemcpy(e->d_stage, simg.data(), simg.size(), hipMemcpyHostToDevice));
-    }
-    {   // device image of the parameter block, and behind it the sweep's task table (DeviceParams::task_tab): draw g is task g / cars_per_block of
-        // car slot g % cars_per_block, with everything the draw and the delivery need precomputed
-        const size_t head = (size_t)pad16(sizeof(DeviceParams));
-        const int cpb = P.cars_per_block, ntasks = cpb * P.tasks_per_car, R = P.n_rays, halfR = R / 2;
-        if (P.tasks_per_car > 256 || R > 0x4000) { ftgp_destroy(e); return fail(FTGP_ERR_ARG, "internal: the task table's fields are too narrow for this fan%s"); }
-        std::vector<int32_t> tt(2 * 4 * (size_t)ntasks, 0);
-        auto wclass = [&](int first, int lim) {          // rays first .. min(first + 63, lim - 1) against the window [eighth, R - eighth)
-            const int last = std::min(first + FTGP_WAVE, lim) - 1, lo = P.eighth, hi = R - P.eighth;
-            if (last < lo || first >= hi || lo >= hi) return 0;
-            return (first >= lo && last < hi) ? 1 : 2;
-        };
-        for (int g = 0; g < ntasks; ++g) {
-            const int kidx = g / cpb, c = g % cpb, ent = P.group_order[kidx], j0 = ent & 0xffff, kind = ent >> 16;
-            const int w0 = kind == 2 ? 2 : wclass(j0, kind == 1 ? halfR : R), w1 = kind == 1 ? wclass(j0 + halfR, R) : 0;
-            const uint32_t plain = (uint32_t)j0 | (uint32_t)kind << 14 | (uint32_t)c << 16;
-            int32_t* a = &tt[4 * (size_t)g];
-            int32_t* b = &tt[4 * (size_t)(ntasks + g)];
-            a[0] = (int32_t)(plain | (uint32_t)w0 << 20 | (uint32_t)w1 << 22 | (uint32_t)(j0 == 0 ? 1 : 0) << 24);
-            b[0] = (int32_t)plain;
-            a[1] = b[1] = c * (int)sizeof(LidarFrame) | kidx << 16;
-            a[2] = b[2] = c * P.ranges_stride * 4;
-            a[3] = b[3] = 4 * (c * P.win_floats + (P.eighth & 3) - P.eighth);
-        }
-        std::vector<unsigned char> pimg(head + sizeof(int32_t) * tt.size() + 16, 0);
-        CREATE_TRY(hipMalloc(&e->d_params, pimg.size()));
-        P.task_tab = reinterpret_cast<const int32_t*>(reinterpret_cast<unsigned char*>(e->d_params) + head);
-        memcpy(pimg.data(), &P, sizeof(DeviceParams));
-        memcpy(pimg.data() + head, tt.data(), sizeof(int32_t) * tt.size());
-        CREATE_TRY(hipMemcpy(e->d_params, pimg.data(), pimg.size(), hipMemcpyHostToDevice));
-    }
-#undef CREATE_TRY
-    int rc = ftgp_reset(e, nullptr);
-    if (rc != 0) { ftgp_destroy(e); return rc; }
-    *out = e;
+    hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, cfg->device_id));
+    Plan pl;
+    if (int rc = plan_create(*cfg, prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, pl)) return rc;
+    std::unique_ptr<FtgpEnv, int (*)(FtgpEnv*)> e(new FtgpEnv(), ftgp_destroy);
+    e->device = cfg->device_id; e->multi = cfg->cars_per_env > 1; e->ext_launch = !getenv("FTGP_LAUNCH_PLAIN");
+    HIP_TRY(make_stream(e->stream)); HIP_TRY(make_stream(e->side));
+    HIP_TRY(make_event(e->ev_start, hipEventDefault)); HIP_TRY(make_event(e->ev_stop[0], hipEventDefault)); HIP_TRY(make_event(e->ev_stop[1], hipEventDefault));
+    HIP_TRY(make_event(e->ev_metrics, hipEventDisableTiming)); HIP_TRY(make_event(e->ev_gather, hipEventDisableTiming));
+    for (const auto& row : kStepKernels) for (const StepKernel& k : row) HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (int rc = upload(e.get(), cfg->track, pl)) return rc;
+    if (int rc = ftgp_reset(e.get(), nullptr)) return rc;
+    *out = e.release();
     return 0;
 }
 
@@ -847,14 +871,14 @@ int ftgp_reset(FtgpEnv* e, const uint8_t* mask)
     HIP_TRY(hipSetDevice(e->device));
     const uint8_t* dmask = nullptr;
     if (mask) {
-        HIP_TRY(hipMemcpyAsync(e->d_env_mask, mask, (size_t)e->P.n_envs, hipMemcpyHostToDevice, e->stream));
-        dmask = e->d_env_mask;
+        HIP_TRY(hipMemcpyAsync(e->d_env_mask.get(), mask, (size_t)e->P.n_envs, hipMemcpyHostToDevice, e->stream.get()));
+        dmask = e->d_env_mask.get();
     }
-    hipLaunchKernelGGL(ftgp_reset_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream, e->P, dmask);
+    hipLaunchKernelGGL(ftgp_reset_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P, dmask);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ftgp_zero_ranges_kernel, dim3(e->P.n_cars), dim3(256), 0, e->stream, e->P, dmask);
+    hipLaunchKernelGGL(ftgp_zero_ranges_kernel, dim3(e->P.n_cars), dim3(256), 0, e->stream.get(), e->P, dmask);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 
@@ -863,15 +887,15 @@ int ftgp_set_ctrl(FtgpEnv* e, const double* ctrl, const uint8_t* car_mask)
     if (!e || !ctrl) return fail(FTGP_ERR_ARG, "null argument%s");
     e->rows_valid = false;
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(e->d_ctrl, ctrl, sizeof(double) * 2 * (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_ctrl.get(), ctrl, sizeof(double) * 2 * (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream.get()));
     const uint8_t* dmask = nullptr;
     if (car_mask) {
-        HIP_TRY(hipMemcpyAsync(e->d_car_mask, car_mask, (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream));
-        dmask = e->d_car_mask;
+        HIP_TRY(hipMemcpyAsync(e->d_car_mask.get(), car_mask, (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream.get()));
+        dmask = e->d_car_mask.get();
     }
-    hipLaunchKernelGGL(ftgp_set_ctrl_kernel, dim3((e->P.n_cars + 255) / 256), dim3(256), 0, e->stream, e->P, e->d_ctrl, dmask);
+    hipLaunchKernelGGL(ftgp_set_ctrl_kernel, dim3((e->P.n_cars + 255) / 256), dim3(256), 0, e->stream.get(), e->P, e->d_ctrl.get(), dmask);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));   // the caller's buffers may be reused as soon as we return
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));   // the caller's buffers may be reused as soon as we return
     return 0;
 }
 
@@ -896,9 +920,9 @@ int ftgp_set_car_policies(FtgpEnv* e, const int32_t* policies)
     // a workgroup holds whole envs, so its car slot c runs the roster's entry c % cars_per_env
     for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->P.car_policy[c] = policies[c % e->P.cars_per_env];
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));           // no launch is reading the block while it changes
-    HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(e->d_params) + offsetof(DeviceParams, car_policy), e->P.car_policy, sizeof e->P.car_policy, hipMemcpyHostToDevice));
-    if (e->h_tables) memcpy(e->h_tables, e->P.car_policy, sizeof e->P.car_policy);    // (no copy from it is pending: the stream is idle)
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the block while it changes
+    HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(e->d_params.get()) + offsetof(DeviceParams, car_policy), e->P.car_policy, sizeof e->P.car_policy, hipMemcpyHostToDevice));
+    if (e->h_tables) memcpy(e->h_tables.get(), e->P.car_policy, sizeof e->P.car_policy);    // (no copy from it is pending: the stream is idle)
     e->table_on_device = 0;
     return 0;
 }
@@ -917,26 +941,25 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
         disparity = disparity || slot[k] == FTGP_POLICY_NIDC || slot[k] == FTGP_POLICY_FAST;
     }
     if (n_ext == 0) return fail(FTGP_ERR_ARG, "device_io_config: at least one slot must be external (FTGP_POLICY_HOST)%s");
-    if (disparity && e->P.n_rays < 8) return fail(FTGP_ERR_ARG, "nidc/fast need n_rays >= 8%s");
-    if (disparity && e->P.n_rays - 2 * e->P.eighth > FTGP_WAVE * FTGP_WAVE) return fail(FTGP_ERR_ARG, "the device drivers handle at most 4096 samples in the front window%s");
+    if (disparity) if (int rc = check_disparity_shape(e->P)) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));           // no copy from the pinned tables is pending while they change
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no copy from the pinned tables is pending while they change
     if (!e->h_tables) {
-        HIP_TRY(hipHostMalloc(&e->h_tables, sizeof(int32_t) * 2 * FTGP_MAX_CARS_PER_BLOCK, hipHostMallocDefault));
-        memcpy(e->h_tables, e->P.car_policy, sizeof e->P.car_policy);
+        HIP_TRY(host_alloc(e->h_tables, sizeof(int32_t) * 2 * FTGP_MAX_CARS_PER_BLOCK, hipHostMallocDefault));
+        memcpy(e->h_tables.get(), e->P.car_policy, sizeof e->P.car_policy);
         e->table_on_device = 0;
     }
-    if (!e->d_prev_abs) HIP_TRY(hipMalloc(&e->d_prev_abs, sizeof(int32_t) * (size_t)e->P.n_cars));
-    if (!e->ev_io_in) HIP_TRY(hipEventCreateWithFlags(&e->ev_io_in, hipEventDisableTiming));
-    if (!e->ev_io_out) HIP_TRY(hipEventCreateWithFlags(&e->ev_io_out, hipEventDisableTiming));
+    if (!e->d_prev_abs) HIP_TRY(dev_alloc(e->d_prev_abs, sizeof(int32_t) * (size_t)e->P.n_cars));
+    if (!e->ev_io_in) HIP_TRY(make_event(e->ev_io_in, hipEventDisableTiming));
+    if (!e->ev_io_out) HIP_TRY(make_event(e->ev_io_out, hipEventDisableTiming));
     // a workgroup holds whole envs, so its car slot c runs entry c % cars_per_env (as ftgp_set_car_policies)
-    for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->h_tables[FTGP_MAX_CARS_PER_BLOCK + c] = slot[c % cpe];
+    for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->h_tables.get()[FTGP_MAX_CARS_PER_BLOCK + c] = slot[c % cpe];
     if (e->table_on_device == 1) e->table_on_device = -1;
     DeviceIoArgs& A = e->io;
     A = DeviceIoArgs{};
     A.max_episode_steps = cfg->max_episode_steps; A.n_ext = n_ext; A.auto_reset = cfg->auto_reset ? 1 : 0;
     for (int k = 0, i = 0; k < FTGP_PAIR_STRIDE; ++k) A.ext_index[k] = (k < cpe && slot[k] == FTGP_POLICY_HOST) ? i++ : -1;
-    A.prev_abs = e->d_prev_abs;
+    A.prev_abs = e->d_prev_abs.get();
     e->io_repeat = cfg->action_repeat;
     e->io_ready = true;
     return 0;
@@ -958,18 +981,18 @@ int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io)
     A.action = io->action; A.obs = io->obs; A.reward = io->reward; A.terminated = io->terminated; A.truncated = io->truncated; A.final_obs = io->final_obs;
     A.vec4 = e->P.n_rays % 4 == 0 && (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
     hipStream_t caller = (hipStream_t)io->stream;
-    HIP_TRY(hipEventRecord(e->ev_io_in, caller));
-    HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_io_in, 0));
+    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
+    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
     const unsigned car_blocks = (unsigned)((e->P.n_cars + 255) / 256);
-    hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream, e->P, A);
+    hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
     if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, e->io_repeat, true)) return rc;
-    hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream, e->P, A);
+    hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
     e->rows_valid = false;
     if (A.auto_reset) e->launch_metrics_valid = false;     // the launch's record describes the state before the resets
-    HIP_TRY(hipEventRecord(e->ev_io_out, e->stream));
-    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out, 0));
+    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
+    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
     return 0;
 }
 
@@ -977,9 +1000,9 @@ int ftgp_get_lidar(FtgpEnv* e, float* out)
 {
     if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpy2DAsync(out, sizeof(float) * (size_t)e->P.n_rays, e->d_ranges, sizeof(float) * (size_t)e->P.ranges_stride,
-                             sizeof(float) * (size_t)e->P.n_rays, (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy2DAsync(out, sizeof(float) * (size_t)e->P.n_rays, e->d_ranges.get(), sizeof(float) * (size_t)e->P.ranges_stride,
+                             sizeof(float) * (size_t)e->P.n_rays, (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 
@@ -1022,10 +1045,10 @@ int ftgp_set_pose(FtgpEnv* e, const double* pose)
     if (!e || !pose) return fail(FTGP_ERR_ARG, "null argument%s");
     e->rows_valid = false; e->launch_metrics_valid = false;
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(e->d_pose, pose, sizeof(double) * FTGP_POSE_DOUBLES * (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(ftgp_set_pose_kernel, dim3((e->P.n_cars + 255) / 256), dim3(256), 0, e->stream, e->P, e->d_pose);
+    HIP_TRY(hipMemcpyAsync(e->d_pose.get(), pose, sizeof(double) * FTGP_POSE_DOUBLES * (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream.get()));
+    hipLaunchKernelGGL(ftgp_set_pose_kernel, dim3((e->P.n_cars + 255) / 256), dim3(256), 0, e->stream.get(), e->P, e->d_pose.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 
@@ -1035,19 +1058,16 @@ int ftgp_policy_eval(FtgpEnv* e, int policy, const float* ranges, double* ctrl_o
     e->rows_valid = false;
     if (policy < FTGP_POLICY_LOBOTOMY || policy > FTGP_POLICY_PER_CAR) return fail(FTGP_ERR_ARG, "policy_eval: device policies only%s");
     if (policy == FTGP_POLICY_PER_CAR && !e->P.car_policy[0]) return fail(FTGP_ERR_STATE, "FTGP_POLICY_PER_CAR without ftgp_set_car_policies%s");
-    if (uses_disparity_driver(e, policy)) {
-        if (e->P.n_rays < 8) return fail(FTGP_ERR_ARG, "nidc/fast need n_rays >= 8%s");
-        if (e->P.n_rays - 2 * e->P.eighth > FTGP_WAVE * FTGP_WAVE) return fail(FTGP_ERR_ARG, "the device drivers handle at most 4096 samples in the front window%s");
-    }
+    if (uses_disparity_driver(e, policy)) if (int rc = check_disparity_shape(e->P)) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpy2DAsync(e->d_ranges, sizeof(float) * (size_t)e->P.ranges_stride, ranges, sizeof(float) * (size_t)e->P.n_rays,
-                             sizeof(float) * (size_t)e->P.n_rays, (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpy2DAsync(e->d_ranges.get(), sizeof(float) * (size_t)e->P.ranges_stride, ranges, sizeof(float) * (size_t)e->P.n_rays,
+                             sizeof(float) * (size_t)e->P.n_rays, (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream.get()));
     const size_t lds = 4 * ((size_t)e->P.win_floats * sizeof(float) + sizeof(CarCore) + FTGP_WAVE * sizeof(int));
     if (lds > 64 * 1024) return fail(FTGP_ERR_ARG, "scan does not fit LDS%s");
-    hipLaunchKernelGGL(ftgp_policy_kernel, dim3((e->P.n_cars + 3) / 4), dim3(256), lds, e->stream, e->P, policy, ctrl_out ? e->d_ctrl : nullptr);
+    hipLaunchKernelGGL(ftgp_policy_kernel, dim3((e->P.n_cars + 3) / 4), dim3(256), lds, e->stream.get(), e->P, policy, ctrl_out ? e->d_ctrl.get() : nullptr);
     HIP_TRY(hipGetLastError());
-    if (ctrl_out) HIP_TRY(hipMemcpyAsync(ctrl_out, e->d_ctrl, sizeof(double) * 2 * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (ctrl_out) HIP_TRY(hipMemcpyAsync(ctrl_out, e->d_ctrl.get(), sizeof(double) * 2 * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 
@@ -1056,7 +1076,7 @@ int ftgp_eval_progress(FtgpEnv* e)
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     e->rows_valid = false; e->launch_metrics_valid = false;
     HIP_TRY(hipSetDevice(e->device));
-    hipLaunchKernelGGL(ftgp_progress_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream, e->P);
+    hipLaunchKernelGGL(ftgp_progress_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1101,10 +1121,10 @@ int ftgp_get_lap_times(FtgpEnv* e, int32_t* counts, double* times)
     if (!e || !counts || !times) return fail(FTGP_ERR_ARG, "null argument%s");
     if (int rc = sync_rows_to_host(e)) return rc;
     for (int i = 0; i < e->P.n_cars; ++i) counts[i] = (int32_t)e->h_core[(size_t)i * kCoreDoubles + 13];
-    HIP_TRY(hipMemcpy2DAsync(times, sizeof(double) * FTGP_MAX_LAP_TIMES, reinterpret_cast<const char*>(e->d_cars) + sizeof(CarCore), sizeof(CarState),   // times[] follows the CarCore head
+    HIP_TRY(hipMemcpy2DAsync(times, sizeof(double) * FTGP_MAX_LAP_TIMES, reinterpret_cast<const char*>(e->d_cars.get()) + sizeof(CarCore), sizeof(CarState),   // times[] follows the CarCore head
                             
-                             sizeof(double) * FTGP_MAX_LAP_TIMES, (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+                             sizeof(double) * FTGP_MAX_LAP_TIMES, (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 
@@ -1131,8 +1151,8 @@ int ftgp_get_steps(FtgpEnv* e, int64_t* out)
 {
     if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(out, e->d_steps, sizeof(int64_t) * (size_t)e->P.n_envs, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(out, e->d_steps.get(), sizeof(int64_t) * (size_t)e->P.n_envs, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 
@@ -1147,11 +1167,11 @@ static int metrics_to_host(FtgpEnv* e, double* out)
             collect_slot(e, e->cur_slot, e->held);
             e->gather_held = true;
         }
-        hipLaunchKernelGGL(ftgp_metrics_kernel, dim3(1), dim3(FTGP_METRIC_THREADS), 0, e->stream, e->P, e->h_metrics_dev + (size_t)e->cur_slot * FTGP_METRIC_DOUBLES);
+        hipLaunchKernelGGL(ftgp_metrics_kernel, dim3(1), dim3(FTGP_METRIC_THREADS), 0, e->stream.get(), e->P, e->h_metrics_dev + (size_t)e->cur_slot * FTGP_METRIC_DOUBLES);
         HIP_TRY(hipGetLastError());
         e->slot_partial[e->cur_slot] = false;
     }
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     collect_slot(e, e->cur_slot, out);
     return 0;
 }
@@ -1183,21 +1203,16 @@ int ftgp_comm_init(FtgpEnv* e, const uint8_t id[128], int rank, int world_size)
     Id128 uid; memcpy(uid.internal, id, 128);
     // the gathered records get buffers of their own (this rank's record slots, h_metrics, written by the step kernel, stay untouched) -- allocated
     // BEFORE the communicator: a handle never holds a communicator without them
-    double* d_gather = nullptr; double* h_gather = nullptr;
-    if (hipMalloc(&d_gather, sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)world_size) != hipSuccess ||
-        hipHostMalloc(&h_gather, sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)world_size, hipHostMallocDefault) != hipSuccess) {
-        if (d_gather) (void)hipFree(d_gather);
+    DevBuf<double> d_gather; HostBuf<double> h_gather;
+    if (dev_alloc(d_gather, sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)world_size) != hipSuccess ||
+        host_alloc(h_gather, sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)world_size, hipHostMallocDefault) != hipSuccess)
         return fail(FTGP_ERR_HIP, "ftgp_comm_init: no memory for the gathered records%s");
-    }
+    // launches from here on leave their record on the device (no partial records to the host); one still in flight finishes first (nothing is enqueued after it)
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     void* comm = nullptr;
     int r = g_rccl.CommInitRank(&comm, world_size, uid, rank);
-    if (r != 0) {
-        (void)hipFree(d_gather); (void)hipHostFree(h_gather);
-        return fail(FTGP_ERR_COMM, "ncclCommInitRank: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
-    }
-    // launches from here on leave their record on the device (no partial records to the host); one that is still in flight finishes first
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->comm = comm; e->d_gather = d_gather; e->h_gather = h_gather;
+    if (r != 0) return fail(FTGP_ERR_COMM, "ncclCommInitRank: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
+    e->comm = comm; e->d_gather = std::move(d_gather); e->h_gather = std::move(h_gather);
     e->rank = rank; e->world = world_size;
     return 0;
 }
@@ -1213,27 +1228,27 @@ int ftgp_metrics_allgather_begin(FtgpEnv* e)
     // a communicator that arrived after a launch whose record went to the host as partial records: the device has no copy of that record
     const bool refresh = !e->launch_metrics_valid || (rccl && e->slot_partial[slot]);
     if (refresh) {                       // otherwise the slot already holds this state's record (step kernel epilogue), on the device and in pinned memory
-        hipLaunchKernelGGL(ftgp_metrics_kernel, dim3(1), dim3(FTGP_METRIC_THREADS), 0, e->stream, e->P, rccl ? e->d_metrics + so : e->h_metrics_dev + so);
+        hipLaunchKernelGGL(ftgp_metrics_kernel, dim3(1), dim3(FTGP_METRIC_THREADS), 0, e->stream.get(), e->P, rccl ? e->d_metrics.get() + so : e->h_metrics_dev + so);
         HIP_TRY(hipGetLastError());
         e->slot_partial[slot] = false;
     }
     e->gather_held = false;
     if (!rccl) {                         // one rank: the "exchange" is the record's arrival in pinned memory
-        if (!refresh && e->timed) e->gather_event = e->ev_stop[slot];      // ... with the launch that wrote it: nothing to enqueue
-        else { HIP_TRY(hipEventRecord(e->ev_gather, e->stream)); e->gather_event = e->ev_gather; }
+        if (!refresh && e->timed) e->gather_event = e->ev_stop[slot].get();      // ... with the launch that wrote it: nothing to enqueue
+        else { HIP_TRY(hipEventRecord(e->ev_gather.get(), e->stream.get())); e->gather_event = e->ev_gather.get(); }
     } else {
         // the record is produced on the compute stream; everything else happens on the side stream, beside the next launch
         // (the launch's own stop event -- it rides on the kernel's dispatch packet -- says when the record is there.  An event of its own, recorded behind the
         // launch, is a barrier packet with a system-scope fence between this launch and the next: measured with a one-rank communicator, the next launch then runs
         // 20 - 25 us longer -- it finds the L2s flushed -- whatever the exchange itself does: profiles/round5/exchange_overlap_one_rank.log)
-        hipEvent_t ready = (!refresh && e->timed) ? e->ev_stop[slot] : e->ev_metrics;
-        if (ready == e->ev_metrics) HIP_TRY(hipEventRecord(e->ev_metrics, e->stream));
-        HIP_TRY(hipStreamWaitEvent(e->side, ready, 0));
-        int r = g_rccl.AllGather(e->d_metrics + so, e->d_gather, FTGP_METRIC_DOUBLES, kNcclFloat64, e->comm, e->side);
+        hipEvent_t ready = (!refresh && e->timed) ? e->ev_stop[slot].get() : e->ev_metrics.get();
+        if (ready == e->ev_metrics.get()) HIP_TRY(hipEventRecord(e->ev_metrics.get(), e->stream.get()));
+        HIP_TRY(hipStreamWaitEvent(e->side.get(), ready, 0));
+        int r = g_rccl.AllGather(e->d_metrics.get() + so, e->d_gather.get(), FTGP_METRIC_DOUBLES, kNcclFloat64, e->comm, e->side.get());
         if (r != 0) return fail(FTGP_ERR_COMM, "ncclAllGather: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
-        HIP_TRY(hipMemcpyAsync(e->h_gather, e->d_gather, sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)e->world, hipMemcpyDeviceToHost, e->side));
-        HIP_TRY(hipEventRecord(e->ev_gather, e->side));
-        e->gather_event = e->ev_gather;
+        HIP_TRY(hipMemcpyAsync(e->h_gather.get(), e->d_gather.get(), sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)e->world, hipMemcpyDeviceToHost, e->side.get()));
+        HIP_TRY(hipEventRecord(e->ev_gather.get(), e->side.get()));
+        e->gather_event = e->ev_gather.get();
     }
     e->gather_open = true; e->gather_slot = slot;
     return 0;
@@ -1246,7 +1261,7 @@ int ftgp_metrics_allgather_end(FtgpEnv* e, double* out)
     HIP_TRY(hipSetDevice(e->device));
     if (!e->gather_held) HIP_TRY(wait_event(e, e->gather_event));      // this exchange only: a later launch on the compute stream is not waited for
     e->gather_open = false;
-    if (e->comm) memcpy(out, e->h_gather, sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)e->world);
+    if (e->comm) memcpy(out, e->h_gather.get(), sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)e->world);
     else if (e->gather_held) memcpy(out, e->held, sizeof e->held);
     else collect_slot(e, e->gather_slot, out);
     return 0;
@@ -1264,7 +1279,7 @@ int ftgp_get_distance_field(FtgpEnv* e, double* out)
     if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     if (!e->d_edt) return fail(FTGP_ERR_STATE, "no distance field: the handle was not created with lidar_mode = FTGP_LIDAR_FAKELIDAR%s");
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpy(out, e->d_edt, sizeof(double) * (size_t)e->P.width * e->P.height, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, e->d_edt.get(), sizeof(double) * (size_t)e->P.width * e->P.height, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1273,28 +1288,18 @@ int ftgp_fakelidar(int device_id, const double* dt, int H, int W, int n_origins,
 {
     if (!dt || !origins || !cosines || !sines || !scan || !points || H < 1 || W < 1 || n_origins < 1 || rangefinders < 1)
         return fail(FTGP_ERR_ARG, "fakelidar: bad argument%s");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FTGP_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback%s");
-    if (device_id < 0 || device_id >= ndev) return fail(FTGP_ERR_ARG, "device_id out of range%s");
-    HIP_TRY(hipSetDevice(device_id));
+    if (int rc = open_device(device_id)) return rc;
     const size_t n = (size_t)n_origins * rangefinders, ndt = (size_t)H * W;
-    double *d_dt = nullptr, *d_o = nullptr, *d_c = nullptr, *d_s = nullptr, *d_scan = nullptr, *d_pts = nullptr; int* d_err = nullptr;
-    int rc = 0, herr = 0;
-    auto cleanup = [&]() { void* b[] = { d_dt, d_o, d_c, d_s, d_scan, d_pts, d_err }; for (void* p : b) if (p) (void)hipFree(p); };
-#define FL_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_err, sizeof g_err, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return FTGP_ERR_HIP; } } while (0)
-    FL_TRY(hipMalloc(&d_dt, ndt * 8)); FL_TRY(hipMalloc(&d_o, (size_t)n_origins * 16)); FL_TRY(hipMalloc(&d_c, n * 8)); FL_TRY(hipMalloc(&d_s, n * 8));
-    FL_TRY(hipMalloc(&d_scan, n * 8)); FL_TRY(hipMalloc(&d_pts, n * 16)); FL_TRY(hipMalloc(&d_err, 4));
-    FL_TRY(hipMemcpy(d_dt, dt, ndt * 8, hipMemcpyHostToDevice)); FL_TRY(hipMemcpy(d_o, origins, (size_t)n_origins * 16, hipMemcpyHostToDevice));
-    FL_TRY(hipMemcpy(d_c, cosines, n * 8, hipMemcpyHostToDevice)); FL_TRY(hipMemcpy(d_s, sines, n * 8, hipMemcpyHostToDevice));
-    FL_TRY(hipMemset(d_err, 0, 4));
-    hipLaunchKernelGGL(ftgp_fakelidar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_dt, H, W, (int)n, rangefinders, d_o, d_c, d_s, eps, d_scan, d_pts, d_err);
-    FL_TRY(hipGetLastError());
-    FL_TRY(hipMemcpy(scan, d_scan, n * 8, hipMemcpyDeviceToHost)); FL_TRY(hipMemcpy(points, d_pts, n * 16, hipMemcpyDeviceToHost));
-    FL_TRY(hipMemcpy(&herr, d_err, 4, hipMemcpyDeviceToHost));
-#undef FL_TRY
-    cleanup();
-    if (herr) rc = fail(FTGP_ERR_ARG, "fakelidar: IndexError (a ray left the image through the right or bottom edge)%s");
-    return rc;
+    DevBuf<double> d_dt, d_o, d_c, d_s, d_scan, d_pts; DevBuf<int> d_err; int herr = 0;
+    HIP_TRY(dev_upload(d_dt, dt, ndt * 8)); HIP_TRY(dev_upload(d_o, origins, (size_t)n_origins * 16)); HIP_TRY(dev_upload(d_c, cosines, n * 8)); HIP_TRY(dev_upload(d_s, sines, n * 8));
+    HIP_TRY(dev_alloc(d_scan, n * 8)); HIP_TRY(dev_alloc(d_pts, n * 16)); HIP_TRY(dev_alloc(d_err, 4));
+    HIP_TRY(hipMemset(d_err.get(), 0, 4));
+    hipLaunchKernelGGL(ftgp_fakelidar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_dt.get(), H, W, (int)n, rangefinders, d_o.get(), d_c.get(), d_s.get(), eps, d_scan.get(), d_pts.get(), d_err.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(scan, d_scan.get(), n * 8, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(points, d_pts.get(), n * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&herr, d_err.get(), 4, hipMemcpyDeviceToHost));
+    if (herr) return fail(FTGP_ERR_ARG, "fakelidar: IndexError (a ray left the image through the right or bottom edge)%s");
+    return 0;
 }
 
 int ftgp_last_kernel_ms(FtgpEnv* e, float* ms)
@@ -1302,8 +1307,8 @@ int ftgp_last_kernel_ms(FtgpEnv* e, float* ms)
     if (!e || !ms) return fail(FTGP_ERR_ARG, "null argument%s");
     if (!e->timed) return fail(FTGP_ERR_STATE, "no step/rollout has been launched yet%s");
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_event(e, e->ev_stop[e->cur_slot]));
-    HIP_TRY(hipEventElapsedTime(ms, e->ev_start, e->ev_stop[e->cur_slot]));
+    HIP_TRY(wait_event(e, e->ev_stop[e->cur_slot].get()));
+    HIP_TRY(hipEventElapsedTime(ms, e->ev_start.get(), e->ev_stop[e->cur_slot].get()));
     return 0;
 }
 
@@ -1354,17 +1359,13 @@ const char* ftgp_build_info(void)
 int ftgp_selftest(int device_id, int64_t* mismatches)
 {
     if (!mismatches) return fail(FTGP_ERR_ARG, "null argument%s");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FTGP_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback%s");
-    if (device_id < 0 || device_id >= ndev) return fail(FTGP_ERR_ARG, "device_id out of range%s");
-    HIP_TRY(hipSetDevice(device_id));
-    unsigned long long* d = nullptr; unsigned long long h = 0;
-    HIP_TRY(hipMalloc(&d, sizeof h));
-    hipError_t e1 = hipMemset(d, 0, sizeof h);
-    hipLaunchKernelGGL(ftgp_selftest_rcp_kernel, dim3(1u << 12), dim3(256), 0, 0, d);
+    if (int rc = open_device(device_id)) return rc;
+    DevBuf<unsigned long long> d; unsigned long long h = 0;
+    HIP_TRY(dev_alloc(d, sizeof h));
+    hipError_t e1 = hipMemset(d.get(), 0, sizeof h);
+    hipLaunchKernelGGL(ftgp_selftest_rcp_kernel, dim3(1u << 12), dim3(256), 0, 0, d.get());
     hipError_t e2 = hipGetLastError();
-    hipError_t e3 = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    hipError_t e3 = hipMemcpy(&h, d.get(), sizeof h, hipMemcpyDeviceToHost);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(FTGP_ERR_HIP, "selftest: HIP error%s");
     *mismatches = (int64_t)h;
     return 0;
@@ -1373,10 +1374,7 @@ int ftgp_selftest(int device_id, int64_t* mismatches)
 const char* ftgp_kernel_name(FtgpEnv* e)
 {
     if (!e) return "ftgp_step_kernel";
-    // <MULTI, FAKE, ROSTER>: the instantiation of the newest launch (before any: the single-driver one)
-    if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return e->multi ? "ftgp_step_kernel<true, true, true>" : "ftgp_step_kernel<false, true, true>";
-    if (e->last_roster) return e->multi ? "ftgp_step_kernel<true, false, true>" : "ftgp_step_kernel<false, false, true>";
-    return e->multi ? "ftgp_step_kernel<true, false, false>" : "ftgp_step_kernel<false, false, false>";
+    return step_kernel(e, e->last_roster).name;      // the instantiation of the newest launch (before any: the single-driver one)
 }
 
 }  // extern "C"
