@@ -22,6 +22,7 @@ SNAPSHOT_DOUBLES = 10
 POSE_DOUBLES = 13
 PROGRESS_INTS = 10
 METRIC_DOUBLES = 8
+MAX_TRACKS = 16             # FTGP_MAX_TRACKS: tracks of one multi-track handle (ftgp_create_tracks)
 
 POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2, 3, 4
 LIDAR_RANGEFINDER, LIDAR_FAKELIDAR = 0, 1
@@ -76,7 +77,7 @@ API_SYMBOLS = (
     "get_steps", "set_pose", "policy_eval", "eval_progress", "metrics_local", "comm_unique_id", "comm_init", "metrics_allgather",
     "metrics_allgather_begin", "metrics_allgather_end", "get_distance_field",
     "last_kernel_ms", "kernel_name", "fakelidar", "selftest", "build_info", "get_race_steps",
-    "device_io_config", "step_device",
+    "device_io_config", "step_device", "create_tracks", "get_track_distance_field",
 )
 
 
@@ -157,6 +158,8 @@ class CLib:
             "build_info": (C.c_char_p, []),
             "device_io_config": (i32, [vp, C.POINTER(FtgpDeviceIoConfig)]),
             "step_device": (i32, [vp, C.POINTER(FtgpDeviceStep)]),
+            "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
+            "get_track_distance_field": (i32, [vp, i32, dp]),
         }
         for name, (res, args) in sigs.items():
             if name == "fakelidar" and self.prefix != "ftgp_":
@@ -205,15 +208,65 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def split_envs(n_envs: int, n_tracks: int) -> tuple:
+    """The default envs_per_track of a multi-track handle: as even as possible, the remainder to the first blocks."""
+    n_envs, n_tracks = int(n_envs), int(n_tracks)
+    return tuple(n_envs // n_tracks + (1 if t < n_envs % n_tracks else 0) for t in range(n_tracks))
+
+
+def track_blocks(n_envs: int, n_tracks: int, envs_per_track=None) -> tuple:
+    """envs_per_track of a multi-track handle, checked (ValueError): 1 <= n_tracks <= MAX_TRACKS, one count >= 1 per track, summing to
+    n_envs; None = ``split_envs``."""
+    n_envs, n_tracks = int(n_envs), int(n_tracks)
+    if not 1 <= n_tracks <= MAX_TRACKS:
+        raise ValueError(f"a handle holds 1 .. {MAX_TRACKS} tracks, got {n_tracks}")
+    if envs_per_track is None:
+        if n_envs < n_tracks:
+            raise ValueError(f"{n_envs} envs cannot give each of {n_tracks} tracks an env")
+        return split_envs(n_envs, n_tracks)
+    counts = tuple(int(c) for c in envs_per_track)
+    if len(counts) != n_tracks:
+        raise ValueError(f"envs_per_track: one count per track, expected {n_tracks}, got {len(counts)}")
+    if min(counts) < 1:
+        raise ValueError(f"envs_per_track: every track needs at least one env, got {counts}")
+    if sum(counts) != n_envs:
+        raise ValueError(f"envs_per_track sums to {sum(counts)}, n_envs is {n_envs}")
+    return counts
+
+
+def _fill_track(t: FtgpTrack, track) -> tuple:
+    """Fill the C struct from a Track; returns the arrays it points into (keep them alive)."""
+    bits = np.ascontiguousarray(track.bits, dtype=np.uint32)
+    path = np.ascontiguousarray(track.path, dtype=np.float64)
+    assert path.shape == (PATH_POINTS, 2)
+    t.width, t.height, t.words_per_row = track.width, track.height, bits.shape[1]
+    t.bits, t.path = bits.ctypes.data, path.ctypes.data
+    t.px_size_x, t.px_size_y, t.origin_x, t.origin_y = track.px_size_x, track.px_size_y, track.origin_x, track.origin_y
+    return bits, path
+
+
 class Env:
-    """A batch of worlds behind one opaque C handle (see include/ftgp.h for the contract of each call)."""
+    """A batch of worlds behind one opaque C handle (see include/ftgp.h for the contract of each call).
+
+    track: one Track (ftgp_create), or a list / tuple of Tracks (ftgp_create_tracks): env block t = envs_per_track[t] consecutive envs
+    on track t, as even a split as possible by default (``split_envs``).  ``tracks`` lists the tracks, ``track_of_env`` (int32 [n_envs])
+    says which track each env races; ``track`` is the first."""
 
     def __init__(self, lib: CLib, track: Track, n_envs: int = 1, cars_per_env: int = 1, n_rays: int = 90,
                  lap_target: int = 10, dt: float = 0.004, spawn_mode: int = 0, seed: int = 1234,
                  device_id: int = 0, vehicle: Optional[FtgpVehicle] = None, env_base: int = 0,
                  bubble_wrap: bool = False, naive_flatten: bool = False, lidar_mode="rangefinder", map_size: float = 0.0,
-                 fan_dirs: Optional[np.ndarray] = None):
-        self.lib, self.track = lib, track
+                 fan_dirs: Optional[np.ndarray] = None, envs_per_track=None):
+        multi = isinstance(track, (list, tuple))
+        tracks = list(track) if multi else [track]
+        if multi:
+            counts = track_blocks(n_envs, len(tracks), envs_per_track)
+        elif envs_per_track is not None:
+            raise ValueError("envs_per_track needs a list of tracks")
+        else:
+            counts = (int(n_envs),)
+        self.lib, self.track, self.tracks, self.envs_per_track = lib, tracks[0], tracks, counts
+        self.track_of_env = np.repeat(np.arange(len(tracks), dtype=np.int32), counts)
         self.n_envs, self.cars_per_env, self.n_rays = int(n_envs), int(cars_per_env), int(n_rays)
         self.n_cars = self.n_envs * self.cars_per_env
         self.dt, self.lap_target = float(dt), int(lap_target)
@@ -228,17 +281,17 @@ class Env:
         self._fan = None if fan_dirs is None else np.ascontiguousarray(fan_dirs, dtype=np.float64).reshape(self.n_rays, 2)
         cfg.fan_dirs = None if self._fan is None else self._fan.ctypes.data
         self.env_base = int(env_base)
-        self._bits = np.ascontiguousarray(track.bits, dtype=np.uint32)
-        self._path = np.ascontiguousarray(track.path, dtype=np.float64)
-        assert self._path.shape == (PATH_POINTS, 2)
-        t = cfg.track
-        t.width, t.height, t.words_per_row = track.width, track.height, self._bits.shape[1]
-        t.bits, t.path = self._bits.ctypes.data, self._path.ctypes.data
-        t.px_size_x, t.px_size_y, t.origin_x, t.origin_y = track.px_size_x, track.px_size_y, track.origin_x, track.origin_y
         cfg.vehicle = vehicle if vehicle is not None else lib.default_vehicle()
         self.cfg = cfg
         self.h = C.c_void_p()
-        lib.check(lib.fn("create")(C.byref(cfg), C.byref(self.h)))
+        if not multi:
+            self._bits, self._path = _fill_track(cfg.track, track)
+            lib.check(lib.fn("create")(C.byref(cfg), C.byref(self.h)))
+        else:
+            self._tracks = (FtgpTrack * len(tracks))()
+            self._keep = [_fill_track(self._tracks[k], t) for k, t in enumerate(tracks)]
+            self._counts = np.array(counts, dtype=np.int32)
+            lib.check(lib.fn("create_tracks")(C.byref(cfg), self._tracks, _ptr(self._counts), len(tracks), C.byref(self.h)))
 
     # -- lifecycle
     def close(self):
@@ -405,6 +458,19 @@ class Env:
         """FAKELIDAR mode: the Euclidean distance transform built at create, float64 [H, W] in pixels (self.dt of custom.py:1152-1153)."""
         out = np.empty((self.track.height, self.track.width), dtype=np.float64)
         self._call("get_distance_field", _ptr(out))
+        return out
+
+    def get_distance_field(self, track: int = 0) -> np.ndarray:
+        """FAKELIDAR mode: the distance transform of track ``track`` of the handle, float64 [H, W] of that track, in pixels."""
+        track = int(track)
+        if not 0 <= track < len(self.tracks):
+            raise ValueError(f"track {track} of a handle with {len(self.tracks)}")
+        t = self.tracks[track]
+        out = np.empty((t.height, t.width), dtype=np.float64)
+        if len(self.tracks) == 1:
+            self._call("get_distance_field", _ptr(out))
+        else:
+            self._call("get_track_distance_field", track, _ptr(out))
         return out
 
     def last_kernel_ms(self) -> float:

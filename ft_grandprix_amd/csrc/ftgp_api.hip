@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 #include <math.h>
 #include <cmath>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,6 +25,23 @@ thread_local char g_err[512] = "";
 int fail(int code, const char* fmt, const char* a = "")
 {
     snprintf(g_err, sizeof g_err, fmt, a);
+    return code;
+}
+
+int failf(int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+// the error of track k of a multi-track handle: its index in front of the message
+int name_track(int code, int k)
+{
+    const std::string m(g_err);
+    snprintf(g_err, sizeof g_err, "track %d: %s", k, m.c_str());
     return code;
 }
 
@@ -86,6 +104,13 @@ int load_rccl()
     return 0;
 }
 
+// the device copy of one track of a handle
+struct TrackBufs {
+    DevBuf<uint16_t> field; DevBuf<uint32_t> bits, nearbits;
+    DevBuf<double> edt;               // FTGP_LIDAR_FAKELIDAR: distance transform
+    int width = 0, height = 0;
+};
+
 }  // namespace
 
 // The members free themselves in reverse order of declaration, the streams last; ftgp_destroy synchronises both streams first.
@@ -98,12 +123,18 @@ struct FtgpEnv {
     bool ext_launch = true;      // FTGP_LAUNCH_PLAIN=1 switches it off (tools/launch_host.sh)
     bool last_roster = false;    // the newest launch ran the ROSTER instantiation
     // device buffers
-    DevBuf<uint16_t> d_field; DevBuf<uint32_t> d_bits, d_nearbits;
-    DevBuf<double> d_path, d_spawn; DevBuf<float> d_ray, d_cover; DevBuf<void> d_veh; DevBuf<unsigned char> d_stage; DevBuf<DeviceParams> d_params;
+    std::vector<TrackBufs> trk;       // per track: box field or distance transform, wall bitmaps (one entry for a one-track handle)
+    DevBuf<double> d_path, d_spawn;   // [n_tracks][FTGP_PATH_POINTS][2] centre-lines, [n_tracks][FTGP_PATH_POINTS][4] spawn tables
+    DevBuf<float> d_ray, d_cover; DevBuf<void> d_veh; DevBuf<unsigned char> d_stage; DevBuf<DeviceParams> d_params;
     DevBuf<CarState> d_cars; DevBuf<float> d_ranges; DevBuf<int64_t> d_steps;
     DevBuf<uint8_t> d_env_mask, d_car_mask; DevBuf<double> d_ctrl, d_pose;
     DevBuf<double> d_metrics, d_gather, d_wg_metrics; DevBuf<unsigned int> d_wg_ticket;
-    DevBuf<double> d_edt, d_fan;      // FTGP_LIDAR_FAKELIDAR: distance transform, binary64 fan
+    DevBuf<double> d_fan;             // FTGP_LIDAR_FAKELIDAR: binary64 fan
+    // multi-track handles (ftgp_create_tracks): one parameter block per track in d_params, the workgroup table behind track 0's
+    int n_tracks = 1;
+    std::vector<size_t> blocks;       // byte offset of each track's parameter block in d_params (track 0: 0)
+    DevBuf<int32_t> d_env_track;      // [n_envs] the track of every env (null with one track)
+    int grid = 0;                     // workgroups of a step launch
     // This rank's metrics record lives in two slots (device memory for RCCL, pinned host memory for the caller) that successive
     // launches alternate between, so that the exchange of launch k's record can run beside launch k + 1.
     int cur_slot = 0;                    // slot of the most recent step launch (or of the record ftgp_metrics_kernel refreshed)
@@ -277,27 +308,35 @@ int sector_count(const FtgpConfig& cfg)
     return n_sectors;
 }
 
-// ftgp_create, step 1: the checks of the configuration (no device call)
-int validate(const FtgpConfig& cfg)
+// ftgp_create, step 1: the checks of the configuration with its tracks (no device call).  named: an error of a track names its index
+// (ftgp_create_tracks).
+int validate(const FtgpConfig& cfg, const FtgpTrack* tracks, int n_tracks, bool named)
 {
     if (cfg.abi_version != FTGP_ABI_VERSION) return fail(FTGP_ERR_ARG, "abi version mismatch%s");
     if (cfg.n_envs < 1 || cfg.cars_per_env < 1 || cfg.cars_per_env > 8 || cfg.n_rays < 1) return fail(FTGP_ERR_ARG, "bad n_envs / cars_per_env / n_rays%s");
     if (cfg.spawn_mode == 0 && (cfg.cars_per_env + 4) * 2 + 1 >= FTGP_PATH_POINTS) return fail(FTGP_ERR_ARG, "too many cars for the reference spawn rule%s");
-    const FtgpTrack& t = cfg.track;
-    if (t.width < 1 || t.height < 1 || !t.bits || !t.path || t.words_per_row < (t.width + 31) / 32) return fail(FTGP_ERR_ARG, "bad track%s");
-    if (t.width > 8192 || t.height > 8192) return fail(FTGP_ERR_ARG, "images above 8192 pixels are not supported%s");
-    // the march addresses the field with a 32-bit byte offset
-    if ((uint64_t)ftgp_plane256(t.width, t.height) * 256u * (uint64_t)sector_count(cfg) > 0xFFFFFFFFull)
-        return fail(FTGP_ERR_ARG, "track image too large: the sector box field (2 bytes per pixel and direction sector) must stay below 4 GiB%s");
+    auto bad = [&](int k, int rc) { return named ? name_track(rc, k) : rc; };
+    for (int k = 0; k < n_tracks; ++k) {
+        const FtgpTrack& t = tracks[k];
+        if (t.width < 1 || t.height < 1 || !t.bits || !t.path || t.words_per_row < (t.width + 31) / 32) return bad(k, fail(FTGP_ERR_ARG, "bad track%s"));
+        if (t.width > 8192 || t.height > 8192) return bad(k, fail(FTGP_ERR_ARG, "images above 8192 pixels are not supported%s"));
+        // the march addresses the field with a 32-bit byte offset
+        if ((uint64_t)ftgp_plane256(t.width, t.height) * 256u * (uint64_t)sector_count(cfg) > 0xFFFFFFFFull)
+            return bad(k, fail(FTGP_ERR_ARG, "track image too large: the sector box field (2 bytes per pixel and direction sector) must stay below 4 GiB%s"));
+    }
     if (cfg.env_base < 0) return fail(FTGP_ERR_ARG, "env_base < 0%s");
     if (cfg.lidar_mode != FTGP_LIDAR_RANGEFINDER && cfg.lidar_mode != FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_ARG, "unknown lidar_mode%s");
-    if (!(cfg.dt > 0.0) || !(t.px_size_x > 0.0) || !(t.px_size_y > 0.0)) return fail(FTGP_ERR_ARG, "bad dt / pixel size%s");
+    if (!(cfg.dt > 0.0)) return fail(FTGP_ERR_ARG, "bad dt / pixel size%s");
+    for (int k = 0; k < n_tracks; ++k)
+        if (!(tracks[k].px_size_x > 0.0) || !(tracks[k].px_size_y > 0.0)) return bad(k, fail(FTGP_ERR_ARG, "bad dt / pixel size%s"));
     const FtgpVehicle& v = cfg.vehicle;
     if (!(v.contact_radius > 0.0) || !(v.mass > 0.0) || !(v.izz > 0.0) || (v.kind != FTGP_VEHICLE_MUSHR && v.kind != FTGP_VEHICLE_TRICYCLE))
         return fail(FTGP_ERR_ARG, "bad vehicle%s");
     if (cfg.bubble_wrap && !(v.softener_radius > 0.0)) return fail(FTGP_ERR_ARG, "bubble_wrap needs vehicle.softener_radius > 0%s");
     return 0;
 }
+
+int validate(const FtgpConfig& cfg) { return validate(cfg, &cfg.track, 1, false); }      // ftgp_create's checks of cfg.track
 
 // ftgp_create, step 2: the plan -- everything that fixes what the step kernel does; host arithmetic only (no HIP call)
 struct Plan {
@@ -309,6 +348,16 @@ struct Plan {
     std::vector<float> cover;         // cover-count thresholds of nidc, then of fast, cover_kmax + 1 each (+ padding)
     std::vector<unsigned char> veh;   // the VehLds image, padded to 16 bytes
     std::vector<int32_t> tasks;       // [2][cars_per_block * tasks_per_car][4] the sweep's task tables (DeviceParams::task_tab)
+    int n_wg = 0;                     // workgroups of a step launch
+    // multi-track handles (plan_tracks); the members above are track 0's and the batch's
+    struct Track {
+        DeviceParams P;               // the track's parameter block: the batch's, with the track's own values (plan_track_params)
+        HostTables tab;
+        std::vector<double> spawn;
+    };
+    std::vector<Track> more;          // tracks 1 .. n_tracks - 1
+    std::vector<int32_t> wg;          // [n_wg][4] the workgroup table (FTGP_PARAMS_BYTES): block offset (set by the upload), first car, cars, track
+    std::vector<int32_t> env_track;   // [n_envs]
 };
 
 // workgroup shape: whole envs, at most 16 cars (K1 / K3 run on the lanes of one wave), two workgroups per CU
@@ -455,6 +504,38 @@ void plan_vehicle(const DeviceParams& P, std::vector<unsigned char>& img)
     memcpy(img.data(), &vl, sizeof vl);
 }
 
+// What of the parameter block depends on the track: image size and strides, sector planes, pixel geometry, the wall-contact reach, the
+// march's snap distance, the frame's edge margin.  P.n_sectors (chosen for the whole batch) must be set.
+void plan_track_params(const FtgpConfig& cfg, const FtgpTrack& t, DeviceParams& P)
+{
+    const FtgpVehicle& v = cfg.vehicle;
+    P.width = t.width; P.height = t.height; P.words_per_row = t.words_per_row; P.fstride = t.width + 2;
+    P.plane256 = ftgp_plane256(t.width, t.height);
+    // a ray's sector is always found among all FTGP_SECTORS; the table says which plane serves it
+    P.n_planes = ftgp_sector_table(P.sector_tab, P.n_sectors, t.width + 2, P.plane256);
+    P.px_size_x = t.px_size_x; P.px_size_y = t.px_size_y; P.origin_x = t.origin_x; P.origin_y = t.origin_y;
+    P.inv_px_x = 1.0 / t.px_size_x; P.inv_px_y = 1.0 / t.px_size_y;
+    P.inv_px_x_f = (float)P.inv_px_x; P.inv_px_y_f = (float)P.inv_px_y;
+    {   // chessboard reach of the largest wall-contact window
+        const double rmax = std::max(v.contact_radius, cfg.bubble_wrap ? v.softener_radius : 0.0);
+        P.contact_reach = std::max((int)ceil(rmax * P.inv_px_x), (int)ceil(rmax * P.inv_px_y));
+    }
+    P.snap_eps = ftgp_snap_eps(t.width, t.height);
+    P.edge_margin = (float)(v.lidar_ring_radius * std::max(P.inv_px_x, P.inv_px_y) * 1.001 + 2.0);
+}
+
+// the track's bitmaps and run lengths, and its spawn table
+void plan_track_tables(const FtgpTrack& t, const DeviceParams& P, HostTables& tab, std::vector<double>& spawn)
+{
+    build_tables(t, P.contact_reach, tab);
+    spawn.assign(4 * FTGP_PATH_POINTS, 0.0);
+    for (int p = 0; p < FTGP_PATH_POINTS; ++p) {      // position_vehicles (custom.py:1240-1245) + euler_to_quaternion([angle, 0, 0]) (custom.py:81-87)
+        const int p1 = (p + 1) % FTGP_PATH_POINTS;
+        const double ang = atan2(t.path[2 * p1 + 1] - t.path[2 * p + 1], t.path[2 * p1] - t.path[2 * p]);
+        spawn[4 * p] = t.path[2 * p]; spawn[4 * p + 1] = t.path[2 * p + 1]; spawn[4 * p + 2] = cos(ang / 2); spawn[4 * p + 3] = sin(ang / 2);
+    }
+}
+
 // n_cu: compute units of the device (the workgroup shape depends on it)
 int plan_create(const FtgpConfig& cfg, int n_cu, Plan& pl)
 {
@@ -470,14 +551,8 @@ int plan_create(const FtgpConfig& cfg, int n_cu, Plan& pl)
     P.bubble_wrap = cfg.bubble_wrap ? 1 : 0;        // cfg.naive_flatten: accepted, no effect on a planar model (custom.py:1338-1339)
     P.lidar_mode = cfg.lidar_mode;
     P.map_size = cfg.map_size > 0.0 ? cfg.map_size : 40.0;                     // 20 * scale, custom.py:1155,1382
-    P.width = t.width; P.height = t.height; P.words_per_row = t.words_per_row; P.fstride = t.width + 2;
-    P.plane256 = ftgp_plane256(t.width, t.height);
-    // a ray's sector is always found among all FTGP_SECTORS; the table says which plane serves it
     P.n_sectors = sector_count(cfg); P.slice_factor = FTGP_SLICE_FACTOR(FTGP_SLOPE_SLICES);
-    P.n_planes = ftgp_sector_table(P.sector_tab, P.n_sectors, t.width + 2, P.plane256);
-    P.px_size_x = t.px_size_x; P.px_size_y = t.px_size_y; P.origin_x = t.origin_x; P.origin_y = t.origin_y;
-    P.inv_px_x = 1.0 / t.px_size_x; P.inv_px_y = 1.0 / t.px_size_y;
-    P.inv_px_x_f = (float)P.inv_px_x; P.inv_px_y_f = (float)P.inv_px_y;
+    plan_track_params(cfg, t, P);
     P.veh = cfg.vehicle;
     {   // static wheel loads from the wheelbase split
         const double wtot = v.mass * v.gravity;
@@ -491,30 +566,19 @@ int plan_create(const FtgpConfig& cfg, int n_cu, Plan& pl)
             P.wheel_load[2] = P.wheel_load[3] = 0.5 * (wtot * (a_f / (a_f + a_r)));
         }
     }
-    {   // chessboard reach of the largest wall-contact window
-        const double rmax = std::max(v.contact_radius, cfg.bubble_wrap ? v.softener_radius : 0.0);
-        P.contact_reach = std::max((int)ceil(rmax * P.inv_px_x), (int)ceil(rmax * P.inv_px_y));
-    }
     P.eighth = (int)((double)cfg.n_rays / 8.0);                    // nidc.py:18
     // the largest cover count any positive sample can produce (that of the smallest positive float), over both drivers
     const double tiny = (double)1.401298464e-45f;
     P.cover_kmax = std::max(1, std::max(cover_count_host(0.24, P.rpp, tiny), cover_count_host(0.12, P.rpp, tiny)));
     P.win_floats = ((P.eighth & 3) + (cfg.n_rays - 2 * P.eighth) + 1 + 3) & ~3;       // window at float (eighth % 4), ranges[0] in the last float
-    P.snap_eps = ftgp_snap_eps(t.width, t.height);
     P.n_cu = n_cu;
-    P.edge_margin = (float)(v.lidar_ring_radius * std::max(P.inv_px_x, P.inv_px_y) * 1.001 + 2.0);
     if ((cfg.n_rays + FTGP_WAVE - 1) / FTGP_WAVE > FTGP_MAX_GROUPS) return fail(FTGP_ERR_ARG, "n_rays above 16384 is not supported%s");
     if (int rc = plan_shape(P)) return rc;
-    build_tables(t, P.contact_reach, pl.tab);
+    pl.n_wg = (P.n_cars + P.cars_per_block - 1) / P.cars_per_block;
     plan_fan(cfg, pl.ray, pl.fan);
     plan_task_order(cfg, pl.ray, P);
     if (int rc = plan_task_table(P, pl.tasks)) return rc;
-    pl.spawn.assign(4 * FTGP_PATH_POINTS, 0.0);
-    for (int p = 0; p < FTGP_PATH_POINTS; ++p) {      // position_vehicles (custom.py:1240-1245) + euler_to_quaternion([angle, 0, 0]) (custom.py:81-87)
-        const int p1 = (p + 1) % FTGP_PATH_POINTS;
-        const double ang = atan2(t.path[2 * p1 + 1] - t.path[2 * p + 1], t.path[2 * p1] - t.path[2 * p]);
-        pl.spawn[4 * p] = t.path[2 * p]; pl.spawn[4 * p + 1] = t.path[2 * p + 1]; pl.spawn[4 * p + 2] = cos(ang / 2); pl.spawn[4 * p + 3] = sin(ang / 2);
-    }
+    plan_track_tables(t, P, pl.tab, pl.spawn);
     {   // cover-count thresholds: nidc (car_width 0.12, nidc.py:5) then fast (0.06, fast.py:4), each padded to the staged size
         const size_t stride = (size_t)P.cover_kmax + 1, padded = (size_t)pad16(sizeof(float) * stride) / sizeof(float);
         pl.cover.assign(stride + padded + 4, 0.0f);
@@ -522,6 +586,66 @@ int plan_create(const FtgpConfig& cfg, int n_cu, Plan& pl)
         build_cover_table(0.06, cfg.n_rays, P.cover_kmax, pl.cover.data() + stride);
     }
     plan_vehicle(P, pl.veh);
+    return 0;
+}
+
+// Workgroup order of a multi-track launch (FTGP_TRACK_ORDER=blocks|xcd).  Workgroups are dealt round robin over the 8 XCDs, so workgroups b
+// and b + 8 share an L2 (observed, not promised).  blocks: the workgroups in car order, track after track -- every XCD then holds a share
+// of every track's field.  xcd: the k-th workgroup in car order takes the k-th index of the grid sorted by (b % 8, b), so that each track
+// owns a run of residues b % 8, in proportion to its number of workgroups, and an L2 holds the fields of one or two tracks.  Results do
+// not depend on the order.
+enum { kOrderBlocks = 0, kOrderXcd = 1 };
+int track_order()
+{
+    const char* sv = getenv("FTGP_TRACK_ORDER");
+    if (sv && strcmp(sv, "blocks") == 0) return kOrderBlocks;
+    if (sv && strcmp(sv, "xcd") == 0) return kOrderXcd;
+    return kOrderXcd;
+}
+
+// The workgroup table: whole envs of one track per workgroup, each block of envs its own workgroups with a ragged last one.  wg[4 b ..]
+// = (0: the block offset, filled in by the upload; first car; cars; track).
+void plan_workgroups(int cpb, int cpe, const int32_t* envs_per_track, int n_tracks, int order, std::vector<int32_t>& wg)
+{
+    std::vector<int32_t> list;
+    int first = 0;
+    for (int t = 0; t < n_tracks; ++t) {
+        const int end = first + envs_per_track[t] * cpe;
+        for (int c0 = first; c0 < end; c0 += cpb) { const int32_t e[4] = { 0, c0, std::min(cpb, end - c0), t }; list.insert(list.end(), e, e + 4); }
+        first = end;
+    }
+    const int n = (int)list.size() / 4;
+    std::vector<int> slot(n);
+    for (int k = 0; k < n; ++k) slot[k] = k;
+    if (order == kOrderXcd) {
+        int k = 0;
+        for (int r = 0; r < 8; ++r)
+            for (int b = r; b < n; b += 8) slot[k++] = b;
+    }
+    wg.assign(list.size(), 0);
+    for (int k = 0; k < n; ++k) std::copy(&list[4 * (size_t)k], &list[4 * (size_t)k] + 4, &wg[4 * (size_t)slot[k]]);
+}
+
+// ftgp_create_tracks, step 2: the plan of the batch (shape, sectors, fan, tasks: as for one track of all n_envs envs), then every track's
+// own block, tables and spawn table, and the workgroup table.  Host arithmetic only.
+int plan_tracks(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, int n_cu, Plan& pl)
+{
+    FtgpConfig c0 = cfg;
+    c0.track = tracks[0];
+    if (int rc = plan_create(c0, n_cu, pl)) return rc;
+    pl.more.resize((size_t)n_tracks - 1);
+    for (int t = 1; t < n_tracks; ++t) {
+        Plan::Track& k = pl.more[(size_t)t - 1];
+        k.P = pl.P;
+        plan_track_params(cfg, tracks[t], k.P);
+        plan_track_tables(tracks[t], k.P, k.tab, k.spawn);
+    }
+    pl.env_track.clear();
+    for (int t = 0; t < n_tracks; ++t) pl.env_track.insert(pl.env_track.end(), (size_t)envs_per_track[t], t);
+    plan_workgroups(pl.P.cars_per_block, cfg.cars_per_env, envs_per_track, n_tracks, track_order(), pl.wg);
+    pl.n_wg = (int)pl.wg.size() / 4;
+    if (getenv("FTGP_VERBOSE"))
+        fprintf(stderr, "ftgp_create: %d tracks, %d workgroups in %s order\n", n_tracks, pl.n_wg, track_order() == kOrderXcd ? "xcd" : "blocks");
     return 0;
 }
 
@@ -546,18 +670,28 @@ int check_disparity_shape(const DeviceParams& P)
     return 0;
 }
 
-// The six instantiations of ftgp_step_kernel<MULTI, FAKE, ROSTER>.  FAKELIDAR always runs the roster one.
+// The six instantiations of ftgp_step_kernel<MULTI, FAKE, ROSTER, false>, and the six of multi-track handles (TRACKS = true).  FAKELIDAR
+// always runs the roster one.  The one-track names keep their three flags: what ftgp_kernel_name has always returned.
 struct StepKernel { void (*fn)(const DeviceParams*, int, int, int); const char* name; };
-const StepKernel kStepKernels[2][3] = {      // [multi][0: single driver, 1: roster, 2: FAKELIDAR]
-    { { ftgp_step_kernel<false, false, false>, "ftgp_step_kernel<false, false, false>" },
-      { ftgp_step_kernel<false, false, true>, "ftgp_step_kernel<false, false, true>" },
-      { ftgp_step_kernel<false, true, true>, "ftgp_step_kernel<false, true, true>" } },
-    { { ftgp_step_kernel<true, false, false>, "ftgp_step_kernel<true, false, false>" },
-      { ftgp_step_kernel<true, false, true>, "ftgp_step_kernel<true, false, true>" },
-      { ftgp_step_kernel<true, true, true>, "ftgp_step_kernel<true, true, true>" } },
+const StepKernel kStepKernels[2][2][3] = {      // [multi-track][multi][0: single driver, 1: roster, 2: FAKELIDAR]
+  { { { ftgp_step_kernel<false, false, false, false>, "ftgp_step_kernel<false, false, false>" },
+      { ftgp_step_kernel<false, false, true, false>, "ftgp_step_kernel<false, false, true>" },
+      { ftgp_step_kernel<false, true, true, false>, "ftgp_step_kernel<false, true, true>" } },
+    { { ftgp_step_kernel<true, false, false, false>, "ftgp_step_kernel<true, false, false>" },
+      { ftgp_step_kernel<true, false, true, false>, "ftgp_step_kernel<true, false, true>" },
+      { ftgp_step_kernel<true, true, true, false>, "ftgp_step_kernel<true, true, true>" } } },
+  { { { ftgp_step_kernel<false, false, false, true>, "ftgp_step_kernel<false, false, false, true>" },
+      { ftgp_step_kernel<false, false, true, true>, "ftgp_step_kernel<false, false, true, true>" },
+      { ftgp_step_kernel<false, true, true, true>, "ftgp_step_kernel<false, true, true, true>" } },
+    { { ftgp_step_kernel<true, false, false, true>, "ftgp_step_kernel<true, false, false, true>" },
+      { ftgp_step_kernel<true, false, true, true>, "ftgp_step_kernel<true, false, true, true>" },
+      { ftgp_step_kernel<true, true, true, true>, "ftgp_step_kernel<true, true, true, true>" } } },
 };
 
-const StepKernel& step_kernel(const FtgpEnv* e, bool roster) { return kStepKernels[e->multi][e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR ? 2 : roster ? 1 : 0]; }
+const StepKernel& step_kernel(const FtgpEnv* e, bool roster)
+{
+    return kStepKernels[e->n_tracks > 1][e->multi][e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR ? 2 : roster ? 1 : 0];
+}
 
 // This rank's record of the launch (or metrics kernel) that wrote `slot`, once its event has been waited for: the record itself, or the
 // sum of the workgroups' partial records (sums of integers, a minimum and a maximum: exact in any order -- bit-identical to what the
@@ -579,8 +713,9 @@ void collect_slot(const FtgpEnv* e, int slot, double* out)
 int use_table(FtgpEnv* e, int which)
 {
     if (e->table_on_device == which) return 0;
-    HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(e->d_params.get()) + offsetof(DeviceParams, car_policy), e->h_tables.get() + which * FTGP_MAX_CARS_PER_BLOCK,
-                           sizeof e->P.car_policy, hipMemcpyHostToDevice, e->stream.get()));
+    for (size_t b : e->blocks)        // every track's parameter block
+        HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(e->d_params.get()) + b + offsetof(DeviceParams, car_policy), e->h_tables.get() + which * FTGP_MAX_CARS_PER_BLOCK,
+                               sizeof e->P.car_policy, hipMemcpyHostToDevice, e->stream.get()));
     e->table_on_device = which;
     return 0;
 }
@@ -596,8 +731,7 @@ int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
     }
     HIP_TRY(hipSetDevice(e->device));
     if (policy == FTGP_POLICY_PER_CAR && n_steps > 0 && e->h_tables) if (int rc = use_table(e, device_io ? 1 : 0)) return rc;
-    const int cpb = e->P.cars_per_block;
-    const int blocks = (e->P.n_cars + cpb - 1) / cpb;
+    const int blocks = e->grid;
     const int slot = e->cur_slot ^ 1;
     // an exchange that is still reading this launch's slot (begin without end, two launches ago) goes first: over RCCL on the device (the
     // side stream's event); with one rank the "exchange" is the record in pinned memory, which is put aside before the slot is reused
@@ -673,44 +807,70 @@ int check_device_buffer(FtgpEnv* e, const void* p, size_t bytes, const char* nam
     return 0;
 }
 
-// ftgp_create, step 3: the upload -- allocate, copy, search the box field (or the distance transform), write the images
-int upload(FtgpEnv* e, const FtgpTrack& t, const Plan& pl)
+// ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images.  tracks:
+// n_tracks = 1 + pl.more.size() of them.
+int upload(FtgpEnv* e, const FtgpTrack* tracks, const Plan& pl)
 {
     memcpy(&e->P, &pl.P, sizeof e->P);          // as it lies, padding included
     DeviceParams& P = e->P;
     hipStream_t s = e->stream.get();
-    const size_t plane = (size_t)t.width * t.height, n_cars = (size_t)P.n_cars;
-    if (P.lidar_mode == FTGP_LIDAR_FAKELIDAR) {
-        // The distance transform of custom.py:1149-1153 / raycast.py:24-27 (scipy.ndimage.distance_transform_edt of the non-wall
-        // mask) without scipy, exact: the squared distance is the minimum over the columns x' of (x - x')^2 + g(x', y)^2 with g the
-        // vertical distance to the nearest wall of column x' -- the run lengths above -- in integers; one correctly rounded sqrt.
-        DevBuf<uint16_t> d_runy;
-        HIP_TRY(dev_upload(d_runy, pl.tab.runy.data(), 2 * plane * sizeof(uint16_t)));
-        HIP_TRY(dev_alloc(e->d_edt, plane * sizeof(double)));
-        HIP_TRY(dev_upload(e->d_fan, pl.fan.data(), pl.fan.size() * sizeof(double)));
-        hipLaunchKernelGGL(ftgp_edt_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, d_runy.get(), t.width, t.height, e->d_edt.get());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));
-        P.edt = e->d_edt.get(); P.fan_dirs = e->d_fan.get();
-    } else {   // sector box field: upload the run lengths, search the boxes on the device
-        const size_t plane_cells = (size_t)P.plane256 * 128;
-        DevBuf<uint16_t> d_runx, d_runy;
-        HIP_TRY(dev_alloc(e->d_field, plane_cells * (size_t)P.n_planes * sizeof(uint16_t)));
-        HIP_TRY(dev_upload(d_runx, pl.tab.runx.data(), 2 * plane * sizeof(uint16_t)));
-        HIP_TRY(dev_upload(d_runy, pl.tab.runy.data(), 2 * plane * sizeof(uint16_t)));
-        hipLaunchKernelGGL(ftgp_box_field_kernel, dim3((unsigned)((plane_cells * P.n_sectors + 255) / 256)), dim3(256), 0, s, d_runx.get(), d_runy.get(), t.width, t.height, P.n_sectors, e->d_field.get());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));
-        P.field = e->d_field.get();
+    const int T = 1 + (int)pl.more.size();
+    const size_t n_cars = (size_t)P.n_cars;
+    e->n_tracks = T;
+    e->trk.resize((size_t)T);
+    auto block_of = [&](int t) -> const DeviceParams& { return t == 0 ? pl.P : pl.more[(size_t)t - 1].P; };
+    if (P.lidar_mode == FTGP_LIDAR_FAKELIDAR) HIP_TRY(dev_upload(e->d_fan, pl.fan.data(), pl.fan.size() * sizeof(double)));
+    for (int k = 0; k < T; ++k) {
+        const FtgpTrack& t = tracks[k];
+        const DeviceParams& Q = block_of(k);
+        const HostTables& tab = k == 0 ? pl.tab : pl.more[(size_t)k - 1].tab;
+        TrackBufs& b = e->trk[(size_t)k];
+        b.width = t.width; b.height = t.height;
+        const size_t plane = (size_t)t.width * t.height;
+        size_t field_bytes = 0;
+        if (P.lidar_mode == FTGP_LIDAR_FAKELIDAR) {
+            // The distance transform of custom.py:1149-1153 / raycast.py:24-27 (scipy.ndimage.distance_transform_edt of the non-wall
+            // mask) without scipy, exact: the squared distance is the minimum over the columns x' of (x - x')^2 + g(x', y)^2 with g the
+            // vertical distance to the nearest wall of column x' -- the run lengths above -- in integers; one correctly rounded sqrt.
+            DevBuf<uint16_t> d_runy;
+            HIP_TRY(dev_upload(d_runy, tab.runy.data(), 2 * plane * sizeof(uint16_t)));
+            field_bytes = plane * sizeof(double);
+            HIP_TRY(dev_alloc(b.edt, field_bytes));
+            hipLaunchKernelGGL(ftgp_edt_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, d_runy.get(), t.width, t.height, b.edt.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
+        } else {   // sector box field: upload the run lengths, search the boxes on the device
+            const size_t plane_cells = (size_t)Q.plane256 * 128;
+            DevBuf<uint16_t> d_runx, d_runy;
+            field_bytes = plane_cells * (size_t)Q.n_planes * sizeof(uint16_t);
+            HIP_TRY(dev_alloc(b.field, field_bytes));
+            HIP_TRY(dev_upload(d_runx, tab.runx.data(), 2 * plane * sizeof(uint16_t)));
+            HIP_TRY(dev_upload(d_runy, tab.runy.data(), 2 * plane * sizeof(uint16_t)));
+            hipLaunchKernelGGL(ftgp_box_field_kernel, dim3((unsigned)((plane_cells * Q.n_sectors + 255) / 256)), dim3(256), 0, s, d_runx.get(), d_runy.get(), t.width, t.height, Q.n_sectors, b.field.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        const size_t sz_bits = sizeof(uint32_t) * (size_t)t.height * t.words_per_row;
+        HIP_TRY(dev_upload(b.bits, tab.bits.data(), sz_bits));
+        HIP_TRY(dev_upload(b.nearbits, tab.nearbits.data(), sz_bits));
+        if (getenv("FTGP_VERBOSE"))
+            fprintf(stderr, "ftgp_create: track %d: %d x %d px, %.1f MB of %s + %.1f MB of wall bitmaps\n", k, t.width, t.height, field_bytes / 1e6,
+                    P.lidar_mode == FTGP_LIDAR_FAKELIDAR ? "distance transform" : "box field", 2.0 * sz_bits / 1e6);
     }
-    const size_t sz_bits = sizeof(uint32_t) * (size_t)t.height * t.words_per_row, sz_path = sizeof(double) * 2 * FTGP_PATH_POINTS;
+    const size_t sz_path = sizeof(double) * 2 * FTGP_PATH_POINTS, sz_spawn = sizeof(double) * 4 * FTGP_PATH_POINTS;
+    {   // centre-lines and spawn tables of all tracks, track after track
+        std::vector<double> paths(2 * FTGP_PATH_POINTS * (size_t)T), spawns(4 * FTGP_PATH_POINTS * (size_t)T);
+        for (int k = 0; k < T; ++k) {
+            memcpy(paths.data() + 2 * FTGP_PATH_POINTS * (size_t)k, tracks[k].path, sz_path);
+            memcpy(spawns.data() + 4 * FTGP_PATH_POINTS * (size_t)k, (k == 0 ? pl.spawn : pl.more[(size_t)k - 1].spawn).data(), sz_spawn);
+        }
+        HIP_TRY(dev_upload(e->d_path, paths.data(), sz_path * T));
+        HIP_TRY(dev_upload(e->d_spawn, spawns.data(), sz_spawn * T));
+    }
     HIP_TRY(dev_upload(e->d_veh, pl.veh.data(), pl.veh.size()));
-    HIP_TRY(dev_upload(e->d_bits, pl.tab.bits.data(), sz_bits));
-    HIP_TRY(dev_upload(e->d_nearbits, pl.tab.nearbits.data(), sz_bits));
-    HIP_TRY(dev_upload(e->d_path, t.path, sz_path));
     HIP_TRY(dev_upload(e->d_ray, pl.ray.data(), sizeof(float) * pl.ray.size()));
-    HIP_TRY(dev_upload(e->d_spawn, pl.spawn.data(), sizeof(double) * pl.spawn.size()));
     HIP_TRY(dev_upload(e->d_cover, pl.cover.data(), sizeof(float) * pl.cover.size()));
+    if (T > 1) HIP_TRY(dev_upload(e->d_env_track, pl.env_track.data(), sizeof(int32_t) * pl.env_track.size()));
     // zeroed on the handle's own stream: a non-blocking stream is not ordered against the null stream, and ftgp_reset() runs on it
     HIP_TRY(dev_zeros(e->d_cars, sizeof(CarState) * n_cars, s)); HIP_TRY(dev_zeros(e->d_ranges, sizeof(float) * n_cars * P.ranges_stride, s));
     HIP_TRY(dev_zeros(e->d_steps, sizeof(int64_t) * (size_t)P.n_envs, s)); HIP_TRY(dev_alloc(e->d_env_mask, (size_t)P.n_envs)); HIP_TRY(dev_alloc(e->d_car_mask, n_cars));
@@ -718,41 +878,88 @@ int upload(FtgpEnv* e, const FtgpTrack& t, const Plan& pl)
     HIP_TRY(dev_alloc(e->d_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2));
     HIP_TRY(host_alloc(e->h_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2, hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer((void**)&e->h_metrics_dev, e->h_metrics.get(), 0));
+    e->grid = pl.n_wg;
+    double* wg_metrics_host = nullptr;
     if (!getenv("FTGP_NO_FUSED_METRICS")) {          // (diagnostic switch: tests compare the fused record with ftgp_metrics_kernel's)
-        const size_t blocks = (n_cars + (size_t)P.cars_per_block - 1) / (size_t)P.cars_per_block;
+        const size_t blocks = (size_t)pl.n_wg;
         HIP_TRY(dev_alloc(e->d_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * blocks));
         HIP_TRY(dev_zeros(e->d_wg_ticket, sizeof(unsigned int), s));
-        P.wg_metrics = e->d_wg_metrics.get(); P.wg_ticket = e->d_wg_ticket.get(); P.metrics_dev = e->d_metrics.get(); P.metrics_host = e->h_metrics_dev;
         e->n_blocks = (int)blocks;
         if (!getenv("FTGP_NO_HOST_SUM")) {           // (diagnostic switch: the device-side hand-off of the record also with one rank)
             HIP_TRY(host_alloc(e->h_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2 * blocks, hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer((void**)&P.wg_metrics_host, e->h_wg_metrics.get(), 0));
+            HIP_TRY(hipHostGetDevicePointer((void**)&wg_metrics_host, e->h_wg_metrics.get(), 0));
         }
     }
     HIP_TRY(dev_alloc(e->d_prog, sizeof(int32_t) * FTGP_PROGRESS_INTS * n_cars)); HIP_TRY(dev_alloc(e->d_core, sizeof(double) * kCoreDoubles * n_cars));
-    P.bits = e->d_bits.get(); P.nearbits = e->d_nearbits.get(); P.path = e->d_path.get(); P.spawn = e->d_spawn.get(); P.veh_dev = e->d_veh.get();
-    P.ray_dir = e->d_ray.get(); P.cover_thr = e->d_cover.get(); P.cars = e->d_cars.get(); P.ranges = e->d_ranges.get(); P.steps = e->d_steps.get();
-    {   // the staging image: the LDS bytes [off_params, off_cars) as every workgroup wants them, then both drivers' cover tables
-        const size_t head = (size_t)(P.off_cars - P.off_params), cover = (size_t)P.stage_cover, stride = (size_t)P.cover_kmax + 1;
-        std::vector<unsigned char> simg(head + 2 * cover, 0);
-        memcpy(simg.data(), &P, offsetof(DeviceParams, veh));      // every pointer of the head is set by now
-        memcpy(simg.data() + (P.off_veh - P.off_params), pl.veh.data(), pl.veh.size());
-        memcpy(simg.data() + (P.off_path - P.off_params), t.path, sz_path);
-        memcpy(simg.data() + (P.off_ray - P.off_params), pl.ray.data(), sizeof(float) * pl.ray.size());
-        memcpy(simg.data() + head, pl.cover.data(), sizeof(float) * stride);
-        memcpy(simg.data() + head + cover, pl.cover.data() + stride, sizeof(float) * stride);
-        HIP_TRY(dev_upload(e->d_stage, simg.data(), simg.size()));
-        P.stage_img = e->d_stage.get();
+    // the device image of the parameter blocks: track 0's block | (several tracks: the workgroup table) | the sweep's task tables | the
+    // blocks of tracks 1 .. T - 1
+    const size_t head = FTGP_PARAMS_BYTES, wg_bytes = T > 1 ? sizeof(int32_t) * pl.wg.size() : 0, tasks_bytes = sizeof(int32_t) * pl.tasks.size();
+    e->blocks.assign((size_t)T, 0);
+    for (int k = 1; k < T; ++k) e->blocks[(size_t)k] = head + wg_bytes + tasks_bytes + (size_t)(k - 1) * head;
+    std::vector<unsigned char> pimg(head + wg_bytes + tasks_bytes + (size_t)(T - 1) * head + 16, 0);
+    HIP_TRY(dev_alloc(e->d_params, pimg.size()));
+    // the staging images, one per track: the LDS bytes [off_params, off_cars) as every workgroup of the track wants them, then both drivers' cover tables
+    const size_t stage_head = (size_t)(P.off_cars - P.off_params), cover = (size_t)P.stage_cover, stride = (size_t)P.cover_kmax + 1;
+    const size_t stage_bytes = stage_head + 2 * cover;
+    HIP_TRY(dev_alloc(e->d_stage, stage_bytes * T));
+    std::vector<unsigned char> simg(stage_bytes * T, 0);
+    for (int k = 0; k < T; ++k) {
+        DeviceParams Q = block_of(k);        // (a copy as it lies, padding included)
+        const TrackBufs& b = e->trk[(size_t)k];
+        Q.edt = b.edt.get(); Q.fan_dirs = e->d_fan.get(); Q.field = b.field.get();
+        if (e->d_wg_metrics) { Q.wg_metrics = e->d_wg_metrics.get(); Q.wg_ticket = e->d_wg_ticket.get(); Q.metrics_dev = e->d_metrics.get(); Q.metrics_host = e->h_metrics_dev; }
+        Q.wg_metrics_host = wg_metrics_host;
+        Q.bits = b.bits.get(); Q.nearbits = b.nearbits.get(); Q.path = e->d_path.get() + 2 * FTGP_PATH_POINTS * (size_t)k; Q.spawn = e->d_spawn.get() + 4 * FTGP_PATH_POINTS * (size_t)k;
+        Q.veh_dev = e->d_veh.get();
+        Q.ray_dir = e->d_ray.get(); Q.cover_thr = e->d_cover.get(); Q.cars = e->d_cars.get(); Q.ranges = e->d_ranges.get(); Q.steps = e->d_steps.get();
+        unsigned char* im = simg.data() + stage_bytes * k;
+        memcpy(im, &Q, offsetof(DeviceParams, veh));      // every pointer of the head is set by now
+        memcpy(im + (P.off_veh - P.off_params), pl.veh.data(), pl.veh.size());
+        memcpy(im + (P.off_path - P.off_params), tracks[k].path, sz_path);
+        memcpy(im + (P.off_ray - P.off_params), pl.ray.data(), sizeof(float) * pl.ray.size());
+        memcpy(im + stage_head, pl.cover.data(), sizeof(float) * stride);
+        memcpy(im + stage_head + cover, pl.cover.data() + stride, sizeof(float) * stride);
+        Q.stage_img = e->d_stage.get() + stage_bytes * k;
+        Q.task_tab = reinterpret_cast<const int32_t*>(reinterpret_cast<unsigned char*>(e->d_params.get()) + head + wg_bytes);
+        memcpy(pimg.data() + e->blocks[(size_t)k], &Q, sizeof(DeviceParams));
+        if (k == 0) memcpy(&P, &Q, sizeof P);
     }
-    {   // device image of the parameter block, and behind it the sweep's task tables
-        const size_t head = (size_t)pad16(sizeof(DeviceParams));
-        std::vector<unsigned char> pimg(head + sizeof(int32_t) * pl.tasks.size() + 16, 0);
-        HIP_TRY(dev_alloc(e->d_params, pimg.size()));
-        P.task_tab = reinterpret_cast<const int32_t*>(reinterpret_cast<unsigned char*>(e->d_params.get()) + head);
-        memcpy(pimg.data(), &P, sizeof(DeviceParams));
-        memcpy(pimg.data() + head, pl.tasks.data(), sizeof(int32_t) * pl.tasks.size());
-        HIP_TRY(hipMemcpy(e->d_params.get(), pimg.data(), pimg.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_stage.get(), simg.data(), simg.size(), hipMemcpyHostToDevice));
+    if (T > 1) {     // the workgroup table: each entry's block offset
+        std::vector<int32_t> wg = pl.wg;
+        for (size_t b = 0; b < wg.size(); b += 4) wg[b] = (int32_t)e->blocks[(size_t)wg[b + 3]];
+        memcpy(pimg.data() + head, wg.data(), wg_bytes);
     }
+    memcpy(pimg.data() + head + wg_bytes, pl.tasks.data(), tasks_bytes);
+    HIP_TRY(hipMemcpy(e->d_params.get(), pimg.data(), pimg.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ftgp_create / ftgp_create_tracks after the checks: device probe, plan, upload, reset.  envs_per_track: null for ftgp_create's one track.
+int create(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, FtgpEnv** out)
+{
+    if (int rc = open_device(cfg.device_id)) return rc;
+    // FTGP_WAIT_SPIN=1: the host waits for a launch by spinning instead of blocking on the interrupt (hipDeviceScheduleSpin: a CPU core per
+    // waiting handle for a shorter wake-up; measured: tools/launch_host.sh).  Best effort: a device that is already active keeps its flags.
+    if (const char* sv = getenv("FTGP_WAIT_SPIN")) { if (atoi(sv) == 1) (void)hipSetDeviceFlags(hipDeviceScheduleSpin); (void)hipGetLastError(); }
+    hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, cfg.device_id));
+    const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    Plan pl;
+    if (n_tracks > 1) { if (int rc = plan_tracks(cfg, tracks, envs_per_track, n_tracks, n_cu, pl)) return rc; }
+    else {
+        FtgpConfig c0 = cfg;
+        c0.track = tracks[0];
+        if (int rc = plan_create(c0, n_cu, pl)) return rc;
+    }
+    std::unique_ptr<FtgpEnv, int (*)(FtgpEnv*)> e(new FtgpEnv(), ftgp_destroy);
+    e->device = cfg.device_id; e->multi = cfg.cars_per_env > 1; e->ext_launch = !getenv("FTGP_LAUNCH_PLAIN");
+    HIP_TRY(make_stream(e->stream)); HIP_TRY(make_stream(e->side));
+    HIP_TRY(make_event(e->ev_start, hipEventDefault)); HIP_TRY(make_event(e->ev_stop[0], hipEventDefault)); HIP_TRY(make_event(e->ev_stop[1], hipEventDefault));
+    HIP_TRY(make_event(e->ev_metrics, hipEventDisableTiming)); HIP_TRY(make_event(e->ev_gather, hipEventDisableTiming));
+    for (const auto& set : kStepKernels) for (const auto& row : set) for (const StepKernel& k : row) HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (int rc = upload(e.get(), tracks, pl)) return rc;
+    if (int rc = ftgp_reset(e.get(), nullptr)) return rc;
+    *out = e.release();
     return 0;
 }
 
@@ -844,24 +1051,24 @@ int ftgp_create(const FtgpConfig* cfg, FtgpEnv** out)
 {
     if (!cfg || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     *out = nullptr;
-    if (int rc = validate(*cfg)) return rc;
-    if (int rc = open_device(cfg->device_id)) return rc;
-    // FTGP_WAIT_SPIN=1: the host waits for a launch by spinning instead of blocking on the interrupt (hipDeviceScheduleSpin: a CPU core per
-    // waiting handle for a shorter wake-up; measured: tools/launch_host.sh).  Best effort: a device that is already active keeps its flags.
-    if (const char* sv = getenv("FTGP_WAIT_SPIN")) { if (atoi(sv) == 1) (void)hipSetDeviceFlags(hipDeviceScheduleSpin); (void)hipGetLastError(); }
-    hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, cfg->device_id));
-    Plan pl;
-    if (int rc = plan_create(*cfg, prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, pl)) return rc;
-    std::unique_ptr<FtgpEnv, int (*)(FtgpEnv*)> e(new FtgpEnv(), ftgp_destroy);
-    e->device = cfg->device_id; e->multi = cfg->cars_per_env > 1; e->ext_launch = !getenv("FTGP_LAUNCH_PLAIN");
-    HIP_TRY(make_stream(e->stream)); HIP_TRY(make_stream(e->side));
-    HIP_TRY(make_event(e->ev_start, hipEventDefault)); HIP_TRY(make_event(e->ev_stop[0], hipEventDefault)); HIP_TRY(make_event(e->ev_stop[1], hipEventDefault));
-    HIP_TRY(make_event(e->ev_metrics, hipEventDisableTiming)); HIP_TRY(make_event(e->ev_gather, hipEventDisableTiming));
-    for (const auto& row : kStepKernels) for (const StepKernel& k : row) HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (int rc = upload(e.get(), cfg->track, pl)) return rc;
-    if (int rc = ftgp_reset(e.get(), nullptr)) return rc;
-    *out = e.release();
-    return 0;
+    if (int rc = validate(*cfg, &cfg->track, 1, false)) return rc;
+    return create(*cfg, &cfg->track, nullptr, 1, out);
+}
+
+int ftgp_create_tracks(const FtgpConfig* cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, FtgpEnv** out)
+{
+    if (!cfg || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    *out = nullptr;
+    if (n_tracks < 1 || n_tracks > FTGP_MAX_TRACKS) return failf(FTGP_ERR_ARG, "ftgp_create_tracks: n_tracks = %d, not in 1 .. %d", n_tracks, FTGP_MAX_TRACKS);
+    if (!tracks || !envs_per_track) return fail(FTGP_ERR_ARG, "ftgp_create_tracks: null tracks / envs_per_track%s");
+    long long sum = 0;
+    for (int k = 0; k < n_tracks; ++k) {
+        if (envs_per_track[k] < 1) return failf(FTGP_ERR_ARG, "track %d: envs_per_track = %d, at least 1 env per track", k, (int)envs_per_track[k]);
+        sum += envs_per_track[k];
+    }
+    if (sum != cfg->n_envs) return failf(FTGP_ERR_ARG, "ftgp_create_tracks: envs_per_track sums to %lld, n_envs is %d", sum, cfg->n_envs);
+    if (int rc = validate(*cfg, tracks, n_tracks, true)) return rc;
+    return create(*cfg, tracks, envs_per_track, n_tracks, out);
 }
 
 int ftgp_reset(FtgpEnv* e, const uint8_t* mask)
@@ -874,7 +1081,7 @@ int ftgp_reset(FtgpEnv* e, const uint8_t* mask)
         HIP_TRY(hipMemcpyAsync(e->d_env_mask.get(), mask, (size_t)e->P.n_envs, hipMemcpyHostToDevice, e->stream.get()));
         dmask = e->d_env_mask.get();
     }
-    hipLaunchKernelGGL(ftgp_reset_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P, dmask);
+    hipLaunchKernelGGL(ftgp_reset_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P, dmask, (const int32_t*)e->d_env_track.get());
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(ftgp_zero_ranges_kernel, dim3(e->P.n_cars), dim3(256), 0, e->stream.get(), e->P, dmask);
     HIP_TRY(hipGetLastError());
@@ -920,8 +1127,9 @@ int ftgp_set_car_policies(FtgpEnv* e, const int32_t* policies)
     // a workgroup holds whole envs, so its car slot c runs the roster's entry c % cars_per_env
     for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->P.car_policy[c] = policies[c % e->P.cars_per_env];
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the block while it changes
-    HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(e->d_params.get()) + offsetof(DeviceParams, car_policy), e->P.car_policy, sizeof e->P.car_policy, hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the blocks while they change
+    for (size_t b : e->blocks)        // every track's parameter block
+        HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(e->d_params.get()) + b + offsetof(DeviceParams, car_policy), e->P.car_policy, sizeof e->P.car_policy, hipMemcpyHostToDevice));
     if (e->h_tables) memcpy(e->h_tables.get(), e->P.car_policy, sizeof e->P.car_policy);    // (no copy from it is pending: the stream is idle)
     e->table_on_device = 0;
     return 0;
@@ -960,6 +1168,7 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
     A.max_episode_steps = cfg->max_episode_steps; A.n_ext = n_ext; A.auto_reset = cfg->auto_reset ? 1 : 0;
     for (int k = 0, i = 0; k < FTGP_PAIR_STRIDE; ++k) A.ext_index[k] = (k < cpe && slot[k] == FTGP_POLICY_HOST) ? i++ : -1;
     A.prev_abs = e->d_prev_abs.get();
+    A.env_track = e->d_env_track.get();
     e->io_repeat = cfg->action_repeat;
     e->io_ready = true;
     return 0;
@@ -1076,7 +1285,7 @@ int ftgp_eval_progress(FtgpEnv* e)
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     e->rows_valid = false; e->launch_metrics_valid = false;
     HIP_TRY(hipSetDevice(e->device));
-    hipLaunchKernelGGL(ftgp_progress_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P);
+    hipLaunchKernelGGL(ftgp_progress_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P, (const int32_t*)e->d_env_track.get());
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1198,6 +1407,7 @@ int ftgp_comm_init(FtgpEnv* e, const uint8_t id[128], int rank, int world_size)
 {
     if (!e || !id || world_size < 1 || rank < 0 || rank >= world_size) return fail(FTGP_ERR_ARG, "bad comm arguments%s");
     if (e->comm) return fail(FTGP_ERR_STATE, "the handle already has a communicator%s");
+    if (e->n_tracks > 1) return fail(FTGP_ERR_STATE, "ftgp_comm_init: multi-rank runs of a multi-track handle are not supported%s");
     if (int rc = load_rccl()) return rc;
     HIP_TRY(hipSetDevice(e->device));
     Id128 uid; memcpy(uid.internal, id, 128);
@@ -1274,13 +1484,22 @@ int ftgp_metrics_allgather(FtgpEnv* e, double* out)
     return ftgp_metrics_allgather_end(e, out);
 }
 
+int ftgp_get_track_distance_field(FtgpEnv* e, int track, double* out)
+{
+    if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    if (track < 0 || track >= e->n_tracks) return failf(FTGP_ERR_ARG, "get_track_distance_field: track %d of a handle with %d", track, e->n_tracks);
+    const TrackBufs& b = e->trk[(size_t)track];
+    if (!b.edt) return fail(FTGP_ERR_STATE, "no distance field: the handle was not created with lidar_mode = FTGP_LIDAR_FAKELIDAR%s");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy(out, b.edt.get(), sizeof(double) * (size_t)b.width * b.height, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int ftgp_get_distance_field(FtgpEnv* e, double* out)
 {
     if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
-    if (!e->d_edt) return fail(FTGP_ERR_STATE, "no distance field: the handle was not created with lidar_mode = FTGP_LIDAR_FAKELIDAR%s");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpy(out, e->d_edt.get(), sizeof(double) * (size_t)e->P.width * e->P.height, hipMemcpyDeviceToHost));
-    return 0;
+    if (e->n_tracks > 1) return fail(FTGP_ERR_STATE, "get_distance_field: the handle has several tracks (ftgp_get_track_distance_field)%s");
+    return ftgp_get_track_distance_field(e, 0, out);
 }
 
 int ftgp_fakelidar(int device_id, const double* dt, int H, int W, int n_origins, const double* origins, int rangefinders,

@@ -127,6 +127,10 @@ struct DeviceParams {
                                   // the second table is for launches whose drivers do not read the scan: window classes 0, no ray 0
 };
 
+// Bytes of one parameter block in device memory.  Multi-track handles (ftgp_create_tracks): the workgroup table follows track 0's block,
+// int4 per workgroup = (byte offset of its track's block from track 0's, first car, number of cars, track).
+#define FTGP_PARAMS_BYTES ((sizeof(DeviceParams) + 15) & ~(size_t)15)
+
 // vehicle constants as staged into LDS
 struct VehLds {
     FtgpVehicle v;

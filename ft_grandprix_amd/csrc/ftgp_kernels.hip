@@ -1,6 +1,6 @@
 // ftgp_kernels.hip -- HIP kernels of the ft_grandprix hot path for gfx950 (CDNA4, wave64).
 //
-//   ftgp_step_kernel<MULTI, FAKE, ROSTER>   n_steps per launch; one workgroup = whole envs, up to 16 cars on up to 16 waves (the headline
+//   ftgp_step_kernel<MULTI, FAKE, ROSTER, TRACKS>   n_steps per launch; one workgroup = whole envs, up to 16 cars on up to 16 waves (the headline
 //       shape is 8 cars on 16 waves, two workgroups per CU), persistent over all steps.  ONE workgroup barrier per step.  Inside a
 //       step, concurrently:
 //         K5       waves 0 .. cars-1, one car each: the driver on the car's PREVIOUS scan (the other LDS scan buffer) -> controls
@@ -16,6 +16,7 @@
 //       centre-line, ray table, cover tables; then the cars' state records and the scan windows the drivers read.  The march reads the
 //       sector box field from L2 (ftgp_march.h).  FAKE: K2 is the reference's own 2-D LiDAR (lidar_fake).  ROSTER: every car slot its own driver.
 //       The end-of-launch metrics record is part of the kernel (launch_metrics).
+//       TRACKS: multi-track handles (ftgp_create_tracks) -- each workgroup looks up its track and first car at entry, then stages and races that track.
 //   ftgp_policy_kernel    K5 alone (ftgp_policy_eval).
 //   ftgp_reset_kernel     K4 reset / spawn (+ K3 at the spawn pose), one car per lane.
 //   ftgp_progress_kernel  K3 alone (after ftgp_set_pose), one car per lane.
@@ -1571,10 +1572,24 @@ __device__ __forceinline__ void stage16(void* dst, const void* src, int bytes)
 // ROSTER: `policy` may be FTGP_POLICY_PER_CAR (every car slot its own driver, ftgp_set_car_policies) -- again its own instantiation, so
 // that the single-driver kernels stay exactly what they were (the multi-car one lost 3 % to the run-time form of this test); the
 // FAKELIDAR kernels, which are for parity and not for throughput, exist in the ROSTER form only.
-template <bool MULTI, bool FAKE, bool ROSTER>
+// TRACKS: the instantiations of multi-track handles (ftgp_create_tracks): the workgroups of a launch race different tracks, each workgroup
+// one.  With TRACKS = false the code is exactly the one-track kernel's.
+template <bool MULTI, bool FAKE, bool ROSTER, bool TRACKS>
 __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(const DeviceParams* __restrict__ Pg, int policy, int n_steps, int metrics_slot)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    // TRACKS: Pg is track 0's parameter block.  The workgroup's entry in the table behind it (ftgp_create_tracks) names the block of the
+    // workgroup's track, Pt (byte offset from track 0's), its first car and its number of cars: scalar loads, once per launch.  From here
+    // on the workgroup runs the one-track code on its track's staging image and block.  (The LDS layout is the same in every block: the
+    // offsets are read from Pg, as with one track.)
+    const DeviceParams* Pt = Pg;
+    int wg_first = 0, wg_cars = 0;
+    if (TRACKS) {
+        typedef const __attribute__((address_space(4))) int* ScalarInts4;
+        const ScalarInts4 ent = reinterpret_cast<ScalarInts4>(reinterpret_cast<uint64_t>(Pg) + FTGP_PARAMS_BYTES) + 4 * blockIdx.x;
+        Pt = reinterpret_cast<const DeviceParams*>(reinterpret_cast<const unsigned char*>(Pg) + ent[0]);
+        wg_first = ent[1]; wg_cars = ent[2];
+    }
     const DeviceParams& P0 = *reinterpret_cast<const DeviceParams*>(lds + Pg->off_params);   // valid after staging + barrier
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1587,7 +1602,7 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
         // (the cover table of the launch's driver; FTGP_POLICY_PER_CAR: both, nidc's first)
         const int head = Pg->off_cars - Pg->off_params;
         const int cover = (policy == FTGP_POLICY_NIDC || policy == FTGP_POLICY_FAST) ? Pg->stage_cover : (ROSTER && policy == FTGP_POLICY_PER_CAR) ? 2 * Pg->stage_cover : 0;
-        const uint4* img = reinterpret_cast<const uint4*>(Pg->stage_img);
+        const uint4* img = reinterpret_cast<const uint4*>(TRACKS ? scalar_view(Pt)->stage_img : Pg->stage_img);
         const uint4* cov = img + ((head + (policy == FTGP_POLICY_FAST ? Pg->stage_cover : 0)) >> 4);
         uint4* d_head = reinterpret_cast<uint4*>(lds + Pg->off_params);
         uint4* d_cov = reinterpret_cast<uint4*>(lds + Pg->off_cover);
@@ -1601,8 +1616,8 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
     __syncthreads();
     const LdsOffsets off = lds_offsets(P0);
     const int cpb = sgpr(P0.cars_per_block);
-    const int ci0 = FTGP_DIAG_WG_GROUP((int)blockIdx.x) * cpb;
-    const int ncars_here = min(cpb, sgpr(P0.n_cars) - ci0);
+    const int ci0 = TRACKS ? wg_first : FTGP_DIAG_WG_GROUP((int)blockIdx.x) * cpb;
+    const int ncars_here = TRACKS ? wg_cars : min(cpb, sgpr(P0.n_cars) - ci0);
     const bool second_half = (((int)blockIdx.x / max(1, sgpr(P0.n_cu))) & 1) != 0;      // see sweep_priority(): workgroups b and b + n_cu share a CU in the first dispatch wave
     const bool need_scan = (policy == FTGP_POLICY_NIDC || policy == FTGP_POLICY_FAST || (ROSTER && policy == FTGP_POLICY_PER_CAR));
     {
@@ -1633,7 +1648,7 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
         if (c < ncars_here) pair_cull_write(L.frame, L.pairs, c, k, P.cars_per_env, L.veh->cull_radius, (float)L.veh->v.lidar_ring_radius);
         __syncthreads();
         if (wave == 0)
-            mate_masks(L.frame, L.pairs, L.mmask, P.mmask_stride, &scalar_view(Pg)->group_order[0], L.ray, P.n_rays, P.tasks_per_car, P.cars_per_env, L.veh->cull_radius, P.group_cg, P.group_sg,
+            mate_masks(L.frame, L.pairs, L.mmask, P.mmask_stride, &scalar_view(Pt)->group_order[0], L.ray, P.n_rays, P.tasks_per_car, P.cars_per_env, L.veh->cull_radius, P.group_cg, P.group_sg,
                        ncars_here, lane_here(), FTGP_WAVE);
     }
     }
@@ -1653,7 +1668,7 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
         // through fresh offsets: nothing of this is carried -- spilled -- from step to step or across the other phase.
         const int par = it & 1;
         if (wave < ncars_here) {         // drivers (and, for the wave that delivers last, dynamics)
-            const ScalarParams G = scalar_view(Pg);
+            const ScalarParams G = scalar_view(Pt);
             const LdsOffsets off = lds_offsets(G);
             const DeviceParams& P = *reinterpret_cast<const DeviceParams*>(lds + off.params);
             const Lds L = lds_view(off, lds);
@@ -1690,7 +1705,7 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
         }
         STAMP(t3);
         if (FTGP_DIAG_RUN_K2) {
-            const ScalarParams G = scalar_view(Pg);
+            const ScalarParams G = scalar_view(Pt);
             const LdsOffsets off = lds_offsets(G);
             const DeviceParams& P = *reinterpret_cast<const DeviceParams*>(lds + off.params);
             const Lds L = lds_view(off, lds);
@@ -1706,7 +1721,7 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
 
     STAMP_FLUSH();
     const DeviceParams& P = P0;
-    const LdsOffsets off_end = lds_offsets(scalar_view(Pg));
+    const LdsOffsets off_end = lds_offsets(scalar_view(Pt));
     const Lds L = lds_view(off_end, lds);
     for (int c = wave; c < ncars_here; c += nwaves) {
         const int ci = ci0 + c;
@@ -1724,12 +1739,18 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
     FTGP_DIAG_WG_EXIT();
 }
 
-template __global__ void ftgp_step_kernel<false, false, false>(const DeviceParams*, int, int, int);
-template __global__ void ftgp_step_kernel<true, false, false>(const DeviceParams*, int, int, int);
-template __global__ void ftgp_step_kernel<false, false, true>(const DeviceParams*, int, int, int);
-template __global__ void ftgp_step_kernel<true, false, true>(const DeviceParams*, int, int, int);
-template __global__ void ftgp_step_kernel<false, true, true>(const DeviceParams*, int, int, int);
-template __global__ void ftgp_step_kernel<true, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, false, false>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, false, false>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, false>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, false>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, true, true, false>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, true, true, false>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, true, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, true, true, true>(const DeviceParams*, int, int, int);
 
 // K5 alone: one wave per car evaluates the driver on the scan stored in P.ranges (ftgp_policy_eval).
 __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int policy, double* __restrict__ ctrl_out)
@@ -1761,11 +1782,16 @@ __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int po
 // =============================================================================================
 // K4: reset / spawn (custom.py:1089-1128, 1232-1245, 81-87), one car per lane; then K3 at the spawn pose.
 // =============================================================================================
-__device__ __forceinline__ void progress_lane(const DeviceParams& P, CarCore& s, int64_t steps, double* __restrict__ times)
+// Multi-track handles: the track of every env (env_track, [n_envs]; null with one track).  Track t's centre-line and spawn table sit
+// t tables behind track 0's (P.path, P.spawn).
+__device__ __forceinline__ int env_track_of(const int32_t* __restrict__ env_track, int env) { return env_track ? env_track[env] : 0; }
+
+// path: the centre-line of the car's track
+__device__ __forceinline__ void progress_lane(const DeviceParams& P, const double* __restrict__ path, CarCore& s, int64_t steps, double* __restrict__ times)
 {
     double best = 0.0; int closest = 0;
     for (int i = 0; i < FTGP_PATH_POINTS; ++i) {
-        const double dx = P.path[2 * i] - s.x, dy = P.path[2 * i + 1] - s.y;
+        const double dx = path[2 * i] - s.x, dy = path[2 * i + 1] - s.y;
         const double d = dx * dx + dy * dy;
         if (i == 0 || d < best) { best = d; closest = i; }
     }
@@ -1776,16 +1802,18 @@ __device__ __forceinline__ void progress_lane(const DeviceParams& P, CarCore& s,
 
 // car ci back at its spawn pose with a cleared race state; car 0 of the env also zeroes the env's steps (ftgp_reset_kernel,
 // ftgp_io_finish_kernel)
-__device__ __forceinline__ void reset_car(const DeviceParams& P, int ci)
+__device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track)
 {
     const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
+    const int trk = env_track_of(env_track, env);
+    const double* spawn = P.spawn + (size_t)trk * 4 * FTGP_PATH_POINTS;
     CarCore s;
     memset(&s, 0, sizeof s);
     const int p = (P.spawn_mode == 0) ? (car + 5) * 2 : (int)((10 + 7 * (long)(P.env_base + env) + 2 * car) % 98);   // custom.py:1112
     s.offset = p;
     s.good_start = 1;
-    s.x = P.spawn[4 * p]; s.y = P.spawn[4 * p + 1];
-    double qw = P.spawn[4 * p + 2], qz = P.spawn[4 * p + 3];
+    s.x = spawn[4 * p]; s.y = spawn[4 * p + 1];
+    double qw = spawn[4 * p + 2], qz = spawn[4 * p + 3];
     if (P.spawn_mode == 1) {
         const uint64_t h = splitmix64(P.seed ^ (0xA0761D6478BD642Full + (uint64_t)((long)P.env_base * P.cars_per_env + ci)));
         const double j = 0.2 * u01(h) - 0.1;
@@ -1797,16 +1825,16 @@ __device__ __forceinline__ void reset_car(const DeviceParams& P, int ci)
     s.qw = qw; s.qz = qz;
     if (car == 0) P.steps[env] = 0;
     for (int k = 0; k < FTGP_MAX_LAP_TIMES; ++k) P.cars[ci].times[k] = 0.0;
-    progress_lane(P, s, 0, P.cars[ci].times);
+    progress_lane(P, P.path + (size_t)trk * 2 * FTGP_PATH_POINTS, s, 0, P.cars[ci].times);
     static_cast<CarCore&>(P.cars[ci]) = s;
 }
 
-__global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ env_mask)
+__global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ env_mask, const int32_t* __restrict__ env_track)
 {
     const int ci = blockIdx.x * blockDim.x + threadIdx.x;
     if (ci >= P.n_cars) return;
     if (env_mask && !env_mask[ci / P.cars_per_env]) return;
-    reset_car(P, ci);
+    reset_car(P, ci, env_track);
 }
 
 // sensordata = 0 after mj_resetData (custom.py:1092): coalesced zero fill of the reset envs' scans
@@ -1818,12 +1846,13 @@ __global__ void ftgp_zero_ranges_kernel(DeviceParams P, const uint8_t* __restric
     for (int j = threadIdx.x; j < P.ranges_stride; j += blockDim.x) r[j] = 0.0f;
 }
 
-__global__ void ftgp_progress_kernel(DeviceParams P)
+__global__ void ftgp_progress_kernel(DeviceParams P, const int32_t* __restrict__ env_track)
 {
     const int ci = blockIdx.x * blockDim.x + threadIdx.x;
     if (ci >= P.n_cars) return;
     CarCore s = static_cast<const CarCore&>(P.cars[ci]);
-    progress_lane(P, s, P.steps[ci / P.cars_per_env], P.cars[ci].times);
+    const int env = ci / P.cars_per_env;
+    progress_lane(P, P.path + (size_t)env_track_of(env_track, env) * 2 * FTGP_PATH_POINTS, s, P.steps[env], P.cars[ci].times);
     static_cast<CarCore&>(P.cars[ci]) = s;
 }
 
@@ -1862,6 +1891,7 @@ struct DeviceIoArgs {
     int32_t n_ext, auto_reset;
     int32_t vec4;                 // n_rays % 4 == 0 and obs / final_obs 16-byte aligned: rows move as float4
     int32_t ext_index[FTGP_PAIR_STRIDE];   // car slot -> its index among the env's external cars, -1 = a bundled driver
+    const int32_t* env_track;     // multi-track handles: the track of every env (reset_car); null with one track
 };
 
 // custom.py:132-143, as ftgp_get_progress column 3 reports it
@@ -1934,7 +1964,7 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_kernel(DeviceP
         __syncthreads();      // the row has been read before it is zeroed
         if (reset) for (int j = t; j < P.ranges_stride; j += FTGP_IO_THREADS) src[j] = 0.0f;
     }
-    if (reset && t < cpe) reset_car(P, ci0 + t);      // (the records were read before the first barrier)
+    if (reset && t < cpe) reset_car(P, ci0 + t, A.env_track);      // (the records were read before the first barrier)
 }
 
 // Packed read-back rows, one car per lane: the host copies 3 small arrays instead of the whole state records.

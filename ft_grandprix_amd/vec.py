@@ -70,10 +70,15 @@ class DeviceVecEnv:
     before their reset (other rows hold older values).  The returned tensors are the env's own buffers: the next ``step`` or
     ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
     synchronises the host.
+
+    track: a Track or the name of a bundled track, or a list of them (one handle, ftgp_create_tracks): env block t = envs_per_track[t]
+    consecutive envs on track t, as even a split as possible by default.  ``track_index`` (int64 [n_envs], on the env's device) says
+    which track each env races, so that a policy can condition on it; ``tracks`` lists the tracks.
     """
 
     def __init__(self, track, n_envs: int = 4096, n_rays: int = 1080, cars_per_env: int = 1, roster=None,
-                 max_episode_steps: int = 3000, action_repeat: int = 1, auto_reset: bool = True, device_id: int = 0, **env_kwargs):
+                 max_episode_steps: int = 3000, action_repeat: int = 1, auto_reset: bool = True, device_id: int = 0,
+                 envs_per_track=None, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
@@ -90,9 +95,14 @@ class DeviceVecEnv:
             raise ValueError('the roster needs at least one "agent" slot')
         if "lidar_mode" in env_kwargs and env_kwargs["lidar_mode"] not in capi.LIDAR_BY_NAME and env_kwargs["lidar_mode"] not in (0, 1):
             raise ValueError(f"unknown lidar_mode {env_kwargs['lidar_mode']!r}")
-        self.track = load_track(track) if isinstance(track, str) else track
-        if not isinstance(self.track, Track):
-            raise ValueError("track: a Track or the name of a bundled track")
+        multi = isinstance(track, (list, tuple))
+        if not multi and envs_per_track is not None:
+            raise ValueError("envs_per_track needs a list of tracks")
+        self.tracks = [load_track(t) if isinstance(t, str) else t for t in (track if multi else [track])]
+        if not all(isinstance(t, Track) for t in self.tracks):
+            raise ValueError("track: a Track or the name of a bundled track, or a list of them")
+        self.envs_per_track = capi.track_blocks(n_envs, len(self.tracks), envs_per_track) if multi else (n_envs,)
+        self.track = self.tracks[0]
         self.n_envs, self.n_rays, self.cars_per_env, self.roster = n_envs, n_rays, cars_per_env, roster
         self.n_agents = roster.count("agent")
         self.max_episode_steps, self.action_repeat, self.auto_reset = int(max_episode_steps), int(action_repeat), bool(auto_reset)
@@ -100,10 +110,13 @@ class DeviceVecEnv:
         lib = capi.load()
         check_single_hip_runtime()                   # before any torch GPU call
         self.device = torch.device("cuda", int(device_id))
-        self.env = capi.Env(lib, self.track, n_envs=n_envs, cars_per_env=cars_per_env, n_rays=n_rays, device_id=int(device_id),
-                            **env_kwargs)
+        if multi:
+            env_kwargs["envs_per_track"] = self.envs_per_track
+        self.env = capi.Env(lib, self.tracks if multi else self.track, n_envs=n_envs, cars_per_env=cars_per_env, n_rays=n_rays,
+                            device_id=int(device_id), **env_kwargs)
         self.env.device_io_config(roster, self.max_episode_steps, self.action_repeat, self.auto_reset)
         z = dict(device=self.device)
+        self.track_index = torch.from_numpy(self.env.track_of_env.astype("int64")).to(self.device)
         self.obs = torch.zeros((n_envs, self.n_agents, n_rays), dtype=torch.float32, **z)
         self.final_obs = torch.zeros_like(self.obs)
         self.reward = torch.zeros((n_envs, self.n_agents), dtype=torch.float32, **z)

@@ -177,6 +177,21 @@ int ftgp_create(const FtgpConfig *cfg, FtgpEnv **out);
 int ftgp_destroy(FtgpEnv *env);
 
 /*
+ * Multi-track batches: several worlds of one handle, each on its own track, stepped by one launch.  The reference builds one world per
+ * track: its GUI lists every PNG of the template directory (custom.py:879-887) and stage() rebuilds the world on the one picked
+ * (custom.py:1133-1194).  Here the envs form contiguous blocks: block t is envs [first_t, first_t + envs_per_track[t]) on tracks[t],
+ * first_t = the sum of the counts before t.  Block t behaves bit for bit like a handle of ftgp_create with
+ *     track = tracks[t], n_envs = envs_per_track[t], env_base = cfg->env_base + first_t
+ * and everything else (vehicle, n_rays, fan, lidar_mode, map_size, dt, spawn mode, seed, ...) from *cfg.  cfg->track is ignored.
+ * 1 <= n_tracks <= FTGP_MAX_TRACKS, every count >= 1, the counts sum to cfg->n_envs.  Every track gets the checks of ftgp_create (an
+ * error names the track's index); all checks run before the device probe.  With one track the handle is ftgp_create's.
+ * Every entry works on such a handle with its documented meaning over all envs, except ftgp_get_distance_field and ftgp_comm_init,
+ * which return FTGP_ERR_STATE on a handle with more than one track (multi-rank runs of multi-track handles are not supported).
+ */
+#define FTGP_MAX_TRACKS 16
+int ftgp_create_tracks(const FtgpConfig *cfg, const FtgpTrack *tracks, const int32_t *envs_per_track, int n_tracks, FtgpEnv **out);
+
+/*
  * Reset.  Replaces Mujoco.reload() = mj_resetData + VehicleState rebuild + position_vehicles
  * (custom.py:1089-1128,1232-1245,81-87).  mask: NULL = all envs, else uint8[n_envs], non-zero = reset.
  * After reset: qvel = 0, ctrl = 0, LiDAR ranges = 0 (custom.py:1092), steps of the
@@ -362,8 +377,12 @@ int ftgp_fakelidar(int device_id, const double *dt, int H, int W, int n_origins,
                    const double *cosines, const double *sines, double eps, double *scan, double *points);
 
 /* FAKELIDAR mode: the distance transform ftgp_create built, double[height][width] in pixels (what the reference calls self.dt,
- * custom.py:1152-1153); FTGP_ERR_STATE in RANGEFINDER mode. */
+ * custom.py:1152-1153); FTGP_ERR_STATE in RANGEFINDER mode and on a handle with more than one track. */
 int ftgp_get_distance_field(FtgpEnv *env, double *out);
+
+/* FAKELIDAR mode: the distance transform of track `track` (0 .. n_tracks - 1) of a handle, double[height][width] of that track; any
+ * handle (one made by ftgp_create has track 0).  FTGP_ERR_ARG for a track out of range, FTGP_ERR_STATE in RANGEFINDER mode. */
+int ftgp_get_track_distance_field(FtgpEnv *env, int track, double *out);
 
 /* Self-test of device arithmetic the kernels rely on (no reference counterpart): the fast reciprocal of the ray set-up against
  * the IEEE division of the specification over all 2^32 binary32 bit patterns.  *mismatches = number of differing results. */

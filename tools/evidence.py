@@ -64,9 +64,11 @@ def publish(dst, files):
     return 1 if bad else 0
 
 
-def code_object_meta(lib=None):
+def code_object_meta(lib=None, tracks=False):
     """.vgpr_count / .sgpr_count / spills / scratch of every ftgp_step_kernel instantiation, from the gfx950 code object inside the
-    library (rocprofv3's VGPR_Count / LDS_Block_Size columns read 32 / 0 for a 63-register kernel with 73 KB of dynamic LDS)."""
+    library (rocprofv3's VGPR_Count / LDS_Block_Size columns read 32 / 0 for a 63-register kernel with 73 KB of dynamic LDS).
+    tracks=False: the six one-track instantiations <MULTI, FAKE, ROSTER[, false]>, keyed by their three flags; tracks=True: the six of
+    multi-track handles, keyed "ftgp_step_kernel<MULTI, FAKE, ROSTER, true>"."""
     lib = lib or os.path.join(ROOT, "ft_grandprix_amd", "lib", "libftgp.so")
     out = {}
     with tempfile.TemporaryDirectory() as td:
@@ -79,8 +81,11 @@ def code_object_meta(lib=None):
         name = re.search(r"\.name:\s+(\S+)", block)
         if not name or "ftgp_step_kernel" not in name.group(1):
             continue
-        flags = re.search(r"ftgp_step_kernelILb(\d)ELb(\d)ELb(\d)E", name.group(1))
-        key = "ftgp_step_kernel<%s, %s, %s>" % tuple("true" if f == "1" else "false" for f in flags.groups()) if flags else name.group(1)
+        flags = re.search(r"ftgp_step_kernelILb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?", name.group(1))
+        if flags and (flags.group(4) == "1") != tracks:
+            continue
+        key = ("ftgp_step_kernel<%s, %s, %s" % tuple("true" if f == "1" else "false" for f in flags.groups()[:3]) + (", true>" if tracks else ">")
+               if flags else name.group(1))
         get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
         out[key] = {"vgpr_count": get("vgpr_count"), "sgpr_count": get("sgpr_count"), "sgpr_spill_count": get("sgpr_spill_count"),
                     "vgpr_spill_count": get("vgpr_spill_count"), "scratch_bytes_per_lane": get("private_segment_fixed_size"),
