@@ -482,8 +482,11 @@ int plan_task_table(const DeviceParams& P, std::vector<int32_t>& tt)
     return 0;
 }
 
-// the VehLds image: the vehicle constants as the step kernel stages them into LDS
-void plan_vehicle(const DeviceParams& P, std::vector<unsigned char>& img)
+// the map's diagonal in world units: no ray between two cars on the map is longer
+double track_diagonal(const FtgpTrack& t) { return hypot((double)t.width * t.px_size_x, (double)t.height * t.px_size_y); }
+
+// the VehLds image: the vehicle constants as the step kernel stages them into LDS; diag = the longest map diagonal of the handle's tracks
+void plan_vehicle(const DeviceParams& P, double diag, std::vector<unsigned char>& img)
 {
     const FtgpVehicle& v = P.veh;
     img.assign((size_t)pad16(sizeof(VehLds)), 0);
@@ -493,11 +496,22 @@ void plan_vehicle(const DeviceParams& P, std::vector<unsigned char>& img)
     const double cx = std::max(fabs(v.box_xmin), fabs(v.box_xmax)), cy = std::max(fabs(v.box_ymin), fabs(v.box_ymax));
     const double rmax = std::max(sqrt(cx * cx + cy * cy), sqrt(v.lidar_x * v.lidar_x + v.lidar_y * v.lidar_y) + v.lidar_ring_radius);
     vl.cull_radius = (float)(1.1 * rmax);
-    {   // the puck inside the box with at least 1e-3 to spare on every side (MuSHR: 0.016, tricycle: 0.0175): coordinates in a mate's frame are below the
-        // map's 40 units, so binary32 rounding of the two tests is below 1e-5 -- the circle can never come out ahead of the box
-        const double m = 1e-3, r = v.lidar_ring_radius;
-        vl.puck_in_box = (v.lidar_x - r >= v.box_xmin + m && v.lidar_x + r <= v.box_xmax - m && v.lidar_y - r >= v.box_ymin + m && v.lidar_y + r <= v.box_ymax - m &&
-                          !getenv("FTGP_PUCK_TEST")) ? 1 : 0;
+    {   // The sweep leaves the puck's circle out when the box's time is the minimum of the two to the bit: the puck inside the box with `need` to spare on
+        // every side.  Both tests work on the same binary32 origin and direction in the mate's frame, so only what follows them counts, and far away that
+        // is the cancellation in the circle's discriminant disc = bq^2 - cq: bq^2 and cq are both about D^2 at D units, their difference is at most r0^2.
+        // What enters disc: two roundings of bq (times 2 bq), three of cq, and the direction's norm, which the formula takes for 1 (disc is off by
+        // (|d|^2 - 1) cq).  With an error of e in disc the circle is met as if its radius were sqrt(r0^2 + e) <= r0 + e / (2 r0), up to that much EARLIER than
+        // the true puck.  e = 5 * 2^-24 * D^2: the largest seen is 3.9 (190 000 hits at 40 to 55 units, oracle with and without the circle:
+        // tests/test_crowded_envs.py repeats the measurement); adding up every rounding's worst case would give about 8, which no ray gets near.
+        // D = the longest ray between two cars on the map: the diagonal of the handle's largest track.  40 x 40 units, r0 = 0.03: 0.0159
+        // (MuSHR has 0.0161 on its tightest side, the tricycle 0.0175: both keep the short path; on a larger map they take the circle test).
+        const double r = v.lidar_ring_radius;
+        const double need = r > 0.0 ? 5.0 * ldexp(1.0, -24) * diag * diag / (2.0 * r) : 0.0;
+        const double have = std::min(std::min(v.lidar_x - r - v.box_xmin, v.box_xmax - (v.lidar_x + r)), std::min(v.lidar_y - r - v.box_ymin, v.box_ymax - (v.lidar_y + r)));
+        vl.puck_in_box = (have >= need && !getenv("FTGP_PUCK_TEST")) ? 1 : 0;
+        if (getenv("FTGP_VERBOSE"))
+            fprintf(stderr, "ftgp_create: inter-vehicle rays test %s (the puck lies %.4f inside the box, %.4f needed on a map of diagonal %.2f)\n",
+                    vl.puck_in_box ? "the box only" : "the box and the puck's circle", have, need, diag);
     }
     vl.box_xmin_f = (float)v.box_xmin; vl.box_xmax_f = (float)v.box_xmax; vl.box_ymin_f = (float)v.box_ymin; vl.box_ymax_f = (float)v.box_ymax;
     vl.lidar_x_f = (float)v.lidar_x; vl.lidar_y_f = (float)v.lidar_y; vl.ring_radius_f = (float)v.lidar_ring_radius;
@@ -585,7 +599,7 @@ int plan_create(const FtgpConfig& cfg, int n_cu, Plan& pl)
         build_cover_table(0.12, cfg.n_rays, P.cover_kmax, pl.cover.data());
         build_cover_table(0.06, cfg.n_rays, P.cover_kmax, pl.cover.data() + stride);
     }
-    plan_vehicle(P, pl.veh);
+    plan_vehicle(P, track_diagonal(t), pl.veh);
     return 0;
 }
 
@@ -640,6 +654,9 @@ int plan_tracks(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* e
         plan_track_params(cfg, tracks[t], k.P);
         plan_track_tables(tracks[t], k.P, k.tab, k.spawn);
     }
+    double diag = 0.0;                        // the vehicle image again, for the largest of the tracks (plan_create saw the first only)
+    for (int t = 0; t < n_tracks; ++t) diag = std::max(diag, track_diagonal(tracks[t]));
+    if (n_tracks > 1) plan_vehicle(pl.P, diag, pl.veh);
     pl.env_track.clear();
     for (int t = 0; t < n_tracks; ++t) pl.env_track.insert(pl.env_track.end(), (size_t)envs_per_track[t], t);
     plan_workgroups(pl.P.cars_per_block, cfg.cars_per_env, envs_per_track, n_tracks, track_order(), pl.wg);

@@ -1644,8 +1644,9 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
     }
     if (MULTI) {                         // env-mate records of the first frames
         __syncthreads();
-        const int c = (int)threadIdx.x / FTGP_PAIR_STRIDE, k = (int)threadIdx.x % FTGP_PAIR_STRIDE;
-        if (c < ncars_here) pair_cull_write(L.frame, L.pairs, c, k, P.cars_per_env, L.veh->cull_radius, (float)L.veh->v.lidar_ring_radius);
+        // (a loop: one wave per workgroup -- FTGP_WAVES_PER_BLOCK=1 -- has 64 threads for up to 16 cars x FTGP_PAIR_STRIDE records)
+        for (int idx = (int)threadIdx.x; idx < ncars_here * FTGP_PAIR_STRIDE; idx += (int)blockDim.x)
+            pair_cull_write(L.frame, L.pairs, idx / FTGP_PAIR_STRIDE, idx % FTGP_PAIR_STRIDE, P.cars_per_env, L.veh->cull_radius, (float)L.veh->v.lidar_ring_radius);
         __syncthreads();
         if (wave == 0)
             mate_masks(L.frame, L.pairs, L.mmask, P.mmask_stride, &scalar_view(Pt)->group_order[0], L.ray, P.n_rays, P.tasks_per_car, P.cars_per_env, L.veh->cull_radius, P.group_cg, P.group_sg,

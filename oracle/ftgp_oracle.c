@@ -79,6 +79,7 @@ struct OracleEnv {
     double wheel_load[4];
     int lidar_mode;          /* 0 = f32 field-accelerated march (== 2 bit for bit), 1 = binary64 plain DDA, 2 = THE SPEC: f32 plain DDA */
     int threads;
+    int box_only;            /* test switch (oracle_set_box_only): ray_vs_cars leaves the puck's circle out -- what the product computes on its fast path */
     double last_ms;
     int32_t car_policy[8];   /* FTGP_POLICY_PER_CAR: the driver of car slot k of every env (the roster, custom.py:1097-1104); 0 = not set */
 };
@@ -331,7 +332,7 @@ static float ray_vs_cars(const OracleEnv *e, int car_index, double lcx, double l
             }
         }
         /* LiDAR puck: circle of radius lidar_ring_radius at (lidar_x, lidar_y) */
-        {
+        if (!e->box_only) {
             float px = lx - (float)v->lidar_x, py = ly - (float)v->lidar_y;
             float bq = fmaf(px, ldx, py * ldy);
             float cq = fmaf(px, px, py * py) - r0 * r0;
@@ -961,6 +962,7 @@ int oracle_destroy(OracleEnv *e)
 
 int oracle_set_threads(OracleEnv *e, int n) { e->threads = n < 1 ? 1 : n; return 0; }
 int oracle_set_lidar_mode(OracleEnv *e, int mode) { e->lidar_mode = mode; return 0; }
+int oracle_set_box_only(OracleEnv *e, int on) { e->box_only = on != 0; return 0; }
 
 int oracle_reset(OracleEnv *e, const uint8_t *mask)
 {

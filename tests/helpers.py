@@ -28,6 +28,7 @@ def load_oracle():
     d.oracle_progress_trace.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     d.oracle_set_lidar_mode.argtypes = [C.c_void_p, C.c_int]
     d.oracle_set_threads.argtypes = [C.c_void_p, C.c_int]
+    d.oracle_set_box_only.argtypes = [C.c_void_p, C.c_int]
     d.oracle_get_field.argtypes = [C.c_void_p, C.c_void_p]
     d.oracle_get_distance_field.argtypes = [C.c_void_p, C.c_void_p]
     return lib

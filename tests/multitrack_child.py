@@ -75,7 +75,7 @@ def equivalence(opt):
     cpe, R, mode = opt["cars_per_env"], opt["n_rays"], opt["lidar_mode"]
     steps = opt.get("steps", 200)
     tracks = [load_track(n) for n in NAMES]
-    roster = ["nidc", "fast", "random"][:cpe] if cpe > 1 else ["fast"]
+    roster = (["nidc", "fast", "random"] * 3)[:cpe] if cpe > 1 else ["fast"]
     for spawn_mode, env_base in ((0, 0), (1, 11)):
         kw = dict(cars_per_env=cpe, n_rays=R, lidar_mode=mode, spawn_mode=spawn_mode, env_base=env_base, seed=99, lap_target=1)
         multi, singles = handles(lib, tracks, COUNTS, **kw)

@@ -88,9 +88,10 @@ def test_twin_one_car_bit_for_bit(repeat):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("roster", [["agent", "nidc", "fast"], ["nidc", "agent", "fast"]])
+@pytest.mark.parametrize("roster", [["agent", "nidc", "fast"], ["nidc", "agent", "fast"],
+                                    ["nidc", "fast", "nidc", "nidc", "agent", "nidc", "agent"]])      # agent slots 4 and 6 of a 7-car env
 def test_twin_roster(roster):
-    out = run_child("twin", n_envs=128, cars_per_env=3, roster=roster, calls=500, action_repeat=2, max_episode_steps=300)
+    out = run_child("twin", n_envs=128, cars_per_env=len(roster), roster=roster, calls=500, action_repeat=2, max_episode_steps=300)
     assert "twin ok" in out
 
 

@@ -160,9 +160,10 @@ def test_device_vec_env_checks_the_tracks_before_a_handle_exists(kwargs, monkeyp
 
 # ---------------------------------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize("cars_per_env", [1, 3])
-@pytest.mark.parametrize("n_rays", [90, 1080])
-@pytest.mark.parametrize("lidar_mode", ["rangefinder", "fakelidar"])
+@pytest.mark.parametrize("lidar_mode, n_rays, cars_per_env",
+                         [(m, r, c) for m in ("rangefinder", "fakelidar") for r in (90, 1080) for c in (1, 3)] +
+                         [("rangefinder", 1080, 7), ("fakelidar", 90, 7)],         # crowded envs: env-mates 4 to 6, two envs per workgroup
+                         ids=lambda v: str(v))
 def test_gpu_four_tracks_equal_the_blocks_bit_for_bit(cars_per_env, n_rays, lidar_mode):
     run_child("equivalence", cars_per_env=cars_per_env, n_rays=n_rays, lidar_mode=lidar_mode, steps=200 if lidar_mode == "rangefinder" else 100)
 
