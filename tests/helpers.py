@@ -80,12 +80,13 @@ def write_template_track(template_dir, name="generated", width=640, height=480, 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # K2 (the rangefinder sweep) against the only LiDAR arithmetic the reference owns: raycast.fakelidar (fixture G2).
-def lidar_from_pixel_origins(lib, track, origins_px, yaw_world, n_rays):
+def lidar_from_pixel_origins(lib, track, origins_px, yaw_world, n_rays, lib_track=None):
     """One env per origin: the car is posed so that its LiDAR centre sits on the pixel position origins_px[k] (wall frame of
-    `track`) with heading yaw_world[k]; returns (ranges [n, R] in world units, the vehicle constants)."""
+    `track`) with heading yaw_world[k]; returns (ranges [n, R] in world units, the vehicle constants).  lib_track: the track the library
+    is told instead of `track` (a deliberately wrong one: tests/test_walls_model.py)."""
     from ft_grandprix_amd import capi
     n = len(origins_px)
-    with capi.Env(lib, track, n_envs=n, n_rays=n_rays) as e:
+    with capi.Env(lib, lib_track or track, n_envs=n, n_rays=n_rays) as e:
         v = e.cfg.vehicle
         pose = e.pose()
         cx = track.origin_x + origins_px[:, 0] * track.px_size_x
@@ -100,11 +101,12 @@ def lidar_from_pixel_origins(lib, track, origins_px, yaw_world, n_rays):
         return e.lidar().astype(np.float64), float(v.lidar_ring_radius)
 
 
-def k2_minus_fakelidar_square_pixels(lib, name, R):
+def k2_minus_fakelidar_square_pixels(lib, name, R, wrong=None):
     """Differences (pixels) between K2's range measured from the LiDAR centre and the reference's own fakelidar scans of fixture
     G2, ray by ray, on the bitmap of track `name` taken with SQUARE pixels (fakelidar works in pixel space, so this is the frame
     in which its uniform fan and K2's coincide).  G2 ray k has the image-frame angle yaw_g + pi - 2 pi k / R (custom.py:1387);
-    K2 ray j of a car with world yaw psi has -(psi + pi + 2 pi j / R) (mushr.em.xml:112-117, y up): the same ray for psi = -yaw_g."""
+    K2 ray j of a car with world yaw psi has -(psi + pi + 2 pi j / R) (mushr.em.xml:112-117, y up): the same ray for psi = -yaw_g.
+    wrong: f(track) -> the track that the library is told, while the cars are posed in the true one."""
     import dataclasses
     from ft_grandprix_amd.track import load_track
     g = g2_fakelidar(name)
@@ -113,7 +115,7 @@ def k2_minus_fakelidar_square_pixels(lib, name, R):
     sq = dataclasses.replace(t, px_size_x=s, px_size_y=s)
     origins, ang, scan = g[f"{name}_origins"], g[f"{name}_{R}_angles"], g[f"{name}_{R}_scan"]
     yaw_g = ang[:, 0] - np.pi
-    rng, r0 = lidar_from_pixel_origins(lib, sq, origins, -yaw_g, R)
+    rng, r0 = lidar_from_pixel_origins(lib, sq, origins, -yaw_g, R, lib_track=wrong(sq) if wrong else None)
     assert (rng > 0).all()                          # every origin is enclosed by walls
     return (rng - r0) / s - scan                    # K2 starts its rays r0 behind the centre
 
