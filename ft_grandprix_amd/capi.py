@@ -22,6 +22,7 @@ SNAPSHOT_DOUBLES = 10
 POSE_DOUBLES = 13
 PROGRESS_INTS = 10
 METRIC_DOUBLES = 8
+STATE_FLOATS = 8            # FTGP_STATE_FLOATS: a state row of the device step (STATE_FIELDS)
 MAX_TRACKS = 16             # FTGP_MAX_TRACKS: tracks of one multi-track handle (ftgp_create_tracks)
 
 POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2, 3, 4
@@ -33,6 +34,7 @@ POLICY_BY_NAME = {"host": POLICY_HOST, "lobotomy": POLICY_LOBOTOMY, "nidc": POLI
 
 PROGRESS_FIELDS = ("laps", "completion", "lap_completion", "absolute_completion", "finished",
                    "off_track", "start", "good_start", "delta", "finish_step")
+STATE_FIELDS = ("v_long", "v_lat", "wz", "u_speed", "u_steer", "centre_dist", "lap_completion", "off_track")
 METRIC_FIELDS = ("steps", "n_cars", "sum_laps", "sum_absolute_completion", "n_finished",
                  "n_off_track", "min_lap_time", "max_lap_time")
 
@@ -78,6 +80,7 @@ API_SYMBOLS = (
     "metrics_allgather_begin", "metrics_allgather_end", "get_distance_field",
     "last_kernel_ms", "kernel_name", "fakelidar", "selftest", "build_info", "get_race_steps",
     "device_io_config", "step_device", "create_tracks", "get_track_distance_field",
+    "device_io_signals", "step_device_ex", "state_device", "get_centre_dist2",
 )
 
 
@@ -88,6 +91,15 @@ class FtgpDeviceIoConfig(C.Structure):
 class FtgpDeviceStep(C.Structure):
     _fields_ = [("stream", C.c_void_p), ("action", C.c_void_p), ("obs", C.c_void_p), ("reward", C.c_void_p),
                 ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("final_obs", C.c_void_p)]
+
+
+class FtgpDeviceSignals(C.Structure):
+    _fields_ = [("scan_pool", C.c_int32), ("scan_max_range", C.c_float), ("terminate_off_track", C.c_int32),
+                ("off_track_penalty", C.c_float)]
+
+
+class FtgpDeviceStepExtra(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("final_state", C.c_void_p)]
 
 
 class FtgpError(RuntimeError):
@@ -158,6 +170,10 @@ class CLib:
             "build_info": (C.c_char_p, []),
             "device_io_config": (i32, [vp, C.POINTER(FtgpDeviceIoConfig)]),
             "step_device": (i32, [vp, C.POINTER(FtgpDeviceStep)]),
+            "device_io_signals": (i32, [vp, C.POINTER(FtgpDeviceSignals)]),
+            "step_device_ex": (i32, [vp, C.POINTER(FtgpDeviceStep), C.POINTER(FtgpDeviceStepExtra)]),
+            "state_device": (i32, [vp, vp, vp]),
+            "get_centre_dist2": (i32, [vp, dp]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -355,11 +371,27 @@ class Env:
         cfg.max_episode_steps, cfg.action_repeat, cfg.auto_reset = int(max_episode_steps), int(action_repeat), int(bool(auto_reset))
         self._call("device_io_config", C.byref(cfg))
 
-    def step_device(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0):
-        """One ftgp_step_device call on integer device addresses (and an integer hipStream_t, 0 = the null stream); only enqueues."""
+    def device_io_signals(self, scan_pool: int = 1, scan_max_range: float = 0.0, terminate_off_track: bool = False,
+                          off_track_penalty: float = 0.0):
+        """ftgp_device_io_signals (after ``device_io_config``, which puts the defaults back): pooled / scaled scans, off-track ends."""
+        s = FtgpDeviceSignals(int(scan_pool), float(scan_max_range), int(bool(terminate_off_track)), float(off_track_penalty))
+        self._call("device_io_signals", C.byref(s))
+
+    def step_device(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0,
+                    state: int = 0, final_state: int = 0):
+        """One ftgp_step_device call on integer device addresses (and an integer hipStream_t, 0 = the null stream); only enqueues.
+        With ``state`` or ``final_state``: ftgp_step_device_ex."""
         io = FtgpDeviceStep(stream or None, action or None, obs or None, reward or None, terminated or None, truncated or None,
                             final_obs or None)
-        self._call("step_device", C.byref(io))
+        if state or final_state:
+            extra = FtgpDeviceStepExtra(state or None, final_state or None)
+            self._call("step_device_ex", C.byref(io), C.byref(extra))
+        else:
+            self._call("step_device", C.byref(io))
+
+    def state_device(self, state: int, stream: int = 0):
+        """ftgp_state_device: the state rows of the current state into device memory at ``state``, ordered on ``stream``; only enqueues."""
+        self._call("state_device", stream or None, state or None)
 
     # -- read-backs
     def lidar(self) -> np.ndarray:
@@ -394,6 +426,12 @@ class Env:
     def progress(self) -> np.ndarray:
         out = np.empty((self.n_cars, PROGRESS_INTS), dtype=np.int32)
         self._call("get_progress", _ptr(out))
+        return out
+
+    def centre_dist2(self) -> np.ndarray:
+        """float64 [n_cars]: the squared distance to the nearest centre-line point the progress block stored last (custom.py:1343)."""
+        out = np.empty(self.n_cars, dtype=np.float64)
+        self._call("get_centre_dist2", _ptr(out))
         return out
 
     def winners(self) -> np.ndarray:

@@ -163,6 +163,8 @@ struct FtgpEnv {
     int table_on_device = 0;          // which of the two the params block holds (-1: neither); only a FTGP_POLICY_PER_CAR launch reads it
     DevBuf<int32_t> d_prev_abs;
     Event ev_io_in, ev_io_out;
+    DeviceSignalArgs sig{};           // ftgp_device_io_signals (the buffers and what depends on them are filled in per call)
+    bool sig_default = true;          // the defaults: a call without state buffers launches ftgp_io_finish_kernel
     struct Checked { const void* p; size_t bytes; };
     Checked io_checked[32] = {};      // device buffers found valid (hipPointerGetAttributes), replaced round robin
     int io_checked_next = 0;
@@ -824,6 +826,24 @@ int check_device_buffer(FtgpEnv* e, const void* p, size_t bytes, const char* nam
     return 0;
 }
 
+// the signals of the device step as the finish kernel takes them (ftgp_device_io_signals has checked s)
+void set_signals(FtgpEnv* e, const FtgpDeviceSignals& s)
+{
+    DeviceSignalArgs& S = e->sig;
+    S = DeviceSignalArgs{};
+    S.pool = s.scan_pool; S.n_beams = e->P.n_rays / s.scan_pool;
+    S.vec_in = e->P.n_rays % 4 == 0;
+    S.path = s.scan_pool >= FTGP_SIG_WAVE_POOL ? FTGP_SIG_PATH_WAVE
+           : (S.vec_in && (s.scan_pool == 1 || s.scan_pool == 2 || s.scan_pool == 4)) ? FTGP_SIG_PATH_REGS : FTGP_SIG_PATH_STAGE;
+    S.chunk_beams = (FTGP_SIG_STAGE_FLOATS / s.scan_pool) & ~3;
+    S.clip = s.scan_max_range > 0.0f;
+    S.limit = S.clip ? s.scan_max_range : INFINITY;
+    S.inv_max_range = S.clip ? 1.0f / s.scan_max_range : 0.0f;
+    S.terminate_off_track = s.terminate_off_track ? 1 : 0;
+    S.penalty = s.off_track_penalty;
+    e->sig_default = s.scan_pool == 1 && !S.clip && !S.terminate_off_track && s.off_track_penalty == 0.0f;
+}
+
 // ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images.  tracks:
 // n_tracks = 1 + pl.more.size() of them.
 int upload(FtgpEnv* e, const FtgpTrack* tracks, const Plan& pl)
@@ -1188,22 +1208,42 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
     A.env_track = e->d_env_track.get();
     e->io_repeat = cfg->action_repeat;
     e->io_ready = true;
+    set_signals(e, FtgpDeviceSignals{ 1, 0.0f, 0, 0.0f });
     return 0;
 }
 
-int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io)
+int ftgp_device_io_signals(FtgpEnv* e, const FtgpDeviceSignals* signals)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_signals before ftgp_device_io_config%s");
+    const FtgpDeviceSignals s = signals ? *signals : FtgpDeviceSignals{ 1, 0.0f, 0, 0.0f };
+    if (s.scan_pool < 1 || e->P.n_rays % s.scan_pool) return fail(FTGP_ERR_ARG, "device_io_signals: scan_pool >= 1 and a divisor of n_rays%s");
+    if (!(s.scan_max_range >= 0.0f) || std::isinf(s.scan_max_range)) return fail(FTGP_ERR_ARG, "device_io_signals: scan_max_range >= 0 and finite%s");
+    if (!(s.off_track_penalty >= 0.0f) || std::isinf(s.off_track_penalty)) return fail(FTGP_ERR_ARG, "device_io_signals: off_track_penalty >= 0 and finite%s");
+    set_signals(e, s);
+    return 0;
+}
+
+int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io) { return ftgp_step_device_ex(e, io, nullptr); }
+
+int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra)
 {
     if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
     if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
     HIP_TRY(hipSetDevice(e->device));
     DeviceIoArgs A = e->io;
-    const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)e->P.n_rays;
+    DeviceSignalArgs S = e->sig;
+    S.state = extra ? extra->state : nullptr; S.final_state = extra ? extra->final_state : nullptr;
+    const bool signals = !e->sig_default || S.state || S.final_state;
+    const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
     if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
     if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
     if (int rc = check_device_buffer(e, io->reward, sizeof(float) * rows, "reward")) return rc;
     if (int rc = check_device_buffer(e, io->terminated, n_envs, "terminated")) return rc;
     if (int rc = check_device_buffer(e, io->truncated, n_envs, "truncated")) return rc;
     if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
+    if (S.state) if (int rc = check_device_buffer(e, S.state, sizeof(float) * FTGP_STATE_FLOATS * rows, "state")) return rc;
+    if (S.final_state) if (int rc = check_device_buffer(e, S.final_state, sizeof(float) * FTGP_STATE_FLOATS * rows, "final_state")) return rc;
     A.action = io->action; A.obs = io->obs; A.reward = io->reward; A.terminated = io->terminated; A.truncated = io->truncated; A.final_obs = io->final_obs;
     A.vec4 = e->P.n_rays % 4 == 0 && (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
     hipStream_t caller = (hipStream_t)io->stream;
@@ -1213,10 +1253,32 @@ int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io)
     hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
     if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, e->io_repeat, true)) return rc;
-    hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A);
+    if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A);
+    else {
+        const bool aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
+        S.vec_out = aligned && S.n_beams % 4 == 0;
+        if (S.path == FTGP_SIG_PATH_REGS && !aligned) S.path = FTGP_SIG_PATH_STAGE;
+        hipLaunchKernelGGL(ftgp_io_finish_signals_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, S);
+    }
     HIP_TRY(hipGetLastError());
     e->rows_valid = false;
     if (A.auto_reset) e->launch_metrics_valid = false;     // the launch's record describes the state before the resets
+    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
+    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
+    return 0;
+}
+
+int ftgp_state_device(FtgpEnv* e, void* stream, float* state)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_state_device before ftgp_device_io_config%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = check_device_buffer(e, state, sizeof(float) * FTGP_STATE_FLOATS * (size_t)e->P.n_envs * (size_t)e->io.n_ext, "state")) return rc;
+    hipStream_t caller = (hipStream_t)stream;
+    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
+    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
+    hipLaunchKernelGGL(ftgp_io_state_kernel, dim3((unsigned)((e->P.n_cars + 255) / 256)), dim3(256), 0, e->stream.get(), e->P, e->io, state);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
     HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
     return 0;
@@ -1312,6 +1374,16 @@ int ftgp_get_progress(FtgpEnv* e, int32_t* out)
     if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     if (int rc = sync_rows_to_host(e)) return rc;
     memcpy(out, e->h_prog.data(), sizeof(int32_t) * e->h_prog.size());
+    return 0;
+}
+
+int ftgp_get_centre_dist2(FtgpEnv* e, double* out)
+{
+    if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy2DAsync(out, sizeof(double), reinterpret_cast<const char*>(e->d_cars.get()) + offsetof(CarCore, dist2), sizeof(CarState),
+                             sizeof(double), (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 

@@ -1801,14 +1801,10 @@ __device__ __forceinline__ void progress_lane(const DeviceParams& P, const doubl
     race_store(r, &s);
 }
 
-// car ci back at its spawn pose with a cleared race state; car 0 of the env also zeroes the env's steps (ftgp_reset_kernel,
-// ftgp_io_finish_kernel)
-__device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track)
+// the spawn state of car ci (car `car` of env `env`, on track trk) with a cleared race state, before K3 has seen the spawn pose
+__device__ __forceinline__ void spawn_state(const DeviceParams& P, int ci, int env, int car, int trk, CarCore& s)
 {
-    const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
-    const int trk = env_track_of(env_track, env);
     const double* spawn = P.spawn + (size_t)trk * 4 * FTGP_PATH_POINTS;
-    CarCore s;
     memset(&s, 0, sizeof s);
     const int p = (P.spawn_mode == 0) ? (car + 5) * 2 : (int)((10 + 7 * (long)(P.env_base + env) + 2 * car) % 98);   // custom.py:1112
     s.offset = p;
@@ -1824,10 +1820,33 @@ __device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const i
         qw = nw / n; qz = nz / n;
     }
     s.qw = qw; s.qz = qz;
+}
+
+// car ci back at its spawn pose with a cleared race state; car 0 of the env also zeroes the env's steps (ftgp_reset_kernel,
+// ftgp_io_finish_kernel)
+__device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track)
+{
+    const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
+    const int trk = env_track_of(env_track, env);
+    CarCore s;
+    spawn_state(P, ci, env, car, trk, s);
     if (car == 0) P.steps[env] = 0;
     for (int k = 0; k < FTGP_MAX_LAP_TIMES; ++k) P.cars[ci].times[k] = 0.0;
     progress_lane(P, P.path + (size_t)trk * 2 * FTGP_PATH_POINTS, s, 0, P.cars[ci].times);
     static_cast<CarCore&>(P.cars[ci]) = s;
+}
+
+// reset_car on the record where it lies (ftgp_io_finish_signals_kernel): the same operations on the same values, without a copy of the
+// record on the lane's stack -- K3 reaches start / finish_step through a pointer, which keeps such a copy in scratch memory
+__device__ __forceinline__ void reset_car_in_place(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track)
+{
+    const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
+    const int trk = env_track_of(env_track, env);
+    CarCore& s = P.cars[ci];
+    spawn_state(P, ci, env, car, trk, s);
+    if (car == 0) P.steps[env] = 0;
+    for (int k = 0; k < FTGP_MAX_LAP_TIMES; ++k) P.cars[ci].times[k] = 0.0;
+    progress_lane(P, P.path + (size_t)trk * 2 * FTGP_PATH_POINTS, s, 0, P.cars[ci].times);
 }
 
 __global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ env_mask, const int32_t* __restrict__ env_track)
@@ -1966,6 +1985,176 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_kernel(DeviceP
         if (reset) for (int j = t; j < P.ranges_stride; j += FTGP_IO_THREADS) src[j] = 0.0f;
     }
     if (reset && t < cpe) reset_car(P, ci0 + t, A.env_track);      // (the records were read before the first barrier)
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device I/O with signals (ftgp_device_io_signals / ftgp_step_device_ex): the same call with ftgp_io_finish_signals_kernel in the
+// place of ftgp_io_finish_kernel -- pooled and scaled scans, a state row per external car, off-track episode ends and penalty.
+// ---------------------------------------------------------------------------------------------
+#define FTGP_SIG_STAGE_FLOATS 4096      // LDS stage of the pooled scan: a chunk is (FTGP_SIG_STAGE_FLOATS / pool) & ~3 beams, whatever n_rays
+#define FTGP_SIG_WAVE_POOL 64           // from this pool on a wave takes a whole beam
+enum { FTGP_SIG_PATH_REGS = 0, FTGP_SIG_PATH_STAGE = 1, FTGP_SIG_PATH_WAVE = 2 };
+struct DeviceSignalArgs {
+    float* state;                 // [n_envs][n_ext][FTGP_STATE_FLOATS] or null
+    float* final_state;           // [n_envs][n_ext][FTGP_STATE_FLOATS] or null
+    int32_t pool, n_beams;        // rays per beam, beams per row (n_rays / pool)
+    int32_t path;                 // FTGP_SIG_PATH_*: how a row is pooled (pooled_row)
+    int32_t chunk_beams;          // FTGP_SIG_PATH_STAGE: beams per staged chunk, a multiple of 4
+    int32_t vec_in;               // n_rays % 4 == 0: rows are read as float4 (they start on 128-byte boundaries)
+    int32_t vec_out;              // n_beams % 4 == 0 and obs / final_obs 16-byte aligned: beams are written as float4
+    int32_t clip;                 // scan_max_range > 0
+    int32_t terminate_off_track;
+    float limit;                  // what a ray without a hit counts as in the minimum: scan_max_range, +inf for raw ranges
+    float inv_max_range;          // 1.0f / scan_max_range, divided once on the host
+    float penalty;
+};
+
+// a range as it enters the minimum: no hit (< 0) = the limit, a hit = min(r, limit)
+__device__ __forceinline__ float sig_ray(float r, float limit) { return r < 0.0f ? limit : fminf(r, limit); }
+__device__ __forceinline__ float4 sig_ray4(float4 v, float limit) { return make_float4(sig_ray(v.x, limit), sig_ray(v.y, limit), sig_ray(v.z, limit), sig_ray(v.w, limit)); }
+// the minimum as it is written: scaled with one multiplication, or raw with -1 for a beam without a hit
+__device__ __forceinline__ float sig_beam(float m, const DeviceSignalArgs& S) { return S.clip ? m * S.inv_max_range : (m == INFINITY ? -1.0f : m); }
+
+// One pooled row by the whole workgroup: src = n_rays ranges (read once, a wave's loads contiguous), out = n_beams floats.
+//   REGS   pool 1, 2 or 4, n_rays % 4 == 0 and obs / final_obs 16-byte aligned: a lane's float4 holds whole beams, the minimum never
+//          leaves its registers, and the lane writes them as one float4 / float2 / float
+//   STAGE  pool < 64: chunks of chunk_beams beams go through LDS as they enter the minimum (float4 in, float4 stage); then one beam per
+//          lane, a lane reading its pool consecutive floats (stride pool dwords over the banks: free of conflicts for an odd pool, 2-way
+//          for pool 10), and four neighbouring lanes' beams leave as one float4
+//   WAVE   pool >= 64: a wave per beam, its lanes striding over the beam, the minimum folded with five shuffles
+// No barrier is left pending: a caller may overwrite src after its own barrier.
+__device__ __forceinline__ void pooled_row(const float* __restrict__ src, float* __restrict__ out, int R, const DeviceSignalArgs& S, float* stage)
+{
+    const int t = threadIdx.x, pool = S.pool, NB = S.n_beams;
+    const float limit = S.limit;
+    if (S.path == FTGP_SIG_PATH_REGS) {
+        for (int j = t; j < R / 4; j += FTGP_IO_THREADS) {
+            const float4 v = sig_ray4(reinterpret_cast<const float4*>(src)[j], limit);
+            if (pool == 1) {
+                reinterpret_cast<float4*>(out)[j] = make_float4(sig_beam(v.x, S), sig_beam(v.y, S), sig_beam(v.z, S), sig_beam(v.w, S));
+            } else if (pool == 2) {
+                reinterpret_cast<float2*>(out)[j] = make_float2(sig_beam(fminf(v.x, v.y), S), sig_beam(fminf(v.z, v.w), S));
+            } else {
+                out[j] = sig_beam(fminf(fminf(v.x, v.y), fminf(v.z, v.w)), S);
+            }
+        }
+        return;
+    }
+    if (S.path == FTGP_SIG_PATH_WAVE) {
+        const int lane = t & (FTGP_WAVE - 1);
+        for (int b = t / FTGP_WAVE; b < NB; b += FTGP_IO_THREADS / FTGP_WAVE) {
+            const float* beam = src + (size_t)b * pool;
+            float m = limit;
+            for (int k = lane; k < pool; k += FTGP_WAVE) m = fminf(m, sig_ray(beam[k], limit));
+            for (int d = FTGP_WAVE / 2; d > 0; d >>= 1) m = fminf(m, __shfl_xor(m, d, FTGP_WAVE));
+            if (lane == 0) out[b] = sig_beam(m, S);
+        }
+        return;
+    }
+    const int CB = S.chunk_beams;
+    for (int b0 = 0; b0 < NB; b0 += CB) {
+        const int nb = min(CB, NB - b0), n = nb * pool;
+        const float* chunk = src + (size_t)b0 * pool;          // (CB % 4 == 0: a chunk starts on a 16-byte boundary)
+        if (S.vec_in) {
+            for (int j = t; j < n / 4; j += FTGP_IO_THREADS) reinterpret_cast<float4*>(stage)[j] = sig_ray4(reinterpret_cast<const float4*>(chunk)[j], limit);
+        } else {
+            for (int j = t; j < n; j += FTGP_IO_THREADS) stage[j] = sig_ray(chunk[j], limit);
+        }
+        __syncthreads();
+        for (int b = t; b < ((nb + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1)); b += FTGP_IO_THREADS) {      // whole waves: the shuffles below need every lane
+            float m = limit;
+            if (b < nb) for (int k = 0; k < pool; ++k) m = fminf(m, stage[b * pool + k]);
+            const float v = sig_beam(m, S);
+            if (S.vec_out) {          // nb % 4 == 0 then, and b % 4 == lane % 4
+                const float v1 = __shfl_down(v, 1, FTGP_WAVE), v2 = __shfl_down(v, 2, FTGP_WAVE), v3 = __shfl_down(v, 3, FTGP_WAVE);
+                if ((b & 3) == 0 && b < nb) reinterpret_cast<float4*>(out + b0)[b / 4] = make_float4(v, v1, v2, v3);
+            } else if (b < nb) out[b0 + b] = v;
+        }
+        __syncthreads();      // the stage is free again
+    }
+}
+
+// the state row of ftgp_step_device_ex / ftgp_state_device (include/ftgp.h): every entry binary64, rounded once
+__device__ __forceinline__ void state_row(const CarCore& a, float* __restrict__ o)
+{
+    const double c = a.qw * a.qw - a.qz * a.qz, s = 2.0 * (a.qw * a.qz);
+    const int lc = a.good_start ? a.completion : -(100 - a.completion);         // custom.py:132-140
+    o[0] = (float)(a.vx * c + a.vy * s);
+    o[1] = (float)(a.vy * c - a.vx * s);
+    o[2] = (float)a.wz;
+    o[3] = (float)a.u_speed;
+    o[4] = (float)a.u_steer;
+    o[5] = (float)sqrt(a.dist2);
+    o[6] = (float)((double)lc / 100.0);
+    o[7] = a.off_track ? 1.0f : 0.0f;
+}
+
+// ftgp_state_device: one car per lane
+__global__ void ftgp_io_state_kernel(DeviceParams P, DeviceIoArgs A, float* __restrict__ state)
+{
+    const int ci = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ci >= P.n_cars) return;
+    const int k = A.ext_index[ci % P.cars_per_env];
+    if (k < 0) return;
+    state_row(P.cars[ci], state + ((size_t)(ci / P.cars_per_env) * A.n_ext + k) * FTGP_STATE_FLOATS);
+}
+
+// ftgp_io_finish_kernel with signals: one workgroup per env.  The rows of obs / final_obs are pooled (pooled_row); an external car that
+// is off_track pays the penalty and, with terminate_off_track, ends its env; state rows are written from the records after the steps
+// (to final_state for an env that is reset here) and again after the reset.
+__global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_signals_kernel(DeviceParams P, DeviceIoArgs A, DeviceSignalArgs S)
+{
+    __shared__ int ended;
+    __shared__ __attribute__((aligned(16))) float stage[FTGP_SIG_STAGE_FLOATS];
+    const int env = blockIdx.x, cpe = P.cars_per_env, ci0 = env * cpe, t = threadIdx.x;
+    if (t == 0) {
+        bool all_finished = true, off = false;
+        for (int c = 0; c < cpe; ++c)
+            if (A.ext_index[c] >= 0) {
+                if (!P.cars[ci0 + c].finished) all_finished = false;
+                if (P.cars[ci0 + c].off_track) off = true;
+            }
+        const bool term = all_finished || (S.terminate_off_track && off);
+        const bool trunc = !term && A.max_episode_steps > 0 && P.steps[env] >= A.max_episode_steps;
+        A.terminated[env] = term ? 1 : 0;
+        A.truncated[env] = trunc ? 1 : 0;
+        ended = (term || trunc) ? 1 : 0;
+    }
+    const bool mine = t < cpe && A.ext_index[t] >= 0;
+    const size_t my_row = (size_t)env * A.n_ext + (mine ? A.ext_index[t] : 0);
+    if (mine) {
+        const CarCore& a = P.cars[ci0 + t];
+        float r = (float)(absolute_completion(a) - A.prev_abs[ci0 + t]);
+        if (a.off_track) r = r - S.penalty;
+        A.reward[my_row] = r;
+    }
+    __syncthreads();
+    const bool reset = A.auto_reset && ended;
+    if (mine) {
+        float* dst = reset ? S.final_state : S.state;
+        if (dst) state_row(P.cars[ci0 + t], dst + my_row * FTGP_STATE_FLOATS);
+    }
+    const int R = P.n_rays, NB = S.n_beams;
+    for (int c = 0; c < cpe; ++c) {
+        const int k = A.ext_index[c];
+        float* src = P.ranges + (size_t)(ci0 + c) * P.ranges_stride;
+        if (k >= 0) {
+            const size_t row = ((size_t)env * A.n_ext + k) * NB;
+            float* obs = A.obs + row;
+            float* dst = !reset ? obs : A.final_obs ? A.final_obs + row : nullptr;      // one call site: the row's code exists once
+            if (dst) pooled_row(src, dst, R, S, stage);
+            if (reset) {
+                if (S.vec_out) for (int j = t; j < NB / 4; j += FTGP_IO_THREADS) reinterpret_cast<float4*>(obs)[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                else for (int j = t; j < NB; j += FTGP_IO_THREADS) obs[j] = 0.0f;
+            }
+        }
+        __syncthreads();      // the row has been read before it is zeroed
+        if (reset) for (int j = t; j < P.ranges_stride; j += FTGP_IO_THREADS) src[j] = 0.0f;
+    }
+    if (reset && t < cpe) {
+        reset_car_in_place(P, ci0 + t, A.env_track);      // (the records were read before the first barrier, and by this lane above)
+        if (mine && S.state) state_row(P.cars[ci0 + t], S.state + my_row * FTGP_STATE_FLOATS);
+    }
 }
 
 // Packed read-back rows, one car per lane: the host copies 3 small arrays instead of the whole state records.

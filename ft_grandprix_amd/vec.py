@@ -13,6 +13,7 @@ in a process that holds two runtimes (``check_single_hip_runtime``).  torch is i
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch  # first: the library must bind to torch's HIP runtime (see above)
 
@@ -67,7 +68,14 @@ class DeviceVecEnv:
     ``step(actions)`` takes float32 [n_envs, n_agents, 2] = (speed, steering_angle) and returns (obs, reward, terminated,
     truncated, info): obs float32 [n_envs, n_agents, n_rays], reward float32 [n_envs, n_agents] = the change of the car's
     absolute completion, terminated / truncated bool [n_envs], info["final_obs"] = the obs of the envs that ended in the call,
-    before their reset (other rows hold older values).  The returned tensors are the env's own buffers: the next ``step`` or
+    before their reset (other rows hold older values).
+
+    Signals (include/ftgp.h: ftgp_device_io_signals / ftgp_step_device_ex), all off by default: ``scan_pool`` = rays per beam (a
+    divisor of n_rays; obs and final_obs are [n_envs, n_agents, n_beams], n_beams = n_rays / scan_pool, a beam = the nearest hit of
+    its rays); ``scan_max_range`` M > 0 clips the ranges to M (no hit = M) and scales them to [0, 1]; ``state=True`` adds
+    info["state"] / info["final_state"], float32 [n_envs, n_agents, 8] (capi.STATE_FIELDS), and ``reset()`` fills ``state``;
+    ``terminate_off_track`` ends an env when one of its agents is off the track; ``off_track_penalty`` is taken off the reward of an
+    agent in every call that leaves it off the track.  The returned tensors are the env's own buffers: the next ``step`` or
     ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
     synchronises the host.
 
@@ -78,12 +86,20 @@ class DeviceVecEnv:
 
     def __init__(self, track, n_envs: int = 4096, n_rays: int = 1080, cars_per_env: int = 1, roster=None,
                  max_episode_steps: int = 3000, action_repeat: int = 1, auto_reset: bool = True, device_id: int = 0,
-                 envs_per_track=None, **env_kwargs):
+                 envs_per_track=None, scan_pool: int = 1, scan_max_range: float = 0.0, state: bool = False,
+                 terminate_off_track: bool = False, off_track_penalty: float = 0.0, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
         if int(action_repeat) < 1:
             raise ValueError("action_repeat >= 1")
+        scan_pool, scan_max_range, off_track_penalty = int(scan_pool), float(scan_max_range), float(off_track_penalty)
+        if scan_pool < 1 or n_rays % scan_pool:
+            raise ValueError(f"scan_pool: >= 1 and a divisor of n_rays = {n_rays}, got {scan_pool}")
+        if not (scan_max_range >= 0.0 and math.isfinite(scan_max_range)):
+            raise ValueError(f"scan_max_range: >= 0 and finite, got {scan_max_range}")
+        if not (off_track_penalty >= 0.0 and math.isfinite(off_track_penalty)):
+            raise ValueError(f"off_track_penalty: >= 0 and finite, got {off_track_penalty}")
         roster = ["agent"] * cars_per_env if roster is None else list(roster)
         if len(roster) != cars_per_env:
             raise ValueError(f"one roster entry per car of an env: expected {cars_per_env}, got {len(roster)}")
@@ -106,6 +122,9 @@ class DeviceVecEnv:
         self.n_envs, self.n_rays, self.cars_per_env, self.roster = n_envs, n_rays, cars_per_env, roster
         self.n_agents = roster.count("agent")
         self.max_episode_steps, self.action_repeat, self.auto_reset = int(max_episode_steps), int(action_repeat), bool(auto_reset)
+        self.scan_pool, self.scan_max_range, self.n_beams = scan_pool, scan_max_range, n_rays // scan_pool
+        self.terminate_off_track, self.off_track_penalty = bool(terminate_off_track), off_track_penalty
+        signals = scan_pool != 1 or scan_max_range > 0.0 or self.terminate_off_track or off_track_penalty > 0.0
 
         lib = capi.load()
         check_single_hip_runtime()                   # before any torch GPU call
@@ -115,9 +134,11 @@ class DeviceVecEnv:
         self.env = capi.Env(lib, self.tracks if multi else self.track, n_envs=n_envs, cars_per_env=cars_per_env, n_rays=n_rays,
                             device_id=int(device_id), **env_kwargs)
         self.env.device_io_config(roster, self.max_episode_steps, self.action_repeat, self.auto_reset)
+        if signals:
+            self.env.device_io_signals(scan_pool, scan_max_range, self.terminate_off_track, off_track_penalty)
         z = dict(device=self.device)
         self.track_index = torch.from_numpy(self.env.track_of_env.astype("int64")).to(self.device)
-        self.obs = torch.zeros((n_envs, self.n_agents, n_rays), dtype=torch.float32, **z)
+        self.obs = torch.zeros((n_envs, self.n_agents, self.n_beams), dtype=torch.float32, **z)
         self.final_obs = torch.zeros_like(self.obs)
         self.reward = torch.zeros((n_envs, self.n_agents), dtype=torch.float32, **z)
         self.terminated = torch.zeros(n_envs, dtype=torch.bool, **z)     # one byte each: the library writes 0 / 1
@@ -129,12 +150,21 @@ class DeviceVecEnv:
                                        self.truncated.data_ptr(), self.final_obs.data_ptr())
         self._io_ref = ctypes.byref(self._io)
         self._step_device = lib.fn("step_device")
+        self.state = self.final_state = None
+        if state:           # ftgp_step_device_ex: a state row per agent (capi.STATE_FIELDS)
+            self.state = torch.zeros((n_envs, self.n_agents, capi.STATE_FLOATS), dtype=torch.float32, **z)
+            self.final_state = torch.zeros_like(self.state)
+            self._extra = capi.FtgpDeviceStepExtra(self.state.data_ptr(), self.final_state.data_ptr())
+            self._extra_ref = ctypes.byref(self._extra)
+            self._step_device_ex = lib.fn("step_device_ex")
 
     def reset(self):
         """Reset every env (synchronous ftgp_reset); obs = the scans right after a reset, all zeros (custom.py:1092)."""
         self.env.reset()
         with torch.cuda.device(self.device):
             self.obs.zero_()
+        if self.state is not None:
+            self.env.state_device(self.state.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return self.obs
 
     def _check_actions(self, actions):
@@ -153,10 +183,16 @@ class DeviceVecEnv:
         self._check_actions(actions)
         self._io.action = actions.data_ptr()
         self._io.stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._step_device(self.env.h, self._io_ref)      # Env.step_device, without rebuilding the argument block
+        if self.state is None:
+            rc = self._step_device(self.env.h, self._io_ref)      # Env.step_device, without rebuilding the argument block
+            if rc:
+                self.env.lib.check(rc)
+            return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
+        rc = self._step_device_ex(self.env.h, self._io_ref, self._extra_ref)
         if rc:
             self.env.lib.check(rc)
-        return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
+        return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs, "state": self.state,
+                                                                        "final_state": self.final_state}
 
     def close(self):
         if getattr(self, "env", None) is not None:

@@ -283,6 +283,57 @@ typedef struct FtgpDeviceStep {
 } FtgpDeviceStep;
 int ftgp_step_device(FtgpEnv *env, const FtgpDeviceStep *io);
 
+/*
+ * Signals of the device step: what a training loop otherwise computes with further kernels over the scans, or reads back through the
+ * host.  The reference has none of this (one world, one Python driver call per car); the pieces are its own: the scan rows of
+ * ftgp_get_lidar, the car record, and the off_track flag of the progress block (custom.py:1343-1345).
+ *
+ * The signals setter is valid after ftgp_device_io_config only (FTGP_ERR_STATE before it), and a later ftgp_device_io_config puts the
+ * defaults {1, 0, 0, 0} back; a NULL argument sets the defaults too.  FTGP_ERR_ARG: a pool < 1 or not dividing n_rays; a max range or a
+ * penalty that is negative, NaN or infinite.  n_beams below = n_rays / scan_pool.
+ *
+ * Pooled scan: beam b of external car i of env e covers rays [b * pool, (b + 1) * pool) of the car's ftgp_get_lidar row, in binary32.
+ *   scan_max_range == 0   ranges < 0 (no hit) are left out, beam = the minimum of the others, -1 for a beam without any hit;
+ *   scan_max_range M > 0  every range r counts as r < 0 ? M : min(r, M); beam = the minimum of those, times inv, where
+ *                         inv = 1.0f / M is divided once on the host in binary32 (the kernel multiplies).
+ * With signals set, obs and final_obs of FtgpDeviceStep are float32[n_envs][n_ext][n_beams].  An env reset in the call gets the beams
+ * of its pre-reset rows in final_obs and zeros in obs; a finished car's beams are zeros (its scan is).
+ *
+ * reward[e][i] = (float)(absolute_completion after - before); if the car is off_track after the call's steps, reward - off_track_penalty
+ * (one binary32 subtraction, in every call while the car stays off-track).  terminated[e] = every external car of e has finished, or
+ * terminate_off_track is set and some external car of e is off_track.  truncated, auto_reset and final_obs: as ftgp_step_device.
+ */
+#define FTGP_STATE_FLOATS 8
+typedef struct FtgpDeviceSignals {
+    int32_t scan_pool;            /* >= 1 and a divisor of n_rays; 1 = one beam per ray */
+    float   scan_max_range;       /* 0 = raw ranges; > 0 = clip and scale to [0, 1] */
+    int32_t terminate_off_track;  /* non-zero: an env also terminates when an external car of it is off_track */
+    float   off_track_penalty;    /* >= 0, subtracted from the reward of an external car that is off_track after the call */
+} FtgpDeviceSignals;
+int ftgp_device_io_signals(FtgpEnv *env, const FtgpDeviceSignals *signals);
+
+/*
+ * The device step with state rows: the same call (the one-argument form is this one with extra = NULL), plus, per external car,
+ * float32[FTGP_STATE_FLOATS] taken from the car's record after the call's steps -- for an env reset in the call, after the reset,
+ * from the spawn state; its pre-reset rows go to final_state, where only rows of envs reset in the call are written.  With
+ * c = qw*qw - qz*qz and s = 2.0*(qw*qz) in binary64, every entry rounded once to binary32:
+ *   0 v_long = vx*c + vy*s    1 v_lat = vy*c - vx*s    2 wz (yaw rate)    3 u_speed, 4 u_steer (the controls in force)
+ *   5 sqrt(dist2), the distance to the nearest centre-line point (custom.py:1343)    6 (double)lap_completion / 100.0 (column 2 of
+ *   ftgp_get_progress)    7 off_track, 0 or 1
+ * state / final_state: float32[n_envs][n_ext][FTGP_STATE_FLOATS], device memory on the handle's device like the other buffers (a
+ * host pointer is FTGP_ERR_ARG before anything is enqueued); either may be NULL.  With default signals and no state buffer the call
+ * launches exactly the kernels of the one-argument form.
+ */
+typedef struct FtgpDeviceStepExtra {
+    float *state;
+    float *final_state;
+} FtgpDeviceStepExtra;
+int ftgp_step_device_ex(FtgpEnv *env, const FtgpDeviceStep *io, const FtgpDeviceStepExtra *extra);
+
+/* The state rows of the current state, without a step (e.g. after ftgp_reset): float32[n_envs][n_ext][FTGP_STATE_FLOATS] in device
+ * memory, ordered on `stream` like a device step (only enqueues).  After ftgp_device_io_config only (FTGP_ERR_STATE before it). */
+int ftgp_state_device(FtgpEnv *env, void *stream, float *state);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).
@@ -302,6 +353,10 @@ int ftgp_get_pose(FtgpEnv *env, double *out);
  * one step in car order (winners[id] = len(winners) + 1 inside the per-car loop, custom.py:1337,1367-1369) -- i.e. by
  * (finish_step, car index).  It survives a multi-step ftgp_rollout, so one launch to the end of a race still says who won. */
 int ftgp_get_progress(FtgpEnv *env, int32_t *out);
+
+/* double[n_cars]: the squared distance to the nearest centre-line point as the progress block stored it last (custom.py:1343; off_track
+ * is this > 1, custom.py:1344) -- the field entry 5 of a device state row is the square root of. */
+int ftgp_get_centre_dist2(FtgpEnv *env, double *out);
 
 /* int32[n_cars]: place of each car among the finishers of its env, 1 = winner, 0 = still racing (Mujoco.winners, custom.py:1125,1367-1369). */
 int ftgp_get_winners(FtgpEnv *env, int32_t *out);

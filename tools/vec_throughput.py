@@ -1,12 +1,14 @@
 """Env-steps/s of the device I/O loop (DeviceVecEnv.step on torch tensors) against the host loop (set_ctrl + step + get_lidar).
 
-    python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track]
+    python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track] [--rows device,torch_pool,signals,host] [--repeats 1,4]
 
 Device loop: constant actions, and random torch actions drawn before every call, at action_repeat 1 and 4; per-call time from HIP
-events on torch's stream around the timed calls.  Host loop: per step set_ctrl (one copy + synchronisation), step(1), get_lidar
-(the whole scan back).  One JSON line per row, then a summary line.  Run it in a fresh process: torch is imported first
+events on torch's stream around the timed calls.  Pooled observations (action_repeat 1, constant actions, beams of --pool rays clipped
+at --max-range and scaled): "torch_pool" = the raw scan plus the torch ops a user would write (-1 -> M, clamp, reshape(...).amin(-1),
+scale), "signals" = the same from the library (scan_pool, scan_max_range, state=True: ftgp_io_finish_signals_kernel).  Host loop: per
+step set_ctrl (one copy + synchronisation), step(1), get_lidar (the whole scan back).  One JSON line per row, then a summary line.  Run it in a fresh process: torch is imported first
 (ft_grandprix_amd/vec.py).  Under `rocprofv3 --kernel-trace --stats -- python tools/vec_throughput.py` the per-kernel times of a call
-(ftgp_io_ingest_kernel, ftgp_step_kernel, ftgp_io_finish_kernel) come out of the stats file.
+(ftgp_io_ingest_kernel, ftgp_step_kernel, ftgp_io_finish_kernel / ftgp_io_finish_signals_kernel) come out of the stats file.
 """
 import argparse
 import json
@@ -25,9 +27,19 @@ from ft_grandprix_amd.track import load_track  # noqa: E402
 from ft_grandprix_amd.vec import DeviceVecEnv  # noqa: E402
 
 
-def device_row(track, a, repeat, actions):
-    venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, max_episode_steps=3000, action_repeat=repeat, spawn_mode=1, seed=7)
+def device_row(track, a, repeat, actions, pooled=None):
+    """pooled: None = the raw scan; "torch" = pooled, clipped and scaled with torch ops after the call; "signals" = by the library."""
+    kw = dict(scan_pool=a.pool, scan_max_range=a.max_range, state=True) if pooled == "signals" else {}
+    venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, max_episode_steps=3000, action_repeat=repeat, spawn_mode=1, seed=7, **kw)
     dev = venv.device
+    M, inv = float(a.max_range), 1.0 / float(a.max_range)
+
+    def step(actions_):
+        obs = venv.step(actions_)[0]
+        if pooled == "torch":
+            obs = torch.where(obs < 0, M, obs).clamp(max=M).reshape(a.envs, 1, a.rays // a.pool, a.pool).amin(-1) * inv
+        return obs
+
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
     const = torch.tensor([1.5, 0.0], device=dev).expand(a.envs, 1, 2).contiguous()
@@ -40,20 +52,22 @@ def device_row(track, a, repeat, actions):
 
     venv.reset()
     for _ in range(a.warmup):
-        venv.step(act())
+        step(act())
     stream = torch.cuda.current_stream(dev)
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record(stream)
     w0 = time.perf_counter()
     for _ in range(a.calls):
-        venv.step(act())
+        step(act())
     t1.record(stream)
     t1.synchronize()
     wall = time.perf_counter() - w0
     ms = t0.elapsed_time(t1)
     step_ms = venv.env.last_kernel_ms()
     venv.close()
-    return {"loop": "device", "actions": actions, "action_repeat": repeat, "envs": a.envs, "rays": a.rays, "calls": a.calls,
+    loop = {None: "device", "torch": "device+torch_pool", "signals": "device+signals"}[pooled]
+    extra = {} if pooled is None else {"pool": a.pool, "max_range": a.max_range}
+    return {"loop": loop, "actions": actions, "action_repeat": repeat, "envs": a.envs, "rays": a.rays, "calls": a.calls, **extra,
             "us_per_call": 1e3 * ms / a.calls, "host_us_per_call": 1e6 * wall / a.calls, "step_kernel_us_last_call": 1e3 * step_ms,
             "env_steps_per_s": a.envs * repeat * a.calls / (ms * 1e-3)}
 
@@ -82,18 +96,29 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--track", default="track")
+    ap.add_argument("--pool", type=int, default=10)
+    ap.add_argument("--max-range", type=float, default=10.0)
+    ap.add_argument("--repeats", default="1,4", help="action_repeat of the device rows, comma-separated")
+    ap.add_argument("--rows", default="device,torch_pool,signals,host", help="comma-separated: device, torch_pool, signals, host")
     a = ap.parse_args()
+    want = set(a.rows.split(","))
     track = load_track(a.track)
     rows = []
-    for repeat in (1, 4):
-        for actions in ("constant", "random"):
-            rows.append(device_row(track, a, repeat, actions))
+    if "device" in want:
+        for repeat in (int(r) for r in a.repeats.split(",")):
+            for actions in ("constant", "random"):
+                rows.append(device_row(track, a, repeat, actions))
+                print(json.dumps(rows[-1]), flush=True)
+    for name, pooled in (("torch_pool", "torch"), ("signals", "signals")):
+        if name in want:
+            rows.append(device_row(track, a, 1, "constant", pooled))
             print(json.dumps(rows[-1]), flush=True)
-    rows.append(host_row(track, a))
-    print(json.dumps(rows[-1]), flush=True)
-    host = rows[-1]["env_steps_per_s"]
-    print(json.dumps({"summary": {f"device_r{r['action_repeat']}_{r['actions']}_over_host": r["env_steps_per_s"] / host
-                                  for r in rows if r["loop"] == "device"}}))
+    if "host" in want:
+        rows.append(host_row(track, a))
+        print(json.dumps(rows[-1]), flush=True)
+        host = rows[-1]["env_steps_per_s"]
+        print(json.dumps({"summary": {f"device_r{r['action_repeat']}_{r['actions']}_over_host": r["env_steps_per_s"] / host
+                                      for r in rows if r["loop"] == "device"}}))
 
 
 if __name__ == "__main__":
