@@ -109,6 +109,7 @@ struct TrackBufs {
     DevBuf<uint16_t> field; DevBuf<uint32_t> bits, nearbits;
     DevBuf<double> edt;               // FTGP_LIDAR_FAKELIDAR: distance transform
     int width = 0, height = 0;
+    size_t block = 0;                 // byte offset of the track's parameter block in d_params (track 0: 0)
 };
 
 }  // namespace
@@ -120,7 +121,7 @@ struct FtgpEnv {
     Stream stream, side;
     Event ev_start, ev_stop[2], ev_metrics, ev_gather;      // ev_stop: one per metrics slot
     bool timed = false;
-    bool ext_launch = true;      // FTGP_LAUNCH_PLAIN=1 switches it off (tools/launch_host.sh)
+    bool ext_launch = true;      // FTGP_LAUNCH_PLAIN switches it off (tools/launch_host.sh)
     bool last_roster = false;    // the newest launch ran the ROSTER instantiation
     // device buffers
     std::vector<TrackBufs> trk;       // per track: box field or distance transform, wall bitmaps (one entry for a one-track handle)
@@ -132,7 +133,6 @@ struct FtgpEnv {
     DevBuf<double> d_fan;             // FTGP_LIDAR_FAKELIDAR: binary64 fan
     // multi-track handles (ftgp_create_tracks): one parameter block per track in d_params, the workgroup table behind track 0's
     int n_tracks = 1;
-    std::vector<size_t> blocks;       // byte offset of each track's parameter block in d_params (track 0: 0)
     DevBuf<int32_t> d_env_track;      // [n_envs] the track of every env (null with one track)
     int grid = 0;                     // workgroups of a step launch
     // This rank's metrics record lives in two slots (device memory for RCCL, pinned host memory for the caller) that successive
@@ -144,7 +144,6 @@ struct FtgpEnv {
     HostBuf<double> h_gather;         // pinned [world][FTGP_METRIC_DOUBLES]: landing buffer of the all-gather
     HostBuf<double> h_wg_metrics;     // pinned [2][workgroups][FTGP_METRIC_DOUBLES]: the workgroups' partial records of a launch (one rank, no communicator:
                                       // nothing on the device needs the launch's record, the host adds the partial records up -- collect_slot())
-    int n_blocks = 0;                 // workgroups of a step launch
     bool slot_partial[2] = { false, false };   // the record of that slot's launch is in h_wg_metrics (partial records), not in h_metrics
     bool gather_open = false;         // ftgp_metrics_allgather_begin without its _end
     int gather_slot = 0;              // the slot that exchange reads
@@ -299,31 +298,58 @@ int open_device(int id)
     return 0;
 }
 
+// The FTGP_* environment switches (INTEGRATION.md has the table).  ftgp_create / ftgp_create_tracks read them once, here, and hand them
+// down: the plan is a function of its arguments.
+enum { kOrderBlocks = 0, kOrderXcd = 1 };     // FTGP_TRACK_ORDER (plan_workgroups)
+struct Switches {
+    bool no_pairs = false, group_order_plain = false, puck_test = false, no_fused_metrics = false, no_host_sum = false, launch_plain = false, verbose = false;
+    int sectors_rt = 0;               // 8, 16, 32 or 64 direction sectors; 0: by car count (sector_count)
+    int waves_per_block = 16;         // 1 .. 16
+    int cars_per_block = 0;           // as given: plan_shape takes it where it is in range, rounded down to whole envs
+    int lds_cap = 80 * 1024;          // bytes, of 16 .. 160 KiB
+    int pair_tail = 2;
+    int track_order = kOrderXcd;
+};
+
+Switches read_switches()
+{
+    Switches sw;
+    sw.no_pairs = getenv("FTGP_NO_PAIRS") != nullptr; sw.group_order_plain = getenv("FTGP_GROUP_ORDER_PLAIN") != nullptr; sw.puck_test = getenv("FTGP_PUCK_TEST") != nullptr;
+    sw.no_fused_metrics = getenv("FTGP_NO_FUSED_METRICS") != nullptr; sw.no_host_sum = getenv("FTGP_NO_HOST_SUM") != nullptr;
+    sw.launch_plain = getenv("FTGP_LAUNCH_PLAIN") != nullptr; sw.verbose = getenv("FTGP_VERBOSE") != nullptr;
+    if (const char* sv = getenv("FTGP_SECTORS_RT")) { const int c = atoi(sv); if (c == 8 || c == 16 || c == 32 || c == 64) sw.sectors_rt = c; }
+    if (const char* sv = getenv("FTGP_WAVES_PER_BLOCK")) { const int c = atoi(sv); if (c >= 1 && c <= 16) sw.waves_per_block = c; }
+    if (const char* sv = getenv("FTGP_CARS_PER_BLOCK")) sw.cars_per_block = atoi(sv);
+    if (const char* sv = getenv("FTGP_LDS_CAP_KB")) { const int c = atoi(sv); if (c >= 16 && c <= 160) sw.lds_cap = c * 1024; }
+    if (const char* sv = getenv("FTGP_PAIR_TAIL")) sw.pair_tail = atoi(sv);
+    if (const char* sv = getenv("FTGP_TRACK_ORDER")) sw.track_order = strcmp(sv, "blocks") == 0 ? kOrderBlocks : kOrderXcd;
+    return sw;
+}
+
 // Direction sectors of the box field: more slope slices mean fewer march iterations and a larger field.  A large batch is bound by
 // throughput and by what of the field its cars keep in the 4-MiB L2s (16 sectors: 32 bytes per pixel); a small one by the latency of
 // its longest rays (64 sectors); 16384 cars (config 5) do best with 8.  Measured: profiles/round4/ab_sectors.log.  Results do not depend on the choice.
-int sector_count(const FtgpConfig& cfg)
+int sector_count(const FtgpConfig& cfg, const Switches& sw)
 {
     const long cars_total = (long)cfg.n_envs * cfg.cars_per_env;
-    int n_sectors = cars_total >= 8192 ? 8 : cars_total >= 2048 ? 16 : 64;
-    if (const char* sv = getenv("FTGP_SECTORS_RT")) { const int c = atoi(sv); if (c == 8 || c == 16 || c == 32 || c == 64) n_sectors = c; }
-    return n_sectors;
+    return sw.sectors_rt ? sw.sectors_rt : cars_total >= 8192 ? 8 : cars_total >= 2048 ? 16 : 64;
 }
 
 // ftgp_create, step 1: the checks of the configuration with its tracks (no device call).  named: an error of a track names its index
 // (ftgp_create_tracks).
-int validate(const FtgpConfig& cfg, const FtgpTrack* tracks, int n_tracks, bool named)
+int validate(const FtgpConfig& cfg, const FtgpTrack* tracks, int n_tracks, bool named, const Switches& sw)
 {
     if (cfg.abi_version != FTGP_ABI_VERSION) return fail(FTGP_ERR_ARG, "abi version mismatch%s");
     if (cfg.n_envs < 1 || cfg.cars_per_env < 1 || cfg.cars_per_env > 8 || cfg.n_rays < 1) return fail(FTGP_ERR_ARG, "bad n_envs / cars_per_env / n_rays%s");
     if (cfg.spawn_mode == 0 && (cfg.cars_per_env + 4) * 2 + 1 >= FTGP_PATH_POINTS) return fail(FTGP_ERR_ARG, "too many cars for the reference spawn rule%s");
     auto bad = [&](int k, int rc) { return named ? name_track(rc, k) : rc; };
+    const uint64_t n_sectors = (uint64_t)sector_count(cfg, sw);
     for (int k = 0; k < n_tracks; ++k) {
         const FtgpTrack& t = tracks[k];
         if (t.width < 1 || t.height < 1 || !t.bits || !t.path || t.words_per_row < (t.width + 31) / 32) return bad(k, fail(FTGP_ERR_ARG, "bad track%s"));
         if (t.width > 8192 || t.height > 8192) return bad(k, fail(FTGP_ERR_ARG, "images above 8192 pixels are not supported%s"));
         // the march addresses the field with a 32-bit byte offset
-        if ((uint64_t)ftgp_plane256(t.width, t.height) * 256u * (uint64_t)sector_count(cfg) > 0xFFFFFFFFull)
+        if ((uint64_t)ftgp_plane256(t.width, t.height) * 256u * n_sectors > 0xFFFFFFFFull)
             return bad(k, fail(FTGP_ERR_ARG, "track image too large: the sector box field (2 bytes per pixel and direction sector) must stay below 4 GiB%s"));
     }
     if (cfg.env_base < 0) return fail(FTGP_ERR_ARG, "env_base < 0%s");
@@ -338,37 +364,32 @@ int validate(const FtgpConfig& cfg, const FtgpTrack* tracks, int n_tracks, bool 
     return 0;
 }
 
-int validate(const FtgpConfig& cfg) { return validate(cfg, &cfg.track, 1, false); }      // ftgp_create's checks of cfg.track
-
 // ftgp_create, step 2: the plan -- everything that fixes what the step kernel does; host arithmetic only (no HIP call)
 struct Plan {
-    DeviceParams P = DeviceParams();  // value-initialised (padding bytes zero: the block is uploaded as it lies); every pointer null
-    HostTables tab;                   // bitmaps and run lengths of the track (build_tables)
+    struct Track {
+        DeviceParams P = DeviceParams();  // the batch's parameter block with the track's own values (plan_track_params).  Value-initialised
+                                          // (padding bytes zero: the block is uploaded as it lies); every pointer null
+        HostTables tab;               // bitmaps and run lengths of the track (build_tables)
+        std::vector<double> spawn;    // [FTGP_PATH_POINTS][4] x, y, qw, qz
+        std::vector<double> path;     // [FTGP_PATH_POINTS][2] the caller's centre-line
+    };
+    std::vector<Track> tracks;        // one per track of the handle (ftgp_create: one)
     std::vector<float> ray;           // [n_rays][2] binary32 fan, zero-padded to 16 bytes (DeviceParams::ray_dir)
     std::vector<double> fan;          // [n_rays][2] binary64 fan (FAKELIDAR: DeviceParams::fan_dirs)
-    std::vector<double> spawn;        // [FTGP_PATH_POINTS][4] x, y, qw, qz
     std::vector<float> cover;         // cover-count thresholds of nidc, then of fast, cover_kmax + 1 each (+ padding)
     std::vector<unsigned char> veh;   // the VehLds image, padded to 16 bytes
     std::vector<int32_t> tasks;       // [2][cars_per_block * tasks_per_car][4] the sweep's task tables (DeviceParams::task_tab)
+    std::vector<int32_t> wg;          // [n_wg][4] the workgroup table: block offset (set by layout_images), first car, cars, track.  Uploaded for several tracks only
+    std::vector<int32_t> env_track;   // [n_envs]; uploaded for several tracks only
     int n_wg = 0;                     // workgroups of a step launch
-    // multi-track handles (plan_tracks); the members above are track 0's and the batch's
-    struct Track {
-        DeviceParams P;               // the track's parameter block: the batch's, with the track's own values (plan_track_params)
-        HostTables tab;
-        std::vector<double> spawn;
-    };
-    std::vector<Track> more;          // tracks 1 .. n_tracks - 1
-    std::vector<int32_t> wg;          // [n_wg][4] the workgroup table (FTGP_PARAMS_BYTES): block offset (set by the upload), first car, cars, track
-    std::vector<int32_t> env_track;   // [n_envs]
 };
 
 // workgroup shape: whole envs, at most 16 cars (K1 / K3 run on the lanes of one wave), two workgroups per CU
 // (<= 80 KiB of LDS each) so that 8 waves per SIMD hide the latency of the field loads
-int plan_shape(DeviceParams& P)
+int plan_shape(DeviceParams& P, const Switches& sw)
 {
     const int unit = P.cars_per_env;
-    int wpb = 16;
-    if (const char* sv = getenv("FTGP_WAVES_PER_BLOCK")) { const int c = atoi(sv); if (c >= 1 && c <= 16) wpb = c; }
+    const int wpb = sw.waves_per_block, lds_cap = sw.lds_cap;
     int want = (FTGP_MAX_CARS_PER_BLOCK / unit) * unit;
     // small batches: fewer cars per workgroup so that every CU gets work.  Up to four envs per CU a batch runs best as ONE workgroup per CU
     // (its step is the driver -> dynamics latency chain plus one sweep task per wave: a second workgroup on the CU only competes for issue
@@ -379,15 +400,13 @@ int plan_shape(DeviceParams& P)
     const int per_cu = (n_units + n_cu - 1) / n_cu;
     const int spread = (per_cu <= 4 ? std::max(1, per_cu) : std::max(1, n_units / (2 * n_cu))) * unit;
     int cpb = std::min(want, spread);
-    if (const char* sv = getenv("FTGP_CARS_PER_BLOCK")) { const int c = atoi(sv); if (c >= unit && c <= FTGP_MAX_CARS_PER_BLOCK) cpb = (c / unit) * unit; }
-    int lds_cap = 80 * 1024;
-    if (const char* sv = getenv("FTGP_LDS_CAP_KB")) { const int c = atoi(sv); if (c >= 16 && c <= 160) lds_cap = c * 1024; }
+    if (sw.cars_per_block >= unit && sw.cars_per_block <= FTGP_MAX_CARS_PER_BLOCK) cpb = (sw.cars_per_block / unit) * unit;
     while (cpb > unit && lds_layout(P, cpb, wpb) > lds_cap) cpb -= unit;
     if (lds_layout(P, cpb, wpb) > 160 * 1024) {
         snprintf(g_err, sizeof g_err, "one env of %d car(s) with a %d-ray scan does not fit the 160 KiB LDS", unit, P.n_rays);
         return FTGP_ERR_ARG;
     }
-    if (getenv("FTGP_VERBOSE"))
+    if (sw.verbose)
         fprintf(stderr, "ftgp_create: %d cars x %d waves per workgroup, %d B of LDS (cap %d)\n", cpb, wpb, lds_layout(P, cpb, wpb), lds_cap);
     return 0;
 }
@@ -415,10 +434,10 @@ void plan_fan(const FtgpConfig& cfg, std::vector<float>& ray, std::vector<double
 }
 
 // the sweep's work list (lidar_groups): draw g -> (kidx = g / cars_per_block, car slot = g % cars_per_block), task = group_order[kidx]
-void plan_task_order(const FtgpConfig& cfg, const std::vector<float>& ray, DeviceParams& P)
+void plan_task_order(const FtgpConfig& cfg, const std::vector<float>& ray, const Switches& sw, DeviceParams& P)
 {
     const int R = cfg.n_rays, halfR = R / 2;
-    bool sym = R % 2 == 0 && !getenv("FTGP_NO_PAIRS");
+    bool sym = R % 2 == 0 && !sw.no_pairs;
     for (int j = 0; sym && j < halfR; ++j)
         sym = ray[2 * (size_t)(j + halfR)] == -ray[2 * (size_t)j] && ray[2 * (size_t)(j + halfR) + 1] == -ray[2 * (size_t)j + 1] &&
               std::signbit(ray[2 * (size_t)(j + halfR)]) != std::signbit(ray[2 * (size_t)j]) && std::signbit(ray[2 * (size_t)(j + halfR) + 1]) != std::signbit(ray[2 * (size_t)j + 1]);
@@ -434,13 +453,12 @@ void plan_task_order(const FtgpConfig& cfg, const std::vector<float>& ray, Devic
     std::vector<std::pair<double, int>> key;
     for (int t : tasks) {
         const double mid = std::min((double)R - 1.0, (double)(t & 0xffff) + 31.5);
-        key.push_back({ getenv("FTGP_GROUP_ORDER_PLAIN") ? 0.0 : -fabs(cos(2.0 * M_PI * mid / (double)R)), t });
+        key.push_back({ sw.group_order_plain ? 0.0 : -fabs(cos(2.0 * M_PI * mid / (double)R)), t });
     }
     std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
     // the cheapest pairs -- the last tasks a sweep draws -- go out as two single groups each: the waves then end a sweep within ONE short
     // group of each other, not within two (the set-up shared inside a pair is worth less than that at the very end)
-    int tail = 2;
-    if (const char* sv = getenv("FTGP_PAIR_TAIL")) tail = atoi(sv);
+    const int tail = sw.pair_tail;
     std::vector<int> order;
     for (size_t k = 0; k < key.size(); ++k) {
         const int t = key[k].second;
@@ -454,7 +472,7 @@ void plan_task_order(const FtgpConfig& cfg, const std::vector<float>& ray, Devic
     const double gamma = 32.0 * (2.0 * M_PI / (double)R) + 0.021;
     if (cfg.fan_dirs || gamma >= 1.5) { P.group_cg = -2.0f; P.group_sg = 0.0f; }
     else { P.group_cg = (float)cos(gamma); P.group_sg = (float)sin(gamma); }
-    if (getenv("FTGP_VERBOSE")) fprintf(stderr, "ftgp_create: %d sweep tasks per car (%s)\n", P.tasks_per_car, sym ? "pairs of opposite ray groups" : "single groups");
+    if (sw.verbose) fprintf(stderr, "ftgp_create: %d sweep tasks per car (%s)\n", P.tasks_per_car, sym ? "pairs of opposite ray groups" : "single groups");
 }
 
 // the sweep's task tables (DeviceParams::task_tab): draw g is task g / cars_per_block of car slot g % cars_per_block, with everything the
@@ -488,7 +506,7 @@ int plan_task_table(const DeviceParams& P, std::vector<int32_t>& tt)
 double track_diagonal(const FtgpTrack& t) { return hypot((double)t.width * t.px_size_x, (double)t.height * t.px_size_y); }
 
 // the VehLds image: the vehicle constants as the step kernel stages them into LDS; diag = the longest map diagonal of the handle's tracks
-void plan_vehicle(const DeviceParams& P, double diag, std::vector<unsigned char>& img)
+void plan_vehicle(const DeviceParams& P, double diag, const Switches& sw, std::vector<unsigned char>& img)
 {
     const FtgpVehicle& v = P.veh;
     img.assign((size_t)pad16(sizeof(VehLds)), 0);
@@ -510,8 +528,8 @@ void plan_vehicle(const DeviceParams& P, double diag, std::vector<unsigned char>
         const double r = v.lidar_ring_radius;
         const double need = r > 0.0 ? 5.0 * ldexp(1.0, -24) * diag * diag / (2.0 * r) : 0.0;
         const double have = std::min(std::min(v.lidar_x - r - v.box_xmin, v.box_xmax - (v.lidar_x + r)), std::min(v.lidar_y - r - v.box_ymin, v.box_ymax - (v.lidar_y + r)));
-        vl.puck_in_box = (have >= need && !getenv("FTGP_PUCK_TEST")) ? 1 : 0;
-        if (getenv("FTGP_VERBOSE"))
+        vl.puck_in_box = (have >= need && !sw.puck_test) ? 1 : 0;
+        if (sw.verbose)
             fprintf(stderr, "ftgp_create: inter-vehicle rays test %s (the puck lies %.4f inside the box, %.4f needed on a map of diagonal %.2f)\n",
                     vl.puck_in_box ? "the box only" : "the box and the puck's circle", have, need, diag);
     }
@@ -552,75 +570,13 @@ void plan_track_tables(const FtgpTrack& t, const DeviceParams& P, HostTables& ta
     }
 }
 
-// n_cu: compute units of the device (the workgroup shape depends on it)
-int plan_create(const FtgpConfig& cfg, int n_cu, Plan& pl)
-{
-    const FtgpTrack& t = cfg.track;
-    const FtgpVehicle& v = cfg.vehicle;
-    DeviceParams& P = pl.P;
-    P.n_envs = cfg.n_envs; P.cars_per_env = cfg.cars_per_env; P.n_cars = cfg.n_envs * cfg.cars_per_env;
-    P.n_rays = cfg.n_rays; P.lap_target = cfg.lap_target; P.spawn_mode = cfg.spawn_mode; P.env_base = cfg.env_base;
-    P.ranges_stride = (cfg.n_rays + 31) & ~31;      // rows start on 128-B boundaries
-    P.seed = cfg.seed; P.dt = cfg.dt;
-    P.rpp = (2 * M_PI) / (double)cfg.n_rays;
-    P.two_over_rpp = (float)(2.0 / P.rpp);
-    P.bubble_wrap = cfg.bubble_wrap ? 1 : 0;        // cfg.naive_flatten: accepted, no effect on a planar model (custom.py:1338-1339)
-    P.lidar_mode = cfg.lidar_mode;
-    P.map_size = cfg.map_size > 0.0 ? cfg.map_size : 40.0;                     // 20 * scale, custom.py:1155,1382
-    P.n_sectors = sector_count(cfg); P.slice_factor = FTGP_SLICE_FACTOR(FTGP_SLOPE_SLICES);
-    plan_track_params(cfg, t, P);
-    P.veh = cfg.vehicle;
-    {   // static wheel loads from the wheelbase split
-        const double wtot = v.mass * v.gravity;
-        if (v.kind == FTGP_VEHICLE_TRICYCLE) {       // two driven wheels behind the origin, the caster (wheel 2) in front
-            const double a_f = v.wheel_x[2], a_r = -0.5 * (v.wheel_x[0] + v.wheel_x[1]);
-            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_f / (a_f + a_r)));
-            P.wheel_load[2] = wtot * (a_r / (a_f + a_r)); P.wheel_load[3] = 0.0;
-        } else {
-            const double a_f = 0.5 * (v.wheel_x[0] + v.wheel_x[1]), a_r = -0.5 * (v.wheel_x[2] + v.wheel_x[3]);
-            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_r / (a_f + a_r)));
-            P.wheel_load[2] = P.wheel_load[3] = 0.5 * (wtot * (a_f / (a_f + a_r)));
-        }
-    }
-    P.eighth = (int)((double)cfg.n_rays / 8.0);                    // nidc.py:18
-    // the largest cover count any positive sample can produce (that of the smallest positive float), over both drivers
-    const double tiny = (double)1.401298464e-45f;
-    P.cover_kmax = std::max(1, std::max(cover_count_host(0.24, P.rpp, tiny), cover_count_host(0.12, P.rpp, tiny)));
-    P.win_floats = ((P.eighth & 3) + (cfg.n_rays - 2 * P.eighth) + 1 + 3) & ~3;       // window at float (eighth % 4), ranges[0] in the last float
-    P.n_cu = n_cu;
-    if ((cfg.n_rays + FTGP_WAVE - 1) / FTGP_WAVE > FTGP_MAX_GROUPS) return fail(FTGP_ERR_ARG, "n_rays above 16384 is not supported%s");
-    if (int rc = plan_shape(P)) return rc;
-    pl.n_wg = (P.n_cars + P.cars_per_block - 1) / P.cars_per_block;
-    plan_fan(cfg, pl.ray, pl.fan);
-    plan_task_order(cfg, pl.ray, P);
-    if (int rc = plan_task_table(P, pl.tasks)) return rc;
-    plan_track_tables(t, P, pl.tab, pl.spawn);
-    {   // cover-count thresholds: nidc (car_width 0.12, nidc.py:5) then fast (0.06, fast.py:4), each padded to the staged size
-        const size_t stride = (size_t)P.cover_kmax + 1, padded = (size_t)pad16(sizeof(float) * stride) / sizeof(float);
-        pl.cover.assign(stride + padded + 4, 0.0f);
-        build_cover_table(0.12, cfg.n_rays, P.cover_kmax, pl.cover.data());
-        build_cover_table(0.06, cfg.n_rays, P.cover_kmax, pl.cover.data() + stride);
-    }
-    plan_vehicle(P, track_diagonal(t), pl.veh);
-    return 0;
-}
-
 // Workgroup order of a multi-track launch (FTGP_TRACK_ORDER=blocks|xcd).  Workgroups are dealt round robin over the 8 XCDs, so workgroups b
 // and b + 8 share an L2 (observed, not promised).  blocks: the workgroups in car order, track after track -- every XCD then holds a share
 // of every track's field.  xcd: the k-th workgroup in car order takes the k-th index of the grid sorted by (b % 8, b), so that each track
 // owns a run of residues b % 8, in proportion to its number of workgroups, and an L2 holds the fields of one or two tracks.  Results do
 // not depend on the order.
-enum { kOrderBlocks = 0, kOrderXcd = 1 };
-int track_order()
-{
-    const char* sv = getenv("FTGP_TRACK_ORDER");
-    if (sv && strcmp(sv, "blocks") == 0) return kOrderBlocks;
-    if (sv && strcmp(sv, "xcd") == 0) return kOrderXcd;
-    return kOrderXcd;
-}
-
 // The workgroup table: whole envs of one track per workgroup, each block of envs its own workgroups with a ragged last one.  wg[4 b ..]
-// = (0: the block offset, filled in by the upload; first car; cars; track).
+// = (0: the block offset, filled in by layout_images; first car; cars; track).
 void plan_workgroups(int cpb, int cpe, const int32_t* envs_per_track, int n_tracks, int order, std::vector<int32_t>& wg)
 {
     std::vector<int32_t> list;
@@ -642,30 +598,146 @@ void plan_workgroups(int cpb, int cpe, const int32_t* envs_per_track, int n_trac
     for (int k = 0; k < n; ++k) std::copy(&list[4 * (size_t)k], &list[4 * (size_t)k] + 4, &wg[4 * (size_t)slot[k]]);
 }
 
-// ftgp_create_tracks, step 2: the plan of the batch (shape, sectors, fan, tasks: as for one track of all n_envs envs), then every track's
-// own block, tables and spawn table, and the workgroup table.  Host arithmetic only.
-int plan_tracks(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, int n_cu, Plan& pl)
+// ftgp_create / ftgp_create_tracks, step 2: the plan of the batch (shape, sectors, fan, tasks: as for one track of all n_envs envs), then
+// every track's own block, tables and spawn table, and the workgroup table.  A function of its arguments; host arithmetic only.
+// envs_per_track: [n_tracks], summing to cfg.n_envs (cfg.track is not read).  n_cu: compute units of the device (the workgroup shape
+// depends on it).
+int plan(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, int n_cu, const Switches& sw, Plan& pl)
 {
-    FtgpConfig c0 = cfg;
-    c0.track = tracks[0];
-    if (int rc = plan_create(c0, n_cu, pl)) return rc;
-    pl.more.resize((size_t)n_tracks - 1);
-    for (int t = 1; t < n_tracks; ++t) {
-        Plan::Track& k = pl.more[(size_t)t - 1];
-        k.P = pl.P;
+    const FtgpVehicle& v = cfg.vehicle;
+    pl.tracks.assign((size_t)n_tracks, Plan::Track());
+    DeviceParams& P = pl.tracks[0].P;               // the batch's values first; the tracks' own follow below
+    P.n_envs = cfg.n_envs; P.cars_per_env = cfg.cars_per_env; P.n_cars = cfg.n_envs * cfg.cars_per_env;
+    P.n_rays = cfg.n_rays; P.lap_target = cfg.lap_target; P.spawn_mode = cfg.spawn_mode; P.env_base = cfg.env_base;
+    P.ranges_stride = (cfg.n_rays + 31) & ~31;      // rows start on 128-B boundaries
+    P.seed = cfg.seed; P.dt = cfg.dt;
+    P.rpp = (2 * M_PI) / (double)cfg.n_rays;
+    P.two_over_rpp = (float)(2.0 / P.rpp);
+    P.bubble_wrap = cfg.bubble_wrap ? 1 : 0;        // cfg.naive_flatten: accepted, no effect on a planar model (custom.py:1338-1339)
+    P.lidar_mode = cfg.lidar_mode;
+    P.map_size = cfg.map_size > 0.0 ? cfg.map_size : 40.0;                     // 20 * scale, custom.py:1155,1382
+    P.n_sectors = sector_count(cfg, sw); P.slice_factor = FTGP_SLICE_FACTOR(FTGP_SLOPE_SLICES);
+    P.veh = cfg.vehicle;
+    {   // static wheel loads from the wheelbase split
+        const double wtot = v.mass * v.gravity;
+        if (v.kind == FTGP_VEHICLE_TRICYCLE) {       // two driven wheels behind the origin, the caster (wheel 2) in front
+            const double a_f = v.wheel_x[2], a_r = -0.5 * (v.wheel_x[0] + v.wheel_x[1]);
+            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_f / (a_f + a_r)));
+            P.wheel_load[2] = wtot * (a_r / (a_f + a_r)); P.wheel_load[3] = 0.0;
+        } else {
+            const double a_f = 0.5 * (v.wheel_x[0] + v.wheel_x[1]), a_r = -0.5 * (v.wheel_x[2] + v.wheel_x[3]);
+            P.wheel_load[0] = P.wheel_load[1] = 0.5 * (wtot * (a_r / (a_f + a_r)));
+            P.wheel_load[2] = P.wheel_load[3] = 0.5 * (wtot * (a_f / (a_f + a_r)));
+        }
+    }
+    P.eighth = (int)((double)cfg.n_rays / 8.0);                    // nidc.py:18
+    // the largest cover count any positive sample can produce (that of the smallest positive float), over both drivers
+    const double tiny = (double)1.401298464e-45f;
+    P.cover_kmax = std::max(1, std::max(cover_count_host(0.24, P.rpp, tiny), cover_count_host(0.12, P.rpp, tiny)));
+    P.win_floats = ((P.eighth & 3) + (cfg.n_rays - 2 * P.eighth) + 1 + 3) & ~3;       // window at float (eighth % 4), ranges[0] in the last float
+    P.n_cu = n_cu;
+    if ((cfg.n_rays + FTGP_WAVE - 1) / FTGP_WAVE > FTGP_MAX_GROUPS) return fail(FTGP_ERR_ARG, "n_rays above 16384 is not supported%s");
+    if (int rc = plan_shape(P, sw)) return rc;
+    plan_fan(cfg, pl.ray, pl.fan);
+    plan_task_order(cfg, pl.ray, sw, P);
+    if (int rc = plan_task_table(P, pl.tasks)) return rc;
+    {   // cover-count thresholds: nidc (car_width 0.12, nidc.py:5) then fast (0.06, fast.py:4), each padded to the staged size
+        const size_t stride = (size_t)P.cover_kmax + 1, padded = (size_t)pad16(sizeof(float) * stride) / sizeof(float);
+        pl.cover.assign(stride + padded + 4, 0.0f);
+        build_cover_table(0.12, cfg.n_rays, P.cover_kmax, pl.cover.data());
+        build_cover_table(0.06, cfg.n_rays, P.cover_kmax, pl.cover.data() + stride);
+    }
+    double diag = 0.0;                              // of the largest track
+    pl.env_track.clear();
+    for (int t = 0; t < n_tracks; ++t) {
+        Plan::Track& k = pl.tracks[(size_t)t];
+        k.P = P;
         plan_track_params(cfg, tracks[t], k.P);
         plan_track_tables(tracks[t], k.P, k.tab, k.spawn);
+        k.path.assign(tracks[t].path, tracks[t].path + 2 * FTGP_PATH_POINTS);
+        diag = std::max(diag, track_diagonal(tracks[t]));
+        pl.env_track.insert(pl.env_track.end(), (size_t)envs_per_track[t], t);
     }
-    double diag = 0.0;                        // the vehicle image again, for the largest of the tracks (plan_create saw the first only)
-    for (int t = 0; t < n_tracks; ++t) diag = std::max(diag, track_diagonal(tracks[t]));
-    if (n_tracks > 1) plan_vehicle(pl.P, diag, pl.veh);
-    pl.env_track.clear();
-    for (int t = 0; t < n_tracks; ++t) pl.env_track.insert(pl.env_track.end(), (size_t)envs_per_track[t], t);
-    plan_workgroups(pl.P.cars_per_block, cfg.cars_per_env, envs_per_track, n_tracks, track_order(), pl.wg);
+    plan_vehicle(P, diag, sw, pl.veh);
+    plan_workgroups(P.cars_per_block, cfg.cars_per_env, envs_per_track, n_tracks, sw.track_order, pl.wg);
     pl.n_wg = (int)pl.wg.size() / 4;
-    if (getenv("FTGP_VERBOSE"))
-        fprintf(stderr, "ftgp_create: %d tracks, %d workgroups in %s order\n", n_tracks, pl.n_wg, track_order() == kOrderXcd ? "xcd" : "blocks");
+    if (sw.verbose)
+        fprintf(stderr, "ftgp_create: %d track(s), %d workgroups in %s order\n", n_tracks, pl.n_wg, sw.track_order == kOrderXcd ? "xcd" : "blocks");
     return 0;
+}
+
+// The device addresses that the parameter blocks and the staging images point to: the upload's allocations (the host checks make them up).
+struct DeviceAddrs {
+    struct Track { const uint16_t* field; const double* edt; const uint32_t* bits, * nearbits; };
+    std::vector<Track> trk;
+    const double* fan = nullptr, * path = nullptr, * spawn = nullptr;      // path, spawn: every track's, track after track
+    const void* veh = nullptr; const float* ray = nullptr, * cover = nullptr;
+    CarState* cars = nullptr; float* ranges = nullptr; int64_t* steps = nullptr;
+    double* wg_metrics = nullptr; unsigned int* wg_ticket = nullptr; double* metrics_dev = nullptr, * metrics_host = nullptr;     // null: no fused metrics
+    double* wg_metrics_host = nullptr;
+    const unsigned char* params = nullptr, * stage = nullptr;              // where the two images will lie
+};
+
+// Sizes of the two images.  Parameter image: track 0's block | (several tracks: the workgroup table) | the sweep's task tables | the
+// blocks of tracks 1 .. T - 1.  Staging image, one per track: the LDS bytes [off_params, off_cars) as every workgroup of the track wants
+// them, then both drivers' cover tables.
+struct ImageSizes { size_t head, wg, tasks, params, stage_head, stage; };
+ImageSizes image_sizes(const Plan& pl)
+{
+    const size_t T = pl.tracks.size();
+    const DeviceParams& P = pl.tracks[0].P;
+    ImageSizes z;
+    z.head = FTGP_PARAMS_BYTES; z.wg = T > 1 ? sizeof(int32_t) * pl.wg.size() : 0; z.tasks = sizeof(int32_t) * pl.tasks.size();
+    z.params = z.head + z.wg + z.tasks + (T - 1) * z.head + 16;
+    z.stage_head = (size_t)(P.off_cars - P.off_params);
+    z.stage = z.stage_head + 2 * (size_t)P.stage_cover;
+    return z;
+}
+
+struct Images {
+    std::vector<unsigned char> params, stage;
+    std::vector<size_t> blocks;       // byte offset of each track's parameter block in the parameter image (track 0: 0)
+    DeviceParams P0;                  // track 0's finished block
+};
+
+// ftgp_create, between plan and upload: both images as they go to the device, every pointer set.  Host arithmetic only (no HIP call).
+void layout_images(const Plan& pl, const DeviceAddrs& a, Images& im)
+{
+    const DeviceParams& P = pl.tracks[0].P;         // (the LDS layout is the batch's)
+    const int T = (int)pl.tracks.size();
+    const ImageSizes z = image_sizes(pl);
+    const size_t sz_path = sizeof(double) * 2 * FTGP_PATH_POINTS, stride = (size_t)P.cover_kmax + 1;
+    im.blocks.assign((size_t)T, 0);
+    for (int k = 1; k < T; ++k) im.blocks[(size_t)k] = z.head + z.wg + z.tasks + (size_t)(k - 1) * z.head;
+    im.params.assign(z.params, 0);
+    im.stage.assign(z.stage * T, 0);
+    for (int k = 0; k < T; ++k) {
+        DeviceParams Q = pl.tracks[(size_t)k].P;     // (a copy as it lies, padding included)
+        const DeviceAddrs::Track& b = a.trk[(size_t)k];
+        Q.edt = b.edt; Q.fan_dirs = a.fan; Q.field = b.field;
+        Q.wg_metrics = a.wg_metrics; Q.wg_ticket = a.wg_ticket; Q.metrics_dev = a.metrics_dev; Q.metrics_host = a.metrics_host;
+        Q.wg_metrics_host = a.wg_metrics_host;
+        Q.bits = b.bits; Q.nearbits = b.nearbits; Q.path = a.path + 2 * FTGP_PATH_POINTS * (size_t)k; Q.spawn = a.spawn + 4 * FTGP_PATH_POINTS * (size_t)k;
+        Q.veh_dev = a.veh;
+        Q.ray_dir = a.ray; Q.cover_thr = a.cover; Q.cars = a.cars; Q.ranges = a.ranges; Q.steps = a.steps;
+        unsigned char* s = im.stage.data() + z.stage * k;
+        memcpy(s, &Q, offsetof(DeviceParams, veh));      // every pointer of the head is set by now
+        memcpy(s + (P.off_veh - P.off_params), pl.veh.data(), pl.veh.size());
+        memcpy(s + (P.off_path - P.off_params), pl.tracks[(size_t)k].path.data(), sz_path);
+        memcpy(s + (P.off_ray - P.off_params), pl.ray.data(), sizeof(float) * pl.ray.size());
+        memcpy(s + z.stage_head, pl.cover.data(), sizeof(float) * stride);
+        memcpy(s + z.stage_head + P.stage_cover, pl.cover.data() + stride, sizeof(float) * stride);
+        Q.stage_img = a.stage + z.stage * k;
+        Q.task_tab = reinterpret_cast<const int32_t*>(a.params + z.head + z.wg);
+        memcpy(im.params.data() + im.blocks[(size_t)k], &Q, sizeof(DeviceParams));
+        if (k == 0) memcpy(&im.P0, &Q, sizeof Q);
+    }
+    if (T > 1) {     // the workgroup table: each entry's block offset
+        std::vector<int32_t> wg = pl.wg;
+        for (size_t b = 0; b < wg.size(); b += 4) wg[b] = (int32_t)im.blocks[(size_t)wg[b + 3]];
+        memcpy(im.params.data() + z.head, wg.data(), z.wg);
+    }
+    memcpy(im.params.data() + z.head + z.wg, pl.tasks.data(), z.tasks);
 }
 
 // Waiting for an event of a launch is a blocked wait.  Polling hipEventQuery instead was measured (tools/launch_host.sh, round 4): 7 us
@@ -719,8 +791,8 @@ void collect_slot(const FtgpEnv* e, int slot, double* out)
 {
     if (!e->slot_partial[slot]) { memcpy(out, e->h_metrics.get() + (size_t)slot * FTGP_METRIC_DOUBLES, sizeof(double) * FTGP_METRIC_DOUBLES); return; }
     double v[FTGP_METRIC_DOUBLES] = { 0, 0, 0, 0, 0, 0, INFINITY, -INFINITY };
-    const double* r = e->h_wg_metrics.get() + (size_t)slot * e->n_blocks * FTGP_METRIC_DOUBLES;
-    for (int b = 0; b < e->n_blocks; ++b, r += FTGP_METRIC_DOUBLES) {
+    const double* r = e->h_wg_metrics.get() + (size_t)slot * e->grid * FTGP_METRIC_DOUBLES;
+    for (int b = 0; b < e->grid; ++b, r += FTGP_METRIC_DOUBLES) {
         for (int q = 0; q < 6; ++q) v[q] += r[q];
         v[6] = fmin(v[6], r[6]); v[7] = fmax(v[7], r[7]);
     }
@@ -732,8 +804,8 @@ void collect_slot(const FtgpEnv* e, int slot, double* out)
 int use_table(FtgpEnv* e, int which)
 {
     if (e->table_on_device == which) return 0;
-    for (size_t b : e->blocks)        // every track's parameter block
-        HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(e->d_params.get()) + b + offsetof(DeviceParams, car_policy), e->h_tables.get() + which * FTGP_MAX_CARS_PER_BLOCK,
+    for (const TrackBufs& t : e->trk)     // every track's parameter block
+        HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(e->d_params.get()) + t.block + offsetof(DeviceParams, car_policy), e->h_tables.get() + which * FTGP_MAX_CARS_PER_BLOCK,
                                sizeof e->P.car_policy, hipMemcpyHostToDevice, e->stream.get()));
     e->table_on_device = which;
     return 0;
@@ -844,26 +916,22 @@ void set_signals(FtgpEnv* e, const FtgpDeviceSignals& s)
     e->sig_default = s.scan_pool == 1 && !S.clip && !S.terminate_off_track && s.off_track_penalty == 0.0f;
 }
 
-// ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images.  tracks:
-// n_tracks = 1 + pl.more.size() of them.
-int upload(FtgpEnv* e, const FtgpTrack* tracks, const Plan& pl)
+// ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images
+int upload(FtgpEnv* e, const Plan& pl, const Switches& sw)
 {
-    memcpy(&e->P, &pl.P, sizeof e->P);          // as it lies, padding included
-    DeviceParams& P = e->P;
+    const DeviceParams& P = pl.tracks[0].P;         // the batch's values (e->P: track 0's finished block, at the end)
     hipStream_t s = e->stream.get();
-    const int T = 1 + (int)pl.more.size();
+    const int T = (int)pl.tracks.size();
     const size_t n_cars = (size_t)P.n_cars;
     e->n_tracks = T;
     e->trk.resize((size_t)T);
-    auto block_of = [&](int t) -> const DeviceParams& { return t == 0 ? pl.P : pl.more[(size_t)t - 1].P; };
     if (P.lidar_mode == FTGP_LIDAR_FAKELIDAR) HIP_TRY(dev_upload(e->d_fan, pl.fan.data(), pl.fan.size() * sizeof(double)));
     for (int k = 0; k < T; ++k) {
-        const FtgpTrack& t = tracks[k];
-        const DeviceParams& Q = block_of(k);
-        const HostTables& tab = k == 0 ? pl.tab : pl.more[(size_t)k - 1].tab;
+        const DeviceParams& Q = pl.tracks[(size_t)k].P;
+        const HostTables& tab = pl.tracks[(size_t)k].tab;
         TrackBufs& b = e->trk[(size_t)k];
-        b.width = t.width; b.height = t.height;
-        const size_t plane = (size_t)t.width * t.height;
+        b.width = Q.width; b.height = Q.height;
+        const size_t plane = (size_t)Q.width * Q.height;
         size_t field_bytes = 0;
         if (P.lidar_mode == FTGP_LIDAR_FAKELIDAR) {
             // The distance transform of custom.py:1149-1153 / raycast.py:24-27 (scipy.ndimage.distance_transform_edt of the non-wall
@@ -873,7 +941,7 @@ int upload(FtgpEnv* e, const FtgpTrack* tracks, const Plan& pl)
             HIP_TRY(dev_upload(d_runy, tab.runy.data(), 2 * plane * sizeof(uint16_t)));
             field_bytes = plane * sizeof(double);
             HIP_TRY(dev_alloc(b.edt, field_bytes));
-            hipLaunchKernelGGL(ftgp_edt_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, d_runy.get(), t.width, t.height, b.edt.get());
+            hipLaunchKernelGGL(ftgp_edt_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, d_runy.get(), Q.width, Q.height, b.edt.get());
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(s));
         } else {   // sector box field: upload the run lengths, search the boxes on the device
@@ -883,23 +951,23 @@ int upload(FtgpEnv* e, const FtgpTrack* tracks, const Plan& pl)
             HIP_TRY(dev_alloc(b.field, field_bytes));
             HIP_TRY(dev_upload(d_runx, tab.runx.data(), 2 * plane * sizeof(uint16_t)));
             HIP_TRY(dev_upload(d_runy, tab.runy.data(), 2 * plane * sizeof(uint16_t)));
-            hipLaunchKernelGGL(ftgp_box_field_kernel, dim3((unsigned)((plane_cells * Q.n_sectors + 255) / 256)), dim3(256), 0, s, d_runx.get(), d_runy.get(), t.width, t.height, Q.n_sectors, b.field.get());
+            hipLaunchKernelGGL(ftgp_box_field_kernel, dim3((unsigned)((plane_cells * Q.n_sectors + 255) / 256)), dim3(256), 0, s, d_runx.get(), d_runy.get(), Q.width, Q.height, Q.n_sectors, b.field.get());
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(s));
         }
-        const size_t sz_bits = sizeof(uint32_t) * (size_t)t.height * t.words_per_row;
+        const size_t sz_bits = sizeof(uint32_t) * (size_t)Q.height * Q.words_per_row;
         HIP_TRY(dev_upload(b.bits, tab.bits.data(), sz_bits));
         HIP_TRY(dev_upload(b.nearbits, tab.nearbits.data(), sz_bits));
-        if (getenv("FTGP_VERBOSE"))
-            fprintf(stderr, "ftgp_create: track %d: %d x %d px, %.1f MB of %s + %.1f MB of wall bitmaps\n", k, t.width, t.height, field_bytes / 1e6,
+        if (sw.verbose)
+            fprintf(stderr, "ftgp_create: track %d: %d x %d px, %.1f MB of %s + %.1f MB of wall bitmaps\n", k, Q.width, Q.height, field_bytes / 1e6,
                     P.lidar_mode == FTGP_LIDAR_FAKELIDAR ? "distance transform" : "box field", 2.0 * sz_bits / 1e6);
     }
     const size_t sz_path = sizeof(double) * 2 * FTGP_PATH_POINTS, sz_spawn = sizeof(double) * 4 * FTGP_PATH_POINTS;
     {   // centre-lines and spawn tables of all tracks, track after track
         std::vector<double> paths(2 * FTGP_PATH_POINTS * (size_t)T), spawns(4 * FTGP_PATH_POINTS * (size_t)T);
         for (int k = 0; k < T; ++k) {
-            memcpy(paths.data() + 2 * FTGP_PATH_POINTS * (size_t)k, tracks[k].path, sz_path);
-            memcpy(spawns.data() + 4 * FTGP_PATH_POINTS * (size_t)k, (k == 0 ? pl.spawn : pl.more[(size_t)k - 1].spawn).data(), sz_spawn);
+            memcpy(paths.data() + 2 * FTGP_PATH_POINTS * (size_t)k, pl.tracks[(size_t)k].path.data(), sz_path);
+            memcpy(spawns.data() + 4 * FTGP_PATH_POINTS * (size_t)k, pl.tracks[(size_t)k].spawn.data(), sz_spawn);
         }
         HIP_TRY(dev_upload(e->d_path, paths.data(), sz_path * T));
         HIP_TRY(dev_upload(e->d_spawn, spawns.data(), sz_spawn * T));
@@ -917,84 +985,51 @@ int upload(FtgpEnv* e, const FtgpTrack* tracks, const Plan& pl)
     HIP_TRY(hipHostGetDevicePointer((void**)&e->h_metrics_dev, e->h_metrics.get(), 0));
     e->grid = pl.n_wg;
     double* wg_metrics_host = nullptr;
-    if (!getenv("FTGP_NO_FUSED_METRICS")) {          // (diagnostic switch: tests compare the fused record with ftgp_metrics_kernel's)
+    if (!sw.no_fused_metrics) {          // (diagnostic switch: tests compare the fused record with ftgp_metrics_kernel's)
         const size_t blocks = (size_t)pl.n_wg;
         HIP_TRY(dev_alloc(e->d_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * blocks));
         HIP_TRY(dev_zeros(e->d_wg_ticket, sizeof(unsigned int), s));
-        e->n_blocks = (int)blocks;
-        if (!getenv("FTGP_NO_HOST_SUM")) {           // (diagnostic switch: the device-side hand-off of the record also with one rank)
+        if (!sw.no_host_sum) {           // (diagnostic switch: the device-side hand-off of the record also with one rank)
             HIP_TRY(host_alloc(e->h_wg_metrics, sizeof(double) * FTGP_METRIC_DOUBLES * 2 * blocks, hipHostMallocMapped));
             HIP_TRY(hipHostGetDevicePointer((void**)&wg_metrics_host, e->h_wg_metrics.get(), 0));
         }
     }
     HIP_TRY(dev_alloc(e->d_prog, sizeof(int32_t) * FTGP_PROGRESS_INTS * n_cars)); HIP_TRY(dev_alloc(e->d_core, sizeof(double) * kCoreDoubles * n_cars));
-    // the device image of the parameter blocks: track 0's block | (several tracks: the workgroup table) | the sweep's task tables | the
-    // blocks of tracks 1 .. T - 1
-    const size_t head = FTGP_PARAMS_BYTES, wg_bytes = T > 1 ? sizeof(int32_t) * pl.wg.size() : 0, tasks_bytes = sizeof(int32_t) * pl.tasks.size();
-    e->blocks.assign((size_t)T, 0);
-    for (int k = 1; k < T; ++k) e->blocks[(size_t)k] = head + wg_bytes + tasks_bytes + (size_t)(k - 1) * head;
-    std::vector<unsigned char> pimg(head + wg_bytes + tasks_bytes + (size_t)(T - 1) * head + 16, 0);
-    HIP_TRY(dev_alloc(e->d_params, pimg.size()));
-    // the staging images, one per track: the LDS bytes [off_params, off_cars) as every workgroup of the track wants them, then both drivers' cover tables
-    const size_t stage_head = (size_t)(P.off_cars - P.off_params), cover = (size_t)P.stage_cover, stride = (size_t)P.cover_kmax + 1;
-    const size_t stage_bytes = stage_head + 2 * cover;
-    HIP_TRY(dev_alloc(e->d_stage, stage_bytes * T));
-    std::vector<unsigned char> simg(stage_bytes * T, 0);
-    for (int k = 0; k < T; ++k) {
-        DeviceParams Q = block_of(k);        // (a copy as it lies, padding included)
-        const TrackBufs& b = e->trk[(size_t)k];
-        Q.edt = b.edt.get(); Q.fan_dirs = e->d_fan.get(); Q.field = b.field.get();
-        if (e->d_wg_metrics) { Q.wg_metrics = e->d_wg_metrics.get(); Q.wg_ticket = e->d_wg_ticket.get(); Q.metrics_dev = e->d_metrics.get(); Q.metrics_host = e->h_metrics_dev; }
-        Q.wg_metrics_host = wg_metrics_host;
-        Q.bits = b.bits.get(); Q.nearbits = b.nearbits.get(); Q.path = e->d_path.get() + 2 * FTGP_PATH_POINTS * (size_t)k; Q.spawn = e->d_spawn.get() + 4 * FTGP_PATH_POINTS * (size_t)k;
-        Q.veh_dev = e->d_veh.get();
-        Q.ray_dir = e->d_ray.get(); Q.cover_thr = e->d_cover.get(); Q.cars = e->d_cars.get(); Q.ranges = e->d_ranges.get(); Q.steps = e->d_steps.get();
-        unsigned char* im = simg.data() + stage_bytes * k;
-        memcpy(im, &Q, offsetof(DeviceParams, veh));      // every pointer of the head is set by now
-        memcpy(im + (P.off_veh - P.off_params), pl.veh.data(), pl.veh.size());
-        memcpy(im + (P.off_path - P.off_params), tracks[k].path, sz_path);
-        memcpy(im + (P.off_ray - P.off_params), pl.ray.data(), sizeof(float) * pl.ray.size());
-        memcpy(im + stage_head, pl.cover.data(), sizeof(float) * stride);
-        memcpy(im + stage_head + cover, pl.cover.data() + stride, sizeof(float) * stride);
-        Q.stage_img = e->d_stage.get() + stage_bytes * k;
-        Q.task_tab = reinterpret_cast<const int32_t*>(reinterpret_cast<unsigned char*>(e->d_params.get()) + head + wg_bytes);
-        memcpy(pimg.data() + e->blocks[(size_t)k], &Q, sizeof(DeviceParams));
-        if (k == 0) memcpy(&P, &Q, sizeof P);
-    }
-    HIP_TRY(hipMemcpy(e->d_stage.get(), simg.data(), simg.size(), hipMemcpyHostToDevice));
-    if (T > 1) {     // the workgroup table: each entry's block offset
-        std::vector<int32_t> wg = pl.wg;
-        for (size_t b = 0; b < wg.size(); b += 4) wg[b] = (int32_t)e->blocks[(size_t)wg[b + 3]];
-        memcpy(pimg.data() + head, wg.data(), wg_bytes);
-    }
-    memcpy(pimg.data() + head + wg_bytes, pl.tasks.data(), tasks_bytes);
-    HIP_TRY(hipMemcpy(e->d_params.get(), pimg.data(), pimg.size(), hipMemcpyHostToDevice));
+    // the two images, laid out for the addresses just allocated
+    const ImageSizes z = image_sizes(pl);
+    HIP_TRY(dev_alloc(e->d_params, z.params));
+    HIP_TRY(dev_alloc(e->d_stage, z.stage * T));
+    DeviceAddrs a;
+    for (const TrackBufs& b : e->trk) a.trk.push_back({ b.field.get(), b.edt.get(), b.bits.get(), b.nearbits.get() });
+    a.fan = e->d_fan.get(); a.path = e->d_path.get(); a.spawn = e->d_spawn.get(); a.veh = e->d_veh.get(); a.ray = e->d_ray.get(); a.cover = e->d_cover.get();
+    a.cars = e->d_cars.get(); a.ranges = e->d_ranges.get(); a.steps = e->d_steps.get();
+    if (e->d_wg_metrics) { a.wg_metrics = e->d_wg_metrics.get(); a.wg_ticket = e->d_wg_ticket.get(); a.metrics_dev = e->d_metrics.get(); a.metrics_host = e->h_metrics_dev; }
+    a.wg_metrics_host = wg_metrics_host;
+    a.params = reinterpret_cast<const unsigned char*>(e->d_params.get()); a.stage = e->d_stage.get();
+    Images im;
+    layout_images(pl, a, im);
+    for (int k = 0; k < T; ++k) e->trk[(size_t)k].block = im.blocks[(size_t)k];
+    memcpy(&e->P, &im.P0, sizeof e->P);         // as it lies, padding included
+    HIP_TRY(hipMemcpy(e->d_stage.get(), im.stage.data(), im.stage.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_params.get(), im.params.data(), im.params.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
-// ftgp_create / ftgp_create_tracks after the checks: device probe, plan, upload, reset.  envs_per_track: null for ftgp_create's one track.
-int create(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, FtgpEnv** out)
+// ftgp_create / ftgp_create_tracks after the checks: device probe, plan, upload, reset
+int create(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, const Switches& sw, FtgpEnv** out)
 {
     if (int rc = open_device(cfg.device_id)) return rc;
-    // FTGP_WAIT_SPIN=1: the host waits for a launch by spinning instead of blocking on the interrupt (hipDeviceScheduleSpin: a CPU core per
-    // waiting handle for a shorter wake-up; measured: tools/launch_host.sh).  Best effort: a device that is already active keeps its flags.
-    if (const char* sv = getenv("FTGP_WAIT_SPIN")) { if (atoi(sv) == 1) (void)hipSetDeviceFlags(hipDeviceScheduleSpin); (void)hipGetLastError(); }
     hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, cfg.device_id));
     const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     Plan pl;
-    if (n_tracks > 1) { if (int rc = plan_tracks(cfg, tracks, envs_per_track, n_tracks, n_cu, pl)) return rc; }
-    else {
-        FtgpConfig c0 = cfg;
-        c0.track = tracks[0];
-        if (int rc = plan_create(c0, n_cu, pl)) return rc;
-    }
+    if (int rc = plan(cfg, tracks, envs_per_track, n_tracks, n_cu, sw, pl)) return rc;
     std::unique_ptr<FtgpEnv, int (*)(FtgpEnv*)> e(new FtgpEnv(), ftgp_destroy);
-    e->device = cfg.device_id; e->multi = cfg.cars_per_env > 1; e->ext_launch = !getenv("FTGP_LAUNCH_PLAIN");
+    e->device = cfg.device_id; e->multi = cfg.cars_per_env > 1; e->ext_launch = !sw.launch_plain;
     HIP_TRY(make_stream(e->stream)); HIP_TRY(make_stream(e->side));
     HIP_TRY(make_event(e->ev_start, hipEventDefault)); HIP_TRY(make_event(e->ev_stop[0], hipEventDefault)); HIP_TRY(make_event(e->ev_stop[1], hipEventDefault));
     HIP_TRY(make_event(e->ev_metrics, hipEventDisableTiming)); HIP_TRY(make_event(e->ev_gather, hipEventDisableTiming));
     for (const auto& set : kStepKernels) for (const auto& row : set) for (const StepKernel& k : row) HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (int rc = upload(e.get(), tracks, pl)) return rc;
+    if (int rc = upload(e.get(), pl, sw)) return rc;
     if (int rc = ftgp_reset(e.get(), nullptr)) return rc;
     *out = e.release();
     return 0;
@@ -1088,14 +1123,16 @@ int ftgp_create(const FtgpConfig* cfg, FtgpEnv** out)
 {
     if (!cfg || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     *out = nullptr;
-    if (int rc = validate(*cfg, &cfg->track, 1, false)) return rc;
-    return create(*cfg, &cfg->track, nullptr, 1, out);
+    const Switches sw = read_switches();
+    if (int rc = validate(*cfg, &cfg->track, 1, false, sw)) return rc;
+    return create(*cfg, &cfg->track, &cfg->n_envs, 1, sw, out);
 }
 
 int ftgp_create_tracks(const FtgpConfig* cfg, const FtgpTrack* tracks, const int32_t* envs_per_track, int n_tracks, FtgpEnv** out)
 {
     if (!cfg || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     *out = nullptr;
+    const Switches sw = read_switches();
     if (n_tracks < 1 || n_tracks > FTGP_MAX_TRACKS) return failf(FTGP_ERR_ARG, "ftgp_create_tracks: n_tracks = %d, not in 1 .. %d", n_tracks, FTGP_MAX_TRACKS);
     if (!tracks || !envs_per_track) return fail(FTGP_ERR_ARG, "ftgp_create_tracks: null tracks / envs_per_track%s");
     long long sum = 0;
@@ -1104,8 +1141,8 @@ int ftgp_create_tracks(const FtgpConfig* cfg, const FtgpTrack* tracks, const int
         sum += envs_per_track[k];
     }
     if (sum != cfg->n_envs) return failf(FTGP_ERR_ARG, "ftgp_create_tracks: envs_per_track sums to %lld, n_envs is %d", sum, cfg->n_envs);
-    if (int rc = validate(*cfg, tracks, n_tracks, true)) return rc;
-    return create(*cfg, tracks, envs_per_track, n_tracks, out);
+    if (int rc = validate(*cfg, tracks, n_tracks, true, sw)) return rc;
+    return create(*cfg, tracks, envs_per_track, n_tracks, sw, out);
 }
 
 int ftgp_reset(FtgpEnv* e, const uint8_t* mask)
@@ -1165,8 +1202,8 @@ int ftgp_set_car_policies(FtgpEnv* e, const int32_t* policies)
     for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->P.car_policy[c] = policies[c % e->P.cars_per_env];
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the blocks while they change
-    for (size_t b : e->blocks)        // every track's parameter block
-        HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(e->d_params.get()) + b + offsetof(DeviceParams, car_policy), e->P.car_policy, sizeof e->P.car_policy, hipMemcpyHostToDevice));
+    for (const TrackBufs& t : e->trk)     // every track's parameter block
+        HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(e->d_params.get()) + t.block + offsetof(DeviceParams, car_policy), e->P.car_policy, sizeof e->P.car_policy, hipMemcpyHostToDevice));
     if (e->h_tables) memcpy(e->h_tables.get(), e->P.car_policy, sizeof e->P.car_policy);    // (no copy from it is pending: the stream is idle)
     e->table_on_device = 0;
     return 0;

@@ -25,7 +25,9 @@ def test_multi_track_plan_holds_what_the_step_kernel_relies_on(plan_tracks_check
     """Each track's parameter block, tables and spawn table are those of a one-track plan of that track over the whole batch; every car
     sits in exactly one workgroup; a workgroup's envs share its track; each block has its own workgroups (a ragged last one); both orders
     cover the same (track, workgroup) set; the XCD order gives each track one run of residues b % 8, in track order, in proportion to
-    its workgroups."""
+    its workgroups.  The two device images laid out from made-up addresses: every workgroup-table entry carries its track's block offset,
+    the block found there has that track's size and buffers, task_tab points at the task tables behind the workgroup table, stage image k
+    holds block k's head, the vehicle, track k's centre-line, the fan and both cover tables; a one-track plan's image has no table."""
     r = plan_tracks_check
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr
     m = re.search(r"plan_tracks_check: (\d+) configs, (\d+) rejected, 0 failures", r.stdout)

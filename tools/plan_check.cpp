@@ -1,9 +1,11 @@
-// Host harness: runs ftgp_create's plan (plan_create: the workgroup shape, the fan, the sweep's task order and task tables) on the CPU, without a
+// Host harness: runs ftgp_create's plan (plan() with one track: the workgroup shape, the fan, the sweep's task order and task tables) on the CPU, without a
 // device, over a matrix of configurations, and checks what the step kernel relies on.
 // Build: hipcc --offload-arch=gfx950 -O2 -ffp-contract=off -std=c++17 -x hip tools/plan_check.cpp -o /tmp/plan_check -ldl
 #include "../ft_grandprix_amd/csrc/ftgp_api.hip"
+#include "plan_digest.h"
 
 static long g_fail = 0;
+static Fnv g_digest;
 #define CHECK(cond, ...) do { if (!(cond)) { ++g_fail; printf("FAIL %s: ", label); printf(__VA_ARGS__); printf("\n"); } } while (0)
 
 // the binary32 fan is point-symmetric to the bit: ray j + n/2 is the negated ray j (both components, sign bits included)
@@ -21,11 +23,11 @@ static bool point_symmetric(const std::vector<float>& ray, int R)
 }
 
 // one configuration; returns 1 when the plan rejected it
-static int check(const FtgpConfig& cfg, const char* label)
+static int check(const FtgpConfig& cfg, const Switches& sw, const char* label)
 {
     Plan pl;
-    const int rc = plan_create(cfg, 256, pl);
-    const DeviceParams& P = pl.P;
+    const int rc = plan(cfg, &cfg.track, &cfg.n_envs, 1, 256, sw, pl);
+    const DeviceParams& P = pl.tracks[0].P;
     const int R = cfg.n_rays, cpe = cfg.cars_per_env;
     if (rc != 0) {
         // only a shape that does not fit: one env of the configuration over the 160 KiB of LDS
@@ -46,7 +48,7 @@ static int check(const FtgpConfig& cfg, const char* label)
     const int sectors = cars >= 8192 ? 8 : cars >= 2048 ? 16 : 64;
     CHECK(P.n_sectors == sectors && P.n_planes == sectors, "%d sectors / %d planes for %ld cars (want %d)", P.n_sectors, P.n_planes, cars, sectors);
     // opposite-group pairs exactly when the fan allows them
-    const bool pairs_expected = R % 2 == 0 && point_symmetric(pl.ray, R) && !getenv("FTGP_NO_PAIRS");
+    const bool pairs_expected = R % 2 == 0 && point_symmetric(pl.ray, R) && !sw.no_pairs;
     // (a pair split at the tail leaves two single groups, the second starting at first + n/2: off the single groups' multiples of 64 unless n/2 is one)
     bool pairs = false;
     for (int k = 0; k < P.tasks_per_car; ++k) pairs = pairs || (P.group_order[k] >> 16) != 0 || (P.group_order[k] & 0xffff) % FTGP_WAVE != 0;
@@ -98,6 +100,9 @@ static int check(const FtgpConfig& cfg, const char* label)
         for (size_t i = 0; i < drawn.size(); ++i) bad += drawn[i] != times[i % R];
         CHECK(bad == 0, "table %d: %ld (car slot, ray) not drawn exactly once (or twice where counted above)", table, bad);
     }
+    Images im;
+    layout_images(pl, made_up_addrs(pl), im);
+    digest_plan(g_digest, pl, im);
     printf("%s: ok, %d x %d waves, %d B of LDS, %d sectors, %d tasks per car%s, %ld rays drawn twice\n", label, cpb, P.waves_per_block, P.lds_bytes, P.n_sectors,
            P.tasks_per_car, pairs ? " (pairs)" : "", twice);
     return 0;
@@ -136,14 +141,14 @@ int main()
                                 if (fan_kind == 1 && R % 2 == 0 && j >= R / 2) { fan[2 * j] = -fan[2 * (j - R / 2)]; fan[2 * j + 1] = -fan[2 * (j - R / 2) + 1]; }
                             }
                             if (fan_kind) cfg.fan_dirs = fan.data();
-                            if (no_pairs) setenv("FTGP_NO_PAIRS", "1", 1); else unsetenv("FTGP_NO_PAIRS");
+                            Switches sw;
+                            sw.no_pairs = no_pairs != 0;
                             char label[160];
                             snprintf(label, sizeof label, "rays %d cars_per_env %d envs %d fan %d mode %d no_pairs %d", R, cpe, n_envs, fan_kind, mode, no_pairs);
-                            if (validate(cfg) != 0) { ++g_fail; printf("FAIL %s: validate: %s\n", label, ftgp_last_error()); continue; }
+                            if (validate(cfg, &cfg.track, 1, false, sw) != 0) { ++g_fail; printf("FAIL %s: validate: %s\n", label, ftgp_last_error()); continue; }
                             ++configs;
-                            rejected += check(cfg, label);
+                            rejected += check(cfg, sw, label);
                         }
-    unsetenv("FTGP_NO_PAIRS");
     {   // above 16384 rays: rejected before the shape
         FtgpConfig cfg{};
         cfg.n_envs = 1; cfg.cars_per_env = 1; cfg.n_rays = 16385; cfg.dt = 0.01;
@@ -151,11 +156,12 @@ int main()
         cfg.track.width = W; cfg.track.height = H; cfg.track.words_per_row = wpr; cfg.track.bits = bits.data(); cfg.track.path = path.data();
         cfg.track.px_size_x = cfg.track.px_size_y = 0.05;
         Plan pl;
-        const int rc = plan_create(cfg, 256, pl);
+        const int rc = plan(cfg, &cfg.track, &cfg.n_envs, 1, 256, Switches(), pl);
         printf("rays 16385: rejected (%d): %s\n", rc, ftgp_last_error());
         const char* label = "rays 16385";
         CHECK(rc == FTGP_ERR_ARG && strcmp(ftgp_last_error(), "n_rays above 16384 is not supported") == 0, "rc %d", rc);
     }
+    printf("digest=%016llx\n", (unsigned long long)g_digest.h);
     printf("plan_check: %ld configs, %ld rejected, %ld failures\n", configs, rejected, g_fail);
     return g_fail ? 1 : 0;
 }

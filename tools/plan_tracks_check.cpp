@@ -1,13 +1,16 @@
-// Host harness: runs ftgp_create_tracks' plan (plan_tracks: the batch's plan, every track's parameter block and tables, the workgroup
-// table) on the CPU, without a device, over synthetic track sets, ragged env counts, 1 / 3 / 8 cars per env and 90 / 1080 rays, in both
-// workgroup orders, and checks what the multi-track step kernel relies on.
+// Host harness: runs ftgp_create_tracks' plan (plan(): the batch's plan, every track's parameter block and tables, the workgroup table)
+// and the layout of the two device images (layout_images, from made-up addresses) on the CPU, without a device, over synthetic track
+// sets, ragged env counts, 1 / 3 / 8 cars per env and 90 / 1080 rays, in both workgroup orders, and checks what the multi-track step
+// kernel relies on.
 // Build: hipcc --offload-arch=gfx950 -O2 -ffp-contract=off -std=c++17 -x hip tools/plan_tracks_check.cpp -o /tmp/plan_tracks_check -ldl
 #include "../ft_grandprix_amd/csrc/ftgp_api.hip"
+#include "plan_digest.h"
 
 #include <set>
 #include <tuple>
 
 static long g_fail = 0;
+static Fnv g_digest;
 #define CHECK(cond, ...) do { if (!(cond)) { ++g_fail; printf("FAIL %s: ", label); printf(__VA_ARGS__); printf("\n"); } } while (0)
 
 // a W x H image walled at its border with a block in the middle, a centre-line on an ellipse
@@ -36,12 +39,57 @@ struct SynthTrack {
 
 using Entry = std::tuple<int, int, int>;       // (track, first car, cars)
 
-static std::vector<int32_t> plan_in(const char* order, const FtgpConfig& cfg, const std::vector<FtgpTrack>& tr, const std::vector<int32_t>& counts, Plan& pl, int& rc)
+static std::vector<int32_t> plan_in(int order, const FtgpConfig& cfg, const std::vector<FtgpTrack>& tr, const std::vector<int32_t>& counts, Plan& pl, int& rc)
 {
-    setenv("FTGP_TRACK_ORDER", order, 1);
-    rc = plan_tracks(cfg, tr.data(), counts.data(), (int)tr.size(), 256, pl);
-    unsetenv("FTGP_TRACK_ORDER");
+    Switches sw;
+    sw.track_order = order;
+    rc = plan(cfg, tr.data(), counts.data(), (int)tr.size(), 256, sw, pl);
     return pl.wg;
+}
+
+// The two device images of a plan, laid out from made-up addresses: what the step kernel finds behind the workgroup table, task_tab and
+// stage_img.  one: the plan has one track (no workgroup table in the image).
+static void check_layout(const Plan& pl, const Images& im, const DeviceAddrs& a, bool one, const char* label)
+{
+    const int T = (int)pl.tracks.size();
+    const DeviceParams& P = pl.tracks[0].P;
+    const size_t head = FTGP_PARAMS_BYTES, wg_bytes = one ? 0 : sizeof(int32_t) * pl.wg.size(), tasks_bytes = sizeof(int32_t) * pl.tasks.size();
+    const size_t stage_bytes = (size_t)(P.off_cars - P.off_params) + 2 * (size_t)P.stage_cover, stride = (size_t)P.cover_kmax + 1;
+    CHECK(im.blocks.size() == (size_t)T && im.blocks[0] == 0, "block offsets: %zu of them, the first at %zu", im.blocks.size(), im.blocks.empty() ? (size_t)0 : im.blocks[0]);
+    CHECK(im.params.size() == head + wg_bytes + tasks_bytes + (size_t)(T - 1) * head + 16 && im.stage.size() == stage_bytes * T, "image sizes %zu / %zu", im.params.size(), im.stage.size());
+    CHECK(memcmp(&im.P0, im.params.data(), sizeof im.P0) == 0, "track 0's finished block is not the head of the image");
+    CHECK(memcmp(im.params.data() + head + wg_bytes, pl.tasks.data(), tasks_bytes) == 0, "the task tables do not sit behind %s", one ? "the block" : "the workgroup table");
+    if (one) CHECK(im.blocks == std::vector<size_t>{ 0 }, "one track: block offsets");
+    else
+        for (size_t b = 0; b < pl.wg.size(); b += 4) {       // the workgroup table: the plan's, each entry with its track's block offset
+            int32_t w[4];
+            memcpy(w, im.params.data() + head + sizeof(int32_t) * b, sizeof w);
+            CHECK(w[1] == pl.wg[b + 1] && w[2] == pl.wg[b + 2] && w[3] == pl.wg[b + 3], "workgroup %zu: the image's entry is not the plan's", b / 4);
+            CHECK(w[3] >= 0 && w[3] < T && (size_t)w[0] == im.blocks[(size_t)w[3]], "workgroup %zu: block offset %d of track %d", b / 4, w[0], w[3]);
+        }
+    for (int k = 0; k < T; ++k) {
+        const Plan::Track& t = pl.tracks[(size_t)k];
+        const size_t off = im.blocks[(size_t)k];
+        CHECK(off % 16 == 0 && off + sizeof(DeviceParams) <= im.params.size() && (k == 0 || off >= head + wg_bytes + tasks_bytes), "track %d: block at %zu", k, off);
+        if (off + sizeof(DeviceParams) > im.params.size()) continue;
+        DeviceParams Q;
+        memcpy(&Q, im.params.data() + off, sizeof Q);
+        CHECK(Q.width == t.P.width && Q.height == t.P.height && Q.px_size_x == t.P.px_size_x && Q.plane256 == t.P.plane256, "track %d: the block at its offset is another track's", k);
+        CHECK(Q.field == a.trk[(size_t)k].field && Q.edt == a.trk[(size_t)k].edt && Q.bits == a.trk[(size_t)k].bits && Q.nearbits == a.trk[(size_t)k].nearbits, "track %d: field / edt / bits / nearbits", k);
+        CHECK(Q.path == a.path + 2 * FTGP_PATH_POINTS * (size_t)k && Q.spawn == a.spawn + 4 * FTGP_PATH_POINTS * (size_t)k, "track %d: path / spawn are not the shared buffers plus the track's stride", k);
+        CHECK(Q.fan_dirs == a.fan && Q.veh_dev == a.veh && Q.ray_dir == a.ray && Q.cover_thr == a.cover && Q.cars == a.cars && Q.ranges == a.ranges && Q.steps == a.steps, "track %d: shared buffers", k);
+        CHECK(Q.wg_metrics == a.wg_metrics && Q.wg_ticket == a.wg_ticket && Q.metrics_dev == a.metrics_dev && Q.metrics_host == a.metrics_host && Q.wg_metrics_host == a.wg_metrics_host, "track %d: metrics buffers", k);
+        CHECK((const unsigned char*)Q.task_tab == a.params + head + wg_bytes, "track %d: task_tab", k);
+        CHECK(Q.stage_img == a.stage + stage_bytes * k, "track %d: stage_img", k);
+        // the staging image: head of the block | vehicle | centre-line | fan | cover tables of nidc and of fast
+        const unsigned char* s = im.stage.data() + stage_bytes * k;
+        CHECK(memcmp(s, &Q, offsetof(DeviceParams, veh)) == 0, "track %d: the stage image does not start with the head of the block", k);
+        CHECK(memcmp(s + (P.off_veh - P.off_params), pl.veh.data(), pl.veh.size()) == 0, "track %d: staged vehicle image", k);
+        CHECK(memcmp(s + (P.off_path - P.off_params), t.path.data(), sizeof(double) * t.path.size()) == 0 && t.path.size() == 2 * FTGP_PATH_POINTS, "track %d: staged centre-line", k);
+        CHECK(memcmp(s + (P.off_ray - P.off_params), pl.ray.data(), sizeof(float) * pl.ray.size()) == 0, "track %d: staged fan", k);
+        CHECK(memcmp(s + (P.off_cars - P.off_params), pl.cover.data(), sizeof(float) * stride) == 0, "track %d: staged cover table of nidc", k);
+        CHECK(memcmp(s + (P.off_cars - P.off_params) + P.stage_cover, pl.cover.data() + stride, sizeof(float) * stride) == 0, "track %d: staged cover table of fast", k);
+    }
 }
 
 // one configuration; returns 1 when the plan rejected it
@@ -49,22 +97,27 @@ static int check(const FtgpConfig& cfg, const std::vector<FtgpTrack>& tr, const 
 {
     const int T = (int)tr.size(), cpe = cfg.cars_per_env, n_cars = cfg.n_envs * cpe;
     Plan pb, px; int rcb = 0, rcx = 0;
-    const std::vector<int32_t> wb = plan_in("blocks", cfg, tr, counts, pb, rcb), wx = plan_in("xcd", cfg, tr, counts, px, rcx);
+    const std::vector<int32_t> wb = plan_in(kOrderBlocks, cfg, tr, counts, pb, rcb), wx = plan_in(kOrderXcd, cfg, tr, counts, px, rcx);
     CHECK(rcb == rcx, "the orders disagree on the plan (%d / %d)", rcb, rcx);
     if (rcb) { printf("%s: rejected (%d): %s\n", label, rcb, ftgp_last_error()); return 1; }
-    const int cpb = pb.P.cars_per_block;
+    const int cpb = pb.tracks[0].P.cars_per_block;
     // each track's block and tables are those of a one-track plan of that track over the whole batch (same shape, sectors and fan)
     for (int t = 0; t < T; ++t) {
-        FtgpConfig c1 = cfg; c1.track = tr[(size_t)t];
         Plan one;
-        CHECK(plan_create(c1, 256, one) == 0, "one-track plan of track %d failed: %s", t, ftgp_last_error());
-        const Plan::Track* k = t ? &pb.more[(size_t)t - 1] : nullptr;
-        const DeviceParams& Q = k ? k->P : pb.P;
-        CHECK(memcmp(&Q, &one.P, sizeof Q) == 0, "track %d: the parameter block differs from its one-track plan's", t);
-        const HostTables& tab = k ? k->tab : pb.tab;
-        CHECK(tab.bits == one.tab.bits && tab.nearbits == one.tab.nearbits && tab.runx == one.tab.runx && tab.runy == one.tab.runy, "track %d: tables differ", t);
-        CHECK((k ? k->spawn : pb.spawn) == one.spawn, "track %d: spawn table differs", t);
+        CHECK(plan(cfg, &tr[(size_t)t], &cfg.n_envs, 1, 256, Switches(), one) == 0, "one-track plan of track %d failed: %s", t, ftgp_last_error());
+        if (one.tracks.size() != 1) continue;
+        const Plan::Track& k = pb.tracks[(size_t)t], & k1 = one.tracks[0];
+        CHECK(memcmp(&k.P, &k1.P, sizeof k.P) == 0, "track %d: the parameter block differs from its one-track plan's", t);
+        CHECK(k.tab.bits == k1.tab.bits && k.tab.nearbits == k1.tab.nearbits && k.tab.runx == k1.tab.runx && k.tab.runy == k1.tab.runy, "track %d: tables differ", t);
+        CHECK(k.spawn == k1.spawn && k.path == k1.path, "track %d: spawn table or centre-line differs", t);
         CHECK(one.tasks == pb.tasks && one.ray == pb.ray, "track %d: the task tables or the fan differ", t);
+        CHECK(one.n_wg == (cfg.n_envs * cpe + cpb - 1) / cpb, "track %d: %d workgroups in its one-track plan", t, one.n_wg);
+        if (t == 0) {       // a one-track handle's images: the block, then the task tables
+            const DeviceAddrs a = made_up_addrs(one);
+            Images im;
+            layout_images(one, a, im);
+            check_layout(one, im, a, true, label);
+        }
     }
     // env -> track
     std::vector<int> env_track(cfg.n_envs, -1);
@@ -113,6 +166,13 @@ static int check(const FtgpConfig& cfg, const std::vector<FtgpTrack>& tr, const 
             if (t) CHECK(lo[(size_t)t] >= hi[(size_t)t - 1], "xcd order: track %d's residues start before track %d's end", t, t - 1);
         }
     }
+    for (const Plan* pl : { &pb, &px }) {
+        const DeviceAddrs a = made_up_addrs(*pl);
+        Images im;
+        layout_images(*pl, a, im);
+        check_layout(*pl, im, a, false, label);
+        digest_plan(g_digest, *pl, im);
+    }
     printf("%s: ok, %d cars per workgroup, %d workgroups\n", label, cpb, nwg[0]);
     return 0;
 }
@@ -148,6 +208,7 @@ int main()
                         rejected += check(cfg, tr, counts, label);
                     }
     }
+    printf("digest=%016llx\n", (unsigned long long)g_digest.h);
     printf("plan_tracks_check: %d configs, %d rejected, %ld failures\n", n, rejected, g_fail);
     return g_fail ? 1 : 0;
 }
