@@ -23,6 +23,7 @@ POSE_DOUBLES = 13
 PROGRESS_INTS = 10
 METRIC_DOUBLES = 8
 STATE_FLOATS = 8            # FTGP_STATE_FLOATS: a state row of the device step (STATE_FIELDS)
+CONTACT_FLOATS = 4          # FTGP_CONTACT_FLOATS: a contact row (CONTACT_FIELDS)
 MAX_TRACKS = 16             # FTGP_MAX_TRACKS: tracks of one multi-track handle (ftgp_create_tracks)
 
 POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2, 3, 4
@@ -35,6 +36,7 @@ POLICY_BY_NAME = {"host": POLICY_HOST, "lobotomy": POLICY_LOBOTOMY, "nidc": POLI
 PROGRESS_FIELDS = ("laps", "completion", "lap_completion", "absolute_completion", "finished",
                    "off_track", "start", "good_start", "delta", "finish_step")
 STATE_FIELDS = ("v_long", "v_lat", "wz", "u_speed", "u_steer", "centre_dist", "lap_completion", "off_track")
+CONTACT_FIELDS = ("wall_pen", "car_pen", "wall_count", "car_count")
 METRIC_FIELDS = ("steps", "n_cars", "sum_laps", "sum_absolute_completion", "n_finished",
                  "n_off_track", "min_lap_time", "max_lap_time")
 
@@ -81,6 +83,7 @@ API_SYMBOLS = (
     "last_kernel_ms", "kernel_name", "fakelidar", "selftest", "build_info", "get_race_steps",
     "device_io_config", "step_device", "create_tracks", "get_track_distance_field",
     "device_io_signals", "step_device_ex", "state_device", "get_centre_dist2",
+    "device_io_contacts", "step_device_contacts", "contacts_device", "get_contacts",
 )
 
 
@@ -100,6 +103,15 @@ class FtgpDeviceSignals(C.Structure):
 
 class FtgpDeviceStepExtra(C.Structure):
     _fields_ = [("state", C.c_void_p), ("final_state", C.c_void_p)]
+
+
+class FtgpDeviceContacts(C.Structure):
+    _fields_ = [("terminate_on_wall", C.c_int32), ("terminate_on_car", C.c_int32), ("wall_penalty", C.c_float),
+                ("car_penalty", C.c_float)]
+
+
+class FtgpDeviceStepContacts(C.Structure):
+    _fields_ = [("contact", C.c_void_p), ("final_contact", C.c_void_p)]
 
 
 class FtgpError(RuntimeError):
@@ -174,6 +186,10 @@ class CLib:
             "step_device_ex": (i32, [vp, C.POINTER(FtgpDeviceStep), C.POINTER(FtgpDeviceStepExtra)]),
             "state_device": (i32, [vp, vp, vp]),
             "get_centre_dist2": (i32, [vp, dp]),
+            "device_io_contacts": (i32, [vp, C.POINTER(FtgpDeviceContacts)]),
+            "step_device_contacts": (i32, [vp, C.POINTER(FtgpDeviceStep), C.POINTER(FtgpDeviceStepExtra), C.POINTER(FtgpDeviceStepContacts)]),
+            "contacts_device": (i32, [vp, vp, vp]),
+            "get_contacts": (i32, [vp, dp]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -377,13 +393,27 @@ class Env:
         s = FtgpDeviceSignals(int(scan_pool), float(scan_max_range), int(bool(terminate_off_track)), float(off_track_penalty))
         self._call("device_io_signals", C.byref(s))
 
+    def device_io_contacts(self, on: bool = True, terminate_on_wall: bool = False, terminate_on_car: bool = False,
+                           wall_penalty: float = 0.0, car_penalty: float = 0.0):
+        """ftgp_device_io_contacts (after ``device_io_config``, which turns contacts off): contact rows, contact episode ends and
+        penalties in every device step; ``on=False`` turns them off again."""
+        if not on:
+            self._call("device_io_contacts", None)
+            return
+        c = FtgpDeviceContacts(int(bool(terminate_on_wall)), int(bool(terminate_on_car)), float(wall_penalty), float(car_penalty))
+        self._call("device_io_contacts", C.byref(c))
+
     def step_device(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0,
-                    state: int = 0, final_state: int = 0):
+                    state: int = 0, final_state: int = 0, contact: int = 0, final_contact: int = 0):
         """One ftgp_step_device call on integer device addresses (and an integer hipStream_t, 0 = the null stream); only enqueues.
-        With ``state`` or ``final_state``: ftgp_step_device_ex."""
+        With ``state`` or ``final_state``: ftgp_step_device_ex; with ``contact`` or ``final_contact``: ftgp_step_device_contacts."""
         io = FtgpDeviceStep(stream or None, action or None, obs or None, reward or None, terminated or None, truncated or None,
                             final_obs or None)
-        if state or final_state:
+        if contact or final_contact:
+            extra = FtgpDeviceStepExtra(state or None, final_state or None) if state or final_state else None
+            con = FtgpDeviceStepContacts(contact or None, final_contact or None)
+            self._call("step_device_contacts", C.byref(io), None if extra is None else C.byref(extra), C.byref(con))
+        elif state or final_state:
             extra = FtgpDeviceStepExtra(state or None, final_state or None)
             self._call("step_device_ex", C.byref(io), C.byref(extra))
         else:
@@ -393,7 +423,18 @@ class Env:
         """ftgp_state_device: the state rows of the current state into device memory at ``state``, ordered on ``stream``; only enqueues."""
         self._call("state_device", stream or None, state or None)
 
+    def contacts_device(self, contact: int, stream: int = 0):
+        """ftgp_contacts_device: the external cars' contact rows at the current state into device memory at ``contact``, ordered on
+        ``stream``; only enqueues."""
+        self._call("contacts_device", stream or None, contact or None)
+
     # -- read-backs
+    def contacts(self) -> np.ndarray:
+        """float32 [n_cars, 4] (CONTACT_FIELDS): the contact row of every car at the current state (ftgp_get_contacts)."""
+        out = np.empty((self.n_cars, CONTACT_FLOATS), dtype=np.float32)
+        self._call("get_contacts", _ptr(out))
+        return out
+
     def lidar(self) -> np.ndarray:
         out = np.empty((self.n_cars, self.n_rays), dtype=np.float32)
         self._call("get_lidar", _ptr(out))

@@ -164,6 +164,9 @@ struct FtgpEnv {
     Event ev_io_in, ev_io_out;
     DeviceSignalArgs sig{};           // ftgp_device_io_signals (the buffers and what depends on them are filled in per call)
     bool sig_default = true;          // the defaults: a call without state buffers launches ftgp_io_finish_kernel
+    bool con_on = false;              // ftgp_device_io_contacts: a call evaluates the contact rows and goes through ftgp_io_finish_signals_kernel
+    FtgpDeviceContacts con{};         // the contact rules while con_on
+    DevBuf<float> d_contact;          // [n_cars][FTGP_CONTACT_FLOATS] every car's contact row, allocated on first use
     struct Checked { const void* p; size_t bytes; };
     Checked io_checked[32] = {};      // device buffers found valid (hipPointerGetAttributes), replaced round robin
     int io_checked_next = 0;
@@ -916,6 +919,28 @@ void set_signals(FtgpEnv* e, const FtgpDeviceSignals& s)
     e->sig_default = s.scan_pool == 1 && !S.clip && !S.terminate_off_track && s.off_track_penalty == 0.0f;
 }
 
+// ftgp_io_contact_kernel on the handle's stream: every car's row to `rows` and / or the external cars' rows to `ext_out`
+int launch_contacts(FtgpEnv* e, float* rows, float* ext_out)
+{
+    DeviceContactArgs C{};
+    C.blocks = reinterpret_cast<const unsigned char*>(e->d_params.get());
+    C.env_track = e->d_env_track.get();
+    C.rows = rows; C.ext_out = ext_out;
+    C.n_ext = e->io.n_ext;
+    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) C.ext_index[k] = e->io_ready ? e->io.ext_index[k] : -1;
+    for (size_t k = 0; k < e->trk.size() && k < FTGP_MAX_TRACKS; ++k) C.block_off[k] = (uint32_t)e->trk[k].block;
+    const unsigned blocks = (unsigned)(((size_t)e->P.n_cars * FTGP_CONTACT_LANES + FTGP_CONTACT_THREADS - 1) / FTGP_CONTACT_THREADS);
+    hipLaunchKernelGGL(ftgp_io_contact_kernel, dim3(blocks), dim3(FTGP_CONTACT_THREADS), 0, e->stream.get(), e->P, C);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ensure_contact_rows(FtgpEnv* e)
+{
+    if (!e->d_contact) HIP_TRY(dev_alloc(e->d_contact, sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_cars));
+    return 0;
+}
+
 // ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images
 int upload(FtgpEnv* e, const Plan& pl, const Switches& sw)
 {
@@ -1246,6 +1271,21 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
     e->io_repeat = cfg->action_repeat;
     e->io_ready = true;
     set_signals(e, FtgpDeviceSignals{ 1, 0.0f, 0, 0.0f });
+    e->con_on = false;
+    return 0;
+}
+
+int ftgp_device_io_contacts(FtgpEnv* e, const FtgpDeviceContacts* contacts)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_contacts before ftgp_device_io_config%s");
+    if (!contacts) { e->con_on = false; return 0; }
+    if (!(contacts->wall_penalty >= 0.0f) || std::isinf(contacts->wall_penalty)) return fail(FTGP_ERR_ARG, "device_io_contacts: wall_penalty >= 0 and finite%s");
+    if (!(contacts->car_penalty >= 0.0f) || std::isinf(contacts->car_penalty)) return fail(FTGP_ERR_ARG, "device_io_contacts: car_penalty >= 0 and finite%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = ensure_contact_rows(e)) return rc;
+    e->con = *contacts;
+    e->con_on = true;
     return 0;
 }
 
@@ -1263,15 +1303,20 @@ int ftgp_device_io_signals(FtgpEnv* e, const FtgpDeviceSignals* signals)
 
 int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io) { return ftgp_step_device_ex(e, io, nullptr); }
 
-int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra)
+int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra) { return ftgp_step_device_contacts(e, io, extra, nullptr); }
+
+int ftgp_step_device_contacts(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts)
 {
     if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
     if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
+    float* contact = contacts ? contacts->contact : nullptr;
+    float* final_contact = contacts ? contacts->final_contact : nullptr;
+    if ((contact || final_contact) && !e->con_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_contacts: contact buffers while contacts are off (ftgp_device_io_contacts)%s");
     HIP_TRY(hipSetDevice(e->device));
     DeviceIoArgs A = e->io;
     DeviceSignalArgs S = e->sig;
     S.state = extra ? extra->state : nullptr; S.final_state = extra ? extra->final_state : nullptr;
-    const bool signals = !e->sig_default || S.state || S.final_state;
+    const bool signals = !e->sig_default || S.state || S.final_state || e->con_on;
     const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
     if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
     if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
@@ -1281,6 +1326,13 @@ int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceSt
     if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
     if (S.state) if (int rc = check_device_buffer(e, S.state, sizeof(float) * FTGP_STATE_FLOATS * rows, "state")) return rc;
     if (S.final_state) if (int rc = check_device_buffer(e, S.final_state, sizeof(float) * FTGP_STATE_FLOATS * rows, "final_state")) return rc;
+    if (contact) if (int rc = check_device_buffer(e, contact, sizeof(float) * FTGP_CONTACT_FLOATS * rows, "contact")) return rc;
+    if (final_contact) if (int rc = check_device_buffer(e, final_contact, sizeof(float) * FTGP_CONTACT_FLOATS * rows, "final_contact")) return rc;
+    if (e->con_on) {
+        S.contact_rows = e->d_contact.get(); S.contact = contact; S.final_contact = final_contact;
+        S.terminate_on_wall = e->con.terminate_on_wall ? 1 : 0; S.terminate_on_car = e->con.terminate_on_car ? 1 : 0;
+        S.wall_penalty = e->con.wall_penalty; S.car_penalty = e->con.car_penalty;
+    }
     A.action = io->action; A.obs = io->obs; A.reward = io->reward; A.terminated = io->terminated; A.truncated = io->truncated; A.final_obs = io->final_obs;
     A.vec4 = e->P.n_rays % 4 == 0 && (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
     hipStream_t caller = (hipStream_t)io->stream;
@@ -1290,6 +1342,7 @@ int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceSt
     hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
     if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, e->io_repeat, true)) return rc;
+    if (e->con_on) if (int rc = launch_contacts(e, e->d_contact.get(), nullptr)) return rc;
     if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A);
     else {
         const bool aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
@@ -1318,6 +1371,32 @@ int ftgp_state_device(FtgpEnv* e, void* stream, float* state)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
     HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
+    return 0;
+}
+
+int ftgp_contacts_device(FtgpEnv* e, void* stream, float* contact)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_contacts_device before ftgp_device_io_config%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = check_device_buffer(e, contact, sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_envs * (size_t)e->io.n_ext, "contact")) return rc;
+    hipStream_t caller = (hipStream_t)stream;
+    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
+    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
+    if (int rc = launch_contacts(e, nullptr, contact)) return rc;
+    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
+    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
+    return 0;
+}
+
+int ftgp_get_contacts(FtgpEnv* e, float* out)
+{
+    if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = ensure_contact_rows(e)) return rc;
+    if (int rc = launch_contacts(e, e->d_contact.get(), nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->d_contact.get(), sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
 

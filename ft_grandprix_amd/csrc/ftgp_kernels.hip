@@ -1897,7 +1897,8 @@ __global__ void ftgp_set_pose_kernel(DeviceParams P, const double* __restrict__ 
 
 // =============================================================================================
 // Device I/O (ftgp_step_device): the caller's actions in, observations / rewards / episode ends out, all in device memory.
-// A call is: ftgp_io_ingest_kernel -> ftgp_step_kernel<.., ROSTER> (action_repeat steps) -> ftgp_io_finish_kernel.
+// A call is: ftgp_io_ingest_kernel -> ftgp_step_kernel<.., ROSTER> (action_repeat steps) -> ftgp_io_finish_kernel; with contacts on,
+// ftgp_io_contact_kernel runs between the steps and the finish kernel.
 // =============================================================================================
 struct DeviceIoArgs {
     const float* action;          // [n_envs][n_ext][2] (speed, steering_angle)
@@ -2007,6 +2008,12 @@ struct DeviceSignalArgs {
     float limit;                  // what a ray without a hit counts as in the minimum: scan_max_range, +inf for raw ranges
     float inv_max_range;          // 1.0f / scan_max_range, divided once on the host
     float penalty;
+    // contacts (ftgp_device_io_contacts): filled in per call
+    const float* contact_rows;    // [n_cars][FTGP_CONTACT_FLOATS] this call's rows (ftgp_io_contact_kernel), null = contacts are off
+    float* contact;               // [n_envs][n_ext][FTGP_CONTACT_FLOATS] or null
+    float* final_contact;         // [n_envs][n_ext][FTGP_CONTACT_FLOATS] or null
+    int32_t terminate_on_wall, terminate_on_car;
+    float wall_penalty, car_penalty;
 };
 
 // a range as it enters the minimum: no hit (< 0) = the limit, a hit = min(r, limit)
@@ -2099,22 +2106,118 @@ __global__ void ftgp_io_state_kernel(DeviceParams P, DeviceIoArgs A, float* __re
     state_row(P.cars[ci], state + ((size_t)(ci / P.cars_per_env) * A.n_ext + k) * FTGP_STATE_FLOATS);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Contacts (ftgp_device_io_contacts / ftgp_step_device_contacts / ftgp_contacts_device / ftgp_get_contacts): the contact row of
+// include/ftgp.h, from the geometry K1's penalty forces use -- wall_search as K1 calls it, the circle pairs as car_contact_mate forms them.
+// ---------------------------------------------------------------------------------------------
+struct DeviceContactArgs {
+    const unsigned char* blocks;          // the handle's parameter blocks in device memory: track t's DeviceParams at block_off[t]
+    const int32_t* env_track;             // the track of every env; null with one track
+    float* rows;                          // [n_cars][FTGP_CONTACT_FLOATS]: every car's row, or null
+    float* ext_out;                       // [n_envs][n_ext][FTGP_CONTACT_FLOATS]: the external cars' rows, or null
+    int32_t n_ext, pad;
+    int32_t ext_index[FTGP_PAIR_STRIDE];  // as DeviceIoArgs (read with ext_out only)
+    uint32_t block_off[FTGP_MAX_TRACKS];
+};
+
+// Sixteen lanes per car, one DPP row: lanes 0..6 take one wall circle each (three chassis circles, the four softeners with bubble_wrap),
+// lanes 8..15 take car slot lane - 8 of the env as mate, all nine circle pairs.  Maxima and counts are folded inside each half of the row
+// with three shuffles, and lane 0 fetches the mates' half with a fourth.  No LDS, no atomics; a wave holds four cars, a workgroup sixteen.
+#define FTGP_CONTACT_LANES 16
+#define FTGP_CONTACT_THREADS 256
+__global__ void __launch_bounds__(FTGP_CONTACT_THREADS) ftgp_io_contact_kernel(DeviceParams P, DeviceContactArgs C)
+{
+    // (the car from the block's first car, not from a global lane number: that one would pass 2^31 at 134 M cars)
+    const int ci = blockIdx.x * (FTGP_CONTACT_THREADS / FTGP_CONTACT_LANES) + threadIdx.x / FTGP_CONTACT_LANES, l = threadIdx.x % FTGP_CONTACT_LANES;
+    const bool live = ci < P.n_cars;
+    const int cpe = P.cars_per_env;
+    const int env = live ? ci / cpe : 0, slot = live ? ci - env * cpe : 0;
+    double pen = 0.0;
+    int hit = 0;
+    if (live && !P.cars[ci].finished) {          // a finished car collides with nothing (custom.py:1452-1457)
+        const CarCore* me = P.cars + ci;
+        const FtgpVehicle& v = P.veh;
+        if (l < 8) {
+            if (l < (P.bubble_wrap ? 7 : 3)) {
+                const DeviceParams& Q = *reinterpret_cast<const DeviceParams*>(C.blocks + C.block_off[env_track_of(C.env_track, env)]);
+                const bool softener = l >= 3;
+                const int k = softener ? l - 3 : l;
+                const double qw = me->qw, qz = me->qz;
+                const double ch = 1.0 - 2.0 * (qz * qz), sh = 2.0 * (qw * qz);
+                const double rxw = softener ? ch * v.wheel_x[k] - sh * v.wheel_y[k] : ch * v.contact_x[k];
+                const double ryw = softener ? sh * v.wheel_x[k] + ch * v.wheel_y[k] : sh * v.contact_x[k];
+                const double px = me->x + rxw, py = me->y + ryw;
+                const WallHit h = wall_search(Q, Q.bits, Q.nearbits, px, py, softener ? v.softener_radius : v.contact_radius);
+                if (h.found) { pen = h.pen; hit = 1; }
+            }
+        } else {
+            const int k = l - 8;
+            const CarCore* b = P.cars + (ci - slot + (k < cpe ? k : slot));
+            if (k < cpe && k != slot && !b->finished) {
+                const double r2 = 2.0 * v.contact_radius;
+                const double qw = me->qw, qz = me->qz;
+                const double ch = 1.0 - 2.0 * (qz * qz), sh = 2.0 * (qw * qz);
+                const double bqw = b->qw, bqz = b->qz;
+                const double cb = 1.0 - 2.0 * (bqz * bqz), sb = 2.0 * (bqw * bqz);
+                #pragma unroll
+                for (int ij = 0; ij < 9; ++ij) {
+                    const int i = ij / 3, j = ij - 3 * i;
+                    const double rxw = ch * v.contact_x[i], ryw = sh * v.contact_x[i];
+                    const double sxw = cb * v.contact_x[j], syw = sb * v.contact_x[j];
+                    const double px = me->x + rxw, py = me->y + ryw;
+                    const double qx = b->x + sxw, qy = b->y + syw;
+                    const double ex = px - qx, ey = py - qy;
+                    const double d2 = ex * ex + ey * ey;
+                    if (d2 >= r2 * r2 || d2 <= 0.0) continue;
+                    const double overlap = r2 - sqrt(d2);
+                    if (!hit || overlap > pen) pen = overlap;
+                    hit = 1;
+                }
+            }
+        }
+    }
+    // every lane of the wave is here: the halves of a row fold on their own (xor 1, 2, 4 stay inside eight lanes)
+    for (int d = 1; d < 8; d <<= 1) {
+        const double o = shfl_xor_f64(pen, d);
+        pen = o > pen ? o : pen;
+        hit += __shfl_xor(hit, d, FTGP_WAVE);
+    }
+    const double car_pen = shfl_xor_f64(pen, 8);
+    const int car_hit = __shfl_xor(hit, 8, FTGP_WAVE);
+    if (!live || l != 0) return;
+    const float4 row = make_float4((float)pen, (float)car_pen, (float)hit, (float)car_hit);
+    if (C.rows) reinterpret_cast<float4*>(C.rows)[ci] = row;
+    if (C.ext_out) {
+        const int k = C.ext_index[slot];
+        if (k >= 0) {
+            float* o = C.ext_out + ((size_t)env * C.n_ext + k) * FTGP_CONTACT_FLOATS;
+            o[0] = row.x; o[1] = row.y; o[2] = row.z; o[3] = row.w;
+        }
+    }
+}
+
 // ftgp_io_finish_kernel with signals: one workgroup per env.  The rows of obs / final_obs are pooled (pooled_row); an external car that
 // is off_track pays the penalty and, with terminate_off_track, ends its env; state rows are written from the records after the steps
-// (to final_state for an env that is reset here) and again after the reset.
+// (to final_state for an env that is reset here) and again after the reset.  With contacts on (S.contact_rows, this call's rows of
+// ftgp_io_contact_kernel) the wall and car penalties and episode ends join, and the rows go out like the state rows -- zeros after a reset.
 __global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_signals_kernel(DeviceParams P, DeviceIoArgs A, DeviceSignalArgs S)
 {
     __shared__ int ended;
     __shared__ __attribute__((aligned(16))) float stage[FTGP_SIG_STAGE_FLOATS];
     const int env = blockIdx.x, cpe = P.cars_per_env, ci0 = env * cpe, t = threadIdx.x;
     if (t == 0) {
-        bool all_finished = true, off = false;
+        bool all_finished = true, off = false, wall = false, car = false;
         for (int c = 0; c < cpe; ++c)
             if (A.ext_index[c] >= 0) {
                 if (!P.cars[ci0 + c].finished) all_finished = false;
                 if (P.cars[ci0 + c].off_track) off = true;
+                if (S.contact_rows) {
+                    const float* cr = S.contact_rows + (size_t)(ci0 + c) * FTGP_CONTACT_FLOATS;
+                    if (cr[2] > 0.0f) wall = true;
+                    if (cr[3] > 0.0f) car = true;
+                }
             }
-        const bool term = all_finished || (S.terminate_off_track && off);
+        const bool term = all_finished || (S.terminate_off_track && off) || (S.terminate_on_wall && wall) || (S.terminate_on_car && car);
         const bool trunc = !term && A.max_episode_steps > 0 && P.steps[env] >= A.max_episode_steps;
         A.terminated[env] = term ? 1 : 0;
         A.truncated[env] = trunc ? 1 : 0;
@@ -2126,6 +2229,11 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_signals_kernel
         const CarCore& a = P.cars[ci0 + t];
         float r = (float)(absolute_completion(a) - A.prev_abs[ci0 + t]);
         if (a.off_track) r = r - S.penalty;
+        if (S.contact_rows) {
+            const float* cr = S.contact_rows + (size_t)(ci0 + t) * FTGP_CONTACT_FLOATS;
+            if (cr[2] > 0.0f) r = r - S.wall_penalty;
+            if (cr[3] > 0.0f) r = r - S.car_penalty;
+        }
         A.reward[my_row] = r;
     }
     __syncthreads();
@@ -2133,6 +2241,12 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_signals_kernel
     if (mine) {
         float* dst = reset ? S.final_state : S.state;
         if (dst) state_row(P.cars[ci0 + t], dst + my_row * FTGP_STATE_FLOATS);
+        if (S.contact_rows) {
+            const float* cr = S.contact_rows + (size_t)(ci0 + t) * FTGP_CONTACT_FLOATS;
+            float* row = reset ? S.final_contact : S.contact;
+            if (row) for (int q = 0; q < FTGP_CONTACT_FLOATS; ++q) row[my_row * FTGP_CONTACT_FLOATS + q] = cr[q];
+            if (reset && S.contact) for (int q = 0; q < FTGP_CONTACT_FLOATS; ++q) S.contact[my_row * FTGP_CONTACT_FLOATS + q] = 0.0f;
+        }
     }
     const int R = P.n_rays, NB = S.n_beams;
     for (int c = 0; c < cpe; ++c) {

@@ -75,8 +75,16 @@ class DeviceVecEnv:
     its rays); ``scan_max_range`` M > 0 clips the ranges to M (no hit = M) and scales them to [0, 1]; ``state=True`` adds
     info["state"] / info["final_state"], float32 [n_envs, n_agents, 8] (capi.STATE_FIELDS), and ``reset()`` fills ``state``;
     ``terminate_off_track`` ends an env when one of its agents is off the track; ``off_track_penalty`` is taken off the reward of an
-    agent in every call that leaves it off the track.  The returned tensors are the env's own buffers: the next ``step`` or
-    ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
+    agent in every call that leaves it off the track.
+
+    Contacts (ftgp_device_io_contacts / ftgp_step_device_contacts), off by default: ``contacts=True`` adds info["contact"] /
+    info["final_contact"], float32 [n_envs, n_agents, 4] (capi.CONTACT_FIELDS: the deepest wall penetration, the deepest overlap with
+    an env-mate, the number of the car's contact circles that touch a wall, the number of env-mates it overlaps) at the pose after the
+    call's steps; ``terminate_on_wall_contact`` / ``terminate_on_car_contact`` end an env when one of its agents touches a wall / a
+    mate, ``wall_contact_penalty`` / ``car_contact_penalty`` are taken off the reward of an agent in every call that leaves it touching.
+    Any of the four implies ``contacts=True``; ``reset()`` zeroes ``contact``.
+
+    The returned tensors are the env's own buffers: the next ``step`` or ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
     synchronises the host.
 
     track: a Track or the name of a bundled track, or a list of them (one handle, ftgp_create_tracks): env block t = envs_per_track[t]
@@ -87,7 +95,9 @@ class DeviceVecEnv:
     def __init__(self, track, n_envs: int = 4096, n_rays: int = 1080, cars_per_env: int = 1, roster=None,
                  max_episode_steps: int = 3000, action_repeat: int = 1, auto_reset: bool = True, device_id: int = 0,
                  envs_per_track=None, scan_pool: int = 1, scan_max_range: float = 0.0, state: bool = False,
-                 terminate_off_track: bool = False, off_track_penalty: float = 0.0, **env_kwargs):
+                 terminate_off_track: bool = False, off_track_penalty: float = 0.0, contacts: bool = False,
+                 terminate_on_wall_contact: bool = False, terminate_on_car_contact: bool = False, wall_contact_penalty: float = 0.0,
+                 car_contact_penalty: float = 0.0, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
@@ -100,6 +110,10 @@ class DeviceVecEnv:
             raise ValueError(f"scan_max_range: >= 0 and finite, got {scan_max_range}")
         if not (off_track_penalty >= 0.0 and math.isfinite(off_track_penalty)):
             raise ValueError(f"off_track_penalty: >= 0 and finite, got {off_track_penalty}")
+        wall_contact_penalty, car_contact_penalty = float(wall_contact_penalty), float(car_contact_penalty)
+        for name, p in (("wall_contact_penalty", wall_contact_penalty), ("car_contact_penalty", car_contact_penalty)):
+            if not (p >= 0.0 and math.isfinite(p)):
+                raise ValueError(f"{name}: >= 0 and finite, got {p}")
         roster = ["agent"] * cars_per_env if roster is None else list(roster)
         if len(roster) != cars_per_env:
             raise ValueError(f"one roster entry per car of an env: expected {cars_per_env}, got {len(roster)}")
@@ -124,6 +138,10 @@ class DeviceVecEnv:
         self.max_episode_steps, self.action_repeat, self.auto_reset = int(max_episode_steps), int(action_repeat), bool(auto_reset)
         self.scan_pool, self.scan_max_range, self.n_beams = scan_pool, scan_max_range, n_rays // scan_pool
         self.terminate_off_track, self.off_track_penalty = bool(terminate_off_track), off_track_penalty
+        self.terminate_on_wall_contact, self.terminate_on_car_contact = bool(terminate_on_wall_contact), bool(terminate_on_car_contact)
+        self.wall_contact_penalty, self.car_contact_penalty = wall_contact_penalty, car_contact_penalty
+        self.contacts = bool(contacts) or self.terminate_on_wall_contact or self.terminate_on_car_contact or \
+            wall_contact_penalty > 0.0 or car_contact_penalty > 0.0
         signals = scan_pool != 1 or scan_max_range > 0.0 or self.terminate_off_track or off_track_penalty > 0.0
 
         lib = capi.load()
@@ -136,6 +154,9 @@ class DeviceVecEnv:
         self.env.device_io_config(roster, self.max_episode_steps, self.action_repeat, self.auto_reset)
         if signals:
             self.env.device_io_signals(scan_pool, scan_max_range, self.terminate_off_track, off_track_penalty)
+        if self.contacts:
+            self.env.device_io_contacts(True, self.terminate_on_wall_contact, self.terminate_on_car_contact, wall_contact_penalty,
+                                        car_contact_penalty)
         z = dict(device=self.device)
         self.track_index = torch.from_numpy(self.env.track_of_env.astype("int64")).to(self.device)
         self.obs = torch.zeros((n_envs, self.n_agents, self.n_beams), dtype=torch.float32, **z)
@@ -157,12 +178,21 @@ class DeviceVecEnv:
             self._extra = capi.FtgpDeviceStepExtra(self.state.data_ptr(), self.final_state.data_ptr())
             self._extra_ref = ctypes.byref(self._extra)
             self._step_device_ex = lib.fn("step_device_ex")
+        self.contact = self.final_contact = None
+        if self.contacts:   # ftgp_step_device_contacts: a contact row per agent (capi.CONTACT_FIELDS)
+            self.contact = torch.zeros((n_envs, self.n_agents, capi.CONTACT_FLOATS), dtype=torch.float32, **z)
+            self.final_contact = torch.zeros_like(self.contact)
+            self._con = capi.FtgpDeviceStepContacts(self.contact.data_ptr(), self.final_contact.data_ptr())
+            self._con_ref = ctypes.byref(self._con)
+            self._step_device_contacts = lib.fn("step_device_contacts")
 
     def reset(self):
         """Reset every env (synchronous ftgp_reset); obs = the scans right after a reset, all zeros (custom.py:1092)."""
         self.env.reset()
         with torch.cuda.device(self.device):
             self.obs.zero_()
+            if self.contact is not None:
+                self.contact.zero_()
         if self.state is not None:
             self.env.state_device(self.state.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return self.obs
@@ -183,16 +213,24 @@ class DeviceVecEnv:
         self._check_actions(actions)
         self._io.action = actions.data_ptr()
         self._io.stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.state is None:
+        if self.state is None and self.contact is None:
             rc = self._step_device(self.env.h, self._io_ref)      # Env.step_device, without rebuilding the argument block
             if rc:
                 self.env.lib.check(rc)
             return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
-        rc = self._step_device_ex(self.env.h, self._io_ref, self._extra_ref)
+        extra = None if self.state is None else self._extra_ref
+        if self.contact is None:
+            rc = self._step_device_ex(self.env.h, self._io_ref, extra)
+        else:
+            rc = self._step_device_contacts(self.env.h, self._io_ref, extra, self._con_ref)
         if rc:
             self.env.lib.check(rc)
-        return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs, "state": self.state,
-                                                                        "final_state": self.final_state}
+        info = {"final_obs": self.final_obs}
+        if self.state is not None:
+            info["state"], info["final_state"] = self.state, self.final_state
+        if self.contact is not None:
+            info["contact"], info["final_contact"] = self.contact, self.final_contact
+        return self.obs, self.reward, self.terminated, self.truncated, info
 
     def close(self):
         if getattr(self, "env", None) is not None:

@@ -334,6 +334,73 @@ int ftgp_step_device_ex(FtgpEnv *env, const FtgpDeviceStep *io, const FtgpDevice
  * memory, ordered on `stream` like a device step (only enqueues).  After ftgp_device_io_config only (FTGP_ERR_STATE before it). */
 int ftgp_state_device(FtgpEnv *env, void *stream, float *state);
 
+/*
+ * Contacts of the device step: did the car hit something.  The reference ends nothing on a contact (MuJoCo resolves it and the race
+ * goes on, custom.py:1425); the pieces are this library's own contact geometry, the one K1's penalty forces use (DESIGN.md "K1").
+ *
+ * The contact row of a car, float32[FTGP_CONTACT_FLOATS], is evaluated at the car's pose as it stands: in a device step at the pose
+ * after the call's steps, before any reset.  Everything is binary64 and every entry is rounded once to binary32.  With
+ * ch = 1.0 - 2.0*(qz*qz) and sh = 2.0*(qw*qz):
+ *   0 wall_pen    the deepest wall penetration over the car's wall circles.  The chassis circles k = 0..2 sit at body (contact_x[k], 0)
+ *                 with radius contact_radius, world centre (x + ch*contact_x[k], y + sh*contact_x[k]); with bubble_wrap there are also
+ *                 the four softeners at body (wheel_x[k], wheel_y[k]) with radius softener_radius, world centre
+ *                 (x + (ch*wx - sh*wy), y + (sh*wx + ch*wy)).  A circle (centre (px, py), radius r) is looked up on the track's image:
+ *                   u = (px - origin_x) * inv_px_x, w = (origin_y - py) * inv_px_y (inv_px = 1.0 / px_size, divided once), ix = floor(u),
+ *                   iy = floor(w); a centre off the image (ix or iy outside [0, width) x [0, height)) touches nothing;
+ *                   the wall pixels (cx, cy) of the rectangle |cx - ix| <= ceil(r * inv_px_x), |cy - iy| <= ceil(r * inv_px_y) on the image:
+ *                   x0 = origin_x + (double)cx * px_size_x, x1 = x0 + px_size_x, y1 = origin_y - (double)cy * px_size_y, y0 = y1 - px_size_y,
+ *                   (qx, qy) = (px, py) clamped to [x0, x1] x [y0, y1], ex = px - qx, ey = py - qy; the pixel touches when
+ *                   ex*ex + ey*ey < r*r, and its penetration is r - sqrt(ex*ex + ey*ey).
+ *                 The circle's penetration is the largest over its touching pixels -- exactly the `pen` K1's wall force starts from at that
+ *                 pose.  0 when no circle touches.
+ *   1 car_pen     the deepest overlap with an env-mate, over every mate b != a of the env that has not finished and the nine pairs (i, j)
+ *                 of chassis circles: P = (x_a + ch_a*contact_x[i], y_a + sh_a*contact_x[i]), Q likewise of b with j, e = P - Q,
+ *                 d2 = ex*ex + ey*ey; a pair counts when 0 < d2 < r2*r2, r2 = 2.0*contact_radius, with overlap r2 - sqrt(d2).  Cars of
+ *                 bundled drivers are mates like any other.  0 when no pair counts.
+ *   2 wall_count  the number of the car's wall circles that touch, 0 to 7
+ *   3 car_count   the number of mates with at least one counting pair, 0 to 7
+ * A finished car collides with nothing (custom.py:1452-1457): its row is all zeros and nobody counts it as a mate.  The test is
+ * geometric overlap: a circle that penetrates but separates fast enough for K1's force to vanish (mag <= 0) still counts.  On a
+ * multi-track handle the wall frame (bitmap, size, origin, pixel sizes) is the one of the env's track.
+ *
+ * The contacts setter is valid after ftgp_device_io_config only (FTGP_ERR_STATE before it); NULL turns contacts off, and so does a
+ * later ftgp_device_io_config; ftgp_device_io_signals leaves them alone.  FTGP_ERR_ARG: a penalty that is negative, NaN or infinite.
+ * A struct of all zeros still turns the contact rows on: it changes no reward and ends no episode.  With contacts on, a device step
+ * evaluates every car's row once, between its steps and its episode rules:
+ *   reward[e][i]   the value of ftgp_device_io_signals' rule (off_track_penalty subtracted as there), then - wall_penalty if the car's
+ *                  wall_count > 0, then - car_penalty if its car_count > 0: binary32 subtractions in this order;
+ *   terminated[e]  that rule's value, or terminate_on_wall and some external car of e has wall_count > 0, or terminate_on_car and some
+ *                  external car of e has car_count > 0;
+ *   truncated, auto_reset, final_obs: unchanged.
+ * The rows are those of the pose after the call's steps: a contact that began and ended inside a call with action_repeat > 1 is not seen.
+ */
+#define FTGP_CONTACT_FLOATS 4
+typedef struct FtgpDeviceContacts {
+    int32_t terminate_on_wall;    /* non-zero: an env also terminates when an external car of it has wall_count > 0 */
+    int32_t terminate_on_car;     /* ... car_count > 0 */
+    float   wall_penalty;         /* >= 0, finite */
+    float   car_penalty;          /* >= 0, finite */
+} FtgpDeviceContacts;
+int ftgp_device_io_contacts(FtgpEnv *env, const FtgpDeviceContacts *contacts);
+
+/*
+ * The device step with contact rows: ftgp_step_device_ex(e, io, x) is this call with contacts = NULL.  contact / final_contact:
+ * float32[n_envs][n_ext][FTGP_CONTACT_FLOATS], device memory on the handle's device (a host pointer is FTGP_ERR_ARG before anything is
+ * enqueued); either may be NULL.  An env reset in the call gets its pre-reset rows in final_contact (only such rows are written there)
+ * and zeros in contact, like obs.  Contact buffers while contacts are off: FTGP_ERR_STATE.  With contacts off and no contact buffers
+ * the call launches exactly the kernels of ftgp_step_device_ex.
+ */
+typedef struct FtgpDeviceStepContacts {
+    float *contact;
+    float *final_contact;
+} FtgpDeviceStepContacts;
+int ftgp_step_device_contacts(FtgpEnv *env, const FtgpDeviceStep *io, const FtgpDeviceStepExtra *extra, const FtgpDeviceStepContacts *contacts);
+
+/* The external cars' contact rows at the current state, without a step: float32[n_envs][n_ext][FTGP_CONTACT_FLOATS] in device memory,
+ * ordered on `stream` like ftgp_state_device (only enqueues).  After ftgp_device_io_config (FTGP_ERR_STATE before it); contacts need
+ * not be on. */
+int ftgp_contacts_device(FtgpEnv *env, void *stream, float *contact);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).
@@ -357,6 +424,9 @@ int ftgp_get_progress(FtgpEnv *env, int32_t *out);
 /* double[n_cars]: the squared distance to the nearest centre-line point as the progress block stored it last (custom.py:1343; off_track
  * is this > 1, custom.py:1344) -- the field entry 5 of a device state row is the square root of. */
 int ftgp_get_centre_dist2(FtgpEnv *env, double *out);
+
+/* float[n_cars][FTGP_CONTACT_FLOATS]: the contact row (see FTGP_CONTACT_FLOATS) of EVERY car at the current state; any handle. */
+int ftgp_get_contacts(FtgpEnv *env, float *out);
 
 /* int32[n_cars]: place of each car among the finishers of its env, 1 = winner, 0 = still racing (Mujoco.winners, custom.py:1125,1367-1369). */
 int ftgp_get_winners(FtgpEnv *env, int32_t *out);

@@ -1,14 +1,17 @@
 """Env-steps/s of the device I/O loop (DeviceVecEnv.step on torch tensors) against the host loop (set_ctrl + step + get_lidar).
 
-    python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track] [--rows device,torch_pool,signals,host] [--repeats 1,4]
+    python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track] [--rows device,torch_pool,signals,contacts,host] [--repeats 1,4] [--cars 1]
 
 Device loop: constant actions, and random torch actions drawn before every call, at action_repeat 1 and 4; per-call time from HIP
 events on torch's stream around the timed calls.  Pooled observations (action_repeat 1, constant actions, beams of --pool rays clipped
 at --max-range and scaled): "torch_pool" = the raw scan plus the torch ops a user would write (-1 -> M, clamp, reshape(...).amin(-1),
-scale), "signals" = the same from the library (scan_pool, scan_max_range, state=True: ftgp_io_finish_signals_kernel).  Host loop: per
+scale), "signals" = the same from the library (scan_pool, scan_max_range, state=True: ftgp_io_finish_signals_kernel), "contacts" = the
+signals row with contact rows, both contact terminations and both penalties on top (ftgp_io_contact_kernel between the step and the
+finish kernel).  --cars: cars per env, every one an agent.  Host loop: per
 step set_ctrl (one copy + synchronisation), step(1), get_lidar (the whole scan back).  One JSON line per row, then a summary line.  Run it in a fresh process: torch is imported first
 (ft_grandprix_amd/vec.py).  Under `rocprofv3 --kernel-trace --stats -- python tools/vec_throughput.py` the per-kernel times of a call
-(ftgp_io_ingest_kernel, ftgp_step_kernel, ftgp_io_finish_kernel / ftgp_io_finish_signals_kernel) come out of the stats file.
+(ftgp_io_ingest_kernel, ftgp_step_kernel, ftgp_io_contact_kernel, ftgp_io_finish_kernel / ftgp_io_finish_signals_kernel) come out of
+the stats file.
 """
 import argparse
 import json
@@ -28,26 +31,29 @@ from ft_grandprix_amd.vec import DeviceVecEnv  # noqa: E402
 
 
 def device_row(track, a, repeat, actions, pooled=None):
-    """pooled: None = the raw scan; "torch" = pooled, clipped and scaled with torch ops after the call; "signals" = by the library."""
-    kw = dict(scan_pool=a.pool, scan_max_range=a.max_range, state=True) if pooled == "signals" else {}
-    venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, max_episode_steps=3000, action_repeat=repeat, spawn_mode=1, seed=7, **kw)
+    """pooled: None = the raw scan; "torch" = pooled, clipped and scaled with torch ops after the call; "signals" = by the library;
+    "contacts" = signals and the contact signals."""
+    kw = dict(scan_pool=a.pool, scan_max_range=a.max_range, state=True) if pooled in ("signals", "contacts") else {}
+    if pooled == "contacts":
+        kw.update(contacts=True, terminate_on_wall_contact=True, terminate_on_car_contact=True, wall_contact_penalty=1.0, car_contact_penalty=0.5)
+    venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, cars_per_env=a.cars, max_episode_steps=3000, action_repeat=repeat, spawn_mode=1, seed=7, **kw)
     dev = venv.device
     M, inv = float(a.max_range), 1.0 / float(a.max_range)
 
     def step(actions_):
         obs = venv.step(actions_)[0]
         if pooled == "torch":
-            obs = torch.where(obs < 0, M, obs).clamp(max=M).reshape(a.envs, 1, a.rays // a.pool, a.pool).amin(-1) * inv
+            obs = torch.where(obs < 0, M, obs).clamp(max=M).reshape(a.envs, a.cars, a.rays // a.pool, a.pool).amin(-1) * inv
         return obs
 
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
-    const = torch.tensor([1.5, 0.0], device=dev).expand(a.envs, 1, 2).contiguous()
+    const = torch.tensor([1.5, 0.0], device=dev).expand(a.envs, a.cars, 2).contiguous()
 
     def act():
         if actions == "constant":
             return const
-        u = torch.rand((a.envs, 1, 2), generator=gen, device=dev)
+        u = torch.rand((a.envs, a.cars, 2), generator=gen, device=dev)
         return torch.stack([3.0 * u[..., 0], 2.0 * u[..., 1] - 1.0], dim=2)
 
     venv.reset()
@@ -65,9 +71,9 @@ def device_row(track, a, repeat, actions, pooled=None):
     ms = t0.elapsed_time(t1)
     step_ms = venv.env.last_kernel_ms()
     venv.close()
-    loop = {None: "device", "torch": "device+torch_pool", "signals": "device+signals"}[pooled]
+    loop = {None: "device", "torch": "device+torch_pool", "signals": "device+signals", "contacts": "device+signals+contacts"}[pooled]
     extra = {} if pooled is None else {"pool": a.pool, "max_range": a.max_range}
-    return {"loop": loop, "actions": actions, "action_repeat": repeat, "envs": a.envs, "rays": a.rays, "calls": a.calls, **extra,
+    return {"loop": loop, "actions": actions, "action_repeat": repeat, "envs": a.envs, "cars": a.cars, "rays": a.rays, "calls": a.calls, **extra,
             "us_per_call": 1e3 * ms / a.calls, "host_us_per_call": 1e6 * wall / a.calls, "step_kernel_us_last_call": 1e3 * step_ms,
             "env_steps_per_s": a.envs * repeat * a.calls / (ms * 1e-3)}
 
@@ -75,8 +81,8 @@ def device_row(track, a, repeat, actions, pooled=None):
 def host_row(track, a):
     lib = capi.load()
     n = max(10, a.calls // 4)
-    with capi.Env(lib, track, n_envs=a.envs, n_rays=a.rays, spawn_mode=1, seed=7) as e:
-        ctrl = np.tile(np.array([1.5, 0.0]), (a.envs, 1))
+    with capi.Env(lib, track, n_envs=a.envs, cars_per_env=a.cars, n_rays=a.rays, spawn_mode=1, seed=7) as e:
+        ctrl = np.tile(np.array([1.5, 0.0]), (a.envs * a.cars, 1))
         for _ in range(5):
             e.set_ctrl(ctrl); e.step(1); e.lidar()
         w0 = time.perf_counter()
@@ -99,7 +105,8 @@ def main():
     ap.add_argument("--pool", type=int, default=10)
     ap.add_argument("--max-range", type=float, default=10.0)
     ap.add_argument("--repeats", default="1,4", help="action_repeat of the device rows, comma-separated")
-    ap.add_argument("--rows", default="device,torch_pool,signals,host", help="comma-separated: device, torch_pool, signals, host")
+    ap.add_argument("--cars", type=int, default=1, help="cars per env, every one an agent")
+    ap.add_argument("--rows", default="device,torch_pool,signals,host", help="comma-separated: device, torch_pool, signals, contacts, host")
     a = ap.parse_args()
     want = set(a.rows.split(","))
     track = load_track(a.track)
@@ -109,7 +116,7 @@ def main():
             for actions in ("constant", "random"):
                 rows.append(device_row(track, a, repeat, actions))
                 print(json.dumps(rows[-1]), flush=True)
-    for name, pooled in (("torch_pool", "torch"), ("signals", "signals")):
+    for name, pooled in (("torch_pool", "torch"), ("signals", "signals"), ("contacts", "contacts")):
         if name in want:
             rows.append(device_row(track, a, 1, "constant", pooled))
             print(json.dumps(rows[-1]), flush=True)
