@@ -84,6 +84,7 @@ API_SYMBOLS = (
     "device_io_config", "step_device", "create_tracks", "get_track_distance_field",
     "device_io_signals", "step_device_ex", "state_device", "get_centre_dist2",
     "device_io_contacts", "step_device_contacts", "contacts_device", "get_contacts",
+    "set_spawn_rule", "get_episodes", "get_start_table",
 )
 
 
@@ -112,6 +113,11 @@ class FtgpDeviceContacts(C.Structure):
 
 class FtgpDeviceStepContacts(C.Structure):
     _fields_ = [("contact", C.c_void_p), ("final_contact", C.c_void_p)]
+
+
+class FtgpSpawnRule(C.Structure):
+    _fields_ = [("first_point", C.c_int32), ("n_points", C.c_int32), ("shuffle_grid", C.c_int32), ("reserved", C.c_int32),
+                ("margin", C.c_double), ("lateral_frac", C.c_double), ("yaw_tan", C.c_double)]
 
 
 class FtgpError(RuntimeError):
@@ -190,6 +196,9 @@ class CLib:
             "step_device_contacts": (i32, [vp, C.POINTER(FtgpDeviceStep), C.POINTER(FtgpDeviceStepExtra), C.POINTER(FtgpDeviceStepContacts)]),
             "contacts_device": (i32, [vp, vp, vp]),
             "get_contacts": (i32, [vp, dp]),
+            "set_spawn_rule": (i32, [vp, C.POINTER(FtgpSpawnRule)]),
+            "get_episodes": (i32, [vp, dp]),
+            "get_start_table": (i32, [vp, i32, dp]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -402,6 +411,33 @@ class Env:
             return
         c = FtgpDeviceContacts(int(bool(terminate_on_wall)), int(bool(terminate_on_car)), float(wall_penalty), float(car_penalty))
         self._call("device_io_contacts", C.byref(c))
+
+    # -- spawn rule (include/ftgp.h: ftgp_set_spawn_rule)
+    def set_spawn_rule(self, on: bool = True, first_point: int = 0, n_points: int = PATH_POINTS, margin: float = 0.0,
+                       lateral_frac: float = 0.0, yaw_tan: float = 0.0, shuffle_grid: bool = False):
+        """ftgp_set_spawn_rule: from now on every reset -- ``reset`` with or without a mask, the auto-reset of a device step -- draws
+        start point, lateral offset, yaw (``yaw_tan`` = tan of half the largest offset) and grid order per (seed, env, episode);
+        ``on=False`` puts the fixed starts of ``spawn_mode`` back.  Every call zeroes ``episodes()``."""
+        if not on:
+            self._call("set_spawn_rule", None)
+            return
+        r = FtgpSpawnRule(int(first_point), int(n_points), int(bool(shuffle_grid)), 0, float(margin), float(lateral_frac), float(yaw_tan))
+        self._call("set_spawn_rule", C.byref(r))
+
+    def episodes(self) -> np.ndarray:
+        """int64 [n_envs]: resets of every env since the spawn rule was set (zeros without a rule)."""
+        out = np.empty(self.n_envs, dtype=np.int64)
+        self._call("get_episodes", _ptr(out))
+        return out
+
+    def start_table(self, track: int = 0) -> np.ndarray:
+        """float64 [100, 6] of track ``track``: x, y, qw, qz of the spawn table, wall clearance to the left and to the right."""
+        track = int(track)
+        if not 0 <= track < len(self.tracks):
+            raise ValueError(f"track {track} of a handle with {len(self.tracks)}")
+        out = np.empty((PATH_POINTS, 6), dtype=np.float64)
+        self._call("get_start_table", track, _ptr(out))
+        return out
 
     def step_device(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0,
                     state: int = 0, final_state: int = 0, contact: int = 0, final_contact: int = 0):

@@ -167,6 +167,10 @@ struct FtgpEnv {
     bool con_on = false;              // ftgp_device_io_contacts: a call evaluates the contact rows and goes through ftgp_io_finish_signals_kernel
     FtgpDeviceContacts con{};         // the contact rules while con_on
     DevBuf<float> d_contact;          // [n_cars][FTGP_CONTACT_FLOATS] every car's contact row, allocated on first use
+    // spawn rule (ftgp_set_spawn_rule)
+    std::vector<double> start_table;  // [n_tracks][FTGP_PATH_POINTS][6] x, y, qw, qz, clear_left, clear_right: the plan's (ftgp_get_start_table)
+    const FtgpSpawnDev* rule = nullptr;      // what the reset paths are handed: d_rule while a rule is set, null without one
+    DevBuf<FtgpSpawnDev> d_rule; DevBuf<int32_t> d_start, d_n_start; DevBuf<double> d_clear; DevBuf<int64_t> d_episodes;      // allocated by the first rule
     struct Checked { const void* p; size_t bytes; };
     Checked io_checked[32] = {};      // device buffers found valid (hipPointerGetAttributes), replaced round robin
     int io_checked_next = 0;
@@ -374,6 +378,7 @@ struct Plan {
                                           // (padding bytes zero: the block is uploaded as it lies); every pointer null
         HostTables tab;               // bitmaps and run lengths of the track (build_tables)
         std::vector<double> spawn;    // [FTGP_PATH_POINTS][4] x, y, qw, qz
+        std::vector<double> clear;    // [FTGP_PATH_POINTS][2] wall clearance to the left / right of the spawn table's points (ftgp_start_table)
         std::vector<double> path;     // [FTGP_PATH_POINTS][2] the caller's centre-line
     };
     std::vector<Track> tracks;        // one per track of the handle (ftgp_create: one)
@@ -566,11 +571,7 @@ void plan_track_tables(const FtgpTrack& t, const DeviceParams& P, HostTables& ta
 {
     build_tables(t, P.contact_reach, tab);
     spawn.assign(4 * FTGP_PATH_POINTS, 0.0);
-    for (int p = 0; p < FTGP_PATH_POINTS; ++p) {      // position_vehicles (custom.py:1240-1245) + euler_to_quaternion([angle, 0, 0]) (custom.py:81-87)
-        const int p1 = (p + 1) % FTGP_PATH_POINTS;
-        const double ang = atan2(t.path[2 * p1 + 1] - t.path[2 * p + 1], t.path[2 * p1] - t.path[2 * p]);
-        spawn[4 * p] = t.path[2 * p]; spawn[4 * p + 1] = t.path[2 * p + 1]; spawn[4 * p + 2] = cos(ang / 2); spawn[4 * p + 3] = sin(ang / 2);
-    }
+    ftgp_spawn_table(t, spawn.data());
 }
 
 // Workgroup order of a multi-track launch (FTGP_TRACK_ORDER=blocks|xcd).  Workgroups are dealt round robin over the 8 XCDs, so workgroups b
@@ -657,6 +658,8 @@ int plan(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per
         k.P = P;
         plan_track_params(cfg, tracks[t], k.P);
         plan_track_tables(tracks[t], k.P, k.tab, k.spawn);
+        k.clear.assign(2 * FTGP_PATH_POINTS, 0.0);
+        ftgp_start_table(tracks[t], k.spawn.data(), k.clear.data());
         k.path.assign(tracks[t].path, tracks[t].path + 2 * FTGP_PATH_POINTS);
         diag = std::max(diag, track_diagonal(tracks[t]));
         pl.env_track.insert(pl.env_track.end(), (size_t)envs_per_track[t], t);
@@ -996,6 +999,13 @@ int upload(FtgpEnv* e, const Plan& pl, const Switches& sw)
         }
         HIP_TRY(dev_upload(e->d_path, paths.data(), sz_path * T));
         HIP_TRY(dev_upload(e->d_spawn, spawns.data(), sz_spawn * T));
+        e->start_table.assign(6 * FTGP_PATH_POINTS * (size_t)T, 0.0);
+        for (int k = 0; k < T; ++k)
+            for (int p = 0; p < FTGP_PATH_POINTS; ++p) {
+                double* row = &e->start_table[6 * (FTGP_PATH_POINTS * (size_t)k + p)];
+                memcpy(row, &pl.tracks[(size_t)k].spawn[4 * (size_t)p], sizeof(double) * 4);
+                memcpy(row + 4, &pl.tracks[(size_t)k].clear[2 * (size_t)p], sizeof(double) * 2);
+            }
     }
     HIP_TRY(dev_upload(e->d_veh, pl.veh.data(), pl.veh.size()));
     HIP_TRY(dev_upload(e->d_ray, pl.ray.data(), sizeof(float) * pl.ray.size()));
@@ -1180,8 +1190,12 @@ int ftgp_reset(FtgpEnv* e, const uint8_t* mask)
         HIP_TRY(hipMemcpyAsync(e->d_env_mask.get(), mask, (size_t)e->P.n_envs, hipMemcpyHostToDevice, e->stream.get()));
         dmask = e->d_env_mask.get();
     }
-    hipLaunchKernelGGL(ftgp_reset_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P, dmask, (const int32_t*)e->d_env_track.get());
+    hipLaunchKernelGGL(ftgp_reset_kernel, dim3((e->P.n_cars + 63) / 64), dim3(64), 0, e->stream.get(), e->P, dmask, (const int32_t*)e->d_env_track.get(), e->rule);
     HIP_TRY(hipGetLastError());
+    if (e->rule) {      // every car has read its env's counter: the launch behind advances it
+        hipLaunchKernelGGL(ftgp_episodes_kernel, dim3((e->P.n_envs + 63) / 64), dim3(64), 0, e->stream.get(), e->P.n_envs, dmask, e->d_episodes.get());
+        HIP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(ftgp_zero_ranges_kernel, dim3(e->P.n_cars), dim3(256), 0, e->stream.get(), e->P, dmask);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
@@ -1343,12 +1357,12 @@ int ftgp_step_device_contacts(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDe
     HIP_TRY(hipGetLastError());
     if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, e->io_repeat, true)) return rc;
     if (e->con_on) if (int rc = launch_contacts(e, e->d_contact.get(), nullptr)) return rc;
-    if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A);
+    if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, e->rule);
     else {
         const bool aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
         S.vec_out = aligned && S.n_beams % 4 == 0;
         if (S.path == FTGP_SIG_PATH_REGS && !aligned) S.path = FTGP_SIG_PATH_STAGE;
-        hipLaunchKernelGGL(ftgp_io_finish_signals_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, S);
+        hipLaunchKernelGGL(ftgp_io_finish_signals_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, S, e->rule);
     }
     HIP_TRY(hipGetLastError());
     e->rows_valid = false;
@@ -1386,6 +1400,69 @@ int ftgp_contacts_device(FtgpEnv* e, void* stream, float* contact)
     if (int rc = launch_contacts(e, nullptr, contact)) return rc;
     HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
     HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
+    return 0;
+}
+
+int ftgp_set_spawn_rule(FtgpEnv* e, const FtgpSpawnRule* r)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    const size_t T = (size_t)e->n_tracks, n_envs = (size_t)e->P.n_envs;
+    std::vector<int32_t> start(FTGP_PATH_POINTS * T, 0), n_start(T, 0);
+    std::vector<double> clear(2 * FTGP_PATH_POINTS * T, 0.0);
+    if (r) {
+        if (r->first_point < 0 || r->first_point >= FTGP_PATH_POINTS) return fail(FTGP_ERR_ARG, "set_spawn_rule: first_point in 0 .. 99%s");
+        if (r->n_points < 1 || r->n_points > FTGP_PATH_POINTS) return fail(FTGP_ERR_ARG, "set_spawn_rule: n_points in 1 .. 100%s");
+        if (r->reserved != 0) return fail(FTGP_ERR_ARG, "set_spawn_rule: reserved must be 0%s");
+        if (!(r->margin >= 0.0) || std::isinf(r->margin)) return fail(FTGP_ERR_ARG, "set_spawn_rule: margin >= 0 and finite%s");
+        if (!(r->lateral_frac >= 0.0 && r->lateral_frac <= 1.0)) return fail(FTGP_ERR_ARG, "set_spawn_rule: lateral_frac in [0, 1]%s");
+        if (!(r->yaw_tan >= 0.0) || std::isinf(r->yaw_tan)) return fail(FTGP_ERR_ARG, "set_spawn_rule: yaw_tan >= 0 and finite%s");
+        for (size_t k = 0; k < T; ++k) {
+            for (int p = 0; p < FTGP_PATH_POINTS; ++p) memcpy(&clear[2 * (FTGP_PATH_POINTS * k + p)], &e->start_table[6 * (FTGP_PATH_POINTS * k + p) + 4], sizeof(double) * 2);
+            n_start[k] = ftgp_start_list(*r, &clear[2 * FTGP_PATH_POINTS * k], &start[FTGP_PATH_POINTS * k]);
+            if (n_start[k] == 0)
+                return failf(FTGP_ERR_ARG, "track %d: set_spawn_rule: none of the %d points from %d on keeps %g of clearance on both sides", (int)k, r->n_points, r->first_point, r->margin);
+        }
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the tables or the counters while they change
+    if (r) {
+        if (!e->d_start) HIP_TRY(dev_alloc(e->d_start, sizeof(int32_t) * start.size()));
+        if (!e->d_n_start) HIP_TRY(dev_alloc(e->d_n_start, sizeof(int32_t) * n_start.size()));
+        if (!e->d_clear) HIP_TRY(dev_alloc(e->d_clear, sizeof(double) * clear.size()));
+        if (!e->d_episodes) HIP_TRY(dev_alloc(e->d_episodes, sizeof(int64_t) * n_envs));
+        if (!e->d_rule) HIP_TRY(dev_alloc(e->d_rule, sizeof(FtgpSpawnDev)));
+        FtgpSpawnDev d{};
+        d.start = e->d_start.get(); d.n_start = e->d_n_start.get(); d.clear = e->d_clear.get(); d.episodes = e->d_episodes.get();
+        d.margin = r->margin; d.lateral_frac = r->lateral_frac; d.yaw_tan = r->yaw_tan; d.shuffle_grid = r->shuffle_grid ? 1 : 0;
+        HIP_TRY(hipMemcpy(e->d_rule.get(), &d, sizeof d, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_start.get(), start.data(), sizeof(int32_t) * start.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_n_start.get(), n_start.data(), sizeof(int32_t) * n_start.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_clear.get(), clear.data(), sizeof(double) * clear.size(), hipMemcpyHostToDevice));
+    }
+    if (e->d_episodes) {
+        HIP_TRY(hipMemsetAsync(e->d_episodes.get(), 0, sizeof(int64_t) * n_envs, e->stream.get()));
+        HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    }
+    e->rule = r ? e->d_rule.get() : nullptr;
+    return 0;
+}
+
+int ftgp_get_episodes(FtgpEnv* e, int64_t* out)
+{
+    if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    const size_t bytes = sizeof(int64_t) * (size_t)e->P.n_envs;
+    if (!e->d_episodes) { memset(out, 0, bytes); return 0; }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(out, e->d_episodes.get(), bytes, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    return 0;
+}
+
+int ftgp_get_start_table(FtgpEnv* e, int track, double* out)
+{
+    if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    if (track < 0 || track >= e->n_tracks) return failf(FTGP_ERR_ARG, "ftgp_get_start_table: track %d of a handle with %d", track, e->n_tracks);
+    memcpy(out, &e->start_table[6 * FTGP_PATH_POINTS * (size_t)track], sizeof(double) * 6 * FTGP_PATH_POINTS);
     return 0;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/ftgp.h"
 #include "ftgp_march.h"
+#include "ftgp_spawn.h"
 
 #define FTGP_WAVE 64
 #define FTGP_MAX_GROUPS 256              // groups of 64 rays per car: n_rays <= 16384
@@ -178,14 +179,7 @@ __device__ __forceinline__ double spec_cos(double x)
     return 1.0 + p;
 }
 
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__host__ __device__ __forceinline__ double u01(uint64_t h) { return (double)(h >> 11) * (1.0 / 9007199254740992.0); }
+// splitmix64 / u01, the counter-based generator: ftgp_spawn.h
 
 // ---------------------------------------------------------------------------------------------
 // wave64 helpers

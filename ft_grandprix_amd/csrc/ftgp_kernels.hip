@@ -1801,11 +1801,22 @@ __device__ __forceinline__ void progress_lane(const DeviceParams& P, const doubl
     race_store(r, &s);
 }
 
-// the spawn state of car ci (car `car` of env `env`, on track trk) with a cleared race state, before K3 has seen the spawn pose
-__device__ __forceinline__ void spawn_state(const DeviceParams& P, int ci, int env, int car, int trk, CarCore& s)
+// the spawn state of car ci (car `car` of env `env`, on track trk) with a cleared race state, before K3 has seen the spawn pose.
+// With a spawn rule (R set: the rule in device memory; ftgp_set_spawn_rule) the pose is that episode's draw of ftgp_spawn.h and the progress offset the
+// nearest centre-line point of that pose; without one, spawn_mode 0 / 1 as ever.
+__device__ __forceinline__ void spawn_state(const DeviceParams& P, const FtgpSpawnDev* __restrict__ R, int64_t episode, int ci, int env, int car, int trk, CarCore& s)
 {
     const double* spawn = P.spawn + (size_t)trk * 4 * FTGP_PATH_POINTS;
     memset(&s, 0, sizeof s);
+    if (R) {
+        FtgpSpawnPose o;
+        ftgp_spawn_draw(P.seed, (uint64_t)(P.env_base + env), (uint64_t)episode, P.cars_per_env, car, R->start + (size_t)trk * FTGP_PATH_POINTS, R->n_start[trk],
+                        R->clear + (size_t)trk * 2 * FTGP_PATH_POINTS, spawn, R->margin, R->lateral_frac, R->yaw_tan, R->shuffle_grid, o);
+        s.offset = o.offset;
+        s.good_start = 1;
+        s.x = o.x; s.y = o.y; s.qw = o.qw; s.qz = o.qz;
+        return;
+    }
     const int p = (P.spawn_mode == 0) ? (car + 5) * 2 : (int)((10 + 7 * (long)(P.env_base + env) + 2 * car) % 98);   // custom.py:1112
     s.offset = p;
     s.good_start = 1;
@@ -1823,13 +1834,13 @@ __device__ __forceinline__ void spawn_state(const DeviceParams& P, int ci, int e
 }
 
 // car ci back at its spawn pose with a cleared race state; car 0 of the env also zeroes the env's steps (ftgp_reset_kernel,
-// ftgp_io_finish_kernel)
-__device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track)
+// ftgp_io_finish_kernel).  episode: the env's episode counter as every car of the env read it before anyone advances it (spawn rule only).
+__device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track, const FtgpSpawnDev* __restrict__ R, int64_t episode)
 {
     const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
     const int trk = env_track_of(env_track, env);
     CarCore s;
-    spawn_state(P, ci, env, car, trk, s);
+    spawn_state(P, R, episode, ci, env, car, trk, s);
     if (car == 0) P.steps[env] = 0;
     for (int k = 0; k < FTGP_MAX_LAP_TIMES; ++k) P.cars[ci].times[k] = 0.0;
     progress_lane(P, P.path + (size_t)trk * 2 * FTGP_PATH_POINTS, s, 0, P.cars[ci].times);
@@ -1838,23 +1849,35 @@ __device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const i
 
 // reset_car on the record where it lies (ftgp_io_finish_signals_kernel): the same operations on the same values, without a copy of the
 // record on the lane's stack -- K3 reaches start / finish_step through a pointer, which keeps such a copy in scratch memory
-__device__ __forceinline__ void reset_car_in_place(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track)
+__device__ __forceinline__ void reset_car_in_place(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track, const FtgpSpawnDev* __restrict__ R, int64_t episode)
 {
     const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
     const int trk = env_track_of(env_track, env);
     CarCore& s = P.cars[ci];
-    spawn_state(P, ci, env, car, trk, s);
+    spawn_state(P, R, episode, ci, env, car, trk, s);
     if (car == 0) P.steps[env] = 0;
     for (int k = 0; k < FTGP_MAX_LAP_TIMES; ++k) P.cars[ci].times[k] = 0.0;
     progress_lane(P, P.path + (size_t)trk * 2 * FTGP_PATH_POINTS, s, 0, P.cars[ci].times);
 }
 
-__global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ env_mask, const int32_t* __restrict__ env_track)
+// With a spawn rule the cars of an env -- lanes of different waves, even of different workgroups -- all spawn with the env's episode
+// counter as it stands: nobody advances it here, ftgp_episodes_kernel does in a launch of its own behind this one.
+__global__ void ftgp_reset_kernel(DeviceParams P, const uint8_t* __restrict__ env_mask, const int32_t* __restrict__ env_track, const FtgpSpawnDev* __restrict__ R)
 {
     const int ci = blockIdx.x * blockDim.x + threadIdx.x;
     if (ci >= P.n_cars) return;
-    if (env_mask && !env_mask[ci / P.cars_per_env]) return;
-    reset_car(P, ci, env_track);
+    const int env = ci / P.cars_per_env;
+    if (env_mask && !env_mask[env]) return;
+    reset_car(P, ci, env_track, R, R ? R->episodes[env] : 0);
+}
+
+// spawn rule: the episode counters of the envs just reset, one env per lane
+__global__ void ftgp_episodes_kernel(int n_envs, const uint8_t* __restrict__ env_mask, int64_t* __restrict__ episodes)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= n_envs) return;
+    if (env_mask && !env_mask[env]) return;
+    episodes[env] += 1;
 }
 
 // sensordata = 0 after mj_resetData (custom.py:1092): coalesced zero fill of the reset envs' scans
@@ -1940,10 +1963,11 @@ __global__ void ftgp_io_ingest_kernel(DeviceParams P, DeviceIoArgs A)
 // One workgroup per env, after the steps: rewards, episode ends, and the observations.  An env that ended with auto_reset on
 // hands its scans to final_obs, gets obs rows of zeros and is reset exactly as ftgp_reset resets it (reset_car, ranges 0).
 #define FTGP_IO_THREADS 256
-__global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_kernel(DeviceParams P, DeviceIoArgs A)
+__global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_kernel(DeviceParams P, DeviceIoArgs A, const FtgpSpawnDev* __restrict__ rule)
 {
     __shared__ int ended;
     const int env = blockIdx.x, cpe = P.cars_per_env, ci0 = env * cpe, t = threadIdx.x;
+    const int64_t episode = rule ? rule->episodes[env] : 0;      // spawn rule: read by every lane before the barriers, advanced behind them
     if (t == 0) {
         bool all_finished = true;
         for (int c = 0; c < cpe; ++c)
@@ -1985,7 +2009,8 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_kernel(DeviceP
         __syncthreads();      // the row has been read before it is zeroed
         if (reset) for (int j = t; j < P.ranges_stride; j += FTGP_IO_THREADS) src[j] = 0.0f;
     }
-    if (reset && t < cpe) reset_car(P, ci0 + t, A.env_track);      // (the records were read before the first barrier)
+    if (reset && t < cpe) reset_car(P, ci0 + t, A.env_track, rule, episode);      // (the records were read before the first barrier)
+    if (reset && t == 0 && rule) rule->episodes[env] = episode + 1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2200,7 +2225,7 @@ __global__ void __launch_bounds__(FTGP_CONTACT_THREADS) ftgp_io_contact_kernel(D
 // is off_track pays the penalty and, with terminate_off_track, ends its env; state rows are written from the records after the steps
 // (to final_state for an env that is reset here) and again after the reset.  With contacts on (S.contact_rows, this call's rows of
 // ftgp_io_contact_kernel) the wall and car penalties and episode ends join, and the rows go out like the state rows -- zeros after a reset.
-__global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_signals_kernel(DeviceParams P, DeviceIoArgs A, DeviceSignalArgs S)
+__global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgpr(72))) ftgp_io_finish_signals_kernel(DeviceParams P, DeviceIoArgs A, DeviceSignalArgs S, const FtgpSpawnDev* __restrict__ rule)
 {
     __shared__ int ended;
     __shared__ __attribute__((aligned(16))) float stage[FTGP_SIG_STAGE_FLOATS];
@@ -2265,9 +2290,16 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_finish_signals_kernel
         __syncthreads();      // the row has been read before it is zeroed
         if (reset) for (int j = t; j < P.ranges_stride; j += FTGP_IO_THREADS) src[j] = 0.0f;
     }
+    // spawn rule: every lane reads the env's episode counter, and a barrier separates the reads from lane 0 advancing it
+    int64_t episode = 0;
+    if (reset && rule) {          // (both uniform over the workgroup)
+        episode = rule->episodes[env];
+        __syncthreads();
+    }
     if (reset && t < cpe) {
-        reset_car_in_place(P, ci0 + t, A.env_track);      // (the records were read before the first barrier, and by this lane above)
+        reset_car_in_place(P, ci0 + t, A.env_track, rule, episode);      // (the records were read before the first barrier, and by this lane above)
         if (mine && S.state) state_row(P.cars[ci0 + t], S.state + my_row * FTGP_STATE_FLOATS);
+        if (t == 0 && rule) rule->episodes[env] = episode + 1;
     }
 }
 

@@ -84,6 +84,15 @@ class DeviceVecEnv:
     mate, ``wall_contact_penalty`` / ``car_contact_penalty`` are taken off the reward of an agent in every call that leaves it touching.
     Any of the four implies ``contacts=True``; ``reset()`` zeroes ``contact``.
 
+    Random starts (ftgp_set_spawn_rule), off by default -- every reset then puts a car back on the pose it had before:
+    ``random_start=True`` draws, at every reset of an env (``reset()`` and the auto-reset alike), a start point among the
+    ``start_points = (first, count)`` path points (first + i) % 100 that keep ``start_margin`` of wall clearance on both sides (None =
+    the chassis' contact radius; with ``bubble_wrap`` the reach of the wheel softeners if that is larger), a lateral offset of up to
+    ``start_lateral`` (0 .. 1) of the room the walls leave beyond that margin, a yaw offset of up to ``start_yaw_jitter`` radians to
+    either side (``start_yaw_jitter`` < pi), and, with ``shuffle_grid``, the grid slots of the env's cars; keyed by (seed, env,
+    episode), so a shard of a larger batch draws what that slice of the whole batch would.  Any of the five implies
+    ``random_start=True``.  ``episode_index()`` = how often each env has been reset since.
+
     The returned tensors are the env's own buffers: the next ``step`` or ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
     synchronises the host.
 
@@ -97,7 +106,8 @@ class DeviceVecEnv:
                  envs_per_track=None, scan_pool: int = 1, scan_max_range: float = 0.0, state: bool = False,
                  terminate_off_track: bool = False, off_track_penalty: float = 0.0, contacts: bool = False,
                  terminate_on_wall_contact: bool = False, terminate_on_car_contact: bool = False, wall_contact_penalty: float = 0.0,
-                 car_contact_penalty: float = 0.0, **env_kwargs):
+                 car_contact_penalty: float = 0.0, random_start: bool = False, start_points=(0, 100), start_margin=None,
+                 start_lateral: float = 0.0, start_yaw_jitter: float = 0.0, shuffle_grid: bool = False, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
@@ -114,6 +124,21 @@ class DeviceVecEnv:
         for name, p in (("wall_contact_penalty", wall_contact_penalty), ("car_contact_penalty", car_contact_penalty)):
             if not (p >= 0.0 and math.isfinite(p)):
                 raise ValueError(f"{name}: >= 0 and finite, got {p}")
+        try:
+            first_point, n_points = (int(v) for v in start_points)
+        except (TypeError, ValueError):
+            raise ValueError(f"start_points: (first point, number of points), got {start_points!r}") from None
+        if not (0 <= first_point < capi.PATH_POINTS and 1 <= n_points <= capi.PATH_POINTS):
+            raise ValueError(f"start_points: first point in 0 .. 99 and 1 .. 100 points, got {start_points!r}")
+        if start_margin is not None and not (float(start_margin) >= 0.0 and math.isfinite(float(start_margin))):
+            raise ValueError(f"start_margin: >= 0 and finite, or None, got {start_margin}")
+        start_lateral, start_yaw_jitter = float(start_lateral), float(start_yaw_jitter)
+        if not 0.0 <= start_lateral <= 1.0:
+            raise ValueError(f"start_lateral: in [0, 1], got {start_lateral}")
+        if not 0.0 <= start_yaw_jitter < math.pi:
+            raise ValueError(f"start_yaw_jitter: radians in [0, pi), got {start_yaw_jitter}")
+        self.random_start = bool(random_start) or (first_point, n_points) != (0, capi.PATH_POINTS) or start_margin is not None or \
+            start_lateral > 0.0 or start_yaw_jitter > 0.0 or bool(shuffle_grid)
         roster = ["agent"] * cars_per_env if roster is None else list(roster)
         if len(roster) != cars_per_env:
             raise ValueError(f"one roster entry per car of an env: expected {cars_per_env}, got {len(roster)}")
@@ -157,6 +182,16 @@ class DeviceVecEnv:
         if self.contacts:
             self.env.device_io_contacts(True, self.terminate_on_wall_contact, self.terminate_on_car_contact, wall_contact_penalty,
                                         car_contact_penalty)
+        self.start_rule = None
+        if self.random_start:
+            if start_margin is None:       # the chassis circles' radius; with bubble_wrap the softeners' sideways reach if that is larger
+                v = self.env.cfg.vehicle
+                start_margin = v.contact_radius
+                if env_kwargs.get("bubble_wrap"):
+                    start_margin = max(start_margin, max(abs(y) for y in v.wheel_y) + v.softener_radius)
+            self.start_rule = dict(first_point=first_point, n_points=n_points, margin=float(start_margin), lateral_frac=start_lateral,
+                                   yaw_tan=math.tan(0.5 * start_yaw_jitter), shuffle_grid=bool(shuffle_grid))
+            self.env.set_spawn_rule(True, **self.start_rule)
         z = dict(device=self.device)
         self.track_index = torch.from_numpy(self.env.track_of_env.astype("int64")).to(self.device)
         self.obs = torch.zeros((n_envs, self.n_agents, self.n_beams), dtype=torch.float32, **z)
@@ -187,7 +222,8 @@ class DeviceVecEnv:
             self._step_device_contacts = lib.fn("step_device_contacts")
 
     def reset(self):
-        """Reset every env (synchronous ftgp_reset); obs = the scans right after a reset, all zeros (custom.py:1092)."""
+        """Reset every env (synchronous ftgp_reset, which follows the start rule); obs = the scans right after a reset, all zeros
+        (custom.py:1092)."""
         self.env.reset()
         with torch.cuda.device(self.device):
             self.obs.zero_()
@@ -196,6 +232,10 @@ class DeviceVecEnv:
         if self.state is not None:
             self.env.state_device(self.state.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return self.obs
+
+    def episode_index(self):
+        """int64 numpy [n_envs]: resets of every env since the start rule was set (``Env.episodes``; zeros without random starts)."""
+        return self.env.episodes()
 
     def _check_actions(self, actions):
         if not isinstance(actions, torch.Tensor):

@@ -401,6 +401,63 @@ int ftgp_step_device_contacts(FtgpEnv *env, const FtgpDeviceStep *io, const Ftgp
  * not be on. */
 int ftgp_contacts_device(FtgpEnv *env, void *stream, float *contact);
 
+/*
+ * Spawn rule: random, wall-aware episode starts.  The reference places car i at path[(i+5)*2] in every episode (custom.py:1112,
+ * 1232-1245); FtgpConfig.spawn_mode 0 / 1 are fixed poses too.  A rule is a property of the handle that every reset obeys once it is
+ * set -- ftgp_reset with or without a mask and the auto-reset of the device step: start point, lateral offset, yaw and grid order are
+ * drawn from the library's counter-based generator keyed by (seed, global env index, episode number), bounded by a per-track
+ * wall-clearance table, and the progress offset is taken at the pose drawn.  With no rule set nothing changes, to the bit.
+ *
+ * Start table (host arithmetic at create, per track).  For path point p with spawn entry (X, Y, qw, qz): ch = 1.0 - 2.0*(qz*qz),
+ * sh = 2.0*(qw*qz); the left normal is (-sh, ch), the right normal its negation.  delta = 0.5 * min(px_size_x, px_size_y),
+ * K = (int)ceil(1.0 / delta) (1.0: the off-track distance, custom.py:1344).  On each side the samples k = 0 .. K sit at
+ * (X + ((double)k*delta)*nx, Y + ((double)k*delta)*ny); a sample is blocked when its pixel -- found as the contact rows find theirs:
+ * u = (px - origin_x)*inv_px_x, w = (origin_y - py)*inv_px_y, floor, bit (ix & 31) of word (ix >> 5) -- is a wall, or when it lies off
+ * the image.  With m the first blocked k (K + 1 if none is), clear[p][side] = delta * (double)max(m - 1, 0).
+ *
+ * The draw, binary64 with one rounding per operation.  G = env_base + env, k = the env's episode counter, c = cars_per_env; splitmix64
+ * and u01 are those of spawn_mode 1 and FTGP_POLICY_RANDOM; mul32(h, n) = ((h >> 32) * (uint64_t)n) >> 32.  start[] = the points
+ * (first_point + i) % 100, i in [0, n_points), in this order, whose clear is >= margin on both sides; n_start their number.
+ *   1. hE = splitmix64(splitmix64(seed ^ (0x5350574E52554C45 + (uint64_t)G)) ^ (uint64_t)k)
+ *   2. b = start[mul32(hE, n_start)]
+ *   3. slot[i] = i; with shuffle_grid: h = hE; for i = c-1 .. 1: h = splitmix64(h), j = mul32(h, i+1), swap slot[i] and slot[j]
+ *   4. car a: p = (b + 2*slot[a]) % 100 (custom.py:1112's spacing); hC = splitmix64(hE ^ (0xD6E8FEB86659FD93 * (uint64_t)(a+1)));
+ *      w = 2.0*u01(hC) - 1.0; v = 2.0*u01(splitmix64(hC)) - 1.0
+ *   5. side = w >= 0 ? left : right; room = max(clear[p][side] - margin, 0.0); lat = (lateral_frac*w)*room;
+ *      x = X_p + lat*(-sh), y = Y_p + lat*ch with ch, sh of the table's quaternion at p
+ *   6. t = yaw_tan*v; n = sqrt(1.0 + t*t), cj = 1.0/n, sj = t/n; nw = qw*cj - qz*sj, nz = qz*cj + qw*sj; m = sqrt(nw*nw + nz*nz);
+ *      qw' = nw/m, qz' = nz/m -- for t != 0; t == 0 (yaw_tan 0) leaves the table's (qw, qz) as they are, so that a rule without
+ *      jitter on one point reproduces spawn_mode 0 to the bit (m is 1 only to within an ulp)
+ *   7. offset = the first index of the smallest dx*dx + dy*dy over the 100 path points at (x, y), the progress block's arithmetic;
+ *      the progress block then runs as at any reset: completion 0 and good_start 1 whatever the offset drawn.
+ * Everything else of a reset is unchanged (velocities, controls and ranges 0, steps 0, lap times cleared).  A grid mate whose point is
+ * blocked gets room 0: no lateral offset.  The rule promises no contact-free start; the contact row after the reset says.
+ * With the rule on, every reset of env e spawns with k = episodes[e] and then sets episodes[e] = k + 1; with the rule off the counters
+ * are not touched.  A shard [env_base, env_base + n) of a larger batch draws exactly what the same slice of the whole batch draws.
+ *
+ * ftgp_set_spawn_rule: NULL = off; valid on any handle; it may synchronise.  FTGP_ERR_ARG, before anything changes: first_point
+ * outside 0..99, n_points outside 1..100, reserved != 0, a margin or yaw_tan that is negative, NaN or infinite, a lateral_frac
+ * outside [0, 1], or a track without a start point left (the message names the track's index).  Every accepted call, NULL included,
+ * zeroes the episode counters.  ftgp_device_io_config, ftgp_device_io_signals and ftgp_device_io_contacts leave the rule alone.
+ */
+typedef struct FtgpSpawnRule {
+    int32_t first_point, n_points;  /* candidates (first_point + i) % 100, i in [0, n_points); 0..99 and 1..100 */
+    int32_t shuffle_grid;           /* non-zero: the cars of an env draw their grid slots */
+    int32_t reserved;               /* 0 */
+    double  margin;                 /* >= 0, finite: a candidate with clear < margin on either side is no start point;
+                                       lateral room on a side = max(clear - margin, 0) */
+    double  lateral_frac;           /* in [0, 1]: share of that room the offset may use */
+    double  yaw_tan;                /* >= 0, finite: tan of half the largest yaw offset */
+} FtgpSpawnRule;
+int ftgp_set_spawn_rule(FtgpEnv *env, const FtgpSpawnRule *rule);
+
+/* int64[n_envs]: resets of every env since the rule was set (all zeros without a rule). */
+int ftgp_get_episodes(FtgpEnv *env, int64_t *out);
+
+/* double[FTGP_PATH_POINTS][6] of track `track` (0 .. n_tracks - 1): x, y, qw, qz of the spawn table, clear_left, clear_right; any handle,
+ * with or without a rule.  FTGP_ERR_ARG for a track out of range. */
+int ftgp_get_start_table(FtgpEnv *env, int track, double *out);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).

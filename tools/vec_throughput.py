@@ -1,13 +1,16 @@
 """Env-steps/s of the device I/O loop (DeviceVecEnv.step on torch tensors) against the host loop (set_ctrl + step + get_lidar).
 
     python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track] [--rows device,torch_pool,signals,contacts,host] [--repeats 1,4] [--cars 1]
+                                   [--max-episode-steps 3000] [--random-start]
 
 Device loop: constant actions, and random torch actions drawn before every call, at action_repeat 1 and 4; per-call time from HIP
 events on torch's stream around the timed calls.  Pooled observations (action_repeat 1, constant actions, beams of --pool rays clipped
 at --max-range and scaled): "torch_pool" = the raw scan plus the torch ops a user would write (-1 -> M, clamp, reshape(...).amin(-1),
 scale), "signals" = the same from the library (scan_pool, scan_max_range, state=True: ftgp_io_finish_signals_kernel), "contacts" = the
 signals row with contact rows, both contact terminations and both penalties on top (ftgp_io_contact_kernel between the step and the
-finish kernel).  --cars: cars per env, every one an agent.  Host loop: per
+finish kernel).  --cars: cars per env, every one an agent.  --random-start: the device rows run under a spawn rule (ftgp_set_spawn_rule:
+lateral share 0.8, yaw offsets up to 0.2 rad, shuffled grid); with a small --max-episode-steps the auto-reset, and with it the draw, runs often.
+Host loop: per
 step set_ctrl (one copy + synchronisation), step(1), get_lidar (the whole scan back).  One JSON line per row, then a summary line.  Run it in a fresh process: torch is imported first
 (ft_grandprix_amd/vec.py).  Under `rocprofv3 --kernel-trace --stats -- python tools/vec_throughput.py` the per-kernel times of a call
 (ftgp_io_ingest_kernel, ftgp_step_kernel, ftgp_io_contact_kernel, ftgp_io_finish_kernel / ftgp_io_finish_signals_kernel) come out of
@@ -36,7 +39,10 @@ def device_row(track, a, repeat, actions, pooled=None):
     kw = dict(scan_pool=a.pool, scan_max_range=a.max_range, state=True) if pooled in ("signals", "contacts") else {}
     if pooled == "contacts":
         kw.update(contacts=True, terminate_on_wall_contact=True, terminate_on_car_contact=True, wall_contact_penalty=1.0, car_contact_penalty=0.5)
-    venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, cars_per_env=a.cars, max_episode_steps=3000, action_repeat=repeat, spawn_mode=1, seed=7, **kw)
+    if a.random_start:
+        kw.update(random_start=True, start_lateral=0.8, start_yaw_jitter=0.2, shuffle_grid=True)
+    venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, cars_per_env=a.cars, max_episode_steps=a.max_episode_steps, action_repeat=repeat, spawn_mode=1,
+                        seed=7, **kw)
     dev = venv.device
     M, inv = float(a.max_range), 1.0 / float(a.max_range)
 
@@ -70,9 +76,13 @@ def device_row(track, a, repeat, actions, pooled=None):
     wall = time.perf_counter() - w0
     ms = t0.elapsed_time(t1)
     step_ms = venv.env.last_kernel_ms()
+    episodes = int(venv.episode_index().sum()) if a.random_start else None
     venv.close()
     loop = {None: "device", "torch": "device+torch_pool", "signals": "device+signals", "contacts": "device+signals+contacts"}[pooled]
     extra = {} if pooled is None else {"pool": a.pool, "max_range": a.max_range}
+    extra["max_episode_steps"] = a.max_episode_steps
+    if a.random_start:
+        extra.update(random_start=True, resets=episodes)
     return {"loop": loop, "actions": actions, "action_repeat": repeat, "envs": a.envs, "cars": a.cars, "rays": a.rays, "calls": a.calls, **extra,
             "us_per_call": 1e3 * ms / a.calls, "host_us_per_call": 1e6 * wall / a.calls, "step_kernel_us_last_call": 1e3 * step_ms,
             "env_steps_per_s": a.envs * repeat * a.calls / (ms * 1e-3)}
@@ -106,6 +116,8 @@ def main():
     ap.add_argument("--max-range", type=float, default=10.0)
     ap.add_argument("--repeats", default="1,4", help="action_repeat of the device rows, comma-separated")
     ap.add_argument("--cars", type=int, default=1, help="cars per env, every one an agent")
+    ap.add_argument("--max-episode-steps", type=int, default=3000, help="truncation of the device rows")
+    ap.add_argument("--random-start", action="store_true", help="the device rows run under a spawn rule")
     ap.add_argument("--rows", default="device,torch_pool,signals,host", help="comma-separated: device, torch_pool, signals, contacts, host")
     a = ap.parse_args()
     want = set(a.rows.split(","))
