@@ -24,6 +24,8 @@ PROGRESS_INTS = 10
 METRIC_DOUBLES = 8
 STATE_FLOATS = 8            # FTGP_STATE_FLOATS: a state row of the device step (STATE_FIELDS)
 CONTACT_FLOATS = 4          # FTGP_CONTACT_FLOATS: a contact row (CONTACT_FIELDS)
+FRAME_FIXED = 4              # FTGP_FRAME_FIXED: the fixed entries of a frame row (FRAME_FIELDS); 2 floats per look-ahead point follow
+MAX_LOOKAHEAD = 16           # FTGP_MAX_LOOKAHEAD
 MAX_TRACKS = 16             # FTGP_MAX_TRACKS: tracks of one multi-track handle (ftgp_create_tracks)
 
 POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2, 3, 4
@@ -37,6 +39,7 @@ PROGRESS_FIELDS = ("laps", "completion", "lap_completion", "absolute_completion"
                    "off_track", "start", "good_start", "delta", "finish_step")
 STATE_FIELDS = ("v_long", "v_lat", "wz", "u_speed", "u_steer", "centre_dist", "lap_completion", "off_track")
 CONTACT_FIELDS = ("wall_pen", "car_pen", "wall_count", "car_count")
+FRAME_FIELDS = ("lat", "cos_h", "sin_h", "s_norm")
 METRIC_FIELDS = ("steps", "n_cars", "sum_laps", "sum_absolute_completion", "n_finished",
                  "n_off_track", "min_lap_time", "max_lap_time")
 
@@ -85,6 +88,7 @@ API_SYMBOLS = (
     "device_io_signals", "step_device_ex", "state_device", "get_centre_dist2",
     "device_io_contacts", "step_device_contacts", "contacts_device", "get_contacts",
     "set_spawn_rule", "get_episodes", "get_start_table",
+    "device_io_frame", "step_device_frame", "frame_device", "get_frames",
 )
 
 
@@ -113,6 +117,14 @@ class FtgpDeviceContacts(C.Structure):
 
 class FtgpDeviceStepContacts(C.Structure):
     _fields_ = [("contact", C.c_void_p), ("final_contact", C.c_void_p)]
+
+
+class FtgpDeviceFrame(C.Structure):
+    _fields_ = [("n_ahead", C.c_int32), ("stride", C.c_int32), ("dense_progress", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FtgpDeviceStepFrame(C.Structure):
+    _fields_ = [("frame", C.c_void_p), ("final_frame", C.c_void_p)]
 
 
 class FtgpSpawnRule(C.Structure):
@@ -196,6 +208,11 @@ class CLib:
             "step_device_contacts": (i32, [vp, C.POINTER(FtgpDeviceStep), C.POINTER(FtgpDeviceStepExtra), C.POINTER(FtgpDeviceStepContacts)]),
             "contacts_device": (i32, [vp, vp, vp]),
             "get_contacts": (i32, [vp, dp]),
+            "device_io_frame": (i32, [vp, C.POINTER(FtgpDeviceFrame)]),
+            "step_device_frame": (i32, [vp, C.POINTER(FtgpDeviceStep), C.POINTER(FtgpDeviceStepExtra), C.POINTER(FtgpDeviceStepContacts),
+                                        C.POINTER(FtgpDeviceStepFrame)]),
+            "frame_device": (i32, [vp, vp, vp]),
+            "get_frames": (i32, [vp, i32, i32, dp]),
             "set_spawn_rule": (i32, [vp, C.POINTER(FtgpSpawnRule)]),
             "get_episodes": (i32, [vp, dp]),
             "get_start_table": (i32, [vp, i32, dp]),
@@ -412,6 +429,16 @@ class Env:
         c = FtgpDeviceContacts(int(bool(terminate_on_wall)), int(bool(terminate_on_car)), float(wall_penalty), float(car_penalty))
         self._call("device_io_contacts", C.byref(c))
 
+    def device_io_frame(self, on: bool = True, n_ahead: int = 0, stride: int = 1, dense_progress: bool = False):
+        """ftgp_device_io_frame (after ``device_io_config``, which turns the frame off): a track-frame row per car in every device step
+        (FRAME_FIELDS, then ``n_ahead`` look-ahead points ``stride`` path points apart, body frame), and with ``dense_progress`` the
+        change of the continuous lap position as the reward; ``on=False`` turns it off again."""
+        if not on:
+            self._call("device_io_frame", None)
+            return
+        f = FtgpDeviceFrame(int(n_ahead), int(stride), int(bool(dense_progress)), 0)
+        self._call("device_io_frame", C.byref(f))
+
     # -- spawn rule (include/ftgp.h: ftgp_set_spawn_rule)
     def set_spawn_rule(self, on: bool = True, first_point: int = 0, n_points: int = PATH_POINTS, margin: float = 0.0,
                        lateral_frac: float = 0.0, yaw_tan: float = 0.0, shuffle_grid: bool = False):
@@ -455,6 +482,19 @@ class Env:
         else:
             self._call("step_device", C.byref(io))
 
+    def step_device_frame(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0,
+                          state: int = 0, final_state: int = 0, contact: int = 0, final_contact: int = 0, frame: int = 0,
+                          final_frame: int = 0):
+        """One ftgp_step_device_frame call on integer device addresses, like ``step_device``; ``frame`` / ``final_frame``: float32
+        [n_envs, n_ext, FRAME_FIXED + 2 * n_ahead], either may be 0."""
+        io = FtgpDeviceStep(stream or None, action or None, obs or None, reward or None, terminated or None, truncated or None,
+                            final_obs or None)
+        extra = FtgpDeviceStepExtra(state or None, final_state or None) if state or final_state else None
+        con = FtgpDeviceStepContacts(contact or None, final_contact or None) if contact or final_contact else None
+        fr = FtgpDeviceStepFrame(frame or None, final_frame or None) if frame or final_frame else None
+        self._call("step_device_frame", C.byref(io), None if extra is None else C.byref(extra), None if con is None else C.byref(con),
+                   None if fr is None else C.byref(fr))
+
     def state_device(self, state: int, stream: int = 0):
         """ftgp_state_device: the state rows of the current state into device memory at ``state``, ordered on ``stream``; only enqueues."""
         self._call("state_device", stream or None, state or None)
@@ -464,7 +504,22 @@ class Env:
         ``stream``; only enqueues."""
         self._call("contacts_device", stream or None, contact or None)
 
+    def frame_device(self, frame: int, stream: int = 0):
+        """ftgp_frame_device: the external cars' frame rows at the current state into device memory at ``frame``, ordered on
+        ``stream``; only enqueues."""
+        self._call("frame_device", stream or None, frame or None)
+
     # -- read-backs
+    def get_frames(self, n_ahead: int = 0, stride: int = 1) -> np.ndarray:
+        """float32 [n_cars, FRAME_FIXED + 2 * n_ahead] (FRAME_FIELDS, then the look-ahead points): the frame row of every car at the
+        current state (ftgp_get_frames)."""
+        n_ahead = int(n_ahead)
+        if not 0 <= n_ahead <= MAX_LOOKAHEAD:
+            raise ValueError(f"n_ahead: 0 .. {MAX_LOOKAHEAD}, got {n_ahead}")
+        out = np.empty((self.n_cars, FRAME_FIXED + 2 * n_ahead), dtype=np.float32)
+        self._call("get_frames", n_ahead, int(stride), _ptr(out))
+        return out
+
     def contacts(self) -> np.ndarray:
         """float32 [n_cars, 4] (CONTACT_FIELDS): the contact row of every car at the current state (ftgp_get_contacts)."""
         out = np.empty((self.n_cars, CONTACT_FLOATS), dtype=np.float32)

@@ -167,6 +167,13 @@ struct FtgpEnv {
     bool con_on = false;              // ftgp_device_io_contacts: a call evaluates the contact rows and goes through ftgp_io_finish_signals_kernel
     FtgpDeviceContacts con{};         // the contact rules while con_on
     DevBuf<float> d_contact;          // [n_cars][FTGP_CONTACT_FLOATS] every car's contact row, allocated on first use
+    bool frame_on = false;            // ftgp_device_io_frame: a call evaluates the frame rows and goes through ftgp_io_finish_signals_kernel
+    FtgpDeviceFrame frame{};          // n_ahead, stride and the reward rule while frame_on
+    DevBuf<float> d_frame;            // [n_cars][FTGP_FRAME_FIXED + 2 * FTGP_MAX_LOOKAHEAD] floats, rows packed at the width in use; allocated on first use.
+                                      // Scratch of one call: ftgp_get_frames packs rows of ITS width in here too, which is safe only because every device
+                                      // step rewrites the buffer on the handle's stream before its finish kernel reads it -- nothing may be kept in it across calls
+    DevBuf<double> d_frame_s;         // [2][n_cars] s before and after a call's steps (dense progress)
+    DevBuf<int32_t> d_frame_flag;     // [2][n_cars] the flags that go with them
     // spawn rule (ftgp_set_spawn_rule)
     std::vector<double> start_table;  // [n_tracks][FTGP_PATH_POINTS][6] x, y, qw, qz, clear_left, clear_right: the plan's (ftgp_get_start_table)
     const FtgpSpawnDev* rule = nullptr;      // what the reset paths are handed: d_rule while a rule is set, null without one
@@ -944,6 +951,32 @@ int ensure_contact_rows(FtgpEnv* e)
     return 0;
 }
 
+// ftgp_io_frame_kernel on the handle's stream: every car's row to `rows` and / or the external cars' rows to `ext_out`, s and the
+// flags to slot `slot` of d_frame_s / d_frame_flag (-1: nowhere)
+int launch_frame(FtgpEnv* e, int n_ahead, int stride, float* rows, float* ext_out, int slot)
+{
+    DeviceFrameArgs F{};
+    F.env_track = e->d_env_track.get();
+    F.rows = rows; F.ext_out = ext_out;
+    F.s_out = slot >= 0 ? e->d_frame_s.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
+    F.flag_out = slot >= 0 ? e->d_frame_flag.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
+    F.n_ext = e->io.n_ext; F.n_ahead = n_ahead; F.stride = stride;
+    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) F.ext_index[k] = e->io_ready ? e->io.ext_index[k] : -1;
+    const unsigned blocks = (unsigned)(((size_t)e->P.n_cars * FTGP_FRAME_LANES + FTGP_FRAME_THREADS - 1) / FTGP_FRAME_THREADS);
+    hipLaunchKernelGGL(ftgp_io_frame_kernel, dim3(blocks), dim3(FTGP_FRAME_THREADS), 0, e->stream.get(), e->P, F);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ensure_frame_rows(FtgpEnv* e)
+{
+    const size_t n_cars = (size_t)e->P.n_cars;
+    if (!e->d_frame) HIP_TRY(dev_alloc(e->d_frame, sizeof(float) * (FTGP_FRAME_FIXED + 2 * FTGP_MAX_LOOKAHEAD) * n_cars));
+    if (!e->d_frame_s) HIP_TRY(dev_alloc(e->d_frame_s, sizeof(double) * 2 * n_cars));
+    if (!e->d_frame_flag) HIP_TRY(dev_alloc(e->d_frame_flag, sizeof(int32_t) * 2 * n_cars));
+    return 0;
+}
+
 // ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images
 int upload(FtgpEnv* e, const Plan& pl, const Switches& sw)
 {
@@ -1286,6 +1319,22 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
     e->io_ready = true;
     set_signals(e, FtgpDeviceSignals{ 1, 0.0f, 0, 0.0f });
     e->con_on = false;
+    e->frame_on = false;
+    return 0;
+}
+
+int ftgp_device_io_frame(FtgpEnv* e, const FtgpDeviceFrame* frame)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_frame before ftgp_device_io_config%s");
+    if (!frame) { e->frame_on = false; return 0; }
+    if (frame->n_ahead < 0 || frame->n_ahead > FTGP_MAX_LOOKAHEAD) return fail(FTGP_ERR_ARG, "device_io_frame: n_ahead in 0 .. 16%s");
+    if (frame->stride < 1 || frame->stride > FTGP_PATH_POINTS / 2) return fail(FTGP_ERR_ARG, "device_io_frame: stride in 1 .. 50%s");
+    if (frame->reserved != 0) return fail(FTGP_ERR_ARG, "device_io_frame: reserved must be 0%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = ensure_frame_rows(e)) return rc;
+    e->frame = *frame;
+    e->frame_on = true;
     return 0;
 }
 
@@ -1317,20 +1366,29 @@ int ftgp_device_io_signals(FtgpEnv* e, const FtgpDeviceSignals* signals)
 
 int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io) { return ftgp_step_device_ex(e, io, nullptr); }
 
-int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra) { return ftgp_step_device_contacts(e, io, extra, nullptr); }
+int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra) { return ftgp_step_device_frame(e, io, extra, nullptr, nullptr); }
 
 int ftgp_step_device_contacts(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts)
+{
+    return ftgp_step_device_frame(e, io, extra, contacts, nullptr);
+}
+
+int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts,
+                           const FtgpDeviceStepFrame* frame)
 {
     if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
     if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
     float* contact = contacts ? contacts->contact : nullptr;
     float* final_contact = contacts ? contacts->final_contact : nullptr;
     if ((contact || final_contact) && !e->con_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_contacts: contact buffers while contacts are off (ftgp_device_io_contacts)%s");
+    float* frame_out = frame ? frame->frame : nullptr;
+    float* final_frame = frame ? frame->final_frame : nullptr;
+    if ((frame_out || final_frame) && !e->frame_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_frame: frame buffers while the frame is off (ftgp_device_io_frame)%s");
     HIP_TRY(hipSetDevice(e->device));
     DeviceIoArgs A = e->io;
     DeviceSignalArgs S = e->sig;
     S.state = extra ? extra->state : nullptr; S.final_state = extra ? extra->final_state : nullptr;
-    const bool signals = !e->sig_default || S.state || S.final_state || e->con_on;
+    const bool signals = !e->sig_default || S.state || S.final_state || e->con_on || e->frame_on;
     const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
     if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
     if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
@@ -1342,6 +1400,19 @@ int ftgp_step_device_contacts(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDe
     if (S.final_state) if (int rc = check_device_buffer(e, S.final_state, sizeof(float) * FTGP_STATE_FLOATS * rows, "final_state")) return rc;
     if (contact) if (int rc = check_device_buffer(e, contact, sizeof(float) * FTGP_CONTACT_FLOATS * rows, "contact")) return rc;
     if (final_contact) if (int rc = check_device_buffer(e, final_contact, sizeof(float) * FTGP_CONTACT_FLOATS * rows, "final_contact")) return rc;
+    const bool dense = e->frame_on && e->frame.dense_progress != 0;
+    if (e->frame_on) {
+        const size_t frame_bytes = sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * e->frame.n_ahead) * rows;
+        if (frame_out) if (int rc = check_device_buffer(e, frame_out, frame_bytes, "frame")) return rc;
+        if (final_frame) if (int rc = check_device_buffer(e, final_frame, frame_bytes, "final_frame")) return rc;
+        const size_t n_cars = (size_t)e->P.n_cars;
+        S.frame_rows = e->d_frame.get(); S.frame = frame_out; S.final_frame = final_frame;
+        S.frame_ahead = e->frame.n_ahead; S.frame_stride = e->frame.stride;
+        if (dense) {
+            S.frame_s0 = e->d_frame_s.get(); S.frame_s1 = e->d_frame_s.get() + n_cars;
+            S.frame_flag0 = e->d_frame_flag.get(); S.frame_flag1 = e->d_frame_flag.get() + n_cars;
+        }
+    }
     if (e->con_on) {
         S.contact_rows = e->d_contact.get(); S.contact = contact; S.final_contact = final_contact;
         S.terminate_on_wall = e->con.terminate_on_wall ? 1 : 0; S.terminate_on_car = e->con.terminate_on_car ? 1 : 0;
@@ -1355,8 +1426,10 @@ int ftgp_step_device_contacts(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDe
     const unsigned car_blocks = (unsigned)((e->P.n_cars + 255) / 256);
     hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
+    if (dense) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 0)) return rc;          // s0: the pose the call begins with
     if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, e->io_repeat, true)) return rc;
     if (e->con_on) if (int rc = launch_contacts(e, e->d_contact.get(), nullptr)) return rc;
+    if (e->frame_on) if (int rc = launch_frame(e, e->frame.n_ahead, e->frame.stride, e->d_frame.get(), nullptr, 1)) return rc;
     if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, e->rule);
     else {
         const bool aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
@@ -1398,6 +1471,22 @@ int ftgp_contacts_device(FtgpEnv* e, void* stream, float* contact)
     HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
     HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
     if (int rc = launch_contacts(e, nullptr, contact)) return rc;
+    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
+    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
+    return 0;
+}
+
+int ftgp_frame_device(FtgpEnv* e, void* stream, float* frame)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_frame_device before ftgp_device_io_config%s");
+    const int n_ahead = e->frame_on ? e->frame.n_ahead : 0, stride = e->frame_on ? e->frame.stride : 1;
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = check_device_buffer(e, frame, sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead) * (size_t)e->P.n_envs * (size_t)e->io.n_ext, "frame")) return rc;
+    hipStream_t caller = (hipStream_t)stream;
+    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
+    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
+    if (int rc = launch_frame(e, n_ahead, stride, nullptr, frame, -1)) return rc;
     HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
     HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
     return 0;
@@ -1473,6 +1562,19 @@ int ftgp_get_contacts(FtgpEnv* e, float* out)
     if (int rc = ensure_contact_rows(e)) return rc;
     if (int rc = launch_contacts(e, e->d_contact.get(), nullptr)) return rc;
     HIP_TRY(hipMemcpyAsync(out, e->d_contact.get(), sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    return 0;
+}
+
+int ftgp_get_frames(FtgpEnv* e, int n_ahead, int stride, float* out)
+{
+    if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    if (n_ahead < 0 || n_ahead > FTGP_MAX_LOOKAHEAD) return fail(FTGP_ERR_ARG, "ftgp_get_frames: n_ahead in 0 .. 16%s");
+    if (stride < 1 || stride > FTGP_PATH_POINTS / 2) return fail(FTGP_ERR_ARG, "ftgp_get_frames: stride in 1 .. 50%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = ensure_frame_rows(e)) return rc;
+    if (int rc = launch_frame(e, n_ahead, stride, e->d_frame.get(), nullptr, -1)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->d_frame.get(), sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead) * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }

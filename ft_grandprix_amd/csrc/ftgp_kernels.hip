@@ -1921,7 +1921,8 @@ __global__ void ftgp_set_pose_kernel(DeviceParams P, const double* __restrict__ 
 // =============================================================================================
 // Device I/O (ftgp_step_device): the caller's actions in, observations / rewards / episode ends out, all in device memory.
 // A call is: ftgp_io_ingest_kernel -> ftgp_step_kernel<.., ROSTER> (action_repeat steps) -> ftgp_io_finish_kernel; with contacts on,
-// ftgp_io_contact_kernel runs between the steps and the finish kernel.
+// ftgp_io_contact_kernel runs between the steps and the finish kernel; with the frame on, so does ftgp_io_frame_kernel, and with the dense
+// reward it also runs behind the ingest kernel, at the pose the call begins with.
 // =============================================================================================
 struct DeviceIoArgs {
     const float* action;          // [n_envs][n_ext][2] (speed, steering_angle)
@@ -2039,6 +2040,15 @@ struct DeviceSignalArgs {
     float* final_contact;         // [n_envs][n_ext][FTGP_CONTACT_FLOATS] or null
     int32_t terminate_on_wall, terminate_on_car;
     float wall_penalty, car_penalty;
+    // track frame (ftgp_device_io_frame): filled in per call
+    const float* frame_rows;      // [n_cars][frame_width] this call's rows (ftgp_io_frame_kernel), null = the frame is off
+    float* frame;                 // [n_envs][n_ext][frame_width] or null
+    float* final_frame;           // [n_envs][n_ext][frame_width] or null
+    const double* frame_s0;       // [n_cars] s at the pose the call began with; null = the integer reward
+    const double* frame_s1;       // [n_cars] s at the pose after the steps
+    const int32_t* frame_flag0;   // [n_cars] FTGP_FRAME_OFF | FTGP_FRAME_FINISHED when the call began
+    const int32_t* frame_flag1;   // [n_cars] ... after the steps
+    int32_t frame_ahead, frame_stride;
 };
 
 // a range as it enters the minimum: no hit (< 0) = the limit, a hit = min(r, limit)
@@ -2221,10 +2231,164 @@ __global__ void __launch_bounds__(FTGP_CONTACT_THREADS) ftgp_io_contact_kernel(D
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Track frame (ftgp_device_io_frame / ftgp_step_device_frame / ftgp_frame_device / ftgp_get_frames): the frame row of include/ftgp.h --
+// the pose projected on the env's centre-line, the track's tangent in the body frame, the lap position, look-ahead points.
+// ---------------------------------------------------------------------------------------------
+#define FTGP_FRAME_OFF 1                  // flag bits kept per car beside s: d_c > 1.0 at the pose; the car had finished
+#define FTGP_FRAME_FINISHED 2
+struct DeviceFrameArgs {
+    const int32_t* env_track;             // the track of every env; null with one track
+    float* rows;                          // [n_cars][FTGP_FRAME_FIXED + 2 * n_ahead]: every car's row, or null
+    float* ext_out;                       // [n_envs][n_ext][FTGP_FRAME_FIXED + 2 * n_ahead]: the external cars' rows, or null
+    double* s_out;                        // [n_cars]: the unrounded s, or null
+    int32_t* flag_out;                    // [n_cars]: FTGP_FRAME_OFF | FTGP_FRAME_FINISHED, or null
+    int32_t n_ext, n_ahead, stride, pad;
+    int32_t ext_index[FTGP_PAIR_STRIDE];  // as DeviceIoArgs (read with ext_out only)
+};
+
+// step 2 of the row: the pose projected on segment a -> a + 1
+struct FrameSeg { double ex, ey, L2, rx, ry, t, g2; };
+__device__ __forceinline__ FrameSeg frame_segment(const double* __restrict__ path, int a, double x, double y)
+{
+    const int b = a + 1 < FTGP_PATH_POINTS ? a + 1 : 0;
+    const double xa = path[2 * a], ya = path[2 * a + 1];
+    FrameSeg g;
+    g.ex = path[2 * b] - xa; g.ey = path[2 * b + 1] - ya;
+    g.L2 = g.ex * g.ex + g.ey * g.ey;
+    g.rx = x - xa; g.ry = y - ya;
+    if (g.L2 == 0.0) { g.ex = 1.0; g.ey = 0.0; g.L2 = 1.0; g.t = 0.0; }
+    else {
+        const double t = (g.rx * g.ex + g.ry * g.ey) / g.L2;
+        g.t = t < 0.0 ? 0.0 : t > 1.0 ? 1.0 : t;
+    }
+    const double fx = xa + g.t * g.ex, fy = ya + g.t * g.ey;
+    const double gx = x - fx, gy = y - fy;
+    g.g2 = gx * gx + gy * gy;
+    return g;
+}
+
+// step 5: the fixed entries of the segment taken; s comes back unrounded
+__device__ __forceinline__ float4 frame_fixed(const FrameSeg& g, int a, double ch, double sh, double& s_out)
+{
+    const double len = sqrt(g.L2);
+    double s = (double)a + g.t;
+    if (s >= 100.0) s = s - 100.0;
+    s_out = s;
+    return make_float4((float)((g.ex * g.ry - g.ey * g.rx) / len), (float)((g.ex * ch + g.ey * sh) / len), (float)((g.ey * ch - g.ex * sh) / len),
+                       (float)(s / 100.0));
+}
+
+// step 6: look-ahead point k behind segment a
+__device__ __forceinline__ float2 frame_ahead(const double* __restrict__ path, int a, int k, int stride, double x, double y, double ch, double sh)
+{
+    const int q = (a + 1 + k * stride) % FTGP_PATH_POINTS;
+    const double dx = path[2 * q] - x, dy = path[2 * q + 1] - y;
+    return make_float2((float)(dx * ch + dy * sh), (float)(dy * ch - dx * sh));
+}
+
+// The whole row by one lane (ftgp_io_finish_signals_kernel, the spawn pose of an env it has just reset): the operations of
+// ftgp_io_frame_kernel on the same values, the search as the progress block runs it.
+__device__ __forceinline__ void frame_row_lane(const double* __restrict__ path, const CarCore& a, int n_ahead, int stride, float* __restrict__ o)
+{
+    const double x = a.x, y = a.y;
+    double best = 0.0; int c = 0;
+    #pragma unroll 1
+    for (int i = 0; i < FTGP_PATH_POINTS; ++i) {
+        const double dx = path[2 * i] - x, dy = path[2 * i + 1] - y;
+        const double d = dx * dx + dy * dy;
+        if (i == 0 || d < best) { best = d; c = i; }
+    }
+    const int pa = c > 0 ? c - 1 : FTGP_PATH_POINTS - 1;
+    FrameSeg g = frame_segment(path, c, x, y);
+    int seg = c;
+    {
+        const FrameSeg ga = frame_segment(path, pa, x, y);
+        if (ga.g2 < g.g2) { g = ga; seg = pa; }
+    }
+    const double ch = a.qw * a.qw - a.qz * a.qz, sh = 2.0 * (a.qw * a.qz);
+    double s;
+    const float4 f = frame_fixed(g, seg, ch, sh, s);
+    o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = f.w;
+    #pragma unroll 1
+    for (int k = 0; k < n_ahead; ++k) {
+        const float2 p = frame_ahead(path, seg, k, stride, x, y, ch, sh);
+        o[FTGP_FRAME_FIXED + 2 * k] = p.x; o[FTGP_FRAME_FIXED + 2 * k + 1] = p.y;
+    }
+}
+
+// Sixteen lanes per car, one DPP row; a wave holds four cars, a workgroup sixteen.  Lane l walks points l, l + 16, ... and keeps its
+// first minimum; the row folds the pair (d, index) with xor-shuffles 1, 2, 4, 8 -- the smaller d wins, on equal d the smaller index, so
+// every lane ends with the progress block's first minimum.  (A NaN never wins.  With a NaN pose every d is NaN and each lane keeps its
+// own (NaN, l): lane 0 has c = 0 as the progress block does, the other lanes of the row disagree with it, every index stays in 0 .. 99
+// and every entry of the row is NaN whichever segment a lane took.)  Lanes 0 and 1 project
+// on segment B = c -> c + 1 and A = c - 1 -> c, one shuffle hands A's g2 to lane 0, which takes A only if it is strictly nearer and
+// writes the fixed entries, s and the flags; lanes 0 .. n_ahead - 1 write one look-ahead pair each.  No LDS, no atomics.
+#define FTGP_FRAME_LANES 16
+#define FTGP_FRAME_THREADS 256
+__global__ void __launch_bounds__(FTGP_FRAME_THREADS) ftgp_io_frame_kernel(DeviceParams P, DeviceFrameArgs F)
+{
+    // (the car from the block's first car, not from a global lane number: that one would pass 2^31 at 134 M cars)
+    const int ci = blockIdx.x * (FTGP_FRAME_THREADS / FTGP_FRAME_LANES) + threadIdx.x / FTGP_FRAME_LANES, l = threadIdx.x % FTGP_FRAME_LANES;
+    const bool live = ci < P.n_cars;
+    const int cpe = P.cars_per_env;
+    const int env = live ? ci / cpe : 0, slot = live ? ci - env * cpe : 0;
+    const double* path = P.path + (size_t)env_track_of(F.env_track, env) * 2 * FTGP_PATH_POINTS;
+    double x = 0.0, y = 0.0, qw = 1.0, qz = 0.0;
+    int fin = 0;
+    double best = INFINITY; int idx = l;      // a lane past n_cars takes part in the shuffles with these
+    if (live) {
+        const CarCore* me = P.cars + ci;
+        x = me->x; y = me->y; qw = me->qw; qz = me->qz; fin = me->finished;
+        #pragma unroll 1
+        for (int i = l; i < FTGP_PATH_POINTS; i += FTGP_FRAME_LANES) {
+            const double dx = path[2 * i] - x, dy = path[2 * i + 1] - y;
+            const double d = dx * dx + dy * dy;
+            if (i == l || d < best) { best = d; idx = i; }
+        }
+    }
+    // every lane of the wave is here: xor 1, 2, 4, 8 stay inside the row of sixteen
+    for (int m = 1; m < FTGP_FRAME_LANES; m <<= 1) {
+        const double od = shfl_xor_f64(best, m);
+        const int oi = __shfl_xor(idx, m, FTGP_WAVE);
+        if (od < best || (od == best && oi < idx)) { best = od; idx = oi; }
+    }
+    const int c = idx;
+    const int pa = c > 0 ? c - 1 : FTGP_PATH_POINTS - 1;
+    FrameSeg g{};
+    if (live && l < 2) g = frame_segment(path, l == 0 ? c : pa, x, y);
+    const double g2a = shfl_xor_f64(g.g2, 1);                          // lane 0 <- lane 1: segment A's distance
+    int take_a = (live && l == 0 && g2a < g.g2) ? 1 : 0;
+    take_a = __shfl(take_a, (int)(threadIdx.x & (FTGP_WAVE - 1) & ~(FTGP_FRAME_LANES - 1)), FTGP_WAVE);      // the row's lane 0 tells the row
+    if (!live) return;
+    const int seg = take_a ? pa : c;
+    const double ch = qw * qw - qz * qz, sh = 2.0 * (qw * qz);
+    const int width = FTGP_FRAME_FIXED + 2 * F.n_ahead;
+    const int k_ext = F.ext_out ? F.ext_index[slot] : -1;
+    float* ext = k_ext >= 0 ? F.ext_out + ((size_t)env * F.n_ext + k_ext) * width : nullptr;
+    float* row = F.rows ? F.rows + (size_t)ci * width : nullptr;
+    if (l == 0) {
+        if (take_a) g = frame_segment(path, pa, x, y);
+        double s;
+        const float4 f = frame_fixed(g, seg, ch, sh, s);
+        if (row) { row[0] = f.x; row[1] = f.y; row[2] = f.z; row[3] = f.w; }
+        if (ext) { ext[0] = f.x; ext[1] = f.y; ext[2] = f.z; ext[3] = f.w; }
+        if (F.s_out) F.s_out[ci] = s;
+        if (F.flag_out) F.flag_out[ci] = (best > 1.0 ? FTGP_FRAME_OFF : 0) | (fin ? FTGP_FRAME_FINISHED : 0);
+    }
+    if (l < F.n_ahead) {
+        const float2 p = frame_ahead(path, seg, l, F.stride, x, y, ch, sh);
+        if (row) { row[FTGP_FRAME_FIXED + 2 * l] = p.x; row[FTGP_FRAME_FIXED + 2 * l + 1] = p.y; }
+        if (ext) { ext[FTGP_FRAME_FIXED + 2 * l] = p.x; ext[FTGP_FRAME_FIXED + 2 * l + 1] = p.y; }
+    }
+}
+
 // ftgp_io_finish_kernel with signals: one workgroup per env.  The rows of obs / final_obs are pooled (pooled_row); an external car that
 // is off_track pays the penalty and, with terminate_off_track, ends its env; state rows are written from the records after the steps
 // (to final_state for an env that is reset here) and again after the reset.  With contacts on (S.contact_rows, this call's rows of
 // ftgp_io_contact_kernel) the wall and car penalties and episode ends join, and the rows go out like the state rows -- zeros after a reset.
+// With the frame on (S.frame_rows, this call's rows of ftgp_io_frame_kernel) those rows go out the same way, evaluated again at the spawn
+// pose after a reset (frame_row_lane), and with S.frame_s0 the base reward is the dense one.
 __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgpr(72))) ftgp_io_finish_signals_kernel(DeviceParams P, DeviceIoArgs A, DeviceSignalArgs S, const FtgpSpawnDev* __restrict__ rule)
 {
     __shared__ int ended;
@@ -2253,6 +2417,14 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
     if (mine) {
         const CarCore& a = P.cars[ci0 + t];
         float r = (float)(absolute_completion(a) - A.prev_abs[ci0 + t]);
+        if (S.frame_s0) {          // dense progress: the change of s over the call, frozen off the track and for a car that had finished
+            const int f0 = S.frame_flag0[ci0 + t], f1 = S.frame_flag1[ci0 + t];
+            double ds = S.frame_s1[ci0 + t] - S.frame_s0[ci0 + t];
+            if (ds >= 50.0) ds = ds - 100.0;
+            if (ds < -50.0) ds = ds + 100.0;
+            if ((f0 & (FTGP_FRAME_OFF | FTGP_FRAME_FINISHED)) || (f1 & FTGP_FRAME_OFF)) ds = 0.0;
+            r = (float)ds;
+        }
         if (a.off_track) r = r - S.penalty;
         if (S.contact_rows) {
             const float* cr = S.contact_rows + (size_t)(ci0 + t) * FTGP_CONTACT_FLOATS;
@@ -2271,6 +2443,12 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
             float* row = reset ? S.final_contact : S.contact;
             if (row) for (int q = 0; q < FTGP_CONTACT_FLOATS; ++q) row[my_row * FTGP_CONTACT_FLOATS + q] = cr[q];
             if (reset && S.contact) for (int q = 0; q < FTGP_CONTACT_FLOATS; ++q) S.contact[my_row * FTGP_CONTACT_FLOATS + q] = 0.0f;
+        }
+        if (S.frame_rows) {
+            const int width = FTGP_FRAME_FIXED + 2 * S.frame_ahead;
+            const float* fr = S.frame_rows + (size_t)(ci0 + t) * width;
+            float* row = reset ? S.final_frame : S.frame;
+            if (row) for (int q = 0; q < width; ++q) row[my_row * width + q] = fr[q];
         }
     }
     const int R = P.n_rays, NB = S.n_beams;
@@ -2299,6 +2477,9 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
     if (reset && t < cpe) {
         reset_car_in_place(P, ci0 + t, A.env_track, rule, episode);      // (the records were read before the first barrier, and by this lane above)
         if (mine && S.state) state_row(P.cars[ci0 + t], S.state + my_row * FTGP_STATE_FLOATS);
+        if (mine && S.frame_rows && S.frame)      // the frame at the spawn pose: a look-ahead of zeros would be a lie
+            frame_row_lane(P.path + (size_t)env_track_of(A.env_track, env) * 2 * FTGP_PATH_POINTS, P.cars[ci0 + t], S.frame_ahead, S.frame_stride,
+                           S.frame + my_row * (FTGP_FRAME_FIXED + 2 * S.frame_ahead));
         if (t == 0 && rule) rule->episodes[env] = episode + 1;
     }
 }

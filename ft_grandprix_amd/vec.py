@@ -84,6 +84,16 @@ class DeviceVecEnv:
     mate, ``wall_contact_penalty`` / ``car_contact_penalty`` are taken off the reward of an agent in every call that leaves it touching.
     Any of the four implies ``contacts=True``; ``reset()`` zeroes ``contact``.
 
+    Track frame (ftgp_device_io_frame / ftgp_step_device_frame), off by default: ``track_frame=True`` adds info["frame"] /
+    info["final_frame"], float32 [n_envs, n_agents, 4 + 2 * lookahead]: capi.FRAME_FIELDS -- the signed lateral offset from the
+    centre-line (positive = left of the direction of travel), cosine and sine of the track's heading in the car's frame, the continuous
+    lap position s / 100 -- then ``lookahead`` (0 .. 16) centre-line points ahead of the car, ``lookahead_stride`` (1 .. 50) path points
+    apart, as (forward, left) in the car's frame.  ``frame`` holds the rows after the call, for an env that was reset those of its
+    spawn pose; ``final_frame`` the rows before the reset; ``reset()`` fills ``frame``.  ``dense_progress=True`` makes the reward the
+    change of s over the call (in path points, a float) in the place of the integer change of absolute completion: zero while the car
+    is off the track or has finished; the penalties come off it as before.  ``lookahead`` > 0 or ``dense_progress`` implies
+    ``track_frame=True``.
+
     Random starts (ftgp_set_spawn_rule), off by default -- every reset then puts a car back on the pose it had before:
     ``random_start=True`` draws, at every reset of an env (``reset()`` and the auto-reset alike), a start point among the
     ``start_points = (first, count)`` path points (first + i) % 100 that keep ``start_margin`` of wall clearance on both sides (None =
@@ -107,7 +117,8 @@ class DeviceVecEnv:
                  terminate_off_track: bool = False, off_track_penalty: float = 0.0, contacts: bool = False,
                  terminate_on_wall_contact: bool = False, terminate_on_car_contact: bool = False, wall_contact_penalty: float = 0.0,
                  car_contact_penalty: float = 0.0, random_start: bool = False, start_points=(0, 100), start_margin=None,
-                 start_lateral: float = 0.0, start_yaw_jitter: float = 0.0, shuffle_grid: bool = False, **env_kwargs):
+                 start_lateral: float = 0.0, start_yaw_jitter: float = 0.0, shuffle_grid: bool = False, track_frame: bool = False,
+                 lookahead: int = 0, lookahead_stride: int = 1, dense_progress: bool = False, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
@@ -139,6 +150,13 @@ class DeviceVecEnv:
             raise ValueError(f"start_yaw_jitter: radians in [0, pi), got {start_yaw_jitter}")
         self.random_start = bool(random_start) or (first_point, n_points) != (0, capi.PATH_POINTS) or start_margin is not None or \
             start_lateral > 0.0 or start_yaw_jitter > 0.0 or bool(shuffle_grid)
+        lookahead, lookahead_stride = int(lookahead), int(lookahead_stride)
+        if not 0 <= lookahead <= capi.MAX_LOOKAHEAD:
+            raise ValueError(f"lookahead: 0 .. {capi.MAX_LOOKAHEAD} points, got {lookahead}")
+        if not 1 <= lookahead_stride <= capi.PATH_POINTS // 2:
+            raise ValueError(f"lookahead_stride: 1 .. {capi.PATH_POINTS // 2} path points, got {lookahead_stride}")
+        self.lookahead, self.lookahead_stride, self.dense_progress = lookahead, lookahead_stride, bool(dense_progress)
+        self.track_frame = bool(track_frame) or lookahead > 0 or self.dense_progress
         roster = ["agent"] * cars_per_env if roster is None else list(roster)
         if len(roster) != cars_per_env:
             raise ValueError(f"one roster entry per car of an env: expected {cars_per_env}, got {len(roster)}")
@@ -182,6 +200,8 @@ class DeviceVecEnv:
         if self.contacts:
             self.env.device_io_contacts(True, self.terminate_on_wall_contact, self.terminate_on_car_contact, wall_contact_penalty,
                                         car_contact_penalty)
+        if self.track_frame:
+            self.env.device_io_frame(True, lookahead, lookahead_stride, self.dense_progress)
         self.start_rule = None
         if self.random_start:
             if start_margin is None:       # the chassis circles' radius; with bubble_wrap the softeners' sideways reach if that is larger
@@ -220,6 +240,13 @@ class DeviceVecEnv:
             self._con = capi.FtgpDeviceStepContacts(self.contact.data_ptr(), self.final_contact.data_ptr())
             self._con_ref = ctypes.byref(self._con)
             self._step_device_contacts = lib.fn("step_device_contacts")
+        self.frame = self.final_frame = None
+        if self.track_frame:   # ftgp_step_device_frame: a frame row per agent (capi.FRAME_FIELDS, then the look-ahead points)
+            self.frame = torch.zeros((n_envs, self.n_agents, capi.FRAME_FIXED + 2 * lookahead), dtype=torch.float32, **z)
+            self.final_frame = torch.zeros_like(self.frame)
+            self._frame = capi.FtgpDeviceStepFrame(self.frame.data_ptr(), self.final_frame.data_ptr())
+            self._frame_ref = ctypes.byref(self._frame)
+            self._step_device_frame = lib.fn("step_device_frame")
 
     def reset(self):
         """Reset every env (synchronous ftgp_reset, which follows the start rule); obs = the scans right after a reset, all zeros
@@ -231,6 +258,8 @@ class DeviceVecEnv:
                 self.contact.zero_()
         if self.state is not None:
             self.env.state_device(self.state.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        if self.frame is not None:
+            self.env.frame_device(self.frame.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return self.obs
 
     def episode_index(self):
@@ -253,13 +282,15 @@ class DeviceVecEnv:
         self._check_actions(actions)
         self._io.action = actions.data_ptr()
         self._io.stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.state is None and self.contact is None:
+        if self.state is None and self.contact is None and self.frame is None:
             rc = self._step_device(self.env.h, self._io_ref)      # Env.step_device, without rebuilding the argument block
             if rc:
                 self.env.lib.check(rc)
             return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
         extra = None if self.state is None else self._extra_ref
-        if self.contact is None:
+        if self.frame is not None:
+            rc = self._step_device_frame(self.env.h, self._io_ref, extra, None if self.contact is None else self._con_ref, self._frame_ref)
+        elif self.contact is None:
             rc = self._step_device_ex(self.env.h, self._io_ref, extra)
         else:
             rc = self._step_device_contacts(self.env.h, self._io_ref, extra, self._con_ref)
@@ -270,6 +301,8 @@ class DeviceVecEnv:
             info["state"], info["final_state"] = self.state, self.final_state
         if self.contact is not None:
             info["contact"], info["final_contact"] = self.contact, self.final_contact
+        if self.frame is not None:
+            info["frame"], info["final_frame"] = self.frame, self.final_frame
         return self.obs, self.reward, self.terminated, self.truncated, info
 
     def close(self):

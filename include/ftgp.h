@@ -402,6 +402,78 @@ int ftgp_step_device_contacts(FtgpEnv *env, const FtgpDeviceStep *io, const Ftgp
 int ftgp_contacts_device(FtgpEnv *env, void *stream, float *contact);
 
 /*
+ * Track frame of the device step: where the car is on the track, where the track points, and what lies ahead.  State entry 5 is an
+ * unsigned distance to a centre-line POINT and the reward counts whole points; the row below projects the pose on the centre-line
+ * itself.  The reference has none of this; the pieces are its centre-line (the 100 path points) and the nearest-point search of the
+ * progress block (custom.py:1343).
+ *
+ * The frame row of a car, float32[FTGP_FRAME_FIXED + 2*n_ahead], is evaluated at the car's pose (x, y, qw, qz) as it stands, for a
+ * finished car too (it is pure geometry).  All arithmetic is binary64 with one rounding per operation (no contraction; / and sqrt are
+ * IEEE; no atan2, sin or cos).  P[i] = (X_i, Y_i) are the 100 centre-line points of the env's track; indices are taken mod 100, the
+ * path is a closed loop.
+ *   1. Nearest point.  c = the first index of the smallest d_i = dx*dx + dy*dy, dx = X_i - x, dy = Y_i - y (the progress block's
+ *      expression and its first-minimum rule).  off = d_c > 1.0.
+ *   2. Projection on segment a -> a+1.  ex = X_{a+1} - X_a, ey = Y_{a+1} - Y_a, L2 = ex*ex + ey*ey; rx = x - X_a, ry = y - Y_a.
+ *      If L2 == 0 (a duplicated point): ex = 1, ey = 0, L2 = 1 and t = 0.  Otherwise t = (rx*ex + ry*ey) / L2, then t < 0 -> 0,
+ *      t > 1 -> 1.  Foot point fx = X_a + t*ex, fy = Y_a + t*ey; gx = x - fx, gy = y - fy, g2 = gx*gx + gy*gy.
+ *   3. Segment choice.  Step 2 for a = (c + 99) % 100 (segment A) and for a = c (segment B); A is taken only if g2_A < g2_B, otherwise
+ *      B.  Below a, ex, ey, L2, rx, ry, t are those of the segment taken, and len = sqrt(L2).
+ *   4. Heading of the car: ch = qw*qw - qz*qz, sh = 2.0*(qw*qz) (as in the state row).
+ *   5. The fixed entries, each rounded once to binary32:
+ *        0 lat    = (ex*ry - ey*rx) / len      signed lateral offset, positive = left of the direction of travel
+ *        1 cos_h  = (ex*ch + ey*sh) / len
+ *        2 sin_h  = (ey*ch - ex*sh) / len      entries 1 and 2: the track's tangent in the body frame; (1, 0) = aligned with the track,
+ *                                              sin_h > 0 = the track turns away to the car's left
+ *        3 s_norm = s / 100.0, s = (double)a + t, and s = s - 100.0 if s >= 100.0      the continuous lap position
+ *   6. Look-ahead, k = 0 .. n_ahead - 1: q = (a + 1 + k*stride) % 100, dx = X_q - x, dy = Y_q - y;
+ *        entry 4 + 2k = dx*ch + dy*sh (body-frame forward), entry 5 + 2k = dy*ch - dx*sh (body-frame left).
+ * On a multi-track handle the path is the one of the env's track.
+ *
+ * The frame setter is valid after ftgp_device_io_config only (FTGP_ERR_STATE before it); NULL turns the frame off, and so does a
+ * later ftgp_device_io_config; the signals and contacts setters leave the frame alone, and the frame leaves the spawn rule alone.
+ * FTGP_ERR_ARG, before anything changes: n_ahead outside 0 .. FTGP_MAX_LOOKAHEAD, stride outside 1 .. 50, reserved != 0.  A struct
+ * {0, 1, 0, 0} still turns the fixed entries on.
+ *
+ * Dense progress reward (dense_progress != 0).  For external car i of env e: (s0, off0) are s and off of the frame at the pose the
+ * call begins with, (s1, off1) at the pose after the call's steps, before any reset (both s unrounded, binary64).  ds = s1 - s0;
+ * if ds >= 50.0, ds = ds - 100.0; if ds < -50.0, ds = ds + 100.0; if off0 or off1, or the car had finished when the call began,
+ * ds = 0.0 (the progress block freezes off the track, custom.py:1345; this also keeps a nearest-point jump across a fold of the track
+ * out of the reward).  The base reward is (float)ds in the place of the integer difference; the off-track, wall and car penalties
+ * follow as binary32 subtractions in the order given above.  With dense_progress == 0 the reward is unchanged to the bit.
+ */
+#define FTGP_FRAME_FIXED 4
+#define FTGP_MAX_LOOKAHEAD 16
+typedef struct FtgpDeviceFrame {
+    int32_t n_ahead;              /* look-ahead points per row, 0 .. FTGP_MAX_LOOKAHEAD */
+    int32_t stride;               /* path points between two of them, 1 .. 50 */
+    int32_t dense_progress;       /* non-zero: the dense progress reward */
+    int32_t reserved;             /* 0 */
+} FtgpDeviceFrame;
+int ftgp_device_io_frame(FtgpEnv *env, const FtgpDeviceFrame *frame);
+
+/*
+ * The device step with frame rows: ftgp_step_device_contacts(e, io, x, c) is this call with frame = NULL.  frame / final_frame:
+ * float32[n_envs][n_ext][FTGP_FRAME_FIXED + 2*n_ahead], device memory on the handle's device (a host pointer is FTGP_ERR_ARG before
+ * anything is enqueued); either may be NULL, and dense_progress works without them.  Rows are those of the pose after the call's
+ * steps.  An env reset in the call gets its pre-reset rows in final_frame (only such rows are written there) and, in frame, the rows
+ * evaluated again at the spawn pose -- like the state rows, not the contact rows: a look-ahead of zeros would be a lie.  Frame buffers
+ * while the frame is off: FTGP_ERR_STATE.  With the frame off and no frame buffers the call launches exactly the kernels of
+ * ftgp_step_device_contacts.
+ */
+typedef struct FtgpDeviceStepFrame {
+    float *frame;
+    float *final_frame;
+} FtgpDeviceStepFrame;
+int ftgp_step_device_frame(FtgpEnv *env, const FtgpDeviceStep *io, const FtgpDeviceStepExtra *extra, const FtgpDeviceStepContacts *contacts,
+                           const FtgpDeviceStepFrame *frame);
+
+/* The external cars' frame rows at the current state, without a step (e.g. after ftgp_reset), with the n_ahead and stride of the
+ * frame setter: float32[n_envs][n_ext][FTGP_FRAME_FIXED + 2*n_ahead] in device memory, ordered on `stream` like ftgp_state_device
+ * (only enqueues).  After ftgp_device_io_config (FTGP_ERR_STATE before it); with the frame off, n_ahead = 0 and the rows are the fixed
+ * entries. */
+int ftgp_frame_device(FtgpEnv *env, void *stream, float *frame);
+
+/*
  * Spawn rule: random, wall-aware episode starts.  The reference places car i at path[(i+5)*2] in every episode (custom.py:1112,
  * 1232-1245); FtgpConfig.spawn_mode 0 / 1 are fixed poses too.  A rule is a property of the handle that every reset obeys once it is
  * set -- ftgp_reset with or without a mask and the auto-reset of the device step: start point, lateral offset, yaw and grid order are
@@ -484,6 +556,10 @@ int ftgp_get_centre_dist2(FtgpEnv *env, double *out);
 
 /* float[n_cars][FTGP_CONTACT_FLOATS]: the contact row (see FTGP_CONTACT_FLOATS) of EVERY car at the current state; any handle. */
 int ftgp_get_contacts(FtgpEnv *env, float *out);
+
+/* float[n_cars][FTGP_FRAME_FIXED + 2*n_ahead]: the frame row (see FTGP_FRAME_FIXED) of EVERY car at the current state, with the
+ * n_ahead (0 .. FTGP_MAX_LOOKAHEAD) and stride (1 .. 50) given here (FTGP_ERR_ARG otherwise); any handle. */
+int ftgp_get_frames(FtgpEnv *env, int n_ahead, int stride, float *out);
 
 /* int32[n_cars]: place of each car among the finishers of its env, 1 = winner, 0 = still racing (Mujoco.winners, custom.py:1125,1367-1369). */
 int ftgp_get_winners(FtgpEnv *env, int32_t *out);

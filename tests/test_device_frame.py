@@ -1,0 +1,328 @@
+"""Track-frame rows and the dense progress reward of the device step (include/ftgp.h: FTGP_FRAME_FIXED, ftgp_device_io_frame /
+ftgp_step_device_frame / ftgp_frame_device / ftgp_get_frames; ft_grandprix_amd/vec.py: DeviceVecEnv(track_frame=, lookahead=,
+lookahead_stride=, dense_progress=)).
+
+CPU: the binding, the argument checks, the numpy model of the header's text (tests/frame_model.py: `frame_rows64`) on hand-written
+poses with exact expected rows, that model against the independent one (`polyline_frame`: brute force over all 100 segments of the
+closed polyline with np.hypot, the tangent as an angle) on the four bundled tracks, and the dense-reward arithmetic.
+
+   Scenes: every path point of a track crossed with LATERALS of the start table's clear_left / clear_right (spawn_model.start_table,
+   which test_spawn_rule.py holds equal to ftgp_get_start_table) along the table's normal, one yaw per pose spread over the circle;
+   and the same offsets once more from the middle of the segment ahead of the point, where no two segments tie.
+   Where the pose lies on the outside of a bend, on the normal through a path point, the nearest point of the polyline is that path
+   point itself and segments A and B are equally near, up to the rounding of either model: the header's choice must then be ONE of the
+   segments the brute force finds nearest (within NEAREST_RTOL = 1e-12 of the smallest np.hypot distance, its own rounding), and its
+   numbers must be the independent model's numbers for THAT segment.  Tolerances: lat within 1e-12 * max(|lat|, 1); the tangent as an
+   angle, atan2(sin_h, cos_h) against theta - yaw, within 1e-12; s within 1e-9 path points (on the circle of 100).  The only poses left
+   out, named, are those where no globally nearest segment is one of the two around the nearest point -- a difference of definition;
+   at most TIED_CAP (1e-2) of a scene.
+   Measured (4 tracks x 100 points x 2 places x 9 offsets = 1800 poses each): left out 1 / 0 / 3 / 2 poses on small-circle / circle /
+   track / inkscape, at most 1.7e-3 of a scene, no band narrowed (the path points are not equally spaced, so mid-segment the nearest
+   POINT can be a neighbour's neighbour; inkscape's point 8 at -0.9 of the right clearance is nearer to segment 3 of the leg beside it).
+   On 485 to 492 poses of a track -- those on a point's normal outside the bend, and on the point itself -- the brute force's first
+   minimum is the other of two tied segments; on the other 1300 and more the header's segment is the brute force's own choice.  Worst
+   deviations: lat 3.9e-15, tangent angle 1.8e-15, s 1.4e-14 path points.
+
+   The issue's case "c = 99 with t = 1, where s wraps to 0" cannot be reached in exact arithmetic: t >= 1 on segment 99 -> 0 means
+   r.e >= |e|^2, and then d_0 = |r|^2 - 2 r.e + |e|^2 <= d_99 - |e|^2, so point 0 is nearer and c = 0 (on equal d the first index, 0
+   again).  HAND has c = 99 with both segments; a = 99 with t = 1 and the wrap are reached through rounding, with c = 0, on
+   `skew_path` (`test_s_wraps_at_100`), and the GPU's set poses run on that path too.
+
+GPU: every scenario runs in a fresh child process (tests/device_frame_child.py) that imports torch before libftgp.so is loaded, one at a
+time, each under a time limit.  A child that ends by a signal, an abort or its time limit fails its test, and every later GPU test of
+this module fails at once without starting anything on the GPU.
+"""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from ft_grandprix_amd import capi
+from tests import frame_model as fm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD = os.path.join(ROOT, "tests", "device_frame_child.py")
+
+BUNDLED = ["small-circle", "circle", "track", "inkscape"]
+LATERALS = (-0.9, -0.6, -0.3, -0.1, 0.0, 0.1, 0.3, 0.6, 0.9)       # of clear_right (negative) / clear_left (positive)
+LAT_RTOL, ANGLE_TOL, S_TOL = 1e-12, 1e-12, 1e-9                     # the issue's
+NEAREST_RTOL = 1e-12
+TIED_CAP = 1e-2
+
+
+# ---------------------------------------------------------------------------------------------------------------------- CPU
+def test_binding_declares_the_frame_entries():
+    assert C.sizeof(capi.FtgpDeviceFrame) == 16
+    assert [getattr(capi.FtgpDeviceFrame, f).offset for f in ("n_ahead", "stride", "dense_progress", "reserved")] == [0, 4, 8, 12]
+    assert C.sizeof(capi.FtgpDeviceStepFrame) == 16 and capi.FtgpDeviceStepFrame.frame.offset == 0 and capi.FtgpDeviceStepFrame.final_frame.offset == 8
+    assert capi.FRAME_FIXED == fm.FRAME_FIXED == len(capi.FRAME_FIELDS) == 4 and capi.MAX_LOOKAHEAD == fm.MAX_LOOKAHEAD == 16
+    assert capi.FRAME_FIELDS == ("lat", "cos_h", "sin_h", "s_norm")
+    lib = capi.load()
+    for name in ("device_io_frame", "step_device_frame", "frame_device", "get_frames"):
+        assert name in capi.API_SYMBOLS and lib.has(name), name
+    for method in ("device_io_frame", "step_device_frame", "frame_device", "get_frames"):
+        assert callable(getattr(capi.Env, method))
+    header = open(os.path.join(ROOT, "include", "ftgp.h")).read()
+    assert "#define FTGP_FRAME_FIXED 4" in header and "#define FTGP_MAX_LOOKAHEAD 16" in header and "#define FTGP_ABI_VERSION 5" in header
+
+
+@pytest.mark.parametrize("kwargs", [dict(lookahead=17), dict(lookahead=-1), dict(lookahead_stride=0), dict(lookahead_stride=51),
+                                    dict(lookahead_stride=-3), dict(lookahead=4, lookahead_stride=51), dict(dense_progress=True, lookahead=-2)])
+def test_device_vec_env_checks_the_frame_arguments_before_a_handle_exists(kwargs, monkeypatch):
+    from ft_grandprix_amd import vec
+
+    def no_load():
+        raise AssertionError("the library was loaded before the arguments were checked")
+    monkeypatch.setattr(capi, "load", no_load)
+    with pytest.raises(ValueError):
+        vec.DeviceVecEnv("small-circle", n_envs=4, n_rays=64, **kwargs)
+
+
+def square_path(duplicate=None):
+    """A square of side 12.5, counter-clockwise from (0, 0), 25 points per side half a unit apart: every coordinate is dyadic.  Point 0 =
+    (0, 0), 25 = (12.5, 0), 50 = (12.5, 12.5), 75 = (0, 12.5), 99 = (0, 0.5).  duplicate = k: point k + 1 is put on point k."""
+    i = 0.5 * np.arange(25)
+    z, top = np.zeros(25), np.full(25, 12.5)
+    p = np.concatenate([np.stack([i, z], 1), np.stack([top, i], 1), np.stack([12.5 - i, top], 1), np.stack([z, 12.5 - i], 1)])
+    if duplicate is not None:
+        p[duplicate + 1] = p[duplicate]
+    return p
+
+
+EAST, WEST = (1.0, 0.0), (0.0, 1.0)          # (qw, qz) of yaw 0 and yaw pi, exact
+
+
+def poses(rows):
+    """(x, y, (qw, qz)) per car -> rows of ftgp_get_pose."""
+    p = np.zeros((len(rows), 13))
+    for k, (x, y, q) in enumerate(rows):
+        p[k, 0], p[k, 1], p[k, 3], p[k, 6] = x, y, q[0], q[1]
+    return p
+
+
+def s_norm(s):
+    return np.float32(s / 100.0)
+
+
+# (what, path, pose, n_ahead, stride, the expected row, the expected (c, a)): every product, sum and quotient below is exact
+HAND = [
+    # halfway between points 6 (3, 0) and 7 (3.5, 0), a quarter unit to the left: d_6 == d_7 -> c = 6, the first; A = 5 -> 6 clamps at
+    # t = 1 (g2 0.125), B = 6 -> 7 has t = 0.5 (g2 0.0625)
+    ("left of a side", None, (3.25, 0.25, EAST), 0, 1, [0.25, 1, 0, s_norm(6.5)], (6, 6)),
+    ("right of a side", None, (3.25, -0.25, EAST), 0, 1, [-0.25, 1, 0, s_norm(6.5)], (6, 6)),
+    ("left of a side, looking back", None, (3.25, 0.25, WEST), 0, 1, [0.25, -1, 0, s_norm(6.5)], (6, 6)),
+    # on point 6: A ends on it (t = 1), B begins on it (t = 0), g2 = 0 both -> B, s = 6 + 0
+    ("on a point", None, (3.0, 0.0, EAST), 1, 1, [0, 1, 0, s_norm(6.0), 0.5, 0], (6, 6)),
+    # c = 0: d_0 == d_99 = 0.125 -> the first; A = 99 -> 0 = (0, 0.5) -> (0, 0) has t = 0.5 and g2 0.0625, B = 0 -> 1 clamps at t = 0 with
+    # g2 0.125: A, strictly.  The track runs down there: the car, looking east, sees it turn away to its right; it sits right of it
+    ("c = 0 takes segment 99 -> 0", None, (-0.25, 0.25, EAST), 2, 1, [-0.25, 0, -1, s_norm(99.5), 0.25, -0.25, 0.75, -0.25], (0, 99)),
+    # outside the corner at point 25 (12.5, 0): A = 24 -> 25 clamps at t = 1, B = 25 -> 26 at t = 0, both feet are the corner and
+    # g2 = 0.5 both -> B: the tangent is north, the car half a unit to its right
+    ("outside a corner, the clamp on both segments, the tie to B", None, (13.0, -0.5, EAST), 0, 1, [-0.5, 0, 1, s_norm(25.0)], (25, 25)),
+    # inside the same corner, on its bisector: A = 24 -> 25 has t = 0.75 and the foot (12.375, 0), B = 25 -> 26 has t = 0.25 and the foot
+    # (12.5, 0.125), g2 = 1/64 both -> B
+    ("inside a corner, both interior, the tie to B", None, (12.375, 0.125, EAST), 0, 1, [0.125, 0, 1, s_norm(25.25)], (25, 25)),
+    # points 10 and 11 both at (5, 0): d_10 == d_11 -> c = 10; B = 10 -> 11 has L2 == 0 -> e = (1, 0), t = 0, g2 = 0.0625; A = 9 -> 10
+    # clamps at t = 1 with the same g2 -> B.  The look-ahead starts with the duplicate itself
+    ("a duplicated point", 10, (5.0, 0.25, EAST), 2, 1, [0.25, 1, 0, s_norm(10.0), 0, -0.25, 1.0, -0.25], (10, 10)),
+    # side 3 runs down the y axis: point 95 = (0, 2.5), 96 = (0, 2); the car left of the axis is right of the direction of travel.
+    # look-ahead with stride 7 from a = 95: points 96, 103 % 100 = 3 = (1.5, 0), 110 % 100 = 10 = (5, 0)
+    ("look-ahead across index 99, stride 7", None, (-0.25, 2.25, EAST), 3, 7,
+     [-0.25, 0, -1, s_norm(95.5), 0.25, -0.25, 1.75, -2.25, 5.25, -2.25], (95, 95)),
+    ("look-ahead across index 99, stride 7, looking back", None, (-0.25, 2.25, WEST), 3, 7,
+     [-0.25, 0, 1, s_norm(95.5), -0.25, 0.25, -1.75, 2.25, -5.25, 2.25], (95, 95)),
+    # stride 50 from a = 99: points 0, 50, 100 % 100 = 0
+    ("stride 50", None, (-0.25, 0.25, EAST), 3, 50, [-0.25, 0, -1, s_norm(99.5), 0.25, -0.25, 12.75, 12.25, 0.25, -0.25], (0, 99)),
+    # c = 99 = (0, 0.5), the last point: above it A = 98 -> 99 is strictly nearer (t = 0.75, g2 1/16 against 5/64), below it B = 99 -> 0
+    # (t = 0.25); side 3 runs down, the car at x > 0 is left of the direction of travel
+    ("c = 99 takes segment 98 -> 99", None, (0.25, 0.625, EAST), 1, 1, [0.25, 0, -1, s_norm(98.75), -0.25, -0.125], (99, 98)),
+    ("c = 99 takes segment 99 -> 0", None, (0.25, 0.375, EAST), 2, 1, [0.25, 0, -1, s_norm(99.25), -0.25, -0.375, 0.25, -0.375], (99, 99)),
+    # three units off the track: off, the row is geometry all the same
+    ("off the track", None, (3.25, -3.0, EAST), 0, 1, [-3.0, 1, 0, s_norm(6.5)], (6, 6)),
+]
+
+
+@pytest.mark.parametrize("case", HAND, ids=[c[0] for c in HAND])
+def test_model_on_hand_written_poses(case):
+    what, dup, pose, n_ahead, stride, want, (c_want, a_want) = case
+    rows, s, off, a, c = fm.frame_rows64(square_path(dup), poses([pose]), n_ahead, stride)
+    assert (int(c[0]), int(a[0])) == (c_want, a_want)
+    np.testing.assert_array_equal(rows.astype(np.float32), np.array([want], dtype=np.float32))
+    np.testing.assert_array_equal(fm.frame_rows(square_path(dup), poses([pose]), n_ahead, stride), np.array([want], dtype=np.float32))
+    assert bool(off[0]) == (what == "off the track")
+    assert np.float32(s[0] / 100.0) == np.float32(want[3])
+
+
+SKEW_SHIFT = (8.1, -24.3)
+SKEW_POINT_99 = (3.800696369503287, -7.398052024670745)
+SKEW_WRAP_POSE = (7.687704582750535, -24.629698178119828)
+
+
+def skew_path():
+    """The square with point 11 on point 10, moved by SKEW_SHIFT (not dyadic) into a 40 x 40 field, and with point 99 moved far
+    away to SKEW_POINT_99: Y_99 + 1.0 * (Y_0 - Y_99) then rounds one ulp below Y_0, so that wherever both segments around point 0 clamp
+    to it (the outside of that corner) segment A = 99 -> 0 is nearer than B by that ulp: a = 99 with t = 1, which no pose reaches in
+    exact arithmetic (module docstring), and s = 100 wraps to 0."""
+    p = square_path(duplicate=10) + np.array(SKEW_SHIFT)
+    p[99] = SKEW_POINT_99
+    return p
+
+
+def test_s_wraps_at_100():
+    """a = 99 with t = 1: fed to the segment arithmetic directly on the exact square, and reached by rounding on the skew path."""
+    g = fm._segment(square_path(), np.array([99]), np.array([0.0]), np.array([0.0]))
+    assert g["t"][0] == 1.0 and g["g2"][0] == 0.0
+    s = g["a"].astype(np.float64) + g["t"]
+    assert np.where(s >= 100.0, s - 100.0, s)[0] == 0.0
+    # a pose cannot get there on the exact square: on point 0 the row takes B = 0 -> 1
+    _, s, _, a, c = fm.frame_rows64(square_path(), poses([(0.0, 0.0, EAST)]))
+    assert (int(c[0]), int(a[0]), s[0]) == (0, 0, 0.0)
+    # the skew path: the foot of A rounds off point 0
+    path = skew_path()
+    foot = path[99] + 1.0 * (path[0] - path[99])
+    assert foot[0] == path[0, 0] and foot[1] < path[0, 1] and path[0, 1] - foot[1] < 1e-14
+    rows, s, off, a, c = fm.frame_rows64(path, poses([(*SKEW_WRAP_POSE, EAST), (SKEW_SHIFT[0] - 0.5, SKEW_SHIFT[1] - 0.5, WEST)]), 1, 1)
+    for i in range(2):
+        g = fm._segment(path, np.array([99]), rows[i:i + 1, 0] * 0 + [SKEW_WRAP_POSE[0], SKEW_SHIFT[0] - 0.5][i],
+                        rows[i:i + 1, 0] * 0 + [SKEW_WRAP_POSE[1], SKEW_SHIFT[1] - 0.5][i])
+        assert g["t"][0] == 1.0
+        assert (int(c[i]), int(a[i]), s[i], rows[i, fm.S_NORM], bool(off[i])) == (0, 99, 0.0, 0.0, False)
+    assert rows[0, fm.LAT] < 0 and rows[0, fm.COS_H] > 0 and rows[0, fm.SIN_H] < 0          # the tangent of 99 -> 0, not of 0 -> 1
+
+
+ALONG = (0.0, 0.5)       # of the segment ahead: on the point's normal, where A and B tie on the outside of a bend, and between two points
+
+
+def bundled_scene(name):
+    """Every path point, and the middle of the segment behind it, crossed with LATERALS of the room the start table gives on that side
+    (mid-segment: the smaller of the two ends'), along the table's normal at the point; yaws spread."""
+    from ft_grandprix_amd.track import load_track
+    from tests import spawn_model as sp
+    t = load_track(name)
+    table = sp.start_table(t)
+    rows = []
+    for p in range(100):
+        x, y, qw, qz, left, right = table[p]
+        nx, ny = table[(p + 1) % 100][0:2]
+        ch, sh = 1.0 - 2.0 * (qz * qz), 2.0 * (qw * qz)
+        for w in ALONG:
+            room = (left, right) if w == 0.0 else (min(left, table[(p + 1) % 100][4]), min(right, table[(p + 1) % 100][5]))
+            for f in LATERALS:
+                lat = f * (room[0] if f >= 0 else room[1])
+                yaw = 2.399963229728653 * len(rows)               # the golden angle: no two poses share a heading
+                rows.append((x + w * (nx - x) + lat * -sh, y + w * (ny - y) + lat * ch, (np.cos(yaw / 2), np.sin(yaw / 2))))
+    return np.asarray(t.path, dtype=np.float64), poses(rows)
+
+
+def wrap(a, period):
+    return (a + 0.5 * period) % period - 0.5 * period
+
+
+@pytest.mark.parametrize("name", BUNDLED)
+def test_header_model_meets_the_polyline_model(name):
+    path, pose = bundled_scene(name)
+    n = len(pose)
+    rows, s, off, a, c = fm.frame_rows64(path, pose)
+    dist, lat, theta, s_all, yaw = fm.polyline_frame(path, pose)
+    k = np.arange(n)
+    nearest = dist <= dist.min(axis=1, keepdims=True) * (1.0 + NEAREST_RTOL)
+    around = np.zeros_like(nearest)
+    around[k, c] = around[k, (c + 99) % 100] = True
+    out = ~(nearest & around).any(axis=1)                      # the globally nearest segment is not one of the two around point c
+    for i in np.nonzero(out)[0]:
+        print(f"{name}: pose {i} (point {i // (len(ALONG) * len(LATERALS))}, along {ALONG[i // len(LATERALS) % len(ALONG)]}, lateral {LATERALS[i % len(LATERALS)]}): the nearest segment {int(dist[i].argmin())} "
+              f"is not around the nearest point {int(c[i])} -- left out")
+    assert out.sum() <= TIED_CAP * n, f"{name}: {int(out.sum())} of {n} poses left out"
+    keep = ~out
+    assert nearest[k, a][keep].all(), f"{name}: the header's segment is not a nearest one: poses {np.nonzero(keep & ~nearest[k, a])[0][:5]}"
+    tied = keep & (dist.argmin(axis=1) != a)
+    d_lat = np.abs(rows[:, fm.LAT] - lat[k, a])
+    d_ang = np.abs(wrap(np.arctan2(rows[:, fm.SIN_H], rows[:, fm.COS_H]) - (theta[a] - yaw), 2.0 * np.pi))
+    d_s = np.abs(wrap(s - s_all[k, a], 100.0))
+    print(f"{name}: {n} poses, {int(out.sum())} left out, {int(tied.sum())} on a segment tied for nearest, {int(off.sum())} off the track; "
+          f"worst lat {d_lat[keep].max():.2e}, angle {d_ang[keep].max():.2e}, s {d_s[keep].max():.2e}")
+    assert (d_lat[keep] <= LAT_RTOL * np.maximum(np.abs(lat[k, a][keep]), 1.0)).all()
+    assert (d_ang[keep] <= ANGLE_TOL).all()
+    assert (d_s[keep] <= S_TOL).all()
+    np.testing.assert_allclose(rows[:, fm.S_NORM], s / 100.0, rtol=0, atol=0)
+    np.testing.assert_allclose(np.hypot(rows[:, fm.COS_H], rows[:, fm.SIN_H]), 1.0, rtol=0, atol=1e-12)
+    assert (rows[keep, fm.LAT] > 0).any() and (rows[keep, fm.LAT] < 0).any() and len(set(a.tolist())) >= 95
+
+
+def test_dense_reward_arithmetic():
+    f = np.float32
+    s0 = np.array([10.25, 99.5, 0.25, 10.0, 10.0, 10.0, 0.0, 60.0, 10.0])
+    s1 = np.array([10.75, 0.25, 99.5, 11.0, 11.0, 11.0, 50.0, 10.0, 9.5])
+    off0 = np.array([0, 0, 0, 1, 0, 0, 0, 0, 0], dtype=bool)
+    off1 = np.array([0, 0, 0, 0, 1, 0, 0, 0, 0], dtype=bool)
+    fin0 = np.array([0, 0, 0, 0, 0, 1, 0, 0, 0], dtype=bool)
+    # forward; across the line forward (-99.25 + 100) and backward (99.25 - 100); frozen by off0, off1, finished; +50 wraps to -50,
+    # -50 stays; backward
+    want = np.array([0.5, 0.75, -0.75, 0, 0, 0, -50.0, -50.0, -0.5], dtype=f)
+    base = fm.dense_reward(s0, off0, s1, off1, fin0)
+    assert base.dtype == f
+    np.testing.assert_array_equal(base, want)
+    # the penalties: binary32 subtractions, off-track first, then wall, then car -- an order that shows in the last bit
+    b = np.array([0.1], dtype=f)
+    r = fm.penalised(b, [True], 0.3, [True], 1e-8, [True], 0.7)
+    assert r[0] == f(f(f(b[0] - f(0.3)) - f(1e-8)) - f(0.7)) and r.dtype == f
+    assert fm.penalised(b, [True], 0.3, [True], 0.7, [True], 1e-8)[0] == f(f(f(b[0] - f(0.3)) - f(0.7)) - f(1e-8))
+    np.testing.assert_array_equal(fm.penalised(base, off1, 2.0), want - np.where(off1, f(2.0), f(0.0)))
+    np.testing.assert_array_equal(fm.penalised(base, np.zeros(9), 2.0, np.zeros(9), 1.0, np.zeros(9), 1.0), want)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- GPU
+CRASHED = []               # the first child that ended by a signal, an abort or its time limit: nothing more is started on the GPU after it
+
+
+def run_child(scenario, timeout=90, **opt):
+    assert not CRASHED, f"not started: an earlier GPU scenario of this module died ({CRASHED[0]}); find its cause first"
+    what = f"{scenario} {json.dumps(opt)}"
+    try:
+        r = subprocess.run([sys.executable, CHILD, scenario, json.dumps(opt)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired as x:
+        CRASHED.append(f"{what}: no end after {timeout} s")
+        out = "".join(s.decode(errors="replace") if isinstance(s, bytes) else (s or "") for s in (x.stdout, x.stderr))
+        raise AssertionError(f"{CRASHED[0]}\n{out[-4000:]}") from None
+    out = r.stdout + r.stderr
+    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
+        CRASHED.append(f"{what}: exit status {r.returncode}")
+    assert r.returncode == 0, f"{what}: exit status {r.returncode}\n{out[-6000:]}"
+    print(out[-3000:])
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("track", ["square", "track"])
+def test_gpu_get_frames_on_set_poses_bit_for_bit(track):
+    """1, 15, 16, 17 and 37 cars; ties, c = 0, c = 99, off the track; n_ahead 0, 1, 16 and stride 1, 7, 50."""
+    assert "set poses ok" in run_child("set_poses", track=track)
+
+
+@pytest.mark.gpu
+def test_gpu_closed_loop_rows_rewards_and_resets():
+    assert "closed loop ok" in run_child("closed_loop", calls=120)
+
+
+@pytest.mark.gpu
+def test_gpu_dense_reward_freezes_off_the_track_and_wraps_at_the_line():
+    assert "frozen ok" in run_child("frozen")
+
+
+@pytest.mark.gpu
+def test_gpu_multi_track_rows_follow_each_envs_path():
+    assert "multi track ok" in run_child("multi_track")
+
+
+@pytest.mark.gpu
+def test_gpu_frame_off_is_the_old_call_and_the_error_codes():
+    assert "off ok" in run_child("off", calls=80)
+
+
+@pytest.mark.gpu
+def test_gpu_track_frame_without_dense_progress_keeps_the_integer_reward():
+    assert "integer ok" in run_child("integer", calls=80)
