@@ -466,34 +466,34 @@ class Env:
         self._call("get_start_table", track, _ptr(out))
         return out
 
+    @staticmethod
+    def _step_args(stream, action, obs, reward, terminated, truncated, final_obs, *rows):
+        """The arguments of a device step by reference: the FtgpDeviceStep block, then for every (struct type, address, final address)
+        of ``rows`` that struct, or None when both addresses are 0."""
+        io = FtgpDeviceStep(*(v or None for v in (stream, action, obs, reward, terminated, truncated, final_obs)))
+        return [C.byref(io)] + [C.byref(T(a or None, b or None)) if a or b else None for T, a, b in rows]
+
     def step_device(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0,
                     state: int = 0, final_state: int = 0, contact: int = 0, final_contact: int = 0):
         """One ftgp_step_device call on integer device addresses (and an integer hipStream_t, 0 = the null stream); only enqueues.
         With ``state`` or ``final_state``: ftgp_step_device_ex; with ``contact`` or ``final_contact``: ftgp_step_device_contacts."""
-        io = FtgpDeviceStep(stream or None, action or None, obs or None, reward or None, terminated or None, truncated or None,
-                            final_obs or None)
-        if contact or final_contact:
-            extra = FtgpDeviceStepExtra(state or None, final_state or None) if state or final_state else None
-            con = FtgpDeviceStepContacts(contact or None, final_contact or None)
-            self._call("step_device_contacts", C.byref(io), None if extra is None else C.byref(extra), C.byref(con))
-        elif state or final_state:
-            extra = FtgpDeviceStepExtra(state or None, final_state or None)
-            self._call("step_device_ex", C.byref(io), C.byref(extra))
+        io, extra, con = self._step_args(stream, action, obs, reward, terminated, truncated, final_obs,
+                                         (FtgpDeviceStepExtra, state, final_state), (FtgpDeviceStepContacts, contact, final_contact))
+        if con is not None:
+            self._call("step_device_contacts", io, extra, con)
+        elif extra is not None:
+            self._call("step_device_ex", io, extra)
         else:
-            self._call("step_device", C.byref(io))
+            self._call("step_device", io)
 
     def step_device_frame(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0,
                           state: int = 0, final_state: int = 0, contact: int = 0, final_contact: int = 0, frame: int = 0,
                           final_frame: int = 0):
         """One ftgp_step_device_frame call on integer device addresses, like ``step_device``; ``frame`` / ``final_frame``: float32
         [n_envs, n_ext, FRAME_FIXED + 2 * n_ahead], either may be 0."""
-        io = FtgpDeviceStep(stream or None, action or None, obs or None, reward or None, terminated or None, truncated or None,
-                            final_obs or None)
-        extra = FtgpDeviceStepExtra(state or None, final_state or None) if state or final_state else None
-        con = FtgpDeviceStepContacts(contact or None, final_contact or None) if contact or final_contact else None
-        fr = FtgpDeviceStepFrame(frame or None, final_frame or None) if frame or final_frame else None
-        self._call("step_device_frame", C.byref(io), None if extra is None else C.byref(extra), None if con is None else C.byref(con),
-                   None if fr is None else C.byref(fr))
+        self._call("step_device_frame", *self._step_args(
+            stream, action, obs, reward, terminated, truncated, final_obs, (FtgpDeviceStepExtra, state, final_state),
+            (FtgpDeviceStepContacts, contact, final_contact), (FtgpDeviceStepFrame, frame, final_frame)))
 
     def state_device(self, state: int, stream: int = 0):
         """ftgp_state_device: the state rows of the current state into device memory at ``state``, ordered on ``stream``; only enqueues."""

@@ -154,33 +154,34 @@ struct FtgpEnv {
     std::vector<int32_t> h_prog; std::vector<double> h_core;
     bool rows_valid = false;          // h_prog / h_core mirror the device state (cleared by every call that changes it)
     bool multi = false;
-    // device I/O (ftgp_device_io_config / ftgp_step_device)
-    bool io_ready = false;
-    DeviceIoArgs io{};                // the episode rules and the slot table; the buffers are filled in per call
-    int io_repeat = 1;
     HostBuf<int32_t> h_tables;        // pinned [2][FTGP_MAX_CARS_PER_BLOCK]: the user's roster (mirror of P.car_policy), the device-io slot table
     int table_on_device = 0;          // which of the two the params block holds (-1: neither); only a FTGP_POLICY_PER_CAR launch reads it
-    DevBuf<int32_t> d_prev_abs;
-    Event ev_io_in, ev_io_out;
-    DeviceSignalArgs sig{};           // ftgp_device_io_signals (the buffers and what depends on them are filled in per call)
-    bool sig_default = true;          // the defaults: a call without state buffers launches ftgp_io_finish_kernel
-    bool con_on = false;              // ftgp_device_io_contacts: a call evaluates the contact rows and goes through ftgp_io_finish_signals_kernel
-    FtgpDeviceContacts con{};         // the contact rules while con_on
-    DevBuf<float> d_contact;          // [n_cars][FTGP_CONTACT_FLOATS] every car's contact row, allocated on first use
-    bool frame_on = false;            // ftgp_device_io_frame: a call evaluates the frame rows and goes through ftgp_io_finish_signals_kernel
-    FtgpDeviceFrame frame{};          // n_ahead, stride and the reward rule while frame_on
-    DevBuf<float> d_frame;            // [n_cars][FTGP_FRAME_FIXED + 2 * FTGP_MAX_LOOKAHEAD] floats, rows packed at the width in use; allocated on first use.
-                                      // Scratch of one call: ftgp_get_frames packs rows of ITS width in here too, which is safe only because every device
-                                      // step rewrites the buffer on the handle's stream before its finish kernel reads it -- nothing may be kept in it across calls
-    DevBuf<double> d_frame_s;         // [2][n_cars] s before and after a call's steps (dense progress)
-    DevBuf<int32_t> d_frame_flag;     // [2][n_cars] the flags that go with them
+    // device I/O (ftgp_device_io_config / ftgp_step_device): everything the device step keeps on the host
+    struct DeviceStep {
+        bool ready = false;               // ftgp_device_io_config has run
+        DeviceIoArgs io{};                // the episode rules and the slot table; the buffers are filled in per call
+        int repeat = 1;
+        DevBuf<int32_t> d_prev_abs;
+        Event ev_in, ev_out;              // the fences between the caller's stream and the handle's
+        DeviceSignalArgs sig{};           // ftgp_device_io_signals (the buffers and what depends on them are filled in per call)
+        bool sig_default = true;          // the defaults: a call without state buffers launches ftgp_io_finish_kernel
+        bool con_on = false;              // ftgp_device_io_contacts: a call evaluates the contact rows and goes through ftgp_io_finish_signals_kernel
+        FtgpDeviceContacts con{};         // the contact rules while con_on
+        DevBuf<float> d_contact;          // [n_cars][FTGP_CONTACT_FLOATS] every car's contact row, allocated on first use
+        bool frame_on = false;            // ftgp_device_io_frame: a call evaluates the frame rows and goes through ftgp_io_finish_signals_kernel
+        FtgpDeviceFrame frame{};          // n_ahead, stride and the reward rule while frame_on
+        DevBuf<float> d_frame;            // [n_cars][FTGP_FRAME_FIXED + 2 * FTGP_MAX_LOOKAHEAD] floats, rows packed at the width in use; allocated on first use.
+                                          // Scratch of one call: ftgp_get_frames packs rows of ITS width in here too, which is safe only because every device
+                                          // step rewrites the buffer on the handle's stream before its finish kernel reads it -- nothing may be kept in it across calls
+        DevBuf<double> d_frame_s;         // [2][n_cars] s before and after a call's steps (dense progress)
+        DevBuf<int32_t> d_frame_flag;     // [2][n_cars] the flags that go with them
+        struct { const void* p; size_t bytes; } checked[32] = {};     // device buffers found valid (hipPointerGetAttributes), replaced round robin
+        int checked_next = 0;
+    } ds;
     // spawn rule (ftgp_set_spawn_rule)
     std::vector<double> start_table;  // [n_tracks][FTGP_PATH_POINTS][6] x, y, qw, qz, clear_left, clear_right: the plan's (ftgp_get_start_table)
     const FtgpSpawnDev* rule = nullptr;      // what the reset paths are handed: d_rule while a rule is set, null without one
     DevBuf<FtgpSpawnDev> d_rule; DevBuf<int32_t> d_start, d_n_start; DevBuf<double> d_clear; DevBuf<int64_t> d_episodes;      // allocated by the first rule
-    struct Checked { const void* p; size_t bytes; };
-    Checked io_checked[32] = {};      // device buffers found valid (hipPointerGetAttributes), replaced round robin
-    int io_checked_next = 0;
     // comm
     void* comm = nullptr; int rank = 0, world = 1;
 };
@@ -753,10 +754,6 @@ void layout_images(const Plan& pl, const DeviceAddrs& a, Images& im)
     memcpy(im.params.data() + z.head + z.wg, pl.tasks.data(), z.tasks);
 }
 
-// Waiting for an event of a launch is a blocked wait.  Polling hipEventQuery instead was measured (tools/launch_host.sh, round 4): 7 us
-// SLOWER per launch -- every query takes the runtime's locks and walks the stream's command list.
-hipError_t wait_event(const FtgpEnv*, hipEvent_t ev) { return hipEventSynchronize(ev); }
-
 // nidc or fast, for every car or for some car of the roster
 bool uses_disparity_driver(const FtgpEnv* e, int policy)
 {
@@ -842,7 +839,9 @@ int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
     if (n_steps > 0 && e->gather_open && e->gather_slot == slot) {
         if (e->comm) HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_gather.get(), 0));
         else if (!e->gather_held) {
-            HIP_TRY(wait_event(e, e->gather_event));
+            // Waiting for an event of a launch is a blocked wait.  Polling hipEventQuery instead was measured (tools/launch_host.sh, round 4):
+            // 7 us SLOWER per launch -- every query takes the runtime's locks and walks the stream's command list.
+            HIP_TRY(hipEventSynchronize(e->gather_event));
             collect_slot(e, slot, e->held);
             e->gather_held = true;
         }
@@ -892,7 +891,8 @@ int sync_rows_to_host(FtgpEnv* e)
 int check_device_buffer(FtgpEnv* e, const void* p, size_t bytes, const char* name)
 {
     if (!p) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is NULL", name);
-    for (const FtgpEnv::Checked& c : e->io_checked) if (c.p == p && c.bytes >= bytes) return 0;
+    auto& ds = e->ds;
+    for (const auto& c : ds.checked) if (c.p == p && c.bytes >= bytes) return 0;
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
@@ -906,15 +906,15 @@ int check_device_buffer(FtgpEnv* e, const void* p, size_t bytes, const char* nam
     }
     const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
     if (q < b || q - b + bytes > size) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is smaller than the layout needs", name);
-    e->io_checked[e->io_checked_next] = { p, bytes };
-    e->io_checked_next = (e->io_checked_next + 1) % (int)(sizeof e->io_checked / sizeof e->io_checked[0]);
+    ds.checked[ds.checked_next] = { p, bytes };
+    ds.checked_next = (ds.checked_next + 1) % (int)(sizeof ds.checked / sizeof ds.checked[0]);
     return 0;
 }
 
 // the signals of the device step as the finish kernel takes them (ftgp_device_io_signals has checked s)
 void set_signals(FtgpEnv* e, const FtgpDeviceSignals& s)
 {
-    DeviceSignalArgs& S = e->sig;
+    DeviceSignalArgs& S = e->ds.sig;
     S = DeviceSignalArgs{};
     S.pool = s.scan_pool; S.n_beams = e->P.n_rays / s.scan_pool;
     S.vec_in = e->P.n_rays % 4 == 0;
@@ -926,7 +926,7 @@ void set_signals(FtgpEnv* e, const FtgpDeviceSignals& s)
     S.inv_max_range = S.clip ? 1.0f / s.scan_max_range : 0.0f;
     S.terminate_off_track = s.terminate_off_track ? 1 : 0;
     S.penalty = s.off_track_penalty;
-    e->sig_default = s.scan_pool == 1 && !S.clip && !S.terminate_off_track && s.off_track_penalty == 0.0f;
+    e->ds.sig_default = s.scan_pool == 1 && !S.clip && !S.terminate_off_track && s.off_track_penalty == 0.0f;
 }
 
 // ftgp_io_contact_kernel on the handle's stream: every car's row to `rows` and / or the external cars' rows to `ext_out`
@@ -936,8 +936,8 @@ int launch_contacts(FtgpEnv* e, float* rows, float* ext_out)
     C.blocks = reinterpret_cast<const unsigned char*>(e->d_params.get());
     C.env_track = e->d_env_track.get();
     C.rows = rows; C.ext_out = ext_out;
-    C.n_ext = e->io.n_ext;
-    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) C.ext_index[k] = e->io_ready ? e->io.ext_index[k] : -1;
+    C.n_ext = e->ds.io.n_ext;
+    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) C.ext_index[k] = e->ds.ready ? e->ds.io.ext_index[k] : -1;
     for (size_t k = 0; k < e->trk.size() && k < FTGP_MAX_TRACKS; ++k) C.block_off[k] = (uint32_t)e->trk[k].block;
     const unsigned blocks = (unsigned)(((size_t)e->P.n_cars * FTGP_CONTACT_LANES + FTGP_CONTACT_THREADS - 1) / FTGP_CONTACT_THREADS);
     hipLaunchKernelGGL(ftgp_io_contact_kernel, dim3(blocks), dim3(FTGP_CONTACT_THREADS), 0, e->stream.get(), e->P, C);
@@ -947,7 +947,7 @@ int launch_contacts(FtgpEnv* e, float* rows, float* ext_out)
 
 int ensure_contact_rows(FtgpEnv* e)
 {
-    if (!e->d_contact) HIP_TRY(dev_alloc(e->d_contact, sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_cars));
+    if (!e->ds.d_contact) HIP_TRY(dev_alloc(e->ds.d_contact, sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_cars));
     return 0;
 }
 
@@ -958,10 +958,10 @@ int launch_frame(FtgpEnv* e, int n_ahead, int stride, float* rows, float* ext_ou
     DeviceFrameArgs F{};
     F.env_track = e->d_env_track.get();
     F.rows = rows; F.ext_out = ext_out;
-    F.s_out = slot >= 0 ? e->d_frame_s.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
-    F.flag_out = slot >= 0 ? e->d_frame_flag.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
-    F.n_ext = e->io.n_ext; F.n_ahead = n_ahead; F.stride = stride;
-    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) F.ext_index[k] = e->io_ready ? e->io.ext_index[k] : -1;
+    F.s_out = slot >= 0 ? e->ds.d_frame_s.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
+    F.flag_out = slot >= 0 ? e->ds.d_frame_flag.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
+    F.n_ext = e->ds.io.n_ext; F.n_ahead = n_ahead; F.stride = stride;
+    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) F.ext_index[k] = e->ds.ready ? e->ds.io.ext_index[k] : -1;
     const unsigned blocks = (unsigned)(((size_t)e->P.n_cars * FTGP_FRAME_LANES + FTGP_FRAME_THREADS - 1) / FTGP_FRAME_THREADS);
     hipLaunchKernelGGL(ftgp_io_frame_kernel, dim3(blocks), dim3(FTGP_FRAME_THREADS), 0, e->stream.get(), e->P, F);
     HIP_TRY(hipGetLastError());
@@ -971,11 +971,39 @@ int launch_frame(FtgpEnv* e, int n_ahead, int stride, float* rows, float* ext_ou
 int ensure_frame_rows(FtgpEnv* e)
 {
     const size_t n_cars = (size_t)e->P.n_cars;
-    if (!e->d_frame) HIP_TRY(dev_alloc(e->d_frame, sizeof(float) * (FTGP_FRAME_FIXED + 2 * FTGP_MAX_LOOKAHEAD) * n_cars));
-    if (!e->d_frame_s) HIP_TRY(dev_alloc(e->d_frame_s, sizeof(double) * 2 * n_cars));
-    if (!e->d_frame_flag) HIP_TRY(dev_alloc(e->d_frame_flag, sizeof(int32_t) * 2 * n_cars));
+    if (!e->ds.d_frame) HIP_TRY(dev_alloc(e->ds.d_frame, sizeof(float) * (FTGP_FRAME_FIXED + 2 * FTGP_MAX_LOOKAHEAD) * n_cars));
+    if (!e->ds.d_frame_s) HIP_TRY(dev_alloc(e->ds.d_frame_s, sizeof(double) * 2 * n_cars));
+    if (!e->ds.d_frame_flag) HIP_TRY(dev_alloc(e->ds.d_frame_flag, sizeof(int32_t) * 2 * n_cars));
     return 0;
 }
+
+// stream `behind` waits for what stream `ahead` holds so far, through event ev
+int stream_waits_for(hipStream_t behind, hipStream_t ahead, const Event& ev)
+{
+    HIP_TRY(hipEventRecord(ev.get(), ahead));
+    HIP_TRY(hipStreamWaitEvent(behind, ev.get(), 0));
+    return 0;
+}
+
+// the two fences of an entry that works on the handle's stream for a caller's: one before the work, one behind it
+int handle_waits_for_caller(FtgpEnv* e, hipStream_t caller) { return stream_waits_for(e->stream.get(), caller, e->ds.ev_in); }
+int caller_waits_for_handle(FtgpEnv* e, hipStream_t caller) { return stream_waits_for(caller, e->stream.get(), e->ds.ev_out); }
+
+// ftgp_state_device, ftgp_contacts_device, ftgp_frame_device (`entry`): the external agents' rows of `floats` floats, written by `launch`
+// on the handle's stream to the caller's buffer `out` (`name` in a refusal)
+template <class Launch>
+int rows_to_device(FtgpEnv* e, const char* entry, void* stream, size_t floats, float* out, const char* name, Launch launch)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->ds.ready) return fail(FTGP_ERR_STATE, "%s before ftgp_device_io_config", entry);
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = check_device_buffer(e, out, sizeof(float) * floats * (size_t)e->P.n_envs * (size_t)e->ds.io.n_ext, name)) return rc;
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    if (int rc = launch()) return rc;
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+bool nonneg_finite(double v) { return v >= 0.0 && !std::isinf(v); }      // a penalty, a range, a margin; a NaN fails as well
 
 // ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images
 int upload(FtgpEnv* e, const Plan& pl, const Switches& sw)
@@ -1303,63 +1331,63 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
         memcpy(e->h_tables.get(), e->P.car_policy, sizeof e->P.car_policy);
         e->table_on_device = 0;
     }
-    if (!e->d_prev_abs) HIP_TRY(dev_alloc(e->d_prev_abs, sizeof(int32_t) * (size_t)e->P.n_cars));
-    if (!e->ev_io_in) HIP_TRY(make_event(e->ev_io_in, hipEventDisableTiming));
-    if (!e->ev_io_out) HIP_TRY(make_event(e->ev_io_out, hipEventDisableTiming));
+    if (!e->ds.d_prev_abs) HIP_TRY(dev_alloc(e->ds.d_prev_abs, sizeof(int32_t) * (size_t)e->P.n_cars));
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
     // a workgroup holds whole envs, so its car slot c runs entry c % cars_per_env (as ftgp_set_car_policies)
     for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->h_tables.get()[FTGP_MAX_CARS_PER_BLOCK + c] = slot[c % cpe];
     if (e->table_on_device == 1) e->table_on_device = -1;
-    DeviceIoArgs& A = e->io;
+    DeviceIoArgs& A = e->ds.io;
     A = DeviceIoArgs{};
     A.max_episode_steps = cfg->max_episode_steps; A.n_ext = n_ext; A.auto_reset = cfg->auto_reset ? 1 : 0;
     for (int k = 0, i = 0; k < FTGP_PAIR_STRIDE; ++k) A.ext_index[k] = (k < cpe && slot[k] == FTGP_POLICY_HOST) ? i++ : -1;
-    A.prev_abs = e->d_prev_abs.get();
+    A.prev_abs = e->ds.d_prev_abs.get();
     A.env_track = e->d_env_track.get();
-    e->io_repeat = cfg->action_repeat;
-    e->io_ready = true;
+    e->ds.repeat = cfg->action_repeat;
+    e->ds.ready = true;
     set_signals(e, FtgpDeviceSignals{ 1, 0.0f, 0, 0.0f });
-    e->con_on = false;
-    e->frame_on = false;
+    e->ds.con_on = false;
+    e->ds.frame_on = false;
     return 0;
 }
 
 int ftgp_device_io_frame(FtgpEnv* e, const FtgpDeviceFrame* frame)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_frame before ftgp_device_io_config%s");
-    if (!frame) { e->frame_on = false; return 0; }
+    if (!e->ds.ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_frame before ftgp_device_io_config%s");
+    if (!frame) { e->ds.frame_on = false; return 0; }
     if (frame->n_ahead < 0 || frame->n_ahead > FTGP_MAX_LOOKAHEAD) return fail(FTGP_ERR_ARG, "device_io_frame: n_ahead in 0 .. 16%s");
     if (frame->stride < 1 || frame->stride > FTGP_PATH_POINTS / 2) return fail(FTGP_ERR_ARG, "device_io_frame: stride in 1 .. 50%s");
     if (frame->reserved != 0) return fail(FTGP_ERR_ARG, "device_io_frame: reserved must be 0%s");
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_frame_rows(e)) return rc;
-    e->frame = *frame;
-    e->frame_on = true;
+    e->ds.frame = *frame;
+    e->ds.frame_on = true;
     return 0;
 }
 
 int ftgp_device_io_contacts(FtgpEnv* e, const FtgpDeviceContacts* contacts)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_contacts before ftgp_device_io_config%s");
-    if (!contacts) { e->con_on = false; return 0; }
-    if (!(contacts->wall_penalty >= 0.0f) || std::isinf(contacts->wall_penalty)) return fail(FTGP_ERR_ARG, "device_io_contacts: wall_penalty >= 0 and finite%s");
-    if (!(contacts->car_penalty >= 0.0f) || std::isinf(contacts->car_penalty)) return fail(FTGP_ERR_ARG, "device_io_contacts: car_penalty >= 0 and finite%s");
+    if (!e->ds.ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_contacts before ftgp_device_io_config%s");
+    if (!contacts) { e->ds.con_on = false; return 0; }
+    if (!nonneg_finite(contacts->wall_penalty)) return fail(FTGP_ERR_ARG, "device_io_contacts: wall_penalty >= 0 and finite%s");
+    if (!nonneg_finite(contacts->car_penalty)) return fail(FTGP_ERR_ARG, "device_io_contacts: car_penalty >= 0 and finite%s");
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_contact_rows(e)) return rc;
-    e->con = *contacts;
-    e->con_on = true;
+    e->ds.con = *contacts;
+    e->ds.con_on = true;
     return 0;
 }
 
 int ftgp_device_io_signals(FtgpEnv* e, const FtgpDeviceSignals* signals)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_signals before ftgp_device_io_config%s");
+    if (!e->ds.ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_signals before ftgp_device_io_config%s");
     const FtgpDeviceSignals s = signals ? *signals : FtgpDeviceSignals{ 1, 0.0f, 0, 0.0f };
     if (s.scan_pool < 1 || e->P.n_rays % s.scan_pool) return fail(FTGP_ERR_ARG, "device_io_signals: scan_pool >= 1 and a divisor of n_rays%s");
-    if (!(s.scan_max_range >= 0.0f) || std::isinf(s.scan_max_range)) return fail(FTGP_ERR_ARG, "device_io_signals: scan_max_range >= 0 and finite%s");
-    if (!(s.off_track_penalty >= 0.0f) || std::isinf(s.off_track_penalty)) return fail(FTGP_ERR_ARG, "device_io_signals: off_track_penalty >= 0 and finite%s");
+    if (!nonneg_finite(s.scan_max_range)) return fail(FTGP_ERR_ARG, "device_io_signals: scan_max_range >= 0 and finite%s");
+    if (!nonneg_finite(s.off_track_penalty)) return fail(FTGP_ERR_ARG, "device_io_signals: off_track_penalty >= 0 and finite%s");
     set_signals(e, s);
     return 0;
 }
@@ -1377,18 +1405,20 @@ int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevic
                            const FtgpDeviceStepFrame* frame)
 {
     if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
-    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
-    float* contact = contacts ? contacts->contact : nullptr;
-    float* final_contact = contacts ? contacts->final_contact : nullptr;
-    if ((contact || final_contact) && !e->con_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_contacts: contact buffers while contacts are off (ftgp_device_io_contacts)%s");
-    float* frame_out = frame ? frame->frame : nullptr;
-    float* final_frame = frame ? frame->final_frame : nullptr;
-    if ((frame_out || final_frame) && !e->frame_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_frame: frame buffers while the frame is off (ftgp_device_io_frame)%s");
+    FtgpEnv::DeviceStep& ds = e->ds;
+    if (!ds.ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
+    // the three optional kinds of rows: floats per row, the caller's two buffers and what a refusal calls them
+    struct Rows { const char* name; const char* final_name; size_t floats; float* out; float* final_out; };
+    const Rows st{ "state", "final_state", FTGP_STATE_FLOATS, extra ? extra->state : nullptr, extra ? extra->final_state : nullptr };
+    const Rows ct{ "contact", "final_contact", FTGP_CONTACT_FLOATS, contacts ? contacts->contact : nullptr, contacts ? contacts->final_contact : nullptr };
+    const Rows fr{ "frame", "final_frame", (size_t)(FTGP_FRAME_FIXED + 2 * ds.frame.n_ahead), frame ? frame->frame : nullptr, frame ? frame->final_frame : nullptr };
+    if ((ct.out || ct.final_out) && !ds.con_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_contacts: contact buffers while contacts are off (ftgp_device_io_contacts)%s");
+    if ((fr.out || fr.final_out) && !ds.frame_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_frame: frame buffers while the frame is off (ftgp_device_io_frame)%s");
     HIP_TRY(hipSetDevice(e->device));
-    DeviceIoArgs A = e->io;
-    DeviceSignalArgs S = e->sig;
-    S.state = extra ? extra->state : nullptr; S.final_state = extra ? extra->final_state : nullptr;
-    const bool signals = !e->sig_default || S.state || S.final_state || e->con_on || e->frame_on;
+    DeviceIoArgs A = ds.io;
+    DeviceSignalArgs S = ds.sig;
+    S.state = st.out; S.final_state = st.final_out;
+    const bool signals = !ds.sig_default || S.state || S.final_state || ds.con_on || ds.frame_on;
     const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
     if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
     if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
@@ -1396,40 +1426,35 @@ int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevic
     if (int rc = check_device_buffer(e, io->terminated, n_envs, "terminated")) return rc;
     if (int rc = check_device_buffer(e, io->truncated, n_envs, "truncated")) return rc;
     if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
-    if (S.state) if (int rc = check_device_buffer(e, S.state, sizeof(float) * FTGP_STATE_FLOATS * rows, "state")) return rc;
-    if (S.final_state) if (int rc = check_device_buffer(e, S.final_state, sizeof(float) * FTGP_STATE_FLOATS * rows, "final_state")) return rc;
-    if (contact) if (int rc = check_device_buffer(e, contact, sizeof(float) * FTGP_CONTACT_FLOATS * rows, "contact")) return rc;
-    if (final_contact) if (int rc = check_device_buffer(e, final_contact, sizeof(float) * FTGP_CONTACT_FLOATS * rows, "final_contact")) return rc;
-    const bool dense = e->frame_on && e->frame.dense_progress != 0;
-    if (e->frame_on) {
-        const size_t frame_bytes = sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * e->frame.n_ahead) * rows;
-        if (frame_out) if (int rc = check_device_buffer(e, frame_out, frame_bytes, "frame")) return rc;
-        if (final_frame) if (int rc = check_device_buffer(e, final_frame, frame_bytes, "final_frame")) return rc;
-        const size_t n_cars = (size_t)e->P.n_cars;
-        S.frame_rows = e->d_frame.get(); S.frame = frame_out; S.final_frame = final_frame;
-        S.frame_ahead = e->frame.n_ahead; S.frame_stride = e->frame.stride;
+    for (const Rows* r : { &st, &ct, &fr }) {
+        if (r->out) if (int rc = check_device_buffer(e, r->out, sizeof(float) * r->floats * rows, r->name)) return rc;
+        if (r->final_out) if (int rc = check_device_buffer(e, r->final_out, sizeof(float) * r->floats * rows, r->final_name)) return rc;
+    }
+    const bool dense = ds.frame_on && ds.frame.dense_progress != 0;
+    if (ds.frame_on) {
+        S.frame_rows = ds.d_frame.get(); S.frame = fr.out; S.final_frame = fr.final_out;
+        S.frame_ahead = ds.frame.n_ahead; S.frame_stride = ds.frame.stride;
         if (dense) {
-            S.frame_s0 = e->d_frame_s.get(); S.frame_s1 = e->d_frame_s.get() + n_cars;
-            S.frame_flag0 = e->d_frame_flag.get(); S.frame_flag1 = e->d_frame_flag.get() + n_cars;
+            S.frame_s0 = ds.d_frame_s.get(); S.frame_s1 = ds.d_frame_s.get() + e->P.n_cars;
+            S.frame_flag0 = ds.d_frame_flag.get(); S.frame_flag1 = ds.d_frame_flag.get() + e->P.n_cars;
         }
     }
-    if (e->con_on) {
-        S.contact_rows = e->d_contact.get(); S.contact = contact; S.final_contact = final_contact;
-        S.terminate_on_wall = e->con.terminate_on_wall ? 1 : 0; S.terminate_on_car = e->con.terminate_on_car ? 1 : 0;
-        S.wall_penalty = e->con.wall_penalty; S.car_penalty = e->con.car_penalty;
+    if (ds.con_on) {
+        S.contact_rows = ds.d_contact.get(); S.contact = ct.out; S.final_contact = ct.final_out;
+        S.terminate_on_wall = ds.con.terminate_on_wall ? 1 : 0; S.terminate_on_car = ds.con.terminate_on_car ? 1 : 0;
+        S.wall_penalty = ds.con.wall_penalty; S.car_penalty = ds.con.car_penalty;
     }
     A.action = io->action; A.obs = io->obs; A.reward = io->reward; A.terminated = io->terminated; A.truncated = io->truncated; A.final_obs = io->final_obs;
     A.vec4 = e->P.n_rays % 4 == 0 && (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
     hipStream_t caller = (hipStream_t)io->stream;
-    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
-    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
+    if (int rc = handle_waits_for_caller(e, caller)) return rc;
     const unsigned car_blocks = (unsigned)((e->P.n_cars + 255) / 256);
     hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
     if (dense) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 0)) return rc;          // s0: the pose the call begins with
-    if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, e->io_repeat, true)) return rc;
-    if (e->con_on) if (int rc = launch_contacts(e, e->d_contact.get(), nullptr)) return rc;
-    if (e->frame_on) if (int rc = launch_frame(e, e->frame.n_ahead, e->frame.stride, e->d_frame.get(), nullptr, 1)) return rc;
+    if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, ds.repeat, true)) return rc;
+    if (ds.con_on) if (int rc = launch_contacts(e, ds.d_contact.get(), nullptr)) return rc;
+    if (ds.frame_on) if (int rc = launch_frame(e, ds.frame.n_ahead, ds.frame.stride, ds.d_frame.get(), nullptr, 1)) return rc;
     if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, e->rule);
     else {
         const bool aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
@@ -1440,56 +1465,28 @@ int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevic
     HIP_TRY(hipGetLastError());
     e->rows_valid = false;
     if (A.auto_reset) e->launch_metrics_valid = false;     // the launch's record describes the state before the resets
-    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
-    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
-    return 0;
+    return caller_waits_for_handle(e, caller);
 }
 
 int ftgp_state_device(FtgpEnv* e, void* stream, float* state)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_state_device before ftgp_device_io_config%s");
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = check_device_buffer(e, state, sizeof(float) * FTGP_STATE_FLOATS * (size_t)e->P.n_envs * (size_t)e->io.n_ext, "state")) return rc;
-    hipStream_t caller = (hipStream_t)stream;
-    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
-    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
-    hipLaunchKernelGGL(ftgp_io_state_kernel, dim3((unsigned)((e->P.n_cars + 255) / 256)), dim3(256), 0, e->stream.get(), e->P, e->io, state);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
-    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
-    return 0;
+    return rows_to_device(e, "ftgp_state_device", stream, FTGP_STATE_FLOATS, state, "state", [&] {
+        hipLaunchKernelGGL(ftgp_io_state_kernel, dim3((unsigned)((e->P.n_cars + 255) / 256)), dim3(256), 0, e->stream.get(), e->P, e->ds.io, state);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 int ftgp_contacts_device(FtgpEnv* e, void* stream, float* contact)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_contacts_device before ftgp_device_io_config%s");
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = check_device_buffer(e, contact, sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_envs * (size_t)e->io.n_ext, "contact")) return rc;
-    hipStream_t caller = (hipStream_t)stream;
-    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
-    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
-    if (int rc = launch_contacts(e, nullptr, contact)) return rc;
-    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
-    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
-    return 0;
+    return rows_to_device(e, "ftgp_contacts_device", stream, FTGP_CONTACT_FLOATS, contact, "contact", [&] { return launch_contacts(e, nullptr, contact); });
 }
 
 int ftgp_frame_device(FtgpEnv* e, void* stream, float* frame)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (!e->io_ready) return fail(FTGP_ERR_STATE, "ftgp_frame_device before ftgp_device_io_config%s");
-    const int n_ahead = e->frame_on ? e->frame.n_ahead : 0, stride = e->frame_on ? e->frame.stride : 1;
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = check_device_buffer(e, frame, sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead) * (size_t)e->P.n_envs * (size_t)e->io.n_ext, "frame")) return rc;
-    hipStream_t caller = (hipStream_t)stream;
-    HIP_TRY(hipEventRecord(e->ev_io_in.get(), caller));
-    HIP_TRY(hipStreamWaitEvent(e->stream.get(), e->ev_io_in.get(), 0));
-    if (int rc = launch_frame(e, n_ahead, stride, nullptr, frame, -1)) return rc;
-    HIP_TRY(hipEventRecord(e->ev_io_out.get(), e->stream.get()));
-    HIP_TRY(hipStreamWaitEvent(caller, e->ev_io_out.get(), 0));
-    return 0;
+    const bool on = e && e->ds.frame_on;
+    const int n_ahead = on ? e->ds.frame.n_ahead : 0, stride = on ? e->ds.frame.stride : 1;
+    return rows_to_device(e, "ftgp_frame_device", stream, (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead), frame, "frame", [&] { return launch_frame(e, n_ahead, stride, nullptr, frame, -1); });
 }
 
 int ftgp_set_spawn_rule(FtgpEnv* e, const FtgpSpawnRule* r)
@@ -1502,9 +1499,9 @@ int ftgp_set_spawn_rule(FtgpEnv* e, const FtgpSpawnRule* r)
         if (r->first_point < 0 || r->first_point >= FTGP_PATH_POINTS) return fail(FTGP_ERR_ARG, "set_spawn_rule: first_point in 0 .. 99%s");
         if (r->n_points < 1 || r->n_points > FTGP_PATH_POINTS) return fail(FTGP_ERR_ARG, "set_spawn_rule: n_points in 1 .. 100%s");
         if (r->reserved != 0) return fail(FTGP_ERR_ARG, "set_spawn_rule: reserved must be 0%s");
-        if (!(r->margin >= 0.0) || std::isinf(r->margin)) return fail(FTGP_ERR_ARG, "set_spawn_rule: margin >= 0 and finite%s");
+        if (!nonneg_finite(r->margin)) return fail(FTGP_ERR_ARG, "set_spawn_rule: margin >= 0 and finite%s");
         if (!(r->lateral_frac >= 0.0 && r->lateral_frac <= 1.0)) return fail(FTGP_ERR_ARG, "set_spawn_rule: lateral_frac in [0, 1]%s");
-        if (!(r->yaw_tan >= 0.0) || std::isinf(r->yaw_tan)) return fail(FTGP_ERR_ARG, "set_spawn_rule: yaw_tan >= 0 and finite%s");
+        if (!nonneg_finite(r->yaw_tan)) return fail(FTGP_ERR_ARG, "set_spawn_rule: yaw_tan >= 0 and finite%s");
         for (size_t k = 0; k < T; ++k) {
             for (int p = 0; p < FTGP_PATH_POINTS; ++p) memcpy(&clear[2 * (FTGP_PATH_POINTS * k + p)], &e->start_table[6 * (FTGP_PATH_POINTS * k + p) + 4], sizeof(double) * 2);
             n_start[k] = ftgp_start_list(*r, &clear[2 * FTGP_PATH_POINTS * k], &start[FTGP_PATH_POINTS * k]);
@@ -1560,8 +1557,8 @@ int ftgp_get_contacts(FtgpEnv* e, float* out)
     if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_contact_rows(e)) return rc;
-    if (int rc = launch_contacts(e, e->d_contact.get(), nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->d_contact.get(), sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    if (int rc = launch_contacts(e, e->ds.d_contact.get(), nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->ds.d_contact.get(), sizeof(float) * FTGP_CONTACT_FLOATS * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
@@ -1573,8 +1570,8 @@ int ftgp_get_frames(FtgpEnv* e, int n_ahead, int stride, float* out)
     if (stride < 1 || stride > FTGP_PATH_POINTS / 2) return fail(FTGP_ERR_ARG, "ftgp_get_frames: stride in 1 .. 50%s");
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_frame_rows(e)) return rc;
-    if (int rc = launch_frame(e, n_ahead, stride, e->d_frame.get(), nullptr, -1)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->d_frame.get(), sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead) * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    if (int rc = launch_frame(e, n_ahead, stride, e->ds.d_frame.get(), nullptr, -1)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->ds.d_frame.get(), sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead) * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }
@@ -1756,7 +1753,7 @@ static int metrics_to_host(FtgpEnv* e, double* out)
         // An exchange that was begun on this very slot and not ended yet (one rank: its "exchange" IS the slot in pinned memory) promised the
         // record of the state at its begin: put that aside before the slot is refreshed with the present state's.
         if (e->gather_open && e->gather_slot == e->cur_slot && !e->comm && !e->gather_held) {
-            HIP_TRY(wait_event(e, e->gather_event));
+            HIP_TRY(hipEventSynchronize(e->gather_event));
             collect_slot(e, e->cur_slot, e->held);
             e->gather_held = true;
         }
@@ -1853,7 +1850,7 @@ int ftgp_metrics_allgather_end(FtgpEnv* e, double* out)
     if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
     if (!e->gather_open) return fail(FTGP_ERR_STATE, "ftgp_metrics_allgather_end without _begin%s");
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->gather_held) HIP_TRY(wait_event(e, e->gather_event));      // this exchange only: a later launch on the compute stream is not waited for
+    if (!e->gather_held) HIP_TRY(hipEventSynchronize(e->gather_event));      // this exchange only: a later launch on the compute stream is not waited for
     e->gather_open = false;
     if (e->comm) memcpy(out, e->h_gather.get(), sizeof(double) * FTGP_METRIC_DOUBLES * (size_t)e->world);
     else if (e->gather_held) memcpy(out, e->held, sizeof e->held);
@@ -1910,7 +1907,7 @@ int ftgp_last_kernel_ms(FtgpEnv* e, float* ms)
     if (!e || !ms) return fail(FTGP_ERR_ARG, "null argument%s");
     if (!e->timed) return fail(FTGP_ERR_STATE, "no step/rollout has been launched yet%s");
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_event(e, e->ev_stop[e->cur_slot].get()));
+    HIP_TRY(hipEventSynchronize(e->ev_stop[e->cur_slot].get()));
     HIP_TRY(hipEventElapsedTime(ms, e->ev_start.get(), e->ev_stop[e->cur_slot].get()));
     return 0;
 }

@@ -1833,23 +1833,11 @@ __device__ __forceinline__ void spawn_state(const DeviceParams& P, const FtgpSpa
     s.qw = qw; s.qz = qz;
 }
 
-// car ci back at its spawn pose with a cleared race state; car 0 of the env also zeroes the env's steps (ftgp_reset_kernel,
-// ftgp_io_finish_kernel).  episode: the env's episode counter as every car of the env read it before anyone advances it (spawn rule only).
+// car ci back at its spawn pose with a cleared race state; car 0 of the env also zeroes the env's steps (ftgp_reset_kernel and both finish
+// kernels).  episode: the env's episode counter as every car of the env read it before anyone advances it (spawn rule only).  The record is
+// reset where it lies, without a copy on the lane's stack -- K3 reaches start / finish_step through a pointer, which would keep such a copy
+// in scratch memory
 __device__ __forceinline__ void reset_car(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track, const FtgpSpawnDev* __restrict__ R, int64_t episode)
-{
-    const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
-    const int trk = env_track_of(env_track, env);
-    CarCore s;
-    spawn_state(P, R, episode, ci, env, car, trk, s);
-    if (car == 0) P.steps[env] = 0;
-    for (int k = 0; k < FTGP_MAX_LAP_TIMES; ++k) P.cars[ci].times[k] = 0.0;
-    progress_lane(P, P.path + (size_t)trk * 2 * FTGP_PATH_POINTS, s, 0, P.cars[ci].times);
-    static_cast<CarCore&>(P.cars[ci]) = s;
-}
-
-// reset_car on the record where it lies (ftgp_io_finish_signals_kernel): the same operations on the same values, without a copy of the
-// record on the lane's stack -- K3 reaches start / finish_step through a pointer, which keeps such a copy in scratch memory
-__device__ __forceinline__ void reset_car_in_place(const DeviceParams& P, int ci, const int32_t* __restrict__ env_track, const FtgpSpawnDev* __restrict__ R, int64_t episode)
 {
     const int env = ci / P.cars_per_env, car = ci % P.cars_per_env;
     const int trk = env_track_of(env_track, env);
@@ -2475,7 +2463,7 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
         __syncthreads();
     }
     if (reset && t < cpe) {
-        reset_car_in_place(P, ci0 + t, A.env_track, rule, episode);      // (the records were read before the first barrier, and by this lane above)
+        reset_car(P, ci0 + t, A.env_track, rule, episode);      // (the records were read before the first barrier, and by this lane above)
         if (mine && S.state) state_row(P.cars[ci0 + t], S.state + my_row * FTGP_STATE_FLOATS);
         if (mine && S.frame_rows && S.frame)      // the frame at the spawn pose: a look-ahead of zeros would be a lie
             frame_row_lane(P.path + (size_t)env_track_of(A.env_track, env) * 2 * FTGP_PATH_POINTS, P.cars[ci0 + t], S.frame_ahead, S.frame_stride,

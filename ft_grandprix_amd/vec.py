@@ -226,27 +226,22 @@ class DeviceVecEnv:
                                        self.truncated.data_ptr(), self.final_obs.data_ptr())
         self._io_ref = ctypes.byref(self._io)
         self._step_device = lib.fn("step_device")
-        self.state = self.final_state = None
-        if state:           # ftgp_step_device_ex: a state row per agent (capi.STATE_FIELDS)
-            self.state = torch.zeros((n_envs, self.n_agents, capi.STATE_FLOATS), dtype=torch.float32, **z)
-            self.final_state = torch.zeros_like(self.state)
-            self._extra = capi.FtgpDeviceStepExtra(self.state.data_ptr(), self.final_state.data_ptr())
-            self._extra_ref = ctypes.byref(self._extra)
-            self._step_device_ex = lib.fn("step_device_ex")
-        self.contact = self.final_contact = None
-        if self.contacts:   # ftgp_step_device_contacts: a contact row per agent (capi.CONTACT_FIELDS)
-            self.contact = torch.zeros((n_envs, self.n_agents, capi.CONTACT_FLOATS), dtype=torch.float32, **z)
-            self.final_contact = torch.zeros_like(self.contact)
-            self._con = capi.FtgpDeviceStepContacts(self.contact.data_ptr(), self.final_contact.data_ptr())
-            self._con_ref = ctypes.byref(self._con)
-            self._step_device_contacts = lib.fn("step_device_contacts")
-        self.frame = self.final_frame = None
-        if self.track_frame:   # ftgp_step_device_frame: a frame row per agent (capi.FRAME_FIELDS, then the look-ahead points)
-            self.frame = torch.zeros((n_envs, self.n_agents, capi.FRAME_FIXED + 2 * lookahead), dtype=torch.float32, **z)
-            self.final_frame = torch.zeros_like(self.frame)
-            self._frame = capi.FtgpDeviceStepFrame(self.frame.data_ptr(), self.final_frame.data_ptr())
-            self._frame_ref = ctypes.byref(self._frame)
-            self._step_device_frame = lib.fn("step_device_frame")
+        self._step_device_frame = lib.fn("step_device_frame")
+        # The optional rows, one per agent: name, on?, floats per row (capi.STATE_FIELDS; capi.CONTACT_FIELDS; capi.FRAME_FIELDS, then the
+        # look-ahead points) and the argument struct of ftgp_step_device_frame that carries the two buffers.  An absent channel leaves
+        # its two attributes None and hands the library a null struct.
+        channels = (("state", bool(state), capi.STATE_FLOATS, capi.FtgpDeviceStepExtra),
+                    ("contact", self.contacts, capi.CONTACT_FLOATS, capi.FtgpDeviceStepContacts),
+                    ("frame", self.track_frame, capi.FRAME_FIXED + 2 * lookahead, capi.FtgpDeviceStepFrame))
+        self._row_info, self._row_refs = {}, []
+        for name, on, width, struct in channels:
+            out = torch.zeros((n_envs, self.n_agents, width), dtype=torch.float32, **z) if on else None
+            final = torch.zeros_like(out) if on else None
+            setattr(self, name, out)
+            setattr(self, "final_" + name, final)
+            if on:
+                self._row_info[name], self._row_info["final_" + name] = out, final
+            self._row_refs.append(ctypes.byref(struct(out.data_ptr(), final.data_ptr())) if on else None)
 
     def reset(self):
         """Reset every env (synchronous ftgp_reset, which follows the start rule); obs = the scans right after a reset, all zeros
@@ -282,28 +277,15 @@ class DeviceVecEnv:
         self._check_actions(actions)
         self._io.action = actions.data_ptr()
         self._io.stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.state is None and self.contact is None and self.frame is None:
+        if not self._row_info:
             rc = self._step_device(self.env.h, self._io_ref)      # Env.step_device, without rebuilding the argument block
             if rc:
                 self.env.lib.check(rc)
             return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
-        extra = None if self.state is None else self._extra_ref
-        if self.frame is not None:
-            rc = self._step_device_frame(self.env.h, self._io_ref, extra, None if self.contact is None else self._con_ref, self._frame_ref)
-        elif self.contact is None:
-            rc = self._step_device_ex(self.env.h, self._io_ref, extra)
-        else:
-            rc = self._step_device_contacts(self.env.h, self._io_ref, extra, self._con_ref)
+        rc = self._step_device_frame(self.env.h, self._io_ref, *self._row_refs)    # a null struct for an absent channel
         if rc:
             self.env.lib.check(rc)
-        info = {"final_obs": self.final_obs}
-        if self.state is not None:
-            info["state"], info["final_state"] = self.state, self.final_state
-        if self.contact is not None:
-            info["contact"], info["final_contact"] = self.contact, self.final_contact
-        if self.frame is not None:
-            info["frame"], info["final_frame"] = self.frame, self.final_frame
-        return self.obs, self.reward, self.terminated, self.truncated, info
+        return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs, **self._row_info}
 
     def close(self):
         if getattr(self, "env", None) is not None:

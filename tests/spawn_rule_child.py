@@ -254,6 +254,33 @@ def errors(opt):
 
 
 # ------------------------------------------------------------------------------------------------------------------ auto-reset
+def finish_kernels_agree(track, dev):
+    """Two device handles, one rule, one stream of actions: P goes through ftgp_io_finish_kernel, S -- state rows, which change no episode
+    -- through ftgp_io_finish_signals_kernel.  The whole record of every car, the progress rows and the steps are equal after every
+    call, and every env is reset within a few of them."""
+    from ft_grandprix_amd.vec import DeviceVecEnv
+    kw = dict(n_envs=8, n_rays=8, cars_per_env=3, roster=["agent", "nidc", "agent"], max_episode_steps=4, action_repeat=2, device_id=0,
+              start_margin=RULE.margin, start_lateral=RULE.lateral_frac, start_yaw_jitter=0.2, shuffle_grid=True, lap_target=1,
+              spawn_mode=1, seed=SEED)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2)
+    with DeviceVecEnv(track, **kw) as P, DeviceVecEnv(track, state=True, **kw) as S:
+        obs = P.reset().clone()
+        S.reset()
+        for call in range(8):
+            act = torch_driver(torch, obs, gen, dev)
+            obs = P.step(act)[0].clone()
+            o = S.step(act)[0].clone()
+            torch.cuda.synchronize()
+            at = f" through both finish kernels, call {call}"
+            np.testing.assert_array_equal(o.cpu().numpy(), obs.cpu().numpy(), err_msg="obs" + at)
+            np.testing.assert_array_equal(bits(S.env.snapshot()), bits(P.env.snapshot()), err_msg="snapshot" + at)
+            np.testing.assert_array_equal(S.env.progress(), P.env.progress(), err_msg="progress" + at)
+            np.testing.assert_array_equal(S.env.steps(), P.env.steps(), err_msg="steps" + at)
+        assert P.episode_index().min() >= 3 and np.array_equal(P.episode_index(), S.episode_index()), (P.episode_index(), S.episode_index())
+    print("both finish kernels: 8 calls, every env reset at least twice, records equal")
+
+
 def auto_reset(opt):
     from ft_grandprix_amd import capi
     from ft_grandprix_amd.track import load_track
@@ -330,6 +357,7 @@ def auto_reset(opt):
     assert resets.min() >= 3, resets
     venv.close()
     B.close()
+    finish_kernels_agree(track, dev)
     print("auto_reset ok")
 
 
