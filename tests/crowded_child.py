@@ -3,7 +3,7 @@
     python tests/crowded_child.py <scenario> [json options]
 
 Every scenario runs envs of 6 to 8 cars (a few of 2 and 5 for the binary64 models) on the product, against the CPU oracle bit for bit
-and -- `rays`, `contacts` -- against the binary64 models of tests/test_crowded_envs.py.  FTGP_VERBOSE is set: ftgp_create's lines about
+and -- `rays`, `contacts` -- against the binary64 models of tests/crowded_model.py.  FTGP_VERBOSE is set: ftgp_create's lines about
 the workgroup shape and the inter-vehicle test go to stderr, where the parent reads them.
 """
 import json
@@ -18,11 +18,9 @@ if ROOT not in sys.path:
 
 os.environ["FTGP_VERBOSE"] = "1"
 
-
-def libs():
-    from ft_grandprix_amd import capi
-    from tests.helpers import load_oracle
-    return capi.load(), load_oracle()
+from tests import crowded_model as T  # noqa: E402
+from tests.crowded_model import FINISHERS, finish_by_teleport  # noqa: E402
+from tests.helpers import libs, open_field, same  # noqa: E402
 
 
 def pair(product, oracle, track, **kw):
@@ -30,18 +28,6 @@ def pair(product, oracle, track, **kw):
     g, o = capi.Env(product, track, **kw), capi.Env(oracle, track, **kw)
     oracle.dll.oracle_set_threads(o.h, 8)
     return g, o
-
-
-def same(g, o, what):
-    """Bit for bit: the state as tests/test_gpu_parity.py compares it, the controls, the winners, the metrics record."""
-    from tests.test_gpu_parity import assert_same_state
-    try:
-        assert_same_state(g, o)
-        np.testing.assert_array_equal(g.ctrl(), o.ctrl())
-        np.testing.assert_array_equal(g.winners(), o.winners())
-        np.testing.assert_array_equal(g.metrics_local(), o.metrics_local())
-    except AssertionError as x:
-        raise AssertionError(f"{what}\n{x}") from None
 
 
 def set_rest_pose(e, pos, yaw):
@@ -53,8 +39,7 @@ def set_rest_pose(e, pos, yaw):
 
 
 def roster_of(cpe):
-    from tests.test_crowded_envs import ROSTER
-    return ROSTER[cpe]
+    return T.ROSTER[cpe]
 
 
 def drive(envs, policy, n):
@@ -76,7 +61,6 @@ def smallest(opt):
 
 def rays(opt):
     """A ray scene of section A on the product: the binary64 model's assertions."""
-    from tests import test_crowded_envs as T
     product, _ = libs()
     T.check_rays(product, tuple(opt["scene"]))
     print("rays ok")
@@ -85,8 +69,6 @@ def rays(opt):
 def contacts(opt):
     """A contact scene of section A on the product: the binary64 model's assertions for the step from rest; then product = oracle after
     that step and after 200 more under the random policy."""
-    from tests import test_crowded_envs as T
-    from tests.test_k1_invariants import open_field
     product, oracle = libs()
     if "scene" in opt:
         cpe, R, half_width, n_envs, seed = opt["scene"]
@@ -245,26 +227,6 @@ def masked_reset(opt):
     print("masked reset ok")
 
 
-FINISHERS = ((0, 1), (0, 4), (0, 6), (1, 5), (1, 7))             # (env, slot)
-
-
-def finish_by_teleport(envs, track, cpe):
-    """Ten steps with the FINISHERS put onto path points start + 25, 50, 75, 99, 0, 1, ... (K3's crossing logic: laps_by_teleport of
-    tests/test_oracle_golden.py); every other car is left alone."""
-    path = np.asarray(track.path, dtype=np.float64)
-    for ahead in (25, 50, 75, 99, 0, 1, 2, 3, 4, 5):
-        for e in envs:
-            pose = e.pose()
-            for env, slot in FINISHERS:
-                q = ((slot + 5) * 2 + ahead) % 100                 # spawn_mode 0: slot s starts on path[(s + 5) * 2] (custom.py:1112)
-                a = np.arctan2(path[(q + 1) % 100, 1] - path[q, 1], path[(q + 1) % 100, 0] - path[q, 0])
-                row = pose[env * cpe + slot]
-                row[0], row[1], row[3], row[6] = path[q, 0], path[q, 1], np.cos(a / 2), np.sin(a / 2)
-                row[7:] = 0.0
-            e.set_pose(pose)
-            e.step(1)
-
-
 def finished_mates(opt):
     """B.3: five of the sixteen cars of two 8-car envs finish (slots 4 to 7 among them): they turn invisible, touch nothing, get the null
     driver and read 0."""
@@ -331,8 +293,6 @@ def puck_margin(opt):
     """B.6: a vehicle whose puck lies only `margin` inside its box behind, mates at the far end of a wall-free map, heading away: the
     specification's min(box, puck) is not the box's time there, and the product must give the oracle's bits."""
     from ft_grandprix_amd import capi
-    from tests import test_crowded_envs as T
-    from tests.test_k1_invariants import open_field
     product, oracle = libs()
     n_envs = opt.get("n_envs", 400)
     v = T.slim_vehicle(product, opt["margin"])

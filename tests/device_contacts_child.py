@@ -6,7 +6,7 @@ ft_grandprix_amd/vec.py).  Exit status 0 = the scenario held; anything else fail
 `static`: poses put with set_pose; ftgp_get_contacts and ftgp_contacts_device against the numpy model of the header
 (tests/contacts_model.py), bit for bit.
 `twin`: a DeviceVecEnv with contacts (handle A) against a twin handle B on the host path, bit for bit at every call, after `twin` of
-tests/device_signals_child.py.  What A must write is modelled from B's host read-backs alone -- the contact rows from pose() and
+tests/device_signals_child.py (the twins: tests/device_twin.py).  What A must write is modelled from B's host read-backs alone -- the contact rows from pose() and
 progress() -- so every count a scenario asserts (`need`) is a count of B's data.
 `off`, `zero`, `errors`: contacts off is the old call; a struct of zeros writes rows and changes nothing else; what must be refused.
 """
@@ -22,16 +22,15 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402  (before the library is loaded)
 
 from tests import contacts_model as cm  # noqa: E402
-from tests import signals_model as sm  # noqa: E402
-from tests.device_signals_child import HostTwin, _same_pose, _apply, _same_state, _tracks, push_off, teleport, torch_driver  # noqa: E402
+from tests import crowded_model as TC  # noqa: E402
+from tests import walls_model as TW  # noqa: E402
+from tests.device_twin import ContactTwin, _apply, _same_pose, _same_state, _tracks, push_off, refused, teleport, torch_driver  # noqa: E402
+from tests.helpers import open_field  # noqa: E402
 
 
 # ------------------------------------------------------------------------------------------------------------------ static scenes
 def static(opt):
     from ft_grandprix_amd import capi
-    from tests import test_crowded_envs as TC
-    from tests import test_walls_model as TW
-    from tests.test_k1_invariants import open_field
     lib = capi.load()
     roster = opt.get("roster")
     if "scene" in opt:
@@ -102,70 +101,6 @@ def nose_to_tail(handles, envs, behind, ahead, cpe, gap=0.18):
         b[:] = a
         b[0], b[1] = a[0] - gap * np.cos(yaw), a[1] - gap * np.sin(yaw)
     _apply(handles, pose)
-
-
-class ContactTwin(HostTwin):
-    """HostTwin with the contact rules of include/ftgp.h on top."""
-
-    def __init__(self, B, roster, paths, tracks, envs_per_track, vehicle, con, **kw):
-        super().__init__(B, roster, paths, **kw)
-        self.tracks, self.envs_per_track, self.vehicle = tracks, envs_per_track, vehicle
-        self.term_wall, self.term_car = con["terminate_on_wall"], con["terminate_on_car"]
-        self.wall_penalty, self.car_penalty = np.float32(con["wall_penalty"]), np.float32(con["car_penalty"])
-        self.count.update(wall_term=0, car_term=0, wall_penalised=0, car_penalised=0, final_wall=0, final_car=0, wall_rows=0, car_rows=0)
-
-    def contacts(self):
-        B = self.B
-        rows = cm.contact_rows_blocks(self.tracks, self.envs_per_track, self.vehicle, B.pose(), B.progress()[:, 4], self.cpe, False)
-        return self._ext(rows)
-
-    def call(self, a):
-        B, n, cpe, ext = self.B, self.n, self.cpe, self.ext
-        p0 = B.progress()
-        for _ in range(self.repeat):
-            fin = B.progress()[:, 4].reshape(n, cpe)
-            ctrl = np.zeros((n, cpe, 2), dtype=np.float64)
-            if self.bundled:
-                ctrl = B.policy_eval("per_car", B.lidar()).reshape(n, cpe, 2)
-            ctrl[:, ext] = np.where(fin[:, ext, None] != 0, 0.0, a)
-            B.set_ctrl(ctrl, self.car_mask if self.bundled else None)
-            B.step(1)
-        p1 = B.progress()
-        contact = self.contacts()                                   # at the pose after the call's steps, before any reset
-        wall, car = contact[:, :, cm.WALL_COUNT] > 0, contact[:, :, cm.CAR_COUNT] > 0
-        off = self._ext(p1[:, 5]) != 0
-        reward = self._ext(p1[:, 3] - p0[:, 3]).astype(np.float32)
-        reward = np.where(off, reward - self.penalty, reward).astype(np.float32)
-        reward = np.where(wall, reward - self.wall_penalty, reward).astype(np.float32)
-        reward = np.where(car, reward - self.car_penalty, reward).astype(np.float32)
-        fin_all = (self._ext(p1[:, 4]) != 0).all(axis=1)
-        old = fin_all | (bool(self.term_off) & off.any(axis=1))
-        by_wall, by_car = bool(self.term_wall) & wall.any(axis=1), bool(self.term_car) & car.any(axis=1)
-        term = old | by_wall | by_car
-        trunc = ~term & (self.max_steps > 0) & (B.steps() >= self.max_steps)
-        lid = self._ext(B.lidar())
-        obs = sm.pool_scan(lid, self.pool, self.M)
-        state = self.state()
-        ended = term | trunc
-        out = dict(reward=reward, terminated=term, truncated=trunc, ended=ended, off=off, by_wall=by_wall, by_car=by_car,
-                   final_obs=None, final_state=None, final_contact=None)
-        c = self.count
-        if self.auto_reset and ended.any():
-            out["final_obs"], out["final_state"], out["final_contact"] = obs[ended].copy(), state[ended].copy(), contact[ended].copy()
-            c["final_wall"] += int(wall[ended].sum()); c["final_car"] += int(car[ended].sum())
-            B.reset(ended.astype(np.uint8))
-            obs[ended] = 0.0
-            contact = contact.copy()
-            contact[ended] = 0.0
-            state = self.state()
-        out["obs"], out["state"], out["contact"] = obs, state, contact
-        c["wall_term"] += int((by_wall & ~old).sum()); c["car_term"] += int((by_car & ~old & ~by_wall).sum())
-        c["off_term"] += int((term & ~fin_all & off.any(axis=1)).sum()); c["fin_term"] += int(fin_all.sum()); c["trunc"] += int(trunc.sum())
-        c["wall_rows"] += int(wall.sum()); c["car_rows"] += int(car.sum())
-        c["wall_penalised"] += int(wall.sum()) if self.wall_penalty > 0 else 0
-        c["car_penalised"] += int(car.sum()) if self.car_penalty > 0 else 0
-        c["penalised"] += int(off.sum())
-        return out
 
 
 def twin(opt):
@@ -349,14 +284,6 @@ def errors(opt):
     from ft_grandprix_amd.vec import DeviceVecEnv
     track = load_track("small-circle")
     lib = capi.load()
-
-    def refused(code, what, f, *a, **k):
-        try:
-            f(*a, **k)
-        except capi.FtgpError as x:
-            assert x.code == code, (what, x)
-        else:
-            raise AssertionError(f"{what} was accepted")
 
     with capi.Env(lib, track, n_envs=8, n_rays=8) as e:
         refused(-4, "contacts before device_io_config", e.device_io_contacts, True)

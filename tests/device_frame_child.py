@@ -24,21 +24,13 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402  (before the library is loaded)
 
 from tests import frame_model as fm  # noqa: E402
+from tests.device_twin import refused  # noqa: E402
+from tests.helpers import open_field  # noqa: E402
 
 DEV = "cuda:0"
 STATE, ARG = -4, -1          # FTGP_ERR_STATE, FTGP_ERR_ARG
 COUNTS = (1, 15, 16, 17, 37)
 AHEAD, STRIDES = (0, 1, 16), (1, 7, 50)
-
-
-def refused(code, what, f, *a, **k):
-    from ft_grandprix_amd import capi
-    try:
-        f(*a, **k)
-    except capi.FtgpError as x:
-        assert x.code == code, (what, x)
-    else:
-        raise AssertionError(f"{what} was accepted")
 
 
 def put(pose, rows):
@@ -51,11 +43,9 @@ def put(pose, rows):
 
 
 def square_track():
-    """`skew_path` of tests/test_device_frame.py in an empty 40 x 40 field: the hand-written square with point 11 on point 10, and with
+    """`skew_path` of tests/frame_model.py in an empty 40 x 40 field: the hand-written square with point 11 on point 10, and with
     point 99 moved so that outside the corner at point 0 rounding takes segment 99 -> 0 with t = 1 and s wraps."""
-    from tests.test_device_frame import skew_path
-    from tests.test_k1_invariants import open_field
-    return dataclasses.replace(open_field(200), path=skew_path(), name="square")
+    return dataclasses.replace(open_field(200), path=fm.skew_path(), name="square")
 
 
 def pose_pool(path, rng, square):
@@ -72,8 +62,7 @@ def pose_pool(path, rng, square):
         for dx, dy in ((0.5, 0.5), (-0.5, -0.5), (0.5, -0.5), (-0.5, 0.5), (0.125, -0.125)):
             pool.append((P(i)[0] + dx, P(i)[1] + dy, 0.7))
     if square:
-        from tests.test_device_frame import SKEW_WRAP_POSE
-        pool += [(*SKEW_WRAP_POSE, 0.3), (P(0)[0] - 0.125, P(0)[1] - 0.5, -2.5)]                 # a = 99 with t = 1 by rounding: s wraps to 0
+        pool += [(*fm.SKEW_WRAP_POSE, 0.3), (P(0)[0] - 0.125, P(0)[1] - 0.5, -2.5)]                 # a = 99 with t = 1 by rounding: s wraps to 0
         pool += [(P(10)[0], P(10)[1] + 0.25, 0.0), (P(10)[0] + 0.125, P(10)[1] - 0.25, 2.0), (P(11)[0], P(11)[1], -1.0)]     # the duplicated point
     for i in (3, 40, 77):                                        # off the track
         pool += [(P(i)[0] + 3.0, P(i)[1] - 2.0, 1.0), (P(i)[0] - 1.0, P(i)[1] + 0.25, -2.0)]

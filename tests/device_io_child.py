@@ -37,31 +37,6 @@ def guard(order):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU scenarios
-def _spawn_point(env, car, cpe, env_base=0):
-    return (10 + 7 * (env_base + env) + 2 * car) % 98          # spawn_mode 1 (ftgp_reset_kernel)
-
-
-def _teleport(handles, track, envs, cars, cpe):
-    """Move the given cars of the given envs, on every handle alike, to the last centre-line point of their lap (through 40 % and
-    80 % of it, so that the progress rule counts no crossing): a short drive forward then finishes the lap.  ftgp_set_pose +
-    ftgp_eval_progress: host calls that both twins make identically."""
-    import numpy as np
-    path = np.asarray(track.path, dtype=np.float64)
-    pose = handles[0].pose()
-    for h in handles[1:]:
-        np.testing.assert_array_equal(h.pose(), pose)
-    for frac in (40, 80, 99):
-        for e in envs:
-            for c in cars:
-                q = (_spawn_point(e, c, cpe) + frac) % 100
-                a = np.arctan2(path[(q + 1) % 100, 1] - path[q, 1], path[(q + 1) % 100, 0] - path[q, 0])
-                row = pose[e * cpe + c]
-                row[0], row[1], row[3], row[6] = path[q, 0], path[q, 1], np.cos(a / 2), np.sin(a / 2)
-        for h in handles:
-            h.set_pose(pose)
-            h.eval_progress()
-
-
 def twin(opt):
     """DeviceVecEnv (handle A) against the host path (twin B), bit for bit, every call."""
     import torch
@@ -69,6 +44,7 @@ def twin(opt):
     from ft_grandprix_amd import capi
     from ft_grandprix_amd.track import load_track
     from ft_grandprix_amd.vec import DeviceVecEnv
+    from tests.device_twin import teleport
 
     n_envs, n_rays, cpe = opt.get("n_envs", 256), opt.get("n_rays", 1080), opt.get("cars_per_env", 1)
     roster = opt.get("roster", ["agent"] * cpe)
@@ -76,6 +52,7 @@ def twin(opt):
     calls, side = opt.get("calls", 1500), opt.get("side_stream", False)
     kw = dict(lap_target=1, spawn_mode=1, seed=7, lidar_mode=opt.get("lidar_mode", "rangefinder"))
     track = load_track(opt.get("track", "small-circle"))
+    paths = [np.asarray(track.path, dtype=np.float64)] * n_envs
     dev = torch.device("cuda", 0)
     venv = DeviceVecEnv(track, n_envs=n_envs, n_rays=n_rays, cars_per_env=cpe, roster=roster, max_episode_steps=M,
                         action_repeat=R, auto_reset=AR, device_id=0, **kw)
@@ -94,7 +71,7 @@ def twin(opt):
     n_term = n_trunc = 0
     for call in range(calls):
         if call % 60 == 5:                        # bring some envs to the end of their lap: terminations
-            _teleport([venv.env, B], track, [e for e in range(n_envs) if (e + call) % 5 == 0], ext, cpe)
+            teleport([venv.env, B], paths, [e for e in range(n_envs) if (e + call) % 5 == 0], ext, cpe, rolling=False)
         with torch.cuda.stream(stream):
             # a torch driver: steer towards the longest range of the front half, speed ~ U(0.5, 3); then noise, some of it past the
             # ctrlrange (speed, steer)

@@ -18,151 +18,7 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 
 from tests import signals_model as sm  # noqa: E402
-
-
-def _spawn_point(env, car):
-    return (10 + 7 * env + 2 * car) % 98          # spawn_mode 1 (ftgp_reset_kernel)
-
-
-def _same_pose(handles):
-    pose = handles[0].pose()
-    for h in handles[1:]:
-        np.testing.assert_array_equal(h.pose(), pose)
-    return pose
-
-
-def _apply(handles, pose):
-    for h in handles:
-        h.set_pose(pose)
-        h.eval_progress()
-
-
-def teleport(handles, paths, envs, cars, cpe):
-    """The given cars, on every handle alike, to the last centre-line point of their lap (through 40 % and 80 % of it, so that the
-    progress rule counts no crossing), rolling along the line at 3 units/s: a short drive then finishes the lap."""
-    pose = _same_pose(handles)
-    for frac in (40, 80, 99):
-        for e in envs:
-            for c in cars:
-                path = paths[e]
-                q = (_spawn_point(e, c) + frac) % 100
-                a = np.arctan2(path[(q + 1) % 100, 1] - path[q, 1], path[(q + 1) % 100, 0] - path[q, 0])
-                row = pose[e * cpe + c]
-                row[0], row[1], row[3], row[6] = path[q, 0], path[q, 1], np.cos(a / 2), np.sin(a / 2)
-                row[7], row[8], row[12] = 3.0 * np.cos(a), 3.0 * np.sin(a), 0.0
-        _apply(handles, pose)
-
-
-def push_off(handles, paths, envs, cars, cpe, dist=1.5):
-    """The given cars, on every handle alike, `dist` units off the centre-line, along the normal at the point nearest to them."""
-    pose = _same_pose(handles)
-    for e in envs:
-        for c in cars:
-            path, row = paths[e], pose[e * cpe + c]
-            q = int(((path - row[0:2]) ** 2).sum(axis=1).argmin())
-            t = path[(q + 1) % 100] - path[(q - 1) % 100]
-            n = np.array([-t[1], t[0]]) / np.hypot(t[0], t[1])
-            row[0], row[1] = path[q, 0] + dist * n[0], path[q, 1] + dist * n[1]
-    _apply(handles, pose)
-
-
-class HostTwin:
-    """Handle B and what a device call must have written, from its host read-backs."""
-
-    def __init__(self, B, roster, paths, pool, M, penalty, term_off, max_steps, repeat, auto_reset, dist2_of=None):
-        self.B, self.roster, self.cpe = B, roster, len(roster)
-        self.ext = [k for k, r in enumerate(roster) if r == "agent"]
-        self.bundled = len(self.ext) < self.cpe
-        self.car_paths = np.repeat(np.asarray(paths), self.cpe, axis=0)          # [n_cars, 100, 2]
-        self.pool, self.M, self.penalty, self.term_off = pool, M, np.float32(penalty), term_off
-        self.max_steps, self.repeat, self.auto_reset = max_steps, repeat, auto_reset
-        self.dist2_of = dist2_of or (lambda b: b.centre_dist2())
-        self.n = B.n_envs
-        self.car_mask = np.zeros((self.n, self.cpe), dtype=np.uint8)
-        self.car_mask[:, self.ext] = 1
-        self.count = dict(off_term=0, fin_term=0, trunc=0, clipped=0, mixed=0, all_miss=0, penalised=0)
-        if self.bundled:
-            B.set_car_policies(["lobotomy" if r == "agent" else r for r in roster])
-
-    def _ext(self, x):
-        return x.reshape((self.n, self.cpe) + x.shape[1:])[:, self.ext]
-
-    def state(self):
-        B = self.B
-        d2, pose, prog = self.dist2_of(B), B.pose(), B.progress()
-        racing = prog[:, 4] == 0
-        # the stored field is the model's value, to the bit: the same subtractions, squares, sum and comparisons (no fused operation)
-        np.testing.assert_array_equal(d2[racing], sm.centre_dist2(pose, self.car_paths)[racing], err_msg="centre_dist2 against numpy")
-        return self._ext(sm.state_rows(pose, B.ctrl(), prog, d2))
-
-    def call(self, a):
-        """One device call on B with actions a float64 [n_envs, n_ext, 2]; returns what A must hold."""
-        B, n, cpe, ext = self.B, self.n, self.cpe, self.ext
-        p0 = B.progress()
-        for _ in range(self.repeat):
-            fin = B.progress()[:, 4].reshape(n, cpe)
-            ctrl = np.zeros((n, cpe, 2), dtype=np.float64)
-            if self.bundled:
-                ctrl = B.policy_eval("per_car", B.lidar()).reshape(n, cpe, 2)
-            ctrl[:, ext] = np.where(fin[:, ext, None] != 0, 0.0, a)
-            B.set_ctrl(ctrl, self.car_mask if self.bundled else None)
-            B.step(1)
-        p1 = B.progress()
-        off = self._ext(p1[:, 5]) != 0
-        reward = self._ext(p1[:, 3] - p0[:, 3]).astype(np.float32)
-        reward = np.where(off, reward - self.penalty, reward).astype(np.float32)
-        fin_all = (self._ext(p1[:, 4]) != 0).all(axis=1)
-        term = fin_all | (bool(self.term_off) & off.any(axis=1))
-        trunc = ~term & (self.max_steps > 0) & (B.steps() >= self.max_steps)
-        lid = self._ext(B.lidar())
-        obs = sm.pool_scan(lid, self.pool, self.M)
-        state = self.state()
-        ended = term | trunc
-        out = dict(reward=reward, terminated=term, truncated=trunc, ended=ended, off=off, final_obs=None, final_state=None)
-        if self.auto_reset and ended.any():
-            out["final_obs"], out["final_state"] = obs[ended].copy(), state[ended].copy()
-            B.reset(ended.astype(np.uint8))
-            obs[ended] = 0.0
-            state = self.state()                  # the spawn state of the envs just reset; the others' rows are what they were
-        out["obs"], out["state"] = obs, state
-        c = self.count
-        c["off_term"] += int((term & ~fin_all).sum()); c["fin_term"] += int(fin_all.sum()); c["trunc"] += int(trunc.sum())
-        mixed, all_miss, clipped = sm.beam_classes(lid, self.pool, self.M)
-        c["mixed"] += mixed; c["all_miss"] += all_miss; c["clipped"] += clipped; c["penalised"] += int(off.sum())
-        return out
-
-
-def torch_driver(torch, obs, gen, dev):
-    """The driver of tests/device_io_child.py on whatever the observation holds: steer towards the largest value of the front half,
-    speed ~ U(0.5, 3); then noise, some of it past the ctrlrange."""
-    n, k, nb = obs.shape
-    front = obs[:, :, nb // 4: 3 * nb // 4]
-    j = front.argmax(dim=2).float() / max(1, front.shape[2] - 1)
-    steer = (j - 0.5) * 2.0
-    speed = 0.5 + 2.5 * torch.rand((n, k), generator=gen, device=dev)
-    act = torch.stack([speed, steer + 0.3 * torch.randn((n, k), generator=gen, device=dev)], dim=2)
-    wild = torch.rand((n, k, 2), generator=gen, device=dev) < 0.05
-    return torch.where(wild, 6.0 * torch.randn((n, k, 2), generator=gen, device=dev), act).contiguous()
-
-
-def _tracks(opt):
-    from ft_grandprix_amd.track import load_track
-    names = opt.get("track", "small-circle")
-    multi = isinstance(names, list)
-    tracks = [sm.open_right_track() if t == "open-right" else load_track(t) for t in (names if multi else [names])]
-    return (tracks if multi else tracks[0]), tracks
-
-
-def _full_state(env):
-    counts, times = env.lap_times()
-    return dict(pose=env.pose(), progress=env.progress(), lap_counts=counts, lap_times=times, steps=env.steps(), lidar=env.lidar(),
-                ctrl=env.ctrl(), dist2=env.centre_dist2(), race_steps=env.race_steps())
-
-
-def _same_state(A, B):
-    a, b = _full_state(A), _full_state(B)
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"handle state at the end: {k}")
+from tests.device_twin import HostTwin, _same_state, _tracks, push_off, refused, teleport, torch_driver  # noqa: E402
 
 
 def twin(opt):
@@ -293,14 +149,6 @@ def errors(opt):
     from ft_grandprix_amd.vec import DeviceVecEnv
     track = load_track("small-circle")
     lib = capi.load()
-
-    def refused(code, what, f, *a, **k):
-        try:
-            f(*a, **k)
-        except capi.FtgpError as x:
-            assert x.code == code, (what, x)
-        else:
-            raise AssertionError(f"{what} was accepted")
 
     with capi.Env(lib, track, n_envs=8, n_rays=64) as e:
         refused(-4, "signals before device_io_config", e.device_io_signals, 4, 5.0)

@@ -126,3 +126,30 @@ def polyline_frame(path, pose):
     s = np.arange(PATH_POINTS)[None] + t
     yaw = 2.0 * np.arctan2(pose[:, 6], pose[:, 3])
     return dist, lat, theta, s, yaw
+
+
+# ---------------------------------------------------------------------------------------------------------------------- paths
+def square_path(duplicate=None):
+    """A square of side 12.5, counter-clockwise from (0, 0), 25 points per side half a unit apart: every coordinate is dyadic.  Point 0 =
+    (0, 0), 25 = (12.5, 0), 50 = (12.5, 12.5), 75 = (0, 12.5), 99 = (0, 0.5).  duplicate = k: point k + 1 is put on point k."""
+    i = 0.5 * np.arange(25)
+    z, top = np.zeros(25), np.full(25, 12.5)
+    p = np.concatenate([np.stack([i, z], 1), np.stack([top, i], 1), np.stack([12.5 - i, top], 1), np.stack([z, 12.5 - i], 1)])
+    if duplicate is not None:
+        p[duplicate + 1] = p[duplicate]
+    return p
+
+
+SKEW_SHIFT = (8.1, -24.3)
+SKEW_POINT_99 = (3.800696369503287, -7.398052024670745)
+SKEW_WRAP_POSE = (7.687704582750535, -24.629698178119828)
+
+
+def skew_path():
+    """The square with point 11 on point 10, moved by SKEW_SHIFT (not dyadic) into a 40 x 40 field, and with point 99 moved far
+    away to SKEW_POINT_99: Y_99 + 1.0 * (Y_0 - Y_99) then rounds one ulp below Y_0, so that wherever both segments around point 0 clamp
+    to it (the outside of that corner) segment A = 99 -> 0 is nearer than B by that ulp: a = 99 with t = 1, which no pose reaches in
+    exact arithmetic (the docstring of tests/test_device_frame.py), and s = 100 wraps to 0."""
+    p = square_path(duplicate=10) + np.array(SKEW_SHIFT)
+    p[99] = SKEW_POINT_99
+    return p

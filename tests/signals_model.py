@@ -66,7 +66,7 @@ def beam_classes(rows, pool, M):
 def open_right_track():
     """The fixture map of the signals tests: 240 x 240 px over [-10, 10]^2, 3-px walls on the left, top and bottom edges, the right side
     open -- scans there hold hits, rays without a hit and ranges of up to 20 units, and nothing keeps a car on the centre-line circle."""
-    from tests.test_walls_model import synthetic
+    from tests.walls_model import synthetic
     wall = np.zeros((240, 240), dtype=bool)
     wall[:, :3] = True
     wall[:3, :] = True

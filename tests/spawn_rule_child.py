@@ -22,7 +22,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402  (before the library is loaded)
 
 from tests import spawn_model as sp  # noqa: E402
-from tests.device_signals_child import HostTwin, _same_state, torch_driver  # noqa: E402
+from tests.device_twin import ContactTwin, HostTwin, _same_state, torch_driver  # noqa: E402
 
 TRACKS = ["track", "circle", "small-circle", "inkscape"]
 RULE = sp.Rule(first_point=0, n_points=100, shuffle_grid=True, margin=0.1, lateral_frac=0.8, yaw_tan=math.tan(0.1))
@@ -285,7 +285,6 @@ def auto_reset(opt):
     from ft_grandprix_amd import capi
     from ft_grandprix_amd.track import load_track
     from ft_grandprix_amd.vec import DeviceVecEnv
-    from tests.device_contacts_child import ContactTwin
     signals = bool(opt.get("signals", False))
     n_envs, n_rays, calls = opt.get("n_envs", 96), opt.get("n_rays", 64), opt.get("calls", 24)
     roster, cpe, R, max_steps = ["agent", "nidc"], 2, 2, 6

@@ -3,8 +3,8 @@ ftgp_contacts_device / ftgp_get_contacts; ft_grandprix_amd/vec.py: DeviceVecEnv(
 terminate_on_car_contact=, wall_contact_penalty=, car_contact_penalty=)).
 
 CPU: the binding, the argument checks, the numpy model of the header's text (tests/contacts_model.py) on hand-written poses, and that
-model against the two independent binary64 models the project has -- `wall_contact_model` of tests/test_walls_model.py and
-`contact_model` of tests/test_crowded_envs.py -- on their own scenes.
+model against the two independent binary64 models the project has -- `wall_contact_model` of tests/walls_model.py and
+`contact_model` of tests/crowded_model.py -- on their own scenes.
 
    Counts must agree car by car.  Penetrations before the binary32 rounding agree with r - hypot(...) of those models within
    CONTACT_RTOL (1e-12) of max(the model's penetration, the circle radius): relative to the penetration where it is deep, to the radius
@@ -16,24 +16,23 @@ model against the two independent binary64 models the project has -- `wall_conta
    deviation 4.4e-16 for walls and 2.3e-15 for cars (20 units from the origin) against bounds of 6.0e-14 to 1.3e-13.
 
 GPU: every scenario runs in a fresh child process (tests/device_contacts_child.py) that imports torch before libftgp.so is loaded, one
-at a time, each under a time limit.  A child that ends by a signal, an abort or its time limit fails its test, and every later GPU
-test of this module fails at once without starting anything on the GPU.
+at a time, each under a time limit.  A child that ends by a signal, an abort or its time limit fails its test, and every later child
+of the session is refused (tests/children.py).
 """
 import ctypes as C
-import json
+import functools
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from ft_grandprix_amd import capi
+from tests import children
 from tests import contacts_model as cm
-from tests import test_crowded_envs as TC
-from tests import test_walls_model as TW
-from tests.test_k1_invariants import open_field
+from tests import crowded_model as TC
+from tests import walls_model as TW
+from tests.helpers import open_field
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "device_contacts_child.py")
@@ -270,24 +269,7 @@ def test_car_rows_meet_the_car_contact_model(oracle, scene):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- GPU
-CRASHED = []               # the first child that ended by a signal, an abort or its time limit: nothing more is started on the GPU after it
-
-
-def run_child(scenario, timeout=300, **opt):
-    assert not CRASHED, f"not started: an earlier GPU scenario of this module died ({CRASHED[0]}); find its cause first"
-    what = f"{scenario} {json.dumps(opt)}"
-    try:
-        r = subprocess.run([sys.executable, CHILD, scenario, json.dumps(opt)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    except subprocess.TimeoutExpired as x:
-        CRASHED.append(f"{what}: no end after {timeout} s")
-        out = "".join(s.decode(errors="replace") if isinstance(s, bytes) else (s or "") for s in (x.stdout, x.stderr))
-        raise AssertionError(f"{CRASHED[0]}\n{out[-4000:]}") from None
-    out = r.stdout + r.stderr
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        CRASHED.append(f"{what}: exit status {r.returncode}")
-    assert r.returncode == 0, f"{what}: exit status {r.returncode}\n{out[-6000:]}"
-    print(out[-3000:])
-    return out
+run_child = functools.partial(children.run_child, CHILD, timeout=300)          # this module's child script and time limit
 
 
 @pytest.mark.gpu

@@ -30,19 +30,19 @@ closed polyline with np.hypot, the tangent as an angle) on the four bundled trac
 
 GPU: every scenario runs in a fresh child process (tests/device_frame_child.py) that imports torch before libftgp.so is loaded, one at a
 time, each under a time limit.  A child that ends by a signal, an abort or its time limit fails its test, and every later GPU test of
-this module fails at once without starting anything on the GPU.
+the session is refused (tests/children.py).
 """
 import ctypes as C
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from ft_grandprix_amd import capi
+from tests import children
 from tests import frame_model as fm
+from tests.frame_model import SKEW_SHIFT, SKEW_WRAP_POSE, skew_path, square_path
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "device_frame_child.py")
@@ -80,17 +80,6 @@ def test_device_vec_env_checks_the_frame_arguments_before_a_handle_exists(kwargs
     monkeypatch.setattr(capi, "load", no_load)
     with pytest.raises(ValueError):
         vec.DeviceVecEnv("small-circle", n_envs=4, n_rays=64, **kwargs)
-
-
-def square_path(duplicate=None):
-    """A square of side 12.5, counter-clockwise from (0, 0), 25 points per side half a unit apart: every coordinate is dyadic.  Point 0 =
-    (0, 0), 25 = (12.5, 0), 50 = (12.5, 12.5), 75 = (0, 12.5), 99 = (0, 0.5).  duplicate = k: point k + 1 is put on point k."""
-    i = 0.5 * np.arange(25)
-    z, top = np.zeros(25), np.full(25, 12.5)
-    p = np.concatenate([np.stack([i, z], 1), np.stack([top, i], 1), np.stack([12.5 - i, top], 1), np.stack([z, 12.5 - i], 1)])
-    if duplicate is not None:
-        p[duplicate + 1] = p[duplicate]
-    return p
 
 
 EAST, WEST = (1.0, 0.0), (0.0, 1.0)          # (qw, qz) of yaw 0 and yaw pi, exact
@@ -155,21 +144,6 @@ def test_model_on_hand_written_poses(case):
     np.testing.assert_array_equal(fm.frame_rows(square_path(dup), poses([pose]), n_ahead, stride), np.array([want], dtype=np.float32))
     assert bool(off[0]) == (what == "off the track")
     assert np.float32(s[0] / 100.0) == np.float32(want[3])
-
-
-SKEW_SHIFT = (8.1, -24.3)
-SKEW_POINT_99 = (3.800696369503287, -7.398052024670745)
-SKEW_WRAP_POSE = (7.687704582750535, -24.629698178119828)
-
-
-def skew_path():
-    """The square with point 11 on point 10, moved by SKEW_SHIFT (not dyadic) into a 40 x 40 field, and with point 99 moved far
-    away to SKEW_POINT_99: Y_99 + 1.0 * (Y_0 - Y_99) then rounds one ulp below Y_0, so that wherever both segments around point 0 clamp
-    to it (the outside of that corner) segment A = 99 -> 0 is nearer than B by that ulp: a = 99 with t = 1, which no pose reaches in
-    exact arithmetic (module docstring), and s = 100 wraps to 0."""
-    p = square_path(duplicate=10) + np.array(SKEW_SHIFT)
-    p[99] = SKEW_POINT_99
-    return p
 
 
 def test_s_wraps_at_100():
@@ -276,24 +250,7 @@ def test_dense_reward_arithmetic():
 
 
 # ---------------------------------------------------------------------------------------------------------------------- GPU
-CRASHED = []               # the first child that ended by a signal, an abort or its time limit: nothing more is started on the GPU after it
-
-
-def run_child(scenario, timeout=90, **opt):
-    assert not CRASHED, f"not started: an earlier GPU scenario of this module died ({CRASHED[0]}); find its cause first"
-    what = f"{scenario} {json.dumps(opt)}"
-    try:
-        r = subprocess.run([sys.executable, CHILD, scenario, json.dumps(opt)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    except subprocess.TimeoutExpired as x:
-        CRASHED.append(f"{what}: no end after {timeout} s")
-        out = "".join(s.decode(errors="replace") if isinstance(s, bytes) else (s or "") for s in (x.stdout, x.stderr))
-        raise AssertionError(f"{CRASHED[0]}\n{out[-4000:]}") from None
-    out = r.stdout + r.stderr
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        CRASHED.append(f"{what}: exit status {r.returncode}")
-    assert r.returncode == 0, f"{what}: exit status {r.returncode}\n{out[-6000:]}"
-    print(out[-3000:])
-    return out
+run_child = functools.partial(children.run_child, CHILD, timeout=90)          # this module's child script and time limit
 
 
 @pytest.mark.gpu

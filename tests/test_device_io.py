@@ -2,29 +2,24 @@
 
 Every GPU scenario runs in a fresh child process (tests/device_io_child.py) that imports torch before libftgp.so is loaded -- one
 HIP runtime per process (vec.py) -- while this process may already hold the library.  The children run one at a time, each under
-a time limit; a failing child fails its test and is not run again.
+a time limit; a failing child fails its test and is not run again (tests/children.py).
 
 GPU: DeviceVecEnv against a twin handle stepped through the host path (set_ctrl + step + get_lidar + reset(mask)), bit for bit at
 every call; the roster; FAKELIDAR mode; ordering on a non-default torch stream; auto_reset off; the slot table kept apart from
 ftgp_set_car_policies' roster; errors.  CPU: the runtime guard, the argument checks, the binding.
 """
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import pytest
+
+from tests import children
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "device_io_child.py")
 
 
-def run_child(scenario, timeout=900, **opt):
-    r = subprocess.run([sys.executable, CHILD, scenario, json.dumps(opt)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, f"{scenario} {opt}: exit status {r.returncode}\n{out[-4000:]}"
-    print(out[-2000:])
-    return out
+run_child = functools.partial(children.run_child, CHILD, timeout=900)          # this module's child script and time limit
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CPU

@@ -3,30 +3,24 @@ ftgp_get_centre_dist2; ft_grandprix_amd/vec.py: DeviceVecEnv(scan_pool=, scan_ma
 off_track_penalty=)).
 
 GPU: every scenario runs in a fresh child process (tests/device_signals_child.py) that imports torch before libftgp.so is loaded, one
-at a time, each under a time limit; a failing child fails its test and is not run again.  A DeviceVecEnv with signals is compared, bit
+at a time, each under a time limit; a failing child fails its test and is not run again (tests/children.py).  A DeviceVecEnv with signals is compared, bit
 for bit at every call, with a numpy model of the header's specification (tests/signals_model.py) fed from the host read-backs of a
 twin handle.  CPU: the binding, the argument checks, the model on hand-written rows, and the fixture map the GPU scenario relies on.
 """
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests import children
 from tests import signals_model as sm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "device_signals_child.py")
 
 
-def run_child(scenario, timeout=600, **opt):
-    r = subprocess.run([sys.executable, CHILD, scenario, json.dumps(opt)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, f"{scenario} {opt}: exit status {r.returncode}\n{out[-4000:]}"
-    print(out[-2000:])
-    return out
+run_child = functools.partial(children.run_child, CHILD, timeout=600)          # this module's child script and time limit
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CPU

@@ -9,33 +9,15 @@ import pytest
 
 from ft_grandprix_amd import capi
 from ft_grandprix_amd.track import load_track
-from tests.helpers import g2_fakelidar, golden
+from tests.helpers import (TOL, assert_same_state, check_laps_with_a_pop, drive_g4_table, g2_fakelidar, golden, laps_by_teleport,
+                           replay_progress_trace)
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4   # north_star tolerance for floating-point outputs
-
 
 def both(product, oracle, track, **kw):
     g, o = capi.Env(product, track, **kw), capi.Env(oracle, track, **kw)
     oracle.dll.oracle_set_threads(o.h, 8)      # envs are independent: OpenMP over envs does not change results
     return g, o
-
-
-def assert_same_state(g, o, exact=True):
-    np.testing.assert_array_equal(g.progress(), o.progress())          # counters: bit-exact
-    np.testing.assert_array_equal(g.steps(), o.steps())
-    cg, tg = g.lap_times(); co, to = o.lap_times()
-    np.testing.assert_array_equal(cg, co)
-    np.testing.assert_allclose(tg, to, rtol=0, atol=1e-12)
-    rg, ro = g.lidar(), o.lidar()
-    np.testing.assert_allclose(rg, ro, rtol=0, atol=TOL)
-    np.testing.assert_allclose(g.pose(), o.pose(), rtol=0, atol=TOL)
-    np.testing.assert_allclose(g.ctrl(), o.ctrl(), rtol=0, atol=TOL)
-    np.testing.assert_allclose(g.snapshot(), o.snapshot(), rtol=0, atol=TOL)
-    if exact:
-        np.testing.assert_array_equal(rg, ro)
-        np.testing.assert_allclose(g.pose(), o.pose(), rtol=0, atol=1e-12)
 
 
 def test_library_is_hip_and_device_present(product):
@@ -227,13 +209,11 @@ def test_k5_wide_window_and_many_disparities(product, oracle):
 @pytest.mark.parametrize("trace", ["forward", "reverse_start", "back_and_forth", "fast_jumps"])
 def test_g5_progress_block_on_gpu(product, trace):
     """K3 against the reference's progress block executed verbatim (fixture g5_progress.npz)."""
-    from tests.test_oracle_golden import replay_progress_trace
     replay_progress_trace(product, trace)
 
 
 def test_lap_time_ring_on_gpu(product, oracle):
     """More laps than FTGP_MAX_LAP_TIMES: the true count and the ring of the newest 32 (lap time k in slot k % 32), GPU = oracle."""
-    from tests.test_oracle_golden import laps_by_teleport
     cg, rg, pg = laps_by_teleport(product)
     co, ro, po = laps_by_teleport(oracle)
     assert cg == co == 37
@@ -244,7 +224,6 @@ def test_lap_time_ring_on_gpu(product, oracle):
 def test_g4_accessor_table_on_gpu(product):
     """Rows a5 / a6: lap_completion / absolute_completion of the reference's truth table (fixture G4) read back through
     ftgp_get_progress columns 2-3 and ftgp_get_snapshot columns 7-8."""
-    from tests.test_oracle_golden import drive_g4_table
     drive_g4_table(product)
 
 
@@ -513,7 +492,6 @@ def test_results_do_not_depend_on_the_sector_count(product, oracle, sectors):
 def test_lap_time_ring_pop_beyond_the_ring_on_gpu(product):
     """The lap-time list beyond the ring's size with a backward crossing (times.pop()) -- the slot the popped entry had overwritten reads
     NaN, not the popped time -- against a Python list, and the 64-bit race steps (ftgp_get_race_steps) beside the int32 row."""
-    from tests.test_oracle_golden import check_laps_with_a_pop
     check_laps_with_a_pop(product)
     t = load_track("track")
     with capi.Env(product, t, n_envs=1, n_rays=8, lap_target=2) as g:        # three laps by teleport, five steps each (laps_by_teleport)

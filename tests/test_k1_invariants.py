@@ -18,19 +18,11 @@ import numpy as np
 import pytest
 
 from ft_grandprix_amd import capi
-from ft_grandprix_amd.track import Track
+from tests.helpers import open_field
 
 DT = 0.004
 L_WHEELBASE = 0.06925 + 0.079          # mushr.em.xml:124,150 (x 0.5 scale)
 X_REAR = 0.079                          # body origin ahead of the rear axle
-
-
-def open_field(px=800):
-    """A 40 x 40 map without a single wall; the centre-line is a circle of radius 12 (it only places the spawn)."""
-    a = 2 * np.pi * np.arange(100) / 100
-    path = np.stack([20 + 12 * np.cos(a), -20 + 12 * np.sin(a)], axis=1)
-    return Track(name="open-field", width=px, height=px, bits=np.zeros((px, (px + 31) // 32), dtype=np.uint32), path=path,
-                 hc=px // 20, vc=px // 20, px_size_x=40.0 / px, px_size_y=40.0 / px, origin_x=0.0, origin_y=0.0, chunks=[])
 
 
 def drive(lib, ctrl_of_env, n_steps, record_every=1):

@@ -3,33 +3,27 @@ tracks).
 
 CPU: ftgp_create_tracks' argument checks run before the device probe (FTGP_ERR_ARG, never FTGP_ERR_NO_DEVICE, on a machine without a
 GPU); the default split and the argument checks of capi.Env and DeviceVecEnv; the binding.
-GPU: every scenario runs in a fresh child process (tests/multitrack_child.py) under a time limit: a four-track handle against one
+GPU: every scenario runs in a fresh child process (tests/multitrack_child.py) under a time limit (tests/children.py): a four-track handle against one
 single-track handle per env block, bit for bit (the matrix of cars per env, rays, lidar modes, spawn modes and policies; masked
 resets, set_pose, the metrics record), against the oracle, both workgroup orders, the distance fields and fixture G8, device I/O.
 """
 import ctypes as C
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from ft_grandprix_amd import capi
 from ft_grandprix_amd.track import load_track
+from tests import children
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "multitrack_child.py")
 NAMES = ["track", "circle", "small-circle", "inkscape"]
 
 
-def run_child(scenario, timeout=600, **opt):
-    r = subprocess.run([sys.executable, CHILD, scenario, json.dumps(opt)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, f"{scenario} {opt}: exit status {r.returncode}\n{out[-4000:]}"
-    print(out[-2000:])
-    return out
+run_child = functools.partial(children.run_child, CHILD, timeout=600)          # this module's child script and time limit
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CPU

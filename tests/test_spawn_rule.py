@@ -7,21 +7,21 @@ The model builds the spawn table's quaternions with math.atan2 / cos / sin, the 
 x, y, qw, qz and both clearances -- is compared bit for bit: feeding the model the harness's columns was not needed.
 
 GPU: every scenario runs in a fresh child process (tests/spawn_rule_child.py) that imports torch before libftgp.so is loaded, one at a
-time, each under a time limit.  A child that ends by a signal, an abort or its time limit fails its test, and every later GPU test of
-this module fails at once without starting anything on the GPU.
+time, each under a time limit.  A child that ends by a signal, an abort or its time limit fails its test, and every later child of
+the session is refused (tests/children.py).
 """
 import ctypes as C
-import json
+import functools
 import math
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from ft_grandprix_amd import capi
 from ft_grandprix_amd.track import load_track
+from tests import children
 from tests import spawn_model as sp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -178,24 +178,7 @@ def test_identity_rule_gives_spawn_mode_0(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- GPU
-CRASHED = []               # the first child that ended by a signal, an abort or its time limit: nothing more is started on the GPU after it
-
-
-def run_child(scenario, timeout=300, **opt):
-    assert not CRASHED, f"not started: an earlier GPU scenario of this module died ({CRASHED[0]}); find its cause first"
-    what = f"{scenario} {json.dumps(opt)}"
-    try:
-        r = subprocess.run([sys.executable, CHILD, scenario, json.dumps(opt)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    except subprocess.TimeoutExpired as x:
-        CRASHED.append(f"{what}: no end after {timeout} s")
-        out = "".join(s.decode(errors="replace") if isinstance(s, bytes) else (s or "") for s in (x.stdout, x.stderr))
-        raise AssertionError(f"{CRASHED[0]}\n{out[-4000:]}") from None
-    out = r.stdout + r.stderr
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        CRASHED.append(f"{what}: exit status {r.returncode}")
-    assert r.returncode == 0, f"{what}: exit status {r.returncode}\n{out[-6000:]}"
-    print(out[-3000:])
-    return out
+run_child = functools.partial(children.run_child, CHILD, timeout=300)          # this module's child script and time limit
 
 
 @pytest.mark.gpu

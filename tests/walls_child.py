@@ -16,10 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+os.environ["FTGP_VERBOSE"] = "1"          # ftgp_create's lines about the workgroup shape go to stderr and into the test's report
+
+from tests import walls_model as T  # noqa: E402
+from tests.helpers import libs, same  # noqa: E402
+
 
 def rays(name):
-    from tests import test_walls_model as T
-    from tests.crowded_child import libs
     product, oracle = libs()
     T.check_rays(product, name)
     sc = T.RAY_SCENES[name]()
@@ -30,8 +33,6 @@ def rays(name):
 
 
 def contacts(name):
-    from tests import test_walls_model as T
-    from tests.crowded_child import libs, same
     product, oracle = libs()
     T.check_contacts(product, name)
     sc = T.contact_scene(name)
