@@ -26,6 +26,9 @@ STATE_FLOATS = 8            # FTGP_STATE_FLOATS: a state row of the device step 
 CONTACT_FLOATS = 4          # FTGP_CONTACT_FLOATS: a contact row (CONTACT_FIELDS)
 FRAME_FIXED = 4              # FTGP_FRAME_FIXED: the fixed entries of a frame row (FRAME_FIELDS); 2 floats per look-ahead point follow
 MAX_LOOKAHEAD = 16           # FTGP_MAX_LOOKAHEAD
+RIVAL_FIXED = 4              # FTGP_RIVAL_FIXED: the fixed entries of a rival row (RIVAL_FIELDS); RIVAL_FLOATS floats per mate slot follow
+RIVAL_FLOATS = 8             # FTGP_RIVAL_FLOATS: a mate slot (RIVAL_MATE_FIELDS)
+MAX_RIVALS = 7               # FTGP_MAX_RIVALS
 MAX_TRACKS = 16             # FTGP_MAX_TRACKS: tracks of one multi-track handle (ftgp_create_tracks)
 
 POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2, 3, 4
@@ -40,6 +43,8 @@ PROGRESS_FIELDS = ("laps", "completion", "lap_completion", "absolute_completion"
 STATE_FIELDS = ("v_long", "v_lat", "wz", "u_speed", "u_steer", "centre_dist", "lap_completion", "off_track")
 CONTACT_FIELDS = ("wall_pen", "car_pen", "wall_count", "car_count")
 FRAME_FIELDS = ("lat", "cos_h", "sin_h", "s_norm")
+RIVAL_FIELDS = ("place", "n_racing", "gap_ahead", "gap_behind")
+RIVAL_MATE_FIELDS = ("fwd", "left", "cos_rel", "sin_rel", "v_fwd", "v_left", "track_gap", "present")
 METRIC_FIELDS = ("steps", "n_cars", "sum_laps", "sum_absolute_completion", "n_finished",
                  "n_off_track", "min_lap_time", "max_lap_time")
 
@@ -89,6 +94,7 @@ API_SYMBOLS = (
     "device_io_contacts", "step_device_contacts", "contacts_device", "get_contacts",
     "set_spawn_rule", "get_episodes", "get_start_table",
     "device_io_frame", "step_device_frame", "frame_device", "get_frames",
+    "device_io_rivals", "step_device_rivals", "rivals_device", "get_rivals",
 )
 
 
@@ -125,6 +131,14 @@ class FtgpDeviceFrame(C.Structure):
 
 class FtgpDeviceStepFrame(C.Structure):
     _fields_ = [("frame", C.c_void_p), ("final_frame", C.c_void_p)]
+
+
+class FtgpDeviceRivals(C.Structure):
+    _fields_ = [("n_rivals", C.c_int32), ("reserved", C.c_int32), ("place_weight", C.c_float), ("reserved_f", C.c_float)]
+
+
+class FtgpDeviceStepRivals(C.Structure):
+    _fields_ = [("rival", C.c_void_p), ("final_rival", C.c_void_p)]
 
 
 class FtgpSpawnRule(C.Structure):
@@ -213,6 +227,11 @@ class CLib:
                                         C.POINTER(FtgpDeviceStepFrame)]),
             "frame_device": (i32, [vp, vp, vp]),
             "get_frames": (i32, [vp, i32, i32, dp]),
+            "device_io_rivals": (i32, [vp, C.POINTER(FtgpDeviceRivals)]),
+            "step_device_rivals": (i32, [vp, C.POINTER(FtgpDeviceStep), C.POINTER(FtgpDeviceStepExtra), C.POINTER(FtgpDeviceStepContacts),
+                                         C.POINTER(FtgpDeviceStepFrame), C.POINTER(FtgpDeviceStepRivals)]),
+            "rivals_device": (i32, [vp, vp, vp]),
+            "get_rivals": (i32, [vp, i32, dp]),
             "set_spawn_rule": (i32, [vp, C.POINTER(FtgpSpawnRule)]),
             "get_episodes": (i32, [vp, dp]),
             "get_start_table": (i32, [vp, i32, dp]),
@@ -439,6 +458,16 @@ class Env:
         f = FtgpDeviceFrame(int(n_ahead), int(stride), int(bool(dense_progress)), 0)
         self._call("device_io_frame", C.byref(f))
 
+    def device_io_rivals(self, on: bool = True, n_rivals: int = 0, place_weight: float = 0.0):
+        """ftgp_device_io_rivals (after ``device_io_config``, which turns rivals off): a rival row per car in every device step
+        (RIVAL_FIELDS, then ``n_rivals`` mate slots of RIVAL_MATE_FIELDS, nearest mate first), and with ``place_weight`` w > 0 the
+        places gained over the call, times w, on top of the reward; ``on=False`` turns them off again."""
+        if not on:
+            self._call("device_io_rivals", None)
+            return
+        r = FtgpDeviceRivals(int(n_rivals), 0, float(place_weight), 0.0)
+        self._call("device_io_rivals", C.byref(r))
+
     # -- spawn rule (include/ftgp.h: ftgp_set_spawn_rule)
     def set_spawn_rule(self, on: bool = True, first_point: int = 0, n_points: int = PATH_POINTS, margin: float = 0.0,
                        lateral_frac: float = 0.0, yaw_tan: float = 0.0, shuffle_grid: bool = False):
@@ -495,6 +524,16 @@ class Env:
             stream, action, obs, reward, terminated, truncated, final_obs, (FtgpDeviceStepExtra, state, final_state),
             (FtgpDeviceStepContacts, contact, final_contact), (FtgpDeviceStepFrame, frame, final_frame)))
 
+    def step_device_rivals(self, action: int, obs: int, reward: int, terminated: int, truncated: int, final_obs: int = 0, stream: int = 0,
+                           state: int = 0, final_state: int = 0, contact: int = 0, final_contact: int = 0, frame: int = 0,
+                           final_frame: int = 0, rival: int = 0, final_rival: int = 0):
+        """One ftgp_step_device_rivals call on integer device addresses, like ``step_device_frame``; ``rival`` / ``final_rival``:
+        float32 [n_envs, n_ext, RIVAL_FIXED + RIVAL_FLOATS * n_rivals], either may be 0."""
+        self._call("step_device_rivals", *self._step_args(
+            stream, action, obs, reward, terminated, truncated, final_obs, (FtgpDeviceStepExtra, state, final_state),
+            (FtgpDeviceStepContacts, contact, final_contact), (FtgpDeviceStepFrame, frame, final_frame),
+            (FtgpDeviceStepRivals, rival, final_rival)))
+
     def state_device(self, state: int, stream: int = 0):
         """ftgp_state_device: the state rows of the current state into device memory at ``state``, ordered on ``stream``; only enqueues."""
         self._call("state_device", stream or None, state or None)
@@ -509,7 +548,22 @@ class Env:
         ``stream``; only enqueues."""
         self._call("frame_device", stream or None, frame or None)
 
+    def rivals_device(self, rival: int, stream: int = 0):
+        """ftgp_rivals_device: the external cars' rival rows at the current state into device memory at ``rival``, ordered on
+        ``stream``; only enqueues."""
+        self._call("rivals_device", stream or None, rival or None)
+
     # -- read-backs
+    def get_rivals(self, n_rivals: int = 0) -> np.ndarray:
+        """float32 [n_cars, RIVAL_FIXED + RIVAL_FLOATS * n_rivals] (RIVAL_FIELDS, then the mate slots of RIVAL_MATE_FIELDS): the rival
+        row of every car at the current state (ftgp_get_rivals)."""
+        n_rivals = int(n_rivals)
+        if not 0 <= n_rivals <= MAX_RIVALS:
+            raise ValueError(f"n_rivals: 0 .. {MAX_RIVALS}, got {n_rivals}")
+        out = np.empty((self.n_cars, RIVAL_FIXED + RIVAL_FLOATS * n_rivals), dtype=np.float32)
+        self._call("get_rivals", n_rivals, _ptr(out))
+        return out
+
     def get_frames(self, n_ahead: int = 0, stride: int = 1) -> np.ndarray:
         """float32 [n_cars, FRAME_FIXED + 2 * n_ahead] (FRAME_FIELDS, then the look-ahead points): the frame row of every car at the
         current state (ftgp_get_frames)."""

@@ -175,6 +175,12 @@ struct FtgpEnv {
                                           // step rewrites the buffer on the handle's stream before its finish kernel reads it -- nothing may be kept in it across calls
         DevBuf<double> d_frame_s;         // [2][n_cars] s before and after a call's steps (dense progress)
         DevBuf<int32_t> d_frame_flag;     // [2][n_cars] the flags that go with them
+        bool rivals_on = false;           // ftgp_device_io_rivals: a call evaluates the rival rows and goes through ftgp_io_finish_signals_kernel
+        FtgpDeviceRivals rivals{};        // n_rivals and the place weight while rivals_on
+        DevBuf<float> d_rival;            // [n_cars][FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * FTGP_MAX_RIVALS] floats, rows packed at the width in use; scratch of one
+                                          // call like d_frame, allocated on first use
+        DevBuf<int32_t> d_frame_c;        // [2][n_cars] the nearest points that go with d_frame_s (the rival rows' race progress)
+        DevBuf<int32_t> d_place0;         // [n_cars] the places when the call began (place reward)
         struct { const void* p; size_t bytes; } checked[32] = {};     // device buffers found valid (hipPointerGetAttributes), replaced round robin
         int checked_next = 0;
     } ds;
@@ -952,14 +958,15 @@ int ensure_contact_rows(FtgpEnv* e)
 }
 
 // ftgp_io_frame_kernel on the handle's stream: every car's row to `rows` and / or the external cars' rows to `ext_out`, s and the
-// flags to slot `slot` of d_frame_s / d_frame_flag (-1: nowhere)
-int launch_frame(FtgpEnv* e, int n_ahead, int stride, float* rows, float* ext_out, int slot)
+// flags to slot `slot` of d_frame_s / d_frame_flag (-1: nowhere), with `want_c` the nearest points to that slot of d_frame_c
+int launch_frame(FtgpEnv* e, int n_ahead, int stride, float* rows, float* ext_out, int slot, bool want_c = false)
 {
     DeviceFrameArgs F{};
     F.env_track = e->d_env_track.get();
     F.rows = rows; F.ext_out = ext_out;
     F.s_out = slot >= 0 ? e->ds.d_frame_s.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
     F.flag_out = slot >= 0 ? e->ds.d_frame_flag.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
+    F.c_out = slot >= 0 && want_c ? e->ds.d_frame_c.get() + (size_t)slot * (size_t)e->P.n_cars : nullptr;
     F.n_ext = e->ds.io.n_ext; F.n_ahead = n_ahead; F.stride = stride;
     for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) F.ext_index[k] = e->ds.ready ? e->ds.io.ext_index[k] : -1;
     const unsigned blocks = (unsigned)(((size_t)e->P.n_cars * FTGP_FRAME_LANES + FTGP_FRAME_THREADS - 1) / FTGP_FRAME_THREADS);
@@ -968,13 +975,53 @@ int launch_frame(FtgpEnv* e, int n_ahead, int stride, float* rows, float* ext_ou
     return 0;
 }
 
+// the two slots of (s, flags) that a launch_frame with a slot writes
+int ensure_frame_slots(FtgpEnv* e)
+{
+    const size_t n_cars = (size_t)e->P.n_cars;
+    if (!e->ds.d_frame_s) HIP_TRY(dev_alloc(e->ds.d_frame_s, sizeof(double) * 2 * n_cars));
+    if (!e->ds.d_frame_flag) HIP_TRY(dev_alloc(e->ds.d_frame_flag, sizeof(int32_t) * 2 * n_cars));
+    return 0;
+}
+
 int ensure_frame_rows(FtgpEnv* e)
 {
     const size_t n_cars = (size_t)e->P.n_cars;
     if (!e->ds.d_frame) HIP_TRY(dev_alloc(e->ds.d_frame, sizeof(float) * (FTGP_FRAME_FIXED + 2 * FTGP_MAX_LOOKAHEAD) * n_cars));
-    if (!e->ds.d_frame_s) HIP_TRY(dev_alloc(e->ds.d_frame_s, sizeof(double) * 2 * n_cars));
-    if (!e->ds.d_frame_flag) HIP_TRY(dev_alloc(e->ds.d_frame_flag, sizeof(int32_t) * 2 * n_cars));
+    return ensure_frame_slots(e);
+}
+
+// ftgp_io_rival_kernel on the handle's stream, behind a launch_frame(.., slot, true) at the same records: every car's row to `rows`
+// and / or the external cars' rows to `ext_out`, or (places_only) nothing but the places to d_place0
+int launch_rivals(FtgpEnv* e, int n_rivals, float* rows, float* ext_out, int slot, bool places_only = false)
+{
+    const size_t at = (size_t)slot * (size_t)e->P.n_cars;
+    DeviceRivalArgs V{};
+    V.s = e->ds.d_frame_s.get() + at; V.c = e->ds.d_frame_c.get() + at; V.flag = e->ds.d_frame_flag.get() + at;
+    V.rows = rows; V.ext_out = ext_out;
+    V.place_out = places_only ? e->ds.d_place0.get() : nullptr;
+    V.n_ext = e->ds.io.n_ext; V.n_rivals = n_rivals;
+    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) V.ext_index[k] = e->ds.ready ? e->ds.io.ext_index[k] : -1;
+    const unsigned blocks = (unsigned)(((size_t)e->P.n_cars * FTGP_RIVAL_LANES + FTGP_RIVAL_THREADS - 1) / FTGP_RIVAL_THREADS);
+    hipLaunchKernelGGL(ftgp_io_rival_kernel, dim3(blocks), dim3(FTGP_RIVAL_THREADS), 0, e->stream.get(), e->P, V);
+    HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int ensure_rival_rows(FtgpEnv* e)
+{
+    const size_t n_cars = (size_t)e->P.n_cars;
+    if (!e->ds.d_rival) HIP_TRY(dev_alloc(e->ds.d_rival, sizeof(float) * (FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * FTGP_MAX_RIVALS) * n_cars));
+    if (!e->ds.d_frame_c) HIP_TRY(dev_alloc(e->ds.d_frame_c, sizeof(int32_t) * 2 * n_cars));
+    if (!e->ds.d_place0) HIP_TRY(dev_alloc(e->ds.d_place0, sizeof(int32_t) * n_cars));
+    return ensure_frame_slots(e);
+}
+
+// the search and the rival kernel at the current records: the two launches of ftgp_rivals_device and ftgp_get_rivals
+int launch_rivals_now(FtgpEnv* e, int n_rivals, float* rows, float* ext_out)
+{
+    if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 1, true)) return rc;
+    return launch_rivals(e, n_rivals, rows, ext_out, 1);
 }
 
 // stream `behind` waits for what stream `ahead` holds so far, through event ev
@@ -989,7 +1036,7 @@ int stream_waits_for(hipStream_t behind, hipStream_t ahead, const Event& ev)
 int handle_waits_for_caller(FtgpEnv* e, hipStream_t caller) { return stream_waits_for(e->stream.get(), caller, e->ds.ev_in); }
 int caller_waits_for_handle(FtgpEnv* e, hipStream_t caller) { return stream_waits_for(caller, e->stream.get(), e->ds.ev_out); }
 
-// ftgp_state_device, ftgp_contacts_device, ftgp_frame_device (`entry`): the external agents' rows of `floats` floats, written by `launch`
+// ftgp_state_device, ftgp_contacts_device, ftgp_frame_device, ftgp_rivals_device (`entry`): the external agents' rows of `floats` floats, written by `launch`
 // on the handle's stream to the caller's buffer `out` (`name` in a refusal)
 template <class Launch>
 int rows_to_device(FtgpEnv* e, const char* entry, void* stream, size_t floats, float* out, const char* name, Launch launch)
@@ -1348,6 +1395,22 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
     set_signals(e, FtgpDeviceSignals{ 1, 0.0f, 0, 0.0f });
     e->ds.con_on = false;
     e->ds.frame_on = false;
+    e->ds.rivals_on = false;
+    return 0;
+}
+
+int ftgp_device_io_rivals(FtgpEnv* e, const FtgpDeviceRivals* rivals)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->ds.ready) return fail(FTGP_ERR_STATE, "ftgp_device_io_rivals before ftgp_device_io_config%s");
+    if (!rivals) { e->ds.rivals_on = false; return 0; }
+    if (rivals->n_rivals < 0 || rivals->n_rivals > FTGP_MAX_RIVALS) return fail(FTGP_ERR_ARG, "device_io_rivals: n_rivals in 0 .. 7%s");
+    if (!nonneg_finite(rivals->place_weight)) return fail(FTGP_ERR_ARG, "device_io_rivals: place_weight >= 0 and finite%s");
+    if (rivals->reserved != 0 || rivals->reserved_f != 0.0f) return fail(FTGP_ERR_ARG, "device_io_rivals: reserved fields must be 0%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = ensure_rival_rows(e)) return rc;
+    e->ds.rivals = *rivals;
+    e->ds.rivals_on = true;
     return 0;
 }
 
@@ -1394,31 +1457,39 @@ int ftgp_device_io_signals(FtgpEnv* e, const FtgpDeviceSignals* signals)
 
 int ftgp_step_device(FtgpEnv* e, const FtgpDeviceStep* io) { return ftgp_step_device_ex(e, io, nullptr); }
 
-int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra) { return ftgp_step_device_frame(e, io, extra, nullptr, nullptr); }
+int ftgp_step_device_ex(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra) { return ftgp_step_device_rivals(e, io, extra, nullptr, nullptr, nullptr); }
 
 int ftgp_step_device_contacts(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts)
 {
-    return ftgp_step_device_frame(e, io, extra, contacts, nullptr);
+    return ftgp_step_device_rivals(e, io, extra, contacts, nullptr, nullptr);
 }
 
 int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts,
                            const FtgpDeviceStepFrame* frame)
 {
+    return ftgp_step_device_rivals(e, io, extra, contacts, frame, nullptr);
+}
+
+int ftgp_step_device_rivals(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts,
+                            const FtgpDeviceStepFrame* frame, const FtgpDeviceStepRivals* rivals)
+{
     if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
     FtgpEnv::DeviceStep& ds = e->ds;
     if (!ds.ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
-    // the three optional kinds of rows: floats per row, the caller's two buffers and what a refusal calls them
+    // the four optional kinds of rows: floats per row, the caller's two buffers and what a refusal calls them
     struct Rows { const char* name; const char* final_name; size_t floats; float* out; float* final_out; };
     const Rows st{ "state", "final_state", FTGP_STATE_FLOATS, extra ? extra->state : nullptr, extra ? extra->final_state : nullptr };
     const Rows ct{ "contact", "final_contact", FTGP_CONTACT_FLOATS, contacts ? contacts->contact : nullptr, contacts ? contacts->final_contact : nullptr };
     const Rows fr{ "frame", "final_frame", (size_t)(FTGP_FRAME_FIXED + 2 * ds.frame.n_ahead), frame ? frame->frame : nullptr, frame ? frame->final_frame : nullptr };
+    const Rows rv{ "rival", "final_rival", (size_t)(FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * ds.rivals.n_rivals), rivals ? rivals->rival : nullptr, rivals ? rivals->final_rival : nullptr };
     if ((ct.out || ct.final_out) && !ds.con_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_contacts: contact buffers while contacts are off (ftgp_device_io_contacts)%s");
     if ((fr.out || fr.final_out) && !ds.frame_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_frame: frame buffers while the frame is off (ftgp_device_io_frame)%s");
+    if ((rv.out || rv.final_out) && !ds.rivals_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_rivals: rival buffers while rivals are off (ftgp_device_io_rivals)%s");
     HIP_TRY(hipSetDevice(e->device));
     DeviceIoArgs A = ds.io;
     DeviceSignalArgs S = ds.sig;
     S.state = st.out; S.final_state = st.final_out;
-    const bool signals = !ds.sig_default || S.state || S.final_state || ds.con_on || ds.frame_on;
+    const bool signals = !ds.sig_default || S.state || S.final_state || ds.con_on || ds.frame_on || ds.rivals_on;
     const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
     if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
     if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
@@ -1426,7 +1497,7 @@ int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevic
     if (int rc = check_device_buffer(e, io->terminated, n_envs, "terminated")) return rc;
     if (int rc = check_device_buffer(e, io->truncated, n_envs, "truncated")) return rc;
     if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
-    for (const Rows* r : { &st, &ct, &fr }) {
+    for (const Rows* r : { &st, &ct, &fr, &rv }) {
         if (r->out) if (int rc = check_device_buffer(e, r->out, sizeof(float) * r->floats * rows, r->name)) return rc;
         if (r->final_out) if (int rc = check_device_buffer(e, r->final_out, sizeof(float) * r->floats * rows, r->final_name)) return rc;
     }
@@ -1438,6 +1509,12 @@ int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevic
             S.frame_s0 = ds.d_frame_s.get(); S.frame_s1 = ds.d_frame_s.get() + e->P.n_cars;
             S.frame_flag0 = ds.d_frame_flag.get(); S.frame_flag1 = ds.d_frame_flag.get() + e->P.n_cars;
         }
+    }
+    const bool place = ds.rivals_on && ds.rivals.place_weight != 0.0f;
+    if (ds.rivals_on) {
+        S.rival_rows = ds.d_rival.get(); S.rival = rv.out; S.final_rival = rv.final_out;
+        S.rival_n = ds.rivals.n_rivals;
+        if (place) { S.place0 = ds.d_place0.get(); S.place_weight = ds.rivals.place_weight; }
     }
     if (ds.con_on) {
         S.contact_rows = ds.d_contact.get(); S.contact = ct.out; S.final_contact = ct.final_out;
@@ -1451,10 +1528,13 @@ int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevic
     const unsigned car_blocks = (unsigned)((e->P.n_cars + 255) / 256);
     hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
-    if (dense) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 0)) return rc;          // s0: the pose the call begins with
+    if (dense || place) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 0, place)) return rc;          // s0: the pose the call begins with
+    if (place) if (int rc = launch_rivals(e, 0, nullptr, nullptr, 0, true)) return rc;      // p0: the places the call begins with
     if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, ds.repeat, true)) return rc;
     if (ds.con_on) if (int rc = launch_contacts(e, ds.d_contact.get(), nullptr)) return rc;
-    if (ds.frame_on) if (int rc = launch_frame(e, ds.frame.n_ahead, ds.frame.stride, ds.d_frame.get(), nullptr, 1)) return rc;
+    if (ds.frame_on) { if (int rc = launch_frame(e, ds.frame.n_ahead, ds.frame.stride, ds.d_frame.get(), nullptr, 1, ds.rivals_on)) return rc; }
+    else if (ds.rivals_on) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 1, true)) return rc;           // the rivals' own search
+    if (ds.rivals_on) if (int rc = launch_rivals(e, ds.rivals.n_rivals, ds.d_rival.get(), nullptr, 1)) return rc;
     if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, e->rule);
     else {
         const bool aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
@@ -1487,6 +1567,15 @@ int ftgp_frame_device(FtgpEnv* e, void* stream, float* frame)
     const bool on = e && e->ds.frame_on;
     const int n_ahead = on ? e->ds.frame.n_ahead : 0, stride = on ? e->ds.frame.stride : 1;
     return rows_to_device(e, "ftgp_frame_device", stream, (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead), frame, "frame", [&] { return launch_frame(e, n_ahead, stride, nullptr, frame, -1); });
+}
+
+int ftgp_rivals_device(FtgpEnv* e, void* stream, float* rival)
+{
+    const int n_rivals = e && e->ds.rivals_on ? e->ds.rivals.n_rivals : 0;
+    return rows_to_device(e, "ftgp_rivals_device", stream, (size_t)(FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * n_rivals), rival, "rival", [&] {
+        if (int rc = ensure_rival_rows(e)) return rc;
+        return launch_rivals_now(e, n_rivals, nullptr, rival);
+    });
 }
 
 int ftgp_set_spawn_rule(FtgpEnv* e, const FtgpSpawnRule* r)
@@ -1572,6 +1661,18 @@ int ftgp_get_frames(FtgpEnv* e, int n_ahead, int stride, float* out)
     if (int rc = ensure_frame_rows(e)) return rc;
     if (int rc = launch_frame(e, n_ahead, stride, e->ds.d_frame.get(), nullptr, -1)) return rc;
     HIP_TRY(hipMemcpyAsync(out, e->ds.d_frame.get(), sizeof(float) * (size_t)(FTGP_FRAME_FIXED + 2 * n_ahead) * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    return 0;
+}
+
+int ftgp_get_rivals(FtgpEnv* e, int n_rivals, float* out)
+{
+    if (!e || !out) return fail(FTGP_ERR_ARG, "null argument%s");
+    if (n_rivals < 0 || n_rivals > FTGP_MAX_RIVALS) return fail(FTGP_ERR_ARG, "ftgp_get_rivals: n_rivals in 0 .. 7%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = ensure_rival_rows(e)) return rc;
+    if (int rc = launch_rivals_now(e, n_rivals, e->ds.d_rival.get(), nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->ds.d_rival.get(), sizeof(float) * (size_t)(FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * n_rivals) * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     return 0;
 }

@@ -1910,7 +1910,8 @@ __global__ void ftgp_set_pose_kernel(DeviceParams P, const double* __restrict__ 
 // Device I/O (ftgp_step_device): the caller's actions in, observations / rewards / episode ends out, all in device memory.
 // A call is: ftgp_io_ingest_kernel -> ftgp_step_kernel<.., ROSTER> (action_repeat steps) -> ftgp_io_finish_kernel; with contacts on,
 // ftgp_io_contact_kernel runs between the steps and the finish kernel; with the frame on, so does ftgp_io_frame_kernel, and with the dense
-// reward it also runs behind the ingest kernel, at the pose the call begins with.
+// reward it also runs behind the ingest kernel, at the pose the call begins with.  With rivals on ftgp_io_rival_kernel follows the frame
+// kernel behind the steps (which runs for the rivals' sake if the frame is off), and with the place reward both run behind the ingest kernel too.
 // =============================================================================================
 struct DeviceIoArgs {
     const float* action;          // [n_envs][n_ext][2] (speed, steering_angle)
@@ -2037,6 +2038,13 @@ struct DeviceSignalArgs {
     const int32_t* frame_flag0;   // [n_cars] FTGP_FRAME_OFF | FTGP_FRAME_FINISHED when the call began
     const int32_t* frame_flag1;   // [n_cars] ... after the steps
     int32_t frame_ahead, frame_stride;
+    // rivals (ftgp_device_io_rivals): filled in per call
+    const float* rival_rows;      // [n_cars][rival_width] this call's rows (ftgp_io_rival_kernel), null = rivals are off
+    float* rival;                 // [n_envs][n_ext][rival_width] or null
+    float* final_rival;           // [n_envs][n_ext][rival_width] or null
+    const int32_t* place0;        // [n_cars] the place when the call began, negative for a car that had finished; null = no place reward
+    int32_t rival_n;              // mate slots per row
+    float place_weight;
 };
 
 // a range as it enters the minimum: no hit (< 0) = the limit, a hit = min(r, limit)
@@ -2231,6 +2239,7 @@ struct DeviceFrameArgs {
     float* ext_out;                       // [n_envs][n_ext][FTGP_FRAME_FIXED + 2 * n_ahead]: the external cars' rows, or null
     double* s_out;                        // [n_cars]: the unrounded s, or null
     int32_t* flag_out;                    // [n_cars]: FTGP_FRAME_OFF | FTGP_FRAME_FINISHED, or null
+    int32_t* c_out;                       // [n_cars]: the nearest point c of step 1 (the rival rows' race progress), or null
     int32_t n_ext, n_ahead, stride, pad;
     int32_t ext_index[FTGP_PAIR_STRIDE];  // as DeviceIoArgs (read with ext_out only)
 };
@@ -2363,11 +2372,250 @@ __global__ void __launch_bounds__(FTGP_FRAME_THREADS) ftgp_io_frame_kernel(Devic
         if (ext) { ext[0] = f.x; ext[1] = f.y; ext[2] = f.z; ext[3] = f.w; }
         if (F.s_out) F.s_out[ci] = s;
         if (F.flag_out) F.flag_out[ci] = (best > 1.0 ? FTGP_FRAME_OFF : 0) | (fin ? FTGP_FRAME_FINISHED : 0);
+        if (F.c_out) F.c_out[ci] = c;
     }
     if (l < F.n_ahead) {
         const float2 p = frame_ahead(path, seg, l, F.stride, x, y, ch, sh);
         if (row) { row[FTGP_FRAME_FIXED + 2 * l] = p.x; row[FTGP_FRAME_FIXED + 2 * l + 1] = p.y; }
         if (ext) { ext[FTGP_FRAME_FIXED + 2 * l] = p.x; ext[FTGP_FRAME_FIXED + 2 * l + 1] = p.y; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Rivals (ftgp_device_io_rivals / ftgp_step_device_rivals / ftgp_rivals_device / ftgp_get_rivals): the rival row of include/ftgp.h -- the
+// car's place in its env's race, the gaps to the cars around it, and the nearest env-mates in its body frame.  The per-car search
+// (s, c, off) is ftgp_io_frame_kernel's, launched just before with s_out, flag_out and c_out.
+// ---------------------------------------------------------------------------------------------
+struct DeviceRivalArgs {
+    const double* s;                      // [n_cars] the unrounded s of every car          } ftgp_io_frame_kernel's outputs
+    const int32_t* c;                     // [n_cars] its nearest point                      } at the same records
+    const int32_t* flag;                  // [n_cars] FTGP_FRAME_OFF | FTGP_FRAME_FINISHED   }
+    float* rows;                          // [n_cars][FTGP_RIVAL_FIXED + 8 * n_rivals]: every car's row, or null
+    float* ext_out;                       // [n_envs][n_ext][FTGP_RIVAL_FIXED + 8 * n_rivals]: the external cars' rows, or null
+    int32_t* place_out;                   // [n_cars]: the place alone, negated for a finished car (the place reward's p0), or null
+    int32_t n_ext, n_rivals;
+    int32_t ext_index[FTGP_PAIR_STRIDE];  // as DeviceIoArgs (read with ext_out only)
+};
+
+// step 1: race progress from what the search found
+__device__ __forceinline__ double rival_progress(int32_t abs_completion, double s, int c, bool off)
+{
+    double f = s - (double)c;
+    if (f >= 50.0) f = f - 100.0;
+    if (f < -50.0) f = f + 100.0;
+    if (off) f = 0.0;
+    return (double)abs_completion + f;
+}
+
+// step 2: is car b (slot b) ahead of car a (slot a)?
+__device__ __forceinline__ bool rival_ahead(bool fin_b, int64_t fs_b, double g_b, int b, bool fin_a, int64_t fs_a, double g_a, int a)
+{
+    if (fin_b && fin_a) return fs_b < fs_a || (fs_b == fs_a && b < a);
+    if (fin_b) return true;
+    if (fin_a) return false;
+    return g_b > g_a || (g_b == g_a && b < a);
+}
+
+// what a mate slot needs of a car
+struct RivalCar { double x, y, ch, sh, vx, vy, s; };
+__device__ __forceinline__ RivalCar rival_car(const CarCore& r, double s)
+{
+    RivalCar k;
+    k.x = r.x; k.y = r.y; k.ch = r.qw * r.qw - r.qz * r.qz; k.sh = 2.0 * (r.qw * r.qz); k.vx = r.vx; k.vy = r.vy; k.s = s;
+    return k;
+}
+
+// step 4: the eight entries of mate b in a's slot o
+__device__ __forceinline__ void rival_mate(const RivalCar& a, const RivalCar& b, float* __restrict__ o)
+{
+    const double dx = b.x - a.x, dy = b.y - a.y, dvx = b.vx - a.vx, dvy = b.vy - a.vy;
+    double tg = b.s - a.s;
+    if (tg >= 50.0) tg = tg - 100.0;
+    if (tg < -50.0) tg = tg + 100.0;
+    o[0] = (float)(dx * a.ch + dy * a.sh);
+    o[1] = (float)(dy * a.ch - dx * a.sh);
+    o[2] = (float)(b.ch * a.ch + b.sh * a.sh);
+    o[3] = (float)(b.sh * a.ch - b.ch * a.sh);
+    o[4] = (float)(dvx * a.ch + dvy * a.sh);
+    o[5] = (float)(dvy * a.ch - dvx * a.sh);
+    o[6] = (float)tg;
+    o[7] = 1.0f;
+}
+
+__device__ __forceinline__ double shfl_f64(double v, int src)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl(lo, src, FTGP_WAVE);
+    hi = __shfl(hi, src, FTGP_WAVE);
+    return __hiloint2double(hi, lo);
+}
+
+// Eight lanes per car: lane j of a group holds slot j of the car's env (a lane past cars_per_env holds nobody), so a wave holds eight
+// cars and a workgroup thirty-two.  Every lane loads its mate's record and the search's results for it and forms g_j and d2_j; place,
+// n_racing and the number of mates are sums and the two gaps minima over the group (xor-shuffles 1, 2, 4 stay inside eight lanes);
+// a mate's rank is the number of mates before it in (d2, slot) order, counted over the group's eight lanes with plain shuffles.  The
+// mate of rank r < n_rivals writes slot r, lane r zero-fills a slot no mate has, lane 0 writes the fixed entries.  No LDS, no atomics.
+#define FTGP_RIVAL_LANES 8
+#define FTGP_RIVAL_THREADS 256
+__global__ void __launch_bounds__(FTGP_RIVAL_THREADS) ftgp_io_rival_kernel(DeviceParams P, DeviceRivalArgs V)
+{
+    // (the car from the block's first car, not from a global lane number: that one would pass 2^31 at 268 M cars)
+    const int ci = blockIdx.x * (FTGP_RIVAL_THREADS / FTGP_RIVAL_LANES) + threadIdx.x / FTGP_RIVAL_LANES, j = threadIdx.x % FTGP_RIVAL_LANES;
+    const bool live = ci < P.n_cars;
+    const int cpe = P.cars_per_env;
+    const int env = live ? ci / cpe : 0, slot = live ? ci - env * cpe : 0;
+    const bool has = live && j < cpe;            // this lane holds a car of the env
+    const bool other = has && j != slot;
+    // a lane that holds nobody takes part in the shuffles with these: not ahead, not racing, no mate, no gap
+    RivalCar a{}, b{};
+    bool fin_a = false, fin_b = false;
+    int64_t fs_a = 0, fs_b = 0;
+    double g_a = 0.0, g_b = 0.0;
+    if (live) {
+        const CarCore& r = P.cars[ci];
+        const int fl = V.flag[ci];
+        a = rival_car(r, V.s[ci]);
+        fin_a = r.finished != 0; fs_a = r.finish_step;
+        g_a = rival_progress(absolute_completion(r), a.s, V.c[ci], (fl & FTGP_FRAME_OFF) != 0);
+    }
+    if (has) {
+        const int cb = ci - slot + j;
+        const CarCore& r = P.cars[cb];
+        const int fl = V.flag[cb];
+        b = rival_car(r, V.s[cb]);
+        fin_b = r.finished != 0; fs_b = r.finish_step;
+        g_b = rival_progress(absolute_completion(r), b.s, V.c[cb], (fl & FTGP_FRAME_OFF) != 0);
+    }
+    const bool ahead = other && rival_ahead(fin_b, fs_b, g_b, j, fin_a, fs_a, g_a, slot);
+    const bool mate = other && !fin_b && !fin_a;
+    const double dx = b.x - a.x, dy = b.y - a.y;
+    const double d2 = dx * dx + dy * dy;
+    double gap_ahead = (mate && ahead) ? g_b - g_a : INFINITY;
+    double gap_behind = (mate && !ahead) ? g_a - g_b : INFINITY;
+    int n_ahead = ahead ? 1 : 0, n_racing = (has && !fin_b) ? 1 : 0, n_mates = mate ? 1 : 0;
+    // every lane of the wave is here
+    for (int m = 1; m < FTGP_RIVAL_LANES; m <<= 1) {
+        const double oa = shfl_xor_f64(gap_ahead, m), ob = shfl_xor_f64(gap_behind, m);
+        if (oa < gap_ahead) gap_ahead = oa;
+        if (ob < gap_behind) gap_behind = ob;
+        n_ahead += __shfl_xor(n_ahead, m, FTGP_WAVE);
+        n_racing += __shfl_xor(n_racing, m, FTGP_WAVE);
+        n_mates += __shfl_xor(n_mates, m, FTGP_WAVE);
+    }
+    const int first = (int)(threadIdx.x & (FTGP_WAVE - 1) & ~(FTGP_RIVAL_LANES - 1));      // the group's lane 0 in the wave
+    int rank = 0;
+    #pragma unroll
+    for (int i = 0; i < FTGP_RIVAL_LANES; ++i) {
+        const double od = shfl_f64(d2, first + i);
+        const int om = __shfl(mate ? 1 : 0, first + i, FTGP_WAVE);
+        if (om && (od < d2 || (od == d2 && i < j))) ++rank;
+    }
+    if (!live) return;
+    const int place = 1 + n_ahead;
+    if (V.place_out && j == 0) V.place_out[ci] = fin_a ? -place : place;
+    const int width = FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * V.n_rivals;
+    const int k_ext = V.ext_out ? V.ext_index[slot] : -1;
+    float* ext = k_ext >= 0 ? V.ext_out + ((size_t)env * V.n_ext + k_ext) * width : nullptr;
+    float* row = V.rows ? V.rows + (size_t)ci * width : nullptr;
+    if (j == 0) {
+        const float f0 = (float)place, f1 = (float)n_racing, f2 = gap_ahead == INFINITY ? 0.0f : (float)gap_ahead, f3 = gap_behind == INFINITY ? 0.0f : (float)gap_behind;
+        if (row) { row[0] = f0; row[1] = f1; row[2] = f2; row[3] = f3; }
+        if (ext) { ext[0] = f0; ext[1] = f1; ext[2] = f2; ext[3] = f3; }
+    }
+    if (mate && rank < V.n_rivals) {
+        float o[FTGP_RIVAL_FLOATS];
+        rival_mate(a, b, o);
+        const int at = FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * rank;
+        #pragma unroll
+        for (int q = 0; q < FTGP_RIVAL_FLOATS; ++q) {
+            if (row) row[at + q] = o[q];
+            if (ext) ext[at + q] = o[q];
+        }
+    }
+    if (j >= n_mates && j < V.n_rivals) {        // a slot no mate has
+        const int at = FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * j;
+        #pragma unroll
+        for (int q = 0; q < FTGP_RIVAL_FLOATS; ++q) {
+            if (row) row[at + q] = 0.0f;
+            if (ext) ext[at + q] = 0.0f;
+        }
+    }
+}
+
+// The rival row by one lane (ftgp_io_finish_signals_kernel, the spawn state of an env it has just reset): what every car of the env
+// put into shared memory -- its RivalCar, g, finished and finish_step -- goes through the operations of ftgp_io_rival_kernel.
+struct RivalLds { RivalCar car[FTGP_PAIR_STRIDE]; double g[FTGP_PAIR_STRIDE]; int64_t finish_step[FTGP_PAIR_STRIDE]; int32_t finished[FTGP_PAIR_STRIDE]; };
+
+// this lane's car into shared memory: the search as the progress block runs it, steps 2 and 3 of the frame row, step 1 of the rival row
+__device__ __forceinline__ void rival_lds_put(const double* __restrict__ path, const CarCore& r, RivalLds& L, int slot)
+{
+    const double x = r.x, y = r.y;
+    double best = 0.0; int c = 0;
+    #pragma unroll 1
+    for (int i = 0; i < FTGP_PATH_POINTS; ++i) {
+        const double dx = path[2 * i] - x, dy = path[2 * i + 1] - y;
+        const double d = dx * dx + dy * dy;
+        if (i == 0 || d < best) { best = d; c = i; }
+    }
+    const int pa = c > 0 ? c - 1 : FTGP_PATH_POINTS - 1;
+    FrameSeg g = frame_segment(path, c, x, y);
+    int seg = c;
+    {
+        const FrameSeg ga = frame_segment(path, pa, x, y);
+        if (ga.g2 < g.g2) { g = ga; seg = pa; }
+    }
+    double s = (double)seg + g.t;
+    if (s >= 100.0) s = s - 100.0;
+    L.car[slot] = rival_car(r, s);
+    L.g[slot] = rival_progress(absolute_completion(r), s, c, best > 1.0);
+    L.finish_step[slot] = r.finish_step;
+    L.finished[slot] = r.finished;
+}
+
+__device__ __forceinline__ void rival_row_lane(const RivalLds& L, int cpe, int slot, int n_rivals, float* __restrict__ o)
+{
+    const RivalCar a = L.car[slot];
+    const double g_a = L.g[slot];
+    const bool fin_a = L.finished[slot] != 0;
+    const int64_t fs_a = L.finish_step[slot];
+    int n_ahead = 0, n_racing = 0;
+    double gap_ahead = INFINITY, gap_behind = INFINITY;
+    #pragma unroll 1
+    for (int b = 0; b < cpe; ++b) {
+        const bool fin_b = L.finished[b] != 0;
+        if (!fin_b) ++n_racing;
+        if (b == slot) continue;
+        const double g_b = L.g[b];
+        const bool ahead = rival_ahead(fin_b, L.finish_step[b], g_b, b, fin_a, fs_a, g_a, slot);
+        if (ahead) ++n_ahead;
+        if (fin_b || fin_a) continue;
+        const double gap = ahead ? g_b - g_a : g_a - g_b;
+        if (ahead) { if (gap < gap_ahead) gap_ahead = gap; }
+        else if (gap < gap_behind) gap_behind = gap;
+    }
+    o[0] = (float)(1 + n_ahead); o[1] = (float)n_racing;
+    o[2] = gap_ahead == INFINITY ? 0.0f : (float)gap_ahead; o[3] = gap_behind == INFINITY ? 0.0f : (float)gap_behind;
+    // the mates in (d2, slot) order: each turn takes the first one behind the last taken
+    double last_d2 = -1.0; int last_b = -1;
+    #pragma unroll 1
+    for (int k = 0; k < n_rivals; ++k) {
+        double best = 0.0; int bb = -1;
+        if (!fin_a) {
+            #pragma unroll 1
+            for (int b = 0; b < cpe; ++b) {
+                if (b == slot || L.finished[b]) continue;
+                const double dx = L.car[b].x - a.x, dy = L.car[b].y - a.y;
+                const double d2 = dx * dx + dy * dy;
+                if (!(d2 > last_d2 || (d2 == last_d2 && b > last_b))) continue;      // taken already
+                if (bb < 0 || d2 < best) { best = d2; bb = b; }
+            }
+        }
+        float* m = o + FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * k;
+        if (bb >= 0) { rival_mate(a, L.car[bb], m); last_d2 = best; last_b = bb; }
+        else {
+            for (int q = 0; q < FTGP_RIVAL_FLOATS; ++q) m[q] = 0.0f;
+            last_d2 = INFINITY; last_b = FTGP_PAIR_STRIDE;      // nobody is left
+        }
     }
 }
 
@@ -2377,10 +2625,13 @@ __global__ void __launch_bounds__(FTGP_FRAME_THREADS) ftgp_io_frame_kernel(Devic
 // ftgp_io_contact_kernel) the wall and car penalties and episode ends join, and the rows go out like the state rows -- zeros after a reset.
 // With the frame on (S.frame_rows, this call's rows of ftgp_io_frame_kernel) those rows go out the same way, evaluated again at the spawn
 // pose after a reset (frame_row_lane), and with S.frame_s0 the base reward is the dense one.
+// With rivals on (S.rival_rows, this call's rows of ftgp_io_rival_kernel) those rows go out like the frame rows, evaluated again at the
+// spawn state after a reset (rival_lds_put, rival_row_lane), and with S.place0 the place term joins the reward behind the penalties.
 __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgpr(72))) ftgp_io_finish_signals_kernel(DeviceParams P, DeviceIoArgs A, DeviceSignalArgs S, const FtgpSpawnDev* __restrict__ rule)
 {
     __shared__ int ended;
     __shared__ __attribute__((aligned(16))) float stage[FTGP_SIG_STAGE_FLOATS];
+    __shared__ RivalLds rival_lds;
     const int env = blockIdx.x, cpe = P.cars_per_env, ci0 = env * cpe, t = threadIdx.x;
     if (t == 0) {
         bool all_finished = true, off = false, wall = false, car = false;
@@ -2419,6 +2670,12 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
             if (cr[2] > 0.0f) r = r - S.wall_penalty;
             if (cr[3] > 0.0f) r = r - S.car_penalty;
         }
+        if (S.place0) {            // place reward: places gained over the call, nothing for a car that had finished
+            const int p0 = S.place0[ci0 + t], p1 = (int)S.rival_rows[(size_t)(ci0 + t) * (FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * S.rival_n)];
+            const float gained = (float)(p0 < 0 ? 0 : p0 - p1);
+            const float term = S.place_weight * gained;
+            r = r + term;
+        }
         A.reward[my_row] = r;
     }
     __syncthreads();
@@ -2437,6 +2694,12 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
             const float* fr = S.frame_rows + (size_t)(ci0 + t) * width;
             float* row = reset ? S.final_frame : S.frame;
             if (row) for (int q = 0; q < width; ++q) row[my_row * width + q] = fr[q];
+        }
+        if (S.rival_rows) {
+            const int width = FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * S.rival_n;
+            const float* rr = S.rival_rows + (size_t)(ci0 + t) * width;
+            float* row = reset ? S.final_rival : S.rival;
+            if (row) for (int q = 0; q < width; ++q) row[my_row * width + q] = rr[q];
         }
     }
     const int R = P.n_rays, NB = S.n_beams;
@@ -2469,6 +2732,11 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
             frame_row_lane(P.path + (size_t)env_track_of(A.env_track, env) * 2 * FTGP_PATH_POINTS, P.cars[ci0 + t], S.frame_ahead, S.frame_stride,
                            S.frame + my_row * (FTGP_FRAME_FIXED + 2 * S.frame_ahead));
         if (t == 0 && rule) rule->episodes[env] = episode + 1;
+    }
+    if (reset && S.rival_rows && S.rival) {      // (uniform over the workgroup) the rival rows at the spawn state: every car's inputs, then the external cars' rows
+        if (t < cpe) rival_lds_put(P.path + (size_t)env_track_of(A.env_track, env) * 2 * FTGP_PATH_POINTS, P.cars[ci0 + t], rival_lds, t);
+        __syncthreads();
+        if (mine) rival_row_lane(rival_lds, cpe, t, S.rival_n, S.rival + my_row * (FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * S.rival_n));
     }
 }
 

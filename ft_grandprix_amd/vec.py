@@ -94,6 +94,15 @@ class DeviceVecEnv:
     is off the track or has finished; the penalties come off it as before.  ``lookahead`` > 0 or ``dense_progress`` implies
     ``track_frame=True``.
 
+    Rivals (ftgp_device_io_rivals / ftgp_step_device_rivals), off by default: ``rivals=True`` adds info["rival"] / info["final_rival"],
+    float32 [n_envs, n_agents, 4 + 8 * n_rivals]: capi.RIVAL_FIELDS -- the car's place in its env's race (1 = in front), the number of
+    cars still racing, the gaps in race progress (path points) to the car ahead and to the car behind -- then ``n_rivals`` (0 .. 7)
+    mate slots of capi.RIVAL_MATE_FIELDS, nearest unfinished env-mate first: its position, heading and relative velocity in the car's
+    frame, the gap along the centre-line, and 1.0; a slot without a mate is zeros, so ``n_rivals`` may exceed ``cars_per_env - 1``.
+    ``rival`` holds the rows after the call, for an env that was reset those of its spawn state; ``final_rival`` the rows before the
+    reset; ``reset()`` fills ``rival``.  ``place_reward`` w > 0 adds w times the places gained over the call to the reward, behind the
+    penalties.  ``n_rivals`` > 0 or ``place_reward`` > 0 implies ``rivals=True``.
+
     Random starts (ftgp_set_spawn_rule), off by default -- every reset then puts a car back on the pose it had before:
     ``random_start=True`` draws, at every reset of an env (``reset()`` and the auto-reset alike), a start point among the
     ``start_points = (first, count)`` path points (first + i) % 100 that keep ``start_margin`` of wall clearance on both sides (None =
@@ -118,7 +127,8 @@ class DeviceVecEnv:
                  terminate_on_wall_contact: bool = False, terminate_on_car_contact: bool = False, wall_contact_penalty: float = 0.0,
                  car_contact_penalty: float = 0.0, random_start: bool = False, start_points=(0, 100), start_margin=None,
                  start_lateral: float = 0.0, start_yaw_jitter: float = 0.0, shuffle_grid: bool = False, track_frame: bool = False,
-                 lookahead: int = 0, lookahead_stride: int = 1, dense_progress: bool = False, **env_kwargs):
+                 lookahead: int = 0, lookahead_stride: int = 1, dense_progress: bool = False, rivals: bool = False, n_rivals: int = 0,
+                 place_reward: float = 0.0, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
@@ -157,6 +167,13 @@ class DeviceVecEnv:
             raise ValueError(f"lookahead_stride: 1 .. {capi.PATH_POINTS // 2} path points, got {lookahead_stride}")
         self.lookahead, self.lookahead_stride, self.dense_progress = lookahead, lookahead_stride, bool(dense_progress)
         self.track_frame = bool(track_frame) or lookahead > 0 or self.dense_progress
+        n_rivals, place_reward = int(n_rivals), float(place_reward)
+        if not 0 <= n_rivals <= capi.MAX_RIVALS:
+            raise ValueError(f"n_rivals: 0 .. {capi.MAX_RIVALS} mate slots, got {n_rivals}")
+        if not (place_reward >= 0.0 and math.isfinite(place_reward)):
+            raise ValueError(f"place_reward: >= 0 and finite, got {place_reward}")
+        self.n_rivals, self.place_reward = n_rivals, place_reward
+        self.rivals = bool(rivals) or n_rivals > 0 or place_reward > 0.0
         roster = ["agent"] * cars_per_env if roster is None else list(roster)
         if len(roster) != cars_per_env:
             raise ValueError(f"one roster entry per car of an env: expected {cars_per_env}, got {len(roster)}")
@@ -202,6 +219,8 @@ class DeviceVecEnv:
                                         car_contact_penalty)
         if self.track_frame:
             self.env.device_io_frame(True, lookahead, lookahead_stride, self.dense_progress)
+        if self.rivals:
+            self.env.device_io_rivals(True, n_rivals, place_reward)
         self.start_rule = None
         if self.random_start:
             if start_margin is None:       # the chassis circles' radius; with bubble_wrap the softeners' sideways reach if that is larger
@@ -226,13 +245,15 @@ class DeviceVecEnv:
                                        self.truncated.data_ptr(), self.final_obs.data_ptr())
         self._io_ref = ctypes.byref(self._io)
         self._step_device = lib.fn("step_device")
-        self._step_device_frame = lib.fn("step_device_frame")
+        self._step_device_rivals = lib.fn("step_device_rivals")
         # The optional rows, one per agent: name, on?, floats per row (capi.STATE_FIELDS; capi.CONTACT_FIELDS; capi.FRAME_FIELDS, then the
-        # look-ahead points) and the argument struct of ftgp_step_device_frame that carries the two buffers.  An absent channel leaves
+        # look-ahead points; capi.RIVAL_FIELDS, then the mate slots) and the argument struct of ftgp_step_device_rivals that carries the
+        # two buffers.  An absent channel leaves
         # its two attributes None and hands the library a null struct.
         channels = (("state", bool(state), capi.STATE_FLOATS, capi.FtgpDeviceStepExtra),
                     ("contact", self.contacts, capi.CONTACT_FLOATS, capi.FtgpDeviceStepContacts),
-                    ("frame", self.track_frame, capi.FRAME_FIXED + 2 * lookahead, capi.FtgpDeviceStepFrame))
+                    ("frame", self.track_frame, capi.FRAME_FIXED + 2 * lookahead, capi.FtgpDeviceStepFrame),
+                    ("rival", self.rivals, capi.RIVAL_FIXED + capi.RIVAL_FLOATS * n_rivals, capi.FtgpDeviceStepRivals))
         self._row_info, self._row_refs = {}, []
         for name, on, width, struct in channels:
             out = torch.zeros((n_envs, self.n_agents, width), dtype=torch.float32, **z) if on else None
@@ -255,6 +276,8 @@ class DeviceVecEnv:
             self.env.state_device(self.state.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         if self.frame is not None:
             self.env.frame_device(self.frame.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        if self.rival is not None:
+            self.env.rivals_device(self.rival.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return self.obs
 
     def episode_index(self):
@@ -282,7 +305,7 @@ class DeviceVecEnv:
             if rc:
                 self.env.lib.check(rc)
             return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
-        rc = self._step_device_frame(self.env.h, self._io_ref, *self._row_refs)    # a null struct for an absent channel
+        rc = self._step_device_rivals(self.env.h, self._io_ref, *self._row_refs)    # a null struct for an absent channel
         if rc:
             self.env.lib.check(rc)
         return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs, **self._row_info}

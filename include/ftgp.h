@@ -474,6 +474,89 @@ int ftgp_step_device_frame(FtgpEnv *env, const FtgpDeviceStep *io, const FtgpDev
 int ftgp_frame_device(FtgpEnv *env, void *stream, float *frame);
 
 /*
+ * Rival rows of the device step: where the other cars of the env are, how fast they close, and whether the car is in front.  The scan
+ * shows a mate only as a few short rays; the row below says it outright.  The reference has none of this; the pieces are the car
+ * records, the nearest-point search of the frame row, absolute_completion and finish_step (the order of ftgp_get_winners).
+ *
+ * The rival row of car a, float32[FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS*n_rivals], is evaluated at the records as they stand.  The
+ * arithmetic rules are those of the frame row: all arithmetic in binary64, one rounding per operation, no contraction, / and sqrt are
+ * IEEE, every entry rounded once to binary32.  Cars are those of a's env, indexed by slot; the path is that of the env's track.
+ *   1. Per car b: its place on the track.  Steps 1 - 3 of the frame row at b's pose give c_b, t_b, the unrounded wrapped s_b and
+ *      off_b (for a finished car too).  f_b = s_b - (double)c_b; if f_b >= 50.0, f_b -= 100.0; if f_b < -50.0, f_b += 100.0; if
+ *      off_b, f_b = 0.0.  Race progress g_b = (double)absolute_completion_b + f_b, absolute_completion_b being column 3 of
+ *      ftgp_get_progress: g_b counts from the car's own start point, it is what decides who reaches lap_target first, and it is
+ *      continuous where the nearest point steps on.
+ *   2. Race order.  For b != a, b is ahead of a when one of these holds:
+ *        both have finished and (finish_step_b, b) < (finish_step_a, a), compared lexicographically with the 64-bit finish_step
+ *          (the order of ftgp_get_winners);
+ *        b has finished and a has not;
+ *        neither has finished, and g_b > g_a;
+ *        neither has finished, g_b == g_a and b < a.
+ *      Otherwise b is not ahead.  Comparisons with NaN are false.
+ *   3. The fixed entries:
+ *        0 place      = 1 + the number of cars ahead of a; for a finished car its ftgp_get_winners place
+ *        1 n_racing   = the number of cars of the env that have not finished
+ *        2 gap_ahead  = the smallest g_b - g_a over unfinished b ahead of a; 0 if there is none or a has finished
+ *        3 gap_behind = the smallest g_a - g_b over unfinished b != a not ahead of a; 0 if there is none or a has finished
+ *   4. Mates.  The mates of a are the unfinished cars b != a -- a finished car is a ghost (custom.py:1441-1466) -- and a finished a
+ *      has no mates.  They are sorted by d2 = dx*dx + dy*dy, dx = x_b - x_a, dy = y_b - y_a, ascending, on equal d2 the smaller slot
+ *      first; the first n_rivals of them fill the row's mate slots k = 0, 1, ...  With ch = qw*qw - qz*qz and sh = 2.0*(qw*qz) of a,
+ *      chb and shb likewise of b, dvx = vx_b - vx_a and dvy = vy_b - vy_a, entry FTGP_RIVAL_FIXED + 8k + i is
+ *        0 fwd       = dx*ch + dy*sh           the mate's position in a's body frame, forward
+ *        1 left      = dy*ch - dx*sh           ... and left
+ *        2 cos_rel   = chb*ch + shb*sh         the mate's heading in a's frame
+ *        3 sin_rel   = shb*ch - chb*sh
+ *        4 v_fwd     = dvx*ch + dvy*sh         the relative velocity in a's frame, forward
+ *        5 v_left    = dvy*ch - dvx*sh         ... and left
+ *        6 track_gap = s_b - s_a; if >= 50.0, - 100.0; if < -50.0, + 100.0      path points along the centre-line, positive = the
+ *                                              mate is further along
+ *        7 present   = 1.0                     the slot holds a mate
+ *      A slot without a mate is eight zeros; n_rivals may exceed cars_per_env - 1, so one policy shape serves every roster.
+ *
+ * The rivals setter is valid after ftgp_device_io_config only (FTGP_ERR_STATE before it); NULL turns rivals off, and so does a later
+ * ftgp_device_io_config; the signals, contacts and frame setters leave rivals alone, and rivals leave them and the spawn rule alone.
+ * Rivals need no frame: they run their own search.  FTGP_ERR_ARG, before anything changes: n_rivals outside 0 .. FTGP_MAX_RIVALS,
+ * place_weight negative, NaN or infinite, a reserved field != 0.  A struct {0, 0, 0, 0} still turns the fixed entries on.
+ *
+ * Place reward (place_weight w != 0).  p0 is a's place at the records the call begins with, p1 its place after the call's steps,
+ * before any reset.  After the off-track, wall and car penalties, in their order: reward = reward + w * (float)(p0 - p1) -- one
+ * binary32 multiplication and one binary32 addition, not fused; the term is 0 if the car had finished when the call began.  With
+ * w == 0 the reward is unchanged to the bit.
+ */
+#define FTGP_RIVAL_FIXED 4
+#define FTGP_RIVAL_FLOATS 8
+#define FTGP_MAX_RIVALS 7
+typedef struct FtgpDeviceRivals {
+    int32_t n_rivals;             /* mate slots per row, 0 .. FTGP_MAX_RIVALS */
+    int32_t reserved;             /* 0 */
+    float place_weight;           /* w of the place reward, >= 0 and finite; 0 = none */
+    float reserved_f;             /* 0 */
+} FtgpDeviceRivals;
+int ftgp_device_io_rivals(FtgpEnv *env, const FtgpDeviceRivals *rivals);
+
+/*
+ * The device step with rival rows: ftgp_step_device_frame(e, io, x, c, f) is this call with rivals = NULL.  rival / final_rival:
+ * float32[n_envs][n_ext][FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS*n_rivals], device memory on the handle's device (a host pointer is
+ * FTGP_ERR_ARG before anything is enqueued); either may be NULL, and the place reward works without them.  Rows are those of the
+ * records after the call's steps.  An env reset in the call gets its pre-reset rows in final_rival (only such rows are written there)
+ * and, in rival, the rows evaluated again at the spawn state, like the frame rows: everyone racing, velocities zero.  Rival buffers
+ * while rivals are off: FTGP_ERR_STATE.  With rivals off and no rival buffers the call launches exactly the kernels of
+ * ftgp_step_device_frame.
+ */
+typedef struct FtgpDeviceStepRivals {
+    float *rival;
+    float *final_rival;
+} FtgpDeviceStepRivals;
+int ftgp_step_device_rivals(FtgpEnv *env, const FtgpDeviceStep *io, const FtgpDeviceStepExtra *extra, const FtgpDeviceStepContacts *contacts,
+                            const FtgpDeviceStepFrame *frame, const FtgpDeviceStepRivals *rivals);
+
+/* The external cars' rival rows at the current state, without a step (e.g. after ftgp_reset), with the n_rivals of the rivals
+ * setter: float32[n_envs][n_ext][FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS*n_rivals] in device memory, ordered on `stream` like
+ * ftgp_frame_device (only enqueues).  After ftgp_device_io_config (FTGP_ERR_STATE before it); with rivals off, n_rivals = 0 and the
+ * rows are the fixed entries. */
+int ftgp_rivals_device(FtgpEnv *env, void *stream, float *rival);
+
+/*
  * Spawn rule: random, wall-aware episode starts.  The reference places car i at path[(i+5)*2] in every episode (custom.py:1112,
  * 1232-1245); FtgpConfig.spawn_mode 0 / 1 are fixed poses too.  A rule is a property of the handle that every reset obeys once it is
  * set -- ftgp_reset with or without a mask and the auto-reset of the device step: start point, lateral offset, yaw and grid order are
@@ -560,6 +643,10 @@ int ftgp_get_contacts(FtgpEnv *env, float *out);
 /* float[n_cars][FTGP_FRAME_FIXED + 2*n_ahead]: the frame row (see FTGP_FRAME_FIXED) of EVERY car at the current state, with the
  * n_ahead (0 .. FTGP_MAX_LOOKAHEAD) and stride (1 .. 50) given here (FTGP_ERR_ARG otherwise); any handle. */
 int ftgp_get_frames(FtgpEnv *env, int n_ahead, int stride, float *out);
+
+/* float[n_cars][FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS*n_rivals]: the rival row (see FTGP_RIVAL_FIXED) of EVERY car at the current
+ * state, with the n_rivals (0 .. FTGP_MAX_RIVALS) given here (FTGP_ERR_ARG otherwise); any handle. */
+int ftgp_get_rivals(FtgpEnv *env, int n_rivals, float *out);
 
 /* int32[n_cars]: place of each car among the finishers of its env, 1 = winner, 0 = still racing (Mujoco.winners, custom.py:1125,1367-1369). */
 int ftgp_get_winners(FtgpEnv *env, int32_t *out);

@@ -1,6 +1,6 @@
 """Env-steps/s of the device I/O loop (DeviceVecEnv.step on torch tensors) against the host loop (set_ctrl + step + get_lidar).
 
-    python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track] [--rows device,torch_pool,signals,contacts,frame,host] [--repeats 1,4] [--cars 1]
+    python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track] [--rows device,torch_pool,signals,contacts,frame,rivals,host] [--repeats 1,4] [--cars 1]
                                    [--max-episode-steps 3000] [--random-start]
 
 Device loop: constant actions, and random torch actions drawn before every call, at action_repeat 1 and 4; per-call time from HIP
@@ -9,7 +9,9 @@ at --max-range and scaled): "torch_pool" = the raw scan plus the torch ops a use
 scale), "signals" = the same from the library (scan_pool, scan_max_range, state=True: ftgp_io_finish_signals_kernel), "contacts" = the
 signals row with contact rows, both contact terminations and both penalties on top (ftgp_io_contact_kernel between the step and the
 finish kernel), "frame" = the raw scan with the track frame on top (lookahead=8, dense_progress=True: ftgp_io_frame_kernel before and
-after the steps, rows and reward by ftgp_io_finish_signals_kernel).  --cars: cars per env, every one an agent.  --random-start: the device rows run under a spawn rule (ftgp_set_spawn_rule:
+after the steps, rows and reward by ftgp_io_finish_signals_kernel), "rivals" = the frame row with the rival rows on top (rivals=True,
+n_rivals=3: ftgp_io_rival_kernel behind the frame kernel; meaningful with --cars 4, and its difference to the frame row is what the
+channel costs).  --cars: cars per env, every one an agent.  --random-start: the device rows run under a spawn rule (ftgp_set_spawn_rule:
 lateral share 0.8, yaw offsets up to 0.2 rad, shuffled grid); with a small --max-episode-steps the auto-reset, and with it the draw, runs often.
 Host loop: per
 step set_ctrl (one copy + synchronisation), step(1), get_lidar (the whole scan back).  One JSON line per row, then a summary line.  Run it in a fresh process: torch is imported first
@@ -36,12 +38,14 @@ from ft_grandprix_amd.vec import DeviceVecEnv  # noqa: E402
 
 def device_row(track, a, repeat, actions, pooled=None):
     """pooled: None = the raw scan; "torch" = pooled, clipped and scaled with torch ops after the call; "signals" = by the library;
-    "contacts" = signals and the contact signals; "frame" = the raw scan, frame rows with 8 look-ahead points and the dense reward."""
+    "contacts" = signals and the contact signals; "frame" = the raw scan, frame rows with 8 look-ahead points and the dense reward; "rivals" = frame and rival rows with 3 mate slots."""
     kw = dict(scan_pool=a.pool, scan_max_range=a.max_range, state=True) if pooled in ("signals", "contacts") else {}
     if pooled == "contacts":
         kw.update(contacts=True, terminate_on_wall_contact=True, terminate_on_car_contact=True, wall_contact_penalty=1.0, car_contact_penalty=0.5)
-    if pooled == "frame":
+    if pooled in ("frame", "rivals"):
         kw.update(lookahead=8, dense_progress=True)
+    if pooled == "rivals":
+        kw.update(rivals=True, n_rivals=3)
     if a.random_start:
         kw.update(random_start=True, start_lateral=0.8, start_yaw_jitter=0.2, shuffle_grid=True)
     venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, cars_per_env=a.cars, max_episode_steps=a.max_episode_steps, action_repeat=repeat, spawn_mode=1,
@@ -81,8 +85,9 @@ def device_row(track, a, repeat, actions, pooled=None):
     step_ms = venv.env.last_kernel_ms()
     episodes = int(venv.episode_index().sum()) if a.random_start else None
     venv.close()
-    loop = {None: "device", "torch": "device+torch_pool", "signals": "device+signals", "contacts": "device+signals+contacts", "frame": "device+frame"}[pooled]
-    extra = {} if pooled in (None, "frame") else {"pool": a.pool, "max_range": a.max_range}
+    loop = {None: "device", "torch": "device+torch_pool", "signals": "device+signals", "contacts": "device+signals+contacts", "frame": "device+frame",
+            "rivals": "device+frame+rivals"}[pooled]
+    extra = {} if pooled in (None, "frame", "rivals") else {"pool": a.pool, "max_range": a.max_range}
     extra["max_episode_steps"] = a.max_episode_steps
     if a.random_start:
         extra.update(random_start=True, resets=episodes)
@@ -121,7 +126,7 @@ def main():
     ap.add_argument("--cars", type=int, default=1, help="cars per env, every one an agent")
     ap.add_argument("--max-episode-steps", type=int, default=3000, help="truncation of the device rows")
     ap.add_argument("--random-start", action="store_true", help="the device rows run under a spawn rule")
-    ap.add_argument("--rows", default="device,torch_pool,signals,host", help="comma-separated: device, torch_pool, signals, contacts, frame, host")
+    ap.add_argument("--rows", default="device,torch_pool,signals,host", help="comma-separated: device, torch_pool, signals, contacts, frame, rivals, host")
     a = ap.parse_args()
     want = set(a.rows.split(","))
     track = load_track(a.track)
@@ -131,7 +136,7 @@ def main():
             for actions in ("constant", "random"):
                 rows.append(device_row(track, a, repeat, actions))
                 print(json.dumps(rows[-1]), flush=True)
-    for name, pooled in (("torch_pool", "torch"), ("signals", "signals"), ("contacts", "contacts"), ("frame", "frame")):
+    for name, pooled in (("torch_pool", "torch"), ("signals", "signals"), ("contacts", "contacts"), ("frame", "frame"), ("rivals", "rivals")):
         if name in want:
             rows.append(device_row(track, a, 1, "constant", pooled))
             print(json.dumps(rows[-1]), flush=True)
