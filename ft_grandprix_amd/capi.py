@@ -30,6 +30,7 @@ RIVAL_FIXED = 4              # FTGP_RIVAL_FIXED: the fixed entries of a rival ro
 RIVAL_FLOATS = 8             # FTGP_RIVAL_FLOATS: a mate slot (RIVAL_MATE_FIELDS)
 MAX_RIVALS = 7               # FTGP_MAX_RIVALS
 MAX_TRACKS = 16             # FTGP_MAX_TRACKS: tracks of one multi-track handle (ftgp_create_tracks)
+DYN_DOUBLES = 8             # FTGP_DYN_DOUBLES: a dynamics row of a car (DYN_FIELDS; ftgp_set_dynamics)
 
 POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2, 3, 4
 LIDAR_RANGEFINDER, LIDAR_FAKELIDAR = 0, 1
@@ -45,6 +46,7 @@ CONTACT_FIELDS = ("wall_pen", "car_pen", "wall_count", "car_count")
 FRAME_FIELDS = ("lat", "cos_h", "sin_h", "s_norm")
 RIVAL_FIELDS = ("place", "n_racing", "gap_ahead", "gap_behind")
 RIVAL_MATE_FIELDS = ("fwd", "left", "cos_rel", "sin_rel", "v_fwd", "v_left", "track_gap", "present")
+DYN_FIELDS = ("mass", "izz", "friction", "tire_damping", "throttle_kv", "throttle_force_limit", "steer_kp", "steer_damping")
 METRIC_FIELDS = ("steps", "n_cars", "sum_laps", "sum_absolute_completion", "n_finished",
                  "n_off_track", "min_lap_time", "max_lap_time")
 
@@ -95,6 +97,7 @@ API_SYMBOLS = (
     "set_spawn_rule", "get_episodes", "get_start_table",
     "device_io_frame", "step_device_frame", "frame_device", "get_frames",
     "device_io_rivals", "step_device_rivals", "rivals_device", "get_rivals",
+    "set_dynamics", "set_dynamics_device", "get_dynamics",
 )
 
 
@@ -235,6 +238,9 @@ class CLib:
             "set_spawn_rule": (i32, [vp, C.POINTER(FtgpSpawnRule)]),
             "get_episodes": (i32, [vp, dp]),
             "get_start_table": (i32, [vp, i32, dp]),
+            "set_dynamics": (i32, [vp, dp, dp]),
+            "set_dynamics_device": (i32, [vp, vp, vp, vp]),
+            "get_dynamics": (i32, [vp, dp, C.POINTER(C.c_int64)]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -494,6 +500,41 @@ class Env:
         out = np.empty((PATH_POINTS, 6), dtype=np.float64)
         self._call("get_start_table", track, _ptr(out))
         return out
+
+    # -- per-car dynamics (include/ftgp.h: ftgp_set_dynamics)
+    def base_dynamics(self) -> np.ndarray:
+        """float64 [DYN_DOUBLES]: the handle's own dynamics row, i.e. the DYN_FIELDS of its vehicle."""
+        return np.array([getattr(self.cfg.vehicle, f) for f in DYN_FIELDS], dtype=np.float64)
+
+    def set_dynamics(self, rows, env_mask: Optional[np.ndarray] = None):
+        """ftgp_set_dynamics: ``rows`` float64 [n_envs, cars_per_env, DYN_DOUBLES] (DYN_FIELDS) become the dynamics of the cars of the
+        envs ``env_mask`` (uint8 [n_envs], None = all) names; the first call turns the table on, every other car starting from the
+        handle's own values.  ``rows=None`` turns the table off."""
+        if rows is None:
+            if env_mask is not None:
+                raise ValueError("set_dynamics(None) takes no mask")
+            self._call("set_dynamics", None, None)
+            return
+        r = np.ascontiguousarray(rows, dtype=np.float64)
+        if r.size != self.n_cars * DYN_DOUBLES:
+            raise ValueError(f"rows: {self.n_cars} x {DYN_DOUBLES} values, got shape {r.shape}")
+        m = None if env_mask is None else np.ascontiguousarray(env_mask, dtype=np.uint8)
+        if m is not None and m.shape != (self.n_envs,):
+            raise ValueError(f"env_mask: one byte per env, expected ({self.n_envs},), got {m.shape}")
+        self._call("set_dynamics", _ptr(r), _ptr(m))
+
+    def set_dynamics_device(self, rows_ptr: int, env_mask_ptr: int = 0, stream: int = 0):
+        """ftgp_set_dynamics_device on integer device addresses (float64 [n_envs, cars_per_env, DYN_DOUBLES], uint8 [n_envs] or 0 = all
+        envs), ordered on ``stream``; only enqueues.  A car whose row is invalid keeps its old one (``dynamics()[1]`` counts them)."""
+        self._call("set_dynamics_device", stream or None, rows_ptr or None, env_mask_ptr or None)
+
+    def dynamics(self):
+        """(rows, rejected): float64 [n_cars, DYN_DOUBLES], the dynamics row in force for every car (the handle's own values while the
+        table is off), and the number of rows the device setter has rejected since the table was turned on."""
+        out = np.empty((self.n_cars, DYN_DOUBLES), dtype=np.float64)
+        rejected = C.c_int64(0)
+        self._call("get_dynamics", _ptr(out), C.byref(rejected))
+        return out, int(rejected.value)
 
     @staticmethod
     def _step_args(stream, action, obs, reward, terminated, truncated, final_obs, *rows):

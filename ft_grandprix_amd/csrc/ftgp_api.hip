@@ -188,6 +188,11 @@ struct FtgpEnv {
     std::vector<double> start_table;  // [n_tracks][FTGP_PATH_POINTS][6] x, y, qw, qz, clear_left, clear_right: the plan's (ftgp_get_start_table)
     const FtgpSpawnDev* rule = nullptr;      // what the reset paths are handed: d_rule while a rule is set, null without one
     DevBuf<FtgpSpawnDev> d_rule; DevBuf<int32_t> d_start, d_n_start; DevBuf<double> d_clear; DevBuf<int64_t> d_episodes;      // allocated by the first rule
+    // per-car dynamics (ftgp_set_dynamics)
+    DevBuf<double> d_dyn;             // [n_cars][FTGP_DYN_RECORD] records, then the rejected counter; allocated by the first setter call (ensure_dynamics)
+    bool dyn_on = false;              // step launches run the DYN instantiations
+    DynArgs dyn{};                    // the handle's own row and the wheel-load rule (the buffers are filled in per call)
+    DevBuf<double> d_dyn_rows;        // [n_cars][FTGP_DYN_DOUBLES] landing buffer of the host setter, allocated on first use
     // comm
     void* comm = nullptr; int rank = 0, world = 1;
 };
@@ -795,8 +800,21 @@ const StepKernel kStepKernels[2][2][3] = {      // [multi-track][multi][0: singl
       { ftgp_step_kernel<true, true, true, true>, "ftgp_step_kernel<true, true, true, true>" } } },
 };
 
+// ftgp_step_kernel<MULTI, false, ROSTER, TRACKS, true>: launches with the table of per-car dynamics on (ftgp_set_dynamics)
+const StepKernel kStepKernelsDyn[2][2][2] = {   // [multi-track][multi][roster]
+  { { { ftgp_step_kernel<false, false, false, false, true>, "ftgp_step_kernel<false, false, false, false, true>" },
+      { ftgp_step_kernel<false, false, true, false, true>, "ftgp_step_kernel<false, false, true, false, true>" } },
+    { { ftgp_step_kernel<true, false, false, false, true>, "ftgp_step_kernel<true, false, false, false, true>" },
+      { ftgp_step_kernel<true, false, true, false, true>, "ftgp_step_kernel<true, false, true, false, true>" } } },
+  { { { ftgp_step_kernel<false, false, false, true, true>, "ftgp_step_kernel<false, false, false, true, true>" },
+      { ftgp_step_kernel<false, false, true, true, true>, "ftgp_step_kernel<false, false, true, true, true>" } },
+    { { ftgp_step_kernel<true, false, false, true, true>, "ftgp_step_kernel<true, false, false, true, true>" },
+      { ftgp_step_kernel<true, false, true, true, true>, "ftgp_step_kernel<true, false, true, true, true>" } } },
+};
+
 const StepKernel& step_kernel(const FtgpEnv* e, bool roster)
 {
+    if (e->dyn_on) return kStepKernelsDyn[e->n_tracks > 1][e->multi][roster];      // (never a FAKELIDAR handle: the setters refuse it)
     return kStepKernels[e->n_tracks > 1][e->multi][e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR ? 2 : roster ? 1 : 0];
 }
 
@@ -858,7 +876,8 @@ int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
     if (!ext) HIP_TRY(hipEventRecord(e->ev_start.get(), e->stream.get()));
     if (n_steps > 0) {
         const dim3 grid(blocks), block(e->P.waves_per_block * FTGP_WAVE);
-        const uint32_t lds = (uint32_t)e->P.lds_bytes;
+        // (with the table of per-car dynamics on, the cars' records lie behind the layout)
+        const uint32_t lds = (uint32_t)e->P.lds_bytes + (e->dyn_on ? (uint32_t)(e->P.cars_per_block * FTGP_DYN_RECORD * sizeof(double)) : 0u);
         hipEvent_t ev0 = ext ? e->ev_start.get() : nullptr, ev1 = ext ? e->ev_stop[slot].get() : nullptr;
         const bool roster = policy == FTGP_POLICY_PER_CAR;
         e->last_roster = roster;
@@ -1050,6 +1069,42 @@ int rows_to_device(FtgpEnv* e, const char* entry, void* stream, size_t floats, f
     return caller_waits_for_handle(e, (hipStream_t)stream);
 }
 
+// The first setter call of a handle: the DYN kernels may use the LDS the others may, the records are allocated (zeroed, the counter with
+// them) and every parameter block learns their address.  ftgp_create does nothing for the table: a handle that never sets one is, on the
+// host and on the device, the handle it always was.
+int ensure_dynamics(FtgpEnv* e)
+{
+    if (e->d_dyn) return 0;
+    for (const auto& set : kStepKernelsDyn) for (const auto& row : set) for (const StepKernel& k : row) HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the blocks while they change
+    DevBuf<double> d;
+    HIP_TRY(dev_alloc(d, FTGP_DYN_BYTES(e->P.n_cars)));
+    HIP_TRY(hipMemset(d.get(), 0, FTGP_DYN_BYTES(e->P.n_cars)));
+    const uint64_t a = (uint64_t)(uintptr_t)d.get();
+    const uint32_t lo = (uint32_t)a, hi = (uint32_t)(a >> 32);
+    for (const TrackBufs& t : e->trk) {   // every track's parameter block
+        unsigned char* block = reinterpret_cast<unsigned char*>(e->d_params.get()) + t.block;
+        HIP_TRY(hipMemcpy(block + offsetof(DeviceParams, dyn_table_lo), &lo, sizeof lo, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(block + offsetof(DeviceParams, dyn_table_hi), &hi, sizeof hi, hipMemcpyHostToDevice));
+    }
+    e->P.dyn_table_lo = lo; e->P.dyn_table_hi = hi;
+    e->d_dyn = std::move(d);
+    return 0;
+}
+
+// ftgp_set_dynamics / ftgp_set_dynamics_device: ftgp_dynamics_kernel on the handle's stream; the first launch since the table was off
+// also gives every car the handle's own row
+int launch_dynamics(FtgpEnv* e, const double* rows, const uint8_t* env_mask)
+{
+    if (int rc = ensure_dynamics(e)) return rc;
+    DynArgs A = e->dyn;
+    A.init = e->dyn_on ? 0 : 1; A.rows = rows; A.env_mask = env_mask;
+    hipLaunchKernelGGL(ftgp_dynamics_kernel, dim3((unsigned)((e->P.n_cars + 255) / 256)), dim3(256), 0, e->stream.get(), e->P, A);
+    HIP_TRY(hipGetLastError());
+    e->dyn_on = true;
+    return 0;
+}
+
 bool nonneg_finite(double v) { return v >= 0.0 && !std::isinf(v); }      // a penalty, a range, a margin; a NaN fails as well
 
 // ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images
@@ -1153,6 +1208,22 @@ int upload(FtgpEnv* e, const Plan& pl, const Switches& sw)
     layout_images(pl, a, im);
     for (int k = 0; k < T; ++k) e->trk[(size_t)k].block = im.blocks[(size_t)k];
     memcpy(&e->P, &im.P0, sizeof e->P);         // as it lies, padding included
+    {   // per-car dynamics: the handle's own row, and plan()'s wheel-load rule as factors of wtot (the same operands, divided once here)
+        const FtgpVehicle& v = e->P.veh;
+        const double base[FTGP_DYN_DOUBLES] = { v.mass, v.izz, v.friction, v.tire_damping, v.throttle_kv, v.throttle_force_limit, v.steer_kp, v.steer_damping };
+        DynArgs& d = e->dyn;
+        memcpy(d.base, base, sizeof base);
+        d.gravity = v.gravity;
+        if (v.kind == FTGP_VEHICLE_TRICYCLE) {
+            const double a_f = v.wheel_x[2], a_r = -0.5 * (v.wheel_x[0] + v.wheel_x[1]);
+            d.load_k[0] = d.load_k[1] = a_f / (a_f + a_r); d.load_half[0] = d.load_half[1] = 1;
+            d.load_k[2] = a_r / (a_f + a_r); d.load_k[3] = 0.0; d.load_half[2] = d.load_half[3] = 0;
+        } else {
+            const double a_f = 0.5 * (v.wheel_x[0] + v.wheel_x[1]), a_r = -0.5 * (v.wheel_x[2] + v.wheel_x[3]);
+            d.load_k[0] = d.load_k[1] = a_r / (a_f + a_r); d.load_k[2] = d.load_k[3] = a_f / (a_f + a_r);
+            for (int r = 0; r < 4; ++r) d.load_half[r] = 1;
+        }
+    }
     HIP_TRY(hipMemcpy(e->d_stage.get(), im.stage.data(), im.stage.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->d_params.get(), im.params.data(), im.params.size(), hipMemcpyHostToDevice));
     return 0;
@@ -1619,6 +1690,76 @@ int ftgp_set_spawn_rule(FtgpEnv* e, const FtgpSpawnRule* r)
         HIP_TRY(hipStreamSynchronize(e->stream.get()));
     }
     e->rule = r ? e->d_rule.get() : nullptr;
+    return 0;
+}
+
+int ftgp_set_dynamics(FtgpEnv* e, const double* rows, const uint8_t* env_mask)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_dynamics: not on a FTGP_LIDAR_FAKELIDAR handle%s");
+    const size_t n_cars = (size_t)e->P.n_cars;
+    HIP_TRY(hipSetDevice(e->device));
+    if (!rows) {                     // off: later launches run the kernels of a handle without a table
+        if (env_mask) return fail(FTGP_ERR_ARG, "ftgp_set_dynamics: a mask without rows%s");
+        if (e->d_dyn) HIP_TRY(hipMemsetAsync(dyn_rejected(&e->P), 0, sizeof(unsigned long long), e->stream.get()));
+        HIP_TRY(hipStreamSynchronize(e->stream.get()));
+        e->dyn_on = false;
+        return 0;
+    }
+    static const char* const names[FTGP_DYN_DOUBLES] = { "mass", "izz", "friction", "tire_damping", "throttle_kv", "throttle_force_limit", "steer_kp", "steer_damping" };
+    for (size_t i = 0; i < n_cars; ++i) {
+        if (env_mask && !env_mask[i / (size_t)e->P.cars_per_env]) continue;
+        for (int k = 0; k < FTGP_DYN_DOUBLES; ++k) {
+            const double x = rows[i * FTGP_DYN_DOUBLES + k];
+            if (!(k < 2 ? x > 0.0 : x >= 0.0) || std::isinf(x))
+                return failf(FTGP_ERR_ARG, "ftgp_set_dynamics: car %zu, entry %d (%s) = %g: every entry finite, mass and izz > 0, the others >= 0", i, k, names[k], x);
+        }
+    }
+    if (!e->d_dyn_rows) HIP_TRY(dev_alloc(e->d_dyn_rows, sizeof(double) * FTGP_DYN_DOUBLES * n_cars));
+    HIP_TRY(hipMemcpyAsync(e->d_dyn_rows.get(), rows, sizeof(double) * FTGP_DYN_DOUBLES * n_cars, hipMemcpyHostToDevice, e->stream.get()));
+    const uint8_t* dmask = nullptr;
+    if (env_mask) {
+        HIP_TRY(hipMemcpyAsync(e->d_env_mask.get(), env_mask, (size_t)e->P.n_envs, hipMemcpyHostToDevice, e->stream.get()));
+        dmask = e->d_env_mask.get();
+    }
+    if (int rc = launch_dynamics(e, e->d_dyn_rows.get(), dmask)) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));   // the caller's buffers may be reused as soon as we return
+    return 0;
+}
+
+int ftgp_set_dynamics_device(FtgpEnv* e, void* stream, const double* rows, const uint8_t* env_mask)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_dynamics_device: not on a FTGP_LIDAR_FAKELIDAR handle%s");
+    HIP_TRY(hipSetDevice(e->device));
+    // (check_device_buffer words its refusals for the device step: put this entry's name in front)
+    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_dynamics_device: %s", m.c_str()); return rc; };
+    if (int rc = check_device_buffer(e, rows, sizeof(double) * FTGP_DYN_DOUBLES * (size_t)e->P.n_cars, "rows")) return refused(rc);
+    if (env_mask) if (int rc = check_device_buffer(e, env_mask, (size_t)e->P.n_envs, "env_mask")) return refused(rc);
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    if (int rc = launch_dynamics(e, rows, env_mask)) return rc;
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+int ftgp_get_dynamics(FtgpEnv* e, double* rows_out, int64_t* rejected_out)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    const size_t n_cars = (size_t)e->P.n_cars;
+    if (!e->dyn_on) {
+        if (rows_out) for (size_t i = 0; i < n_cars; ++i) memcpy(rows_out + i * FTGP_DYN_DOUBLES, e->dyn.base, sizeof e->dyn.base);
+        if (rejected_out) *rejected_out = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    unsigned long long rejected = 0;
+    if (rows_out)        // the first eight doubles of every record
+        HIP_TRY(hipMemcpy2DAsync(rows_out, sizeof(double) * FTGP_DYN_DOUBLES, dyn_table(&e->P), sizeof(double) * FTGP_DYN_RECORD,
+                                 sizeof(double) * FTGP_DYN_DOUBLES, n_cars, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipMemcpyAsync(&rejected, dyn_rejected(&e->P), sizeof rejected, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    if (rejected_out) *rejected_out = (int64_t)rejected;
     return 0;
 }
 

@@ -65,7 +65,7 @@ struct DeviceParams {
     double px_size_x, px_size_y, origin_x, origin_y, inv_px_x, inv_px_y;
     float inv_px_x_f, inv_px_y_f;
     float snap_eps;               // the march re-checks a landing point with the exact comparisons within this distance of a pixel boundary
-    uint32_t reserved_m0;         // (rounds 2 - 4: the ray pool's division by multiplication)
+    uint32_t dyn_table_lo;        // per-car dynamics (ftgp_set_dynamics): the low half of the records' device address, 0 until the first setter call (dyn_table())
     uint32_t plane256;            // bytes per (padded) sector plane of the box field / 256
     int32_t n_sectors;            // direction sectors of this handle's box field: 8 x (1, 2, 4 or 8 slope slices per octant)
     float slice_factor;           // FTGP_SLICE_FACTOR(FTGP_SLOPE_SLICES): a ray's sector is found among all FTGP_SECTORS, sector_tab maps it to planes
@@ -85,7 +85,7 @@ struct DeviceParams {
     int32_t lidar_mode, pad_e;
     int32_t tasks_per_car;        // the sweep's work list per car (lidar_groups): groups of 64 consecutive rays, or pairs of opposite groups
     float group_cg, group_sg;     // cos / sin of the half-width of a ray group as mate_masks() needs it (cg < -1: no bound, e.g. a caller's fan)
-    uint32_t reserved_m1;         // (rounds 4 - 5: the group draw's division by multiplication; a draw now reads its task descriptor, task_tab)
+    uint32_t dyn_table_hi;        // ... and its high half (two words that were spare: the block's layout is what it was)
     const uint16_t* field;        // [n_sectors][height + 2][width + 2] box entries (ftgp_march.h), HBM/L2
     const uint32_t* bits;         // [height][words_per_row] wall bitmap
     const uint32_t* nearbits;     // [height][words_per_row] wall bitmap dilated by contact_reach (early-out of the wall contact)
@@ -141,6 +141,27 @@ struct VehLds {
                                   // the puck, min(box, puck) is the box's time to the bit, and ray_vs_car() leaves the circle test (a square root) out
     // binary32 of the constants the inter-vehicle ray test uses (the conversions the specification makes per test, made once)
     float box_xmin_f, box_xmax_f, box_ymin_f, box_ymax_f, lidar_x_f, lidar_y_f, ring_radius_f, pad_f;
+};
+
+// Per-car dynamics (ftgp_set_dynamics): one record of FTGP_DYN_RECORD doubles per car in HBM, allocated by the first setter call: the
+// eight entries of the car's row in the header's order, then its four static wheel loads; behind the records, the counter of rejected
+// rows.  The parameter blocks carry the address in two spare words (dyn_table_lo / _hi), so their layout, the staging image and the LDS
+// offsets are what they were.  A step launch with the table on stages its workgroup's records into LDS behind the layout of
+// lds_layout(), at lds_bytes (ftgp_step_kernel<..., DYN = true>).
+#define FTGP_DYN_RECORD 12
+enum { kDynMass = 0, kDynIzz, kDynFriction, kDynTireDamping, kDynThrottleKv, kDynThrottleForceLimit, kDynSteerKp, kDynSteerDamping, kDynWheelLoad };
+template <class PP> __host__ __device__ inline double* dyn_table(PP p) { return reinterpret_cast<double*>(((uint64_t)p->dyn_table_hi << 32) | (uint64_t)p->dyn_table_lo); }
+template <class PP> __host__ __device__ inline unsigned long long* dyn_rejected(PP p) { return reinterpret_cast<unsigned long long*>(dyn_table(p) + (size_t)p->n_cars * FTGP_DYN_RECORD); }
+#define FTGP_DYN_BYTES(n_cars) ((size_t)(n_cars) * FTGP_DYN_RECORD * sizeof(double) + 16)
+// ftgp_dynamics_kernel's arguments: the handle's own row and what turns a mass into wheel loads (plan()'s static wheel loads: load[r] =
+// wtot * load_k[r], halved where load_half[r])
+struct DynArgs {
+    double base[FTGP_DYN_DOUBLES];
+    double gravity, load_k[4];
+    int32_t load_half[4];
+    int32_t init, pad;                // init: the table is being turned on -- every car's record starts as the handle's own
+    const double* rows;               // [n_cars][FTGP_DYN_DOUBLES] or null
+    const uint8_t* env_mask;          // [n_envs] or null = all envs
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -980,9 +980,11 @@ __device__ __forceinline__ void quad_argmin_step(double& best, int& idx)
 //   K3  25 centre-line points per lane, first minimum wins; steps += 1 happens between K1 and K3, as in custom.py:1425-1426
 //       followed by the head of the next loop iteration.
 // Then the LiDAR frames of the next step are written.
-template <bool MULTI>
+// DYN: the table of per-car dynamics is on (ftgp_set_dynamics): the eight entries of the car's row and its wheel loads come from the car's
+// own record in LDS (`dyn`, FTGP_DYN_RECORD doubles per car slot: the car's four lanes read one address), everything else from L.veh as ever.
+template <bool MULTI, bool DYN>
 __device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds& L, LidarFrame* next_frames, PairCull* next_pairs, unsigned char* next_mmask, ScalarInts order,
-                                               int* unsafe_next, int ncars_here, int ci0)
+                                               int* unsafe_next, int ncars_here, int ci0, const double* dyn)
 {
     const int lane = lane_here();
     const int c = lane >> 2, r = lane & 3;
@@ -993,6 +995,7 @@ __device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds&
     const bool finished = st->finished != 0;
     SUBSTAMP_BEGIN();
     {   // ---- wheel r
+        const double* mine = dyn + (on ? c : 0) * FTGP_DYN_RECORD;      // (DYN only)
         const double qw = st->qw, qz = st->qz;
         const double ch = 1.0 - 2.0 * (qz * qz), sh = 2.0 * (qw * qz);
         const double vx = st->vx, vy = st->vy, wz = st->wz;
@@ -1009,9 +1012,17 @@ __device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds&
         if (!tri) {
             // velocity servo on the tendon = mean wheel spin, mushr.em.xml:180,191-196
             const double wbar = 0.25 * (((st->w[0] + st->w[1]) + st->w[2]) + st->w[3]);
-            double fa = v.throttle_kv * (st->u_speed - v.throttle_gear * wbar);
-            if (fa > v.throttle_force_limit) fa = v.throttle_force_limit;
-            if (fa < -v.throttle_force_limit) fa = -v.throttle_force_limit;
+            double fa;
+            if constexpr (DYN) {
+                const double flim = mine[kDynThrottleForceLimit];
+                fa = mine[kDynThrottleKv] * (st->u_speed - v.throttle_gear * wbar);
+                if (fa > flim) fa = flim;
+                if (fa < -flim) fa = -flim;
+            } else {
+                fa = v.throttle_kv * (st->u_speed - v.throttle_gear * wbar);
+                if (fa > v.throttle_force_limit) fa = v.throttle_force_limit;
+                if (fa < -v.throttle_force_limit) fa = -v.throttle_force_limit;
+            }
             torque = (v.throttle_gear * 0.25) * fa;
         } else {
             // two torque motors on the tendons 0.5 (l + r) and 0.5 (r - l), controls clamped to their ctrlrange (car.em.xml:126-139)
@@ -1031,8 +1042,14 @@ __device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds&
         const double fdx = ch * cwi - sh * swi, fdy = sh * cwi + ch * swi;
         const double vlong = (vpx * fdx + vpy * fdy) - v.wheel_radius * wi;
         const double vlat = vpy * fdx - vpx * fdy;
-        double flong = -(v.tire_damping * vlong), flat = -(v.tire_damping * vlat);
-        const double lim = v.friction * L.veh->wheel_load[r];
+        double flong, flat, lim;
+        if constexpr (DYN) {
+            flong = -(mine[kDynTireDamping] * vlong); flat = -(mine[kDynTireDamping] * vlat);
+            lim = mine[kDynFriction] * mine[kDynWheelLoad + r];
+        } else {
+            flong = -(v.tire_damping * vlong); flat = -(v.tire_damping * vlat);
+            lim = v.friction * L.veh->wheel_load[r];
+        }
         const double m2 = flong * flong + flat * flat;
         if (m2 > lim * lim) { const double sc = lim / sqrt(m2); flong = flong * sc; flat = flat * sc; }
         Force t;
@@ -1078,11 +1095,19 @@ __device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds&
         }
         const double dt = P.dt;
         Dyn o;
-        o.vx = st->vx + dt * (f.fx / v.mass);
-        o.vy = st->vy + dt * (f.fy / v.mass);
-        o.wz = st->wz + dt * (f.tz / v.izz);
-        // position servo on the steering joint, implicit damping (mushr.em.xml:78,179)
-        o.qsd = (v.steer_inertia * st->qsd + dt * (v.steer_kp * (st->u_steer - st->qs))) / (v.steer_inertia + dt * v.steer_damping);
+        if constexpr (DYN) {         // (the car's own mass, yaw inertia and steering servo)
+            const double* mine = dyn + c * FTGP_DYN_RECORD;
+            o.vx = st->vx + dt * (f.fx / mine[kDynMass]);
+            o.vy = st->vy + dt * (f.fy / mine[kDynMass]);
+            o.wz = st->wz + dt * (f.tz / mine[kDynIzz]);
+            o.qsd = (v.steer_inertia * st->qsd + dt * (mine[kDynSteerKp] * (st->u_steer - st->qs))) / (v.steer_inertia + dt * mine[kDynSteerDamping]);
+        } else {
+            o.vx = st->vx + dt * (f.fx / v.mass);
+            o.vy = st->vy + dt * (f.fy / v.mass);
+            o.wz = st->wz + dt * (f.tz / v.izz);
+            // position servo on the steering joint, implicit damping (mushr.em.xml:78,179)
+            o.qsd = (v.steer_inertia * st->qsd + dt * (v.steer_kp * (st->u_steer - st->qs))) / (v.steer_inertia + dt * v.steer_damping);
+        }
         o.qs = st->qs + dt * o.qsd;
         if (o.qs > v.steer_limit) { o.qs = v.steer_limit; if (o.qsd > 0.0) o.qsd = 0.0; }
         if (o.qs < -v.steer_limit) { o.qs = -v.steer_limit; if (o.qsd < 0.0) o.qsd = 0.0; }
@@ -1574,7 +1599,10 @@ __device__ __forceinline__ void stage16(void* dst, const void* src, int bytes)
 // FAKELIDAR kernels, which are for parity and not for throughput, exist in the ROSTER form only.
 // TRACKS: the instantiations of multi-track handles (ftgp_create_tracks): the workgroups of a launch race different tracks, each workgroup
 // one.  With TRACKS = false the code is exactly the one-track kernel's.
-template <bool MULTI, bool FAKE, bool ROSTER, bool TRACKS>
+// DYN: launches with the table of per-car dynamics on (ftgp_set_dynamics) -- their own instantiations once more, MULTI x ROSTER x TRACKS with
+// FAKE = false: the workgroup stages its cars' records into LDS behind the layout, at lds_bytes (the launch asks for cars_per_block records
+// more), and dynamics_lanes() reads them.  With DYN = false the code is exactly what it was.
+template <bool MULTI, bool FAKE, bool ROSTER, bool TRACKS, bool DYN = false>
 __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(const DeviceParams* __restrict__ Pg, int policy, int n_steps, int metrics_slot)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -1642,6 +1670,11 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
         wave_lds_sync();
         if (lane == 0 && !frame_write(P, L.veh->v, L.cars + c, L.frame + c, c)) atomicOr(L.pool + 4, 1);
     }
+    if (DYN) {                           // the cars' dynamics records (read from the next step barrier on)
+        const double* src = dyn_table(scalar_view(Pt)) + (size_t)ci0 * FTGP_DYN_RECORD;       // (the address: from the block in device memory, which the first setter call patched)
+        double* dst = reinterpret_cast<double*>(lds + P.lds_bytes);
+        for (int i = (int)threadIdx.x; i < ncars_here * FTGP_DYN_RECORD; i += (int)blockDim.x) dst[i] = src[i];
+    }
     if (MULTI) {                         // env-mate records of the first frames
         __syncthreads();
         // (a loop: one wave per workgroup -- FTGP_WAVES_PER_BLOCK=1 -- has 64 threads for up to 16 cars x FTGP_PAIR_STRIDE records)
@@ -1697,8 +1730,8 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
                 if (n == ncars_here - 1) {            // every driver of the workgroup has delivered its controls
                     if (lane_here() == 0) { L.pool[par ^ 1] = 0; L.pool[2 + (par ^ 1)] = 0; }     // the next step's counters (idle during this step)
                     if (FTGP_DIAG_RUN_K1)
-                        dynamics_lanes<MULTI>(P, L, next_frames, L.pairs + (par ^ 1) * cpb * FTGP_PAIR_STRIDE, L.mmask + (par ^ 1) * cpb * G->mmask_stride, &G->group_order[0],
-                                              L.pool + 4 + (par ^ 1), ncars_here, ci0);
+                        dynamics_lanes<MULTI, DYN>(P, L, next_frames, L.pairs + (par ^ 1) * cpb * FTGP_PAIR_STRIDE, L.mmask + (par ^ 1) * cpb * G->mmask_stride, &G->group_order[0],
+                                                   L.pool + 4 + (par ^ 1), ncars_here, ci0, DYN ? reinterpret_cast<const double*>(lds + opaque(G->lds_bytes)) : nullptr);
                     STAMP(t2); STAMP_ADD(2, t2 - t1); STAMP_ADD(7, 1);
                 }
             }
@@ -1752,6 +1785,14 @@ template __global__ void ftgp_step_kernel<false, false, true, true>(const Device
 template __global__ void ftgp_step_kernel<true, false, true, true>(const DeviceParams*, int, int, int);
 template __global__ void ftgp_step_kernel<false, true, true, true>(const DeviceParams*, int, int, int);
 template __global__ void ftgp_step_kernel<true, true, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, false, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, false, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, false, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, false, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, true, true>(const DeviceParams*, int, int, int);
 
 // K5 alone: one wave per car evaluates the driver on the scan stored in P.ranges (ftgp_policy_eval).
 __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int policy, double* __restrict__ ctrl_out)
@@ -1894,6 +1935,37 @@ __global__ void ftgp_set_ctrl_kernel(DeviceParams P, const double* __restrict__ 
     if (mask && !mask[ci]) return;
     P.cars[ci].u_speed = ctrl[2 * ci];
     P.cars[ci].u_steer = ctrl[2 * ci + 1];
+}
+
+// ftgp_set_dynamics / ftgp_set_dynamics_device: one car per thread writes its dynamics record -- at `init` the handle's own row, then, for
+// a car of a masked env, the caller's row if it is valid (every entry finite, mass > 0, izz > 0, entries 2-7 >= 0); an invalid row leaves
+// the record as it is and counts.  The wheel loads are plan()'s expressions on the row's mass (binary64, one rounding per operation).
+__device__ __forceinline__ void dyn_record_write(double* rec, const double* row, const DynArgs& A)
+{
+    for (int k = 0; k < FTGP_DYN_DOUBLES; ++k) rec[k] = row[k];
+    const double wtot = row[kDynMass] * A.gravity;
+    for (int r = 0; r < 4; ++r) {
+        const double w = wtot * A.load_k[r];
+        rec[kDynWheelLoad + r] = A.load_half[r] ? 0.5 * w : w;
+    }
+}
+
+__global__ void ftgp_dynamics_kernel(DeviceParams P, DynArgs A)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P.n_cars) return;
+    double* rec = dyn_table(&P) + (size_t)i * FTGP_DYN_RECORD;
+    if (A.init) dyn_record_write(rec, A.base, A);
+    if (!A.rows || (A.env_mask && !A.env_mask[i / P.cars_per_env])) return;
+    double row[FTGP_DYN_DOUBLES];
+    bool ok = true;
+    for (int k = 0; k < FTGP_DYN_DOUBLES; ++k) {
+        row[k] = A.rows[(size_t)i * FTGP_DYN_DOUBLES + k];
+        ok = ok && row[k] >= 0.0 && row[k] < INFINITY;            // (false for a NaN)
+    }
+    ok = ok && row[kDynMass] > 0.0 && row[kDynIzz] > 0.0;
+    if (ok) dyn_record_write(rec, row, A);
+    else atomicAdd(dyn_rejected(&P), 1ull);
 }
 
 __global__ void ftgp_set_pose_kernel(DeviceParams P, const double* __restrict__ pose)

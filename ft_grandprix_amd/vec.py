@@ -112,6 +112,15 @@ class DeviceVecEnv:
     episode), so a shard of a larger batch draws what that slice of the whole batch would.  Any of the five implies
     ``random_start=True``.  ``episode_index()`` = how often each env has been reset since.
 
+    Dynamics randomisation (ftgp_set_dynamics_device), off by default -- every car then is the handle's vehicle:
+    ``randomize_dynamics`` = a dict from a name of capi.DYN_FIELDS (mass, izz, friction, tire_damping, throttle_kv,
+    throttle_force_limit, steer_kp, steer_damping) to ``(lo, hi)`` in absolute units; fields not named keep the handle's value.  A
+    fresh row per car is drawn uniformly (a ``torch.Generator`` on the device, seeded with ``dynamics_seed``) at construction and at
+    ``reset()`` for every env, and inside every ``step`` for the envs whose episode ended in that call: an env gets new dynamics
+    exactly when it starts a new episode, with no host synchronisation.  ``dynamics`` is the torch mirror of the rows in force, float64
+    [n_envs, cars_per_env, 8], for privileged critics (None while the table is off).  ``set_dynamics(rows, env_mask=None)`` takes rows
+    of the caller's choosing, for curricula.  Not with lidar_mode "fakelidar".
+
     The returned tensors are the env's own buffers: the next ``step`` or ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
     synchronises the host.
 
@@ -128,7 +137,7 @@ class DeviceVecEnv:
                  car_contact_penalty: float = 0.0, random_start: bool = False, start_points=(0, 100), start_margin=None,
                  start_lateral: float = 0.0, start_yaw_jitter: float = 0.0, shuffle_grid: bool = False, track_frame: bool = False,
                  lookahead: int = 0, lookahead_stride: int = 1, dense_progress: bool = False, rivals: bool = False, n_rivals: int = 0,
-                 place_reward: float = 0.0, **env_kwargs):
+                 place_reward: float = 0.0, randomize_dynamics=None, dynamics_seed: int = 0, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
@@ -174,6 +183,24 @@ class DeviceVecEnv:
             raise ValueError(f"place_reward: >= 0 and finite, got {place_reward}")
         self.n_rivals, self.place_reward = n_rivals, place_reward
         self.rivals = bool(rivals) or n_rivals > 0 or place_reward > 0.0
+        dyn_bounds = {}
+        if randomize_dynamics is not None:
+            if not isinstance(randomize_dynamics, dict):
+                raise ValueError("randomize_dynamics: a dict from a field of capi.DYN_FIELDS to (lo, hi)")
+            for name, bounds in randomize_dynamics.items():
+                if name not in capi.DYN_FIELDS:
+                    raise ValueError(f"randomize_dynamics: unknown field {name!r}, use one of {capi.DYN_FIELDS}")
+                try:
+                    lo, hi = (float(b) for b in bounds)
+                except (TypeError, ValueError):
+                    raise ValueError(f"randomize_dynamics[{name!r}]: (lo, hi), got {bounds!r}") from None
+                if not (math.isfinite(lo) and math.isfinite(hi)):
+                    raise ValueError(f"randomize_dynamics[{name!r}]: finite bounds, got {bounds!r}")
+                if lo > hi:
+                    raise ValueError(f"randomize_dynamics[{name!r}]: lo <= hi, got {bounds!r}")
+                if (lo <= 0.0) if name in ("mass", "izz") else (lo < 0.0):
+                    raise ValueError(f"randomize_dynamics[{name!r}]: lo {'> 0' if name in ('mass', 'izz') else '>= 0'}, got {bounds!r}")
+                dyn_bounds[name] = (lo, hi)
         roster = ["agent"] * cars_per_env if roster is None else list(roster)
         if len(roster) != cars_per_env:
             raise ValueError(f"one roster entry per car of an env: expected {cars_per_env}, got {len(roster)}")
@@ -263,11 +290,74 @@ class DeviceVecEnv:
             if on:
                 self._row_info[name], self._row_info["final_" + name] = out, final
             self._row_refs.append(ctypes.byref(struct(out.data_ptr(), final.data_ptr())) if on else None)
+        # dynamics randomisation: the bounds of every field as tensors (a field not named: lo = hi = the handle's value), the generator,
+        # the mirror of the rows in force and the mask of a step's draw
+        self.dynamics, self._dyn_lo = None, None
+        self._set_dynamics_device = lib.fn("set_dynamics_device")
+        if randomize_dynamics is not None:
+            base = self.env.base_dynamics()
+            lo = [dyn_bounds.get(f, (b, b))[0] for f, b in zip(capi.DYN_FIELDS, base)]
+            hi = [dyn_bounds.get(f, (b, b))[1] for f, b in zip(capi.DYN_FIELDS, base)]
+            self._dyn_lo = torch.tensor(lo, dtype=torch.float64, **z)
+            self._dyn_hi = torch.tensor(hi, dtype=torch.float64, **z)
+            self._dyn_span = self._dyn_hi - self._dyn_lo
+            self._dyn_gen = torch.Generator(device=self.device)
+            self._dyn_gen.manual_seed(int(dynamics_seed))
+            self._dyn_mask = torch.ones(n_envs, dtype=torch.bool, **z)
+            self._dyn_draw = torch.empty((n_envs, cars_per_env, capi.DYN_DOUBLES), dtype=torch.float64, **z)
+            self._draw_dynamics(None)
+
+    def _draw_dynamics(self, mask):
+        """A fresh table for every car, applied to the envs of ``mask`` (bool [n_envs] on the device, None = all) on torch's stream."""
+        with torch.cuda.device(self.device):
+            # (five torch launches a draw, into buffers the env keeps: the host side of a step is what bounds a one-step call)
+            rows = self._dyn_draw
+            rows.uniform_(0.0, 1.0, generator=self._dyn_gen)
+            torch.addcmul(self._dyn_lo, self._dyn_span, rows, out=rows)
+            torch.minimum(rows, self._dyn_hi, out=rows)
+            self._apply_dynamics(rows, mask, valid=True)
+
+    def _apply_dynamics(self, rows, mask, valid=False):
+        self._dyn_rows = rows                         # (kept until the next draw: the library reads it in stream order)
+        rc = self._set_dynamics_device(self.env.h, torch.cuda.current_stream(self.device).cuda_stream or None, rows.data_ptr(),
+                                       None if mask is None else mask.data_ptr())
+        if rc:
+            self.env.lib.check(rc)
+        if self.dynamics is None:
+            base = torch.tensor(self.env.base_dynamics(), dtype=torch.float64, device=self.device)
+            self.dynamics = base.expand(self.n_envs, self.cars_per_env, capi.DYN_DOUBLES).contiguous()
+        if valid:                                    # a draw within checked bounds: every row is taken
+            if mask is None:
+                self.dynamics.copy_(rows)
+            else:
+                torch.where(mask[:, None, None], rows, self.dynamics, out=self.dynamics)
+            return
+        # the library's rule for a row it takes: every entry finite, mass and izz > 0, the others >= 0
+        take = (torch.isfinite(rows) & (rows >= 0.0)).all(dim=2) & (rows[:, :, 0] > 0.0) & (rows[:, :, 1] > 0.0)
+        if mask is not None:
+            take = take & mask.to(torch.bool)[:, None]
+        torch.where(take[:, :, None], rows, self.dynamics, out=self.dynamics)
+
+    def set_dynamics(self, rows, env_mask=None):
+        """Rows of the caller's choosing (float64 [n_envs, cars_per_env, 8], capi.DYN_FIELDS) for the envs ``env_mask`` (bool or uint8
+        [n_envs], None = all) names, on torch's current stream; a car whose row is invalid keeps its old one."""
+        rows = torch.as_tensor(rows, dtype=torch.float64, device=self.device).contiguous()
+        if rows.shape != (self.n_envs, self.cars_per_env, capi.DYN_DOUBLES):
+            raise ValueError(f"rows: shape {(self.n_envs, self.cars_per_env, capi.DYN_DOUBLES)}, got {tuple(rows.shape)}")
+        if env_mask is not None:
+            env_mask = torch.as_tensor(env_mask, device=self.device)
+            if env_mask.shape != (self.n_envs,) or env_mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"env_mask: bool or uint8 [{self.n_envs}], got {env_mask.dtype} {tuple(env_mask.shape)}")
+            env_mask = env_mask.contiguous()
+        self._dyn_keep = env_mask
+        self._apply_dynamics(rows, env_mask)
 
     def reset(self):
         """Reset every env (synchronous ftgp_reset, which follows the start rule); obs = the scans right after a reset, all zeros
         (custom.py:1092)."""
         self.env.reset()
+        if self._dyn_lo is not None:
+            self._draw_dynamics(None)
         with torch.cuda.device(self.device):
             self.obs.zero_()
             if self.contact is not None:
@@ -304,11 +394,20 @@ class DeviceVecEnv:
             rc = self._step_device(self.env.h, self._io_ref)      # Env.step_device, without rebuilding the argument block
             if rc:
                 self.env.lib.check(rc)
+            if self._dyn_lo is not None:
+                self._redraw_ended()
             return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs}
         rc = self._step_device_rivals(self.env.h, self._io_ref, *self._row_refs)    # a null struct for an absent channel
         if rc:
             self.env.lib.check(rc)
+        if self._dyn_lo is not None:
+            self._redraw_ended()
         return self.obs, self.reward, self.terminated, self.truncated, {"final_obs": self.final_obs, **self._row_info}
+
+    def _redraw_ended(self):
+        """New dynamics for the envs whose episode ended in the step just enqueued (they start a new episode)."""
+        torch.logical_or(self.terminated, self.truncated, out=self._dyn_mask)
+        self._draw_dynamics(self._dyn_mask)
 
     def close(self):
         if getattr(self, "env", None) is not None:

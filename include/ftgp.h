@@ -613,6 +613,37 @@ int ftgp_get_episodes(FtgpEnv *env, int64_t *out);
  * with or without a rule.  FTGP_ERR_ARG for a track out of range. */
 int ftgp_get_start_table(FtgpEnv *env, int track, double *out);
 
+/* ---- Per-car vehicle dynamics (domain randomisation; no reference counterpart) -------------------------------------------------------
+ * A handle may carry one dynamics row per car, FTGP_DYN_DOUBLES binary64 values, row of car (env * cars_per_env + car):
+ *   0 mass  1 izz  2 friction  3 tire_damping  4 throttle_kv  5 throttle_force_limit  6 steer_kp  7 steer_damping
+ * With the table on, car a integrates as a handle would whose FtgpConfig.vehicle is this handle's with these eight fields replaced
+ * by row a.  Everything else stays the handle's: geometry, contact stiffness and damping, wheel and steering inertias, limits, kind,
+ * the LiDAR.  The static wheel loads of car a follow from its mass by the rule of ftgp_create, in binary64, one rounding per
+ * operation: wtot = mass * gravity; with a_f, a_r the distances of the front and rear axle from the origin,
+ *   FTGP_VEHICLE_MUSHR     load fl = fr = 0.5 * (wtot * (a_r / (a_f + a_r))), bl = br = 0.5 * (wtot * (a_f / (a_f + a_r)))
+ *   FTGP_VEHICLE_TRICYCLE  load l = r = 0.5 * (wtot * (a_f / (a_f + a_r))), caster = wtot * (a_r / (a_f + a_r))
+ * so a row equal to the handle's own eight values reproduces the handle without a table to the bit.  FTGP_VEHICLE_TRICYCLE reads
+ * entries 0-3 only; entries 4-7 are stored and ignored.
+ *
+ * The table is off on a new handle.  The first accepted setter call turns it on: every car's row starts as the handle's own values,
+ * then the given rows of the masked envs replace theirs.  rows: [n_envs][cars_per_env][FTGP_DYN_DOUBLES]; env_mask: uint8[n_envs],
+ * non-zero = take this env's rows, NULL = all envs (the mask of ftgp_reset).  ftgp_set_dynamics(env, NULL, NULL) turns the table off
+ * and zeroes the rejected counter.  ftgp_reset, the auto-reset of a device step, ftgp_device_io_config, the ftgp_device_io_* setters
+ * and ftgp_set_spawn_rule leave the table alone.  Valid on multi-track handles and on shards (rows are indexed by the handle's own
+ * envs); FTGP_ERR_STATE on a FTGP_LIDAR_FAKELIDAR handle.
+ *
+ * A valid row has every entry finite, mass > 0, izz > 0 and entries 2-7 >= 0.  ftgp_set_dynamics (host buffers, synchronous) returns
+ * FTGP_ERR_ARG before anything changes; the message names the first bad car and entry.  ftgp_set_dynamics_device (device buffers on
+ * the handle's device) only enqueues (a handle's first setter call allocates the table and may synchronise), ordered on `stream` like ftgp_state_device: the handle's stream waits for `stream`, and
+ * `stream` for the work.  FTGP_ERR_ARG for a buffer that is not device memory, before anything is enqueued.  It cannot look at the
+ * values without a synchronisation: a car whose new row is invalid keeps its old row, and a device counter goes up by one.
+ * ftgp_get_dynamics (host, synchronous): the rows in force, double[n_cars][FTGP_DYN_DOUBLES], and the number of rows rejected since
+ * the table was turned on (either pointer may be NULL); with the table off, the handle's values for every car and 0. */
+#define FTGP_DYN_DOUBLES 8
+int ftgp_set_dynamics(FtgpEnv *env, const double *rows, const uint8_t *env_mask);
+int ftgp_set_dynamics_device(FtgpEnv *env, void *stream, const double *rows, const uint8_t *env_mask);
+int ftgp_get_dynamics(FtgpEnv *env, double *rows_out, int64_t *rejected_out);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).

@@ -64,11 +64,12 @@ def publish(dst, files):
     return 1 if bad else 0
 
 
-def code_object_meta(lib=None, tracks=False):
+def code_object_meta(lib=None, tracks=False, dynamics=False):
     """.vgpr_count / .sgpr_count / spills / scratch of every ftgp_step_kernel instantiation, from the gfx950 code object inside the
     library (rocprofv3's VGPR_Count / LDS_Block_Size columns read 32 / 0 for a 63-register kernel with 73 KB of dynamic LDS).
     tracks=False: the six one-track instantiations <MULTI, FAKE, ROSTER[, false]>, keyed by their three flags; tracks=True: the six of
-    multi-track handles, keyed "ftgp_step_kernel<MULTI, FAKE, ROSTER, true>"."""
+    multi-track handles, keyed "ftgp_step_kernel<MULTI, FAKE, ROSTER, true>".  dynamics=True: the eight instantiations of launches with
+    the per-car dynamics table on (ftgp_set_dynamics) instead, both kinds of handle, keyed by all five flags."""
     lib = lib or os.path.join(ROOT, "ft_grandprix_amd", "lib", "libftgp.so")
     out = {}
     with tempfile.TemporaryDirectory() as td:
@@ -81,10 +82,13 @@ def code_object_meta(lib=None, tracks=False):
         name = re.search(r"\.name:\s+(\S+)", block)
         if not name or "ftgp_step_kernel" not in name.group(1):
             continue
-        flags = re.search(r"ftgp_step_kernelILb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?", name.group(1))
-        if flags and (flags.group(4) == "1") != tracks:
+        flags = re.search(r"ftgp_step_kernelILb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?(?:Lb(\d)E)?", name.group(1))
+        if flags and (flags.group(5) == "1") != dynamics:
             continue
-        key = ("ftgp_step_kernel<%s, %s, %s" % tuple("true" if f == "1" else "false" for f in flags.groups()[:3]) + (", true>" if tracks else ">")
+        if flags and not dynamics and (flags.group(4) == "1") != tracks:
+            continue
+        key = ("ftgp_step_kernel<%s>" % ", ".join("true" if f == "1" else "false" for f in flags.groups()) if flags and dynamics else
+               "ftgp_step_kernel<%s, %s, %s" % tuple("true" if f == "1" else "false" for f in flags.groups()[:3]) + (", true>" if tracks else ">")
                if flags else name.group(1))
         get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
         out[key] = {"vgpr_count": get("vgpr_count"), "sgpr_count": get("sgpr_count"), "sgpr_spill_count": get("sgpr_spill_count"),

@@ -1,7 +1,7 @@
 """Env-steps/s of the device I/O loop (DeviceVecEnv.step on torch tensors) against the host loop (set_ctrl + step + get_lidar).
 
     python tools/vec_throughput.py [--envs 4096] [--rays 1080] [--calls 200] [--warmup 20] [--track track] [--rows device,torch_pool,signals,contacts,frame,rivals,host] [--repeats 1,4] [--cars 1]
-                                   [--max-episode-steps 3000] [--random-start]
+                                   [--max-episode-steps 3000] [--random-start] [--dynamics]
 
 Device loop: constant actions, and random torch actions drawn before every call, at action_repeat 1 and 4; per-call time from HIP
 events on torch's stream around the timed calls.  Pooled observations (action_repeat 1, constant actions, beams of --pool rays clipped
@@ -13,6 +13,8 @@ after the steps, rows and reward by ftgp_io_finish_signals_kernel), "rivals" = t
 n_rivals=3: ftgp_io_rival_kernel behind the frame kernel; meaningful with --cars 4, and its difference to the frame row is what the
 channel costs).  --cars: cars per env, every one an agent.  --random-start: the device rows run under a spawn rule (ftgp_set_spawn_rule:
 lateral share 0.8, yaw offsets up to 0.2 rad, shuffled grid); with a small --max-episode-steps the auto-reset, and with it the draw, runs often.
+--dynamics: the device rows run with the per-car dynamics table on (randomize_dynamics: friction 0.3 .. 0.9, mass 4 .. 8 kg; the step
+kernel's DYN form, and a fresh draw for the envs that ended after every call); the row without the switch is what it is compared with.
 Host loop: per
 step set_ctrl (one copy + synchronisation), step(1), get_lidar (the whole scan back).  One JSON line per row, then a summary line.  Run it in a fresh process: torch is imported first
 (ft_grandprix_amd/vec.py).  Under `rocprofv3 --kernel-trace --stats -- python tools/vec_throughput.py` the per-kernel times of a call
@@ -48,6 +50,8 @@ def device_row(track, a, repeat, actions, pooled=None):
         kw.update(rivals=True, n_rivals=3)
     if a.random_start:
         kw.update(random_start=True, start_lateral=0.8, start_yaw_jitter=0.2, shuffle_grid=True)
+    if a.dynamics:
+        kw.update(randomize_dynamics={"friction": (0.3, 0.9), "mass": (4.0, 8.0)}, dynamics_seed=3)
     venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, cars_per_env=a.cars, max_episode_steps=a.max_episode_steps, action_repeat=repeat, spawn_mode=1,
                         seed=7, **kw)
     dev = venv.device
@@ -83,6 +87,7 @@ def device_row(track, a, repeat, actions, pooled=None):
     wall = time.perf_counter() - w0
     ms = t0.elapsed_time(t1)
     step_ms = venv.env.last_kernel_ms()
+    kernel = venv.env.kernel_name()
     episodes = int(venv.episode_index().sum()) if a.random_start else None
     venv.close()
     loop = {None: "device", "torch": "device+torch_pool", "signals": "device+signals", "contacts": "device+signals+contacts", "frame": "device+frame",
@@ -91,6 +96,8 @@ def device_row(track, a, repeat, actions, pooled=None):
     extra["max_episode_steps"] = a.max_episode_steps
     if a.random_start:
         extra.update(random_start=True, resets=episodes)
+    if a.dynamics:
+        extra.update(dynamics=True, step_kernel=kernel)
     return {"loop": loop, "actions": actions, "action_repeat": repeat, "envs": a.envs, "cars": a.cars, "rays": a.rays, "calls": a.calls, **extra,
             "us_per_call": 1e3 * ms / a.calls, "host_us_per_call": 1e6 * wall / a.calls, "step_kernel_us_last_call": 1e3 * step_ms,
             "env_steps_per_s": a.envs * repeat * a.calls / (ms * 1e-3)}
@@ -126,6 +133,7 @@ def main():
     ap.add_argument("--cars", type=int, default=1, help="cars per env, every one an agent")
     ap.add_argument("--max-episode-steps", type=int, default=3000, help="truncation of the device rows")
     ap.add_argument("--random-start", action="store_true", help="the device rows run under a spawn rule")
+    ap.add_argument("--dynamics", action="store_true", help="the device rows run with the per-car dynamics table on (randomize_dynamics)")
     ap.add_argument("--rows", default="device,torch_pool,signals,host", help="comma-separated: device, torch_pool, signals, contacts, frame, rivals, host")
     a = ap.parse_args()
     want = set(a.rows.split(","))
