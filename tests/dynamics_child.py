@@ -21,8 +21,7 @@ from ft_grandprix_amd import capi  # noqa: E402
 from ft_grandprix_amd.track import load_track  # noqa: E402
 from tests import helpers  # noqa: E402
 
-LO = np.array([0.7, 0.7, 0.6, 0.7, 0.6, 0.4, 0.6, 0.7])
-HI = np.array([1.4, 1.4, 1.8, 1.4, 1.4, 1.0, 1.5, 1.5])
+LO, HI = helpers.DYN_LO, helpers.DYN_HI             # (tests/test_free_step.py draws its rows between the same)
 LOOP = dict(n_rays=64, spawn_mode=1, seed=5)          # the closed loop of scenario 1
 ERR_ARG, ERR_STATE = -1, -4
 

@@ -12,6 +12,9 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.path.join(ORACLE_DIR, "libftgp_oracle.so")
 TOL = 1e-4   # north_star tolerance for floating-point outputs
+# factors on a vehicle's eight dynamics fields (capi.DYN_FIELDS) between which the tests draw per-car rows
+DYN_LO = np.array([0.7, 0.7, 0.6, 0.7, 0.6, 0.4, 0.6, 0.7])
+DYN_HI = np.array([1.4, 1.4, 1.8, 1.4, 1.4, 1.0, 1.5, 1.5])
 
 
 def load_oracle():
