@@ -31,6 +31,9 @@ RIVAL_FLOATS = 8             # FTGP_RIVAL_FLOATS: a mate slot (RIVAL_MATE_FIELDS
 MAX_RIVALS = 7               # FTGP_MAX_RIVALS
 MAX_TRACKS = 16             # FTGP_MAX_TRACKS: tracks of one multi-track handle (ftgp_create_tracks)
 DYN_DOUBLES = 8             # FTGP_DYN_DOUBLES: a dynamics row of a car (DYN_FIELDS; ftgp_set_dynamics)
+DYN_RECORD = 12             # FTGP_DYN_RECORD: a dynamics record of an env-state record: the row, then the four static wheel loads
+ENV_STATE_VERSION = 1       # FTGP_ENV_STATE_VERSION
+ENV_STATE_MAGIC = 0x53454746    # FTGP_ENV_STATE_MAGIC
 
 POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2, 3, 4
 LIDAR_RANGEFINDER, LIDAR_FAKELIDAR = 0, 1
@@ -98,6 +101,7 @@ API_SYMBOLS = (
     "device_io_frame", "step_device_frame", "frame_device", "get_frames",
     "device_io_rivals", "step_device_rivals", "rivals_device", "get_rivals",
     "set_dynamics", "set_dynamics_device", "get_dynamics",
+    "env_state_bytes", "save_envs_device", "load_envs_device", "get_env_state_rejected", "obs_device",
 )
 
 
@@ -241,6 +245,11 @@ class CLib:
             "set_dynamics": (i32, [vp, dp, dp]),
             "set_dynamics_device": (i32, [vp, vp, vp, vp]),
             "get_dynamics": (i32, [vp, dp, C.POINTER(C.c_int64)]),
+            "env_state_bytes": (i32, [vp, C.POINTER(C.c_size_t)]),
+            "save_envs_device": (i32, [vp, vp, vp, C.c_int64, vp]),
+            "load_envs_device": (i32, [vp, vp, vp, C.c_int64, vp]),
+            "get_env_state_rejected": (i32, [vp, C.POINTER(C.c_int64)]),
+            "obs_device": (i32, [vp, vp, vp]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -536,6 +545,35 @@ class Env:
         self._call("get_dynamics", _ptr(out), C.byref(rejected))
         return out, int(rejected.value)
 
+    # -- env states on the device (include/ftgp.h: ftgp_save_envs_device)
+    def env_state_bytes(self) -> int:
+        """Bytes of one env-state record of this handle (= ``env_state_layout(n_rays, cars_per_env)["bytes"]``)."""
+        n = C.c_size_t(0)
+        self._call("env_state_bytes", C.byref(n))
+        return int(n.value)
+
+    def save_envs_device(self, rows_ptr: int, n_rows: int, env_mask_ptr: int = 0, stream: int = 0):
+        """ftgp_save_envs_device on integer device addresses: env e of the mask (uint8 [n_envs], 0 = all envs) writes row e of the
+        ``n_rows`` >= n_envs records at ``rows_ptr``; ordered on ``stream``, only enqueues."""
+        self._call("save_envs_device", stream or None, rows_ptr or None, int(n_rows), env_mask_ptr or None)
+
+    def load_envs_device(self, rows_ptr: int, n_rows: int, src_row_ptr: int = 0, stream: int = 0):
+        """ftgp_load_envs_device on integer device addresses: env e takes row src_row[e] (int32 [n_envs], 0 = row e; a negative entry
+        keeps the env) of the ``n_rows`` records at ``rows_ptr``; ordered on ``stream``, only enqueues.  A row that does not fit the env
+        leaves it untouched (``env_state_rejected()`` counts them)."""
+        self._call("load_envs_device", stream or None, rows_ptr or None, int(n_rows), src_row_ptr or None)
+
+    def env_state_rejected(self) -> int:
+        """Rows ftgp_load_envs_device has refused over the handle's life (synchronous)."""
+        n = C.c_int64(0)
+        self._call("get_env_state_rejected", C.byref(n))
+        return int(n.value)
+
+    def obs_device(self, obs: int, stream: int = 0):
+        """ftgp_obs_device: the agents' observation rows at the state as it stands into device memory at ``obs`` (float32 [n_envs,
+        n_ext, n_beams]), ordered on ``stream``; only enqueues."""
+        self._call("obs_device", stream or None, obs or None)
+
     @staticmethod
     def _step_args(stream, action, obs, reward, terminated, truncated, final_obs, *rows):
         """The arguments of a device step by reference: the FtgpDeviceStep block, then for every (struct type, address, final address)
@@ -746,6 +784,76 @@ class Env:
     def kernel_name(self) -> str:
         s = self.lib.fn("kernel_name")(self.h)
         return s.decode() if s else ""
+
+
+# the car record of an env-state record (include/ftgp.h), 448 bytes
+CAR_STATE_DTYPE = np.dtype(
+    [(n, "<f8") for n in ("x", "y", "qw", "qz", "vx", "vy", "wz", "qs", "qsd")] + [("w", "<f8", (4,))]
+    + [(n, "<f8") for n in ("u_speed", "u_steer", "last_steer", "dist2")]
+    + [(n, "<i4") for n in ("completion", "laps", "offset", "n_times", "good_start", "finished", "off_track", "delta")]
+    + [("start", "<i8"), ("finish_step", "<i8"), ("_pad", "V8"), ("times", "<f8", (MAX_LAP_TIMES,))])
+CAR_STATE_FIELDS = tuple(n for n in CAR_STATE_DTYPE.names if n != "_pad")
+ENV_STATE_HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("n_rays", "<i4"), ("cars_per_env", "<i4"), ("lidar_mode", "<i4"),
+                                   ("reserved", "<i4"), ("fingerprint", "<u8"), ("steps", "<i8"), ("episodes", "<i8")])
+assert CAR_STATE_DTYPE.itemsize == 448 and ENV_STATE_HEADER_DTYPE.itemsize == 48
+
+
+def env_state_layout(n_rays: int, cars_per_env: int) -> dict:
+    """Byte offsets and sizes of one env-state record (include/ftgp.h: ftgp_save_envs_device): "header", "steps", "episodes", "cars",
+    "dyn", "ranges" = where each part starts; "car_bytes", "dyn_bytes", "row_bytes" = the stride of a car inside the three per-car
+    parts; "bytes" = bytes_per_env.  Every part starts on a 16-byte boundary and the size is a multiple of 16."""
+    n_rays, c = int(n_rays), int(cars_per_env)
+    if n_rays < 1 or not 1 <= c <= 8:
+        raise ValueError(f"n_rays >= 1 and 1 <= cars_per_env <= 8, got {n_rays}, {c}")
+    car_bytes, dyn_bytes, row_bytes = CAR_STATE_DTYPE.itemsize, 8 * DYN_RECORD, (4 * n_rays + 15) & ~15
+    cars = ENV_STATE_HEADER_DTYPE.itemsize
+    dyn = cars + c * car_bytes
+    ranges = dyn + c * dyn_bytes
+    return {"header": 0, "steps": 32, "episodes": 40, "cars": cars, "dyn": dyn, "ranges": ranges, "car_bytes": car_bytes,
+            "dyn_bytes": dyn_bytes, "row_bytes": row_bytes, "bytes": ranges + c * row_bytes}
+
+
+def unpack_env_state(buf, n_rays: int, cars_per_env: int) -> dict:
+    """Decode env-state records: ``buf`` = uint8, one record or [n] records of ``env_state_layout(...)["bytes"]`` bytes.  Returns a dict
+    of arrays with a leading axis of n: the header fields (ENV_STATE_HEADER_DTYPE: magic ... fingerprint, steps, episodes) [n]; the car
+    fields by name (CAR_STATE_FIELDS) [n, cars_per_env, ...]; "dyn" float64 [n, cars_per_env, DYN_RECORD]; "ranges" float32
+    [n, cars_per_env, n_rays]."""
+    lay = env_state_layout(n_rays, cars_per_env)
+    b = np.ascontiguousarray(buf, dtype=np.uint8)
+    if b.size % lay["bytes"] or (b.ndim > 1 and b.shape[-1] != lay["bytes"]):
+        raise ValueError(f"records of {lay['bytes']} bytes, got shape {b.shape}")
+    b = b.reshape(-1, lay["bytes"])
+    n, c = b.shape[0], int(cars_per_env)
+    head = np.ascontiguousarray(b[:, :lay["cars"]]).view(ENV_STATE_HEADER_DTYPE).reshape(n)
+    out = {name: head[name].copy() for name in ENV_STATE_HEADER_DTYPE.names}
+    cars = np.ascontiguousarray(b[:, lay["cars"]:lay["dyn"]]).view(CAR_STATE_DTYPE).reshape(n, c)
+    out.update({name: cars[name].copy() for name in CAR_STATE_FIELDS})
+    out["dyn"] = np.ascontiguousarray(b[:, lay["dyn"]:lay["ranges"]]).view("<f8").reshape(n, c, DYN_RECORD)
+    rows = np.ascontiguousarray(b[:, lay["ranges"]:]).view("<f4").reshape(n, c, lay["row_bytes"] // 4)
+    out["ranges"] = rows[:, :, :int(n_rays)].copy()
+    return out
+
+
+def track_fingerprint(track) -> int:
+    """The track fingerprint of an env-state record (include/ftgp.h): the splitmix64 fold over width, height, the bitmap words (bits
+    beyond the width cleared) and the bit patterns of the 200 path doubles."""
+    m = (1 << 64) - 1
+
+    def splitmix64(z):
+        z = (z + 0x9E3779B97F4A7C15) & m
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        return z ^ (z >> 31)
+
+    bits = np.ascontiguousarray(track.bits, dtype=np.uint32).copy()
+    if track.width % 32:
+        bits[:, track.width // 32] &= np.uint32((1 << (track.width % 32)) - 1)
+    bits[:, (track.width + 31) // 32:] = 0
+    path = np.ascontiguousarray(track.path, dtype=np.float64).reshape(-1).view(np.uint64)
+    h = 0
+    for v in [track.width, track.height] + bits.reshape(-1).tolist() + path.tolist():
+        h = splitmix64(h ^ int(v))
+    return h
 
 
 def lap_time_list(count: int, ring: np.ndarray) -> list:

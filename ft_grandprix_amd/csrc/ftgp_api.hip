@@ -193,6 +193,9 @@ struct FtgpEnv {
     bool dyn_on = false;              // step launches run the DYN instantiations
     DynArgs dyn{};                    // the handle's own row and the wheel-load rule (the buffers are filled in per call)
     DevBuf<double> d_dyn_rows;        // [n_cars][FTGP_DYN_DOUBLES] landing buffer of the host setter, allocated on first use
+    // env states (ftgp_save_envs_device / ftgp_load_envs_device)
+    std::vector<uint64_t> track_fp;   // [n_tracks] the tracks' fingerprints (include/ftgp.h), folded at create
+    DevBuf<EnvStateAux> d_state_aux;  // the handle's own dynamics record, the rejected counter, the fingerprints; allocated by the first save or load
     // comm
     void* comm = nullptr; int rank = 0, world = 1;
 };
@@ -1105,6 +1108,50 @@ int launch_dynamics(FtgpEnv* e, const double* rows, const uint8_t* env_mask)
     return 0;
 }
 
+// the track fingerprint of an env-state record (include/ftgp.h): a splitmix64 fold over the size, the wall bitmap and the centre-line
+uint64_t track_fingerprint(int width, int height, const std::vector<uint32_t>& bits, const std::vector<double>& path)
+{
+    uint64_t h = 0;
+    auto fold = [&h](uint64_t v) { h = splitmix64(h ^ v); };
+    fold((uint64_t)width); fold((uint64_t)height);
+    for (const uint32_t w : bits) fold((uint64_t)w);
+    for (int i = 0; i < 2 * FTGP_PATH_POINTS; ++i) { uint64_t b; memcpy(&b, &path[(size_t)i], sizeof b); fold(b); }
+    return h;
+}
+
+// bytes of one env-state record, and its scan rows in uint4
+size_t env_state_row_vec(const DeviceParams& P) { return ((size_t)P.n_rays * sizeof(float) + 15) / 16; }
+size_t env_state_bytes(const DeviceParams& P)
+{
+    return 16 * (FTGP_ENV_STATE_HEAD + (size_t)P.cars_per_env * ((size_t)FTGP_CAR_VEC + FTGP_DYN_VEC + env_state_row_vec(P)));
+}
+
+// A handle's first save or load: the handle's own dynamics record, a zeroed counter and the fingerprints go to device memory.
+int ensure_env_state(FtgpEnv* e)
+{
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (e->d_state_aux) return 0;
+    EnvStateAux a{};
+    memcpy(a.own, e->dyn.base, sizeof e->dyn.base);
+    for (int r = 0; r < 4; ++r) a.own[kDynWheelLoad + r] = e->P.wheel_load[r];
+    for (size_t k = 0; k < e->track_fp.size() && k < FTGP_MAX_TRACKS; ++k) a.track_fp[k] = e->track_fp[k];
+    HIP_TRY(dev_upload(e->d_state_aux, &a, sizeof a));
+    return 0;
+}
+
+// the arguments both env-state kernels take, and their launch shape: a wave per env
+EnvStateArgs env_state_args(FtgpEnv* e, void* rows, int64_t n_rows)
+{
+    EnvStateArgs A{};
+    A.rows = static_cast<uint4*>(rows); A.n_rows = n_rows;
+    A.env_track = e->d_env_track.get(); A.aux = e->d_state_aux.get(); A.episodes = e->d_episodes.get();
+    A.dyn = e->dyn_on ? reinterpret_cast<uint4*>(dyn_table(&e->P)) : nullptr;
+    A.row_vec = (int32_t)env_state_row_vec(e->P); A.env_vec = (int32_t)(env_state_bytes(e->P) / 16);
+    return A;
+}
+unsigned env_state_blocks(const FtgpEnv* e) { const int per = FTGP_ENV_STATE_THREADS / FTGP_WAVE; return (unsigned)((e->P.n_envs + per - 1) / per); }
+
 bool nonneg_finite(double v) { return v >= 0.0 && !std::isinf(v); }      // a penalty, a range, a margin; a NaN fails as well
 
 // ftgp_create, step 3: the upload -- allocate, copy, search the box fields (or the distance transforms), write the images
@@ -1170,6 +1217,8 @@ int upload(FtgpEnv* e, const Plan& pl, const Switches& sw)
                 memcpy(row + 4, &pl.tracks[(size_t)k].clear[2 * (size_t)p], sizeof(double) * 2);
             }
     }
+    e->track_fp.clear();
+    for (int k = 0; k < T; ++k) e->track_fp.push_back(track_fingerprint(pl.tracks[(size_t)k].P.width, pl.tracks[(size_t)k].P.height, pl.tracks[(size_t)k].tab.bits, pl.tracks[(size_t)k].path));
     HIP_TRY(dev_upload(e->d_veh, pl.veh.data(), pl.veh.size()));
     HIP_TRY(dev_upload(e->d_ray, pl.ray.data(), sizeof(float) * pl.ray.size()));
     HIP_TRY(dev_upload(e->d_cover, pl.cover.data(), sizeof(float) * pl.cover.size()));
@@ -1761,6 +1810,84 @@ int ftgp_get_dynamics(FtgpEnv* e, double* rows_out, int64_t* rejected_out)
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     if (rejected_out) *rejected_out = (int64_t)rejected;
     return 0;
+}
+
+int ftgp_env_state_bytes(FtgpEnv* e, size_t* bytes_per_env)
+{
+    if (!e || !bytes_per_env) return fail(FTGP_ERR_ARG, "null argument%s");
+    *bytes_per_env = env_state_bytes(e->P);
+    return 0;
+}
+
+// the checks ftgp_save_envs_device and ftgp_load_envs_device (`entry`) share; `need_all`: row e of every env must exist
+static int env_state_checks(FtgpEnv* e, const char* entry, const void* rows, int64_t n_rows, bool need_all, const void* per_env, size_t per_env_bytes, const char* per_env_name)
+{
+    // (check_device_buffer words its refusals for the device step: put this entry's name in front)
+    auto refused = [entry](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "%s: %s", entry, m.c_str()); return rc; };
+    if (n_rows < 1 || n_rows > 0x7fffffffll) return failf(FTGP_ERR_ARG, "%s: n_rows = %lld, not in 1 .. 2^31 - 1", entry, (long long)n_rows);
+    if (need_all && n_rows < e->P.n_envs) return failf(FTGP_ERR_ARG, "%s: n_rows = %lld, fewer than the handle's %d envs", entry, (long long)n_rows, e->P.n_envs);
+    if (int rc = check_device_buffer(e, rows, env_state_bytes(e->P) * (size_t)n_rows, "rows")) return refused(rc);
+    if ((uintptr_t)rows % 16 != 0) return failf(FTGP_ERR_ARG, "%s: rows is not 16-byte aligned", entry);
+    if (per_env) if (int rc = check_device_buffer(e, per_env, per_env_bytes, per_env_name)) return refused(rc);
+    return 0;
+}
+
+int ftgp_save_envs_device(FtgpEnv* e, void* stream, void* rows, int64_t n_rows, const uint8_t* env_mask)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = env_state_checks(e, "ftgp_save_envs_device", rows, n_rows, true, env_mask, (size_t)e->P.n_envs, "env_mask")) return rc;
+    if (int rc = ensure_env_state(e)) return rc;
+    EnvStateArgs A = env_state_args(e, rows, n_rows);
+    A.env_mask = env_mask;
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    hipLaunchKernelGGL(ftgp_env_save_kernel, dim3(env_state_blocks(e)), dim3(FTGP_ENV_STATE_THREADS), 0, e->stream.get(), e->P, A);
+    HIP_TRY(hipGetLastError());
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+int ftgp_load_envs_device(FtgpEnv* e, void* stream, const void* rows, int64_t n_rows, const int32_t* src_row)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = env_state_checks(e, "ftgp_load_envs_device", rows, n_rows, !src_row, src_row, sizeof(int32_t) * (size_t)e->P.n_envs, "src_row")) return rc;
+    if (int rc = ensure_env_state(e)) return rc;
+    EnvStateArgs A = env_state_args(e, const_cast<void*>(rows), n_rows);
+    A.src_row = src_row;
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    hipLaunchKernelGGL(ftgp_env_load_kernel, dim3(env_state_blocks(e)), dim3(FTGP_ENV_STATE_THREADS), 0, e->stream.get(), e->P, A);
+    HIP_TRY(hipGetLastError());
+    e->rows_valid = false; e->launch_metrics_valid = false;
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+int ftgp_get_env_state_rejected(FtgpEnv* e, int64_t* rejected)
+{
+    if (!e || !rejected) return fail(FTGP_ERR_ARG, "null argument%s");
+    *rejected = 0;
+    if (!e->d_state_aux) return 0;          // no load yet
+    HIP_TRY(hipSetDevice(e->device));
+    unsigned long long n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, &e->d_state_aux.get()->rejected, sizeof n, hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    *rejected = (int64_t)n;
+    return 0;
+}
+
+int ftgp_obs_device(FtgpEnv* e, void* stream, float* obs)
+{
+    const size_t n_beams = e && e->ds.ready ? (size_t)e->ds.sig.n_beams : 1;
+    return rows_to_device(e, "ftgp_obs_device", stream, n_beams, obs, "obs", [&] {
+        DeviceIoArgs A = e->ds.io;
+        DeviceSignalArgs S = e->ds.sig;
+        A.obs = obs;
+        const bool aligned = (uintptr_t)obs % 16 == 0;          // as a device step chooses (ftgp_step_device_rivals)
+        S.vec_out = aligned && S.n_beams % 4 == 0;
+        if (S.path == FTGP_SIG_PATH_REGS && !aligned) S.path = FTGP_SIG_PATH_STAGE;
+        hipLaunchKernelGGL(ftgp_io_obs_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, S);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 int ftgp_get_episodes(FtgpEnv* e, int64_t* out)

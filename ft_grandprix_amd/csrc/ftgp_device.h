@@ -148,7 +148,7 @@ struct VehLds {
 // rows.  The parameter blocks carry the address in two spare words (dyn_table_lo / _hi), so their layout, the staging image and the LDS
 // offsets are what they were.  A step launch with the table on stages its workgroup's records into LDS behind the layout of
 // lds_layout(), at lds_bytes (ftgp_step_kernel<..., DYN = true>).
-#define FTGP_DYN_RECORD 12
+// (FTGP_DYN_RECORD = 12: include/ftgp.h, where the env-state record documents it)
 enum { kDynMass = 0, kDynIzz, kDynFriction, kDynTireDamping, kDynThrottleKv, kDynThrottleForceLimit, kDynSteerKp, kDynSteerDamping, kDynWheelLoad };
 template <class PP> __host__ __device__ inline double* dyn_table(PP p) { return reinterpret_cast<double*>(((uint64_t)p->dyn_table_hi << 32) | (uint64_t)p->dyn_table_lo); }
 template <class PP> __host__ __device__ inline unsigned long long* dyn_rejected(PP p) { return reinterpret_cast<unsigned long long*>(dyn_table(p) + (size_t)p->n_cars * FTGP_DYN_RECORD); }

@@ -2812,6 +2812,149 @@ __global__ void __launch_bounds__(FTGP_IO_THREADS) __attribute__((amdgpu_num_vgp
     }
 }
 
+// ftgp_obs_device: the external cars' observation rows at the scans as they stand, one workgroup per env -- pooled_row as the finish
+// kernel above calls it, so a row is what a step's obs holds for those scans.  (ftgp_io_finish_kernel copies the scans as they are;
+// pool 1 without a clip gives the same bits for every range a sweep writes: a hit >= 0, or -1.)
+__global__ void __launch_bounds__(FTGP_IO_THREADS) ftgp_io_obs_kernel(DeviceParams P, DeviceIoArgs A, DeviceSignalArgs S)
+{
+    __shared__ __attribute__((aligned(16))) float stage[FTGP_SIG_STAGE_FLOATS];
+    const int env = blockIdx.x, cpe = P.cars_per_env, ci0 = env * cpe;
+    for (int c = 0; c < cpe; ++c) {
+        const int k = A.ext_index[c];
+        if (k < 0) continue;      // (uniform over the workgroup)
+        pooled_row(P.ranges + (size_t)(ci0 + c) * P.ranges_stride, A.obs + ((size_t)env * A.n_ext + k) * S.n_beams, P.n_rays, S, stage);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Env states (ftgp_save_envs_device / ftgp_load_envs_device): the record of include/ftgp.h -- header, steps and episodes, the car
+// records, the dynamics records, the scans -- gathered from / scattered to the handle's five state arrays.  A wave per env, the env
+// index wave-uniform; every part starts on a 16-byte boundary on both sides, so a part moves as uint4, lane i taking vector i, i + 64,
+// ...: a wave's loads and stores cover consecutive 1 KiB.  No LDS, no scratch, nothing indexed by a lane but global memory.
+// ---------------------------------------------------------------------------------------------
+#define FTGP_ENV_STATE_THREADS 256
+#define FTGP_ENV_STATE_HEAD 3                             // uint4: magic version n_rays cars | lidar_mode 0 fingerprint | steps episodes
+#define FTGP_CAR_VEC ((int)(sizeof(CarState) / 16))
+#define FTGP_DYN_VEC ((int)(FTGP_DYN_RECORD * sizeof(double) / 16))
+static_assert(sizeof(CarState) % 16 == 0 && (FTGP_DYN_RECORD * sizeof(double)) % 16 == 0, "the parts of an env-state record move as uint4");
+static_assert(sizeof(CarState) == 448 && offsetof(CarCore, completion) == 136 && offsetof(CarCore, start) == 168 && sizeof(CarCore) == 192,
+              "the car record of an env-state record is part of the interface (include/ftgp.h)");
+
+// what a handle's first save or load puts into device memory
+struct EnvStateAux {
+    double own[FTGP_DYN_RECORD];              // the handle's own dynamics record: what a save writes while the table is off
+    unsigned long long rejected, pad;         // rows a load has refused
+    uint64_t track_fp[FTGP_MAX_TRACKS];       // the tracks' fingerprints
+};
+static_assert(offsetof(EnvStateAux, own) == 0 && offsetof(EnvStateAux, rejected) % 16 == 0, "EnvStateAux layout");
+
+struct EnvStateArgs {
+    uint4* rows;                  // [n_rows][env_vec] the caller's records (a load only reads them)
+    int64_t n_rows;
+    const uint8_t* env_mask;      // save: [n_envs] or null = all envs
+    const int32_t* src_row;       // load: [n_envs] or null = row e
+    const int32_t* env_track;     // the track of every env; null with one track
+    EnvStateAux* aux;
+    int64_t* episodes;            // [n_envs]; null on a handle that never had a spawn rule
+    uint4* dyn;                   // the dynamics records; null while the table is off
+    int32_t row_vec;              // uint4 per scan row of a record: pad16(4 n_rays) / 16
+    int32_t env_vec;              // uint4 per record
+};
+
+__device__ __forceinline__ int env_state_env() { return sgpr((int)(blockIdx.x * (FTGP_ENV_STATE_THREADS / FTGP_WAVE) + threadIdx.x / FTGP_WAVE)); }
+
+__global__ void __launch_bounds__(FTGP_ENV_STATE_THREADS) ftgp_env_save_kernel(DeviceParams P, EnvStateArgs A)
+{
+    const int env = env_state_env();
+    if (env >= P.n_envs) return;
+    if (A.env_mask && !A.env_mask[env]) return;
+    const int lane = lane_id(), cpe = P.cars_per_env;
+    uint4* o = A.rows + (size_t)env * (size_t)A.env_vec;
+    if (lane < FTGP_ENV_STATE_HEAD) {
+        const uint64_t fp = A.aux->track_fp[env_track_of(A.env_track, env)];
+        const uint64_t steps = (uint64_t)P.steps[env], episodes = A.episodes ? (uint64_t)A.episodes[env] : 0ull;
+        uint4 v = make_uint4(FTGP_ENV_STATE_MAGIC, FTGP_ENV_STATE_VERSION, (uint32_t)P.n_rays, (uint32_t)cpe);
+        if (lane == 1) v = make_uint4((uint32_t)P.lidar_mode, 0u, (uint32_t)fp, (uint32_t)(fp >> 32));
+        if (lane == 2) v = make_uint4((uint32_t)steps, (uint32_t)(steps >> 32), (uint32_t)episodes, (uint32_t)(episodes >> 32));
+        o[lane] = v;
+    }
+    o += FTGP_ENV_STATE_HEAD;
+    const int n_car = cpe * FTGP_CAR_VEC, n_dyn = cpe * FTGP_DYN_VEC;
+    const uint4* cars = reinterpret_cast<const uint4*>(P.cars + (size_t)env * cpe);
+    for (int i = lane; i < n_car; i += FTGP_WAVE) o[i] = cars[i];
+    o += n_car;
+    if (A.dyn) {
+        const uint4* dyn = A.dyn + (size_t)env * n_dyn;
+        for (int i = lane; i < n_dyn; i += FTGP_WAVE) o[i] = dyn[i];
+    } else {
+        const uint4* own = reinterpret_cast<const uint4*>(A.aux->own);
+        for (int i = lane; i < n_dyn; i += FTGP_WAVE) o[i] = own[i % FTGP_DYN_VEC];
+    }
+    o += n_dyn;
+    for (int c = 0; c < cpe; ++c) {
+        // (a scan row in the handle is ranges_stride floats, a multiple of 32 >= n_rays: the last vector of a record's row lies inside it)
+        const uint4* src = reinterpret_cast<const uint4*>(P.ranges + (size_t)(env * cpe + c) * P.ranges_stride);
+        for (int j = lane; j < A.row_vec; j += FTGP_WAVE) {
+            uint4 v = src[j];
+            const int left = P.n_rays - 4 * j;        // rays from this vector on, >= 1: zeros behind the row's last ray
+            if (left < 4) v.w = 0u;
+            if (left < 3) v.z = 0u;
+            if (left < 2) v.y = 0u;
+            o[(size_t)c * A.row_vec + j] = v;
+        }
+    }
+}
+
+// The header is compared before the first store: an env is loaded whole or not at all.
+__global__ void __launch_bounds__(FTGP_ENV_STATE_THREADS) ftgp_env_load_kernel(DeviceParams P, EnvStateArgs A)
+{
+    const int env = env_state_env();
+    if (env >= P.n_envs) return;
+    const int r = A.src_row ? sgpr(A.src_row[env]) : env;
+    if (r < 0) return;
+    const int lane = lane_id(), cpe = P.cars_per_env;
+    bool ok = (int64_t)r < A.n_rows;
+    const uint4* s = A.rows + (ok ? (size_t)r * (size_t)A.env_vec : 0);
+    uint4 h2 = make_uint4(0u, 0u, 0u, 0u);
+    if (ok) {
+        const uint4 h0 = s[0], h1 = s[1];
+        h2 = s[2];
+        const uint64_t fp = A.aux->track_fp[env_track_of(A.env_track, env)];
+        ok = h0.x == FTGP_ENV_STATE_MAGIC && h0.y == FTGP_ENV_STATE_VERSION && h0.z == (uint32_t)P.n_rays && h0.w == (uint32_t)cpe &&
+             h1.x == (uint32_t)P.lidar_mode && h1.z == (uint32_t)fp && h1.w == (uint32_t)(fp >> 32);
+    }
+    if (!ok) {
+        if (lane == 0) atomicAdd(&A.aux->rejected, 1ull);
+        return;
+    }
+    if (lane == 0) {
+        P.steps[env] = (int64_t)(((uint64_t)h2.y << 32) | h2.x);
+        if (A.episodes) A.episodes[env] = (int64_t)(((uint64_t)h2.w << 32) | h2.z);
+    }
+    s += FTGP_ENV_STATE_HEAD;
+    const int n_car = cpe * FTGP_CAR_VEC, n_dyn = cpe * FTGP_DYN_VEC;
+    uint4* cars = reinterpret_cast<uint4*>(P.cars + (size_t)env * cpe);
+    for (int i = lane; i < n_car; i += FTGP_WAVE) cars[i] = s[i];
+    s += n_car;
+    if (A.dyn) {
+        uint4* dyn = A.dyn + (size_t)env * n_dyn;
+        for (int i = lane; i < n_dyn; i += FTGP_WAVE) dyn[i] = s[i];
+    }
+    s += n_dyn;
+    const int whole = P.n_rays / 4, tail = P.n_rays % 4;
+    for (int c = 0; c < cpe; ++c) {
+        float* dst = P.ranges + (size_t)(env * cpe + c) * P.ranges_stride;
+        const uint4* row = s + (size_t)c * A.row_vec;
+        for (int j = lane; j < whole; j += FTGP_WAVE) reinterpret_cast<uint4*>(dst)[j] = row[j];
+        if (tail && lane == whole % FTGP_WAVE) {          // the row's last one to three rays: what lies behind them in the handle stays
+            const uint4 v = row[whole];
+            dst[4 * whole] = __uint_as_float(v.x);
+            if (tail > 1) dst[4 * whole + 1] = __uint_as_float(v.y);
+            if (tail > 2) dst[4 * whole + 2] = __uint_as_float(v.z);
+        }
+    }
+}
+
 // Packed read-back rows, one car per lane: the host copies 3 small arrays instead of the whole state records.
 //   prog  int32[n_cars][FTGP_PROGRESS_INTS]   (custom.py:91-143: lap_completion / absolute_completion folded in)
 //   core  double[n_cars][16]: x y qw qz vx vy wz u_speed u_steer laps lap_completion absolute_completion steps n_times start finish_step (the last two: int64 bit patterns)

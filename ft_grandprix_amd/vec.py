@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes
 import math
 
+import numpy as np
 import torch  # first: the library must bind to torch's HIP runtime (see above)
 
 from . import capi
@@ -57,6 +58,21 @@ def check_single_hip_runtime(maps_text: str | None = None) -> None:
             continue
         if len(paths) > 1:
             raise RuntimeError(f"{RUNTIME_ERROR} (two copies of {name} are mapped: {', '.join(paths)})")
+
+
+class EnvSnapshot:
+    """Saved env states (``DeviceVecEnv.save_state``).  ``data``: uint8 [n_rows, bytes_per_env] on the env's device, row e = the
+    record of env e (include/ftgp.h: ftgp_save_envs_device; ``capi.unpack_env_state`` decodes it) -- ``data.cpu()`` or ``torch.save``
+    of it is the checkpoint.  ``dynamics``: a clone of the env's ``dynamics`` mirror, float64 [n_rows, cars_per_env, 8], None while
+    the table is off.  ``generator_state``: the state of the generator the dynamics are drawn with, None without
+    ``randomize_dynamics``."""
+
+    def __init__(self, data, dynamics=None, generator_state=None):
+        self.data, self.dynamics, self.generator_state = data, dynamics, generator_state
+
+    @property
+    def bytes_per_env(self) -> int:
+        return int(self.data.shape[1])
 
 
 class DeviceVecEnv:
@@ -120,6 +136,11 @@ class DeviceVecEnv:
     exactly when it starts a new episode, with no host synchronisation.  ``dynamics`` is the torch mirror of the rows in force, float64
     [n_envs, cars_per_env, 8], for privileged critics (None while the table is off).  ``set_dynamics(rows, env_mask=None)`` takes rows
     of the caller's choosing, for curricula.  Not with lidar_mode "fakelidar".
+
+    Saved states (ftgp_save_envs_device / ftgp_load_envs_device): ``save_state(env_mask=None)`` returns an ``EnvSnapshot`` of the envs'
+    whole state -- poses, velocities, steering joint, wheel spins, controls, race and lap fields, step and episode counters, dynamics,
+    scans; ``load_state(snap, src=None)`` puts env e back to row ``src[e]`` (negative = keep) and evaluates ``obs`` and the optional
+    rows again; ``fork(src)`` = ``load_state(save_state(), src)``, the copy a sampling planner makes.  All on torch's stream.
 
     The returned tensors are the env's own buffers: the next ``step`` or ``reset`` overwrites them -- clone what you keep.  Work is ordered on ``torch.cuda.current_stream(device)``; nothing
     synchronises the host.
@@ -222,6 +243,7 @@ class DeviceVecEnv:
         self.track = self.tracks[0]
         self.n_envs, self.n_rays, self.cars_per_env, self.roster = n_envs, n_rays, cars_per_env, roster
         self.n_agents = roster.count("agent")
+        self.bytes_per_env = capi.env_state_layout(n_rays, cars_per_env)["bytes"]      # of an env-state record (save_state)
         self.max_episode_steps, self.action_repeat, self.auto_reset = int(max_episode_steps), int(action_repeat), bool(auto_reset)
         self.scan_pool, self.scan_max_range, self.n_beams = scan_pool, scan_max_range, n_rays // scan_pool
         self.terminate_off_track, self.off_track_penalty = bool(terminate_off_track), off_track_penalty
@@ -408,6 +430,120 @@ class DeviceVecEnv:
         """New dynamics for the envs whose episode ended in the step just enqueued (they start a new episode)."""
         torch.logical_or(self.terminated, self.truncated, out=self._dyn_mask)
         self._draw_dynamics(self._dyn_mask)
+
+    # -- env states: save, restore, fork (include/ftgp.h: ftgp_save_envs_device / ftgp_load_envs_device)
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _device_guard(self):
+        return torch.cuda.device(self.device)
+
+    def _check_env_vector(self, name, t, dtypes):
+        """``t``: a contiguous tensor [n_envs] of one of ``dtypes`` on the env's device (ValueError otherwise)."""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: a torch tensor")
+        if t.device != self.device:
+            raise ValueError(f"{name} is on {t.device}, the env on {self.device}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name}: {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        if t.shape != (self.n_envs,):
+            raise ValueError(f"{name}: shape ({self.n_envs},), got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: a contiguous tensor")
+
+    def _check_snapshot(self, snap, need_all):
+        """``snap``: an EnvSnapshot whose records are this env's, on its device; ``need_all``: with a row for every env."""
+        if not isinstance(snap, EnvSnapshot) or not isinstance(snap.data, torch.Tensor):
+            raise ValueError("an EnvSnapshot (DeviceVecEnv.save_state)")
+        d = snap.data
+        if d.dtype != torch.uint8 or d.dim() != 2:
+            raise ValueError(f"snapshot data: uint8 [n_rows, bytes_per_env], got {d.dtype} {tuple(d.shape)}")
+        if d.shape[1] != self.bytes_per_env:
+            raise ValueError(f"snapshot records of {d.shape[1]} bytes, this env's are {self.bytes_per_env} (n_rays {self.n_rays}, "
+                             f"{self.cars_per_env} cars per env)")
+        if d.device != self.device:
+            raise ValueError(f"snapshot data is on {d.device}, the env on {self.device}")
+        if not d.is_contiguous() or d.data_ptr() % 16:
+            raise ValueError("snapshot data: a contiguous, 16-byte aligned tensor")
+        if d.shape[0] < 1 or (need_all and d.shape[0] < self.n_envs):
+            raise ValueError(f"snapshot of {d.shape[0]} rows, the env has {self.n_envs} envs")
+        if snap.dynamics is not None and (not isinstance(snap.dynamics, torch.Tensor) or snap.dynamics.device != self.device or
+                                          snap.dynamics.shape != (d.shape[0], self.cars_per_env, capi.DYN_DOUBLES)):
+            raise ValueError(f"snapshot dynamics: float64 [{d.shape[0]}, {self.cars_per_env}, {capi.DYN_DOUBLES}] on {self.device}")
+
+    def save_state(self, env_mask=None, out=None):
+        """The state of the envs ``env_mask`` names (bool or uint8 [n_envs] on the device, None = all) as an ``EnvSnapshot``: row e of
+        ``data`` is env e's record; a new snapshot holds zeros in the rows of the other envs (no env takes such a row back), ``out`` (a
+        snapshot of this env's, with a row per env) keeps what they held.  On torch's current stream; nothing synchronises."""
+        if env_mask is not None:
+            self._check_env_vector("env_mask", env_mask, (torch.bool, torch.uint8))
+        if out is not None:
+            self._check_snapshot(out, True)
+        with self._device_guard():
+            snap = out if out is not None else EnvSnapshot(torch.zeros((self.n_envs, self.bytes_per_env), dtype=torch.uint8,
+                                                                       device=self.device))
+            self.env.save_envs_device(snap.data.data_ptr(), snap.data.shape[0], 0 if env_mask is None else env_mask.data_ptr(),
+                                      self._stream())
+            self._state_keep = (snap, env_mask)           # (the library reads and writes them in stream order)
+            if self.dynamics is not None:
+                if snap.dynamics is None:                      # (a row per record, also beyond the envs in a caller's larger buffer)
+                    snap.dynamics = self.dynamics.new_zeros((snap.data.shape[0],) + tuple(self.dynamics.shape[1:]))
+                mine = snap.dynamics[:self.n_envs]
+                if env_mask is None:
+                    mine.copy_(self.dynamics)
+                else:
+                    torch.where(env_mask.to(torch.bool)[:, None, None], self.dynamics, mine, out=mine)
+            snap.generator_state = self._dyn_gen.get_state() if self._dyn_lo is not None else None
+        return snap
+
+    def _state_headers(self):
+        """uint8 [n_envs, 32] on the device: the header a record must carry for env e to take it (the library's rule)."""
+        if getattr(self, "_state_header", None) is None:
+            head = np.zeros(self.n_envs, dtype=capi.ENV_STATE_HEADER_DTYPE)
+            head["magic"], head["version"] = capi.ENV_STATE_MAGIC, capi.ENV_STATE_VERSION
+            head["n_rays"], head["cars_per_env"], head["lidar_mode"] = self.n_rays, self.cars_per_env, self.env.cfg.lidar_mode
+            fps = np.array([capi.track_fingerprint(t) for t in self.tracks], dtype=np.uint64)
+            head["fingerprint"] = fps[self.env.track_of_env]
+            self._state_header = torch.from_numpy(head.view(np.uint8).reshape(self.n_envs, -1)[:, :32].copy()).to(self.device)
+        return self._state_header
+
+    def load_state(self, snap, src=None):
+        """Put envs back to saved states: env e takes row ``src[e]`` of ``snap`` (int32 or int64 [n_envs] on the device; a negative entry
+        keeps the env as it is; None = row e).  A row that is not a record of this env's shape and track, or lies outside the snapshot,
+        leaves the env untouched (``env.env_state_rejected()`` counts them).  The ``dynamics`` mirror follows for the envs taken; the
+        generator of the dynamics draw is put back only with ``src=None``.  ``obs`` and the ``state`` / ``contact`` / ``frame`` /
+        ``rival`` rows are evaluated again at the loaded state; ``reward``, ``terminated``, ``truncated`` and the ``final_*`` buffers
+        are left alone.  On torch's current stream; nothing synchronises.  Returns ``obs``."""
+        self._check_snapshot(snap, src is None)
+        if src is not None:
+            self._check_env_vector("src", src, (torch.int32, torch.int64))
+        n_rows = snap.data.shape[0]
+        with self._device_guard():
+            src32 = None if src is None else src.to(torch.int32).contiguous()
+            self._state_keep = (snap, src32)
+            stream = self._stream()
+            self.env.load_envs_device(snap.data.data_ptr(), n_rows, 0 if src32 is None else src32.data_ptr(), stream)
+            if self.dynamics is not None and snap.dynamics is not None:
+                idx = torch.arange(self.n_envs, device=self.device) if src is None else src.to(torch.int64)
+                safe = idx.clamp(0, n_rows - 1)
+                take = (idx >= 0) & (idx < n_rows) & (snap.data[safe, :32] == self._state_headers()).all(dim=1)
+                torch.where(take[:, None, None], snap.dynamics[safe], self.dynamics, out=self.dynamics)
+            if src is None and snap.generator_state is not None and self._dyn_lo is not None:
+                self._dyn_gen.set_state(snap.generator_state)
+            self.env.obs_device(self.obs.data_ptr(), stream)
+            for rows, refresh in ((self.state, self.env.state_device), (self.contact, self.env.contacts_device),
+                                  (self.frame, self.env.frame_device), (self.rival, self.env.rivals_device)):
+                if rows is not None:
+                    refresh(rows.data_ptr(), stream)
+        return self.obs
+
+    def fork(self, src):
+        """``load_state(save_state(), src)``: env e continues from the state env ``src[e]`` is in now (a negative entry keeps env e).
+        What is drawn per env index -- the "random" driver, the next random start -- differs between the copies; everything else
+        continues to the bit."""
+        self._check_env_vector("src", src, (torch.int32, torch.int64))
+        self._fork_snap = self.save_state(out=getattr(self, "_fork_snap", None))      # (one buffer, written whole by every fork)
+        return self.load_state(self._fork_snap, src)
 
     def close(self):
         if getattr(self, "env", None) is not None:

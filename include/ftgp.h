@@ -644,6 +644,76 @@ int ftgp_set_dynamics(FtgpEnv *env, const double *rows, const uint8_t *env_mask)
 int ftgp_set_dynamics_device(FtgpEnv *env, void *stream, const double *rows, const uint8_t *env_mask);
 int ftgp_get_dynamics(FtgpEnv *env, double *rows_out, int64_t *rejected_out);
 
+/* ---- Env states on the device: save, restore, fork (no reference counterpart) ---------------------------------------------------------
+ * Everything an env carries from one step to the next, as one record in device memory: the env's step count, its episode counter, its
+ * cars' records (pose, velocities, the steering joint, the wheel spins, controls, fast.py's last steering angle, the race fields and
+ * the lap-time ring), their dynamics records and their scans.  A save writes records, a load takes them back; a fork is a save
+ * followed by a load with a row table.  Both only enqueue, like ftgp_set_dynamics_device.
+ *
+ * The record of one env is ftgp_env_state_bytes() bytes, a multiple of 16; every part starts on a 16-byte boundary.  With
+ * c = cars_per_env and pad16(n) = (n + 15) & ~15, little-endian as the device stores it:
+ *   offset  0  uint32 magic = 0x53454746 ("FGES")
+ *           4  uint32 version = FTGP_ENV_STATE_VERSION
+ *           8  int32  n_rays
+ *          12  int32  cars_per_env
+ *          16  int32  lidar_mode
+ *          20  int32  reserved = 0
+ *          24  uint64 track fingerprint (below) of the env's track
+ *          32  int64  steps       (ftgp_get_steps)
+ *          40  int64  episodes    (ftgp_get_episodes; 0 on a handle that never had a spawn rule)
+ *          48  c car records of 448 bytes, car slot 0 first.  Doubles at byte 0, 8, ...: x, y, qw, qz, vx, vy, wz, qs, qsd (the steering
+ *              joint's angle and rate), w[4] (wheel spins fl, fr, bl, br), u_speed, u_steer, last_steer, dist2 (ftgp_get_centre_dist2);
+ *              int32 at byte 136: completion, laps, offset, n_times, good_start, finished, off_track, delta; int64 at byte 168: start,
+ *              finish_step (meaningful while finished != 0); double times[FTGP_MAX_LAP_TIMES] at byte 192 (the ring of ftgp_get_lap_times)
+ *          48 + 448 c  c dynamics records of FTGP_DYN_RECORD doubles: the car's FTGP_DYN_DOUBLES row, then its four static wheel loads.
+ *              With the table off: the handle's own eight values and its wheel loads
+ *          48 + 544 c  c scan rows of pad16(4 n_rays) bytes: the car's ftgp_get_lidar row as binary32 -- what the next driver call
+ *              reads -- then zeros up to the boundary
+ *   bytes_per_env = 48 + 544 c + c pad16(4 n_rays)          (4912 for 1 car x 1080 rays)
+ *
+ * Track fingerprint, computed once per track on the host at create, with splitmix64 the spawn rule's:
+ *   h = 0; for every v of the sequence below, as uint64: h = splitmix64(h ^ v)
+ *   sequence: width, height; the bitmap words [height][words_per_row] in row order, bits beyond the width cleared; the bit patterns of
+ *   the 200 path doubles (x0, y0, x1, ...).
+ *
+ * ftgp_save_envs_device: env e of env_mask (uint8[n_envs] in device memory, non-zero = save; NULL = all envs: the mask of
+ * ftgp_set_dynamics_device) writes row e of rows, n_rows rows of bytes_per_env bytes; n_rows >= n_envs (FTGP_ERR_ARG otherwise).  Rows
+ * of other envs are not touched.
+ *
+ * ftgp_load_envs_device: env e takes row src_row[e] of rows (int32[n_envs] in device memory; NULL = row e, which needs
+ * n_rows >= n_envs).  A negative entry leaves the env exactly as it is.  The kernel cannot report without a synchronisation: a row
+ * whose index is >= n_rows, or whose magic, version, n_rays, cars_per_env, lidar_mode or fingerprint is not that of env e -- the
+ * fingerprint of e's own track, so a row saved on another track of a multi-track handle is refused -- leaves the env untouched and
+ * adds one to a device counter, which ftgp_get_env_state_rejected reads (host, synchronous).  The counter counts over the handle's
+ * life: nothing resets it, no ftgp_device_io_config either; a caller compares two readings.  An env is loaded whole or not at all.
+ * An accepted row writes steps; episodes, if the handle has or had a spawn rule (otherwise the entry is ignored); the car records;
+ * the scans; and the dynamics records if the dynamics table is on.  With the table off they are ignored and the cars stay the
+ * handle's vehicle.  The records are taken as they are: rows that a save wrote are valid, rows of other origin are the caller's.
+ * The vehicle constants, dt, lap_target, seed, env_base and the device-io rules are neither in the record nor checked: loading across
+ * handles that differ there is the caller's business.  Load touches neither the spawn rule, nor whether the dynamics table is on, nor
+ * the device-io setters.  A row loaded into another env index continues bit for bit except for what is drawn per global env index:
+ * FTGP_POLICY_RANDOM, the spawn rule's next draw and spawn_mode 1's pose at the next reset.
+ *
+ * Both are ordered on `stream` like ftgp_set_dynamics_device (the handle's stream waits for `stream`, and `stream` for the work) and are
+ * valid on any handle after create: FTGP_LIDAR_FAKELIDAR, shards, multi-track handles and the tricycle included, with or without
+ * ftgp_device_io_config.  A handle's first call allocates a few bytes and may synchronise.  FTGP_ERR_ARG, before anything is enqueued
+ * and with the entry's name in front: a buffer that is not device memory on the handle's device or is smaller than the layout needs,
+ * rows not 16-byte aligned, n_rows < n_envs where it is needed, n_rows < 1 or >= 2^31.  There is no env-to-env copy in place: save,
+ * then load with src_row, which has no read-after-write hazard. */
+#define FTGP_ENV_STATE_VERSION 1
+#define FTGP_ENV_STATE_MAGIC 0x53454746u
+#define FTGP_DYN_RECORD 12
+int ftgp_env_state_bytes(FtgpEnv *env, size_t *bytes_per_env);
+int ftgp_save_envs_device(FtgpEnv *env, void *stream, void *rows, int64_t n_rows, const uint8_t *env_mask);
+int ftgp_load_envs_device(FtgpEnv *env, void *stream, const void *rows, int64_t n_rows, const int32_t *src_row);
+int ftgp_get_env_state_rejected(FtgpEnv *env, int64_t *rejected);
+
+/* The agents' observation rows at the state as it stands, without a step (e.g. after ftgp_load_envs_device, where obs is not zeros as
+ * it is after a reset): float32[n_envs][n_ext][n_beams] in device memory, pooled, clipped and scaled by the signals in force, by the
+ * device function the device step pools with -- a row equals to the bit what a step's obs holds for those scans.  Ordered on `stream`
+ * like ftgp_state_device (only enqueues).  After ftgp_device_io_config only (FTGP_ERR_STATE before it). */
+int ftgp_obs_device(FtgpEnv *env, void *stream, float *obs);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).
