@@ -39,8 +39,14 @@ POLICY_HOST, POLICY_LOBOTOMY, POLICY_NIDC, POLICY_FAST, POLICY_RANDOM = 0, 1, 2,
 LIDAR_RANGEFINDER, LIDAR_FAKELIDAR = 0, 1
 LIDAR_BY_NAME = {"rangefinder": LIDAR_RANGEFINDER, "fakelidar": LIDAR_FAKELIDAR}
 POLICY_PER_CAR = 5
+POLICY_NET0 = 6             # FTGP_POLICY_NET0 .. FTGP_POLICY_NET3: the network drivers of slots 0 .. 3 (ftgp_set_net)
+MAX_NETS = 4                # FTGP_MAX_NETS
+NET_MAX_LAYERS, NET_MAX_INPUTS, NET_MAX_HIDDEN, NET_STATE_INPUTS = 4, 256, 128, 5       # FTGP_NET_*
+ACT_IDENTITY, ACT_RELU, ACT_TANH = 0, 1, 2
+ACT_BY_NAME = {"identity": ACT_IDENTITY, "relu": ACT_RELU, "tanh": ACT_TANH}
 POLICY_BY_NAME = {"host": POLICY_HOST, "lobotomy": POLICY_LOBOTOMY, "nidc": POLICY_NIDC,
-                  "fast": POLICY_FAST, "random": POLICY_RANDOM, "per_car": POLICY_PER_CAR}
+                  "fast": POLICY_FAST, "random": POLICY_RANDOM, "per_car": POLICY_PER_CAR,
+                  "net0": POLICY_NET0, "net1": POLICY_NET0 + 1, "net2": POLICY_NET0 + 2, "net3": POLICY_NET0 + 3}
 
 PROGRESS_FIELDS = ("laps", "completion", "lap_completion", "absolute_completion", "finished",
                    "off_track", "start", "good_start", "delta", "finish_step")
@@ -102,6 +108,7 @@ API_SYMBOLS = (
     "device_io_rivals", "step_device_rivals", "rivals_device", "get_rivals",
     "set_dynamics", "set_dynamics_device", "get_dynamics",
     "env_state_bytes", "save_envs_device", "load_envs_device", "get_env_state_rejected", "obs_device",
+    "set_net", "set_net_device", "get_net",
 )
 
 
@@ -151,6 +158,80 @@ class FtgpDeviceStepRivals(C.Structure):
 class FtgpSpawnRule(C.Structure):
     _fields_ = [("first_point", C.c_int32), ("n_points", C.c_int32), ("shuffle_grid", C.c_int32), ("reserved", C.c_int32),
                 ("margin", C.c_double), ("lateral_frac", C.c_double), ("yaw_tan", C.c_double)]
+
+
+class FtgpNetDesc(C.Structure):
+    _fields_ = [("pool", C.c_int32), ("max_range", C.c_float), ("beam_first", C.c_int32), ("n_beams", C.c_int32),
+                ("use_state", C.c_int32), ("n_layers", C.c_int32), ("width", C.c_int32 * NET_MAX_LAYERS),
+                ("hidden_act", C.c_int32), ("out_act", C.c_int32), ("out_scale", C.c_float * 2), ("out_offset", C.c_float * 2),
+                ("reserved", C.c_int32)]
+
+
+def net_desc(layers, *, pool, max_range, beam_first, n_beams, use_state=False, hidden_act="tanh", out_act="tanh",
+             out_scale=(1, 1), out_offset=(0, 0)):
+    """(FtgpNetDesc, flat float32 parameters) of a network given as a list of (W [n_out, n_in], b [n_out]) pairs, with every check of
+    ftgp_set_net that needs no handle (ValueError): the widths, the activations, the output map, the shapes of the arrays.  The window
+    rule needs n_rays: ``check_net_window``."""
+    layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
+    if not 1 <= len(layers) <= NET_MAX_LAYERS:
+        raise ValueError(f"a network has 1 .. {NET_MAX_LAYERS} layers, got {len(layers)}")
+    if int(pool) < 1 or int(n_beams) < 1 or int(beam_first) < 0:
+        raise ValueError(f"pool >= 1, n_beams >= 1, beam_first >= 0: got {pool}, {n_beams}, {beam_first}")
+    if not (np.isfinite(max_range) and max_range > 0):
+        raise ValueError(f"max_range must be finite and > 0, got {max_range}")
+    n_in = int(n_beams) + (NET_STATE_INPUTS if use_state else 0)
+    if n_in > NET_MAX_INPUTS:
+        raise ValueError(f"n_beams + 5 use_state = {n_in} inputs, at most {NET_MAX_INPUTS}")
+    for name, act in (("hidden_act", hidden_act), ("out_act", out_act)):
+        if act not in ACT_BY_NAME:
+            raise ValueError(f"{name}: one of {sorted(ACT_BY_NAME)}, got {act!r}")
+    scale, offset = np.asarray(out_scale, dtype=np.float32), np.asarray(out_offset, dtype=np.float32)
+    if scale.shape != (2,) or offset.shape != (2,) or not (np.isfinite(scale).all() and np.isfinite(offset).all()):
+        raise ValueError("out_scale and out_offset: two finite numbers each")
+    d = FtgpNetDesc(pool=int(pool), max_range=float(max_range), beam_first=int(beam_first), n_beams=int(n_beams),
+                    use_state=1 if use_state else 0, n_layers=len(layers), hidden_act=ACT_BY_NAME[hidden_act], out_act=ACT_BY_NAME[out_act])
+    flat, width = [], n_in
+    for l, (W, b) in enumerate(layers):
+        last = l == len(layers) - 1
+        if W.ndim != 2 or W.shape[1] != width or b.shape != (W.shape[0],):
+            raise ValueError(f"layer {l}: W [n_out, {width}] and b [n_out] (torch's nn.Linear layout), got {W.shape} and {b.shape}")
+        if last and W.shape[0] != 2:
+            raise ValueError(f"the last layer has exactly 2 outputs (speed, steering_angle), got {W.shape[0]}")
+        if not last and not 1 <= W.shape[0] <= NET_MAX_HIDDEN:
+            raise ValueError(f"layer {l}: a hidden width is 1 .. {NET_MAX_HIDDEN}, got {W.shape[0]}")
+        d.width[l] = width = W.shape[0]
+        flat += [W.ravel(), b.ravel()]
+    for k in range(2):
+        d.out_scale[k], d.out_offset[k] = float(scale[k]), float(offset[k])
+    return d, np.ascontiguousarray(np.concatenate(flat), dtype=np.float32)
+
+
+def check_net_window(n_rays: int, pool: int, beam_first: int, n_beams: int):
+    """The window rule of ftgp_set_net (ValueError): the device drivers see rays [eighth, n_rays - eighth) only."""
+    eighth = int(n_rays / 8.0)
+    if n_rays % pool:
+        raise ValueError(f"pool {pool} does not divide n_rays {n_rays}")
+    if beam_first * pool < eighth or (beam_first + n_beams) * pool > n_rays - eighth:
+        raise ValueError(f"beams {beam_first} .. {beam_first + n_beams - 1} of pool {pool} leave the drivers' scan window, "
+                         f"rays [{eighth}, {n_rays - eighth}) of {n_rays}: the rear quarter of the scan is not an input")
+
+
+def net_param_count(d: FtgpNetDesc) -> int:
+    n, n_in = 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0)
+    for l in range(d.n_layers):
+        n, n_in = n + d.width[l] * n_in + d.width[l], d.width[l]
+    return n
+
+
+def net_layers(d: FtgpNetDesc, flat: np.ndarray) -> list:
+    """The (W, b) pairs of a flat parameter buffer in ftgp_set_net's layout."""
+    out, o, n_in = [], 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0)
+    for l in range(d.n_layers):
+        n_out = d.width[l]
+        W = flat[o:o + n_out * n_in].reshape(n_out, n_in); o += n_out * n_in
+        out.append((W.copy(), flat[o:o + n_out].copy())); o += n_out
+        n_in = n_out
+    return out
 
 
 class FtgpError(RuntimeError):
@@ -250,6 +331,9 @@ class CLib:
             "load_envs_device": (i32, [vp, vp, vp, C.c_int64, vp]),
             "get_env_state_rejected": (i32, [vp, C.POINTER(C.c_int64)]),
             "obs_device": (i32, [vp, vp, vp]),
+            "set_net": (i32, [vp, i32, C.POINTER(FtgpNetDesc), dp]),
+            "set_net_device": (i32, [vp, vp, i32, vp]),
+            "get_net": (i32, [vp, i32, C.POINTER(FtgpNetDesc), dp]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -544,6 +628,31 @@ class Env:
         rejected = C.c_int64(0)
         self._call("get_dynamics", _ptr(out), C.byref(rejected))
         return out, int(rejected.value)
+
+    # -- network drivers (include/ftgp.h: ftgp_set_net)
+    def set_net(self, slot: int, layers, *, pool=None, max_range=None, beam_first=None, n_beams=None, use_state=False,
+                hidden_act="tanh", out_act="tanh", out_scale=(1, 1), out_offset=(0, 0)):
+        """ftgp_set_net: ``layers`` = [(W [n_out, n_in], b [n_out]), ...] (torch's nn.Linear layout) becomes the network driver
+        ``"net<slot>"``; ``layers=None`` clears the slot."""
+        if layers is None:
+            self._call("set_net", int(slot), None, None)
+            return
+        d, flat = net_desc(layers, pool=pool, max_range=max_range, beam_first=beam_first, n_beams=n_beams, use_state=use_state,
+                           hidden_act=hidden_act, out_act=out_act, out_scale=out_scale, out_offset=out_offset)
+        self._call("set_net", int(slot), C.byref(d), _ptr(flat))
+
+    def set_net_device(self, slot: int, address: int, stream: int = 0):
+        """ftgp_set_net_device: new parameters for a defined slot from the integer device address of a float32 buffer in
+        ftgp_set_net's flat layout, ordered on ``stream``; only enqueues."""
+        self._call("set_net_device", stream or None, int(slot), address or None)
+
+    def net(self, slot: int):
+        """(FtgpNetDesc, [(W, b), ...]): the description and the parameters in force of a defined slot (ftgp_get_net)."""
+        d = FtgpNetDesc()
+        self._call("get_net", int(slot), C.byref(d), None)
+        flat = np.empty(net_param_count(d), dtype=np.float32)
+        self._call("get_net", int(slot), C.byref(d), _ptr(flat))
+        return d, net_layers(d, flat)
 
     # -- env states on the device (include/ftgp.h: ftgp_save_envs_device)
     def env_state_bytes(self) -> int:

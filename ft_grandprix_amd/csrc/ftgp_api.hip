@@ -193,6 +193,12 @@ struct FtgpEnv {
     bool dyn_on = false;              // step launches run the DYN instantiations
     DynArgs dyn{};                    // the handle's own row and the wheel-load rule (the buffers are filled in per call)
     DevBuf<double> d_dyn_rows;        // [n_cars][FTGP_DYN_DOUBLES] landing buffer of the host setter, allocated on first use
+    // network drivers (ftgp_set_net)
+    DevBuf<NetDev> d_nets;            // [FTGP_MAX_NETS] the records the kernels read; allocated by the first setter call (ensure_nets)
+    NetDev nets[FTGP_MAX_NETS] = {};  // their host mirror (defined = 0: an empty slot)
+    FtgpNetDesc net_desc[FTGP_MAX_NETS] = {};     // the descriptions as the caller gave them (ftgp_get_net)
+    DevBuf<float> d_net_params[FTGP_MAX_NETS];    // the slots' parameters in the library's layout
+    bool last_net = false;            // the newest launch ran a NET instantiation
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
     std::vector<uint64_t> track_fp;   // [n_tracks] the tracks' fingerprints (include/ftgp.h), folded at create
     DevBuf<EnvStateAux> d_state_aux;  // the handle's own dynamics record, the rejected counter, the fingerprints; allocated by the first save or load
@@ -815,8 +821,21 @@ const StepKernel kStepKernelsDyn[2][2][2] = {   // [multi-track][multi][roster]
       { ftgp_step_kernel<true, false, true, true, true>, "ftgp_step_kernel<true, false, true, true, true>" } } },
 };
 
-const StepKernel& step_kernel(const FtgpEnv* e, bool roster)
+// ftgp_step_kernel<MULTI, false, true, TRACKS, DYN, true>: launches that name a network driver (ftgp_set_net)
+const StepKernel kStepKernelsNet[2][2][2] = {   // [multi-track][multi][dynamics table]
+  { { { ftgp_step_kernel<false, false, true, false, false, true>, "ftgp_step_kernel<false, false, true, false, false, true>" },
+      { ftgp_step_kernel<false, false, true, false, true, true>, "ftgp_step_kernel<false, false, true, false, true, true>" } },
+    { { ftgp_step_kernel<true, false, true, false, false, true>, "ftgp_step_kernel<true, false, true, false, false, true>" },
+      { ftgp_step_kernel<true, false, true, false, true, true>, "ftgp_step_kernel<true, false, true, false, true, true>" } } },
+  { { { ftgp_step_kernel<false, false, true, true, false, true>, "ftgp_step_kernel<false, false, true, true, false, true>" },
+      { ftgp_step_kernel<false, false, true, true, true, true>, "ftgp_step_kernel<false, false, true, true, true, true>" } },
+    { { ftgp_step_kernel<true, false, true, true, false, true>, "ftgp_step_kernel<true, false, true, true, false, true>" },
+      { ftgp_step_kernel<true, false, true, true, true, true>, "ftgp_step_kernel<true, false, true, true, true, true>" } } },
+};
+
+const StepKernel& step_kernel(const FtgpEnv* e, bool roster, bool net = false)
 {
+    if (net) return kStepKernelsNet[e->n_tracks > 1][e->multi][e->dyn_on];           // (never a FAKELIDAR handle: ftgp_set_net refuses it)
     if (e->dyn_on) return kStepKernelsDyn[e->n_tracks > 1][e->multi][roster];      // (never a FAKELIDAR handle: the setters refuse it)
     return kStepKernels[e->n_tracks > 1][e->multi][e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR ? 2 : roster ? 1 : 0];
 }
@@ -848,11 +867,31 @@ int use_table(FtgpEnv* e, int which)
     return 0;
 }
 
+// The network drivers a launch or a ftgp_policy_eval with `policy` names: bit s = slot s.  FTGP_POLICY_PER_CAR: those of the slot table
+// it would run with (device_io: the device-io table).
+unsigned nets_named(const FtgpEnv* e, int policy, bool device_io)
+{
+    if (is_net_policy(policy)) return 1u << (policy - FTGP_POLICY_NET0);
+    if (policy != FTGP_POLICY_PER_CAR) return 0;
+    const int32_t* table = device_io ? e->h_tables.get() + FTGP_MAX_CARS_PER_BLOCK : e->P.car_policy;
+    unsigned m = 0;
+    for (int k = 0; k < e->P.cars_per_env; ++k) if (is_net_policy(table[k])) m |= 1u << (table[k] - FTGP_POLICY_NET0);
+    return m;
+}
+int check_nets_defined(const FtgpEnv* e, unsigned named)
+{
+    for (int s = 0; s < FTGP_MAX_NETS; ++s)
+        if ((named >> s & 1u) && !e->nets[s].defined) return failf(FTGP_ERR_STATE, "FTGP_POLICY_NET%d: network slot %d is not defined (ftgp_set_net)", s, s);
+    return 0;
+}
+
 // device_io: the launch of ftgp_step_device (the device-io slot table; checked by ftgp_device_io_config)
 int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
 {
     e->rows_valid = false;
     if (n_steps < 0) return fail(FTGP_ERR_ARG, "n_steps < 0%s");
+    const unsigned named = nets_named(e, policy, device_io);
+    if (int rc = check_nets_defined(e, named)) return rc;
     if (!device_io) {
         if (policy == FTGP_POLICY_PER_CAR && !e->P.car_policy[0]) return fail(FTGP_ERR_STATE, "FTGP_POLICY_PER_CAR without ftgp_set_car_policies%s");
         if (uses_disparity_driver(e, policy)) if (int rc = check_disparity_shape(e->P)) return rc;
@@ -884,11 +923,12 @@ int launch_steps(FtgpEnv* e, int policy, int n_steps, bool device_io = false)
         hipEvent_t ev0 = ext ? e->ev_start.get() : nullptr, ev1 = ext ? e->ev_stop[slot].get() : nullptr;
         const bool roster = policy == FTGP_POLICY_PER_CAR;
         e->last_roster = roster;
+        e->last_net = named != 0;
         // one rank and no communicator: the workgroups' partial records go straight to pinned host memory (bit 1 of the slot argument)
         const bool partial = e->h_wg_metrics != nullptr && e->comm == nullptr && e->d_wg_metrics != nullptr;
         const int slot_arg = slot | (partial ? 2 : 0);
         e->slot_partial[slot] = partial;
-        hipExtLaunchKernelGGL(step_kernel(e, roster).fn, grid, block, lds, e->stream.get(), ev0, ev1, 0, e->d_params.get(), policy, n_steps, slot_arg);
+        hipExtLaunchKernelGGL(step_kernel(e, roster, named != 0).fn, grid, block, lds, e->stream.get(), ev0, ev1, 0, e->d_params.get(), policy, n_steps, slot_arg);
         HIP_TRY(hipGetLastError());
         e->cur_slot = slot;
         e->launch_metrics_valid = e->d_wg_metrics != nullptr;
@@ -1456,7 +1496,7 @@ int ftgp_step(FtgpEnv* e, int n_steps)
 int ftgp_rollout(FtgpEnv* e, int policy, int n_steps)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (policy < FTGP_POLICY_HOST || policy > FTGP_POLICY_PER_CAR) return fail(FTGP_ERR_ARG, "unknown policy%s");
+    if (policy < FTGP_POLICY_HOST || policy > FTGP_POLICY_NET3) return fail(FTGP_ERR_ARG, "unknown policy%s");
     return launch_steps(e, policy, n_steps);
 }
 
@@ -1464,7 +1504,8 @@ int ftgp_set_car_policies(FtgpEnv* e, const int32_t* policies)
 {
     if (!e || !policies) return fail(FTGP_ERR_ARG, "null argument%s");
     for (int k = 0; k < e->P.cars_per_env; ++k)
-        if (policies[k] < FTGP_POLICY_LOBOTOMY || policies[k] > FTGP_POLICY_RANDOM) return fail(FTGP_ERR_ARG, "set_car_policies: lobotomy / nidc / fast / random only%s");
+        if ((policies[k] < FTGP_POLICY_LOBOTOMY || policies[k] > FTGP_POLICY_RANDOM) && !is_net_policy(policies[k]))
+            return fail(FTGP_ERR_ARG, "set_car_policies: lobotomy / nidc / fast / random / net0 .. net3 only%s");
     // a workgroup holds whole envs, so its car slot c runs the roster's entry c % cars_per_env
     for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->P.car_policy[c] = policies[c % e->P.cars_per_env];
     HIP_TRY(hipSetDevice(e->device));
@@ -1485,7 +1526,8 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
     int n_ext = 0; bool disparity = false;
     for (int k = 0; k < cpe; ++k) {
         slot[k] = cfg->roster ? cfg->roster[k] : FTGP_POLICY_HOST;
-        if (slot[k] < FTGP_POLICY_HOST || slot[k] > FTGP_POLICY_RANDOM) return fail(FTGP_ERR_ARG, "device_io_config: host / lobotomy / nidc / fast / random only%s");
+        if ((slot[k] < FTGP_POLICY_HOST || slot[k] > FTGP_POLICY_RANDOM) && !is_net_policy(slot[k]))
+            return fail(FTGP_ERR_ARG, "device_io_config: host / lobotomy / nidc / fast / random / net0 .. net3 only%s");
         n_ext += slot[k] == FTGP_POLICY_HOST;
         disparity = disparity || slot[k] == FTGP_POLICY_NIDC || slot[k] == FTGP_POLICY_FAST;
     }
@@ -1596,6 +1638,7 @@ int ftgp_step_device_rivals(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevi
     if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
     FtgpEnv::DeviceStep& ds = e->ds;
     if (!ds.ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
+    if (int rc = check_nets_defined(e, nets_named(e, FTGP_POLICY_PER_CAR, true))) return rc;      // (before anything is enqueued)
     // the four optional kinds of rows: floats per row, the caller's two buffers and what a refusal calls them
     struct Rows { const char* name; const char* final_name; size_t floats; float* out; float* final_out; };
     const Rows st{ "state", "final_state", FTGP_STATE_FLOATS, extra ? extra->state : nullptr, extra ? extra->final_state : nullptr };
@@ -1812,6 +1855,151 @@ int ftgp_get_dynamics(FtgpEnv* e, double* rows_out, int64_t* rejected_out)
     return 0;
 }
 
+// ---- network drivers ----
+// what ftgp_set_net checks of a description (include/ftgp.h); the message names the field
+static int check_net_desc(const FtgpEnv* e, const FtgpNetDesc& d)
+{
+    const int R = e->P.n_rays, eighth = e->P.eighth;
+    if (d.reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_set_net: reserved must be 0%s");
+    if (d.pool < 1 || R % d.pool != 0) return failf(FTGP_ERR_ARG, "ftgp_set_net: pool = %d must be >= 1 and divide n_rays = %d", d.pool, R);
+    if (!(d.max_range > 0.0f) || std::isinf(d.max_range)) return failf(FTGP_ERR_ARG, "ftgp_set_net: max_range = %g must be finite and > 0", (double)d.max_range);
+    if (d.n_beams < 1 || d.beam_first < 0 || d.n_beams > FTGP_NET_MAX_INPUTS || d.beam_first > R)
+        return failf(FTGP_ERR_ARG, "ftgp_set_net: beam_first = %d, n_beams = %d out of range", d.beam_first, d.n_beams);
+    if ((int64_t)d.beam_first * d.pool < eighth || (int64_t)(d.beam_first + d.n_beams) * d.pool > R - eighth)
+        return failf(FTGP_ERR_ARG, "ftgp_set_net: beams %d .. %d of pool %d leave the drivers' scan window, rays [%d, %d) of %d (beam_first, n_beams)", d.beam_first,
+                     d.beam_first + d.n_beams - 1, d.pool, eighth, R - eighth, R);
+    if (d.use_state != 0 && d.use_state != 1) return failf(FTGP_ERR_ARG, "ftgp_set_net: use_state = %d must be 0 or 1", d.use_state);
+    if (d.n_layers < 1 || d.n_layers > FTGP_NET_MAX_LAYERS) return failf(FTGP_ERR_ARG, "ftgp_set_net: n_layers = %d outside 1 .. %d", d.n_layers, FTGP_NET_MAX_LAYERS);
+    if (ftgp_net_inputs(&d) > FTGP_NET_MAX_INPUTS) return failf(FTGP_ERR_ARG, "ftgp_set_net: n_beams + 5 use_state = %d inputs, at most %d", ftgp_net_inputs(&d), FTGP_NET_MAX_INPUTS);
+    for (int l = 0; l < FTGP_NET_MAX_LAYERS; ++l) {
+        const int w = d.width[l];
+        if (l >= d.n_layers) { if (w != 0) return failf(FTGP_ERR_ARG, "ftgp_set_net: width[%d] = %d behind the last layer must be 0", l, w); }
+        else if (l == d.n_layers - 1) { if (w != 2) return failf(FTGP_ERR_ARG, "ftgp_set_net: width[%d] = %d: the last layer has exactly 2 outputs", l, w); }
+        else if (w < 1 || w > FTGP_NET_MAX_HIDDEN) return failf(FTGP_ERR_ARG, "ftgp_set_net: width[%d] = %d outside 1 .. %d", l, w, FTGP_NET_MAX_HIDDEN);
+    }
+    if (d.hidden_act < FTGP_ACT_IDENTITY || d.hidden_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_net: hidden_act = %d is no FTGP_ACT_*", d.hidden_act);
+    if (d.out_act < FTGP_ACT_IDENTITY || d.out_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_net: out_act = %d is no FTGP_ACT_*", d.out_act);
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(d.out_scale[k])) return failf(FTGP_ERR_ARG, "ftgp_set_net: out_scale[%d] is not finite", k);
+        if (!std::isfinite(d.out_offset[k])) return failf(FTGP_ERR_ARG, "ftgp_set_net: out_offset[%d] is not finite", k);
+    }
+    return 0;
+}
+
+// the record of a description: the library's layout (NetDev) without the buffer's address
+static NetDev net_record(const FtgpNetDesc& d)
+{
+    NetDev N{};
+    N.defined = 1; N.pool = d.pool; N.beam_first = d.beam_first; N.n_beams = d.n_beams; N.use_state = d.use_state; N.n_layers = d.n_layers;
+    N.hidden_act = d.hidden_act; N.out_act = d.out_act;
+    N.width[0] = ftgp_net_inputs(&d);
+    int o = 0;
+    for (int l = 0; l < d.n_layers; ++l) {
+        N.width[l + 1] = d.width[l];
+        const int ld = (d.width[l] + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
+        N.w_off[l] = o; o += N.width[l] * ld;
+        N.b_off[l] = o; o += ld;
+    }
+    N.n_floats = o;
+    N.max_range = d.max_range; N.inv_max_range = 1.0f / d.max_range;
+    for (int k = 0; k < 2; ++k) { N.out_scale[k] = d.out_scale[k]; N.out_offset[k] = d.out_offset[k]; }
+    return N;
+}
+
+// The first setter call of a handle: the NET kernels may use the LDS the others may, the records are allocated (zeroed: every slot
+// empty) and every parameter block learns their address.  ftgp_create does nothing for the networks.
+static int ensure_nets(FtgpEnv* e)
+{
+    if (e->d_nets) return 0;
+    for (const auto& set : kStepKernelsNet) for (const auto& row : set) for (const StepKernel& k : row) HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the blocks while they change
+    DevBuf<NetDev> d;
+    HIP_TRY(dev_alloc(d, sizeof(NetDev) * FTGP_MAX_NETS));
+    HIP_TRY(hipMemset(d.get(), 0, sizeof(NetDev) * FTGP_MAX_NETS));
+    const uint64_t a = (uint64_t)(uintptr_t)d.get();
+    const uint32_t lo = (uint32_t)a, hi = (uint32_t)(a >> 32);
+    for (const TrackBufs& t : e->trk) {   // every track's parameter block
+        unsigned char* block = reinterpret_cast<unsigned char*>(e->d_params.get()) + t.block;
+        HIP_TRY(hipMemcpy(block + offsetof(DeviceParams, net_table_lo), &lo, sizeof lo, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(block + offsetof(DeviceParams, net_table_hi), &hi, sizeof hi, hipMemcpyHostToDevice));
+    }
+    e->P.net_table_lo = lo; e->P.net_table_hi = hi;
+    e->d_nets = std::move(d);
+    return 0;
+}
+
+int ftgp_set_net(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const float* params)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_net: not on a FTGP_LIDAR_FAKELIDAR handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (desc) {
+        if (int rc = check_net_desc(e, *desc)) return rc;
+        if (!params) return fail(FTGP_ERR_ARG, "ftgp_set_net: params is NULL%s");
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (!desc && !e->d_nets) return 0;        // nothing was ever defined
+    if (int rc = ensure_nets(e)) return rc;
+    NetDev N{};
+    DevBuf<float> buf;
+    if (desc) {
+        N = net_record(*desc);
+        std::vector<float> img((size_t)N.n_floats, 0.0f);     // the library's layout; the padding is zeros
+        const float* src = params;
+        for (int l = 0; l < N.n_layers; ++l) {
+            const int n_in = N.width[l], n_out = N.width[l + 1], ld = (n_out + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
+            for (int j = 0; j < n_out; ++j) for (int k = 0; k < n_in; ++k) img[(size_t)N.w_off[l] + (size_t)k * ld + j] = *src++;
+            for (int j = 0; j < n_out; ++j) img[(size_t)N.b_off[l] + j] = *src++;
+        }
+        HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
+        N.params = buf.get();
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the slot while it changes
+    HIP_TRY(hipMemcpy(e->d_nets.get() + slot, &N, sizeof N, hipMemcpyHostToDevice));
+    e->nets[slot] = N;
+    e->net_desc[slot] = desc ? *desc : FtgpNetDesc{};
+    e->d_net_params[slot] = std::move(buf);                   // (the old buffer goes: nothing reads it any more)
+    return 0;
+}
+
+int ftgp_set_net_device(FtgpEnv* e, void* stream, int slot, const float* params)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_device: network slot %d is not defined (ftgp_set_net)", slot);
+    HIP_TRY(hipSetDevice(e->device));
+    const int n = (int)ftgp_net_param_count(&e->net_desc[slot]);
+    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_net_device: %s", m.c_str()); return rc; };
+    if (int rc = check_device_buffer(e, params, sizeof(float) * (size_t)n, "params")) return refused(rc);
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream.get(), e->nets[slot], params, e->d_net_params[slot].get(), n);
+    HIP_TRY(hipGetLastError());
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+int ftgp_get_net(FtgpEnv* e, int slot, FtgpNetDesc* desc_out, float* params_out)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    const NetDev& N = e->nets[slot];
+    if (!N.defined) return failf(FTGP_ERR_STATE, "ftgp_get_net: network slot %d is not defined (ftgp_set_net)", slot);
+    if (desc_out) *desc_out = e->net_desc[slot];
+    if (!params_out) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<float> img((size_t)N.n_floats);
+    HIP_TRY(hipMemcpyAsync(img.data(), e->d_net_params[slot].get(), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    float* dst = params_out;
+    for (int l = 0; l < N.n_layers; ++l) {
+        const int n_in = N.width[l], n_out = N.width[l + 1], ld = (n_out + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
+        for (int j = 0; j < n_out; ++j) for (int k = 0; k < n_in; ++k) *dst++ = img[(size_t)N.w_off[l] + (size_t)k * ld + j];
+        for (int j = 0; j < n_out; ++j) *dst++ = img[(size_t)N.b_off[l] + j];
+    }
+    return 0;
+}
+
 int ftgp_env_state_bytes(FtgpEnv* e, size_t* bytes_per_env)
 {
     if (!e || !bytes_per_env) return fail(FTGP_ERR_ARG, "null argument%s");
@@ -2005,8 +2193,9 @@ int ftgp_policy_eval(FtgpEnv* e, int policy, const float* ranges, double* ctrl_o
 {
     if (!e || !ranges) return fail(FTGP_ERR_ARG, "null argument%s");
     e->rows_valid = false;
-    if (policy < FTGP_POLICY_LOBOTOMY || policy > FTGP_POLICY_PER_CAR) return fail(FTGP_ERR_ARG, "policy_eval: device policies only%s");
+    if (policy < FTGP_POLICY_LOBOTOMY || policy > FTGP_POLICY_NET3) return fail(FTGP_ERR_ARG, "policy_eval: device policies only%s");
     if (policy == FTGP_POLICY_PER_CAR && !e->P.car_policy[0]) return fail(FTGP_ERR_STATE, "FTGP_POLICY_PER_CAR without ftgp_set_car_policies%s");
+    if (int rc = check_nets_defined(e, nets_named(e, policy, false))) return rc;
     if (uses_disparity_driver(e, policy)) if (int rc = check_disparity_shape(e->P)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipMemcpy2DAsync(e->d_ranges.get(), sizeof(float) * (size_t)e->P.ranges_stride, ranges, sizeof(float) * (size_t)e->P.n_rays,
@@ -2343,7 +2532,7 @@ int ftgp_selftest(int device_id, int64_t* mismatches)
 const char* ftgp_kernel_name(FtgpEnv* e)
 {
     if (!e) return "ftgp_step_kernel";
-    return step_kernel(e, e->last_roster).name;      // the instantiation of the newest launch (before any: the single-driver one)
+    return step_kernel(e, e->last_roster, e->last_net).name;      // the instantiation of the newest launch (before any: the single-driver one)
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include "../../include/ftgp.h"
 #include "ftgp_march.h"
 #include "ftgp_spawn.h"
+#include "ftgp_net.h"
 
 #define FTGP_WAVE 64
 #define FTGP_MAX_GROUPS 256              // groups of 64 rays per car: n_rays <= 16384
@@ -69,14 +70,16 @@ struct DeviceParams {
     uint32_t plane256;            // bytes per (padded) sector plane of the box field / 256
     int32_t n_sectors;            // direction sectors of this handle's box field: 8 x (1, 2, 4 or 8 slope slices per octant)
     float slice_factor;           // FTGP_SLICE_FACTOR(FTGP_SLOPE_SLICES): a ray's sector is found among all FTGP_SECTORS, sector_tab maps it to planes
-    int32_t n_planes, reserved4;  // planes of the field (= n_sectors)
+    int32_t n_planes;             // planes of the field (= n_sectors)
+    uint32_t net_table_lo;        // network drivers (ftgp_set_net): the low half of the NetDev table's device address, 0 until the first setter call (net_table())
     int32_t contact_reach;        // chessboard reach (pixels) of the wall-contact window; `nearbits` is the wall set dilated by it
     // step-kernel launch shape and LDS layout (byte offsets, all 16-B aligned)
     int32_t cars_per_block, waves_per_block, eighth, win_floats;   // win_floats: floats per LDS scan row: (eighth % 4) + (n_rays - 2*eighth) + 1, padded to 4
     int32_t off_params, off_veh, off_path, off_ray, off_cars, off_frame, off_steps, off_scan, off_list, off_pool, off_k1, off_cover, lds_bytes, cover_kmax;
     int32_t off_mmask, mmask_stride;      // multi-car envs: [2][cars_per_block][mmask_stride] bytes, which env-mates a ray group can see (mate_masks)
     int32_t bubble_wrap;          // custom.py:1041-1055: the four wheel softeners collide with the walls
-    int32_t n_cu, pad_c;          // compute units of the device (sweep_priority)
+    int32_t n_cu;                 // compute units of the device (sweep_priority)
+    uint32_t net_table_hi;        // ... and its high half (two words that were spare: the block's layout is what it was)
     float edge_margin, pad_d;     // pixels: a LiDAR centre at least this far from every image edge has all its ray origins on the image (frame_write)
     // FTGP_LIDAR_FAKELIDAR (raycast.py:5-21 inside the step loop): the distance transform, the binary64 fan and the world size of the map
     const double* edt;            // [height][width] exact Euclidean distance to the nearest wall pixel (0 on walls), pixels; null in RANGEFINDER mode
@@ -163,6 +166,23 @@ struct DynArgs {
     const double* rows;               // [n_cars][FTGP_DYN_DOUBLES] or null
     const uint8_t* env_mask;          // [n_envs] or null = all envs
 };
+
+// Network drivers (ftgp_set_net): FTGP_MAX_NETS records in HBM, allocated by the first setter call; the parameter blocks carry the
+// table's address in two spare words (net_table_lo / _hi), as with the dynamics table.  A record is the description as the kernel reads
+// it (scalar loads) and the address of the slot's parameters in the LIBRARY's layout: per layer the weights transposed and padded,
+// Wt[n_in][ld] with ld = n_out rounded up to 64 (the padding is zeros), then b[ld] -- lane j of a wave owns neurons j and j + 64, and the
+// wave's load of row k is one or two coalesced 256-byte segments that every car shares through L2.
+struct alignas(16) NetDev {
+    int32_t defined, pool, beam_first, n_beams, use_state, n_layers, hidden_act, out_act;
+    int32_t width[FTGP_NET_MAX_LAYERS + 1];       // width[0] = n_in, width[l + 1] = outputs of layer l
+    int32_t w_off[FTGP_NET_MAX_LAYERS], b_off[FTGP_NET_MAX_LAYERS];      // float offsets of Wt and b of layer l in params
+    int32_t n_floats, pad0, pad1;                 // floats of the slot's buffer in the library's layout
+    float max_range, inv_max_range, out_scale[2], out_offset[2];
+    const float* params;
+};
+static_assert(sizeof(NetDev) == 128, "NetDev layout");
+template <class PP> __host__ __device__ inline const NetDev* net_table(PP p) { return reinterpret_cast<const NetDev*>(((uint64_t)p->net_table_hi << 32) | (uint64_t)p->net_table_lo); }
+__host__ __device__ inline bool is_net_policy(int policy) { return policy >= FTGP_POLICY_NET0 && policy <= FTGP_POLICY_NET3; }
 
 // ---------------------------------------------------------------------------------------------
 // Specified polynomials (DESIGN.md "arithmetic rules"): Taylor series in Horner form on x*x.

@@ -1434,6 +1434,115 @@ __device__ __forceinline__ void policy_apply(const DeviceParams& P, const Driver
     }
 }
 
+// The network driver (include/ftgp.h "Network drivers"; the element operations: ftgp_net.h) of one car by one wave, lane = neuron:
+//   inputs   input i lives in lane i % 64, register i / 64 (four registers: FTGP_NET_MAX_INPUTS = 256).  A lane forms the beams it owns
+//            from the car's scan window in LDS -- pool reads and a running minimum each -- and the lanes that own a state input take
+//            it from the car's record.
+//   layer    lane j accumulates neurons j and j + 64 (FTGP_NET_MAX_HIDDEN = 128): acc = b[j], then for k ascending one fmaf with
+//            x[k], which reaches all lanes as a scalar (v_readlane with a wave-uniform k), and Wt[k][j]: the wave's load of row k is one
+//            coalesced segment per 64 neurons, shared by every car through L2.  The rows are independent of the accumulators, so the
+//            unrolled loop has the loads of the rows ahead in flight under the fma chain, which is sequential by specification.
+//   outputs  become the next layer's inputs in place: registers 0 and 1.
+// No LDS beyond the window, no per-car state.  `win` is the address at which sample j of the car's scan sits when j is added.
+typedef const __attribute__((address_space(4))) NetDev* ScalarNet;
+// rows [0, n) of one register's worth of inputs (n <= 64), FTGP_NET_AHEAD weights per lane at a time: the loads of the next rows are
+// issued before the fma chain of the rows at hand (sixteen more in flight spill under the step kernel's 64 VGPRs)
+#define FTGP_NET_AHEAD 6
+template <bool WIDE>
+__device__ __forceinline__ void net_rows(const float* __restrict__ row, int ld, int n, float xr, float& a0, float& a1)
+{
+    constexpr int U = WIDE ? FTGP_NET_AHEAD / 2 : FTGP_NET_AHEAD;
+    float w0[U], w1[U];
+    auto fetch = [&](float* d0, float* d1, int k) {
+        #pragma unroll
+        for (int u = 0; u < U; ++u) { d0[u] = row[(size_t)(k + u) * ld]; if (WIDE) d1[u] = row[(size_t)(k + u) * ld + FTGP_WAVE]; }
+    };
+    auto chain = [&](const float* s0, const float* s1, int k) {
+        #pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float xk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xr), k + u));
+            a0 = fmaf(s0[u], xk, a0);
+            if (WIDE) a1 = fmaf(s1[u], xk, a1);
+        }
+    };
+    int k = 0;
+    if (n >= U) {
+        fetch(w0, w1, 0);
+        for (; k + 2 * U <= n; k += U) {
+            float v0[U], v1[U];
+            fetch(v0, v1, k + U);
+            chain(w0, w1, k);
+            #pragma unroll
+            for (int u = 0; u < U; ++u) { w0[u] = v0[u]; if (WIDE) w1[u] = v1[u]; }
+        }
+        chain(w0, w1, k);
+        k += U;
+    }
+    for (; k < n; ++k) {
+        const float xk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xr), k));
+        a0 = fmaf(row[(size_t)k * ld], xk, a0);
+        if (WIDE) a1 = fmaf(row[(size_t)k * ld + FTGP_WAVE], xk, a1);
+    }
+}
+__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st)
+{
+    uint64_t ta = (uint64_t)(table + slot); asm volatile("" : "+s"(ta));
+    const ScalarNet N = (ScalarNet)ta;
+    const int lane = lane_here();
+    const int pool = N->pool, n_beams = N->n_beams;
+    const float M = N->max_range, inv = N->inv_max_range;
+    float x[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    {
+        const float* __restrict__ mine = win + (N->beam_first + lane) * pool;
+        #pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r * FTGP_WAVE < n_beams && r * FTGP_WAVE + lane < n_beams) x[r] = ftgp_net_beam(mine + r * FTGP_WAVE * pool, pool, M, inv);
+    }
+    if (N->use_state) {
+        #pragma unroll
+        for (int q = 0; q < FTGP_NET_STATE_INPUTS; ++q) {
+            const float v = ftgp_net_state(q, st->qw, st->qz, st->vx, st->vy, st->wz, st->u_speed, st->u_steer);
+            const int i = n_beams + q;
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) if ((i >> 6) == r && lane == (i & (FTGP_WAVE - 1))) x[r] = v;
+        }
+    }
+    const float* __restrict__ params = uniform_ptr(N->params);
+    const int n_layers = N->n_layers;
+    for (int l = 0; l < n_layers; ++l) {
+        const int n_in = N->width[l], n_out = N->width[l + 1];
+        const int ld = (n_out + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
+        const float* __restrict__ W = params + N->w_off[l] + lane;
+        const float* __restrict__ B = params + N->b_off[l] + lane;
+        float a0 = B[0], a1 = 0.0f;
+        if (ld > FTGP_WAVE) {
+            a1 = B[FTGP_WAVE];
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) if (r * FTGP_WAVE < n_in) net_rows<true>(W + (size_t)r * FTGP_WAVE * ld, ld, min(FTGP_WAVE, n_in - r * FTGP_WAVE), x[r], a0, a1);
+        } else {
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) if (r * FTGP_WAVE < n_in) net_rows<false>(W + (size_t)r * FTGP_WAVE * ld, ld, min(FTGP_WAVE, n_in - r * FTGP_WAVE), x[r], a0, a1);
+        }
+        const int act = l + 1 < n_layers ? N->hidden_act : N->out_act;
+        x[0] = ftgp_net_act(act, a0); x[1] = 0.0f; x[2] = 0.0f; x[3] = 0.0f;
+        if (ld > FTGP_WAVE) x[1] = ftgp_net_act(act, a1);
+    }
+    const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 0)), y1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 1));
+    const float scale[2] = { N->out_scale[0], N->out_scale[1] }, offset[2] = { N->out_offset[0], N->out_offset[1] };
+    double us, ut;
+    ftgp_net_controls(y0, y1, scale, offset, &us, &ut);
+    if (lane == 0) { st->u_speed = us; st->u_steer = ut; }
+}
+// the driver FTGP_POLICY_NET0 + slot of one car: a finished car gets the null driver before the network is looked at
+__device__ __forceinline__ void policy_apply_net(const NetDev* table, int slot, const float* scan, int eighth, CarCore* st)
+{
+    if (st->finished) {
+        if (lane_id() == 0) { st->u_speed = 0.0; st->u_steer = 0.0; }
+        return;
+    }
+    policy_net(table, slot, scan + scan_window_first(eighth) - eighth, st);
+}
+
 // =============================================================================================
 // End-of-launch metrics record (FTGP_METRIC_DOUBLES; the record ftgp_metrics_kernel computes from the state in HBM), folded into
 // the step kernel so that a launch needs no second kernel and no second synchronisation: every workgroup reduces its own cars
@@ -1602,7 +1711,10 @@ __device__ __forceinline__ void stage16(void* dst, const void* src, int bytes)
 // DYN: launches with the table of per-car dynamics on (ftgp_set_dynamics) -- their own instantiations once more, MULTI x ROSTER x TRACKS with
 // FAKE = false: the workgroup stages its cars' records into LDS behind the layout, at lds_bytes (the launch asks for cars_per_block records
 // more), and dynamics_lanes() reads them.  With DYN = false the code is exactly what it was.
-template <bool MULTI, bool FAKE, bool ROSTER, bool TRACKS, bool DYN = false>
+// NET: launches whose policy, roster or device-io slot table names a network driver (FTGP_POLICY_NET0 ..., ftgp_set_net) -- ROSTER form
+// only, FAKE = false, MULTI x TRACKS x DYN: `policy` may then be a network's number (every car) or FTGP_POLICY_PER_CAR with networks
+// among the slots; policy_net() is one more case of K5.  With NET = false the code is exactly what it was.
+template <bool MULTI, bool FAKE, bool ROSTER, bool TRACKS, bool DYN = false, bool NET = false>
 __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(const DeviceParams* __restrict__ Pg, int policy, int n_steps, int metrics_slot)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -1647,7 +1759,8 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
     const int ci0 = TRACKS ? wg_first : FTGP_DIAG_WG_GROUP((int)blockIdx.x) * cpb;
     const int ncars_here = TRACKS ? wg_cars : min(cpb, sgpr(P0.n_cars) - ci0);
     const bool second_half = (((int)blockIdx.x / max(1, sgpr(P0.n_cu))) & 1) != 0;      // see sweep_priority(): workgroups b and b + n_cu share a CU in the first dispatch wave
-    const bool need_scan = (policy == FTGP_POLICY_NIDC || policy == FTGP_POLICY_FAST || (ROSTER && policy == FTGP_POLICY_PER_CAR));
+    // (a NET launch's policy is a network's number or FTGP_POLICY_PER_CAR: its drivers read the scan)
+    const bool need_scan = NET ? true : (policy == FTGP_POLICY_NIDC || policy == FTGP_POLICY_FAST || (ROSTER && policy == FTGP_POLICY_PER_CAR));
     {
     const DeviceParams& P = P0;
     const Lds L = lds_view(off, lds);
@@ -1712,7 +1825,14 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
             // the driver -> dynamics chain is the latency-critical path of a step and a small share of its instructions: let it issue first
             if (FTGP_DIAG_PRIO) __builtin_amdgcn_s_setprio(3);
             for (int c = wave; c < ncars_here; c += nwaves) {
-                if (ROSTER && policy == FTGP_POLICY_PER_CAR) {
+                if constexpr (NET) {      // the launch's driver, or some slot's, is a network: the slot's driver, networks among them
+                    const int pol = policy == FTGP_POLICY_PER_CAR ? G->car_policy[c] : policy;
+                    if (is_net_policy(pol)) policy_apply_net(net_table(G), pol - FTGP_POLICY_NET0, scan_prev + c * win_floats, G->eighth, L.cars + c);
+                    else if (policy == FTGP_POLICY_PER_CAR)
+                        policy_apply(P, driver_shape(G), pol, scan_prev + c * win_floats, L.cars + c, ci0 + c, L.steps[c], L.list + wave * FTGP_WAVE,
+                                     L.cover + (pol == FTGP_POLICY_FAST ? (G->stage_cover >> 2) : 0));
+                }
+                else if (ROSTER && policy == FTGP_POLICY_PER_CAR) {
                     // the roster's drivers: car slot c of the workgroup has its own (wave-uniform: a scalar load); both cover tables are staged
                     const int pol = G->car_policy[c];
                     policy_apply(P, driver_shape(G), pol, scan_prev + c * win_floats, L.cars + c, ci0 + c, L.steps[c], L.list + wave * FTGP_WAVE,
@@ -1793,6 +1913,14 @@ template __global__ void ftgp_step_kernel<false, false, false, true, true>(const
 template __global__ void ftgp_step_kernel<true, false, false, true, true>(const DeviceParams*, int, int, int);
 template __global__ void ftgp_step_kernel<false, false, true, true, true>(const DeviceParams*, int, int, int);
 template __global__ void ftgp_step_kernel<true, false, true, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, false, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, false, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, true, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, true, false, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, false, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, false, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<false, false, true, true, true, true>(const DeviceParams*, int, int, int);
+template __global__ void ftgp_step_kernel<true, false, true, true, true, true>(const DeviceParams*, int, int, int);
 
 // K5 alone: one wave per car evaluates the driver on the scan stored in P.ranges (ftgp_policy_eval).
 __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int policy, double* __restrict__ ctrl_out)
@@ -1813,11 +1941,28 @@ __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int po
         reinterpret_cast<uint32_t*>(st)[lane] = reinterpret_cast<const uint32_t*>(static_cast<const CarCore*>(&P.cars[ci]))[lane];
     wave_lds_sync();
     const int pol = policy == FTGP_POLICY_PER_CAR ? P.car_policy[ci % P.cars_per_env] : policy;
-    policy_apply(P, driver_shape(&P), pol, scan, st, ci, P.steps[ci / P.cars_per_env], list, P.cover_thr + (pol == FTGP_POLICY_FAST ? P.cover_kmax + 1 : 0));
+    if (is_net_policy(pol)) policy_apply_net(net_table(&P), pol - FTGP_POLICY_NET0, scan, P.eighth, st);
+    else policy_apply(P, driver_shape(&P), pol, scan, st, ci, P.steps[ci / P.cars_per_env], list, P.cover_thr + (pol == FTGP_POLICY_FAST ? P.cover_kmax + 1 : 0));
     wave_lds_sync();
     if (lane == 0) {
         P.cars[ci].u_speed = st->u_speed; P.cars[ci].u_steer = st->u_steer; P.cars[ci].last_steer = st->last_steer;
         if (ctrl_out) { ctrl_out[2 * ci] = st->u_speed; ctrl_out[2 * ci + 1] = st->u_steer; }
+    }
+}
+
+// ftgp_set_net_device: the parameters of a slot from the caller's layout (per layer W[n_out][n_in], then b[n_out]) into the library's
+// (NetDev: Wt[n_in][ld], then b[ld]); one thread per parameter, the padding stays the zeros ftgp_set_net wrote.  n = the caller's count.
+__global__ void ftgp_net_params_kernel(NetDev N, const float* __restrict__ src, float* __restrict__ dst, int n)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = src[i];
+    for (int l = 0; l < N.n_layers; ++l) {
+        const int n_in = N.width[l], n_out = N.width[l + 1], ld = (n_out + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
+        if (i < n_in * n_out) { dst[N.w_off[l] + (i % n_in) * ld + i / n_in] = v; return; }
+        i -= n_in * n_out;
+        if (i < n_out) { dst[N.b_off[l] + i] = v; return; }
+        i -= n_out;
     }
 }
 

@@ -1,0 +1,87 @@
+// ftgp_net.h -- the network driver (include/ftgp.h: ftgp_set_net): the element operations of one evaluation, shared by the HIP kernels
+// and by the host harness (tools/net_check.cpp compiles exactly these functions for the CPU; tests/net_model.py restates the header's
+// text in numpy and the two are compared bit for bit).
+//
+// Every operation is binary32 with one rounding, written out one by one; the library is compiled with -ffp-contract=off, and fmaf is
+// written where a fused multiply-add is specified.  Comparisons are written as comparisons (no fminf / fmaxf): what a NaN does is then
+// part of the text.  The state inputs are binary64, rounded once.
+// (This file is not among the hashed kernel sources -- tools/evidence.py and bench.py keep one list --: after a change here alone,
+// rebuild with __graft_entry__.build(force=True).)
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include "../../include/ftgp.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+#ifndef FTGP_HD
+#if defined(__HIPCC__)
+#define FTGP_HD __host__ __device__ __forceinline__
+#else
+#define FTGP_HD static inline
+#endif
+#endif
+
+// ---- scan input ----
+// a range as it enters a beam's minimum: no hit (< 0) = M, a hit = min(r, M)
+FTGP_HD float ftgp_net_ray(float r, float M) { return r < 0.0f ? M : (r < M ? r : M); }
+// the running minimum: the first of equal values stays
+FTGP_HD float ftgp_net_min(float m, float v) { return v < m ? v : m; }
+// the beam over `pool` consecutive ranges, scaled by inv = float32(1) / float32(M)
+FTGP_HD float ftgp_net_beam(const float* r, int pool, float M, float inv)
+{
+    float m = ftgp_net_ray(r[0], M);
+    for (int p = 1; p < pool; ++p) m = ftgp_net_min(m, ftgp_net_ray(r[p], M));
+    return m * inv;
+}
+
+// ---- state inputs: entries 0 - 4 of the state row (ftgp_state_device), binary64 rounded once ----
+FTGP_HD float ftgp_net_state(int i, double qw, double qz, double vx, double vy, double wz, double u_speed, double u_steer)
+{
+    const double c = qw * qw - qz * qz, s = 2.0 * (qw * qz);
+    switch (i) {
+    case 0: return (float)(vx * c + vy * s);
+    case 1: return (float)(vy * c - vx * s);
+    case 2: return (float)wz;
+    case 3: return (float)u_speed;
+    default: return (float)u_steer;
+    }
+}
+
+// ---- activations ----
+FTGP_HD float ftgp_net_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }      // a NaN stays a NaN
+FTGP_HD float ftgp_net_relu(float a) { return a > 0.0f ? a : 0.0f; }                                       // a NaN gives 0
+// Lambert's continued fraction of tanh, twelve levels, from the inside out
+FTGP_HD float ftgp_net_tanh(float a)
+{
+    const float x = ftgp_net_clamp(a, -9.0f, 9.0f);
+    const float x2 = x * x;
+    float d = 25.0f;
+    for (int k = 11; k >= 0; --k) d = (float)(2 * k + 1) + x2 / d;
+    return ftgp_net_clamp(x / d, -1.0f, 1.0f);
+}
+FTGP_HD float ftgp_net_act(int act, float a)
+{
+    return act == FTGP_ACT_TANH ? ftgp_net_tanh(a) : act == FTGP_ACT_RELU ? ftgp_net_relu(a) : a;
+}
+
+// ---- controls: the output map and its guard ----
+FTGP_HD void ftgp_net_controls(float y0, float y1, const float* scale, const float* offset, double* u_speed, double* u_steer)
+{
+    const float a = fmaf(y0, scale[0], offset[0]), b = fmaf(y1, scale[1], offset[1]);
+    const bool ok = (a - a == 0.0f) && (b - b == 0.0f);          // both finite
+    *u_speed = ok ? (double)a : 0.0;
+    *u_steer = ok ? (double)b : 0.0;
+}
+
+// ---- shapes: what ftgp_set_net checks, and the sizes that follow from a description ----
+FTGP_HD int ftgp_net_inputs(const FtgpNetDesc* d) { return d->n_beams + (d->use_state ? FTGP_NET_STATE_INPUTS : 0); }
+// number of binary32 parameters in the caller's layout: per layer W[n_out][n_in], then b[n_out]
+FTGP_HD size_t ftgp_net_param_count(const FtgpNetDesc* d)
+{
+    size_t n = 0;
+    int n_in = ftgp_net_inputs(d);
+    for (int l = 0; l < d->n_layers; ++l) { n += (size_t)d->width[l] * (size_t)n_in + (size_t)d->width[l]; n_in = d->width[l]; }
+    return n;
+}

@@ -1,0 +1,107 @@
+"""Network drivers: a trained MLP as a device policy (include/ftgp.h "Network drivers").
+
+A ``NetSpec`` is everything ``ftgp_set_net`` takes: which beams of the scan the network reads, whether the five state inputs follow,
+the layers in torch's ``nn.Linear`` layout, the two activations and the output map.  ``from_torch`` freezes an ``nn.Sequential`` of
+``Linear`` / ``ReLU`` / ``Tanh`` / ``Identity`` into one; ``save`` / ``load`` keep it as an ``.npz``.
+
+The library evaluates the network in binary32 with a fixed order of operations and its own TANH (a continued fraction, within 2.7e-7
+of ``tanh``): a network trained with torch's ``tanh`` runs with activations that differ in the seventh digit.
+"""
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import capi
+
+
+@dataclass
+class NetSpec:
+    layers: list                      # [(W float32 [n_out, n_in], b float32 [n_out]), ...]
+    pool: int
+    max_range: float
+    beam_first: int
+    n_beams: int
+    use_state: bool = False
+    hidden_act: str = "tanh"
+    out_act: str = "tanh"
+    out_scale: tuple = (1.0, 1.0)
+    out_offset: tuple = (0.0, 0.0)
+    _flat: np.ndarray = field(default=None, repr=False, compare=False)
+
+    def __post_init__(self):
+        self.layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in self.layers]
+        self.out_scale = tuple(float(x) for x in self.out_scale)
+        self.out_offset = tuple(float(x) for x in self.out_offset)
+        _, self._flat = capi.net_desc(self.layers, **self.input_fields())      # every check that needs no handle
+
+    def input_fields(self) -> dict:
+        return dict(pool=self.pool, max_range=self.max_range, beam_first=self.beam_first, n_beams=self.n_beams, use_state=self.use_state,
+                    hidden_act=self.hidden_act, out_act=self.out_act, out_scale=self.out_scale, out_offset=self.out_offset)
+
+    @property
+    def n_in(self) -> int:
+        return self.n_beams + (capi.NET_STATE_INPUTS if self.use_state else 0)
+
+    @property
+    def widths(self) -> tuple:
+        """(n_in, outputs of layer 0, ...): two specs of equal shape can replace one another through ftgp_set_net_device."""
+        return (self.n_in,) + tuple(W.shape[0] for W, _ in self.layers)
+
+    def shape_key(self) -> tuple:
+        d = self.input_fields()
+        return (self.widths,) + tuple(d[k] for k in sorted(d))
+
+    def flat_params(self) -> np.ndarray:
+        """float32, ftgp_set_net's layout: per layer W[n_out][n_in], then b[n_out]."""
+        return self._flat.copy()
+
+    def check_window(self, n_rays: int):
+        capi.check_net_window(n_rays, self.pool, self.beam_first, self.n_beams)
+
+    def save(self, path):
+        arrays = {}
+        for l, (W, b) in enumerate(self.layers):
+            arrays[f"W{l}"], arrays[f"b{l}"] = W, b
+        np.savez(path, n_layers=len(self.layers), pool=self.pool, max_range=np.float32(self.max_range), beam_first=self.beam_first,
+                 n_beams=self.n_beams, use_state=int(self.use_state), hidden_act=self.hidden_act, out_act=self.out_act,
+                 out_scale=np.asarray(self.out_scale, dtype=np.float32), out_offset=np.asarray(self.out_offset, dtype=np.float32), **arrays)
+
+
+def load(path) -> NetSpec:
+    with np.load(path, allow_pickle=False) as z:
+        layers = [(z[f"W{l}"], z[f"b{l}"]) for l in range(int(z["n_layers"]))]
+        return NetSpec(layers, pool=int(z["pool"]), max_range=float(z["max_range"]), beam_first=int(z["beam_first"]), n_beams=int(z["n_beams"]),
+                       use_state=bool(int(z["use_state"])), hidden_act=str(z["hidden_act"]), out_act=str(z["out_act"]),
+                       out_scale=tuple(z["out_scale"]), out_offset=tuple(z["out_offset"]))
+
+
+def from_torch(module, **input_fields) -> NetSpec:
+    """Freeze ``nn.Sequential(Linear, act, Linear, act, ..., Linear[, act])`` with act in ReLU / Tanh / Identity.  Every hidden layer
+    must use the same activation; a Linear without one behind it has the identity.  ``input_fields``: pool, max_range, beam_first,
+    n_beams and optionally use_state, out_scale, out_offset.  Anything else in the module is refused."""
+    import torch.nn as nn
+    if not isinstance(module, nn.Sequential):
+        raise TypeError(f"from_torch takes an nn.Sequential of Linear / ReLU / Tanh / Identity, got {type(module).__name__}")
+    for k in ("hidden_act", "out_act"):
+        if k in input_fields:
+            raise TypeError(f"{k} is read from the module")
+    names = {nn.ReLU: "relu", nn.Tanh: "tanh", nn.Identity: "identity"}
+    layers, acts = [], []
+    for i, m in enumerate(module):
+        if isinstance(m, nn.Linear):
+            if m.bias is None:
+                raise ValueError(f"module {i}: a Linear without bias is not supported (give it a zero bias)")
+            layers.append((m.weight.detach().cpu().numpy().astype(np.float32), m.bias.detach().cpu().numpy().astype(np.float32)))
+            acts.append("identity")
+        elif type(m) in names:
+            if not layers or acts[-1] != "identity":
+                raise ValueError(f"module {i}: {type(m).__name__} must follow a Linear, one activation per layer")
+            acts[-1] = names[type(m)]
+        else:
+            raise TypeError(f"module {i}: {type(m).__name__} is not supported: Linear, ReLU, Tanh and Identity only")
+    if not layers:
+        raise ValueError("the module has no Linear layer")
+    hidden = set(acts[:-1])
+    if len(hidden) > 1:
+        raise ValueError(f"every hidden layer must use the same activation, got {acts[:-1]}")
+    return NetSpec(layers, hidden_act=hidden.pop() if hidden else "tanh", out_act=acts[-1], **input_fields)

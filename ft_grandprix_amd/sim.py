@@ -168,8 +168,9 @@ class Simulator:
         states = []
         for e in range(self.n_envs):
             for i, car in enumerate(self.cars):
-                path = resolve_driver_path(car["driver"])
-                states.append(VehicleState(id=e * self.cars_per_env + i, offset=(i + 5) * 2, driver=load_driver(path),
+                # ("net": the network driver of slot 0 -- set_net() --, which exists on the device only: step() gives it the null driver)
+                path = "net" if car["driver"] == "net" else resolve_driver_path(car["driver"])
+                states.append(VehicleState(id=e * self.cars_per_env + i, offset=(i + 5) * 2, driver=LobotomyDriver() if path == "net" else load_driver(path),
                                            label=car.get("name", f"car #{i}"), driver_path=path))
         self.vehicle_states = states
         self.steps = 0
@@ -237,16 +238,25 @@ class Simulator:
     # the reference's bundled drivers, restated on the device (K5): roster module path -> device policy
     BUNDLED = {"ft_grandprix.nidc": "nidc", "ft_grandprix.fast": "fast", "ft_grandprix.lobotomy": "lobotomy"}
 
+    def set_net(self, spec, slot: int = 0):
+        """Put a network (net.NetSpec, e.g. net.load("file.npz")) into slot ``slot``: rollout("net") runs it for every car, and
+        rollout("roster") gives it to the roster entries whose "driver" is "net"."""
+        spec.check_window(self.n_rays)
+        self.env.set_net(slot, spec.layers, **spec.input_fields())
+        self.net_slot = slot
+
     def roster_policies(self) -> Optional[List[str]]:
         """The device policy of every roster entry, or None when some entry is not one of the reference's bundled drivers
         (``ft_grandprix.nidc`` / ``.fast`` / ``.lobotomy``, as module path or file:// string, custom.py:1097-1104)."""
-        names = [self.BUNDLED.get(resolve_driver_path(car["driver"]) or "") for car in self.cars]
+        names = [f"net{getattr(self, 'net_slot', 0)}" if car["driver"] == "net" else self.BUNDLED.get(resolve_driver_path(car["driver"]) or "") for car in self.cars]
         return None if any(n is None for n in names) else names
 
     def rollout(self, policy: Optional[str], n_steps: int):
         """n_steps on the device in ONE launch: with one of the on-device drivers ("nidc", "fast", "lobotomy", "random") for every
         car, or -- policy "roster" / None -- with every car's own bundled driver as the roster names them (template/cars/cars.json:
         nidc, fast, nidc).  The race state -- laps, lap times, finished, winners -- is the same as after n_steps single steps."""
+        if policy == "net":
+            policy = f"net{getattr(self, 'net_slot', 0)}"
         if policy in (None, "roster", "per_car"):
             names = self.roster_policies()
             if names is None:
@@ -285,12 +295,19 @@ def main(argv=None):
     ap.add_argument("--rays", type=int, default=90, help="rangefinders per car (custom.py:1158 uses 90)")
     ap.add_argument("--envs", type=int, default=1, help="independent copies of the world (every copy runs the whole roster)")
     ap.add_argument("--lap-target", type=int, default=10)
-    ap.add_argument("--device-policy", default=None, choices=("nidc", "fast", "lobotomy", "random", "roster"),
+    ap.add_argument("--device-policy", default=None, choices=("nidc", "fast", "lobotomy", "random", "roster", "net"),
                     help="run the whole loop on the device (ONE launch) instead of calling the roster's Python drivers: with this built-in driver "
-                         "for every car, or -- roster -- with each car's own, when the roster names only the reference's bundled drivers")
+                         "for every car, or -- roster -- with each car's own, when the roster names only the reference's bundled drivers "
+                         "and \"net\"; net: the network of --net for every car")
+    ap.add_argument("--net", default=None, help="a network saved by ft_grandprix_amd.net.NetSpec.save (.npz): --device-policy net runs it for every "
+                                                "car, --device-policy roster for the roster entries whose \"driver\" is \"net\"")
     ap.add_argument("--lidar", default="rangefinder", choices=("rangefinder", "fakelidar"))
     ap.add_argument("--report", type=int, default=0, help="print the standings every this many steps")
     args = ap.parse_args(argv)
+    if args.device_policy == "net" and not args.net:
+        ap.error("--device-policy net needs --net file.npz")
+    if args.net and args.device_policy not in ("net", "roster"):
+        ap.error("--net goes with --device-policy net or roster")
     sys.path.insert(0, os.getcwd())                      # roster entries are module paths relative to the working directory, as in the reference
     roster = Simulator.load_roster(args.cars) if args.cars else [{"driver": args.driver, "name": "car #0"}]
     track = load_track_from_template(args.template_dir, args.track) if args.template_dir else load_track(args.track)
@@ -304,6 +321,9 @@ def main(argv=None):
                   f"lap times {[round(t, 3) for t in vs.times[-3:]]}{fin}")
 
     try:
+        if args.net:
+            from . import net
+            sim.set_net(net.load(args.net))
         if args.device_policy:
             sim.rollout(args.device_policy, args.steps)
         else:

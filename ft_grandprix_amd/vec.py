@@ -22,7 +22,7 @@ from . import capi
 from .track import Track, load_track
 
 RUNTIME_ERROR = "libftgp.so was loaded before torch in this process; start a fresh process"
-ROSTER_NAMES = ("agent", "host", "lobotomy", "nidc", "fast", "random")
+ROSTER_NAMES = ("agent", "host", "lobotomy", "nidc", "fast", "random", "net0", "net1", "net2", "net3")
 
 
 def mapped_hip_runtimes(maps_text: str | None = None) -> dict:
@@ -137,6 +137,17 @@ class DeviceVecEnv:
     [n_envs, cars_per_env, 8], for privileged critics (None while the table is off).  ``set_dynamics(rows, env_mask=None)`` takes rows
     of the caller's choosing, for curricula.  Not with lidar_mode "fakelidar".
 
+    Network drivers (ftgp_set_net / ftgp_set_net_device): the roster names ``"net0"`` .. ``"net3"`` are slots driven by a frozen MLP
+    that the library evaluates inside the step kernel, e.g. ``roster=["agent", "net0", "fast"]``: an earlier policy as an opponent in
+    the same world.  ``nets`` = a dict from a slot (0 .. 3) to a ``net.NetSpec`` or an ``nn.Sequential`` with the input fields as
+    ``(module, dict(pool=..., max_range=..., beam_first=..., n_beams=...))``; ``set_net(slot, spec_or_module, **input_fields)`` defines
+    or replaces one later: the first time, and whenever the shape changes, through the host setter (it synchronises); afterwards, for
+    the same shape, through the device setter on torch's current stream.  A roster slot whose network is not defined makes ``step``
+    raise.  Action repeat: a network slot is evaluated at every physics step, like the bundled drivers, while an agent's action is
+    held for ``action_repeat`` steps -- with ``action_repeat > 1`` a net slot is a different driver from the same network run as an
+    agent.  What a net slot sees is what an agent is given with ``scan_pool`` / ``scan_max_range`` / ``state=True`` equal to the
+    network's description: the beams ``beam_first .. beam_first + n_beams - 1`` of ``obs`` and entries 0 - 4 of ``state``.
+
     Saved states (ftgp_save_envs_device / ftgp_load_envs_device): ``save_state(env_mask=None)`` returns an ``EnvSnapshot`` of the envs'
     whole state -- poses, velocities, steering joint, wheel spins, controls, race and lap fields, step and episode counters, dynamics,
     scans; ``load_state(snap, src=None)`` puts env e back to row ``src[e]`` (negative = keep) and evaluates ``obs`` and the optional
@@ -158,7 +169,7 @@ class DeviceVecEnv:
                  car_contact_penalty: float = 0.0, random_start: bool = False, start_points=(0, 100), start_margin=None,
                  start_lateral: float = 0.0, start_yaw_jitter: float = 0.0, shuffle_grid: bool = False, track_frame: bool = False,
                  lookahead: int = 0, lookahead_stride: int = 1, dense_progress: bool = False, rivals: bool = False, n_rivals: int = 0,
-                 place_reward: float = 0.0, randomize_dynamics=None, dynamics_seed: int = 0, **env_kwargs):
+                 place_reward: float = 0.0, randomize_dynamics=None, dynamics_seed: int = 0, nets=None, **env_kwargs):
         n_envs, n_rays, cars_per_env = int(n_envs), int(n_rays), int(cars_per_env)
         if n_envs < 1 or n_rays < 1 or not 1 <= cars_per_env <= 8:
             raise ValueError("n_envs >= 1, n_rays >= 1 and 1 <= cars_per_env <= 8")
@@ -231,6 +242,14 @@ class DeviceVecEnv:
         roster = ["agent" if r == "host" else r for r in roster]
         if "agent" not in roster:
             raise ValueError('the roster needs at least one "agent" slot')
+        net_specs = {}
+        if nets is not None:
+            if not isinstance(nets, dict):
+                raise ValueError("nets: a dict from a slot (0 .. 3) to a NetSpec, or to (nn.Sequential, dict of input fields)")
+            if env_kwargs.get("lidar_mode") in ("fakelidar", capi.LIDAR_FAKELIDAR):
+                raise ValueError("network drivers are not available with lidar_mode 'fakelidar'")
+            for slot, what in nets.items():
+                net_specs[self._check_net_slot(slot)] = self._net_spec(what, n_rays)
         if "lidar_mode" in env_kwargs and env_kwargs["lidar_mode"] not in capi.LIDAR_BY_NAME and env_kwargs["lidar_mode"] not in (0, 1):
             raise ValueError(f"unknown lidar_mode {env_kwargs['lidar_mode']!r}")
         multi = isinstance(track, (list, tuple))
@@ -280,6 +299,9 @@ class DeviceVecEnv:
             self.start_rule = dict(first_point=first_point, n_points=n_points, margin=float(start_margin), lateral_frac=start_lateral,
                                    yaw_tan=math.tan(0.5 * start_yaw_jitter), shuffle_grid=bool(shuffle_grid))
             self.env.set_spawn_rule(True, **self.start_rule)
+        self._nets = {}                              # slot -> (shape key, the device tensor of the parameters last handed over)
+        for slot, spec in net_specs.items():
+            self.set_net(slot, spec)
         z = dict(device=self.device)
         self.track_index = torch.from_numpy(self.env.track_of_env.astype("int64")).to(self.device)
         self.obs = torch.zeros((n_envs, self.n_agents, self.n_beams), dtype=torch.float32, **z)
@@ -373,6 +395,61 @@ class DeviceVecEnv:
             env_mask = env_mask.contiguous()
         self._dyn_keep = env_mask
         self._apply_dynamics(rows, env_mask)
+
+    @staticmethod
+    def _check_net_slot(slot) -> int:
+        if isinstance(slot, str) and slot in ROSTER_NAMES[-capi.MAX_NETS:]:
+            slot = int(slot[3:])
+        if not isinstance(slot, int) or not 0 <= slot < capi.MAX_NETS:
+            raise ValueError(f"network slot: 0 .. {capi.MAX_NETS - 1} (or 'net0' .. 'net3'), got {slot!r}")
+        return slot
+
+    @staticmethod
+    def _net_spec(what, n_rays: int, **input_fields):
+        """A NetSpec from a NetSpec, an nn.Sequential (with input fields) or (nn.Sequential, dict), checked against n_rays: everything
+        ftgp_set_net checks, without a handle."""
+        from . import net
+        if isinstance(what, tuple) and len(what) == 2 and isinstance(what[1], dict):
+            what, input_fields = what[0], {**what[1], **input_fields}
+        if isinstance(what, net.NetSpec):
+            if input_fields:
+                raise ValueError("a NetSpec carries its input fields")
+            spec = what
+        else:
+            spec = net.from_torch(what, **input_fields)
+        spec.check_window(n_rays)
+        return spec
+
+    def set_net(self, slot, spec_or_module, **input_fields):
+        """Define or replace network slot ``slot`` (0 .. 3 or its roster name).  The first time, and when the shape differs from the
+        slot's, through ftgp_set_net (synchronises); for the same shape through ftgp_set_net_device on torch's current stream: the
+        self-play loop that refreshes a frozen opponent.  ``None`` clears the slot."""
+        slot = self._check_net_slot(slot)
+        if spec_or_module is None:
+            self.env.set_net(slot, None)
+            self._nets.pop(slot, None)
+            return
+        spec = self._net_spec(spec_or_module, self.n_rays, **input_fields)
+        key = spec.shape_key()
+        if slot in self._nets and self._nets[slot][0] == key:
+            with torch.cuda.device(self.device):
+                params = torch.from_numpy(spec.flat_params()).to(self.device, non_blocking=False)
+                self.env.set_net_device(slot, params.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            self._nets[slot] = (key, params)         # (kept until the next one: the library reads it in stream order)
+            return
+        self.env.set_net(slot, spec.layers, **spec.input_fields())
+        self._nets[slot] = (key, None)
+
+    def set_net_params(self, slot, params):
+        """New parameters for a defined slot from a float32 tensor on the env's device in ftgp_set_net's flat layout (``NetSpec.flat_params``),
+        on torch's current stream, without leaving the device."""
+        slot = self._check_net_slot(slot)
+        if slot not in self._nets:
+            raise ValueError(f"network slot {slot} is not defined: set_net first")
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous():
+            raise ValueError(f"params: a contiguous float32 tensor on {self.device}")
+        self.env.set_net_device(slot, params.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        self._nets[slot] = (self._nets[slot][0], params)
 
     def reset(self):
         """Reset every env (synchronous ftgp_reset, which follows the start rule); obs = the scans right after a reset, all zeros

@@ -40,6 +40,7 @@ extern "C" {
 #define FTGP_POLICY_FAST      3  /* ft_grandprix/fast.py:118-139 : same + straight-line boost */
 #define FTGP_POLICY_RANDOM    4  /* counter-based RNG keyed (seed, car, step): speed~U(0,3), steer~U(-1,1) */
 #define FTGP_POLICY_PER_CAR   5  /* every car slot of an env its own driver, as set by ftgp_set_car_policies (the roster) */
+/* 6 .. 9: FTGP_POLICY_NET0 .. FTGP_POLICY_NET3, the network drivers (ftgp_set_net, below) */
 
 #define FTGP_VEHICLE_MUSHR     0
 #define FTGP_VEHICLE_TRICYCLE  1
@@ -227,6 +228,7 @@ int ftgp_rollout(FtgpEnv *env, int policy, int n_steps);
  * car slot k of every env; ftgp_rollout(FTGP_POLICY_PER_CAR, n) and ftgp_policy_eval(FTGP_POLICY_PER_CAR, ...) then evaluate each
  * car with its own driver.  Replaces the per-vehicle Driver() instances the reference builds from the roster's "driver" strings
  * and calls one by one (custom.py:1097-1104,1398-1411; template/cars/cars.json: nidc, fast, nidc).  Survives ftgp_reset.
+ * FTGP_POLICY_NET0 .. NET3 (ftgp_set_net) are accepted too, here and in the roster of ftgp_device_io_config: a slot driven by a network.
  */
 int ftgp_set_car_policies(FtgpEnv *env, const int32_t *policies);
 
@@ -713,6 +715,85 @@ int ftgp_get_env_state_rejected(FtgpEnv *env, int64_t *rejected);
  * device function the device step pools with -- a row equals to the bit what a step's obs holds for those scans.  Ordered on `stream`
  * like ftgp_state_device (only enqueues).  After ftgp_device_io_config only (FTGP_ERR_STATE before it). */
 int ftgp_obs_device(FtgpEnv *env, void *stream, float *obs);
+
+/* ---- Network drivers: a trained MLP as a device policy (no reference counterpart) ------------------------------------------------------
+ * A handle carries up to FTGP_MAX_NETS networks, slots 0 .. 3.  Slot s is the device policy FTGP_POLICY_NET0 + s, usable wherever a
+ * bundled driver is: ftgp_rollout, ftgp_set_car_policies, ftgp_policy_eval, the roster of ftgp_device_io_config.  Using a policy
+ * whose slot is not defined is FTGP_ERR_STATE at the call that would launch it.  The driver is evaluated inside the step kernel's
+ * driver phase, at every physics step, on the scan of the previous step -- what nidc and fast see.  It keeps no per-car state:
+ * last_steer is untouched and the env-state record is what it was.
+ *
+ * Everything below is binary32 with one rounding per written operation unless it says binary64; fmaf(a, b, c) is the fused a*b + c
+ * with one rounding; nothing else is contracted.  Comparisons with a NaN are false.
+ *
+ * Scan input.  s(r) = r < 0 ? M : (r < M ? r : M) for a range r of the car's ftgp_get_lidar row, M = max_range.  Beam b covers rays
+ * [b*pool, (b+1)*pool): m = s(r_0); then for p = 1 .. pool-1 in this order, m = s(r_p) if s(r_p) < m; beam = m * inv with
+ * inv = float32(1) / float32(M), divided once on the host.  For ranges without a NaN this is beam b of the device step's signals with
+ * scan_pool = pool and scan_max_range = M.  Inputs 0 .. n_beams-1 are beams beam_first .. beam_first + n_beams - 1.
+ * Restriction: the device drivers see only the scan window [eighth, n_rays - eighth), eighth = (int)(n_rays / 8.0) -- the samples
+ * nidc and fast keep (nidc.py:18-19), 811 at 1080 rays -- so a network's beams must lie inside it: the rear quarter of the scan is
+ * not an input.  At 1080 rays and pool 10 that allows beams 14 .. 93.
+ *
+ * State input (use_state = 1): inputs n_beams .. n_beams + 4 are entries 0 - 4 of the state row (v_long, v_lat, wz, u_speed,
+ * u_steer), computed exactly as ftgp_state_device documents them -- binary64, each rounded once to binary32 -- from the car's record
+ * at the moment the driver runs: the velocities after the previous step and the controls then in force.
+ *
+ * Layers.  n_layers in 1 .. FTGP_NET_MAX_LAYERS; n_in = n_beams + 5*use_state, 1 <= n_in <= FTGP_NET_MAX_INPUTS; width[l] is the number
+ * of outputs of layer l: hidden widths 1 .. FTGP_NET_MAX_HIDDEN, width[n_layers - 1] exactly 2; entries of width[] past n_layers are 0.
+ * Parameters: binary32 in torch's nn.Linear layout -- per layer W[n_out][n_in], then b[n_out] -- the layers one after the other in one
+ * flat buffer.  Neuron j of a layer with input x: acc = b[j]; for k = 0 .. n_in-1 ascending, acc = fmaf(W[j][k], x[k], acc); output =
+ * act(acc), hidden_act for every layer but the last, out_act for the last.
+ *   FTGP_ACT_IDENTITY  acc
+ *   FTGP_ACT_RELU      acc > 0 ? acc : 0
+ *   FTGP_ACT_TANH      with clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v) (a NaN stays a NaN):
+ *                      x = clamp(acc, -9, 9); x2 = x*x; d = 25; for k = 11, 10, .., 0: d = (float)(2k+1) + x2 / d; y = x / d;
+ *                      output = clamp(y, -1, 1).  Lambert's continued fraction, twelve levels, evaluated from the inside out: within
+ *                      2.7e-7 of tanh on [-12, 12]; before the last clamp it overshoots 1 by 2.4e-7.  / is IEEE division.
+ *
+ * Controls.  With (y0, y1) the outputs of the last layer: a = fmaf(y0, out_scale[0], out_offset[0]), b = fmaf(y1, out_scale[1],
+ * out_offset[1]); u_speed = (double)a, u_steer = (double)b; if a or b is not finite, both are 0: a diverged network acts as the
+ * null driver and cannot put a NaN into a car's state.  A finished car gets (0, 0) before the network is looked at (custom.py:1446).
+ *
+ * ftgp_set_net (host buffers; may synchronise) defines or replaces slot `slot`; desc = NULL clears it.  Everything is checked before
+ * anything changes; FTGP_ERR_ARG names the field: a slot outside 0 .. 3; pool < 1 or not dividing n_rays; max_range not finite or
+ * <= 0; n_beams < 1, beam_first < 0, beam_first*pool < eighth or (beam_first + n_beams)*pool > n_rays - eighth (the window rule);
+ * use_state not 0 or 1; n_layers, n_in or a width out of range, the last width != 2; an unknown activation; out_scale / out_offset
+ * not finite; reserved != 0; params = NULL.  FTGP_ERR_STATE on a FTGP_LIDAR_FAKELIDAR handle, as ftgp_set_dynamics.
+ * ftgp_set_net_device replaces the parameters of a slot that is defined, from device memory on the handle's device in the same
+ * layout; it only enqueues, ordered on `stream` like ftgp_set_dynamics_device (the handle's stream waits for `stream`, and `stream`
+ * for the work) -- the self-play loop that refreshes a frozen opponent from the training network without leaving the device.  A host
+ * pointer or a buffer too small is FTGP_ERR_ARG before anything is enqueued; a slot not defined is FTGP_ERR_STATE.
+ * ftgp_get_net (host, synchronous): the description and the parameters in force, in the caller's layout, ftgp_net_param_count floats
+ * = the sum over the layers of n_out*n_in + n_out; either pointer may be NULL; FTGP_ERR_STATE for a slot not defined.
+ * ftgp_reset, the auto-reset of a device step, ftgp_device_io_config and the ftgp_device_io_* setters, ftgp_set_spawn_rule,
+ * ftgp_set_dynamics and the env-state calls leave the networks alone.  Launches that name no network run exactly the kernels they
+ * ran before any network was set. */
+#define FTGP_POLICY_NET0      6  /* the network of slot 0 (ftgp_set_net) ... */
+#define FTGP_POLICY_NET1      7
+#define FTGP_POLICY_NET2      8
+#define FTGP_POLICY_NET3      9  /* ... of slot 3 */
+#define FTGP_MAX_NETS 4
+#define FTGP_NET_MAX_LAYERS 4
+#define FTGP_NET_MAX_INPUTS 256
+#define FTGP_NET_MAX_HIDDEN 128
+#define FTGP_NET_STATE_INPUTS 5
+#define FTGP_ACT_IDENTITY 0
+#define FTGP_ACT_RELU     1
+#define FTGP_ACT_TANH     2
+typedef struct FtgpNetDesc {
+    int32_t pool;                 /* rays per beam, >= 1 and a divisor of n_rays */
+    float   max_range;            /* M > 0, finite */
+    int32_t beam_first, n_beams;  /* the beams taken, inside the drivers' scan window */
+    int32_t use_state;            /* 0 or 1: five state inputs behind the beams */
+    int32_t n_layers;             /* 1 .. FTGP_NET_MAX_LAYERS */
+    int32_t width[FTGP_NET_MAX_LAYERS];   /* outputs per layer; width[n_layers - 1] = 2, the rest 0 */
+    int32_t hidden_act, out_act;  /* FTGP_ACT_* */
+    float   out_scale[2], out_offset[2];  /* the output map, finite */
+    int32_t reserved;             /* 0 */
+} FtgpNetDesc;
+int ftgp_set_net(FtgpEnv *env, int slot, const FtgpNetDesc *desc, const float *params);
+int ftgp_set_net_device(FtgpEnv *env, void *stream, int slot, const float *params);
+int ftgp_get_net(FtgpEnv *env, int slot, FtgpNetDesc *desc_out, float *params_out);
 
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 

@@ -6,6 +6,7 @@
     python3 tools/evidence.py publish DST FILE...      copy into DST (profiles/roundN) -- REFUSES a file whose stamp (or, for a
                                                        .json, whose "kernel_source_sha") is not the current sources' hash
     python3 tools/evidence.py meta [lib.so]            resource usage of the step kernels from the code object's metadata
+    python3 tools/evidence.py meta-net [lib.so]        ... of the instantiations of launches that name a network driver
 """
 import hashlib, json, os, re, shutil, subprocess, sys, tempfile, time
 
@@ -64,12 +65,13 @@ def publish(dst, files):
     return 1 if bad else 0
 
 
-def code_object_meta(lib=None, tracks=False, dynamics=False):
+def code_object_meta(lib=None, tracks=False, dynamics=False, net=False):
     """.vgpr_count / .sgpr_count / spills / scratch of every ftgp_step_kernel instantiation, from the gfx950 code object inside the
     library (rocprofv3's VGPR_Count / LDS_Block_Size columns read 32 / 0 for a 63-register kernel with 73 KB of dynamic LDS).
     tracks=False: the six one-track instantiations <MULTI, FAKE, ROSTER[, false]>, keyed by their three flags; tracks=True: the six of
     multi-track handles, keyed "ftgp_step_kernel<MULTI, FAKE, ROSTER, true>".  dynamics=True: the eight instantiations of launches with
-    the per-car dynamics table on (ftgp_set_dynamics) instead, both kinds of handle, keyed by all five flags."""
+    the per-car dynamics table on (ftgp_set_dynamics) instead, both kinds of handle, keyed by all five flags.  net=True: the eight
+    instantiations of launches that name a network driver (ftgp_set_net) instead, keyed by all six flags."""
     lib = lib or os.path.join(ROOT, "ft_grandprix_amd", "lib", "libftgp.so")
     out = {}
     with tempfile.TemporaryDirectory() as td:
@@ -82,12 +84,17 @@ def code_object_meta(lib=None, tracks=False, dynamics=False):
         name = re.search(r"\.name:\s+(\S+)", block)
         if not name or "ftgp_step_kernel" not in name.group(1):
             continue
-        flags = re.search(r"ftgp_step_kernelILb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?(?:Lb(\d)E)?", name.group(1))
-        if flags and (flags.group(5) == "1") != dynamics:
+        flags = re.search(r"ftgp_step_kernelILb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?(?:Lb(\d)E)?(?:Lb(\d)E)?", name.group(1))
+        if flags and (flags.group(6) == "1") != net:
             continue
-        if flags and not dynamics and (flags.group(4) == "1") != tracks:
+        if flags and net:
+            flags_all = ", ".join("true" if f == "1" else "false" for f in flags.groups())
+        if flags and not net and (flags.group(5) == "1") != dynamics:
             continue
-        key = ("ftgp_step_kernel<%s>" % ", ".join("true" if f == "1" else "false" for f in flags.groups()) if flags and dynamics else
+        if flags and not net and not dynamics and (flags.group(4) == "1") != tracks:
+            continue
+        key = ("ftgp_step_kernel<%s>" % flags_all if flags and net else
+               "ftgp_step_kernel<%s>" % ", ".join("true" if f == "1" else "false" for f in flags.groups()[:5]) if flags and dynamics else
                "ftgp_step_kernel<%s, %s, %s" % tuple("true" if f == "1" else "false" for f in flags.groups()[:3]) + (", true>" if tracks else ">")
                if flags else name.group(1))
         get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
@@ -108,5 +115,7 @@ if __name__ == "__main__":
         raise SystemExit(publish(sys.argv[2], sys.argv[3:]))
     elif cmd == "meta":
         print(json.dumps(code_object_meta(sys.argv[2] if len(sys.argv) > 2 else None), indent=1))
+    elif cmd == "meta-net":
+        print(json.dumps(code_object_meta(sys.argv[2] if len(sys.argv) > 2 else None, net=True), indent=1))
     else:
         raise SystemExit(__doc__)

@@ -1,0 +1,61 @@
+// Host harness: evaluates a whole network driver with the SHIPPED element operations (csrc/ftgp_net.h) in the written order of
+// include/ftgp.h "Network drivers" on the CPU, prints the controls and writes them as raw binary, for tests/test_net_driver.py to
+// compare bit for bit with the numpy model of the header's text (tests/net_model.py).
+// Build: c++ -O2 -ffp-contract=off -std=c++17 tools/net_check.cpp -o /tmp/net_check        (no HIP needed)
+// Input:  int32 n_rays, n_cars, pool, beam_first, n_beams, use_state, n_layers, width[4], hidden_act, out_act, n_params;
+//         float max_range, out_scale[2], out_offset[2]; float params[n_params] (ftgp_set_net's layout);
+//         float ranges[n_cars][n_rays]; double record[n_cars][7] = qw, qz, vx, vy, wz, u_speed, u_steer.
+// Output: double ctrl[n_cars][2].
+#include "../ft_grandprix_amd/csrc/ftgp_net.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+
+int main(int argc, char** argv)
+{
+    if (argc != 3) { fprintf(stderr, "usage: net_check in.bin out.bin\n"); return 2; }
+    FILE* f = fopen(argv[1], "rb"); if (!f) { perror("open"); return 2; }
+    int32_t h[14]; float g[5];
+    if (fread(h, 4, 14, f) != 14 || fread(g, 4, 5, f) != 5) return 2;
+    const int n_rays = h[0], n_cars = h[1];
+    FtgpNetDesc d{};
+    d.pool = h[2]; d.beam_first = h[3]; d.n_beams = h[4]; d.use_state = h[5]; d.n_layers = h[6];
+    for (int l = 0; l < FTGP_NET_MAX_LAYERS; ++l) d.width[l] = h[7 + l];
+    d.hidden_act = h[11]; d.out_act = h[12];
+    d.max_range = g[0]; d.out_scale[0] = g[1]; d.out_scale[1] = g[2]; d.out_offset[0] = g[3]; d.out_offset[1] = g[4];
+    const int eighth = (int)(n_rays / 8.0);
+    if (n_rays < 1 || n_cars < 1 || d.pool < 1 || n_rays % d.pool || d.n_beams < 1 || d.n_layers < 1 || d.n_layers > FTGP_NET_MAX_LAYERS ||
+        d.beam_first * d.pool < eighth || (d.beam_first + d.n_beams) * d.pool > n_rays - eighth || ftgp_net_inputs(&d) > FTGP_NET_MAX_INPUTS ||
+        (size_t)h[13] != ftgp_net_param_count(&d)) { fprintf(stderr, "bad description\n"); return 2; }
+    std::vector<float> params((size_t)h[13]), ranges((size_t)n_cars * n_rays);
+    std::vector<double> rec((size_t)n_cars * 7), ctrl((size_t)n_cars * 2);
+    if (fread(params.data(), 4, params.size(), f) != params.size() || fread(ranges.data(), 4, ranges.size(), f) != ranges.size() ||
+        fread(rec.data(), 8, rec.size(), f) != rec.size()) return 2;
+    fclose(f);
+    const float inv = 1.0f / d.max_range;
+    for (int c = 0; c < n_cars; ++c) {
+        float x[FTGP_NET_MAX_INPUTS], y[FTGP_NET_MAX_INPUTS];
+        for (int b = 0; b < d.n_beams; ++b) x[b] = ftgp_net_beam(&ranges[(size_t)c * n_rays + (size_t)(d.beam_first + b) * d.pool], d.pool, d.max_range, inv);
+        const double* r = &rec[(size_t)c * 7];
+        if (d.use_state) for (int q = 0; q < FTGP_NET_STATE_INPUTS; ++q) x[d.n_beams + q] = ftgp_net_state(q, r[0], r[1], r[2], r[3], r[4], r[5], r[6]);
+        int n_in = ftgp_net_inputs(&d);
+        const float* p = params.data();
+        for (int l = 0; l < d.n_layers; ++l) {
+            const int n_out = d.width[l], act = l + 1 < d.n_layers ? d.hidden_act : d.out_act;
+            const float* W = p; const float* B = p + (size_t)n_out * n_in;
+            for (int j = 0; j < n_out; ++j) {
+                float acc = B[j];
+                for (int k = 0; k < n_in; ++k) acc = fmaf(W[(size_t)j * n_in + k], x[k], acc);
+                y[j] = ftgp_net_act(act, acc);
+            }
+            for (int j = 0; j < n_out; ++j) x[j] = y[j];
+            p = B + n_out; n_in = n_out;
+        }
+        ftgp_net_controls(x[0], x[1], d.out_scale, d.out_offset, &ctrl[2 * c], &ctrl[2 * c + 1]);
+        printf("car %d: speed %a steer %a\n", c, ctrl[2 * c], ctrl[2 * c + 1]);
+    }
+    FILE* o = fopen(argv[2], "wb"); if (!o) { perror("open"); return 2; }
+    fwrite(ctrl.data(), 8, ctrl.size(), o);
+    fclose(o);
+    return 0;
+}

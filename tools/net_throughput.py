@@ -1,0 +1,100 @@
+"""What a network driver costs a step: rollout("net0") against rollout("fast") and rollout("lobotomy"), and against the device step
+with one agent whose network torch evaluates.
+
+    python tools/net_throughput.py [--envs 4096] [--rays 1080] [--steps 500] [--launches 5] [--track track] [--calls 500] [--rows rollout,agent]
+
+rollout rows: one launch of --steps steps per measurement, --launches of them after one warm-up launch; env-steps/s from the wall clock
+around the launch and its synchronisation, and the step kernel's own time from ftgp_last_kernel_ms.  The network is a random
+85 -> 64 -> 64 -> 2 tanh MLP on beams 14 .. 93 of pool 10 and the five state inputs (at another --rays: the beams of the scan window).
+agent row: DeviceVecEnv(roster=["agent"], scan_pool, scan_max_range, state=True), the same network as an nn.Sequential evaluated by
+torch before every call, --calls calls of one step; per-call time from HIP events on torch's stream.  One JSON line per row.  Run it in
+a fresh process: torch is imported first (ft_grandprix_amd/vec.py).  Under `rocprofv3 --kernel-trace --stats -- python
+tools/net_throughput.py --rows rollout` the per-kernel times come out of the stats file.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402  (before libftgp.so)
+import numpy as np  # noqa: E402
+
+from ft_grandprix_amd import capi, net  # noqa: E402
+from ft_grandprix_amd.track import load_track  # noqa: E402
+
+
+def make_module(n_in):
+    torch.manual_seed(0)
+    return torch.nn.Sequential(torch.nn.Linear(n_in, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, 2), torch.nn.Tanh())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--rays", type=int, default=1080)
+    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--launches", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=500)
+    ap.add_argument("--pool", type=int, default=10)
+    ap.add_argument("--track", default="track")
+    ap.add_argument("--rows", default="rollout,agent")
+    a = ap.parse_args()
+    eighth = int(a.rays / 8.0)
+    first = -(-eighth // a.pool)
+    n_beams = (a.rays - eighth) // a.pool - first
+    fields = dict(pool=a.pool, max_range=10.0, beam_first=first, n_beams=n_beams, use_state=True, out_scale=(2.0, 0.6), out_offset=(2.5, 0.0))
+    module = make_module(n_beams + 5)
+    spec = net.from_torch(module, **fields)
+    track = load_track(a.track)
+    rows = a.rows.split(",")
+    if "rollout" in rows:
+        lib = capi.load()
+        for policy in ("lobotomy", "fast", "net0"):
+            with capi.Env(lib, track, n_envs=a.envs, n_rays=a.rays, spawn_mode=1, seed=7) as g:
+                if policy == "net0":
+                    g.set_net(0, spec.layers, **spec.input_fields())
+                g.rollout(policy, a.steps)
+                g.steps()
+                wall, kern = [], []
+                for _ in range(a.launches):
+                    t0 = time.perf_counter()
+                    g.rollout(policy, a.steps)
+                    kern.append(g.last_kernel_ms())
+                    wall.append(time.perf_counter() - t0)
+                print(json.dumps({"row": f"rollout {policy}", "envs": a.envs, "rays": a.rays, "steps": a.steps, "kernel": g.kernel_name(),
+                                  "env_steps_per_s": a.envs * a.steps / float(np.median(wall)), "kernel_ms_median": float(np.median(kern)),
+                                  "kernel_us_per_step": 1e3 * float(np.median(kern)) / a.steps, "off_track": int(g.progress()[:, 5].sum())}), flush=True)
+    if "agent" in rows:
+        from ft_grandprix_amd.vec import DeviceVecEnv
+        venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, roster=["agent"], scan_pool=a.pool, scan_max_range=10.0, state=True, spawn_mode=1, seed=7)
+        dev = venv.device
+        policy = module.to(dev)
+        scale, offset = torch.tensor(fields["out_scale"], device=dev), torch.tensor(fields["out_offset"], device=dev)
+        obs, state = venv.reset(), venv.state
+
+        @torch.no_grad()
+        def act():
+            x = torch.cat([obs[:, 0, first:first + n_beams], state[:, 0, :5]], dim=1)
+            return (policy(x) * scale + offset)[:, None, :].contiguous()
+        for _ in range(20):
+            venv.step(act())
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        e0.record()
+        for _ in range(a.calls):
+            venv.step(act())
+        e1.record()
+        torch.cuda.synchronize(dev)
+        wall = time.perf_counter() - t0
+        print(json.dumps({"row": "device step, torch evaluates the network", "envs": a.envs, "rays": a.rays, "calls": a.calls,
+                          "env_steps_per_s": a.envs * a.calls / wall, "us_per_call_events": 1e3 * e0.elapsed_time(e1) / a.calls}), flush=True)
+        venv.close()
+
+
+if __name__ == "__main__":
+    main()
