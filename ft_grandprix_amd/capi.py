@@ -109,6 +109,7 @@ API_SYMBOLS = (
     "set_dynamics", "set_dynamics_device", "get_dynamics",
     "env_state_bytes", "save_envs_device", "load_envs_device", "get_env_state_rejected", "obs_device",
     "set_net", "set_net_device", "get_net",
+    "collect_device",
 )
 
 
@@ -165,6 +166,35 @@ class FtgpNetDesc(C.Structure):
                 ("use_state", C.c_int32), ("n_layers", C.c_int32), ("width", C.c_int32 * NET_MAX_LAYERS),
                 ("hidden_act", C.c_int32), ("out_act", C.c_int32), ("out_scale", C.c_float * 2), ("out_offset", C.c_float * 2),
                 ("reserved", C.c_int32)]
+
+
+class FtgpCollect(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("slot", C.c_int32), ("n_decisions", C.c_int32), ("std", C.c_float * 2), ("lo", C.c_float * 2),
+                ("hi", C.c_float * 2), ("noise", C.c_void_p), ("inputs", C.c_void_p), ("mean", C.c_void_p), ("action", C.c_void_p),
+                ("reward", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("next_inputs", C.c_void_p),
+                ("reset_dynamics", C.c_void_p), ("reserved", C.c_int32)]
+
+
+def collect_args(n_decisions, slot=0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e30, 1e30))) -> "FtgpCollect":
+    """An FtgpCollect with the scalar fields set and every check of ftgp_collect_device that needs no handle (ValueError): T >= 1, a
+    slot in 0 .. 3, std >= 0 and finite, a finite clip with lo <= hi per component.  The buffers are left NULL."""
+    if isinstance(n_decisions, bool) or not isinstance(n_decisions, (int, np.integer)) or not 1 <= int(n_decisions) < 2 ** 31:
+        raise ValueError(f"n_decisions: an integer >= 1, got {n_decisions!r}")
+    if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < MAX_NETS:
+        raise ValueError(f"network slot: 0 .. {MAX_NETS - 1}, got {slot!r}")
+    try:
+        sd = np.asarray(std, dtype=np.float32)
+        lim = np.asarray(clip, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"std: two numbers, clip: ((lo, hi), (lo, hi)); got {std!r}, {clip!r}") from None
+    if sd.shape != (2,) or not (np.isfinite(sd).all() and (sd >= 0).all()):
+        raise ValueError(f"std: two finite numbers >= 0 (speed, steering_angle), got {std!r}")
+    if lim.shape != (2, 2) or not np.isfinite(lim).all() or not (lim[:, 0] <= lim[:, 1]).all():
+        raise ValueError(f"clip: ((lo, hi), (lo, hi)), finite with lo <= hi, got {clip!r}")
+    c = FtgpCollect(slot=int(slot), n_decisions=int(n_decisions))
+    for k in range(2):
+        c.std[k], c.lo[k], c.hi[k] = float(sd[k]), float(lim[k, 0]), float(lim[k, 1])
+    return c
 
 
 def net_desc(layers, *, pool, max_range, beam_first, n_beams, use_state=False, hidden_act="tanh", out_act="tanh",
@@ -334,6 +364,7 @@ class CLib:
             "set_net": (i32, [vp, i32, C.POINTER(FtgpNetDesc), dp]),
             "set_net_device": (i32, [vp, vp, i32, vp]),
             "get_net": (i32, [vp, i32, C.POINTER(FtgpNetDesc), dp]),
+            "collect_device": (i32, [vp, C.POINTER(FtgpCollect)]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -653,6 +684,21 @@ class Env:
         flat = np.empty(net_param_count(d), dtype=np.float32)
         self._call("get_net", int(slot), C.byref(d), _ptr(flat))
         return d, net_layers(d, flat)
+
+    # -- collected rollouts (include/ftgp.h: ftgp_collect_device)
+    def collect_device(self, n_decisions: int, inputs: int, mean: int, action: int, reward: int, terminated: int, truncated: int, *,
+                       slot: int = 0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e30, 1e30)), noise: int = 0, next_inputs: int = 0,
+                       reset_dynamics: int = 0, stream: int = 0):
+        """One ftgp_collect_device call on integer device addresses (0 = NULL for the optional ``noise``, ``next_inputs`` and
+        ``reset_dynamics``), ordered on ``stream``; only enqueues.  ``n_decisions`` decisions of network slot ``slot`` for every
+        external car; the buffers hold ``n_decisions`` times the rows of one decision."""
+        c = collect_args(n_decisions, slot, std, clip)
+        c.stream = stream or None
+        for name, v in (("noise", noise), ("inputs", inputs), ("mean", mean), ("action", action), ("reward", reward),
+                        ("terminated", terminated), ("truncated", truncated), ("next_inputs", next_inputs),
+                        ("reset_dynamics", reset_dynamics)):
+            setattr(c, name, v or None)
+        self._call("collect_device", C.byref(c))
 
     # -- env states on the device (include/ftgp.h: ftgp_save_envs_device)
     def env_state_bytes(self) -> int:

@@ -181,6 +181,7 @@ struct FtgpEnv {
                                           // call like d_frame, allocated on first use
         DevBuf<int32_t> d_frame_c;        // [2][n_cars] the nearest points that go with d_frame_s (the rival rows' race progress)
         DevBuf<int32_t> d_place0;         // [n_cars] the places when the call began (place reward)
+        DevBuf<float> d_collect_obs;      // [n_cars][n_rays] ftgp_collect_device: where the obs rows of its device steps go (not part of the record); allocated on first use
         struct { const void* p; size_t bytes; } checked[32] = {};     // device buffers found valid (hipPointerGetAttributes), replaced round robin
         int checked_next = 0;
     } ds;
@@ -1137,11 +1138,12 @@ int ensure_dynamics(FtgpEnv* e)
 
 // ftgp_set_dynamics / ftgp_set_dynamics_device: ftgp_dynamics_kernel on the handle's stream; the first launch since the table was off
 // also gives every car the handle's own row
-int launch_dynamics(FtgpEnv* e, const double* rows, const uint8_t* env_mask)
+// (env_mask_or: with env_mask, an env is taken if either byte is set -- the terminated | truncated of a collected decision)
+int launch_dynamics(FtgpEnv* e, const double* rows, const uint8_t* env_mask, const uint8_t* env_mask_or = nullptr)
 {
     if (int rc = ensure_dynamics(e)) return rc;
     DynArgs A = e->dyn;
-    A.init = e->dyn_on ? 0 : 1; A.rows = rows; A.env_mask = env_mask;
+    A.init = e->dyn_on ? 0 : 1; A.rows = rows; A.env_mask = env_mask; A.env_mask_or = env_mask_or;
     hipLaunchKernelGGL(ftgp_dynamics_kernel, dim3((unsigned)((e->P.n_cars + 255) / 256)), dim3(256), 0, e->stream.get(), e->P, A);
     HIP_TRY(hipGetLastError());
     e->dyn_on = true;
@@ -1335,6 +1337,104 @@ int create(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_p
     if (int rc = upload(e.get(), pl, sw)) return rc;
     if (int rc = ftgp_reset(e.get(), nullptr)) return rc;
     *out = e.release();
+    return 0;
+}
+
+// One device step in two halves, shared by ftgp_step_device_rivals and ftgp_collect_device.  plan_device_step: every check of the call
+// and the kernels' argument blocks; nothing is enqueued.  enqueue_device_step: the launches of one call on the handle's stream, without
+// the fences to and from a caller's stream, with `between` run behind the steps' own kernels (launch_steps and the contact, frame and
+// rival rows) and in front of the finish kernel, where an env that ended is reset.
+struct DeviceStepPlan {
+    DeviceIoArgs A; DeviceSignalArgs S;
+    bool signals = false, dense = false, place = false, aligned = false;
+};
+
+int plan_device_step(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts,
+                     const FtgpDeviceStepFrame* frame, const FtgpDeviceStepRivals* rivals, DeviceStepPlan& plan)
+{
+    if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
+    FtgpEnv::DeviceStep& ds = e->ds;
+    if (!ds.ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
+    if (int rc = check_nets_defined(e, nets_named(e, FTGP_POLICY_PER_CAR, true))) return rc;      // (before anything is enqueued)
+    // the four optional kinds of rows: floats per row, the caller's two buffers and what a refusal calls them
+    struct Rows { const char* name; const char* final_name; size_t floats; float* out; float* final_out; };
+    const Rows st{ "state", "final_state", FTGP_STATE_FLOATS, extra ? extra->state : nullptr, extra ? extra->final_state : nullptr };
+    const Rows ct{ "contact", "final_contact", FTGP_CONTACT_FLOATS, contacts ? contacts->contact : nullptr, contacts ? contacts->final_contact : nullptr };
+    const Rows fr{ "frame", "final_frame", (size_t)(FTGP_FRAME_FIXED + 2 * ds.frame.n_ahead), frame ? frame->frame : nullptr, frame ? frame->final_frame : nullptr };
+    const Rows rv{ "rival", "final_rival", (size_t)(FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * ds.rivals.n_rivals), rivals ? rivals->rival : nullptr, rivals ? rivals->final_rival : nullptr };
+    if ((ct.out || ct.final_out) && !ds.con_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_contacts: contact buffers while contacts are off (ftgp_device_io_contacts)%s");
+    if ((fr.out || fr.final_out) && !ds.frame_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_frame: frame buffers while the frame is off (ftgp_device_io_frame)%s");
+    if ((rv.out || rv.final_out) && !ds.rivals_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_rivals: rival buffers while rivals are off (ftgp_device_io_rivals)%s");
+    HIP_TRY(hipSetDevice(e->device));
+    DeviceIoArgs& A = plan.A;
+    DeviceSignalArgs& S = plan.S;
+    A = ds.io;
+    S = ds.sig;
+    S.state = st.out; S.final_state = st.final_out;
+    plan.signals = !ds.sig_default || S.state || S.final_state || ds.con_on || ds.frame_on || ds.rivals_on;
+    const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
+    if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
+    if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
+    if (int rc = check_device_buffer(e, io->reward, sizeof(float) * rows, "reward")) return rc;
+    if (int rc = check_device_buffer(e, io->terminated, n_envs, "terminated")) return rc;
+    if (int rc = check_device_buffer(e, io->truncated, n_envs, "truncated")) return rc;
+    if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
+    for (const Rows* r : { &st, &ct, &fr, &rv }) {
+        if (r->out) if (int rc = check_device_buffer(e, r->out, sizeof(float) * r->floats * rows, r->name)) return rc;
+        if (r->final_out) if (int rc = check_device_buffer(e, r->final_out, sizeof(float) * r->floats * rows, r->final_name)) return rc;
+    }
+    plan.dense = ds.frame_on && ds.frame.dense_progress != 0;
+    if (ds.frame_on) {
+        S.frame_rows = ds.d_frame.get(); S.frame = fr.out; S.final_frame = fr.final_out;
+        S.frame_ahead = ds.frame.n_ahead; S.frame_stride = ds.frame.stride;
+        if (plan.dense) {
+            S.frame_s0 = ds.d_frame_s.get(); S.frame_s1 = ds.d_frame_s.get() + e->P.n_cars;
+            S.frame_flag0 = ds.d_frame_flag.get(); S.frame_flag1 = ds.d_frame_flag.get() + e->P.n_cars;
+        }
+    }
+    plan.place = ds.rivals_on && ds.rivals.place_weight != 0.0f;
+    if (ds.rivals_on) {
+        S.rival_rows = ds.d_rival.get(); S.rival = rv.out; S.final_rival = rv.final_out;
+        S.rival_n = ds.rivals.n_rivals;
+        if (plan.place) { S.place0 = ds.d_place0.get(); S.place_weight = ds.rivals.place_weight; }
+    }
+    if (ds.con_on) {
+        S.contact_rows = ds.d_contact.get(); S.contact = ct.out; S.final_contact = ct.final_out;
+        S.terminate_on_wall = ds.con.terminate_on_wall ? 1 : 0; S.terminate_on_car = ds.con.terminate_on_car ? 1 : 0;
+        S.wall_penalty = ds.con.wall_penalty; S.car_penalty = ds.con.car_penalty;
+    }
+    A.action = io->action; A.obs = io->obs; A.reward = io->reward; A.terminated = io->terminated; A.truncated = io->truncated; A.final_obs = io->final_obs;
+    A.vec4 = e->P.n_rays % 4 == 0 && (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
+    plan.aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
+    return 0;
+}
+
+template <class Between>
+int enqueue_device_step(FtgpEnv* e, const DeviceStepPlan& plan, Between between)
+{
+    FtgpEnv::DeviceStep& ds = e->ds;
+    const DeviceIoArgs& A = plan.A;
+    const unsigned car_blocks = (unsigned)((e->P.n_cars + 255) / 256);
+    hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
+    HIP_TRY(hipGetLastError());
+    if (plan.dense || plan.place) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 0, plan.place)) return rc;          // s0: the pose the call begins with
+    if (plan.place) if (int rc = launch_rivals(e, 0, nullptr, nullptr, 0, true)) return rc;      // p0: the places the call begins with
+    if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, ds.repeat, true)) return rc;
+    if (ds.con_on) if (int rc = launch_contacts(e, ds.d_contact.get(), nullptr)) return rc;
+    if (ds.frame_on) { if (int rc = launch_frame(e, ds.frame.n_ahead, ds.frame.stride, ds.d_frame.get(), nullptr, 1, ds.rivals_on)) return rc; }
+    else if (ds.rivals_on) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 1, true)) return rc;           // the rivals' own search
+    if (ds.rivals_on) if (int rc = launch_rivals(e, ds.rivals.n_rivals, ds.d_rival.get(), nullptr, 1)) return rc;
+    if (int rc = between()) return rc;
+    if (!plan.signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, e->rule);
+    else {
+        DeviceSignalArgs S = plan.S;
+        S.vec_out = plan.aligned && S.n_beams % 4 == 0;
+        if (S.path == FTGP_SIG_PATH_REGS && !plan.aligned) S.path = FTGP_SIG_PATH_STAGE;
+        hipLaunchKernelGGL(ftgp_io_finish_signals_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, S, e->rule);
+    }
+    HIP_TRY(hipGetLastError());
+    e->rows_valid = false;
+    if (A.auto_reset) e->launch_metrics_valid = false;     // the launch's record describes the state before the resets
     return 0;
 }
 
@@ -1635,79 +1735,86 @@ int ftgp_step_device_frame(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevic
 int ftgp_step_device_rivals(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepExtra* extra, const FtgpDeviceStepContacts* contacts,
                             const FtgpDeviceStepFrame* frame, const FtgpDeviceStepRivals* rivals)
 {
-    if (!e || !io) return fail(FTGP_ERR_ARG, "null argument%s");
-    FtgpEnv::DeviceStep& ds = e->ds;
-    if (!ds.ready) return fail(FTGP_ERR_STATE, "ftgp_step_device before ftgp_device_io_config%s");
-    if (int rc = check_nets_defined(e, nets_named(e, FTGP_POLICY_PER_CAR, true))) return rc;      // (before anything is enqueued)
-    // the four optional kinds of rows: floats per row, the caller's two buffers and what a refusal calls them
-    struct Rows { const char* name; const char* final_name; size_t floats; float* out; float* final_out; };
-    const Rows st{ "state", "final_state", FTGP_STATE_FLOATS, extra ? extra->state : nullptr, extra ? extra->final_state : nullptr };
-    const Rows ct{ "contact", "final_contact", FTGP_CONTACT_FLOATS, contacts ? contacts->contact : nullptr, contacts ? contacts->final_contact : nullptr };
-    const Rows fr{ "frame", "final_frame", (size_t)(FTGP_FRAME_FIXED + 2 * ds.frame.n_ahead), frame ? frame->frame : nullptr, frame ? frame->final_frame : nullptr };
-    const Rows rv{ "rival", "final_rival", (size_t)(FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * ds.rivals.n_rivals), rivals ? rivals->rival : nullptr, rivals ? rivals->final_rival : nullptr };
-    if ((ct.out || ct.final_out) && !ds.con_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_contacts: contact buffers while contacts are off (ftgp_device_io_contacts)%s");
-    if ((fr.out || fr.final_out) && !ds.frame_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_frame: frame buffers while the frame is off (ftgp_device_io_frame)%s");
-    if ((rv.out || rv.final_out) && !ds.rivals_on) return fail(FTGP_ERR_STATE, "ftgp_step_device_rivals: rival buffers while rivals are off (ftgp_device_io_rivals)%s");
-    HIP_TRY(hipSetDevice(e->device));
-    DeviceIoArgs A = ds.io;
-    DeviceSignalArgs S = ds.sig;
-    S.state = st.out; S.final_state = st.final_out;
-    const bool signals = !ds.sig_default || S.state || S.final_state || ds.con_on || ds.frame_on || ds.rivals_on;
-    const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
-    if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
-    if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
-    if (int rc = check_device_buffer(e, io->reward, sizeof(float) * rows, "reward")) return rc;
-    if (int rc = check_device_buffer(e, io->terminated, n_envs, "terminated")) return rc;
-    if (int rc = check_device_buffer(e, io->truncated, n_envs, "truncated")) return rc;
-    if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
-    for (const Rows* r : { &st, &ct, &fr, &rv }) {
-        if (r->out) if (int rc = check_device_buffer(e, r->out, sizeof(float) * r->floats * rows, r->name)) return rc;
-        if (r->final_out) if (int rc = check_device_buffer(e, r->final_out, sizeof(float) * r->floats * rows, r->final_name)) return rc;
-    }
-    const bool dense = ds.frame_on && ds.frame.dense_progress != 0;
-    if (ds.frame_on) {
-        S.frame_rows = ds.d_frame.get(); S.frame = fr.out; S.final_frame = fr.final_out;
-        S.frame_ahead = ds.frame.n_ahead; S.frame_stride = ds.frame.stride;
-        if (dense) {
-            S.frame_s0 = ds.d_frame_s.get(); S.frame_s1 = ds.d_frame_s.get() + e->P.n_cars;
-            S.frame_flag0 = ds.d_frame_flag.get(); S.frame_flag1 = ds.d_frame_flag.get() + e->P.n_cars;
-        }
-    }
-    const bool place = ds.rivals_on && ds.rivals.place_weight != 0.0f;
-    if (ds.rivals_on) {
-        S.rival_rows = ds.d_rival.get(); S.rival = rv.out; S.final_rival = rv.final_out;
-        S.rival_n = ds.rivals.n_rivals;
-        if (place) { S.place0 = ds.d_place0.get(); S.place_weight = ds.rivals.place_weight; }
-    }
-    if (ds.con_on) {
-        S.contact_rows = ds.d_contact.get(); S.contact = ct.out; S.final_contact = ct.final_out;
-        S.terminate_on_wall = ds.con.terminate_on_wall ? 1 : 0; S.terminate_on_car = ds.con.terminate_on_car ? 1 : 0;
-        S.wall_penalty = ds.con.wall_penalty; S.car_penalty = ds.con.car_penalty;
-    }
-    A.action = io->action; A.obs = io->obs; A.reward = io->reward; A.terminated = io->terminated; A.truncated = io->truncated; A.final_obs = io->final_obs;
-    A.vec4 = e->P.n_rays % 4 == 0 && (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
+    DeviceStepPlan plan;
+    if (int rc = plan_device_step(e, io, extra, contacts, frame, rivals, plan)) return rc;       // (before anything is enqueued)
     hipStream_t caller = (hipStream_t)io->stream;
     if (int rc = handle_waits_for_caller(e, caller)) return rc;
-    const unsigned car_blocks = (unsigned)((e->P.n_cars + 255) / 256);
-    hipLaunchKernelGGL(ftgp_io_ingest_kernel, dim3(car_blocks), dim3(256), 0, e->stream.get(), e->P, A);
+    if (int rc = enqueue_device_step(e, plan, [] { return 0; })) return rc;
+    return caller_waits_for_handle(e, caller);
+}
+
+// LDS of a workgroup of ftgp_collect_act_kernel: four waves, each the rays its network's beams cover and the car's record
+static size_t collect_act_lds(const NetDev& N) { return 4 * ((size_t)N.n_beams * (size_t)N.pool * sizeof(float) + sizeof(CarCore)); }
+
+// ftgp_collect_act_kernel on the handle's stream for the rows of one decision: inputs, mean and action -- or, with mean == null, the
+// inputs alone (next_inputs)
+static int launch_collect_act(FtgpEnv* e, const FtgpCollect& c, const float* noise, float* inputs, float* mean, float* action)
+{
+    CollectActArgs C{};
+    C.noise = noise; C.inputs = inputs; C.mean = mean; C.action = action;
+    for (int k = 0; k < 2; ++k) { C.std[k] = c.std[k]; C.lo[k] = c.lo[k]; C.hi[k] = c.hi[k]; }
+    C.slot = c.slot; C.n_ext = e->ds.io.n_ext; C.n_rows = e->P.n_envs * e->ds.io.n_ext;
+    for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) if (e->ds.io.ext_index[k] >= 0) C.ext_slot[e->ds.io.ext_index[k]] = k;
+    const size_t lds = collect_act_lds(e->nets[c.slot]);
+    void (*kernel)(DeviceParams, CollectActArgs) = mean ? ftgp_collect_act_kernel<true> : ftgp_collect_act_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((C.n_rows + 3) / 4)), dim3(256), lds, e->stream.get(), e->P, C);
     HIP_TRY(hipGetLastError());
-    if (dense || place) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 0, place)) return rc;          // s0: the pose the call begins with
-    if (place) if (int rc = launch_rivals(e, 0, nullptr, nullptr, 0, true)) return rc;      // p0: the places the call begins with
-    if (int rc = launch_steps(e, FTGP_POLICY_PER_CAR, ds.repeat, true)) return rc;
-    if (ds.con_on) if (int rc = launch_contacts(e, ds.d_contact.get(), nullptr)) return rc;
-    if (ds.frame_on) { if (int rc = launch_frame(e, ds.frame.n_ahead, ds.frame.stride, ds.d_frame.get(), nullptr, 1, ds.rivals_on)) return rc; }
-    else if (ds.rivals_on) if (int rc = launch_frame(e, 0, 1, nullptr, nullptr, 1, true)) return rc;           // the rivals' own search
-    if (ds.rivals_on) if (int rc = launch_rivals(e, ds.rivals.n_rivals, ds.d_rival.get(), nullptr, 1)) return rc;
-    if (!signals) hipLaunchKernelGGL(ftgp_io_finish_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, e->rule);
-    else {
-        const bool aligned = (uintptr_t)io->obs % 16 == 0 && (uintptr_t)io->final_obs % 16 == 0;
-        S.vec_out = aligned && S.n_beams % 4 == 0;
-        if (S.path == FTGP_SIG_PATH_REGS && !aligned) S.path = FTGP_SIG_PATH_STAGE;
-        hipLaunchKernelGGL(ftgp_io_finish_signals_kernel, dim3((unsigned)e->P.n_envs), dim3(FTGP_IO_THREADS), 0, e->stream.get(), e->P, A, S, e->rule);
+    return 0;
+}
+
+int ftgp_collect_device(FtgpEnv* e, const FtgpCollect* c)
+{
+    if (!e || !c) return fail(FTGP_ERR_ARG, "null argument%s");
+    FtgpEnv::DeviceStep& ds = e->ds;
+    if (!ds.ready) return fail(FTGP_ERR_STATE, "ftgp_collect_device before ftgp_device_io_config%s");
+    if (c->reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_collect_device: reserved must be 0%s");
+    if (c->slot < 0 || c->slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_collect_device: slot = %d outside 0 .. %d", c->slot, FTGP_MAX_NETS - 1);
+    if (!e->nets[c->slot].defined) return failf(FTGP_ERR_STATE, "ftgp_collect_device: network slot %d is not defined (ftgp_set_net)", c->slot);
+    if (c->n_decisions < 1) return failf(FTGP_ERR_ARG, "ftgp_collect_device: n_decisions = %d must be >= 1", c->n_decisions);
+    for (int k = 0; k < 2; ++k) {
+        if (!nonneg_finite(c->std[k])) return failf(FTGP_ERR_ARG, "ftgp_collect_device: std[%d] = %g must be >= 0 and finite", k, (double)c->std[k]);
+        if (!std::isfinite(c->lo[k])) return failf(FTGP_ERR_ARG, "ftgp_collect_device: lo[%d] is not finite", k);
+        if (!std::isfinite(c->hi[k])) return failf(FTGP_ERR_ARG, "ftgp_collect_device: hi[%d] is not finite", k);
+        if (!(c->lo[k] <= c->hi[k])) return failf(FTGP_ERR_ARG, "ftgp_collect_device: lo[%d] = %g above hi[%d] = %g", k, (double)c->lo[k], k, (double)c->hi[k]);
     }
-    HIP_TRY(hipGetLastError());
-    e->rows_valid = false;
-    if (A.auto_reset) e->launch_metrics_valid = false;     // the launch's record describes the state before the resets
+    // (a FTGP_LIDAR_FAKELIDAR handle, where ftgp_set_dynamics is FTGP_ERR_STATE, has no defined slot: ftgp_set_net refuses it)
+    if (c->reset_dynamics && !ds.io.auto_reset) return fail(FTGP_ERR_STATE, "ftgp_collect_device: reset_dynamics while auto_reset is off (ftgp_device_io_config)%s");
+    if (collect_act_lds(e->nets[c->slot]) > 64 * 1024)
+        return failf(FTGP_ERR_ARG, "ftgp_collect_device: slot %d: the %d rays of its beams (n_beams * pool) do not fit LDS four cars to a workgroup", c->slot, e->nets[c->slot].n_beams * e->nets[c->slot].pool);
+    HIP_TRY(hipSetDevice(e->device));
+    // every buffer at its full T-fold size, in size_t (a product that does not fit is a buffer too small)
+    const size_t T = (size_t)c->n_decisions, n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)ds.io.n_ext, n_in = (size_t)e->nets[c->slot].width[0];
+    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_collect_device: %s", m.c_str()); return rc; };
+    auto checked = [&](const void* p, size_t per_decision, const char* name) {
+        size_t bytes = 0;
+        if (__builtin_mul_overflow(T, per_decision, &bytes)) return failf(FTGP_ERR_ARG, "ftgp_collect_device: %s is smaller than the layout needs", name);
+        return check_device_buffer(e, p, bytes, name) ? refused(FTGP_ERR_ARG) : 0;
+    };
+    if (c->noise) if (int rc = checked(c->noise, sizeof(float) * 2 * rows, "noise")) return rc;
+    if (int rc = checked(c->inputs, sizeof(float) * n_in * rows, "inputs")) return rc;
+    if (int rc = checked(c->mean, sizeof(float) * 2 * rows, "mean")) return rc;
+    if (int rc = checked(c->action, sizeof(float) * 2 * rows, "action")) return rc;
+    if (int rc = checked(c->reward, sizeof(float) * rows, "reward")) return rc;
+    if (int rc = checked(c->terminated, n_envs, "terminated")) return rc;
+    if (int rc = checked(c->truncated, n_envs, "truncated")) return rc;
+    if (c->next_inputs) if (int rc = checked(c->next_inputs, sizeof(float) * n_in * rows, "next_inputs")) return rc;
+    if (c->reset_dynamics) if (int rc = checked(c->reset_dynamics, sizeof(double) * FTGP_DYN_DOUBLES * (size_t)e->P.n_cars, "reset_dynamics")) return rc;
+    // the obs rows of the device step are not part of the record: scratch of the handle's, at the widest row a signals setting gives
+    if (!ds.d_collect_obs) HIP_TRY(dev_alloc(ds.d_collect_obs, sizeof(float) * (size_t)e->P.n_cars * (size_t)e->P.n_rays));
+    const FtgpDeviceStep io{ c->stream, c->action, ds.d_collect_obs.get(), c->reward, c->terminated, c->truncated, nullptr };
+    DeviceStepPlan plan;
+    if (int rc = plan_device_step(e, &io, nullptr, nullptr, nullptr, nullptr, plan)) return rc;
+    if (c->reset_dynamics) if (int rc = ensure_dynamics(e)) return rc;
+    hipStream_t caller = (hipStream_t)c->stream;
+    if (int rc = handle_waits_for_caller(e, caller)) return rc;
+    for (size_t t = 0; t < T; ++t) {
+        float* action = c->action + t * rows * 2;
+        if (int rc = launch_collect_act(e, *c, c->noise ? c->noise + t * rows * 2 : nullptr, c->inputs + t * rows * n_in, c->mean + t * rows * 2, action)) return rc;
+        plan.A.action = action; plan.A.reward = c->reward + t * rows; plan.A.terminated = c->terminated + t * n_envs; plan.A.truncated = c->truncated + t * n_envs;
+        if (int rc = enqueue_device_step(e, plan, [&] { return c->next_inputs ? launch_collect_act(e, *c, nullptr, c->next_inputs + t * rows * n_in, nullptr, nullptr) : 0; })) return rc;
+        if (c->reset_dynamics)
+            if (int rc = launch_dynamics(e, c->reset_dynamics + t * (size_t)e->P.n_cars * FTGP_DYN_DOUBLES, plan.A.terminated, plan.A.truncated)) return rc;
+    }
     return caller_waits_for_handle(e, caller);
 }
 

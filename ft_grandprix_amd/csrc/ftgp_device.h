@@ -165,6 +165,7 @@ struct DynArgs {
     int32_t init, pad;                // init: the table is being turned on -- every car's record starts as the handle's own
     const double* rows;               // [n_cars][FTGP_DYN_DOUBLES] or null
     const uint8_t* env_mask;          // [n_envs] or null = all envs
+    const uint8_t* env_mask_or;       // [n_envs] or null: with env_mask, an env is taken if either byte is set (ftgp_collect_device: terminated | truncated)
 };
 
 // Network drivers (ftgp_set_net): FTGP_MAX_NETS records in HBM, allocated by the first setter call; the parameter blocks carry the

@@ -18,6 +18,7 @@
 //       The end-of-launch metrics record is part of the kernel (launch_metrics).
 //       TRACKS: multi-track handles (ftgp_create_tracks) -- each workgroup looks up its track and first car at entry, then stages and races that track.
 //   ftgp_policy_kernel    K5 alone (ftgp_policy_eval).
+//   ftgp_collect_act_kernel  the network of a slot for every external car, one wave each: inputs, mean and action of a collected decision.
 //   ftgp_reset_kernel     K4 reset / spawn (+ K3 at the spawn pose), one car per lane.
 //   ftgp_progress_kernel  K3 alone (after ftgp_set_pose), one car per lane.
 //   ftgp_fakelidar_kernel raycast.fakelidar restated, one ray per lane.
@@ -1484,14 +1485,13 @@ __device__ __forceinline__ void net_rows(const float* __restrict__ row, int ld, 
         if (WIDE) a1 = fmaf(row[(size_t)k * ld + FTGP_WAVE], xk, a1);
     }
 }
-__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st)
+// "Scan input" and "State input": the car's inputs into x, input i in lane i % 64 of register i / 64 (the act kernel records them)
+__device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __restrict__ win, const CarCore* st, float (&x)[4])
 {
-    uint64_t ta = (uint64_t)(table + slot); asm volatile("" : "+s"(ta));
-    const ScalarNet N = (ScalarNet)ta;
     const int lane = lane_here();
     const int pool = N->pool, n_beams = N->n_beams;
     const float M = N->max_range, inv = N->inv_max_range;
-    float x[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    x[0] = 0.0f; x[1] = 0.0f; x[2] = 0.0f; x[3] = 0.0f;
     {
         const float* __restrict__ mine = win + (N->beam_first + lane) * pool;
         #pragma unroll
@@ -1507,6 +1507,11 @@ __device__ __forceinline__ void policy_net(const NetDev* table, int slot, const 
             for (int r = 0; r < 4; ++r) if ((i >> 6) == r && lane == (i & (FTGP_WAVE - 1))) x[r] = v;
         }
     }
+}
+// "Layers": x becomes the outputs of the last layer, y0 in lane 0 and y1 in lane 1 of x[0]
+__device__ __forceinline__ void net_layers(const ScalarNet N, float (&x)[4])
+{
+    const int lane = lane_here();
     const float* __restrict__ params = uniform_ptr(N->params);
     const int n_layers = N->n_layers;
     for (int l = 0; l < n_layers; ++l) {
@@ -1527,6 +1532,20 @@ __device__ __forceinline__ void policy_net(const NetDev* table, int slot, const 
         x[0] = ftgp_net_act(act, a0); x[1] = 0.0f; x[2] = 0.0f; x[3] = 0.0f;
         if (ld > FTGP_WAVE) x[1] = ftgp_net_act(act, a1);
     }
+}
+// the record of slot `slot` behind scalar loads
+__device__ __forceinline__ ScalarNet scalar_net(const NetDev* table, int slot)
+{
+    uint64_t ta = (uint64_t)(table + slot); asm volatile("" : "+s"(ta));
+    return (ScalarNet)ta;
+}
+__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st)
+{
+    const ScalarNet N = scalar_net(table, slot);
+    const int lane = lane_here();
+    float x[4];
+    net_inputs(N, win, st, x);
+    net_layers(N, x);
     const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 0)), y1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 1));
     const float scale[2] = { N->out_scale[0], N->out_scale[1] }, offset[2] = { N->out_offset[0], N->out_offset[1] };
     double us, ut;
@@ -1966,6 +1985,65 @@ __global__ void ftgp_net_params_kernel(NetDev N, const float* __restrict__ src, 
     }
 }
 
+// ftgp_collect_device, step 1 "Act" (include/ftgp.h "Collected rollouts"): one wave per external car, four per workgroup, as K5 alone.
+// The wave stages the rays its network's beams cover and the car's record in LDS, forms the inputs (net_inputs) and writes them down
+// -- input i from lane i % 64, n_in consecutive floats per row --, evaluates the layers (net_layers), and lanes 0 and 1 turn the two
+// outputs into mean and action with the element operations of ftgp_net.h.  ACT = false: the input half alone (next_inputs).
+// (A template, behind the step kernel's instantiations in the file: the code object lays the kernels out in that order, and the
+// step kernels stay where they were.)
+struct CollectActArgs {
+    const float* noise;           // [n_rows][2] or null = zeros
+    float* inputs;                // [n_rows][n_in]
+    float* mean;                  // [n_rows][2]; unused, as noise and action, by the ACT = false instantiation
+    float* action;                // [n_rows][2]
+    float std[2], lo[2], hi[2];
+    int32_t slot, n_ext, n_rows, pad;
+    int32_t ext_slot[FTGP_PAIR_STRIDE];      // index among the env's external cars -> car slot
+};
+template <bool ACT>
+__global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, CollectActArgs C)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int row = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+    if (row >= C.n_rows) return;                                 // (whole waves leave: nothing below meets a workgroup barrier)
+    const int ci = (row / C.n_ext) * P.cars_per_env + C.ext_slot[row % C.n_ext];
+    const ScalarNet N = scalar_net(net_table(&P), C.slot);
+    CarCore* st = reinterpret_cast<CarCore*>(lds) + wave;
+    // the rays of the beams: [beam_first * pool, (beam_first + n_beams) * pool), inside the car's row by ftgp_set_net's rule; a wave's part of
+    // the LDS holds exactly these (the host sizes it: collect_act_lds)
+    const int j0 = N->beam_first * N->pool, j1 = j0 + N->n_beams * N->pool;
+    float* scan = reinterpret_cast<float*>(lds + 4 * sizeof(CarCore)) + wave * (j1 - j0);
+    float* win = scan - j0;                                      // sample j of the car's scan sits at win[j]
+    const float* my_ranges = P.ranges + (size_t)ci * P.ranges_stride;
+    for (int j = j0 + lane; j < j1; j += FTGP_WAVE) win[j] = my_ranges[j];
+    if (lane < (int)(sizeof(CarCore) / 4))
+        reinterpret_cast<uint32_t*>(st)[lane] = reinterpret_cast<const uint32_t*>(static_cast<const CarCore*>(&P.cars[ci]))[lane];
+    wave_lds_sync();
+    float x[4];
+    net_inputs(N, win, st, x);
+    const int n_in = N->width[0];
+    float* in_row = C.inputs + (size_t)row * n_in;
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) if (r * FTGP_WAVE + lane < n_in) in_row[r * FTGP_WAVE + lane] = x[r];
+    if (!ACT) return;
+    const int k = lane & 1;
+    float m = 0.0f, a = 0.0f;
+    if (!sgpr(st->finished)) {                                   // a finished car: (0, 0) before the network is looked at
+        net_layers(N, x);
+        const float nz = C.noise ? C.noise[(size_t)row * 2 + k] : 0.0f;
+        m = ftgp_net_mean(x[0], k ? N->out_scale[1] : N->out_scale[0], k ? N->out_offset[1] : N->out_offset[0]);
+        a = ftgp_net_clip(ftgp_net_noisy(m, k ? C.std[1] : C.std[0], nz), k ? C.lo[1] : C.lo[0], k ? C.hi[1] : C.hi[0]);
+        const bool both = (__ballot(ftgp_net_finite(a)) & 3ull) == 3ull;
+        a = ftgp_net_guarded(a, both);
+    }
+    if (lane < 2) { C.mean[(size_t)row * 2 + lane] = m; C.action[(size_t)row * 2 + lane] = a; }
+}
+
+template __global__ void ftgp_collect_act_kernel<true>(DeviceParams, CollectActArgs);
+template __global__ void ftgp_collect_act_kernel<false>(DeviceParams, CollectActArgs);
+
 // =============================================================================================
 // K4: reset / spawn (custom.py:1089-1128, 1232-1245, 81-87), one car per lane; then K3 at the spawn pose.
 // =============================================================================================
@@ -2084,7 +2162,7 @@ __global__ void ftgp_set_ctrl_kernel(DeviceParams P, const double* __restrict__ 
 
 // ftgp_set_dynamics / ftgp_set_dynamics_device: one car per thread writes its dynamics record -- at `init` the handle's own row, then, for
 // a car of a masked env, the caller's row if it is valid (every entry finite, mass > 0, izz > 0, entries 2-7 >= 0); an invalid row leaves
-// the record as it is and counts.  The wheel loads are plan()'s expressions on the row's mass (binary64, one rounding per operation).
+// the record as it is and counts.  A second mask, if given, is OR-ed with the first (ftgp_collect_device).  The wheel loads are plan()'s expressions on the row's mass (binary64, one rounding per operation).
 __device__ __forceinline__ void dyn_record_write(double* rec, const double* row, const DynArgs& A)
 {
     for (int k = 0; k < FTGP_DYN_DOUBLES; ++k) rec[k] = row[k];
@@ -2101,7 +2179,7 @@ __global__ void ftgp_dynamics_kernel(DeviceParams P, DynArgs A)
     if (i >= P.n_cars) return;
     double* rec = dyn_table(&P) + (size_t)i * FTGP_DYN_RECORD;
     if (A.init) dyn_record_write(rec, A.base, A);
-    if (!A.rows || (A.env_mask && !A.env_mask[i / P.cars_per_env])) return;
+    if (!A.rows || (A.env_mask && !(A.env_mask[i / P.cars_per_env] | (A.env_mask_or ? A.env_mask_or[i / P.cars_per_env] : 0)))) return;
     double row[FTGP_DYN_DOUBLES];
     bool ok = true;
     for (int k = 0; k < FTGP_DYN_DOUBLES; ++k) {

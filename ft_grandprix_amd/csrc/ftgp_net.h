@@ -1,6 +1,7 @@
 // ftgp_net.h -- the network driver (include/ftgp.h: ftgp_set_net): the element operations of one evaluation, shared by the HIP kernels
 // and by the host harness (tools/net_check.cpp compiles exactly these functions for the CPU; tests/net_model.py restates the header's
-// text in numpy and the two are compared bit for bit).
+// text in numpy and the two are compared bit for bit) -- and of a collected decision (ftgp_collect_device: the mean, the noise, the clip and
+// the guard; tools/collect_check.cpp and tests/collect_model.py likewise).
 //
 // Every operation is binary32 with one rounding, written out one by one; the library is compiled with -ffp-contract=off, and fmaf is
 // written where a fused multiply-add is specified.  Comparisons are written as comparisons (no fminf / fmaxf): what a NaN does is then
@@ -74,6 +75,15 @@ FTGP_HD void ftgp_net_controls(float y0, float y1, const float* scale, const flo
     *u_speed = ok ? (double)a : 0.0;
     *u_steer = ok ? (double)b : 0.0;
 }
+
+// ---- collected actions (include/ftgp.h "Collected rollouts", step 1): the mean, the noise, the clip and the guard, one element each
+// (tools/collect_check.cpp compiles these for the CPU; tests/collect_model.py restates the header's text)
+FTGP_HD float ftgp_net_mean(float y, float scale, float offset) { return fmaf(y, scale, offset); }          // not guarded: a diverged network shows
+FTGP_HD float ftgp_net_noisy(float m, float std, float noise) { return fmaf(std, noise, m); }               // 0 * inf = NaN: the guard's business
+FTGP_HD float ftgp_net_clip(float a, float lo, float hi) { return a < lo ? lo : (a > hi ? hi : a); }        // a NaN stays a NaN
+FTGP_HD bool ftgp_net_finite(float a) { return a - a == 0.0f; }
+// the guard: both components, or neither
+FTGP_HD float ftgp_net_guarded(float a, bool both_finite) { return both_finite ? a : 0.0f; }
 
 // ---- shapes: what ftgp_set_net checks, and the sizes that follow from a description ----
 FTGP_HD int ftgp_net_inputs(const FtgpNetDesc* d) { return d->n_beams + (d->use_state ? FTGP_NET_STATE_INPUTS : 0); }

@@ -75,6 +75,18 @@ class EnvSnapshot:
         return int(self.data.shape[1])
 
 
+class Rollout:
+    """T decisions of a network on the device (``DeviceVecEnv.collect``), torch tensors on the env's device with T in front:
+    ``inputs`` float32 [T, n_envs, n_agents, n_in] what the network saw, ``mean`` and ``action`` [T, n_envs, n_agents, 2] what it
+    proposed and what was applied, ``reward`` [T, n_envs, n_agents], ``terminated`` / ``truncated`` bool [T, n_envs],
+    ``next_inputs`` as ``inputs`` (the state after decision t's steps, before any reset; None unless asked for) and ``noise`` the
+    draws that were used (None without exploration)."""
+
+    def __init__(self, inputs, mean, action, reward, terminated, truncated, next_inputs=None, noise=None):
+        self.inputs, self.mean, self.action, self.reward = inputs, mean, action, reward
+        self.terminated, self.truncated, self.next_inputs, self.noise = terminated, truncated, next_inputs, noise
+
+
 class DeviceVecEnv:
     """``n_envs`` worlds of ``cars_per_env`` cars each, stepped from torch tensors on ``cuda:device_id``.
 
@@ -147,6 +159,11 @@ class DeviceVecEnv:
     held for ``action_repeat`` steps -- with ``action_repeat > 1`` a net slot is a different driver from the same network run as an
     agent.  What a net slot sees is what an agent is given with ``scan_pool`` / ``scan_max_range`` / ``state=True`` equal to the
     network's description: the beams ``beam_first .. beam_first + n_beams - 1`` of ``obs`` and entries 0 - 4 of ``state``.
+
+    Collected rollouts (ftgp_collect_device): ``collect(n_decisions, slot=0, std=, clip=, noise=, next_inputs=, out=)`` runs T decisions
+    of network slot ``slot`` for every agent in one call that only enqueues and returns a ``Rollout`` of torch tensors -- what the
+    network saw, its mean, the action applied (mean + std * noise, clipped), the reward and the episode ends per decision -- to the bit
+    what T ``step`` calls fed those actions would leave; ``step`` and ``collect`` may alternate.
 
     Saved states (ftgp_save_envs_device / ftgp_load_envs_device): ``save_state(env_mask=None)`` returns an ``EnvSnapshot`` of the envs'
     whole state -- poses, velocities, steering joint, wheel spins, controls, race and lap fields, step and episode counters, dynamics,
@@ -507,6 +524,86 @@ class DeviceVecEnv:
         """New dynamics for the envs whose episode ended in the step just enqueued (they start a new episode)."""
         torch.logical_or(self.terminated, self.truncated, out=self._dyn_mask)
         self._draw_dynamics(self._dyn_mask)
+
+    # -- collected rollouts (include/ftgp.h: ftgp_collect_device)
+    def collect(self, n_decisions, slot=0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e30, 1e30)), noise=None, next_inputs=False, out=None):
+        """``n_decisions`` = T decisions of network slot ``slot`` for every agent, in one call that only enqueues, on torch's current
+        stream: a ``Rollout`` of what the network saw, proposed, what was applied and what came back (ftgp_collect_device).
+        action = clip(mean + std * noise) per component, ``clip`` = ((lo, hi) of the speed, (lo, hi) of the steering angle).  ``noise``:
+        None = no exploration, True = one ``torch.randn`` on the env's device, or a float32 tensor [T, n_envs, n_agents, 2] of the
+        caller's draws.  ``next_inputs=True`` also records the inputs after every decision's steps, before any reset.  ``out``: a
+        ``Rollout`` of an earlier call with the same T, slot and ``next_inputs``, whose tensors are written again (with ``noise=True``
+        its noise tensor too: drawn into in place).  With
+        ``randomize_dynamics`` the T row sets are drawn up front and an env takes decision t's rows when its episode ends there.
+        ``obs`` and the optional rows are evaluated again at the state the call leaves, so ``step`` and ``collect`` may alternate."""
+        c = capi.collect_args(n_decisions, slot, std, clip)
+        T, slot = c.n_decisions, c.slot
+        if slot not in self._nets:
+            raise ValueError(f"network slot {slot} is not defined: set_net first")
+        n_in = self._nets[slot][0][0][0]
+        lead = (T, self.n_envs, self.n_agents)
+        if noise is not None and noise is not True:
+            if not isinstance(noise, torch.Tensor) or noise.dtype != torch.float32 or noise.device != self.device or \
+                    tuple(noise.shape) != lead + (2,) or not noise.is_contiguous():
+                raise ValueError(f"noise: None, True or a contiguous float32 tensor {lead + (2,)} on {self.device}")
+        shapes = dict(inputs=lead + (n_in,), mean=lead + (2,), action=lead + (2,), reward=lead, terminated=(T, self.n_envs),
+                      truncated=(T, self.n_envs))
+        if next_inputs:
+            shapes["next_inputs"] = lead + (n_in,)
+        if out is not None:
+            if not isinstance(out, Rollout):
+                raise ValueError("out: a Rollout of an earlier collect")
+            for name, shape in shapes.items():
+                t = getattr(out, name)
+                want = torch.bool if name in ("terminated", "truncated") else torch.float32
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != want or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"out.{name}: a contiguous {want} tensor {shape} on {self.device} (same T, slot and next_inputs)")
+        with self._device_guard():
+            if out is None:
+                out = Rollout(**{name: torch.zeros(shape, dtype=torch.bool if name in ("terminated", "truncated") else torch.float32,
+                                                   device=self.device) for name, shape in shapes.items()})
+            if not next_inputs:
+                out.next_inputs = None
+            if noise is True:                            # drawn into the tensor an earlier call left in `out`, if it fits
+                kept = out.noise
+                fits = isinstance(kept, torch.Tensor) and tuple(kept.shape) == lead + (2,) and kept.dtype == torch.float32 and \
+                    kept.device == self.device and kept.is_contiguous()
+                noise = kept.normal_() if fits else torch.randn(lead + (2,), dtype=torch.float32, device=self.device)
+            out.noise = noise
+            rows = None
+            if self._dyn_lo is not None:                 # (one block per T, kept on the env and drawn into again)
+                shape = (T, self.n_envs, self.cars_per_env, capi.DYN_DOUBLES)
+                rows = getattr(self, "_collect_rows", None)
+                if rows is None or tuple(rows.shape) != shape:
+                    rows = self._collect_rows = torch.empty(shape, dtype=torch.float64, device=self.device)
+                rows.uniform_(0.0, 1.0, generator=self._dyn_gen)
+                torch.addcmul(self._dyn_lo, self._dyn_span, rows, out=rows)
+                torch.minimum(rows, self._dyn_hi, out=rows)
+            stream = self._stream()
+            for name in ("inputs", "mean", "action", "reward", "terminated", "truncated"):
+                setattr(c, name, getattr(out, name).data_ptr())
+            c.stream = stream or None
+            c.noise = None if noise is None else noise.data_ptr()
+            c.next_inputs = out.next_inputs.data_ptr() if next_inputs else None
+            c.reset_dynamics = None if rows is None else rows.data_ptr()
+            self._collect_keep = (out, noise, rows)      # (the library reads and writes them in stream order)
+            rc = self.env.lib.fn("collect_device")(self.env.h, ctypes.byref(c))
+            if rc:
+                self.env.lib.check(rc)
+            if rows is not None:                         # the mirror: the rows of the last decision at which an env ended, if any
+                if self.dynamics is None:                # (the table is turned on by the call: every car starts from the handle's values)
+                    base = torch.tensor(self.env.base_dynamics(), dtype=torch.float64, device=self.device)
+                    self.dynamics = base.expand(self.n_envs, self.cars_per_env, capi.DYN_DOUBLES).contiguous()
+                ended = out.terminated | out.truncated
+                last = (ended * torch.arange(1, T + 1, device=self.device)[:, None]).amax(dim=0)
+                taken = rows[(last - 1).clamp(min=0), torch.arange(self.n_envs, device=self.device)]
+                torch.where((last > 0)[:, None, None], taken, self.dynamics, out=self.dynamics)
+            self.env.obs_device(self.obs.data_ptr(), stream)
+            for buf, refresh in ((self.state, self.env.state_device), (self.contact, self.env.contacts_device),
+                                 (self.frame, self.env.frame_device), (self.rival, self.env.rivals_device)):
+                if buf is not None:
+                    refresh(buf.data_ptr(), stream)
+        return out
 
     # -- env states: save, restore, fork (include/ftgp.h: ftgp_save_envs_device / ftgp_load_envs_device)
     def _stream(self):

@@ -795,6 +795,62 @@ int ftgp_set_net(FtgpEnv *env, int slot, const FtgpNetDesc *desc, const float *p
 int ftgp_set_net_device(FtgpEnv *env, void *stream, int slot, const float *params);
 int ftgp_get_net(FtgpEnv *env, int slot, FtgpNetDesc *desc_out, float *params_out);
 
+/* ---- Collected rollouts: T decisions of a network on the device, written down (no reference counterpart) ------------------------------
+ * ftgp_collect_device drives every external slot of a device-io handle with network slot `slot` for n_decisions = T decisions, with
+ * optional exploration noise, and records per decision what the network saw, what it proposed, what was applied and what came back.
+ * One decision is one ftgp_step_device call's worth of work.  The call only enqueues.
+ *
+ * Everything in step 1 is binary32 with one rounding per written operation; fmaf(a, b, c) is the fused a*b + c with one rounding;
+ * nothing else is contracted.  Comparisons with a NaN are false.  Decision t = 0 .. T-1:
+ *   1. Act.  For external car i of env e, at the records and scans as they stand: x = the network's input vector exactly as "Scan
+ *      input" and "State input" of ftgp_set_net define it -- the beams from the car's ftgp_get_lidar row, the state entries 0 - 4 from
+ *      the car's record with the controls then in force.  inputs[t][e][i] = x, for a finished car too.  A finished car gets mean =
+ *      action = (0, 0) and the network is not looked at (the network driver's rule).  Otherwise, with y = the layers on x and k = 0, 1:
+ *        m_k = fmaf(y_k, out_scale[k], out_offset[k])
+ *        a_k = fmaf(std[k], noise[t][e][i][k], m_k)              (noise = NULL: every draw is 0; 0 * infinity is a NaN)
+ *        a_k = a_k < lo[k] ? lo[k] : (a_k > hi[k] ? hi[k] : a_k)  (a NaN stays a NaN; an infinite a_k becomes the bound)
+ *        if a_0 or a_1 is not finite, both are 0
+ *      mean[t][e][i] = (m_0, m_1) as computed -- not guarded, so a diverged network shows -- and action[t][e][i] = (a_0, a_1).
+ *   2. Step.  Steps 2 - 5 of ftgp_step_device run with action = action[t], under every rule in force: signals, contacts, frame, rivals
+ *      and their rewards and terminations, max_episode_steps, action_repeat, auto_reset and the spawn rule.  reward[t], terminated[t]
+ *      and truncated[t] are that call's outputs.  The obs and row buffers of the device step are not part of the record: they go to
+ *      scratch memory of the handle's.
+ *   3. Next inputs.  If next_inputs is given, next_inputs[t][e][i] = step 1's x at the state after the call's physics steps and before
+ *      the reset of an env that ended (the reset is the finish kernel's) -- what a value bootstrap needs at a truncation.
+ *   4. Dynamics on reset.  If reset_dynamics is given, the envs with terminated[t] | truncated[t] take rows [t], exactly as
+ *      ftgp_set_dynamics_device with that mask would do it: an invalid row keeps the old one and counts as rejected, and the first
+ *      decision turns the table on.  FTGP_ERR_STATE if auto_reset is off, and on a handle where ftgp_set_dynamics is.
+ * The contract: after the call, the handle and the outputs are to the bit what T calls of ftgp_step_device_rivals fed action[0 .. T-1]
+ * would leave -- with reset_dynamics, the masked ftgp_set_dynamics_device calls between them.  So the network is evaluated once per
+ * decision and the action holds for action_repeat physics steps (a roster network is evaluated at every physics step); with
+ * action_repeat = 1, noise = NULL, a clip that does not bind and no episode end, a collected agent moves bit for bit like a car of
+ * ftgp_rollout(env, FTGP_POLICY_NET0 + slot, T).
+ *
+ * Ordering: the handle's stream waits for `stream` once at the start, and `stream` for the handle's once at the end; nothing blocks
+ * the host.  A handle's first call allocates scratch memory and may synchronise.  Every buffer is device memory on the handle's
+ * device, dense, at T times the size of one decision (computed in size_t).  Errors, all before anything is enqueued: FTGP_ERR_STATE
+ * before ftgp_device_io_config or for a slot not defined (the roster's network slots included); FTGP_ERR_ARG, naming the field, for
+ * n_decisions < 1, a slot outside 0 .. 3, std negative or not finite, lo or hi not finite or lo > hi, reserved != 0, a buffer that is
+ * NULL (noise, next_inputs and reset_dynamics may be), not device memory on the handle's device or too small, and for a slot whose
+ * beams cover more than 4048 rays (n_beams * pool; four cars' rays share a workgroup's 64 KiB of LDS). */
+typedef struct FtgpCollect {
+    void *stream;                 /* as FtgpDeviceStep.stream */
+    int32_t slot;                 /* 0 .. FTGP_MAX_NETS-1, must be defined */
+    int32_t n_decisions;          /* T >= 1 */
+    float std[2];                 /* >= 0, finite */
+    float lo[2], hi[2];           /* finite, lo[k] <= hi[k]: the action's clip */
+    const float *noise;           /* optional float32[T][n_envs][n_ext][2], the caller's draws (e.g. one torch.randn); NULL = zeros */
+    float *inputs;                /* float32[T][n_envs][n_ext][n_in] */
+    float *mean;                  /* float32[T][n_envs][n_ext][2] */
+    float *action;                /* float32[T][n_envs][n_ext][2] */
+    float *reward;                /* float32[T][n_envs][n_ext] */
+    uint8_t *terminated, *truncated;   /* uint8[T][n_envs] */
+    float *next_inputs;           /* optional, as inputs: the state after decision t's steps, BEFORE any reset */
+    const double *reset_dynamics; /* optional double[T][n_envs][cars_per_env][FTGP_DYN_DOUBLES] */
+    int32_t reserved;             /* 0 */
+} FtgpCollect;
+int ftgp_collect_device(FtgpEnv *env, const FtgpCollect *c);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).

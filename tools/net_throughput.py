@@ -1,15 +1,19 @@
 """What a network driver costs a step: rollout("net0") against rollout("fast") and rollout("lobotomy"), and against the device step
 with one agent whose network torch evaluates.
 
-    python tools/net_throughput.py [--envs 4096] [--rays 1080] [--steps 500] [--launches 5] [--track track] [--calls 500] [--rows rollout,agent]
+    python tools/net_throughput.py [--envs 4096] [--rays 1080] [--steps 500] [--launches 5] [--track track] [--calls 500]
+                                   [--decisions 100] [--rows rollout,agent,collect]
 
 rollout rows: one launch of --steps steps per measurement, --launches of them after one warm-up launch; env-steps/s from the wall clock
 around the launch and its synchronisation, and the step kernel's own time from ftgp_last_kernel_ms.  The network is a random
 85 -> 64 -> 64 -> 2 tanh MLP on beams 14 .. 93 of pool 10 and the five state inputs (at another --rays: the beams of the scan window).
 agent row: DeviceVecEnv(roster=["agent"], scan_pool, scan_max_range, state=True), the same network as an nn.Sequential evaluated by
-torch before every call, --calls calls of one step; per-call time from HIP events on torch's stream.  One JSON line per row.  Run it in
+torch before every call, --calls calls of one step; per-call time from HIP events on torch's stream.
+collect row: the same env with the network in slot 0, DeviceVecEnv.collect (ftgp_collect_device) of --decisions decisions a call with
+noise drawn by one torch.randn, next_inputs on; --launches calls after one warm-up call; per-decision time from HIP events around the
+calls, env-steps/s from the wall clock -- the row to hold against the agent row of the same run.  One JSON line per row.  Run it in
 a fresh process: torch is imported first (ft_grandprix_amd/vec.py).  Under `rocprofv3 --kernel-trace --stats -- python
-tools/net_throughput.py --rows rollout` the per-kernel times come out of the stats file.
+tools/net_throughput.py --rows rollout` (or `--rows collect`) the per-kernel times come out of the stats file.
 """
 import argparse
 import json
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--calls", type=int, default=500)
+    ap.add_argument("--decisions", type=int, default=100)
     ap.add_argument("--pool", type=int, default=10)
     ap.add_argument("--track", default="track")
     ap.add_argument("--rows", default="rollout,agent")
@@ -93,6 +98,28 @@ def main():
         wall = time.perf_counter() - t0
         print(json.dumps({"row": "device step, torch evaluates the network", "envs": a.envs, "rays": a.rays, "calls": a.calls,
                           "env_steps_per_s": a.envs * a.calls / wall, "us_per_call_events": 1e3 * e0.elapsed_time(e1) / a.calls}), flush=True)
+        venv.close()
+    if "collect" in rows:
+        from ft_grandprix_amd.vec import DeviceVecEnv
+        venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, roster=["agent"], scan_pool=a.pool, scan_max_range=10.0, state=True, spawn_mode=1, seed=7,
+                            nets={0: spec})
+        dev = venv.device
+        venv.reset()
+        kw = dict(std=(0.3, 0.1), clip=((0.0, 5.0), (-0.6, 0.6)), noise=True, next_inputs=True)
+        roll = venv.collect(a.decisions, **kw)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        e0.record()
+        for _ in range(a.launches):
+            roll = venv.collect(a.decisions, out=roll, **kw)
+        e1.record()
+        torch.cuda.synchronize(dev)
+        wall = time.perf_counter() - t0
+        n = a.launches * a.decisions
+        print(json.dumps({"row": "collect, network on the device", "envs": a.envs, "rays": a.rays, "calls": a.launches, "decisions_per_call": a.decisions,
+                          "env_steps_per_s": a.envs * n / wall, "us_per_decision_events": 1e3 * e0.elapsed_time(e1) / n,
+                          "us_per_decision_wall": 1e6 * wall / n, "ends": int((roll.terminated | roll.truncated).sum())}), flush=True)
         venv.close()
 
 
