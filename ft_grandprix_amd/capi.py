@@ -108,7 +108,7 @@ API_SYMBOLS = (
     "device_io_rivals", "step_device_rivals", "rivals_device", "get_rivals",
     "set_dynamics", "set_dynamics_device", "get_dynamics",
     "env_state_bytes", "save_envs_device", "load_envs_device", "get_env_state_rejected", "obs_device",
-    "set_net", "set_net_device", "get_net",
+    "set_net", "set_net_device", "get_net", "set_net_frame", "get_net_frame",
     "collect_device",
 )
 
@@ -168,6 +168,10 @@ class FtgpNetDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class FtgpNetFrame(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("n_ahead", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FtgpCollect(C.Structure):
     _fields_ = [("stream", C.c_void_p), ("slot", C.c_int32), ("n_decisions", C.c_int32), ("std", C.c_float * 2), ("lo", C.c_float * 2),
                 ("hi", C.c_float * 2), ("noise", C.c_void_p), ("inputs", C.c_void_p), ("mean", C.c_void_p), ("action", C.c_void_p),
@@ -197,11 +201,26 @@ def collect_args(n_decisions, slot=0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e3
     return c
 
 
+def net_frame(frame=False, lookahead=0, lookahead_stride=1) -> "FtgpNetFrame":
+    """The FtgpNetFrame of ftgp_set_net_frame with its checks (ValueError): lookahead 0 .. 16 and lookahead_stride 1 .. 50, checked
+    with the frame off too; ``lookahead > 0`` implies ``frame``, as in DeviceVecEnv."""
+    for name, v, lo, hi in (("lookahead", lookahead, 0, MAX_LOOKAHEAD), ("lookahead_stride", lookahead_stride, 1, 50)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name}: an integer in {lo} .. {hi}, got {v!r}")
+    return FtgpNetFrame(enabled=1 if (frame or int(lookahead) > 0) else 0, n_ahead=int(lookahead), stride=int(lookahead_stride))
+
+
+def net_frame_inputs(f) -> int:
+    """Frame entries behind the beams and the state inputs: 0 without frame inputs (``f`` an FtgpNetFrame or None)."""
+    return FRAME_FIXED + 2 * f.n_ahead if f is not None and f.enabled else 0
+
+
 def net_desc(layers, *, pool, max_range, beam_first, n_beams, use_state=False, hidden_act="tanh", out_act="tanh",
-             out_scale=(1, 1), out_offset=(0, 0)):
+             out_scale=(1, 1), out_offset=(0, 0), frame=False, lookahead=0, lookahead_stride=1):
     """(FtgpNetDesc, flat float32 parameters) of a network given as a list of (W [n_out, n_in], b [n_out]) pairs, with every check of
-    ftgp_set_net that needs no handle (ValueError): the widths, the activations, the output map, the shapes of the arrays.  The window
-    rule needs n_rays: ``check_net_window``."""
+    ftgp_set_net and ftgp_set_net_frame that needs no handle (ValueError): the widths, the activations, the output map, the shapes of
+    the arrays, the frame fields (``net_frame`` makes the struct).  The window rule needs n_rays: ``check_net_window``."""
+    n_frame = net_frame_inputs(net_frame(frame, lookahead, lookahead_stride))
     layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
     if not 1 <= len(layers) <= NET_MAX_LAYERS:
         raise ValueError(f"a network has 1 .. {NET_MAX_LAYERS} layers, got {len(layers)}")
@@ -209,9 +228,9 @@ def net_desc(layers, *, pool, max_range, beam_first, n_beams, use_state=False, h
         raise ValueError(f"pool >= 1, n_beams >= 1, beam_first >= 0: got {pool}, {n_beams}, {beam_first}")
     if not (np.isfinite(max_range) and max_range > 0):
         raise ValueError(f"max_range must be finite and > 0, got {max_range}")
-    n_in = int(n_beams) + (NET_STATE_INPUTS if use_state else 0)
+    n_in = int(n_beams) + (NET_STATE_INPUTS if use_state else 0) + n_frame
     if n_in > NET_MAX_INPUTS:
-        raise ValueError(f"n_beams + 5 use_state = {n_in} inputs, at most {NET_MAX_INPUTS}")
+        raise ValueError(f"n_beams + 5 use_state + {n_frame} frame entries = {n_in} inputs, at most {NET_MAX_INPUTS}")
     for name, act in (("hidden_act", hidden_act), ("out_act", out_act)):
         if act not in ACT_BY_NAME:
             raise ValueError(f"{name}: one of {sorted(ACT_BY_NAME)}, got {act!r}")
@@ -246,16 +265,16 @@ def check_net_window(n_rays: int, pool: int, beam_first: int, n_beams: int):
                          f"rays [{eighth}, {n_rays - eighth}) of {n_rays}: the rear quarter of the scan is not an input")
 
 
-def net_param_count(d: FtgpNetDesc) -> int:
-    n, n_in = 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0)
+def net_param_count(d: FtgpNetDesc, frame=None) -> int:
+    n, n_in = 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0) + net_frame_inputs(frame)
     for l in range(d.n_layers):
         n, n_in = n + d.width[l] * n_in + d.width[l], d.width[l]
     return n
 
 
-def net_layers(d: FtgpNetDesc, flat: np.ndarray) -> list:
-    """The (W, b) pairs of a flat parameter buffer in ftgp_set_net's layout."""
-    out, o, n_in = [], 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0)
+def net_layers(d: FtgpNetDesc, flat: np.ndarray, frame=None) -> list:
+    """The (W, b) pairs of a flat parameter buffer in ftgp_set_net's layout (``frame``: the slot's FtgpNetFrame, if it has one)."""
+    out, o, n_in = [], 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0) + net_frame_inputs(frame)
     for l in range(d.n_layers):
         n_out = d.width[l]
         W = flat[o:o + n_out * n_in].reshape(n_out, n_in); o += n_out * n_in
@@ -364,6 +383,8 @@ class CLib:
             "set_net": (i32, [vp, i32, C.POINTER(FtgpNetDesc), dp]),
             "set_net_device": (i32, [vp, vp, i32, vp]),
             "get_net": (i32, [vp, i32, C.POINTER(FtgpNetDesc), dp]),
+            "set_net_frame": (i32, [vp, i32, C.POINTER(FtgpNetDesc), C.POINTER(FtgpNetFrame), dp]),
+            "get_net_frame": (i32, [vp, i32, C.POINTER(FtgpNetFrame)]),
             "collect_device": (i32, [vp, C.POINTER(FtgpCollect)]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
@@ -662,15 +683,21 @@ class Env:
 
     # -- network drivers (include/ftgp.h: ftgp_set_net)
     def set_net(self, slot: int, layers, *, pool=None, max_range=None, beam_first=None, n_beams=None, use_state=False,
-                hidden_act="tanh", out_act="tanh", out_scale=(1, 1), out_offset=(0, 0)):
-        """ftgp_set_net: ``layers`` = [(W [n_out, n_in], b [n_out]), ...] (torch's nn.Linear layout) becomes the network driver
-        ``"net<slot>"``; ``layers=None`` clears the slot."""
+                hidden_act="tanh", out_act="tanh", out_scale=(1, 1), out_offset=(0, 0), frame=False, lookahead=0, lookahead_stride=1):
+        """ftgp_set_net / ftgp_set_net_frame: ``layers`` = [(W [n_out, n_in], b [n_out]), ...] (torch's nn.Linear layout) becomes the
+        network driver ``"net<slot>"``; ``layers=None`` clears the slot.  ``frame`` (or ``lookahead > 0``): the track-frame row with
+        ``lookahead`` points every ``lookahead_stride`` path points follows the beams and the state inputs."""
         if layers is None:
             self._call("set_net", int(slot), None, None)
             return
         d, flat = net_desc(layers, pool=pool, max_range=max_range, beam_first=beam_first, n_beams=n_beams, use_state=use_state,
-                           hidden_act=hidden_act, out_act=out_act, out_scale=out_scale, out_offset=out_offset)
-        self._call("set_net", int(slot), C.byref(d), _ptr(flat))
+                           hidden_act=hidden_act, out_act=out_act, out_scale=out_scale, out_offset=out_offset,
+                           frame=frame, lookahead=lookahead, lookahead_stride=lookahead_stride)
+        f = net_frame(frame, lookahead, lookahead_stride)
+        if f.enabled:
+            self._call("set_net_frame", int(slot), C.byref(d), C.byref(f), _ptr(flat))
+        else:
+            self._call("set_net", int(slot), C.byref(d), _ptr(flat))
 
     def set_net_device(self, slot: int, address: int, stream: int = 0):
         """ftgp_set_net_device: new parameters for a defined slot from the integer device address of a float32 buffer in
@@ -679,11 +706,22 @@ class Env:
 
     def net(self, slot: int):
         """(FtgpNetDesc, [(W, b), ...]): the description and the parameters in force of a defined slot (ftgp_get_net)."""
-        d = FtgpNetDesc()
+        d, f = FtgpNetDesc(), FtgpNetFrame()
         self._call("get_net", int(slot), C.byref(d), None)
-        flat = np.empty(net_param_count(d), dtype=np.float32)
+        self._call("get_net_frame", int(slot), C.byref(f))
+        flat = np.empty(net_param_count(d, f), dtype=np.float32)
         self._call("get_net", int(slot), C.byref(d), _ptr(flat))
-        return d, net_layers(d, flat)
+        return d, net_layers(d, flat, f)
+
+    def net_frame(self, slot: int) -> dict:
+        """The frame inputs of a defined slot (ftgp_get_net_frame): ``dict(frame, lookahead, lookahead_stride)``, set_net's keywords."""
+        f = FtgpNetFrame()
+        self._call("get_net_frame", int(slot), C.byref(f))
+        return dict(frame=bool(f.enabled), lookahead=int(f.n_ahead), lookahead_stride=int(f.stride) if f.enabled else 1)
+
+    def get_net(self, slot: int):
+        """(FtgpNetDesc, [(W, b), ...], dict(frame, lookahead, lookahead_stride)): ``net`` and ``net_frame`` of a defined slot."""
+        return self.net(slot) + (self.net_frame(slot),)
 
     # -- collected rollouts (include/ftgp.h: ftgp_collect_device)
     def collect_device(self, n_decisions: int, inputs: int, mean: int, action: int, reward: int, terminated: int, truncated: int, *,

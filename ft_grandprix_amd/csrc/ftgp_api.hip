@@ -198,6 +198,7 @@ struct FtgpEnv {
     DevBuf<NetDev> d_nets;            // [FTGP_MAX_NETS] the records the kernels read; allocated by the first setter call (ensure_nets)
     NetDev nets[FTGP_MAX_NETS] = {};  // their host mirror (defined = 0: an empty slot)
     FtgpNetDesc net_desc[FTGP_MAX_NETS] = {};     // the descriptions as the caller gave them (ftgp_get_net)
+    FtgpNetFrame net_frame[FTGP_MAX_NETS] = {};   // ... and the frame inputs (ftgp_get_net_frame); zeros = none
     DevBuf<float> d_net_params[FTGP_MAX_NETS];    // the slots' parameters in the library's layout
     bool last_net = false;            // the newest launch ran a NET instantiation
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
@@ -1755,6 +1756,7 @@ static int launch_collect_act(FtgpEnv* e, const FtgpCollect& c, const float* noi
     for (int k = 0; k < 2; ++k) { C.std[k] = c.std[k]; C.lo[k] = c.lo[k]; C.hi[k] = c.hi[k]; }
     C.slot = c.slot; C.n_ext = e->ds.io.n_ext; C.n_rows = e->P.n_envs * e->ds.io.n_ext;
     for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) if (e->ds.io.ext_index[k] >= 0) C.ext_slot[e->ds.io.ext_index[k]] = k;
+    C.env_track = e->d_env_track.get();
     const size_t lds = collect_act_lds(e->nets[c.slot]);
     void (*kernel)(DeviceParams, CollectActArgs) = mean ? ftgp_collect_act_kernel<true> : ftgp_collect_act_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((C.n_rows + 3) / 4)), dim3(256), lds, e->stream.get(), e->P, C);
@@ -1993,13 +1995,36 @@ static int check_net_desc(const FtgpEnv* e, const FtgpNetDesc& d)
     return 0;
 }
 
-// the record of a description: the library's layout (NetDev) without the buffer's address
-static NetDev net_record(const FtgpNetDesc& d)
+// what ftgp_set_net_frame checks beyond the description: the frame struct (as ftgp_device_io_frame checks its own: the ranges hold
+// for a struct that is off too) and the width with the frame entries
+static int check_net_frame(const FtgpNetDesc& d, const FtgpNetFrame& f)
+{
+    if (f.enabled != 0 && f.enabled != 1) return failf(FTGP_ERR_ARG, "ftgp_set_net_frame: enabled = %d must be 0 or 1", f.enabled);
+    if (f.n_ahead < 0 || f.n_ahead > FTGP_MAX_LOOKAHEAD) return failf(FTGP_ERR_ARG, "ftgp_set_net_frame: n_ahead = %d outside 0 .. %d", f.n_ahead, FTGP_MAX_LOOKAHEAD);
+    if (f.stride < 1 || f.stride > 50) return failf(FTGP_ERR_ARG, "ftgp_set_net_frame: stride = %d outside 1 .. 50", f.stride);
+    if (f.reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_set_net_frame: reserved must be 0%s");
+    const int n_in = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(&f);
+    if (n_in > FTGP_NET_MAX_INPUTS)
+        return failf(FTGP_ERR_ARG, "ftgp_set_net_frame: n_in = n_beams + 5 use_state + %d frame entries = %d inputs, at most %d", ftgp_net_frame_inputs(&f), n_in, FTGP_NET_MAX_INPUTS);
+    return 0;
+}
+
+// floats of a slot's parameters in the caller's layout: per layer W[n_out][n_in], then b[n_out], with the slot's true n_in
+static size_t net_param_count(const NetDev& N)
+{
+    size_t n = 0;
+    for (int l = 0; l < N.n_layers; ++l) n += (size_t)N.width[l + 1] * (size_t)N.width[l] + (size_t)N.width[l + 1];
+    return n;
+}
+
+// the record of a description: the library's layout (NetDev) without the buffer's address; f = null: no frame inputs
+static NetDev net_record(const FtgpNetDesc& d, const FtgpNetFrame* f)
 {
     NetDev N{};
     N.defined = 1; N.pool = d.pool; N.beam_first = d.beam_first; N.n_beams = d.n_beams; N.use_state = d.use_state; N.n_layers = d.n_layers;
     N.hidden_act = d.hidden_act; N.out_act = d.out_act;
-    N.width[0] = ftgp_net_inputs(&d);
+    N.width[0] = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f);
+    if (f && f->enabled) { N.frame_first = ftgp_net_inputs(&d); N.frame_shape = f->n_ahead | f->stride << 8; }
     int o = 0;
     for (int l = 0; l < d.n_layers; ++l) {
         N.width[l + 1] = d.width[l];
@@ -2035,13 +2060,16 @@ static int ensure_nets(FtgpEnv* e)
     return 0;
 }
 
-int ftgp_set_net(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const float* params)
+int ftgp_set_net(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const float* params) { return ftgp_set_net_frame(e, slot, desc, nullptr, params); }
+
+int ftgp_set_net_frame(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const FtgpNetFrame* frame, const float* params)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_net: not on a FTGP_LIDAR_FAKELIDAR handle%s");
     if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
     if (desc) {
         if (int rc = check_net_desc(e, *desc)) return rc;
+        if (frame) if (int rc = check_net_frame(*desc, *frame)) return rc;
         if (!params) return fail(FTGP_ERR_ARG, "ftgp_set_net: params is NULL%s");
     }
     HIP_TRY(hipSetDevice(e->device));
@@ -2050,7 +2078,7 @@ int ftgp_set_net(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const float* par
     NetDev N{};
     DevBuf<float> buf;
     if (desc) {
-        N = net_record(*desc);
+        N = net_record(*desc, frame);
         std::vector<float> img((size_t)N.n_floats, 0.0f);     // the library's layout; the padding is zeros
         const float* src = params;
         for (int l = 0; l < N.n_layers; ++l) {
@@ -2065,6 +2093,7 @@ int ftgp_set_net(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const float* par
     HIP_TRY(hipMemcpy(e->d_nets.get() + slot, &N, sizeof N, hipMemcpyHostToDevice));
     e->nets[slot] = N;
     e->net_desc[slot] = desc ? *desc : FtgpNetDesc{};
+    e->net_frame[slot] = (desc && frame && frame->enabled) ? *frame : FtgpNetFrame{};
     e->d_net_params[slot] = std::move(buf);                   // (the old buffer goes: nothing reads it any more)
     return 0;
 }
@@ -2075,7 +2104,7 @@ int ftgp_set_net_device(FtgpEnv* e, void* stream, int slot, const float* params)
     if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
     if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_device: network slot %d is not defined (ftgp_set_net)", slot);
     HIP_TRY(hipSetDevice(e->device));
-    const int n = (int)ftgp_net_param_count(&e->net_desc[slot]);
+    const int n = (int)net_param_count(e->nets[slot]);
     auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_net_device: %s", m.c_str()); return rc; };
     if (int rc = check_device_buffer(e, params, sizeof(float) * (size_t)n, "params")) return refused(rc);
     if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
@@ -2104,6 +2133,15 @@ int ftgp_get_net(FtgpEnv* e, int slot, FtgpNetDesc* desc_out, float* params_out)
         for (int j = 0; j < n_out; ++j) for (int k = 0; k < n_in; ++k) *dst++ = img[(size_t)N.w_off[l] + (size_t)k * ld + j];
         for (int j = 0; j < n_out; ++j) *dst++ = img[(size_t)N.b_off[l] + j];
     }
+    return 0;
+}
+
+int ftgp_get_net_frame(FtgpEnv* e, int slot, FtgpNetFrame* frame_out)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_frame: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_frame: network slot %d is not defined (ftgp_set_net)", slot);
+    if (frame_out) *frame_out = e->net_frame[slot];
     return 0;
 }
 
@@ -2309,7 +2347,8 @@ int ftgp_policy_eval(FtgpEnv* e, int policy, const float* ranges, double* ctrl_o
                              sizeof(float) * (size_t)e->P.n_rays, (size_t)e->P.n_cars, hipMemcpyHostToDevice, e->stream.get()));
     const size_t lds = 4 * ((size_t)e->P.win_floats * sizeof(float) + sizeof(CarCore) + FTGP_WAVE * sizeof(int));
     if (lds > 64 * 1024) return fail(FTGP_ERR_ARG, "scan does not fit LDS%s");
-    hipLaunchKernelGGL(ftgp_policy_kernel, dim3((e->P.n_cars + 3) / 4), dim3(256), lds, e->stream.get(), e->P, policy, ctrl_out ? e->d_ctrl.get() : nullptr);
+    hipLaunchKernelGGL(ftgp_policy_kernel, dim3((e->P.n_cars + 3) / 4), dim3(256), lds, e->stream.get(), e->P, policy, ctrl_out ? e->d_ctrl.get() : nullptr,
+                       (const int32_t*)e->d_env_track.get());
     HIP_TRY(hipGetLastError());
     if (ctrl_out) HIP_TRY(hipMemcpyAsync(ctrl_out, e->d_ctrl.get(), sizeof(double) * 2 * (size_t)e->P.n_cars, hipMemcpyDeviceToHost, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));

@@ -6,6 +6,7 @@
 #include "ftgp_march.h"
 #include "ftgp_spawn.h"
 #include "ftgp_net.h"
+#include "ftgp_frame.h"
 
 #define FTGP_WAVE 64
 #define FTGP_MAX_GROUPS 256              // groups of 64 rays per car: n_rays <= 16384
@@ -177,7 +178,9 @@ struct alignas(16) NetDev {
     int32_t defined, pool, beam_first, n_beams, use_state, n_layers, hidden_act, out_act;
     int32_t width[FTGP_NET_MAX_LAYERS + 1];       // width[0] = n_in, width[l + 1] = outputs of layer l
     int32_t w_off[FTGP_NET_MAX_LAYERS], b_off[FTGP_NET_MAX_LAYERS];      // float offsets of Wt and b of layer l in params
-    int32_t n_floats, pad0, pad1;                 // floats of the slot's buffer in the library's layout
+    int32_t n_floats;                             // floats of the slot's buffer in the library's layout
+    int32_t frame_first, frame_shape;             // frame inputs (ftgp_set_net_frame; the two words that were spare): the index of the first one, and
+                                                  // n_ahead | stride << 8 -- 0 = none, as ftgp_set_net leaves it (an enabled frame has stride >= 1)
     float max_range, inv_max_range, out_scale[2], out_offset[2];
     const float* params;
 };

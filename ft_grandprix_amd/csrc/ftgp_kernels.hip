@@ -1486,11 +1486,79 @@ __device__ __forceinline__ void net_rows(const float* __restrict__ row, int ld, 
     }
 }
 // "Scan input" and "State input": the car's inputs into x, input i in lane i % 64 of register i / 64 (the act kernel records them)
-__device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __restrict__ win, const CarCore* st, float (&x)[4])
+// "Frame inputs" (ftgp_set_net_frame): the frame row of the car's record, entry j into the lane that owns input frame_first + j.  The wave
+// has one car.  Search: lane l takes points l and l + 64 (l < 36) with K3's expression and keeps its first minimum; the pair (d, index)
+// folds over xor-shuffles 1 .. 32 with the order "smaller d, then smaller index" (frame_nearer) -- the frame kernel's argument, widened
+// from a row of sixteen to the wave: every lane ends with K3's first minimum.  (A NaN pose: every lane keeps its own (NaN, l), lane 0 has
+// c = 0 as K3 does, and c is read from lane 0.)  Segment choice: lanes 0 and 1 project on segments B and A, and only g2 leaves them.
+// Fixed entries: lanes 0 .. 3 project on the segment taken and lane k forms entry k -- one division in the code, not four side by side,
+// whose temporaries do not fit the step kernel's 64 registers -- and v_readlane hands the four to the lanes that own those inputs.
+// Look-ahead: the lane that owns an entry forms its pair and keeps its half.  The block is at most 36 wide, so a lane owns at most one
+// entry.  The three phases hang on wave-uniform values (c, then the segment) in SGPRs, so what one phase computed is dead in the next.
+// `path`: the centre-line of the car's track, LDS in the step kernel, device memory elsewhere.  Returns the lane's entry and, in reg,
+// the register it belongs to (-1: the lane owns none).
+__device__ __forceinline__ float net_frame_entry(const double* __restrict__ path, const CarCore* st, int first, int n_ahead, int stride, int& reg)
+{
+    const int lane = lane_here();
+    int c;
+    {
+        const double px = st->x, py = st->y;
+        double best = frame_dist2(path, lane, px, py); int idx = lane;
+        if (lane < FTGP_PATH_POINTS - FTGP_WAVE) {
+            const double d = frame_dist2(path, lane + FTGP_WAVE, px, py);
+            if (d < best) { best = d; idx = lane + FTGP_WAVE; }
+        }
+        // (ds_bpermute at addresses formed here from lane_here(): __shfl_xor forms them from the lane counters, the optimiser moves the six
+        // in front of the step loop and they end up in scratch memory under the step kernel's 64 registers)
+        #pragma unroll
+        for (int m = 1; m < FTGP_WAVE; m <<= 1) {
+            const int from = (lane ^ m) << 2;
+            const double od = __hiloint2double(__builtin_amdgcn_ds_bpermute(from, __double2hiint(best)), __builtin_amdgcn_ds_bpermute(from, __double2loint(best)));
+            const int oi = __builtin_amdgcn_ds_bpermute(from, idx);
+            if (frame_nearer(od, oi, best, idx)) { best = od; idx = oi; }
+        }
+        c = __builtin_amdgcn_readfirstlane(idx);
+    }
+    const int pa = c > 0 ? c - 1 : FTGP_PATH_POINTS - 1;
+    int seg;
+    {
+        double g2 = 0.0;
+        if (lane < 2) g2 = frame_segment(path, lane == 0 ? c : pa, st->x, st->y).g2;
+        const double g2b = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(g2), 0), __builtin_amdgcn_readlane(__double2loint(g2), 0));
+        const double g2a = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(g2), 1), __builtin_amdgcn_readlane(__double2loint(g2), 1));
+        seg = __builtin_amdgcn_readfirstlane(g2a < g2b ? pa : c);        // A only if strictly nearer
+    }
+    const double qw = st->qw, qz = st->qz;
+    const double ch = qw * qw - qz * qz, sh = 2.0 * (qw * qz);
+    float e = 0.0f;
+    if (lane < FTGP_FRAME_FIXED) {
+        double s;
+        e = frame_fixed_entry(frame_segment(path, seg, st->x, st->y), seg, ch, sh, lane, s);
+    }
+    const int j = (lane - first) & (FTGP_WAVE - 1);               // the entry this lane owns, if j < width
+    reg = j < FTGP_FRAME_FIXED + 2 * n_ahead ? (first + j) >> 6 : -1;
+    const int ei = __float_as_int(e);
+    float v = __int_as_float(j == 0 ? __builtin_amdgcn_readlane(ei, 0) : j == 1 ? __builtin_amdgcn_readlane(ei, 1) : j == 2 ? __builtin_amdgcn_readlane(ei, 2)
+                                                                                                                            : __builtin_amdgcn_readlane(ei, 3));
+    if (j >= FTGP_FRAME_FIXED && reg >= 0) {
+        const FramePoint p = frame_ahead(path, seg, (j - FTGP_FRAME_FIXED) >> 1, stride, st->x, st->y, ch, sh);
+        v = (j & 1) ? p.y : p.x;
+    }
+    return v;
+}
+// path(): the centre-line of the car's track, asked for by a slot with frame inputs only (elsewhere than in the step kernel it costs a
+// scalar load and a wait, which a launch without frame inputs does not pay)
+template <class PathFn>
+__device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __restrict__ win, const CarCore* st, PathFn path, float (&x)[4])
 {
     const int lane = lane_here();
     const int pool = N->pool, n_beams = N->n_beams;
     const float M = N->max_range, inv = N->inv_max_range;
+    // (the frame entry first: its binary64 then has the registers to itself, not the four of x as well)
+    const int shape = N->frame_shape;
+    int frame_reg = -1;
+    float frame_v = 0.0f;
+    if (shape != 0) frame_v = net_frame_entry(path(), st, N->frame_first, shape & 0xff, shape >> 8, frame_reg);   // wave-uniform: the slot's record
     x[0] = 0.0f; x[1] = 0.0f; x[2] = 0.0f; x[3] = 0.0f;
     {
         const float* __restrict__ mine = win + (N->beam_first + lane) * pool;
@@ -1507,6 +1575,8 @@ __device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __res
             for (int r = 0; r < 4; ++r) if ((i >> 6) == r && lane == (i & (FTGP_WAVE - 1))) x[r] = v;
         }
     }
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) if (frame_reg == r) x[r] = frame_v;
 }
 // "Layers": x becomes the outputs of the last layer, y0 in lane 0 and y1 in lane 1 of x[0]
 __device__ __forceinline__ void net_layers(const ScalarNet N, float (&x)[4])
@@ -1539,12 +1609,13 @@ __device__ __forceinline__ ScalarNet scalar_net(const NetDev* table, int slot)
     uint64_t ta = (uint64_t)(table + slot); asm volatile("" : "+s"(ta));
     return (ScalarNet)ta;
 }
-__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st)
+template <class PathFn>
+__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st, PathFn path)
 {
     const ScalarNet N = scalar_net(table, slot);
     const int lane = lane_here();
     float x[4];
-    net_inputs(N, win, st, x);
+    net_inputs(N, win, st, path, x);
     net_layers(N, x);
     const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 0)), y1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 1));
     const float scale[2] = { N->out_scale[0], N->out_scale[1] }, offset[2] = { N->out_offset[0], N->out_offset[1] };
@@ -1553,13 +1624,14 @@ __device__ __forceinline__ void policy_net(const NetDev* table, int slot, const 
     if (lane == 0) { st->u_speed = us; st->u_steer = ut; }
 }
 // the driver FTGP_POLICY_NET0 + slot of one car: a finished car gets the null driver before the network is looked at
-__device__ __forceinline__ void policy_apply_net(const NetDev* table, int slot, const float* scan, int eighth, CarCore* st)
+template <class PathFn>
+__device__ __forceinline__ void policy_apply_net(const NetDev* table, int slot, const float* scan, int eighth, CarCore* st, PathFn path)
 {
     if (st->finished) {
         if (lane_id() == 0) { st->u_speed = 0.0; st->u_steer = 0.0; }
         return;
     }
-    policy_net(table, slot, scan + scan_window_first(eighth) - eighth, st);
+    policy_net(table, slot, scan + scan_window_first(eighth) - eighth, st, path);
 }
 
 // =============================================================================================
@@ -1846,7 +1918,7 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
             for (int c = wave; c < ncars_here; c += nwaves) {
                 if constexpr (NET) {      // the launch's driver, or some slot's, is a network: the slot's driver, networks among them
                     const int pol = policy == FTGP_POLICY_PER_CAR ? G->car_policy[c] : policy;
-                    if (is_net_policy(pol)) policy_apply_net(net_table(G), pol - FTGP_POLICY_NET0, scan_prev + c * win_floats, G->eighth, L.cars + c);
+                    if (is_net_policy(pol)) policy_apply_net(net_table(G), pol - FTGP_POLICY_NET0, scan_prev + c * win_floats, G->eighth, L.cars + c, [&] { return L.path; });
                     else if (policy == FTGP_POLICY_PER_CAR)
                         policy_apply(P, driver_shape(G), pol, scan_prev + c * win_floats, L.cars + c, ci0 + c, L.steps[c], L.list + wave * FTGP_WAVE,
                                      L.cover + (pol == FTGP_POLICY_FAST ? (G->stage_cover >> 2) : 0));
@@ -1942,7 +2014,8 @@ template __global__ void ftgp_step_kernel<false, false, true, true, true, true>(
 template __global__ void ftgp_step_kernel<true, false, true, true, true, true>(const DeviceParams*, int, int, int);
 
 // K5 alone: one wave per car evaluates the driver on the scan stored in P.ranges (ftgp_policy_eval).
-__global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int policy, double* __restrict__ ctrl_out)
+// env_track: the track of every env, null with one track (a network's frame inputs read the centre-line of the car's track)
+__global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int policy, double* __restrict__ ctrl_out, const int32_t* __restrict__ env_track)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int lane = lane_id();
@@ -1960,7 +2033,9 @@ __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int po
         reinterpret_cast<uint32_t*>(st)[lane] = reinterpret_cast<const uint32_t*>(static_cast<const CarCore*>(&P.cars[ci]))[lane];
     wave_lds_sync();
     const int pol = policy == FTGP_POLICY_PER_CAR ? P.car_policy[ci % P.cars_per_env] : policy;
-    if (is_net_policy(pol)) policy_apply_net(net_table(&P), pol - FTGP_POLICY_NET0, scan, P.eighth, st);
+    if (is_net_policy(pol))
+        policy_apply_net(net_table(&P), pol - FTGP_POLICY_NET0, scan, P.eighth, st,
+                         [&] { return P.path + (size_t)(env_track ? env_track[ci / P.cars_per_env] : 0) * 2 * FTGP_PATH_POINTS; });
     else policy_apply(P, driver_shape(&P), pol, scan, st, ci, P.steps[ci / P.cars_per_env], list, P.cover_thr + (pol == FTGP_POLICY_FAST ? P.cover_kmax + 1 : 0));
     wave_lds_sync();
     if (lane == 0) {
@@ -1999,6 +2074,7 @@ struct CollectActArgs {
     float std[2], lo[2], hi[2];
     int32_t slot, n_ext, n_rows, pad;
     int32_t ext_slot[FTGP_PAIR_STRIDE];      // index among the env's external cars -> car slot
+    const int32_t* env_track;     // the track of every env; null with one track (frame inputs: the centre-line of the car's track)
 };
 template <bool ACT>
 __global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, CollectActArgs C)
@@ -2022,7 +2098,7 @@ __global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, C
         reinterpret_cast<uint32_t*>(st)[lane] = reinterpret_cast<const uint32_t*>(static_cast<const CarCore*>(&P.cars[ci]))[lane];
     wave_lds_sync();
     float x[4];
-    net_inputs(N, win, st, x);
+    net_inputs(N, win, st, [&] { return P.path + (size_t)(C.env_track ? C.env_track[row / C.n_ext] : 0) * 2 * FTGP_PATH_POINTS; }, x);
     const int n_in = N->width[0];
     float* in_row = C.inputs + (size_t)row * n_in;
     #pragma unroll
@@ -2539,74 +2615,13 @@ struct DeviceFrameArgs {
     int32_t ext_index[FTGP_PAIR_STRIDE];  // as DeviceIoArgs (read with ext_out only)
 };
 
-// step 2 of the row: the pose projected on segment a -> a + 1
-struct FrameSeg { double ex, ey, L2, rx, ry, t, g2; };
-__device__ __forceinline__ FrameSeg frame_segment(const double* __restrict__ path, int a, double x, double y)
-{
-    const int b = a + 1 < FTGP_PATH_POINTS ? a + 1 : 0;
-    const double xa = path[2 * a], ya = path[2 * a + 1];
-    FrameSeg g;
-    g.ex = path[2 * b] - xa; g.ey = path[2 * b + 1] - ya;
-    g.L2 = g.ex * g.ex + g.ey * g.ey;
-    g.rx = x - xa; g.ry = y - ya;
-    if (g.L2 == 0.0) { g.ex = 1.0; g.ey = 0.0; g.L2 = 1.0; g.t = 0.0; }
-    else {
-        const double t = (g.rx * g.ex + g.ry * g.ey) / g.L2;
-        g.t = t < 0.0 ? 0.0 : t > 1.0 ? 1.0 : t;
-    }
-    const double fx = xa + g.t * g.ex, fy = ya + g.t * g.ey;
-    const double gx = x - fx, gy = y - fy;
-    g.g2 = gx * gx + gy * gy;
-    return g;
-}
-
-// step 5: the fixed entries of the segment taken; s comes back unrounded
-__device__ __forceinline__ float4 frame_fixed(const FrameSeg& g, int a, double ch, double sh, double& s_out)
-{
-    const double len = sqrt(g.L2);
-    double s = (double)a + g.t;
-    if (s >= 100.0) s = s - 100.0;
-    s_out = s;
-    return make_float4((float)((g.ex * g.ry - g.ey * g.rx) / len), (float)((g.ex * ch + g.ey * sh) / len), (float)((g.ey * ch - g.ex * sh) / len),
-                       (float)(s / 100.0));
-}
-
-// step 6: look-ahead point k behind segment a
-__device__ __forceinline__ float2 frame_ahead(const double* __restrict__ path, int a, int k, int stride, double x, double y, double ch, double sh)
-{
-    const int q = (a + 1 + k * stride) % FTGP_PATH_POINTS;
-    const double dx = path[2 * q] - x, dy = path[2 * q + 1] - y;
-    return make_float2((float)(dx * ch + dy * sh), (float)(dy * ch - dx * sh));
-}
+// steps 1 - 6, element by element: ftgp_frame.h (frame_dist2, frame_nearer, frame_segment, frame_fixed, frame_ahead)
 
 // The whole row by one lane (ftgp_io_finish_signals_kernel, the spawn pose of an env it has just reset): the operations of
-// ftgp_io_frame_kernel on the same values, the search as the progress block runs it.
+// ftgp_io_frame_kernel on the same values, the search as the progress block runs it (frame_row).
 __device__ __forceinline__ void frame_row_lane(const double* __restrict__ path, const CarCore& a, int n_ahead, int stride, float* __restrict__ o)
 {
-    const double x = a.x, y = a.y;
-    double best = 0.0; int c = 0;
-    #pragma unroll 1
-    for (int i = 0; i < FTGP_PATH_POINTS; ++i) {
-        const double dx = path[2 * i] - x, dy = path[2 * i + 1] - y;
-        const double d = dx * dx + dy * dy;
-        if (i == 0 || d < best) { best = d; c = i; }
-    }
-    const int pa = c > 0 ? c - 1 : FTGP_PATH_POINTS - 1;
-    FrameSeg g = frame_segment(path, c, x, y);
-    int seg = c;
-    {
-        const FrameSeg ga = frame_segment(path, pa, x, y);
-        if (ga.g2 < g.g2) { g = ga; seg = pa; }
-    }
-    const double ch = a.qw * a.qw - a.qz * a.qz, sh = 2.0 * (a.qw * a.qz);
-    double s;
-    const float4 f = frame_fixed(g, seg, ch, sh, s);
-    o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = f.w;
-    #pragma unroll 1
-    for (int k = 0; k < n_ahead; ++k) {
-        const float2 p = frame_ahead(path, seg, k, stride, x, y, ch, sh);
-        o[FTGP_FRAME_FIXED + 2 * k] = p.x; o[FTGP_FRAME_FIXED + 2 * k + 1] = p.y;
-    }
+    frame_row(path, a.x, a.y, a.qw, a.qz, n_ahead, stride, o);
 }
 
 // Sixteen lanes per car, one DPP row; a wave holds four cars, a workgroup sixteen.  Lane l walks points l, l + 16, ... and keeps its
@@ -2662,7 +2677,7 @@ __global__ void __launch_bounds__(FTGP_FRAME_THREADS) ftgp_io_frame_kernel(Devic
     if (l == 0) {
         if (take_a) g = frame_segment(path, pa, x, y);
         double s;
-        const float4 f = frame_fixed(g, seg, ch, sh, s);
+        const FrameFixed f = frame_fixed(g, seg, ch, sh, s);
         if (row) { row[0] = f.x; row[1] = f.y; row[2] = f.z; row[3] = f.w; }
         if (ext) { ext[0] = f.x; ext[1] = f.y; ext[2] = f.z; ext[3] = f.w; }
         if (F.s_out) F.s_out[ci] = s;
@@ -2670,7 +2685,7 @@ __global__ void __launch_bounds__(FTGP_FRAME_THREADS) ftgp_io_frame_kernel(Devic
         if (F.c_out) F.c_out[ci] = c;
     }
     if (l < F.n_ahead) {
-        const float2 p = frame_ahead(path, seg, l, F.stride, x, y, ch, sh);
+        const FramePoint p = frame_ahead(path, seg, l, F.stride, x, y, ch, sh);
         if (row) { row[FTGP_FRAME_FIXED + 2 * l] = p.x; row[FTGP_FRAME_FIXED + 2 * l + 1] = p.y; }
         if (ext) { ext[FTGP_FRAME_FIXED + 2 * l] = p.x; ext[FTGP_FRAME_FIXED + 2 * l + 1] = p.y; }
     }

@@ -87,6 +87,8 @@ FTGP_HD float ftgp_net_guarded(float a, bool both_finite) { return both_finite ?
 
 // ---- shapes: what ftgp_set_net checks, and the sizes that follow from a description ----
 FTGP_HD int ftgp_net_inputs(const FtgpNetDesc* d) { return d->n_beams + (d->use_state ? FTGP_NET_STATE_INPUTS : 0); }
+// the frame entries behind them (ftgp_set_net_frame): none without the struct or with enabled == 0
+FTGP_HD int ftgp_net_frame_inputs(const FtgpNetFrame* f) { return (f && f->enabled) ? FTGP_FRAME_FIXED + 2 * f->n_ahead : 0; }
 // number of binary32 parameters in the caller's layout: per layer W[n_out][n_in], then b[n_out]
 FTGP_HD size_t ftgp_net_param_count(const FtgpNetDesc* d)
 {

@@ -300,7 +300,9 @@ def main(argv=None):
                          "for every car, or -- roster -- with each car's own, when the roster names only the reference's bundled drivers "
                          "and \"net\"; net: the network of --net for every car")
     ap.add_argument("--net", default=None, help="a network saved by ft_grandprix_amd.net.NetSpec.save (.npz): --device-policy net runs it for every "
-                                                "car, --device-policy roster for the roster entries whose \"driver\" is \"net\"")
+                                                "car, --device-policy roster for the roster entries whose \"driver\" is \"net\".  The file's "
+                                                "frame, lookahead and lookahead_stride fields give the network the track-frame row as inputs "
+                                                "behind the beams and the state (a file without them: none)")
     ap.add_argument("--lidar", default="rangefinder", choices=("rangefinder", "fakelidar"))
     ap.add_argument("--report", type=int, default=0, help="print the standings every this many steps")
     args = ap.parse_args(argv)

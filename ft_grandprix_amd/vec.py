@@ -159,6 +159,11 @@ class DeviceVecEnv:
     held for ``action_repeat`` steps -- with ``action_repeat > 1`` a net slot is a different driver from the same network run as an
     agent.  What a net slot sees is what an agent is given with ``scan_pool`` / ``scan_max_range`` / ``state=True`` equal to the
     network's description: the beams ``beam_first .. beam_first + n_beams - 1`` of ``obs`` and entries 0 - 4 of ``state``.
+    With frame inputs (``NetSpec(frame=, lookahead=, lookahead_stride=)``, ftgp_set_net_frame) the train-to-deploy rule is: a net slot
+    with (``frame``, ``lookahead``, ``lookahead_stride``) sees ``cat(obs[beams], state[:5], frame)`` of an agent whose env has the same
+    three settings (``track_frame``, ``lookahead``, ``lookahead_stride``).  The slot's frame inputs do not depend on the env's own
+    frame setting: a net slot with frame inputs runs in an env that has the frame off.  ``nets=``, ``set_net`` and ``collect`` follow
+    the spec; ``Rollout.inputs`` is as wide as the spec's ``n_in``.
 
     Collected rollouts (ftgp_collect_device): ``collect(n_decisions, slot=0, std=, clip=, noise=, next_inputs=, out=)`` runs T decisions
     of network slot ``slot`` for every agent in one call that only enqueues and returns a ``Rollout`` of torch tensors -- what the

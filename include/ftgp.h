@@ -795,6 +795,39 @@ int ftgp_set_net(FtgpEnv *env, int slot, const FtgpNetDesc *desc, const float *p
 int ftgp_set_net_device(FtgpEnv *env, void *stream, int slot, const float *params);
 int ftgp_get_net(FtgpEnv *env, int slot, FtgpNetDesc *desc_out, float *params_out);
 
+/* Frame inputs: the track frame behind the beams and the state inputs, so that a policy trained on the device step's frame row
+ * (ftgp_device_io_frame) can be a roster slot, be evaluated in one launch and be collected (ftgp_collect_device).
+ * ftgp_set_net_frame is ftgp_set_net with one more struct; frame == NULL or enabled == 0 is ftgp_set_net to the letter, and
+ * ftgp_set_net keeps defining a slot without frame inputs.
+ *
+ * Input width.  n_in = n_beams + 5*use_state + enabled*(FTGP_FRAME_FIXED + 2*n_ahead), 1 <= n_in <= FTGP_NET_MAX_INPUTS.  The frame
+ * entries come last: inputs n_in - (FTGP_FRAME_FIXED + 2*n_ahead) .. n_in - 1 are entries 0, 1, .. of the frame row.
+ * Frame entries.  The frame row of "Track frame" above, steps 1 - 6 verbatim, with the SLOT's n_ahead and stride: binary64 with one
+ * rounding per operation, each entry rounded once to binary32, the first-minimum rule for c, segment B on a tie.  It is evaluated at
+ * the car's record (x, y, qw, qz) at the moment the driver runs -- where the state inputs are taken -- and on a multi-track handle
+ * with the path of the env's track.  The slot's frame inputs do not depend on ftgp_device_io_frame being on, nor on its n_ahead and
+ * stride; they equal the device step's `frame` row of the same record when the two settings agree.  So what a net slot sees is what
+ * an agent is given: cat(obs[beam_first .. beam_first + n_beams), state[0 .. 5), frame) of an agent whose env has scan_pool = pool,
+ * scan_max_range = max_range and the same (n_ahead, stride).  Rival rows as inputs are not part of this.
+ * A finished car still gets (0, 0) before the network is looked at.  ftgp_collect_device's x, inputs and next_inputs are this wider
+ * vector, for a finished car too.  ftgp_get_net returns the parameters with the slot's true n_in (the first layer has n_in columns),
+ * and ftgp_set_net_device takes them so: the same layout, a larger count.  The env-state record and the parameter block's layout are
+ * what they were.
+ *
+ * The setter carries all of ftgp_set_net's checks and, before anything changes (a refused call leaves a defined slot in force),
+ * FTGP_ERR_ARG naming the field for: enabled not 0 or 1; n_ahead outside 0 .. FTGP_MAX_LOOKAHEAD or stride outside 1 .. 50 -- checked
+ * with enabled == 0 too, as ftgp_device_io_frame checks its struct --; reserved != 0; n_in > FTGP_NET_MAX_INPUTS.
+ * ftgp_get_net_frame (host): the frame inputs of a defined slot as the setter was given them; a slot defined without frame inputs
+ * reads {0, 0, 0, 0}.  FTGP_ERR_STATE for a slot not defined. */
+typedef struct FtgpNetFrame {     /* 16 bytes */
+    int32_t enabled;              /* 0 or 1: the frame row behind the beams and the state inputs */
+    int32_t n_ahead;              /* look-ahead points, 0 .. FTGP_MAX_LOOKAHEAD */
+    int32_t stride;               /* path points between two of them, 1 .. 50 */
+    int32_t reserved;             /* 0 */
+} FtgpNetFrame;
+int ftgp_set_net_frame(FtgpEnv *env, int slot, const FtgpNetDesc *desc, const FtgpNetFrame *frame, const float *params);
+int ftgp_get_net_frame(FtgpEnv *env, int slot, FtgpNetFrame *frame_out);
+
 /* ---- Collected rollouts: T decisions of a network on the device, written down (no reference counterpart) ------------------------------
  * ftgp_collect_device drives every external slot of a device-io handle with network slot `slot` for n_decisions = T decisions, with
  * optional exploration noise, and records per decision what the network saw, what it proposed, what was applied and what came back.
@@ -804,7 +837,8 @@ int ftgp_get_net(FtgpEnv *env, int slot, FtgpNetDesc *desc_out, float *params_ou
  * nothing else is contracted.  Comparisons with a NaN are false.  Decision t = 0 .. T-1:
  *   1. Act.  For external car i of env e, at the records and scans as they stand: x = the network's input vector exactly as "Scan
  *      input" and "State input" of ftgp_set_net define it -- the beams from the car's ftgp_get_lidar row, the state entries 0 - 4 from
- *      the car's record with the controls then in force.  inputs[t][e][i] = x, for a finished car too.  A finished car gets mean =
+ *      the car's record with the controls then in force, and, for a slot with frame inputs (ftgp_set_net_frame), the frame row of that
+ *      record behind them.  inputs[t][e][i] = x, for a finished car too.  A finished car gets mean =
  *      action = (0, 0) and the network is not looked at (the network driver's rule).  Otherwise, with y = the layers on x and k = 0, 1:
  *        m_k = fmaf(y_k, out_scale[k], out_offset[k])
  *        a_k = fmaf(std[k], noise[t][e][i][k], m_k)              (noise = NULL: every draw is 0; 0 * infinity is a NaN)

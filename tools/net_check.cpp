@@ -6,17 +6,34 @@
 //         float max_range, out_scale[2], out_offset[2]; float params[n_params] (ftgp_set_net's layout);
 //         float ranges[n_cars][n_rays]; double record[n_cars][7] = qw, qz, vx, vy, wz, u_speed, u_steer.
 // Output: double ctrl[n_cars][2].
+// Frame mode (net_check --frame in.bin out.bin; include/ftgp.h: ftgp_set_net_frame): the network's frame inputs with the shipped element
+// operations of csrc/ftgp_frame.h, for tests/test_net_frame.py and tests/net_frame_model.py.  The input has, behind out_offset, int32
+// frame[3] = enabled, n_ahead, stride; n_params counts the first layer with the true n_in; a record is double[9] = qw, qz, vx, vy, wz,
+// u_speed, u_steer, x, y; behind the records double path[100][2].  It prints every car's full input vector and its controls, and the
+// output is float inputs[n_cars][n_in], then double ctrl[n_cars][2].
 #include "../ft_grandprix_amd/csrc/ftgp_net.h"
+#include "../ft_grandprix_amd/csrc/ftgp_frame.h"
+#include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
 
 int main(int argc, char** argv)
 {
-    if (argc != 3) { fprintf(stderr, "usage: net_check in.bin out.bin\n"); return 2; }
+    const bool frame_mode = argc == 4 && !strcmp(argv[1], "--frame");
+    if (argc != 3 && !frame_mode) { fprintf(stderr, "usage: net_check [--frame] in.bin out.bin\n"); return 2; }
+    if (frame_mode) { ++argv; }
     FILE* f = fopen(argv[1], "rb"); if (!f) { perror("open"); return 2; }
     int32_t h[14]; float g[5];
     if (fread(h, 4, 14, f) != 14 || fread(g, 4, 5, f) != 5) return 2;
+    FtgpNetFrame fr{};
+    if (frame_mode) {
+        int32_t q[3];
+        if (fread(q, 4, 3, f) != 3) return 2;
+        fr.enabled = q[0]; fr.n_ahead = q[1]; fr.stride = q[2];
+        if ((fr.enabled != 0 && fr.enabled != 1) || fr.n_ahead < 0 || fr.n_ahead > FTGP_MAX_LOOKAHEAD || fr.stride < 1 || fr.stride > 50) { fprintf(stderr, "bad frame\n"); return 2; }
+    }
+    const int n_frame = ftgp_net_frame_inputs(&fr), rec_w = frame_mode ? 9 : 7;
     const int n_rays = h[0], n_cars = h[1];
     FtgpNetDesc d{};
     d.pool = h[2]; d.beam_first = h[3]; d.n_beams = h[4]; d.use_state = h[5]; d.n_layers = h[6];
@@ -25,20 +42,30 @@ int main(int argc, char** argv)
     d.max_range = g[0]; d.out_scale[0] = g[1]; d.out_scale[1] = g[2]; d.out_offset[0] = g[3]; d.out_offset[1] = g[4];
     const int eighth = (int)(n_rays / 8.0);
     if (n_rays < 1 || n_cars < 1 || d.pool < 1 || n_rays % d.pool || d.n_beams < 1 || d.n_layers < 1 || d.n_layers > FTGP_NET_MAX_LAYERS ||
-        d.beam_first * d.pool < eighth || (d.beam_first + d.n_beams) * d.pool > n_rays - eighth || ftgp_net_inputs(&d) > FTGP_NET_MAX_INPUTS ||
-        (size_t)h[13] != ftgp_net_param_count(&d)) { fprintf(stderr, "bad description\n"); return 2; }
+        d.beam_first * d.pool < eighth || (d.beam_first + d.n_beams) * d.pool > n_rays - eighth || ftgp_net_inputs(&d) + n_frame > FTGP_NET_MAX_INPUTS ||
+        (size_t)h[13] != ftgp_net_param_count(&d) + (size_t)d.width[0] * (size_t)n_frame) { fprintf(stderr, "bad description\n"); return 2; }
     std::vector<float> params((size_t)h[13]), ranges((size_t)n_cars * n_rays);
-    std::vector<double> rec((size_t)n_cars * 7), ctrl((size_t)n_cars * 2);
+    std::vector<double> rec((size_t)n_cars * rec_w), ctrl((size_t)n_cars * 2), path((size_t)2 * FTGP_PATH_POINTS);
     if (fread(params.data(), 4, params.size(), f) != params.size() || fread(ranges.data(), 4, ranges.size(), f) != ranges.size() ||
         fread(rec.data(), 8, rec.size(), f) != rec.size()) return 2;
+    if (frame_mode && fread(path.data(), 8, path.size(), f) != path.size()) return 2;
     fclose(f);
+    const int n_in0 = ftgp_net_inputs(&d) + n_frame;
+    std::vector<float> inputs((size_t)n_cars * n_in0);
     const float inv = 1.0f / d.max_range;
     for (int c = 0; c < n_cars; ++c) {
         float x[FTGP_NET_MAX_INPUTS], y[FTGP_NET_MAX_INPUTS];
         for (int b = 0; b < d.n_beams; ++b) x[b] = ftgp_net_beam(&ranges[(size_t)c * n_rays + (size_t)(d.beam_first + b) * d.pool], d.pool, d.max_range, inv);
-        const double* r = &rec[(size_t)c * 7];
+        const double* r = &rec[(size_t)c * rec_w];
         if (d.use_state) for (int q = 0; q < FTGP_NET_STATE_INPUTS; ++q) x[d.n_beams + q] = ftgp_net_state(q, r[0], r[1], r[2], r[3], r[4], r[5], r[6]);
-        int n_in = ftgp_net_inputs(&d);
+        if (n_frame) frame_row(path.data(), r[7], r[8], r[0], r[1], fr.n_ahead, fr.stride, x + ftgp_net_inputs(&d));      // the frame entries come last
+        int n_in = n_in0;
+        for (int k = 0; k < n_in0; ++k) inputs[(size_t)c * n_in0 + k] = x[k];
+        if (frame_mode) {
+            printf("car %d: inputs", c);
+            for (int k = 0; k < n_in0; ++k) printf(" %a", (double)x[k]);
+            printf("\n");
+        }
         const float* p = params.data();
         for (int l = 0; l < d.n_layers; ++l) {
             const int n_out = d.width[l], act = l + 1 < d.n_layers ? d.hidden_act : d.out_act;
@@ -55,6 +82,7 @@ int main(int argc, char** argv)
         printf("car %d: speed %a steer %a\n", c, ctrl[2 * c], ctrl[2 * c + 1]);
     }
     FILE* o = fopen(argv[2], "wb"); if (!o) { perror("open"); return 2; }
+    if (frame_mode) fwrite(inputs.data(), 4, inputs.size(), o);
     fwrite(ctrl.data(), 8, ctrl.size(), o);
     fclose(o);
     return 0;

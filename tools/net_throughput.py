@@ -7,6 +7,9 @@ with one agent whose network torch evaluates.
 rollout rows: one launch of --steps steps per measurement, --launches of them after one warm-up launch; env-steps/s from the wall clock
 around the launch and its synchronisation, and the step kernel's own time from ftgp_last_kernel_ms.  The network is a random
 85 -> 64 -> 64 -> 2 tanh MLP on beams 14 .. 93 of pool 10 and the five state inputs (at another --rays: the beams of the scan window).
+The "rollout net0 frame" and "collect ... frame inputs" rows run an 85 + 4 + 2 * 8 -> 64 -> 64 -> 2 network: the same inputs and the
+track-frame row with eight look-ahead points behind them (ftgp_set_net_frame) -- what the frame inputs cost beside the same network
+without them.
 agent row: DeviceVecEnv(roster=["agent"], scan_pool, scan_max_range, state=True), the same network as an nn.Sequential evaluated by
 torch before every call, --calls calls of one step; per-call time from HIP events on torch's stream.
 collect row: the same env with the network in slot 0, DeviceVecEnv.collect (ftgp_collect_device) of --decisions decisions a call with
@@ -54,14 +57,15 @@ def main():
     fields = dict(pool=a.pool, max_range=10.0, beam_first=first, n_beams=n_beams, use_state=True, out_scale=(2.0, 0.6), out_offset=(2.5, 0.0))
     module = make_module(n_beams + 5)
     spec = net.from_torch(module, **fields)
+    spec_frame = net.from_torch(make_module(n_beams + 5 + 4 + 2 * 8), lookahead=8, lookahead_stride=1, **fields)
     track = load_track(a.track)
     rows = a.rows.split(",")
     if "rollout" in rows:
         lib = capi.load()
-        for policy in ("lobotomy", "fast", "net0"):
+        for policy, what in (("lobotomy", None), ("fast", None), ("net0", spec), ("net0", spec_frame)):
             with capi.Env(lib, track, n_envs=a.envs, n_rays=a.rays, spawn_mode=1, seed=7) as g:
-                if policy == "net0":
-                    g.set_net(0, spec.layers, **spec.input_fields())
+                if what is not None:
+                    g.set_net(0, what.layers, **what.input_fields())
                 g.rollout(policy, a.steps)
                 g.steps()
                 wall, kern = [], []
@@ -70,7 +74,7 @@ def main():
                     g.rollout(policy, a.steps)
                     kern.append(g.last_kernel_ms())
                     wall.append(time.perf_counter() - t0)
-                print(json.dumps({"row": f"rollout {policy}", "envs": a.envs, "rays": a.rays, "steps": a.steps, "kernel": g.kernel_name(),
+                print(json.dumps({"row": f"rollout {policy}" + (" frame" if what is spec_frame else ""), "envs": a.envs, "rays": a.rays, "steps": a.steps, "kernel": g.kernel_name(),
                                   "env_steps_per_s": a.envs * a.steps / float(np.median(wall)), "kernel_ms_median": float(np.median(kern)),
                                   "kernel_us_per_step": 1e3 * float(np.median(kern)) / a.steps, "off_track": int(g.progress()[:, 5].sum())}), flush=True)
     if "agent" in rows:
@@ -99,10 +103,11 @@ def main():
         print(json.dumps({"row": "device step, torch evaluates the network", "envs": a.envs, "rays": a.rays, "calls": a.calls,
                           "env_steps_per_s": a.envs * a.calls / wall, "us_per_call_events": 1e3 * e0.elapsed_time(e1) / a.calls}), flush=True)
         venv.close()
-    if "collect" in rows:
+    collect_rows = ((spec, "collect, network on the device"), (spec_frame, "collect, network on the device, frame inputs")) if "collect" in rows else ()
+    for the_spec, label in collect_rows:
         from ft_grandprix_amd.vec import DeviceVecEnv
         venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, roster=["agent"], scan_pool=a.pool, scan_max_range=10.0, state=True, spawn_mode=1, seed=7,
-                            nets={0: spec})
+                            nets={0: the_spec})
         dev = venv.device
         venv.reset()
         kw = dict(std=(0.3, 0.1), clip=((0.0, 5.0), (-0.6, 0.6)), noise=True, next_inputs=True)
@@ -117,7 +122,7 @@ def main():
         torch.cuda.synchronize(dev)
         wall = time.perf_counter() - t0
         n = a.launches * a.decisions
-        print(json.dumps({"row": "collect, network on the device", "envs": a.envs, "rays": a.rays, "calls": a.launches, "decisions_per_call": a.decisions,
+        print(json.dumps({"row": label, "n_in": the_spec.n_in, "envs": a.envs, "rays": a.rays, "calls": a.launches, "decisions_per_call": a.decisions,
                           "env_steps_per_s": a.envs * n / wall, "us_per_decision_events": 1e3 * e0.elapsed_time(e1) / n,
                           "us_per_decision_wall": 1e6 * wall / n, "ends": int((roll.terminated | roll.truncated).sum())}), flush=True)
         venv.close()
