@@ -108,7 +108,7 @@ API_SYMBOLS = (
     "device_io_rivals", "step_device_rivals", "rivals_device", "get_rivals",
     "set_dynamics", "set_dynamics_device", "get_dynamics",
     "env_state_bytes", "save_envs_device", "load_envs_device", "get_env_state_rejected", "obs_device",
-    "set_net", "set_net_device", "get_net", "set_net_frame", "get_net_frame",
+    "set_net", "set_net_device", "get_net", "set_net_frame", "get_net_frame", "set_net_rivals", "get_net_rivals",
     "collect_device",
 )
 
@@ -172,6 +172,10 @@ class FtgpNetFrame(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("n_ahead", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FtgpNetRivals(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("n_rivals", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class FtgpCollect(C.Structure):
     _fields_ = [("stream", C.c_void_p), ("slot", C.c_int32), ("n_decisions", C.c_int32), ("std", C.c_float * 2), ("lo", C.c_float * 2),
                 ("hi", C.c_float * 2), ("noise", C.c_void_p), ("inputs", C.c_void_p), ("mean", C.c_void_p), ("action", C.c_void_p),
@@ -215,12 +219,27 @@ def net_frame_inputs(f) -> int:
     return FRAME_FIXED + 2 * f.n_ahead if f is not None and f.enabled else 0
 
 
+def net_rivals(rivals=False, n_rivals=0) -> "FtgpNetRivals":
+    """The FtgpNetRivals of ftgp_set_net_rivals with its checks (ValueError): n_rivals 0 .. 7, checked with rivals off too;
+    ``n_rivals > 0`` implies ``rivals``, as ``lookahead`` does for ``frame``."""
+    if isinstance(n_rivals, bool) or not isinstance(n_rivals, (int, np.integer)) or not 0 <= int(n_rivals) <= MAX_RIVALS:
+        raise ValueError(f"n_rivals: an integer in 0 .. {MAX_RIVALS}, got {n_rivals!r}")
+    return FtgpNetRivals(enabled=1 if (rivals or int(n_rivals) > 0) else 0, n_rivals=int(n_rivals))
+
+
+def net_rival_inputs(r) -> int:
+    """Rival entries at the end of the input vector: 0 without rival inputs (``r`` an FtgpNetRivals or None)."""
+    return RIVAL_FIXED + RIVAL_FLOATS * r.n_rivals if r is not None and r.enabled else 0
+
+
 def net_desc(layers, *, pool, max_range, beam_first, n_beams, use_state=False, hidden_act="tanh", out_act="tanh",
-             out_scale=(1, 1), out_offset=(0, 0), frame=False, lookahead=0, lookahead_stride=1):
+             out_scale=(1, 1), out_offset=(0, 0), frame=False, lookahead=0, lookahead_stride=1, rivals=False, n_rivals=0):
     """(FtgpNetDesc, flat float32 parameters) of a network given as a list of (W [n_out, n_in], b [n_out]) pairs, with every check of
     ftgp_set_net and ftgp_set_net_frame that needs no handle (ValueError): the widths, the activations, the output map, the shapes of
-    the arrays, the frame fields (``net_frame`` makes the struct).  The window rule needs n_rays: ``check_net_window``."""
+    the arrays, the frame fields (``net_frame`` makes the struct) and the rival fields (``net_rivals``).  The window rule needs n_rays:
+    ``check_net_window``."""
     n_frame = net_frame_inputs(net_frame(frame, lookahead, lookahead_stride))
+    n_rival = net_rival_inputs(net_rivals(rivals, n_rivals))
     layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
     if not 1 <= len(layers) <= NET_MAX_LAYERS:
         raise ValueError(f"a network has 1 .. {NET_MAX_LAYERS} layers, got {len(layers)}")
@@ -228,9 +247,9 @@ def net_desc(layers, *, pool, max_range, beam_first, n_beams, use_state=False, h
         raise ValueError(f"pool >= 1, n_beams >= 1, beam_first >= 0: got {pool}, {n_beams}, {beam_first}")
     if not (np.isfinite(max_range) and max_range > 0):
         raise ValueError(f"max_range must be finite and > 0, got {max_range}")
-    n_in = int(n_beams) + (NET_STATE_INPUTS if use_state else 0) + n_frame
+    n_in = int(n_beams) + (NET_STATE_INPUTS if use_state else 0) + n_frame + n_rival
     if n_in > NET_MAX_INPUTS:
-        raise ValueError(f"n_beams + 5 use_state + {n_frame} frame entries = {n_in} inputs, at most {NET_MAX_INPUTS}")
+        raise ValueError(f"n_beams + 5 use_state + {n_frame} frame entries + {n_rival} rival entries = {n_in} inputs, at most {NET_MAX_INPUTS}")
     for name, act in (("hidden_act", hidden_act), ("out_act", out_act)):
         if act not in ACT_BY_NAME:
             raise ValueError(f"{name}: one of {sorted(ACT_BY_NAME)}, got {act!r}")
@@ -265,16 +284,17 @@ def check_net_window(n_rays: int, pool: int, beam_first: int, n_beams: int):
                          f"rays [{eighth}, {n_rays - eighth}) of {n_rays}: the rear quarter of the scan is not an input")
 
 
-def net_param_count(d: FtgpNetDesc, frame=None) -> int:
-    n, n_in = 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0) + net_frame_inputs(frame)
+def net_param_count(d: FtgpNetDesc, frame=None, rivals=None) -> int:
+    n, n_in = 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0) + net_frame_inputs(frame) + net_rival_inputs(rivals)
     for l in range(d.n_layers):
         n, n_in = n + d.width[l] * n_in + d.width[l], d.width[l]
     return n
 
 
-def net_layers(d: FtgpNetDesc, flat: np.ndarray, frame=None) -> list:
-    """The (W, b) pairs of a flat parameter buffer in ftgp_set_net's layout (``frame``: the slot's FtgpNetFrame, if it has one)."""
-    out, o, n_in = [], 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0) + net_frame_inputs(frame)
+def net_layers(d: FtgpNetDesc, flat: np.ndarray, frame=None, rivals=None) -> list:
+    """The (W, b) pairs of a flat parameter buffer in ftgp_set_net's layout (``frame``, ``rivals``: the slot's FtgpNetFrame and
+    FtgpNetRivals, if it has them)."""
+    out, o, n_in = [], 0, d.n_beams + (NET_STATE_INPUTS if d.use_state else 0) + net_frame_inputs(frame) + net_rival_inputs(rivals)
     for l in range(d.n_layers):
         n_out = d.width[l]
         W = flat[o:o + n_out * n_in].reshape(n_out, n_in); o += n_out * n_in
@@ -385,6 +405,8 @@ class CLib:
             "get_net": (i32, [vp, i32, C.POINTER(FtgpNetDesc), dp]),
             "set_net_frame": (i32, [vp, i32, C.POINTER(FtgpNetDesc), C.POINTER(FtgpNetFrame), dp]),
             "get_net_frame": (i32, [vp, i32, C.POINTER(FtgpNetFrame)]),
+            "set_net_rivals": (i32, [vp, i32, C.POINTER(FtgpNetDesc), C.POINTER(FtgpNetFrame), C.POINTER(FtgpNetRivals), dp]),
+            "get_net_rivals": (i32, [vp, i32, C.POINTER(FtgpNetRivals)]),
             "collect_device": (i32, [vp, C.POINTER(FtgpCollect)]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
@@ -683,18 +705,23 @@ class Env:
 
     # -- network drivers (include/ftgp.h: ftgp_set_net)
     def set_net(self, slot: int, layers, *, pool=None, max_range=None, beam_first=None, n_beams=None, use_state=False,
-                hidden_act="tanh", out_act="tanh", out_scale=(1, 1), out_offset=(0, 0), frame=False, lookahead=0, lookahead_stride=1):
-        """ftgp_set_net / ftgp_set_net_frame: ``layers`` = [(W [n_out, n_in], b [n_out]), ...] (torch's nn.Linear layout) becomes the
+                hidden_act="tanh", out_act="tanh", out_scale=(1, 1), out_offset=(0, 0), frame=False, lookahead=0, lookahead_stride=1,
+                rivals=False, n_rivals=0):
+        """ftgp_set_net / ftgp_set_net_frame / ftgp_set_net_rivals: ``layers`` = [(W [n_out, n_in], b [n_out]), ...] (torch's nn.Linear layout) becomes the
         network driver ``"net<slot>"``; ``layers=None`` clears the slot.  ``frame`` (or ``lookahead > 0``): the track-frame row with
-        ``lookahead`` points every ``lookahead_stride`` path points follows the beams and the state inputs."""
+        ``lookahead`` points every ``lookahead_stride`` path points follows the beams and the state inputs.  ``rivals`` (or
+        ``n_rivals > 0``): the rival row of the car's env with ``n_rivals`` mate slots follows those."""
         if layers is None:
             self._call("set_net", int(slot), None, None)
             return
         d, flat = net_desc(layers, pool=pool, max_range=max_range, beam_first=beam_first, n_beams=n_beams, use_state=use_state,
                            hidden_act=hidden_act, out_act=out_act, out_scale=out_scale, out_offset=out_offset,
-                           frame=frame, lookahead=lookahead, lookahead_stride=lookahead_stride)
+                           frame=frame, lookahead=lookahead, lookahead_stride=lookahead_stride, rivals=rivals, n_rivals=n_rivals)
         f = net_frame(frame, lookahead, lookahead_stride)
-        if f.enabled:
+        r = net_rivals(rivals, n_rivals)
+        if r.enabled:
+            self._call("set_net_rivals", int(slot), C.byref(d), C.byref(f), C.byref(r), _ptr(flat))
+        elif f.enabled:
             self._call("set_net_frame", int(slot), C.byref(d), C.byref(f), _ptr(flat))
         else:
             self._call("set_net", int(slot), C.byref(d), _ptr(flat))
@@ -706,12 +733,13 @@ class Env:
 
     def net(self, slot: int):
         """(FtgpNetDesc, [(W, b), ...]): the description and the parameters in force of a defined slot (ftgp_get_net)."""
-        d, f = FtgpNetDesc(), FtgpNetFrame()
+        d, f, r = FtgpNetDesc(), FtgpNetFrame(), FtgpNetRivals()
         self._call("get_net", int(slot), C.byref(d), None)
         self._call("get_net_frame", int(slot), C.byref(f))
-        flat = np.empty(net_param_count(d, f), dtype=np.float32)
+        self._call("get_net_rivals", int(slot), C.byref(r))
+        flat = np.empty(net_param_count(d, f, r), dtype=np.float32)
         self._call("get_net", int(slot), C.byref(d), _ptr(flat))
-        return d, net_layers(d, flat, f)
+        return d, net_layers(d, flat, f, r)
 
     def net_frame(self, slot: int) -> dict:
         """The frame inputs of a defined slot (ftgp_get_net_frame): ``dict(frame, lookahead, lookahead_stride)``, set_net's keywords."""
@@ -719,9 +747,18 @@ class Env:
         self._call("get_net_frame", int(slot), C.byref(f))
         return dict(frame=bool(f.enabled), lookahead=int(f.n_ahead), lookahead_stride=int(f.stride) if f.enabled else 1)
 
+    def net_rivals(self, slot: int) -> dict:
+        """The rival inputs of a defined slot (ftgp_get_net_rivals): ``dict(rivals, n_rivals)``, set_net's keywords."""
+        r = FtgpNetRivals()
+        self._call("get_net_rivals", int(slot), C.byref(r))
+        return dict(rivals=bool(r.enabled), n_rivals=int(r.n_rivals))
+
     def get_net(self, slot: int):
-        """(FtgpNetDesc, [(W, b), ...], dict(frame, lookahead, lookahead_stride)): ``net`` and ``net_frame`` of a defined slot."""
-        return self.net(slot) + (self.net_frame(slot),)
+        """(FtgpNetDesc, [(W, b), ...], dict(frame, lookahead, lookahead_stride)): ``net`` and ``net_frame`` of a defined slot; for a slot
+        with rival inputs the dict has ``net_rivals``' two fields (rivals, n_rivals) as well -- set_net's keywords, so
+        ``set_net(slot, layers, **fields_of_the_description, **that_dict)`` defines the same slot again."""
+        r = self.net_rivals(slot)
+        return self.net(slot) + ({**self.net_frame(slot), **(r if r["rivals"] else {})},)
 
     # -- collected rollouts (include/ftgp.h: ftgp_collect_device)
     def collect_device(self, n_decisions: int, inputs: int, mean: int, action: int, reward: int, terminated: int, truncated: int, *,

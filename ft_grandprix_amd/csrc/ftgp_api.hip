@@ -199,6 +199,7 @@ struct FtgpEnv {
     NetDev nets[FTGP_MAX_NETS] = {};  // their host mirror (defined = 0: an empty slot)
     FtgpNetDesc net_desc[FTGP_MAX_NETS] = {};     // the descriptions as the caller gave them (ftgp_get_net)
     FtgpNetFrame net_frame[FTGP_MAX_NETS] = {};   // ... and the frame inputs (ftgp_get_net_frame); zeros = none
+    FtgpNetRivals net_rivals[FTGP_MAX_NETS] = {}; // ... and the rival inputs (ftgp_get_net_rivals); zeros = none
     DevBuf<float> d_net_params[FTGP_MAX_NETS];    // the slots' parameters in the library's layout
     bool last_net = false;            // the newest launch ran a NET instantiation
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
@@ -2009,6 +2010,20 @@ static int check_net_frame(const FtgpNetDesc& d, const FtgpNetFrame& f)
     return 0;
 }
 
+// what ftgp_set_net_rivals checks beyond that: the rivals struct (n_rivals holds for a struct that is off too) and the width with the
+// rival entries behind the frame's
+static int check_net_rivals(const FtgpNetDesc& d, const FtgpNetFrame* f, const FtgpNetRivals& r)
+{
+    if (r.enabled != 0 && r.enabled != 1) return failf(FTGP_ERR_ARG, "ftgp_set_net_rivals: enabled = %d must be 0 or 1", r.enabled);
+    if (r.n_rivals < 0 || r.n_rivals > FTGP_MAX_RIVALS) return failf(FTGP_ERR_ARG, "ftgp_set_net_rivals: n_rivals = %d outside 0 .. %d", r.n_rivals, FTGP_MAX_RIVALS);
+    if (r.reserved[0] != 0 || r.reserved[1] != 0) return fail(FTGP_ERR_ARG, "ftgp_set_net_rivals: reserved must be 0%s");
+    const int n_in = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f) + ftgp_net_rival_inputs(&r);
+    if (n_in > FTGP_NET_MAX_INPUTS)
+        return failf(FTGP_ERR_ARG, "ftgp_set_net_rivals: n_in = n_beams + 5 use_state + %d frame entries + %d rival entries = %d inputs, at most %d",
+                     ftgp_net_frame_inputs(f), ftgp_net_rival_inputs(&r), n_in, FTGP_NET_MAX_INPUTS);
+    return 0;
+}
+
 // floats of a slot's parameters in the caller's layout: per layer W[n_out][n_in], then b[n_out], with the slot's true n_in
 static size_t net_param_count(const NetDev& N)
 {
@@ -2017,14 +2032,15 @@ static size_t net_param_count(const NetDev& N)
     return n;
 }
 
-// the record of a description: the library's layout (NetDev) without the buffer's address; f = null: no frame inputs
-static NetDev net_record(const FtgpNetDesc& d, const FtgpNetFrame* f)
+// the record of a description: the library's layout (NetDev) without the buffer's address; f = null: no frame inputs, r = null: no rival inputs
+static NetDev net_record(const FtgpNetDesc& d, const FtgpNetFrame* f, const FtgpNetRivals* r)
 {
     NetDev N{};
     N.defined = 1; N.pool = d.pool; N.beam_first = d.beam_first; N.n_beams = d.n_beams; N.use_state = d.use_state; N.n_layers = d.n_layers;
     N.hidden_act = d.hidden_act; N.out_act = d.out_act;
-    N.width[0] = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f);
+    N.width[0] = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f) + ftgp_net_rival_inputs(r);
     if (f && f->enabled) { N.frame_first = ftgp_net_inputs(&d); N.frame_shape = f->n_ahead | f->stride << 8; }
+    if (r && r->enabled) { N.rival_first = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f); N.rival_shape = 1 | r->n_rivals << 8; }
     int o = 0;
     for (int l = 0; l < d.n_layers; ++l) {
         N.width[l + 1] = d.width[l];
@@ -2060,9 +2076,11 @@ static int ensure_nets(FtgpEnv* e)
     return 0;
 }
 
-int ftgp_set_net(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const float* params) { return ftgp_set_net_frame(e, slot, desc, nullptr, params); }
+int ftgp_set_net(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const float* params) { return ftgp_set_net_rivals(e, slot, desc, nullptr, nullptr, params); }
 
-int ftgp_set_net_frame(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const FtgpNetFrame* frame, const float* params)
+int ftgp_set_net_frame(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const FtgpNetFrame* frame, const float* params) { return ftgp_set_net_rivals(e, slot, desc, frame, nullptr, params); }
+
+int ftgp_set_net_rivals(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const FtgpNetFrame* frame, const FtgpNetRivals* rivals, const float* params)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_net: not on a FTGP_LIDAR_FAKELIDAR handle%s");
@@ -2070,6 +2088,7 @@ int ftgp_set_net_frame(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftgp
     if (desc) {
         if (int rc = check_net_desc(e, *desc)) return rc;
         if (frame) if (int rc = check_net_frame(*desc, *frame)) return rc;
+        if (rivals) if (int rc = check_net_rivals(*desc, frame, *rivals)) return rc;
         if (!params) return fail(FTGP_ERR_ARG, "ftgp_set_net: params is NULL%s");
     }
     HIP_TRY(hipSetDevice(e->device));
@@ -2078,7 +2097,7 @@ int ftgp_set_net_frame(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftgp
     NetDev N{};
     DevBuf<float> buf;
     if (desc) {
-        N = net_record(*desc, frame);
+        N = net_record(*desc, frame, rivals);
         std::vector<float> img((size_t)N.n_floats, 0.0f);     // the library's layout; the padding is zeros
         const float* src = params;
         for (int l = 0; l < N.n_layers; ++l) {
@@ -2094,6 +2113,7 @@ int ftgp_set_net_frame(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftgp
     e->nets[slot] = N;
     e->net_desc[slot] = desc ? *desc : FtgpNetDesc{};
     e->net_frame[slot] = (desc && frame && frame->enabled) ? *frame : FtgpNetFrame{};
+    e->net_rivals[slot] = (desc && rivals && rivals->enabled) ? *rivals : FtgpNetRivals{};
     e->d_net_params[slot] = std::move(buf);                   // (the old buffer goes: nothing reads it any more)
     return 0;
 }
@@ -2142,6 +2162,15 @@ int ftgp_get_net_frame(FtgpEnv* e, int slot, FtgpNetFrame* frame_out)
     if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_frame: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
     if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_frame: network slot %d is not defined (ftgp_set_net)", slot);
     if (frame_out) *frame_out = e->net_frame[slot];
+    return 0;
+}
+
+int ftgp_get_net_rivals(FtgpEnv* e, int slot, FtgpNetRivals* rivals_out)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_rivals: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_rivals: network slot %d is not defined (ftgp_set_net)", slot);
+    if (rivals_out) *rivals_out = e->net_rivals[slot];
     return 0;
 }
 

@@ -7,6 +7,7 @@
 #include "ftgp_spawn.h"
 #include "ftgp_net.h"
 #include "ftgp_frame.h"
+#include "ftgp_rival.h"
 
 #define FTGP_WAVE 64
 #define FTGP_MAX_GROUPS 256              // groups of 64 rays per car: n_rays <= 16384
@@ -183,8 +184,10 @@ struct alignas(16) NetDev {
                                                   // n_ahead | stride << 8 -- 0 = none, as ftgp_set_net leaves it (an enabled frame has stride >= 1)
     float max_range, inv_max_range, out_scale[2], out_offset[2];
     const float* params;
+    int32_t rival_first, rival_shape;             // rival inputs (ftgp_set_net_rivals): the index of the first one, and enabled | n_rivals << 8 -- 0 = none
+    int32_t pad0, pad1;
 };
-static_assert(sizeof(NetDev) == 128, "NetDev layout");
+static_assert(sizeof(NetDev) == 144, "NetDev layout");
 template <class PP> __host__ __device__ inline const NetDev* net_table(PP p) { return reinterpret_cast<const NetDev*>(((uint64_t)p->net_table_hi << 32) | (uint64_t)p->net_table_lo); }
 __host__ __device__ inline bool is_net_policy(int policy) { return policy >= FTGP_POLICY_NET0 && policy <= FTGP_POLICY_NET3; }
 

@@ -1445,6 +1445,7 @@ __device__ __forceinline__ void policy_apply(const DeviceParams& P, const Driver
 //            unrolled loop has the loads of the rows ahead in flight under the fma chain, which is sequential by specification.
 //   outputs  become the next layer's inputs in place: registers 0 and 1.
 // No LDS beyond the window, no per-car state.  `win` is the address at which sample j of the car's scan sits when j is added.
+#define FTGP_RIVAL_LANES 8             // lanes per env slot, in ftgp_io_rival_kernel and in the network driver's rival inputs
 typedef const __attribute__((address_space(4))) NetDev* ScalarNet;
 // rows [0, n) of one register's worth of inputs (n <= 64), FTGP_NET_AHEAD weights per lane at a time: the loads of the next rows are
 // issued before the fma chain of the rows at hand (sixteen more in flight spill under the step kernel's 64 VGPRs)
@@ -1546,19 +1547,135 @@ __device__ __forceinline__ float net_frame_entry(const double* __restrict__ path
     }
     return v;
 }
-// path(): the centre-line of the car's track, asked for by a slot with frame inputs only (elsewhere than in the step kernel it costs a
-// scalar load and a wait, which a launch without frame inputs does not pay)
-template <class PathFn>
-__device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __restrict__ win, const CarCore* st, PathFn path, float (&x)[4])
+// "Rival inputs" (ftgp_set_net_rivals): the rival row of the car in slot `slot` of its env, entry j into the lane that owns input
+// rival_first + j.  The wave has one car a and reads every car of the env where its record lies (`cars`: the env's slot 0 -- the
+// workgroup's LDS in the step kernel, device memory elsewhere).  Eight lanes per env slot, as ftgp_io_rival_kernel groups them: lane
+// (b, i) = 8 b + i.
+//   search    lane (b, i) walks points i, i + 8, ... of the path for car b with K3's expression and keeps its first minimum; the pair
+//             folds over xor 1, 2, 4 with frame_nearer: lane (b, 0) ends with K3's first minimum (a NaN pose: every lane keeps its own,
+//             lane (b, 0) has c = 0 as K3 does), and c is taken from that lane.
+//   segment   lanes (b, 0) and (b, 1) project on segments B and A; only t and g2 leave lane (b, 1).  Lane (b, 0) forms s_b, off_b, g_b
+//             and hands s_b and g_b to its group.
+//   a         car a's s and g reach all lanes by v_readlane at the wave-uniform lane 8 slot.
+//   place     place, n_racing and the mates are ballots and popcounts over the lanes (b, 0); the two gaps are minima folded over xor 8,
+//             16, 32 (the eight lanes of a group hold the same value).
+//   rank      lane (b, i) asks whether mate i comes before mate b in (d2, slot) order; a ballot gives mate b its rank as the popcount of
+//             byte b.
+//   entries   lane (b, q) forms entry q of mate b (rival_mate_entry) and, if b's rank is below n_rivals, sends it to the lane that owns
+//             that input -- a forward permute; every other lane sends to the lane 63 places behind rival_first, which owns no rival
+//             entry since the block is at most 60 wide.  A lane nobody sends to receives 0: the slot without a mate.
+// The phases hang on values in SGPRs (the slot, the ballots) and on s_b, g_b; the addresses of the permutes are formed on the spot (see
+// net_frame_entry).  Nothing here reads the controls, so in the step kernel no barrier is needed: dynamics_lanes() runs only after every
+// driver of the workgroup has delivered, and until then every record's pose, velocity, completion and finish fields are the previous
+// step's.  Returns the lane's entry and, in reg, the register it belongs to (-1: the lane owns none).
+__device__ __forceinline__ int32_t absolute_completion(const CarCore& a);
+__device__ __forceinline__ RivalCar rival_car(const CarCore& r, double s) { return rival_car(r.x, r.y, r.qw, r.qz, r.vx, r.vy, s); }
+__device__ __forceinline__ double net_pull_f64(int from, double v)
+{
+    return __hiloint2double(__builtin_amdgcn_ds_bpermute(from, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(from, __double2loint(v)));
+}
+// the centre-line of the car's track; the record of its env's slot 0 and the bytes from one record to the next (CarCore in LDS, CarState in
+// device memory); its slot; cars per env
+struct NetEnv { const double* path; const CarCore* cars; int stride, slot, cpe; };
+__device__ __forceinline__ const CarCore* net_env_car(const NetEnv& E, int k) { return reinterpret_cast<const CarCore*>(reinterpret_cast<const unsigned char*>(E.cars) + (size_t)k * E.stride); }
+__device__ __forceinline__ float net_rival_entry(const NetEnv E, int first, int n_rivals, int& reg)
 {
     const int lane = lane_here();
+    const int b = lane >> 3, i = lane & (FTGP_RIVAL_LANES - 1);
+    const int slot = __builtin_amdgcn_readfirstlane(E.slot), cpe = __builtin_amdgcn_readfirstlane(E.cpe);
+    const bool has = b < cpe;
+    const CarCore* rb = net_env_car(E, has ? b : slot);      // (a group that holds nobody reads a's record: in bounds, and nothing of it is used)
+    const double* __restrict__ path = E.path;
+    double s_b, g_b;
+    {
+        const double px = rb->x, py = rb->y;
+        double best = frame_dist2(path, i, px, py); int idx = i;
+        #pragma unroll 1
+        for (int p = i + FTGP_RIVAL_LANES; p < FTGP_PATH_POINTS; p += FTGP_RIVAL_LANES) {
+            const double d = frame_dist2(path, p, px, py);
+            if (d < best) { best = d; idx = p; }
+        }
+        #pragma unroll
+        for (int m = 1; m < FTGP_RIVAL_LANES; m <<= 1) {
+            const int from = (lane ^ m) << 2;
+            const double od = net_pull_f64(from, best);
+            const int oi = __builtin_amdgcn_ds_bpermute(from, idx);
+            if (frame_nearer(od, oi, best, idx)) { best = od; idx = oi; }
+        }
+        const int head = (lane & ~(FTGP_RIVAL_LANES - 1)) << 2;
+        const int c = __builtin_amdgcn_ds_bpermute(head, idx);
+        const int pa = c > 0 ? c - 1 : FTGP_PATH_POINTS - 1;
+        double t = 0.0, g2 = 0.0;
+        if (i < 2) { const FrameSeg g = frame_segment(path, i == 0 ? c : pa, px, py); t = g.t; g2 = g.g2; }
+        const double ta = net_pull_f64(head + 4, t), g2a = net_pull_f64(head + 4, g2);
+        const bool take_a = g2a < g2;                    // A only if strictly nearer
+        double s = (double)(take_a ? pa : c) + (take_a ? ta : t);
+        if (s >= 100.0) s = s - 100.0;
+        const double g = rival_progress(absolute_completion(*rb), s, c, best > 1.0);
+        s_b = net_pull_f64(head, s); g_b = net_pull_f64(head, g);
+    }
+    const int la = slot * FTGP_RIVAL_LANES;
+    const double s_a = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(s_b), la), __builtin_amdgcn_readlane(__double2loint(s_b), la));
+    const double g_a = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(g_b), la), __builtin_amdgcn_readlane(__double2loint(g_b), la));
+    const CarCore* ra = net_env_car(E, slot);
+    const bool fin_a = ra->finished != 0, fin_b = rb->finished != 0;
+    const bool other = has && b != slot;
+    const bool ahead = other && rival_ahead(fin_b, rb->finish_step, g_b, b, fin_a, ra->finish_step, g_a, slot);
+    const bool mate = other && !fin_b && !fin_a;
+    const int place = 1 + __builtin_popcountll(__builtin_amdgcn_ballot_w64(ahead && i == 0));
+    const int n_racing = __builtin_popcountll(__builtin_amdgcn_ballot_w64(has && !fin_b && i == 0));
+    float fixed;
+    {
+        double gap_ahead = (mate && ahead) ? g_b - g_a : INFINITY;
+        double gap_behind = (mate && !ahead) ? g_a - g_b : INFINITY;
+        #pragma unroll
+        for (int m = FTGP_RIVAL_LANES; m < FTGP_WAVE; m <<= 1) {
+            const int from = (lane ^ m) << 2;
+            const double oa = net_pull_f64(from, gap_ahead), ob = net_pull_f64(from, gap_behind);
+            if (oa < gap_ahead) gap_ahead = oa;
+            if (ob < gap_behind) gap_behind = ob;
+        }
+        const float f2 = gap_ahead == INFINITY ? 0.0f : (float)gap_ahead, f3 = gap_behind == INFINITY ? 0.0f : (float)gap_behind;
+        const int j = (lane - first) & (FTGP_WAVE - 1);
+        fixed = j == 0 ? (float)place : j == 1 ? (float)n_racing : j == 2 ? f2 : f3;
+    }
+    const RivalCar a = rival_car(*ra, s_a), m = rival_car(*rb, s_b);
+    int rank;
+    {
+        const double dx = m.x - a.x, dy = m.y - a.y;
+        const double d2 = dx * dx + dy * dy;
+        const uint64_t mates = __builtin_amdgcn_ballot_w64(mate);
+        const double od = net_pull_f64(i << 5, d2);      // lane (i, 0)
+        const bool before = ((mates >> (i * FTGP_RIVAL_LANES)) & 1) != 0 && (od < d2 || (od == d2 && i < b));
+        const uint64_t bal = __builtin_amdgcn_ballot_w64(before);
+        rank = __builtin_popcount((uint32_t)(bal >> (b * FTGP_RIVAL_LANES)) & 0xffu);
+    }
+    const float e = rival_mate_entry(a, m, i);
+    const int to = (mate && rank < n_rivals) ? first + FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * rank + i : first + FTGP_WAVE - 1;
+    float v = __int_as_float(__builtin_amdgcn_ds_permute((to & (FTGP_WAVE - 1)) << 2, __float_as_int(e)));
+    const int j = (lane - first) & (FTGP_WAVE - 1);               // the entry this lane owns, if j < width
+    reg = j < FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * n_rivals ? (first + j) >> 6 : -1;
+    if (j < FTGP_RIVAL_FIXED) v = fixed;
+    return v;
+}
+// env(): the centre-line of the car's track, the records of its env and its slot there, asked for by a slot with frame or rival inputs
+// only (elsewhere than in the step kernel the path costs a scalar load and a wait, which a launch without such inputs does not pay)
+template <class EnvFn>
+__device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __restrict__ win, const CarCore* st, EnvFn env, float (&x)[4])
+{
+    const int lane = lane_here();
+    // (the rival entry before everything else: its binary64 then has the registers to itself)
+    const int rshape = N->rival_shape;
+    int rival_reg = -1;
+    float rival_v = 0.0f;
+    if (rshape != 0) rival_v = net_rival_entry(env(), N->rival_first, rshape >> 8, rival_reg);      // wave-uniform: the slot's record
     const int pool = N->pool, n_beams = N->n_beams;
     const float M = N->max_range, inv = N->inv_max_range;
     // (the frame entry first: its binary64 then has the registers to itself, not the four of x as well)
     const int shape = N->frame_shape;
     int frame_reg = -1;
     float frame_v = 0.0f;
-    if (shape != 0) frame_v = net_frame_entry(path(), st, N->frame_first, shape & 0xff, shape >> 8, frame_reg);   // wave-uniform: the slot's record
+    if (shape != 0) frame_v = net_frame_entry(env().path, st, N->frame_first, shape & 0xff, shape >> 8, frame_reg);   // wave-uniform: the slot's record
     x[0] = 0.0f; x[1] = 0.0f; x[2] = 0.0f; x[3] = 0.0f;
     {
         const float* __restrict__ mine = win + (N->beam_first + lane) * pool;
@@ -1577,6 +1694,8 @@ __device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __res
     }
     #pragma unroll
     for (int r = 0; r < 4; ++r) if (frame_reg == r) x[r] = frame_v;
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) if (rival_reg == r) x[r] = rival_v;
 }
 // "Layers": x becomes the outputs of the last layer, y0 in lane 0 and y1 in lane 1 of x[0]
 __device__ __forceinline__ void net_layers(const ScalarNet N, float (&x)[4])
@@ -1609,13 +1728,13 @@ __device__ __forceinline__ ScalarNet scalar_net(const NetDev* table, int slot)
     uint64_t ta = (uint64_t)(table + slot); asm volatile("" : "+s"(ta));
     return (ScalarNet)ta;
 }
-template <class PathFn>
-__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st, PathFn path)
+template <class EnvFn>
+__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st, EnvFn env)
 {
     const ScalarNet N = scalar_net(table, slot);
     const int lane = lane_here();
     float x[4];
-    net_inputs(N, win, st, path, x);
+    net_inputs(N, win, st, env, x);
     net_layers(N, x);
     const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 0)), y1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 1));
     const float scale[2] = { N->out_scale[0], N->out_scale[1] }, offset[2] = { N->out_offset[0], N->out_offset[1] };
@@ -1624,14 +1743,14 @@ __device__ __forceinline__ void policy_net(const NetDev* table, int slot, const 
     if (lane == 0) { st->u_speed = us; st->u_steer = ut; }
 }
 // the driver FTGP_POLICY_NET0 + slot of one car: a finished car gets the null driver before the network is looked at
-template <class PathFn>
-__device__ __forceinline__ void policy_apply_net(const NetDev* table, int slot, const float* scan, int eighth, CarCore* st, PathFn path)
+template <class EnvFn>
+__device__ __forceinline__ void policy_apply_net(const NetDev* table, int slot, const float* scan, int eighth, CarCore* st, EnvFn env)
 {
     if (st->finished) {
         if (lane_id() == 0) { st->u_speed = 0.0; st->u_steer = 0.0; }
         return;
     }
-    policy_net(table, slot, scan + scan_window_first(eighth) - eighth, st, path);
+    policy_net(table, slot, scan + scan_window_first(eighth) - eighth, st, env);
 }
 
 // =============================================================================================
@@ -1918,7 +2037,8 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
             for (int c = wave; c < ncars_here; c += nwaves) {
                 if constexpr (NET) {      // the launch's driver, or some slot's, is a network: the slot's driver, networks among them
                     const int pol = policy == FTGP_POLICY_PER_CAR ? G->car_policy[c] : policy;
-                    if (is_net_policy(pol)) policy_apply_net(net_table(G), pol - FTGP_POLICY_NET0, scan_prev + c * win_floats, G->eighth, L.cars + c, [&] { return L.path; });
+                    if (is_net_policy(pol)) policy_apply_net(net_table(G), pol - FTGP_POLICY_NET0, scan_prev + c * win_floats, G->eighth, L.cars + c,
+                                                            [&] { const int cpe = G->cars_per_env, sl = c % cpe; return NetEnv{ L.path, L.cars + (c - sl), (int)sizeof(CarCore), sl, cpe }; });
                     else if (policy == FTGP_POLICY_PER_CAR)
                         policy_apply(P, driver_shape(G), pol, scan_prev + c * win_floats, L.cars + c, ci0 + c, L.steps[c], L.list + wave * FTGP_WAVE,
                                      L.cover + (pol == FTGP_POLICY_FAST ? (G->stage_cover >> 2) : 0));
@@ -2035,7 +2155,9 @@ __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int po
     const int pol = policy == FTGP_POLICY_PER_CAR ? P.car_policy[ci % P.cars_per_env] : policy;
     if (is_net_policy(pol))
         policy_apply_net(net_table(&P), pol - FTGP_POLICY_NET0, scan, P.eighth, st,
-                         [&] { return P.path + (size_t)(env_track ? env_track[ci / P.cars_per_env] : 0) * 2 * FTGP_PATH_POINTS; });
+                         [&] { const int env = ci / P.cars_per_env;
+                               return NetEnv{ P.path + (size_t)(env_track ? env_track[env] : 0) * 2 * FTGP_PATH_POINTS, P.cars + (size_t)env * P.cars_per_env,
+                                              (int)sizeof(CarState), ci - env * P.cars_per_env, P.cars_per_env }; });
     else policy_apply(P, driver_shape(&P), pol, scan, st, ci, P.steps[ci / P.cars_per_env], list, P.cover_thr + (pol == FTGP_POLICY_FAST ? P.cover_kmax + 1 : 0));
     wave_lds_sync();
     if (lane == 0) {
@@ -2098,7 +2220,9 @@ __global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, C
         reinterpret_cast<uint32_t*>(st)[lane] = reinterpret_cast<const uint32_t*>(static_cast<const CarCore*>(&P.cars[ci]))[lane];
     wave_lds_sync();
     float x[4];
-    net_inputs(N, win, st, [&] { return P.path + (size_t)(C.env_track ? C.env_track[row / C.n_ext] : 0) * 2 * FTGP_PATH_POINTS; }, x);
+    net_inputs(N, win, st, [&] { const int env = row / C.n_ext;
+                                 return NetEnv{ P.path + (size_t)(C.env_track ? C.env_track[env] : 0) * 2 * FTGP_PATH_POINTS, P.cars + (size_t)env * P.cars_per_env,
+                                                (int)sizeof(CarState), ci - env * P.cars_per_env, P.cars_per_env }; }, x);
     const int n_in = N->width[0];
     float* in_row = C.inputs + (size_t)row * n_in;
     #pragma unroll
@@ -2707,50 +2831,7 @@ struct DeviceRivalArgs {
     int32_t ext_index[FTGP_PAIR_STRIDE];  // as DeviceIoArgs (read with ext_out only)
 };
 
-// step 1: race progress from what the search found
-__device__ __forceinline__ double rival_progress(int32_t abs_completion, double s, int c, bool off)
-{
-    double f = s - (double)c;
-    if (f >= 50.0) f = f - 100.0;
-    if (f < -50.0) f = f + 100.0;
-    if (off) f = 0.0;
-    return (double)abs_completion + f;
-}
-
-// step 2: is car b (slot b) ahead of car a (slot a)?
-__device__ __forceinline__ bool rival_ahead(bool fin_b, int64_t fs_b, double g_b, int b, bool fin_a, int64_t fs_a, double g_a, int a)
-{
-    if (fin_b && fin_a) return fs_b < fs_a || (fs_b == fs_a && b < a);
-    if (fin_b) return true;
-    if (fin_a) return false;
-    return g_b > g_a || (g_b == g_a && b < a);
-}
-
-// what a mate slot needs of a car
-struct RivalCar { double x, y, ch, sh, vx, vy, s; };
-__device__ __forceinline__ RivalCar rival_car(const CarCore& r, double s)
-{
-    RivalCar k;
-    k.x = r.x; k.y = r.y; k.ch = r.qw * r.qw - r.qz * r.qz; k.sh = 2.0 * (r.qw * r.qz); k.vx = r.vx; k.vy = r.vy; k.s = s;
-    return k;
-}
-
-// step 4: the eight entries of mate b in a's slot o
-__device__ __forceinline__ void rival_mate(const RivalCar& a, const RivalCar& b, float* __restrict__ o)
-{
-    const double dx = b.x - a.x, dy = b.y - a.y, dvx = b.vx - a.vx, dvy = b.vy - a.vy;
-    double tg = b.s - a.s;
-    if (tg >= 50.0) tg = tg - 100.0;
-    if (tg < -50.0) tg = tg + 100.0;
-    o[0] = (float)(dx * a.ch + dy * a.sh);
-    o[1] = (float)(dy * a.ch - dx * a.sh);
-    o[2] = (float)(b.ch * a.ch + b.sh * a.sh);
-    o[3] = (float)(b.sh * a.ch - b.ch * a.sh);
-    o[4] = (float)(dvx * a.ch + dvy * a.sh);
-    o[5] = (float)(dvy * a.ch - dvx * a.sh);
-    o[6] = (float)tg;
-    o[7] = 1.0f;
-}
+// steps 1 - 4, element by element: ftgp_rival.h (rival_progress, rival_ahead, RivalCar / rival_car, rival_mate)
 
 __device__ __forceinline__ double shfl_f64(double v, int src)
 {
@@ -2765,7 +2846,6 @@ __device__ __forceinline__ double shfl_f64(double v, int src)
 // n_racing and the number of mates are sums and the two gaps minima over the group (xor-shuffles 1, 2, 4 stay inside eight lanes);
 // a mate's rank is the number of mates before it in (d2, slot) order, counted over the group's eight lanes with plain shuffles.  The
 // mate of rank r < n_rivals writes slot r, lane r zero-fills a slot no mate has, lane 0 writes the fixed entries.  No LDS, no atomics.
-#define FTGP_RIVAL_LANES 8
 #define FTGP_RIVAL_THREADS 256
 __global__ void __launch_bounds__(FTGP_RIVAL_THREADS) ftgp_io_rival_kernel(DeviceParams P, DeviceRivalArgs V)
 {
@@ -2859,74 +2939,17 @@ struct RivalLds { RivalCar car[FTGP_PAIR_STRIDE]; double g[FTGP_PAIR_STRIDE]; in
 // this lane's car into shared memory: the search as the progress block runs it, steps 2 and 3 of the frame row, step 1 of the rival row
 __device__ __forceinline__ void rival_lds_put(const double* __restrict__ path, const CarCore& r, RivalLds& L, int slot)
 {
-    const double x = r.x, y = r.y;
-    double best = 0.0; int c = 0;
-    #pragma unroll 1
-    for (int i = 0; i < FTGP_PATH_POINTS; ++i) {
-        const double dx = path[2 * i] - x, dy = path[2 * i + 1] - y;
-        const double d = dx * dx + dy * dy;
-        if (i == 0 || d < best) { best = d; c = i; }
-    }
-    const int pa = c > 0 ? c - 1 : FTGP_PATH_POINTS - 1;
-    FrameSeg g = frame_segment(path, c, x, y);
-    int seg = c;
-    {
-        const FrameSeg ga = frame_segment(path, pa, x, y);
-        if (ga.g2 < g.g2) { g = ga; seg = pa; }
-    }
-    double s = (double)seg + g.t;
-    if (s >= 100.0) s = s - 100.0;
+    double s, g;
+    rival_place(path, r.x, r.y, absolute_completion(r), s, g);
     L.car[slot] = rival_car(r, s);
-    L.g[slot] = rival_progress(absolute_completion(r), s, c, best > 1.0);
+    L.g[slot] = g;
     L.finish_step[slot] = r.finish_step;
     L.finished[slot] = r.finished;
 }
 
 __device__ __forceinline__ void rival_row_lane(const RivalLds& L, int cpe, int slot, int n_rivals, float* __restrict__ o)
 {
-    const RivalCar a = L.car[slot];
-    const double g_a = L.g[slot];
-    const bool fin_a = L.finished[slot] != 0;
-    const int64_t fs_a = L.finish_step[slot];
-    int n_ahead = 0, n_racing = 0;
-    double gap_ahead = INFINITY, gap_behind = INFINITY;
-    #pragma unroll 1
-    for (int b = 0; b < cpe; ++b) {
-        const bool fin_b = L.finished[b] != 0;
-        if (!fin_b) ++n_racing;
-        if (b == slot) continue;
-        const double g_b = L.g[b];
-        const bool ahead = rival_ahead(fin_b, L.finish_step[b], g_b, b, fin_a, fs_a, g_a, slot);
-        if (ahead) ++n_ahead;
-        if (fin_b || fin_a) continue;
-        const double gap = ahead ? g_b - g_a : g_a - g_b;
-        if (ahead) { if (gap < gap_ahead) gap_ahead = gap; }
-        else if (gap < gap_behind) gap_behind = gap;
-    }
-    o[0] = (float)(1 + n_ahead); o[1] = (float)n_racing;
-    o[2] = gap_ahead == INFINITY ? 0.0f : (float)gap_ahead; o[3] = gap_behind == INFINITY ? 0.0f : (float)gap_behind;
-    // the mates in (d2, slot) order: each turn takes the first one behind the last taken
-    double last_d2 = -1.0; int last_b = -1;
-    #pragma unroll 1
-    for (int k = 0; k < n_rivals; ++k) {
-        double best = 0.0; int bb = -1;
-        if (!fin_a) {
-            #pragma unroll 1
-            for (int b = 0; b < cpe; ++b) {
-                if (b == slot || L.finished[b]) continue;
-                const double dx = L.car[b].x - a.x, dy = L.car[b].y - a.y;
-                const double d2 = dx * dx + dy * dy;
-                if (!(d2 > last_d2 || (d2 == last_d2 && b > last_b))) continue;      // taken already
-                if (bb < 0 || d2 < best) { best = d2; bb = b; }
-            }
-        }
-        float* m = o + FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * k;
-        if (bb >= 0) { rival_mate(a, L.car[bb], m); last_d2 = best; last_b = bb; }
-        else {
-            for (int q = 0; q < FTGP_RIVAL_FLOATS; ++q) m[q] = 0.0f;
-            last_d2 = INFINITY; last_b = FTGP_PAIR_STRIDE;      // nobody is left
-        }
-    }
+    rival_row(L.car, L.g, L.finish_step, L.finished, cpe, slot, n_rivals, o);
 }
 
 // ftgp_io_finish_kernel with signals: one workgroup per env.  The rows of obs / final_obs are pooled (pooled_row); an external car that

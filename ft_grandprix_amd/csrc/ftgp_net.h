@@ -89,6 +89,8 @@ FTGP_HD float ftgp_net_guarded(float a, bool both_finite) { return both_finite ?
 FTGP_HD int ftgp_net_inputs(const FtgpNetDesc* d) { return d->n_beams + (d->use_state ? FTGP_NET_STATE_INPUTS : 0); }
 // the frame entries behind them (ftgp_set_net_frame): none without the struct or with enabled == 0
 FTGP_HD int ftgp_net_frame_inputs(const FtgpNetFrame* f) { return (f && f->enabled) ? FTGP_FRAME_FIXED + 2 * f->n_ahead : 0; }
+// ... and the rival entries behind those (ftgp_set_net_rivals): none without the struct or with enabled == 0
+FTGP_HD int ftgp_net_rival_inputs(const FtgpNetRivals* r) { return (r && r->enabled) ? FTGP_RIVAL_FIXED + FTGP_RIVAL_FLOATS * r->n_rivals : 0; }
 // number of binary32 parameters in the caller's layout: per layer W[n_out][n_in], then b[n_out]
 FTGP_HD size_t ftgp_net_param_count(const FtgpNetDesc* d)
 {

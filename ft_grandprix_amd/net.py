@@ -1,7 +1,8 @@
 """Network drivers: a trained MLP as a device policy (include/ftgp.h "Network drivers").
 
-A ``NetSpec`` is everything ``ftgp_set_net`` / ``ftgp_set_net_frame`` take: which beams of the scan the network reads, whether the five
-state inputs follow, whether the track-frame row (``frame``, ``lookahead``, ``lookahead_stride``) follows those, the layers in torch's ``nn.Linear`` layout, the two activations and the output map.  ``from_torch`` freezes an ``nn.Sequential`` of
+A ``NetSpec`` is everything ``ftgp_set_net`` / ``ftgp_set_net_frame`` / ``ftgp_set_net_rivals`` take: which beams of the scan the network
+reads, whether the five state inputs follow, whether the track-frame row (``frame``, ``lookahead``, ``lookahead_stride``) follows those
+and the rival row (``rivals``, ``n_rivals``) follows that, the layers in torch's ``nn.Linear`` layout, the two activations and the output map.  ``from_torch`` freezes an ``nn.Sequential`` of
 ``Linear`` / ``ReLU`` / ``Tanh`` / ``Identity`` into one; ``save`` / ``load`` keep it as an ``.npz``.
 
 The library evaluates the network in binary32 with a fixed order of operations and its own TANH (a continued fraction, within 2.7e-7
@@ -29,6 +30,8 @@ class NetSpec:
     frame: bool = False               # the track-frame row behind the beams and the state inputs (ftgp_set_net_frame)
     lookahead: int = 0                # look-ahead points of that row; > 0 turns ``frame`` on, as in DeviceVecEnv
     lookahead_stride: int = 1         # path points between two of them
+    rivals: bool = False              # the rival row of the car's env behind all of those (ftgp_set_net_rivals)
+    n_rivals: int = 0                 # mate slots of that row, 0 .. 7; > 0 turns ``rivals`` on, as in DeviceVecEnv
     _flat: np.ndarray = field(default=None, repr=False, compare=False)
 
     def __post_init__(self):
@@ -37,12 +40,14 @@ class NetSpec:
         self.out_offset = tuple(float(x) for x in self.out_offset)
         f = capi.net_frame(self.frame, self.lookahead, self.lookahead_stride)      # the ranges, before anything is loaded
         self.frame, self.lookahead, self.lookahead_stride = bool(f.enabled), int(f.n_ahead), int(f.stride)
+        r = capi.net_rivals(self.rivals, self.n_rivals)
+        self.rivals, self.n_rivals = bool(r.enabled), int(r.n_rivals)
         _, self._flat = capi.net_desc(self.layers, **self.input_fields())      # every check that needs no handle
 
     def input_fields(self) -> dict:
         return dict(pool=self.pool, max_range=self.max_range, beam_first=self.beam_first, n_beams=self.n_beams, use_state=self.use_state,
                     hidden_act=self.hidden_act, out_act=self.out_act, out_scale=self.out_scale, out_offset=self.out_offset,
-                    frame=self.frame, lookahead=self.lookahead, lookahead_stride=self.lookahead_stride)
+                    frame=self.frame, lookahead=self.lookahead, lookahead_stride=self.lookahead_stride, rivals=self.rivals, n_rivals=self.n_rivals)
 
     @property
     def n_frame(self) -> int:
@@ -50,8 +55,13 @@ class NetSpec:
         return capi.FRAME_FIXED + 2 * self.lookahead if self.frame else 0
 
     @property
+    def n_rival(self) -> int:
+        """Rival entries at the end of the input vector, behind the frame entries: 0 without rival inputs."""
+        return capi.RIVAL_FIXED + capi.RIVAL_FLOATS * self.n_rivals if self.rivals else 0
+
+    @property
     def n_in(self) -> int:
-        return self.n_beams + (capi.NET_STATE_INPUTS if self.use_state else 0) + self.n_frame
+        return self.n_beams + (capi.NET_STATE_INPUTS if self.use_state else 0) + self.n_frame + self.n_rival
 
     @property
     def widths(self) -> tuple:
@@ -76,7 +86,8 @@ class NetSpec:
         np.savez(path, n_layers=len(self.layers), pool=self.pool, max_range=np.float32(self.max_range), beam_first=self.beam_first,
                  n_beams=self.n_beams, use_state=int(self.use_state), hidden_act=self.hidden_act, out_act=self.out_act,
                  out_scale=np.asarray(self.out_scale, dtype=np.float32), out_offset=np.asarray(self.out_offset, dtype=np.float32),
-                 frame=int(self.frame), lookahead=self.lookahead, lookahead_stride=self.lookahead_stride, **arrays)
+                 frame=int(self.frame), lookahead=self.lookahead, lookahead_stride=self.lookahead_stride,
+                 rivals=int(self.rivals), n_rivals=self.n_rivals, **arrays)
 
 
 def load(path) -> NetSpec:
@@ -84,6 +95,9 @@ def load(path) -> NetSpec:
         layers = [(z[f"W{l}"], z[f"b{l}"]) for l in range(int(z["n_layers"]))]
         # (a file written before the frame inputs existed has none of the three keys: the frame is off)
         frame = dict(frame=bool(int(z["frame"])), lookahead=int(z["lookahead"]), lookahead_stride=int(z["lookahead_stride"])) if "frame" in z.files else {}
+        # (... and one written before the rival inputs existed has neither of their two keys: rivals are off)
+        if "rivals" in z.files:
+            frame.update(rivals=bool(int(z["rivals"])), n_rivals=int(z["n_rivals"]))
         return NetSpec(layers, pool=int(z["pool"]), max_range=float(z["max_range"]), beam_first=int(z["beam_first"]), n_beams=int(z["n_beams"]),
                        use_state=bool(int(z["use_state"])), hidden_act=str(z["hidden_act"]), out_act=str(z["out_act"]),
                        out_scale=tuple(z["out_scale"]), out_offset=tuple(z["out_offset"]), **frame)
@@ -92,7 +106,7 @@ def load(path) -> NetSpec:
 def from_torch(module, **input_fields) -> NetSpec:
     """Freeze ``nn.Sequential(Linear, act, Linear, act, ..., Linear[, act])`` with act in ReLU / Tanh / Identity.  Every hidden layer
     must use the same activation; a Linear without one behind it has the identity.  ``input_fields``: pool, max_range, beam_first,
-    n_beams and optionally use_state, out_scale, out_offset, frame, lookahead, lookahead_stride.  Anything else in the module is refused."""
+    n_beams and optionally use_state, out_scale, out_offset, frame, lookahead, lookahead_stride, rivals, n_rivals.  Anything else in the module is refused."""
     import torch.nn as nn
     if not isinstance(module, nn.Sequential):
         raise TypeError(f"from_torch takes an nn.Sequential of Linear / ReLU / Tanh / Identity, got {type(module).__name__}")

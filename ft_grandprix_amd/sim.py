@@ -302,7 +302,8 @@ def main(argv=None):
     ap.add_argument("--net", default=None, help="a network saved by ft_grandprix_amd.net.NetSpec.save (.npz): --device-policy net runs it for every "
                                                 "car, --device-policy roster for the roster entries whose \"driver\" is \"net\".  The file's "
                                                 "frame, lookahead and lookahead_stride fields give the network the track-frame row as inputs "
-                                                "behind the beams and the state (a file without them: none)")
+                                                "behind the beams and the state, its rivals and n_rivals fields the rival row of the car's env behind "
+                                                "those (a file without them: none)")
     ap.add_argument("--lidar", default="rangefinder", choices=("rangefinder", "fakelidar"))
     ap.add_argument("--report", type=int, default=0, help="print the standings every this many steps")
     args = ap.parse_args(argv)

@@ -164,6 +164,11 @@ class DeviceVecEnv:
     three settings (``track_frame``, ``lookahead``, ``lookahead_stride``).  The slot's frame inputs do not depend on the env's own
     frame setting: a net slot with frame inputs runs in an env that has the frame off.  ``nets=``, ``set_net`` and ``collect`` follow
     the spec; ``Rollout.inputs`` is as wide as the spec's ``n_in``.
+    With rival inputs (``NetSpec(rivals=, n_rivals=)``, ftgp_set_net_rivals) the rule goes one row further: a net slot with ``n_rivals``
+    sees ``cat(obs[beams], state[:5], frame, rival)`` of an agent whose env has ``rivals=True`` and the same ``n_rivals`` -- the race
+    place, the gaps and the nearest env-mates of the car, every car of the env counted whoever drives it.  The slot's rival inputs are
+    its own too: a slot with rival inputs runs in an env whose ``rivals`` is off or has another ``n_rivals``; with one car per env the
+    block is (1, 1, 0, 0, zeros).  ``nets=``, ``set_net`` and ``collect`` follow the spec here as well.
 
     Collected rollouts (ftgp_collect_device): ``collect(n_decisions, slot=0, std=, clip=, noise=, next_inputs=, out=)`` runs T decisions
     of network slot ``slot`` for every agent in one call that only enqueues and returns a ``Rollout`` of torch tensors -- what the

@@ -808,7 +808,7 @@ int ftgp_get_net(FtgpEnv *env, int slot, FtgpNetDesc *desc_out, float *params_ou
  * with the path of the env's track.  The slot's frame inputs do not depend on ftgp_device_io_frame being on, nor on its n_ahead and
  * stride; they equal the device step's `frame` row of the same record when the two settings agree.  So what a net slot sees is what
  * an agent is given: cat(obs[beam_first .. beam_first + n_beams), state[0 .. 5), frame) of an agent whose env has scan_pool = pool,
- * scan_max_range = max_range and the same (n_ahead, stride).  Rival rows as inputs are not part of this.
+ * scan_max_range = max_range and the same (n_ahead, stride).  (Rival rows as inputs: ftgp_set_net_rivals, below.)
  * A finished car still gets (0, 0) before the network is looked at.  ftgp_collect_device's x, inputs and next_inputs are this wider
  * vector, for a finished car too.  ftgp_get_net returns the parameters with the slot's true n_in (the first layer has n_in columns),
  * and ftgp_set_net_device takes them so: the same layout, a larger count.  The env-state record and the parameter block's layout are
@@ -828,6 +828,42 @@ typedef struct FtgpNetFrame {     /* 16 bytes */
 int ftgp_set_net_frame(FtgpEnv *env, int slot, const FtgpNetDesc *desc, const FtgpNetFrame *frame, const float *params);
 int ftgp_get_net_frame(FtgpEnv *env, int slot, FtgpNetFrame *frame_out);
 
+/* Rival inputs: the rival row behind the beams, the state inputs and the frame inputs, so that a racing policy trained on the device
+ * step's rival row (ftgp_device_io_rivals) can be its own frozen opponent, be evaluated in one launch and be collected.
+ * ftgp_set_net_rivals is ftgp_set_net_frame with one more struct; rivals == NULL or enabled == 0 is ftgp_set_net_frame to the letter,
+ * and ftgp_set_net and ftgp_set_net_frame keep defining slots without rival inputs.
+ *
+ * Input width.  n_in = n_beams + 5*use_state + frame.enabled*(FTGP_FRAME_FIXED + 2*n_ahead) + enabled*(FTGP_RIVAL_FIXED +
+ * FTGP_RIVAL_FLOATS*n_rivals), 1 <= n_in <= FTGP_NET_MAX_INPUTS.  The rival entries come last: inputs n_in - (FTGP_RIVAL_FIXED +
+ * FTGP_RIVAL_FLOATS*n_rivals) .. n_in - 1 are entries 0, 1, .. of the rival row.
+ * Rival entries.  The rival row of "Rival rows of the device step" above, steps 1 - 4 verbatim, with the SLOT's n_rivals: binary64 with
+ * one rounding per operation and no contraction, each entry rounded once to binary32; the (d2, slot) order of the mates, the ghost
+ * rule for finished cars and eight zeros for a slot without a mate; f_b = 0 for an off-track car and the 64-bit finish_step order
+ * among finishers.  The row is evaluated on the records of ALL cars of the car's env at the moment the driver runs -- where the state
+ * and frame inputs are taken; inside a launch of several steps, the records after the previous step -- and every car of the env
+ * counts, whoever drives it.  On a multi-track handle the path is that of the env's track, for every mate's search.  The slot's rival
+ * inputs do not depend on ftgp_device_io_rivals being on, nor on its n_rivals; they equal the device step's `rival` row of the same
+ * records when the two n_rivals agree.  So what a net slot sees is cat(obs[beams], state[0 .. 5), frame, rival) of an agent.  With one
+ * car per env the block is (1, 1, 0, 0, zeros): one policy shape serves every roster.
+ * A finished car still gets (0, 0) before the network is looked at.  ftgp_collect_device's x, inputs and next_inputs are this wider
+ * vector, for a finished car too: its place is its ftgp_get_winners place, its gaps are 0 and it has no mates.  ftgp_get_net and
+ * ftgp_set_net_device use the slot's true n_in.  FtgpNetDesc, FtgpNetFrame, FtgpConfig, the env-state record and the parameter block's
+ * layout are what they were.
+ *
+ * The setter carries all of ftgp_set_net_frame's checks and, before anything changes (a refused call leaves a defined slot in force),
+ * FTGP_ERR_ARG naming the field for: enabled not 0 or 1; n_rivals outside 0 .. FTGP_MAX_RIVALS -- checked with enabled == 0 too --; a
+ * reserved word != 0; n_in > FTGP_NET_MAX_INPUTS.
+ * ftgp_get_net_rivals (host): the rival inputs of a defined slot as the setter was given them; a slot defined without rival inputs
+ * reads {0, 0, {0, 0}}.  FTGP_ERR_STATE for a slot not defined. */
+typedef struct FtgpNetRivals {    /* 16 bytes */
+    int32_t enabled;              /* 0 or 1: the rival row behind the beams, the state inputs and the frame inputs */
+    int32_t n_rivals;             /* mate slots, 0 .. FTGP_MAX_RIVALS */
+    int32_t reserved[2];          /* 0 */
+} FtgpNetRivals;
+int ftgp_set_net_rivals(FtgpEnv *env, int slot, const FtgpNetDesc *desc, const FtgpNetFrame *frame,
+                        const FtgpNetRivals *rivals, const float *params);
+int ftgp_get_net_rivals(FtgpEnv *env, int slot, FtgpNetRivals *rivals_out);
+
 /* ---- Collected rollouts: T decisions of a network on the device, written down (no reference counterpart) ------------------------------
  * ftgp_collect_device drives every external slot of a device-io handle with network slot `slot` for n_decisions = T decisions, with
  * optional exploration noise, and records per decision what the network saw, what it proposed, what was applied and what came back.
@@ -838,7 +874,7 @@ int ftgp_get_net_frame(FtgpEnv *env, int slot, FtgpNetFrame *frame_out);
  *   1. Act.  For external car i of env e, at the records and scans as they stand: x = the network's input vector exactly as "Scan
  *      input" and "State input" of ftgp_set_net define it -- the beams from the car's ftgp_get_lidar row, the state entries 0 - 4 from
  *      the car's record with the controls then in force, and, for a slot with frame inputs (ftgp_set_net_frame), the frame row of that
- *      record behind them.  inputs[t][e][i] = x, for a finished car too.  A finished car gets mean =
+ *      record behind them, and, for a slot with rival inputs (ftgp_set_net_rivals), the rival row of the env's records behind those.  inputs[t][e][i] = x, for a finished car too.  A finished car gets mean =
  *      action = (0, 0) and the network is not looked at (the network driver's rule).  Otherwise, with y = the layers on x and k = 0, 1:
  *        m_k = fmaf(y_k, out_scale[k], out_offset[k])
  *        a_k = fmaf(std[k], noise[t][e][i][k], m_k)              (noise = NULL: every draw is 0; 0 * infinity is a NaN)

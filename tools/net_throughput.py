@@ -2,7 +2,7 @@
 with one agent whose network torch evaluates.
 
     python tools/net_throughput.py [--envs 4096] [--rays 1080] [--steps 500] [--launches 5] [--track track] [--calls 500]
-                                   [--decisions 100] [--rows rollout,agent,collect]
+                                   [--decisions 100] [--rows rollout,agent,collect,roster,collect2]
 
 rollout rows: one launch of --steps steps per measurement, --launches of them after one warm-up launch; env-steps/s from the wall clock
 around the launch and its synchronisation, and the step kernel's own time from ftgp_last_kernel_ms.  The network is a random
@@ -10,6 +10,10 @@ around the launch and its synchronisation, and the step kernel's own time from f
 The "rollout net0 frame" and "collect ... frame inputs" rows run an 85 + 4 + 2 * 8 -> 64 -> 64 -> 2 network: the same inputs and the
 track-frame row with eight look-ahead points behind them (ftgp_set_net_frame) -- what the frame inputs cost beside the same network
 without them.
+roster rows (--rows roster): --envs envs of FOUR cars, a roster of four network slots, rollout("per_car"): the 85 -> 64 -> 64 -> 2 network
+in every slot, and the same network with the rival row of three mate slots behind its inputs (85 + 4 + 8 * 3 -> ..., ftgp_set_net_rivals)
+-- what the rival inputs cost, and the MULTI NET step kernels' timing.  us per step is the launch's; per decision it is that over the
+four cars.  collect2 rows (--rows collect2): collect with two agents and two bundled cars per env, without and with the rival inputs.
 agent row: DeviceVecEnv(roster=["agent"], scan_pool, scan_max_range, state=True), the same network as an nn.Sequential evaluated by
 torch before every call, --calls calls of one step; per-call time from HIP events on torch's stream.
 collect row: the same env with the network in slot 0, DeviceVecEnv.collect (ftgp_collect_device) of --decisions decisions a call with
@@ -58,6 +62,7 @@ def main():
     module = make_module(n_beams + 5)
     spec = net.from_torch(module, **fields)
     spec_frame = net.from_torch(make_module(n_beams + 5 + 4 + 2 * 8), lookahead=8, lookahead_stride=1, **fields)
+    spec_rivals = net.from_torch(make_module(n_beams + 5 + 4 + 8 * 3), n_rivals=3, **fields)
     track = load_track(a.track)
     rows = a.rows.split(",")
     if "rollout" in rows:
@@ -77,6 +82,25 @@ def main():
                 print(json.dumps({"row": f"rollout {policy}" + (" frame" if what is spec_frame else ""), "envs": a.envs, "rays": a.rays, "steps": a.steps, "kernel": g.kernel_name(),
                                   "env_steps_per_s": a.envs * a.steps / float(np.median(wall)), "kernel_ms_median": float(np.median(kern)),
                                   "kernel_us_per_step": 1e3 * float(np.median(kern)) / a.steps, "off_track": int(g.progress()[:, 5].sum())}), flush=True)
+    if "roster" in rows:
+        lib = capi.load()
+        for what, label in ((spec, "roster of four net slots"), (spec_rivals, "roster of four net slots, rival inputs")):
+            with capi.Env(lib, track, n_envs=a.envs, cars_per_env=4, n_rays=a.rays, spawn_mode=1, seed=7) as g:
+                for s in range(4):
+                    g.set_net(s, what.layers, **what.input_fields())
+                g.set_car_policies(["net0", "net1", "net2", "net3"])
+                g.rollout("per_car", a.steps)
+                g.steps()
+                wall, kern = [], []
+                for _ in range(a.launches):
+                    t0 = time.perf_counter()
+                    g.rollout("per_car", a.steps)
+                    kern.append(g.last_kernel_ms())
+                    wall.append(time.perf_counter() - t0)
+                us = 1e3 * float(np.median(kern)) / a.steps
+                print(json.dumps({"row": label, "n_in": what.n_in, "envs": a.envs, "cars_per_env": 4, "rays": a.rays, "steps": a.steps, "kernel": g.kernel_name(),
+                                  "env_steps_per_s": a.envs * a.steps / float(np.median(wall)), "kernel_ms_median": float(np.median(kern)),
+                                  "kernel_us_per_step": us, "kernel_ns_per_decision": 1e3 * us / (4 * a.envs), "off_track": int(g.progress()[:, 5].sum())}), flush=True)
     if "agent" in rows:
         from ft_grandprix_amd.vec import DeviceVecEnv
         venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, roster=["agent"], scan_pool=a.pool, scan_max_range=10.0, state=True, spawn_mode=1, seed=7)
@@ -103,11 +127,14 @@ def main():
         print(json.dumps({"row": "device step, torch evaluates the network", "envs": a.envs, "rays": a.rays, "calls": a.calls,
                           "env_steps_per_s": a.envs * a.calls / wall, "us_per_call_events": 1e3 * e0.elapsed_time(e1) / a.calls}), flush=True)
         venv.close()
-    collect_rows = ((spec, "collect, network on the device"), (spec_frame, "collect, network on the device, frame inputs")) if "collect" in rows else ()
-    for the_spec, label in collect_rows:
+    collect_rows = ((spec, "collect, network on the device", ["agent"]), (spec_frame, "collect, network on the device, frame inputs", ["agent"])) if "collect" in rows else ()
+    if "collect2" in rows:
+        two = ["agent", "fast", "agent", "fast"]
+        collect_rows += ((spec, "collect, two agents of four cars", two), (spec_rivals, "collect, two agents of four cars, rival inputs", two))
+    for the_spec, label, roster in collect_rows:
         from ft_grandprix_amd.vec import DeviceVecEnv
-        venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, roster=["agent"], scan_pool=a.pool, scan_max_range=10.0, state=True, spawn_mode=1, seed=7,
-                            nets={0: the_spec})
+        venv = DeviceVecEnv(track, n_envs=a.envs, n_rays=a.rays, cars_per_env=len(roster), roster=roster, scan_pool=a.pool, scan_max_range=10.0, state=True, spawn_mode=1,
+                            seed=7, nets={0: the_spec})
         dev = venv.device
         venv.reset()
         kw = dict(std=(0.3, 0.1), clip=((0.0, 5.0), (-0.6, 0.6)), noise=True, next_inputs=True)
@@ -122,7 +149,7 @@ def main():
         torch.cuda.synchronize(dev)
         wall = time.perf_counter() - t0
         n = a.launches * a.decisions
-        print(json.dumps({"row": label, "n_in": the_spec.n_in, "envs": a.envs, "rays": a.rays, "calls": a.launches, "decisions_per_call": a.decisions,
+        print(json.dumps({"row": label, "n_in": the_spec.n_in, "envs": a.envs, "agents_per_env": roster.count("agent"), "rays": a.rays, "calls": a.launches, "decisions_per_call": a.decisions,
                           "env_steps_per_s": a.envs * n / wall, "us_per_decision_events": 1e3 * e0.elapsed_time(e1) / n,
                           "us_per_decision_wall": 1e6 * wall / n, "ends": int((roll.terminated | roll.truncated).sum())}), flush=True)
         venv.close()
