@@ -110,6 +110,7 @@ API_SYMBOLS = (
     "env_state_bytes", "save_envs_device", "load_envs_device", "get_env_state_rejected", "obs_device",
     "set_net", "set_net_device", "get_net", "set_net_frame", "get_net_frame", "set_net_rivals", "get_net_rivals",
     "collect_device",
+    "set_net_population", "set_net_population_device", "get_net_population",
 )
 
 
@@ -303,6 +304,35 @@ def net_layers(d: FtgpNetDesc, flat: np.ndarray, frame=None, rivals=None) -> lis
     return out
 
 
+def net_population_args(params, env_member, n_envs: int, count=None):
+    """(params float32 [n_members, count], env_member int32 [n_envs] or None) of ftgp_set_net_population with every check that needs no
+    handle (ValueError): a two-dimensional float32 array of 1 .. n_envs rows -- ``count`` columns where the caller knows the slot's
+    count --, and a map of n_envs integers in [0, n_members).  ``params=None`` is the population's removal: (None, None)."""
+    if params is None:
+        if env_member is not None:
+            raise ValueError("env_member without params: a population is removed with params=None alone")
+        return None, None
+    p = np.asarray(params)
+    if p.dtype != np.float32:
+        raise ValueError(f"params: float32 [n_members, count], got dtype {p.dtype}")
+    if p.ndim != 2 or p.shape[1] < 1:
+        raise ValueError(f"params: float32 [n_members, count], got shape {p.shape}")
+    if not 1 <= p.shape[0] <= int(n_envs):
+        raise ValueError(f"params: 1 .. n_envs = {int(n_envs)} members, got {p.shape[0]}")
+    if count is not None and p.shape[1] != int(count):
+        raise ValueError(f"params: the slot's networks have {int(count)} parameters, got rows of {p.shape[1]}")
+    if env_member is None:
+        return np.ascontiguousarray(p), None
+    m = np.asarray(env_member)
+    if m.dtype == np.bool_ or not np.issubdtype(m.dtype, np.integer):
+        raise ValueError(f"env_member: integers [n_envs], got dtype {m.dtype}")
+    if m.shape != (int(n_envs),):
+        raise ValueError(f"env_member: one member per env, shape ({int(n_envs)},), got {m.shape}")
+    if m.size and (m.min() < 0 or m.max() >= p.shape[0]):
+        raise ValueError(f"env_member: entries in [0, n_members = {p.shape[0]}), got {int(m.min())} .. {int(m.max())}")
+    return np.ascontiguousarray(p), np.ascontiguousarray(m, dtype=np.int32)
+
+
 class FtgpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ftgp error {code}: {msg}")
@@ -408,6 +438,9 @@ class CLib:
             "set_net_rivals": (i32, [vp, i32, C.POINTER(FtgpNetDesc), C.POINTER(FtgpNetFrame), C.POINTER(FtgpNetRivals), dp]),
             "get_net_rivals": (i32, [vp, i32, C.POINTER(FtgpNetRivals)]),
             "collect_device": (i32, [vp, C.POINTER(FtgpCollect)]),
+            "set_net_population": (i32, [vp, i32, i32, dp, dp]),
+            "set_net_population_device": (i32, [vp, vp, i32, vp, vp]),
+            "get_net_population": (i32, [vp, i32, C.POINTER(C.c_int32), dp, i32, dp]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -759,6 +792,47 @@ class Env:
         ``set_net(slot, layers, **fields_of_the_description, **that_dict)`` defines the same slot again."""
         r = self.net_rivals(slot)
         return self.net(slot) + ({**self.net_frame(slot), **(r if r["rivals"] else {})},)
+
+    # -- network populations (include/ftgp.h: ftgp_set_net_population)
+    def _net_count(self, slot: int) -> int:
+        """Floats of a defined slot's parameters in the caller's layout, from its description alone (nothing is read back)."""
+        d, f, r = FtgpNetDesc(), FtgpNetFrame(), FtgpNetRivals()
+        self._call("get_net", int(slot), C.byref(d), None)
+        self._call("get_net_frame", int(slot), C.byref(f))
+        self._call("get_net_rivals", int(slot), C.byref(r))
+        return net_param_count(d, f, r)
+
+    def set_net_population(self, slot: int, params, env_member=None):
+        """ftgp_set_net_population: ``params`` float32 [n_members, count] -- one row per member in ftgp_set_net's flat layout
+        (``NetSpec.flat_params``, ``net.stack_params``) -- and ``env_member`` int32 [n_envs] (None: env e gets member e % n_members) make
+        defined slot ``slot`` a population: env e's cars driven by ``"net<slot>"`` run member env_member[e].  ``params=None`` removes it."""
+        p, m = net_population_args(params, env_member, self.n_envs)
+        if p is None:
+            self._call("set_net_population", int(slot), 0, None, None)
+            return
+        net_population_args(p, None, self.n_envs, self._net_count(slot))      # (a slot that is not defined: the library's message)
+        self._call("set_net_population", int(slot), int(p.shape[0]), _ptr(p), _ptr(m) if m is not None else None)
+
+    def set_net_population_device(self, slot: int, params_address: int, env_member_address: int = 0, stream: int = 0):
+        """ftgp_set_net_population_device: new parameters (float32 [n_members, count]) and / or a new map (int32 [n_envs]) for a slot
+        that carries a population, from integer device addresses (0 = keep), ordered on ``stream``; only enqueues.  A map entry
+        outside [0, n_members) is taken as member 0."""
+        self._call("set_net_population_device", stream or None, int(slot), params_address or None, env_member_address or None)
+
+    def get_net_population(self, slot: int, member=None):
+        """ftgp_get_net_population: (n_members, env_member int32 [n_envs]) of a defined slot -- (0, None) without a population --, or,
+        with ``member``, that member's flat float32 parameters."""
+        n = C.c_int32(0)
+        self._call("get_net_population", int(slot), C.byref(n), None, 0, None)
+        if member is None:
+            if n.value == 0:
+                return 0, None
+            m = np.empty(self.n_envs, dtype=np.int32)
+            self._call("get_net_population", int(slot), None, _ptr(m), 0, None)
+            return int(n.value), m
+        flat = np.empty(self._net_count(slot), dtype=np.float32)
+        self._call("get_net_population", int(slot), None, None, int(member), _ptr(flat))
+        return flat
 
     # -- collected rollouts (include/ftgp.h: ftgp_collect_device)
     def collect_device(self, n_decisions: int, inputs: int, mean: int, action: int, reward: int, terminated: int, truncated: int, *,

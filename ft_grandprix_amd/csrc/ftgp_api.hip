@@ -201,6 +201,10 @@ struct FtgpEnv {
     FtgpNetFrame net_frame[FTGP_MAX_NETS] = {};   // ... and the frame inputs (ftgp_get_net_frame); zeros = none
     FtgpNetRivals net_rivals[FTGP_MAX_NETS] = {}; // ... and the rival inputs (ftgp_get_net_rivals); zeros = none
     DevBuf<float> d_net_params[FTGP_MAX_NETS];    // the slots' parameters in the library's layout
+    // populations (ftgp_set_net_population): pop_members[s] > 0 = slot s carries one, and its record's params and env_member point here
+    int pop_members[FTGP_MAX_NETS] = {};
+    DevBuf<float> d_pop_params[FTGP_MAX_NETS];    // [n_members] parameter sets in the library's layout, net_member_stride(n_floats) floats apart
+    DevBuf<int32_t> d_pop_map[FTGP_MAX_NETS];     // [n_envs] the member of every env
     bool last_net = false;            // the newest launch ran a NET instantiation
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
     std::vector<uint64_t> track_fp;   // [n_tracks] the tracks' fingerprints (include/ftgp.h), folded at create
@@ -2054,6 +2058,16 @@ static NetDev net_record(const FtgpNetDesc& d, const FtgpNetFrame* f, const Ftgp
     return N;
 }
 
+// a host buffer of n elements for a network entry: a failed allocation is an error code, no exception crosses the C interface
+extern "C++" {
+template <class T> static int net_host_buffer(std::vector<T>& v, size_t n, const char* entry)
+{
+    try { v.assign(n, T()); }
+    catch (const std::bad_alloc&) { return failf(FTGP_ERR_HIP, "%s: no host memory for %zu bytes", entry, n * sizeof(T)); }
+    return 0;
+}
+}
+
 // The first setter call of a handle: the NET kernels may use the LDS the others may, the records are allocated (zeroed: every slot
 // empty) and every parameter block learns their address.  ftgp_create does nothing for the networks.
 static int ensure_nets(FtgpEnv* e)
@@ -2098,13 +2112,9 @@ int ftgp_set_net_rivals(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftg
     DevBuf<float> buf;
     if (desc) {
         N = net_record(*desc, frame, rivals);
-        std::vector<float> img((size_t)N.n_floats, 0.0f);     // the library's layout; the padding is zeros
-        const float* src = params;
-        for (int l = 0; l < N.n_layers; ++l) {
-            const int n_in = N.width[l], n_out = N.width[l + 1], ld = (n_out + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
-            for (int j = 0; j < n_out; ++j) for (int k = 0; k < n_in; ++k) img[(size_t)N.w_off[l] + (size_t)k * ld + j] = *src++;
-            for (int j = 0; j < n_out; ++j) img[(size_t)N.b_off[l] + j] = *src++;
-        }
+        std::vector<float> img;                               // the library's layout; the padding is zeros
+        if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_set_net")) return rc;
+        ftgp_net_population_to_library(N.n_layers, N.width, 1, params, img.data());
         HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
         N.params = buf.get();
     }
@@ -2115,6 +2125,7 @@ int ftgp_set_net_rivals(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftg
     e->net_frame[slot] = (desc && frame && frame->enabled) ? *frame : FtgpNetFrame{};
     e->net_rivals[slot] = (desc && rivals && rivals->enabled) ? *rivals : FtgpNetRivals{};
     e->d_net_params[slot] = std::move(buf);                   // (the old buffer goes: nothing reads it any more)
+    e->pop_members[slot] = 0; e->d_pop_params[slot] = DevBuf<float>(); e->d_pop_map[slot] = DevBuf<int32_t>();      // ... and a population with it
     return 0;
 }
 
@@ -2123,6 +2134,7 @@ int ftgp_set_net_device(FtgpEnv* e, void* stream, int slot, const float* params)
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
     if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_device: network slot %d is not defined (ftgp_set_net)", slot);
+    if (e->pop_members[slot]) return failf(FTGP_ERR_STATE, "ftgp_set_net_device: network slot %d carries a population of %d members (ftgp_set_net_population_device)", slot, e->pop_members[slot]);
     HIP_TRY(hipSetDevice(e->device));
     const int n = (int)net_param_count(e->nets[slot]);
     auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_net_device: %s", m.c_str()); return rc; };
@@ -2130,7 +2142,7 @@ int ftgp_set_net_device(FtgpEnv* e, void* stream, int slot, const float* params)
     if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
     if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
     if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream.get(), e->nets[slot], params, e->d_net_params[slot].get(), n);
+    hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream.get(), e->nets[slot], params, e->d_net_params[slot].get(), n, 0, 1);
     HIP_TRY(hipGetLastError());
     return caller_waits_for_handle(e, (hipStream_t)stream);
 }
@@ -2144,15 +2156,103 @@ int ftgp_get_net(FtgpEnv* e, int slot, FtgpNetDesc* desc_out, float* params_out)
     if (desc_out) *desc_out = e->net_desc[slot];
     if (!params_out) return 0;
     HIP_TRY(hipSetDevice(e->device));
-    std::vector<float> img((size_t)N.n_floats);
+    std::vector<float> img;
+    if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_get_net")) return rc;
     HIP_TRY(hipMemcpyAsync(img.data(), e->d_net_params[slot].get(), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
-    float* dst = params_out;
-    for (int l = 0; l < N.n_layers; ++l) {
-        const int n_in = N.width[l], n_out = N.width[l + 1], ld = (n_out + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
-        for (int j = 0; j < n_out; ++j) for (int k = 0; k < n_in; ++k) *dst++ = img[(size_t)N.w_off[l] + (size_t)k * ld + j];
-        for (int j = 0; j < n_out; ++j) *dst++ = img[(size_t)N.b_off[l] + j];
+    ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), params_out);
+    return 0;
+}
+
+// ---- network populations: one parameter set per env (include/ftgp.h "Network populations") ----
+int ftgp_set_net_population(FtgpEnv* e, int slot, int n_members, const float* params, const int32_t* env_member)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_population: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_population: network slot %d is not defined (ftgp_set_net)", slot);
+    const int n_envs = e->P.n_envs;
+    if (n_members < 0 || n_members > n_envs) return failf(FTGP_ERR_ARG, "ftgp_set_net_population: n_members = %d outside 0 .. n_envs = %d", n_members, n_envs);
+    if (n_members > 0 && !params) return fail(FTGP_ERR_ARG, "ftgp_set_net_population: params is NULL%s");
+    if (n_members > 0 && env_member)
+        for (int i = 0; i < n_envs; ++i)
+            if (env_member[i] < 0 || env_member[i] >= n_members)
+                return failf(FTGP_ERR_ARG, "ftgp_set_net_population: env_member[%d] = %d outside [0, n_members = %d)", i, env_member[i], n_members);
+    HIP_TRY(hipSetDevice(e->device));
+    NetDev N = e->nets[slot];
+    DevBuf<float> buf;
+    DevBuf<int32_t> map;
+    if (n_members > 0) {
+        const size_t stride = (size_t)net_member_stride(N.n_floats);
+        std::vector<float> img;                               // the library's layout; the padding is zeros
+        std::vector<int32_t> members;
+        if (int rc = net_host_buffer(img, (size_t)n_members * stride, "ftgp_set_net_population")) return rc;
+        if (int rc = net_host_buffer(members, (size_t)n_envs, "ftgp_set_net_population")) return rc;
+        ftgp_net_population_to_library(N.n_layers, N.width, n_members, params, img.data());
+        for (int i = 0; i < n_envs; ++i) members[(size_t)i] = env_member ? env_member[i] : i % n_members;
+        HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
+        HIP_TRY(dev_upload(map, members.data(), sizeof(int32_t) * members.size()));
+        N.params = buf.get(); N.env_member = map.get();
+    } else {
+        if (!e->pop_members[slot]) return 0;                     // there is none
+        N.params = e->d_net_params[slot].get(); N.env_member = nullptr;        // the slot's single set is in force again
     }
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the slot while it changes
+    HIP_TRY(hipMemcpy(e->d_nets.get() + slot, &N, sizeof N, hipMemcpyHostToDevice));
+    e->nets[slot] = N;
+    e->pop_members[slot] = n_members;
+    e->d_pop_params[slot] = std::move(buf);                   // (the old buffers go: nothing reads them any more)
+    e->d_pop_map[slot] = std::move(map);
+    return 0;
+}
+
+int ftgp_set_net_population_device(FtgpEnv* e, void* stream, int slot, const float* params, const int32_t* env_member)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_population_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_population_device: network slot %d is not defined (ftgp_set_net)", slot);
+    const int M = e->pop_members[slot], n_envs = e->P.n_envs;
+    if (!M) return failf(FTGP_ERR_STATE, "ftgp_set_net_population_device: network slot %d carries no population (ftgp_set_net_population)", slot);
+    HIP_TRY(hipSetDevice(e->device));
+    const NetDev& N = e->nets[slot];
+    const int n = (int)net_param_count(N);
+    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_net_population_device: %s", m.c_str()); return rc; };
+    if (params) if (int rc = check_device_buffer(e, params, sizeof(float) * (size_t)n * (size_t)M, "params")) return refused(rc);
+    if (env_member) if (int rc = check_device_buffer(e, env_member, sizeof(int32_t) * (size_t)n_envs, "env_member")) return refused(rc);
+    if (!params && !env_member) return 0;
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    if (params) {
+        hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min(M, FTGP_NET_PARAMS_GRID_Y)), dim3(256), 0, e->stream.get(), N, params,
+                           e->d_pop_params[slot].get(), n, net_member_stride(N.n_floats), M);
+        HIP_TRY(hipGetLastError());
+    }
+    if (env_member) {
+        hipLaunchKernelGGL(ftgp_net_map_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, e->stream.get(), env_member, e->d_pop_map[slot].get(), n_envs, M);
+        HIP_TRY(hipGetLastError());
+    }
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+int ftgp_get_net_population(FtgpEnv* e, int slot, int32_t* n_members_out, int32_t* env_member_out, int member, float* params_out)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_population: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    const NetDev& N = e->nets[slot];
+    if (!N.defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_population: network slot %d is not defined (ftgp_set_net)", slot);
+    const int M = e->pop_members[slot];
+    if (n_members_out) *n_members_out = M;
+    if (!env_member_out && !params_out) return 0;
+    if (!M) return failf(FTGP_ERR_STATE, "ftgp_get_net_population: network slot %d carries no population (ftgp_set_net_population)", slot);
+    if (params_out && (member < 0 || member >= M)) return failf(FTGP_ERR_ARG, "ftgp_get_net_population: member = %d outside [0, n_members = %d)", member, M);
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<float> img;
+    if (int rc = net_host_buffer(img, params_out ? (size_t)N.n_floats : 0, "ftgp_get_net_population")) return rc;
+    if (env_member_out) HIP_TRY(hipMemcpyAsync(env_member_out, e->d_pop_map[slot].get(), sizeof(int32_t) * (size_t)e->P.n_envs, hipMemcpyDeviceToHost, e->stream.get()));
+    if (params_out)
+        HIP_TRY(hipMemcpyAsync(img.data(), e->d_pop_params[slot].get() + (size_t)member * (size_t)net_member_stride(N.n_floats), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    if (params_out) ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), params_out);
     return 0;
 }
 

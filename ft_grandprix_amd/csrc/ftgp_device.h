@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include "../../include/ftgp.h"
 #include "ftgp_march.h"
 #include "ftgp_spawn.h"
@@ -185,9 +186,12 @@ struct alignas(16) NetDev {
     float max_range, inv_max_range, out_scale[2], out_offset[2];
     const float* params;
     int32_t rival_first, rival_shape;             // rival inputs (ftgp_set_net_rivals): the index of the first one, and enabled | n_rivals << 8 -- 0 = none
-    int32_t pad0, pad1;
+    const int32_t* env_member;                    // a population (ftgp_set_net_population; the eight bytes that were spare): [n_envs] the member of
+                                                  // every env, and params is then [n_members] sets, net_member_stride(n_floats) floats apart; null = none
 };
-static_assert(sizeof(NetDev) == 144, "NetDev layout");
+static_assert(sizeof(NetDev) == 144 && offsetof(NetDev, env_member) == 136, "NetDev layout");
+// floats from one member's parameters to the next in a population: the slot's n_floats rounded up to 64 floats, a whole 256-byte segment
+__host__ __device__ inline int net_member_stride(int n_floats) { return ftgp_net_member_stride(n_floats); }
 template <class PP> __host__ __device__ inline const NetDev* net_table(PP p) { return reinterpret_cast<const NetDev*>(((uint64_t)p->net_table_hi << 32) | (uint64_t)p->net_table_lo); }
 __host__ __device__ inline bool is_net_policy(int policy) { return policy >= FTGP_POLICY_NET0 && policy <= FTGP_POLICY_NET3; }
 

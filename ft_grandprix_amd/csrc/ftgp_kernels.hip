@@ -1698,10 +1698,18 @@ __device__ __forceinline__ void net_inputs(const ScalarNet N, const float* __res
     for (int r = 0; r < 4; ++r) if (rival_reg == r) x[r] = rival_v;
 }
 // "Layers": x becomes the outputs of the last layer, y0 in lane 0 and y1 in lane 1 of x[0]
-__device__ __forceinline__ void net_layers(const ScalarNet N, float (&x)[4])
+// A slot with a population (ftgp_set_net_population): the parameters are those of the member of the car's env, one more wave-uniform
+// scalar -- params + env_member[env] * stride, two scalar loads ahead of the first row.  env_of(): the car's env in the handle, asked
+// for by such a slot only.
+template <class EnvOf>
+__device__ __forceinline__ void net_layers(const ScalarNet N, EnvOf env_of, float (&x)[4])
 {
     const int lane = lane_here();
     const float* __restrict__ params = uniform_ptr(N->params);
+    if (const int32_t* map = N->env_member) {
+        const int member = __builtin_amdgcn_readfirstlane(uniform_ptr(map)[__builtin_amdgcn_readfirstlane(env_of())]);
+        params = uniform_ptr(params + (size_t)member * (size_t)net_member_stride(N->n_floats));
+    }
     const int n_layers = N->n_layers;
     for (int l = 0; l < n_layers; ++l) {
         const int n_in = N->width[l], n_out = N->width[l + 1];
@@ -1728,14 +1736,14 @@ __device__ __forceinline__ ScalarNet scalar_net(const NetDev* table, int slot)
     uint64_t ta = (uint64_t)(table + slot); asm volatile("" : "+s"(ta));
     return (ScalarNet)ta;
 }
-template <class EnvFn>
-__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st, EnvFn env)
+template <class EnvFn, class EnvOf>
+__device__ __forceinline__ void policy_net(const NetDev* table, int slot, const float* __restrict__ win, CarCore* st, EnvFn env, EnvOf env_of)
 {
     const ScalarNet N = scalar_net(table, slot);
     const int lane = lane_here();
     float x[4];
     net_inputs(N, win, st, env, x);
-    net_layers(N, x);
+    net_layers(N, env_of, x);
     const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 0)), y1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), 1));
     const float scale[2] = { N->out_scale[0], N->out_scale[1] }, offset[2] = { N->out_offset[0], N->out_offset[1] };
     double us, ut;
@@ -1743,14 +1751,14 @@ __device__ __forceinline__ void policy_net(const NetDev* table, int slot, const 
     if (lane == 0) { st->u_speed = us; st->u_steer = ut; }
 }
 // the driver FTGP_POLICY_NET0 + slot of one car: a finished car gets the null driver before the network is looked at
-template <class EnvFn>
-__device__ __forceinline__ void policy_apply_net(const NetDev* table, int slot, const float* scan, int eighth, CarCore* st, EnvFn env)
+template <class EnvFn, class EnvOf>
+__device__ __forceinline__ void policy_apply_net(const NetDev* table, int slot, const float* scan, int eighth, CarCore* st, EnvFn env, EnvOf env_of)
 {
     if (st->finished) {
         if (lane_id() == 0) { st->u_speed = 0.0; st->u_steer = 0.0; }
         return;
     }
-    policy_net(table, slot, scan + scan_window_first(eighth) - eighth, st, env);
+    policy_net(table, slot, scan + scan_window_first(eighth) - eighth, st, env, env_of);
 }
 
 // =============================================================================================
@@ -2038,7 +2046,8 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
                 if constexpr (NET) {      // the launch's driver, or some slot's, is a network: the slot's driver, networks among them
                     const int pol = policy == FTGP_POLICY_PER_CAR ? G->car_policy[c] : policy;
                     if (is_net_policy(pol)) policy_apply_net(net_table(G), pol - FTGP_POLICY_NET0, scan_prev + c * win_floats, G->eighth, L.cars + c,
-                                                            [&] { const int cpe = G->cars_per_env, sl = c % cpe; return NetEnv{ L.path, L.cars + (c - sl), (int)sizeof(CarCore), sl, cpe }; });
+                                                            [&] { const int cpe = G->cars_per_env, sl = c % cpe; return NetEnv{ L.path, L.cars + (c - sl), (int)sizeof(CarCore), sl, cpe }; },
+                                                            [&] { return (ci0 + c) / G->cars_per_env; });
                     else if (policy == FTGP_POLICY_PER_CAR)
                         policy_apply(P, driver_shape(G), pol, scan_prev + c * win_floats, L.cars + c, ci0 + c, L.steps[c], L.list + wave * FTGP_WAVE,
                                      L.cover + (pol == FTGP_POLICY_FAST ? (G->stage_cover >> 2) : 0));
@@ -2157,7 +2166,8 @@ __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int po
         policy_apply_net(net_table(&P), pol - FTGP_POLICY_NET0, scan, P.eighth, st,
                          [&] { const int env = ci / P.cars_per_env;
                                return NetEnv{ P.path + (size_t)(env_track ? env_track[env] : 0) * 2 * FTGP_PATH_POINTS, P.cars + (size_t)env * P.cars_per_env,
-                                              (int)sizeof(CarState), ci - env * P.cars_per_env, P.cars_per_env }; });
+                                              (int)sizeof(CarState), ci - env * P.cars_per_env, P.cars_per_env }; },
+                         [&] { return ci / P.cars_per_env; });
     else policy_apply(P, driver_shape(&P), pol, scan, st, ci, P.steps[ci / P.cars_per_env], list, P.cover_thr + (pol == FTGP_POLICY_FAST ? P.cover_kmax + 1 : 0));
     wave_lds_sync();
     if (lane == 0) {
@@ -2168,18 +2178,15 @@ __global__ void __launch_bounds__(256) ftgp_policy_kernel(DeviceParams P, int po
 
 // ftgp_set_net_device: the parameters of a slot from the caller's layout (per layer W[n_out][n_in], then b[n_out]) into the library's
 // (NetDev: Wt[n_in][ld], then b[ld]); one thread per parameter, the padding stays the zeros ftgp_set_net wrote.  n = the caller's count.
-__global__ void ftgp_net_params_kernel(NetDev N, const float* __restrict__ src, float* __restrict__ dst, int n)
+// ftgp_set_net_population_device: the same for every one of n_members members, n floats apart in src, stride floats apart in dst;
+// members blockIdx.y, blockIdx.y + gridDim.y, ... (the host caps the grid's y at FTGP_NET_PARAMS_GRID_Y, n_members is bounded by n_envs alone).
+#define FTGP_NET_PARAMS_GRID_Y 1024
+__global__ void ftgp_net_params_kernel(NetDev N, const float* __restrict__ src, float* __restrict__ dst, int n, int stride, int n_members)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float v = src[i];
-    for (int l = 0; l < N.n_layers; ++l) {
-        const int n_in = N.width[l], n_out = N.width[l + 1], ld = (n_out + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
-        if (i < n_in * n_out) { dst[N.w_off[l] + (i % n_in) * ld + i / n_in] = v; return; }
-        i -= n_in * n_out;
-        if (i < n_out) { dst[N.b_off[l] + i] = v; return; }
-        i -= n_out;
-    }
+    const int at = ftgp_net_library_index(N.n_layers, N.width, i);       // (i < n = the caller's count: never -1)
+    for (int m = blockIdx.y; m < n_members; m += gridDim.y) dst[(size_t)m * (size_t)stride + (size_t)at] = src[(size_t)m * (size_t)n + (size_t)i];
 }
 
 // ftgp_collect_device, step 1 "Act" (include/ftgp.h "Collected rollouts"): one wave per external car, four per workgroup, as K5 alone.
@@ -2231,7 +2238,7 @@ __global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, C
     const int k = lane & 1;
     float m = 0.0f, a = 0.0f;
     if (!sgpr(st->finished)) {                                   // a finished car: (0, 0) before the network is looked at
-        net_layers(N, x);
+        net_layers(N, [&] { return row / C.n_ext; }, x);
         const float nz = C.noise ? C.noise[(size_t)row * 2 + k] : 0.0f;
         m = ftgp_net_mean(x[0], k ? N->out_scale[1] : N->out_scale[0], k ? N->out_offset[1] : N->out_offset[0]);
         a = ftgp_net_clip(ftgp_net_noisy(m, k ? C.std[1] : C.std[0], nz), k ? C.lo[1] : C.lo[0], k ? C.hi[1] : C.hi[0]);
@@ -2243,6 +2250,16 @@ __global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, C
 
 template __global__ void ftgp_collect_act_kernel<true>(DeviceParams, CollectActArgs);
 template __global__ void ftgp_collect_act_kernel<false>(DeviceParams, CollectActArgs);
+
+// ftgp_set_net_population_device: the env-to-member map from the caller's buffer; an entry outside [0, n_members) cannot be refused without
+// a synchronisation and becomes member 0, so that no car reads parameters outside the population's buffer
+__global__ void ftgp_net_map_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst, int n_envs, int n_members)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_envs) return;
+    const int32_t m = src[e];
+    dst[e] = (m >= 0 && m < n_members) ? m : 0;
+}
 
 // =============================================================================================
 // K4: reset / spawn (custom.py:1089-1128, 1232-1245, 81-87), one car per lane; then K3 at the spawn pose.

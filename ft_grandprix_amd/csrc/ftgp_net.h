@@ -99,3 +99,54 @@ FTGP_HD size_t ftgp_net_param_count(const FtgpNetDesc* d)
     for (int l = 0; l < d->n_layers; ++l) { n += (size_t)d->width[l] * (size_t)n_in + (size_t)d->width[l]; n_in = d->width[l]; }
     return n;
 }
+
+// ---- the library's layout of a parameter set, and of a population of them (ftgp_set_net_population) ----
+// width[0] = n_in, width[l + 1] = outputs of layer l.  Per layer the weights transposed and padded, Wt[n_in][ld] with ld = n_out rounded
+// up to 64, then b[ld]; the padding is zeros.  (tools/net_layout_check.cpp compiles these for the CPU; tests/test_net_population.py
+// compares them with numpy.)
+FTGP_HD int ftgp_net_ld(int n_out) { return (n_out + 63) & ~63; }
+// floats of one set in the caller's layout and in the library's
+FTGP_HD int ftgp_net_caller_floats(int n_layers, const int32_t* width)
+{
+    int n = 0;
+    for (int l = 0; l < n_layers; ++l) n += width[l + 1] * width[l] + width[l + 1];
+    return n;
+}
+FTGP_HD int ftgp_net_library_floats(int n_layers, const int32_t* width)
+{
+    int n = 0;
+    for (int l = 0; l < n_layers; ++l) n += (width[l] + 1) * ftgp_net_ld(width[l + 1]);
+    return n;
+}
+// where float i of the caller's layout (per layer W[n_out][n_in], then b[n_out]) sits in the library's; -1 past the last one
+FTGP_HD int ftgp_net_library_index(int n_layers, const int32_t* width, int i)
+{
+    int o = 0;
+    if (i < 0) return -1;
+    for (int l = 0; l < n_layers; ++l) {
+        const int n_in = width[l], n_out = width[l + 1], ld = ftgp_net_ld(n_out);
+        if (i < n_in * n_out) return o + (i % n_in) * ld + i / n_in;
+        i -= n_in * n_out; o += n_in * ld;
+        if (i < n_out) return o + i;
+        i -= n_out; o += ld;
+    }
+    return -1;
+}
+// floats from one member of a population to the next: the library's floats rounded up to 64, a whole 256-byte segment
+FTGP_HD int ftgp_net_member_stride(int n_floats) { return (n_floats + 63) & ~63; }
+// n_members sets, member after member in the caller's layout, into the library's at img -- [n_members] sets ftgp_net_member_stride
+// apart, zeroed by the caller: only the parameters are written, the padding stays -- and back
+FTGP_HD void ftgp_net_population_to_library(int n_layers, const int32_t* width, int n_members, const float* src, float* img)
+{
+    const int count = ftgp_net_caller_floats(n_layers, width);
+    const size_t stride = (size_t)ftgp_net_member_stride(ftgp_net_library_floats(n_layers, width));
+    for (size_t m = 0; m < (size_t)n_members; ++m)
+        for (int i = 0; i < count; ++i) img[m * stride + (size_t)ftgp_net_library_index(n_layers, width, i)] = src[m * (size_t)count + (size_t)i];
+}
+FTGP_HD void ftgp_net_population_from_library(int n_layers, const int32_t* width, int n_members, const float* img, float* dst)
+{
+    const int count = ftgp_net_caller_floats(n_layers, width);
+    const size_t stride = (size_t)ftgp_net_member_stride(ftgp_net_library_floats(n_layers, width));
+    for (size_t m = 0; m < (size_t)n_members; ++m)
+        for (int i = 0; i < count; ++i) dst[m * (size_t)count + (size_t)i] = img[m * stride + (size_t)ftgp_net_library_index(n_layers, width, i)];
+}

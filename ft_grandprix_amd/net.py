@@ -76,6 +76,23 @@ class NetSpec:
         """float32, ftgp_set_net's layout: per layer W[n_out][n_in], then b[n_out]."""
         return self._flat.copy()
 
+    @property
+    def param_count(self) -> int:
+        """Floats of ``flat_params``: the row width of a population (``stack_params``, ftgp_set_net_population)."""
+        return int(self._flat.size)
+
+    def with_params(self, flat) -> "NetSpec":
+        """A spec of the same shape and input fields with the parameters of one flat float32 row in ``flat_params``' layout -- a
+        member of a population, the winner for example."""
+        flat = np.asarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat)
+        if flat.dtype != np.float32 or flat.shape != (self.param_count,):
+            raise ValueError(f"flat: float32 [{self.param_count}], got {flat.dtype} {flat.shape}")
+        layers, o = [], 0
+        for W, b in self.layers:
+            layers.append((flat[o:o + W.size].reshape(W.shape), flat[o + W.size:o + W.size + b.size]))
+            o += W.size + b.size
+        return NetSpec(layers, **self.input_fields())
+
     def check_window(self, n_rays: int):
         capi.check_net_window(n_rays, self.pool, self.beam_first, self.n_beams)
 
@@ -101,6 +118,18 @@ def load(path) -> NetSpec:
         return NetSpec(layers, pool=int(z["pool"]), max_range=float(z["max_range"]), beam_first=int(z["beam_first"]), n_beams=int(z["n_beams"]),
                        use_state=bool(int(z["use_state"])), hidden_act=str(z["hidden_act"]), out_act=str(z["out_act"]),
                        out_scale=tuple(z["out_scale"]), out_offset=tuple(z["out_offset"]), **frame)
+
+
+def stack_params(specs) -> np.ndarray:
+    """float32 [len(specs), param_count]: the flat parameters of specs of one shape, a row per member -- what
+    ``set_net_population`` takes.  Specs whose ``shape_key()`` differ are refused (ValueError)."""
+    specs = list(specs)
+    if not specs or not all(isinstance(s, NetSpec) for s in specs):
+        raise ValueError("stack_params: a non-empty list of NetSpec")
+    for i, s in enumerate(specs):
+        if s.shape_key() != specs[0].shape_key():
+            raise ValueError(f"stack_params: spec {i} differs in shape or input fields from spec 0: {s.shape_key()} != {specs[0].shape_key()}")
+    return np.stack([s.flat_params() for s in specs])
 
 
 def from_torch(module, **input_fields) -> NetSpec:

@@ -327,6 +327,7 @@ class DeviceVecEnv:
                                    yaw_tan=math.tan(0.5 * start_yaw_jitter), shuffle_grid=bool(shuffle_grid))
             self.env.set_spawn_rule(True, **self.start_rule)
         self._nets = {}                              # slot -> (shape key, the device tensor of the parameters last handed over)
+        self._pops = {}                              # slot -> (n_members, the device tensors last handed over): slots with a population
         for slot, spec in net_specs.items():
             self.set_net(slot, spec)
         z = dict(device=self.device)
@@ -455,17 +456,19 @@ class DeviceVecEnv:
         if spec_or_module is None:
             self.env.set_net(slot, None)
             self._nets.pop(slot, None)
+            self._pops.pop(slot, None)
             return
         spec = self._net_spec(spec_or_module, self.n_rays, **input_fields)
         key = spec.shape_key()
-        if slot in self._nets and self._nets[slot][0] == key:
+        if slot in self._nets and self._nets[slot][0] == key and slot not in self._pops:
             with torch.cuda.device(self.device):
                 params = torch.from_numpy(spec.flat_params()).to(self.device, non_blocking=False)
                 self.env.set_net_device(slot, params.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
             self._nets[slot] = (key, params)         # (kept until the next one: the library reads it in stream order)
             return
-        self.env.set_net(slot, spec.layers, **spec.input_fields())
+        self.env.set_net(slot, spec.layers, **spec.input_fields())      # (defines the slot without a population)
         self._nets[slot] = (key, None)
+        self._pops.pop(slot, None)
 
     def set_net_params(self, slot, params):
         """New parameters for a defined slot from a float32 tensor on the env's device in ftgp_set_net's flat layout (``NetSpec.flat_params``),
@@ -473,10 +476,70 @@ class DeviceVecEnv:
         slot = self._check_net_slot(slot)
         if slot not in self._nets:
             raise ValueError(f"network slot {slot} is not defined: set_net first")
+        if slot in self._pops:
+            raise ValueError(f"network slot {slot} carries a population: set_population replaces its members")
         if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous():
             raise ValueError(f"params: a contiguous float32 tensor on {self.device}")
         self.env.set_net_device(slot, params.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         self._nets[slot] = (self._nets[slot][0], params)
+
+    def set_population(self, slot, params, env_member=None):
+        """Make defined slot ``slot`` a population (ftgp_set_net_population): ``params`` [n_members, count] float32, a row per member in
+        ``NetSpec.flat_params``' layout (``net.stack_params``), and ``env_member`` [n_envs] integers.  ``env_member=None`` is always
+        "env e runs member e % n_members"; ``env_member="keep"`` leaves the map of a population of as many members in force (ValueError
+        without one).  Env e's cars driven by ``"net<slot>"`` -- in ``step``, ``collect(slot=...)`` and the roster -- then run member
+        env_member[e].  numpy arrays go the host way (synchronises; a map entry outside [0, n_members) is a ValueError).  Torch tensors
+        on the env's device replace the members and the map (int32) of a population of the same n_members on torch's current stream
+        without a synchronisation -- the ES loop --, where a map entry out of range cannot be refused and is taken as member 0; the
+        first population of a slot, or another n_members, is allocated through the host way.  ``params=None`` removes the population:
+        the slot's own network drives again."""
+        slot = self._check_net_slot(slot)
+        if slot not in self._nets:
+            raise ValueError(f"network slot {slot} is not defined: set_net first")
+        if params is None:
+            capi.net_population_args(None, None if isinstance(env_member, str) else env_member, self.n_envs)
+            self.env.set_net_population(slot, None)
+            self._pops.pop(slot, None)
+            return
+        widths = self._nets[slot][0][0]
+        count = sum(widths[l + 1] * widths[l] + widths[l + 1] for l in range(len(widths) - 1))
+        keep = isinstance(env_member, str)
+        if keep:
+            n = getattr(params, "shape", (None,))[0]
+            if env_member != "keep" or slot not in self._pops or self._pops[slot][0] != n:
+                raise ValueError(f'env_member="keep": slot {slot} must carry a population of as many members as params has rows; got {env_member!r}')
+        if isinstance(params, torch.Tensor):
+            m = None if keep else env_member
+            if params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or params.dim() != 2:
+                raise ValueError(f"params: a contiguous float32 tensor [n_members, count] on {self.device}, or a numpy array")
+            if m is not None and (not isinstance(m, torch.Tensor) or m.dtype != torch.int32 or m.device != self.device
+                                  or not m.is_contiguous() or tuple(m.shape) != (self.n_envs,)):
+                raise ValueError(f"env_member: with a tensor of params, a contiguous int32 tensor [{self.n_envs}] on {self.device}, or None")
+            if params.shape[1] != count:
+                raise ValueError(f"params: the slot's networks have {count} parameters, got rows of {params.shape[1]}")
+            if slot in self._pops and self._pops[slot][0] == params.shape[0]:
+                with torch.cuda.device(self.device):
+                    if m is None and not keep:
+                        m = (torch.arange(self.n_envs, dtype=torch.int32, device=self.device) % params.shape[0]).contiguous()
+                    self.env.set_net_population_device(slot, params.data_ptr(), m.data_ptr() if m is not None else 0,
+                                                       torch.cuda.current_stream(self.device).cuda_stream)
+                self._pops[slot] = (params.shape[0], params, m)      # (kept until the next ones: read in stream order)
+                return
+            params, env_member = params.cpu().numpy(), (m.cpu().numpy() if m is not None else None)
+        if keep:
+            env_member = self.env.get_net_population(slot)[1]
+        p, m = capi.net_population_args(params, env_member, self.n_envs, count)
+        self.env.set_net_population(slot, p, m)
+        self._pops[slot] = (p.shape[0], None, None)
+
+    def population(self, slot):
+        """(n_members, env_member int32 [n_envs], params float32 [n_members, count]) of a slot's population as the library holds it
+        (synchronises), or None for a slot without one."""
+        slot = self._check_net_slot(slot)
+        n, m = self.env.get_net_population(slot)
+        if n == 0:
+            return None
+        return n, m, np.stack([self.env.get_net_population(slot, k) for k in range(n)])
 
     def reset(self):
         """Reset every env (synchronous ftgp_reset, which follows the start rule); obs = the scans right after a reset, all zeros

@@ -864,6 +864,43 @@ int ftgp_set_net_rivals(FtgpEnv *env, int slot, const FtgpNetDesc *desc, const F
                         const FtgpNetRivals *rivals, const float *params);
 int ftgp_get_net_rivals(FtgpEnv *env, int slot, FtgpNetRivals *rivals_out);
 
+/* ---- Network populations: one parameter set per env in a single launch (no reference counterpart) ------------------------------------
+ * A defined slot may carry a population: n_members parameter sets of the slot's shape and an env-to-member map.  A car of env e (the
+ * handle's local env index) driven by that slot is evaluated with the parameters of member env_member[e] -- in the step kernel's driver
+ * phase (ftgp_rollout, ftgp_step_device and their kin), in ftgp_policy_eval and in ftgp_collect_device (Act and next_inputs).  Nothing
+ * else about the network driver changes: the inputs, the order of operations, TANH, the guard and the finished-car rule are the text of
+ * "Network drivers" above, with "the slot's parameters" read as "the parameters of the env's member".  Evolution strategies,
+ * population-based training, a league of checkpoints, a sweep of policies: M sets side by side, no launch per set.
+ *
+ * ftgp_set_net_population (host buffers; may synchronise).  params = float32[n_members][count], count = the floats ftgp_get_net returns
+ * for the slot (ftgp_set_net's layout with the slot's true n_in), member after member.  env_member = int32[n_envs], or NULL for
+ * env_member[e] = e % n_members.  Everything is checked before anything changes, and a refused call leaves the slot as it was:
+ * FTGP_ERR_STATE for a slot that is not defined; FTGP_ERR_ARG, naming the field, for a slot outside 0 .. 3, n_members outside
+ * 0 .. n_envs, params == NULL with n_members > 0, an env_member entry outside [0, n_members).  A failed allocation is FTGP_ERR_HIP with
+ * nothing changed.  n_members == 0 removes the population: the slot's single parameter set, which is kept throughout, is in force
+ * again.  A second call replaces the population, members and map.
+ *
+ * ftgp_set_net_population_device replaces the members' parameters and/or the map of a slot that carries a population, from device
+ * memory on the handle's device in the same layouts (NULL = keep), ordered on `stream` exactly as ftgp_set_net_device; it only
+ * enqueues.  n_members stays what the host setter made it.  The buffers are checked as ftgp_step_device checks its own before anything
+ * is enqueued; FTGP_ERR_STATE for a slot that is not defined or carries no population.  The map's entries cannot be checked without a
+ * synchronisation: an entry outside [0, n_members) is taken as member 0.
+ *
+ * ftgp_get_net_population (host, synchronous): n_members (0 = no population); the map in force; the parameters of member `member` in
+ * the caller's layout.  Each output may be NULL; asking for the map or for parameters of a slot without a population is FTGP_ERR_STATE,
+ * a member outside [0, n_members) with params_out set is FTGP_ERR_ARG.
+ *
+ * With the other entries: ftgp_set_net, ftgp_set_net_frame and ftgp_set_net_rivals (re)define a slot without a population.
+ * ftgp_set_net_device on a slot with a population is FTGP_ERR_STATE (use ftgp_set_net_population_device).  ftgp_get_net keeps returning
+ * the description and the slot's single set.  ftgp_reset, auto-reset, the spawn rule, the dynamics table and the ftgp_device_io_*
+ * setters leave the population and the map alone, and so do the env-state calls: an env that loads another env's state keeps its own
+ * member -- the member belongs to the env index, not to the state record, which is unchanged (FTGP_ENV_STATE_VERSION too).
+ * Memory: a member takes the slot's library layout (every layer's outputs padded to 64) rounded up to 64 floats; with n_members different
+ * members in flight every car streams its own weights, which the cars of one member share through L2. */
+int ftgp_set_net_population(FtgpEnv *env, int slot, int n_members, const float *params, const int32_t *env_member);
+int ftgp_set_net_population_device(FtgpEnv *env, void *stream, int slot, const float *params, const int32_t *env_member);
+int ftgp_get_net_population(FtgpEnv *env, int slot, int32_t *n_members_out, int32_t *env_member_out, int member, float *params_out);
+
 /* ---- Collected rollouts: T decisions of a network on the device, written down (no reference counterpart) ------------------------------
  * ftgp_collect_device drives every external slot of a device-io handle with network slot `slot` for n_decisions = T decisions, with
  * optional exploration noise, and records per decision what the network saw, what it proposed, what was applied and what came back.

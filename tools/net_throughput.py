@@ -2,7 +2,8 @@
 with one agent whose network torch evaluates.
 
     python tools/net_throughput.py [--envs 4096] [--rays 1080] [--steps 500] [--launches 5] [--track track] [--calls 500]
-                                   [--decisions 100] [--rows rollout,agent,collect,roster,collect2]
+                                   [--decisions 100] [--rows rollout,agent,collect,roster,collect2,population,sequential]
+                                   [--members 1,64,4096]
 
 rollout rows: one launch of --steps steps per measurement, --launches of them after one warm-up launch; env-steps/s from the wall clock
 around the launch and its synchronisation, and the step kernel's own time from ftgp_last_kernel_ms.  The network is a random
@@ -14,6 +15,12 @@ roster rows (--rows roster): --envs envs of FOUR cars, a roster of four network 
 in every slot, and the same network with the rival row of three mate slots behind its inputs (85 + 4 + 8 * 3 -> ..., ftgp_set_net_rivals)
 -- what the rival inputs cost, and the MULTI NET step kernels' timing.  us per step is the launch's; per decision it is that over the
 four cars.  collect2 rows (--rows collect2): collect with two agents and two bundled cars per env, without and with the rival inputs.
+population rows (--rows population): the rollout row's network as a population (ftgp_set_net_population) of --members members on
+--envs envs, env e running member e % M, every member a perturbation of the network drawn by torch on the device and handed over by
+ftgp_set_net_population_device: one launch of --steps steps runs them all.  member_steps_per_s = envs x steps over the wall clock.
+sequential row (--rows sequential): the way without a population, for the middle --members entry M: ONE handle of envs / M envs, and
+per member an ftgp_set_net_device and a launch of --steps steps, M launches; member_steps_per_s = envs x steps over the wall clock
+of the M launches.  It uses no population entry, so the same file runs on a tree from before them.
 agent row: DeviceVecEnv(roster=["agent"], scan_pool, scan_max_range, state=True), the same network as an nn.Sequential evaluated by
 torch before every call, --calls calls of one step; per-call time from HIP events on torch's stream.
 collect row: the same env with the network in slot 0, DeviceVecEnv.collect (ftgp_collect_device) of --decisions decisions a call with
@@ -54,6 +61,7 @@ def main():
     ap.add_argument("--pool", type=int, default=10)
     ap.add_argument("--track", default="track")
     ap.add_argument("--rows", default="rollout,agent")
+    ap.add_argument("--members", default="1,64,4096")
     a = ap.parse_args()
     eighth = int(a.rays / 8.0)
     first = -(-eighth // a.pool)
@@ -82,6 +90,60 @@ def main():
                 print(json.dumps({"row": f"rollout {policy}" + (" frame" if what is spec_frame else ""), "envs": a.envs, "rays": a.rays, "steps": a.steps, "kernel": g.kernel_name(),
                                   "env_steps_per_s": a.envs * a.steps / float(np.median(wall)), "kernel_ms_median": float(np.median(kern)),
                                   "kernel_us_per_step": 1e3 * float(np.median(kern)) / a.steps, "off_track": int(g.progress()[:, 5].sum())}), flush=True)
+    members = [int(m) for m in a.members.split(",")]
+
+    def perturbed(n):
+        gen = torch.Generator(device="cuda"); gen.manual_seed(n)
+        theta = torch.from_numpy(spec.flat_params()).to("cuda")
+        return (theta[None, :] + 0.05 * torch.randn((n, theta.numel()), generator=gen, device="cuda")).contiguous()
+    if "population" in rows:
+        lib = capi.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        for M in members:
+            with capi.Env(lib, track, n_envs=a.envs, n_rays=a.rays, spawn_mode=1, seed=7) as g:
+                g.set_net(0, spec.layers, **spec.input_fields())
+                params = perturbed(M)
+                # what one car reads of its member per step: every layer's n_in rows and its bias, each padded to 64 floats (the library's layout)
+                w = spec.widths
+                row_bytes = sum((w[l] + 1) * 4 * 64 * -(-w[l + 1] // 64) for l in range(len(w) - 1))
+                g.set_net_population(0, np.zeros((M, spec.param_count), dtype=np.float32))       # allocates; the members come from the device
+                g.set_net_population_device(0, params.data_ptr(), 0, stream)
+                g.rollout("net0", a.steps)
+                g.steps()
+                wall, kern = [], []
+                for _ in range(a.launches):
+                    t0 = time.perf_counter()
+                    g.set_net_population_device(0, params.data_ptr(), 0, stream)                # a generation's hand-over is part of its cost
+                    g.rollout("net0", a.steps)
+                    kern.append(g.last_kernel_ms())
+                    wall.append(time.perf_counter() - t0)
+                us = 1e3 * float(np.median(kern)) / a.steps
+                print(json.dumps({"row": f"population of {M}", "members": M, "envs": a.envs, "rays": a.rays, "steps": a.steps, "kernel": g.kernel_name(),
+                                  "member_steps_per_s": a.envs * a.steps / float(np.median(wall)), "kernel_ms_median": float(np.median(kern)),
+                                  "kernel_us_per_step": us, "weights_MB_per_step_if_unshared": 1e-6 * row_bytes * a.envs,
+                                  "off_track": int(g.progress()[:, 5].sum())}), flush=True)
+    if "sequential" in rows:
+        lib = capi.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        M = members[len(members) // 2]
+        with capi.Env(lib, track, n_envs=a.envs // M, n_rays=a.rays, spawn_mode=1, seed=7) as g:
+            g.set_net(0, spec.layers, **spec.input_fields())
+            params = perturbed(M)
+            g.rollout("net0", a.steps)
+            g.steps()
+            wall, kern = [], []
+            for _ in range(a.launches):
+                t0 = time.perf_counter()
+                k = 0.0
+                for m in range(M):
+                    g.set_net_device(0, params[m].data_ptr(), stream)
+                    g.rollout("net0", a.steps)
+                    k += g.last_kernel_ms()
+                wall.append(time.perf_counter() - t0)
+                kern.append(k)
+            print(json.dumps({"row": f"sequential: {M} launches of {a.envs // M} envs", "members": M, "envs": a.envs // M, "rays": a.rays, "steps": a.steps,
+                              "kernel": g.kernel_name(), "member_steps_per_s": (a.envs // M) * M * a.steps / float(np.median(wall)),
+                              "kernel_ms_median_all_launches": float(np.median(kern)), "kernel_us_per_step_one_launch": 1e3 * float(np.median(kern)) / (M * a.steps)}), flush=True)
     if "roster" in rows:
         lib = capi.load()
         for what, label in ((spec, "roster of four net slots"), (spec_rivals, "roster of four net slots, rival inputs")):
