@@ -345,6 +345,7 @@ int open_device(int id)
 enum { kOrderBlocks = 0, kOrderXcd = 1 };     // FTGP_TRACK_ORDER (plan_workgroups)
 struct Switches {
     bool no_pairs = false, group_order_plain = false, puck_test = false, no_fused_metrics = false, no_host_sum = false, launch_plain = false, verbose = false;
+    bool scan_every_step = false;     // FTGP_SCAN_EVERY_STEP: no window-only steps (plan_window_table)
     int sectors_rt = 0;               // 8, 16, 32 or 64 direction sectors; 0: by car count (sector_count)
     int waves_per_block = 16;         // 1 .. 16
     int cars_per_block = 0;           // as given: plan_shape takes it where it is in range, rounded down to whole envs
@@ -359,6 +360,7 @@ Switches read_switches()
     sw.no_pairs = getenv("FTGP_NO_PAIRS") != nullptr; sw.group_order_plain = getenv("FTGP_GROUP_ORDER_PLAIN") != nullptr; sw.puck_test = getenv("FTGP_PUCK_TEST") != nullptr;
     sw.no_fused_metrics = getenv("FTGP_NO_FUSED_METRICS") != nullptr; sw.no_host_sum = getenv("FTGP_NO_HOST_SUM") != nullptr;
     sw.launch_plain = getenv("FTGP_LAUNCH_PLAIN") != nullptr; sw.verbose = getenv("FTGP_VERBOSE") != nullptr;
+    if (const char* sv = getenv("FTGP_SCAN_EVERY_STEP")) sw.scan_every_step = atoi(sv) != 0;
     if (const char* sv = getenv("FTGP_SECTORS_RT")) { const int c = atoi(sv); if (c == 8 || c == 16 || c == 32 || c == 64) sw.sectors_rt = c; }
     if (const char* sv = getenv("FTGP_WAVES_PER_BLOCK")) { const int c = atoi(sv); if (c >= 1 && c <= 16) sw.waves_per_block = c; }
     if (const char* sv = getenv("FTGP_CARS_PER_BLOCK")) sw.cars_per_block = atoi(sv);
@@ -422,6 +424,7 @@ struct Plan {
     std::vector<float> cover;         // cover-count thresholds of nidc, then of fast, cover_kmax + 1 each (+ padding)
     std::vector<unsigned char> veh;   // the VehLds image, padded to 16 bytes
     std::vector<int32_t> tasks;       // [2][cars_per_block * tasks_per_car][4] the sweep's task tables (DeviceParams::task_tab)
+    std::vector<int32_t> tasks_win;   // [cars_per_block * win_tasks_per_car][4] the window-only table, behind them in the parameter image (plan_window_table)
     std::vector<int32_t> wg;          // [n_wg][4] the workgroup table: block offset (set by layout_images), first car, cars, track.  Uploaded for several tracks only
     std::vector<int32_t> env_track;   // [n_envs]; uploaded for several tracks only
     int n_wg = 0;                     // workgroups of a step launch
@@ -543,6 +546,59 @@ int plan_task_table(const DeviceParams& P, std::vector<int32_t>& tt)
         a[3] = b[3] = 4 * (c * P.win_floats + (P.eighth & 3) - P.eighth);
     }
     return 0;
+}
+
+// The window-only table (DeviceParams::task_tab's third; tt: the two tables of plan_task_table).  Inside a launch whose drivers read the scan, a range
+// of any step but the last has one reader, the next step's driver, and that reads ranges[0] and ranges[eighth : n - eighth]: every other ray of
+// such a step -- the rear quarter of the fan, where the rays look down the track and march longest -- is overwritten unread.  So those steps draw
+// from a list without them: the first table's tasks in its order (long first, the short singles of FTGP_PAIR_TAIL at the end), less the tasks that
+// hold no ray the drivers read; a pair of which one whole group is unread goes out as the other group alone (bit 26 where that is the second
+// one: its mate mask is the pair's second); a task that keeps unread rays says so (bit 25) and its lanes test their ray (lidar_groups).  Ray 0
+// stays lane 0 of its group.  The rank in [1] is still the group's in group_order: mate_masks() is what it was.  A fan without an unread ray
+// (n_rays < 8) gets the first table again.  FTGP_SCAN_EVERY_STEP: no such table, win_tasks_per_car = 0.
+void plan_window_table(const Switches& sw, const std::vector<int32_t>& tt, DeviceParams& P, std::vector<int32_t>& tw)
+{
+    const int cpb = P.cars_per_block, R = P.n_rays, halfR = R / 2;
+    tw.clear();
+    P.win_tasks_per_car = 0;
+    if (sw.scan_every_step) {
+        if (sw.verbose) fprintf(stderr, "ftgp_create: FTGP_SCAN_EVERY_STEP: every step of a launch sweeps and stores every ray\n");
+        return;
+    }
+    auto live = [&](int j) { return j == 0 || (j >= P.eighth && j < R - P.eighth); };
+    std::vector<std::pair<int, uint32_t>> list;      // (rank, [0] of car slot 0)
+    for (int k = 0; k < P.tasks_per_car; ++k) {
+        uint32_t x = (uint32_t)tt[4 * (size_t)k * cpb];
+        const int j0 = x & 0x3fff, kind = (x >> 14) & 3;
+        int n[2] = { 0, 0 }, l[2] = { 0, 0 };        // rays, and rays somebody reads, of the task's first / second group
+        for (int lane = 0; lane < FTGP_WAVE; ++lane) {
+            int j; bool mine;
+            if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? halfR : 0); mine = (lane & 31) < halfR - j0; }
+            else { j = j0 + lane; mine = j < (kind == 1 ? halfR : R); }
+            if (!mine) continue;
+            ++n[0]; l[0] += live(j) ? 1 : 0;
+            if (kind == 1) { ++n[1]; l[1] += live(j + halfR) ? 1 : 0; }
+        }
+        if (l[0] + l[1] == 0) continue;
+        if (kind == 1 && n[0] == FTGP_WAVE && (l[0] == 0 || l[1] == 0)) {      // (a pair of whole groups: either is a single group's 64 lanes)
+            if (l[0] == 0) { x = (uint32_t)(j0 + halfR) | ((x >> 22) & 3u) << 20 | 1u << 26; n[0] = n[1]; l[0] = l[1]; }
+            else x &= ~(3u << 14 | 3u << 22);
+            n[1] = l[1] = 0;
+        }
+        if (l[0] + l[1] < n[0] + n[1]) x |= 1u << 25;
+        list.push_back({ k, x });
+    }
+    P.win_tasks_per_car = (int)list.size();
+    const int ntasks = cpb * P.win_tasks_per_car;
+    tw.assign(4 * (size_t)ntasks, 0);
+    for (int g = 0; g < ntasks; ++g) {
+        const int c = g % cpb, kidx = list[(size_t)(g / cpb)].first;
+        const int32_t* a = &tt[4 * ((size_t)kidx * cpb + c)];
+        int32_t* w = &tw[4 * (size_t)g];
+        w[0] = (int32_t)(list[(size_t)(g / cpb)].second | (uint32_t)c << 16);
+        w[1] = a[1]; w[2] = a[2]; w[3] = a[3];
+    }
+    if (sw.verbose) fprintf(stderr, "ftgp_create: %d of them on the window-only steps of a launch\n", P.win_tasks_per_car);
 }
 
 // the map's diagonal in world units: no ray between two cars on the map is longer
@@ -680,6 +736,7 @@ int plan(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per
     plan_fan(cfg, pl.ray, pl.fan);
     plan_task_order(cfg, pl.ray, sw, P);
     if (int rc = plan_task_table(P, pl.tasks)) return rc;
+    plan_window_table(sw, pl.tasks, P, pl.tasks_win);
     {   // cover-count thresholds: nidc (car_width 0.12, nidc.py:5) then fast (0.06, fast.py:4), each padded to the staged size
         const size_t stride = (size_t)P.cover_kmax + 1, padded = (size_t)pad16(sizeof(float) * stride) / sizeof(float);
         pl.cover.assign(stride + padded + 4, 0.0f);
@@ -719,7 +776,7 @@ struct DeviceAddrs {
     const unsigned char* params = nullptr, * stage = nullptr;              // where the two images will lie
 };
 
-// Sizes of the two images.  Parameter image: track 0's block | (several tracks: the workgroup table) | the sweep's task tables | the
+// Sizes of the two images.  Parameter image: track 0's block | (several tracks: the workgroup table) | the sweep's task tables, all three | the
 // blocks of tracks 1 .. T - 1.  Staging image, one per track: the LDS bytes [off_params, off_cars) as every workgroup of the track wants
 // them, then both drivers' cover tables.
 struct ImageSizes { size_t head, wg, tasks, params, stage_head, stage; };
@@ -728,7 +785,7 @@ ImageSizes image_sizes(const Plan& pl)
     const size_t T = pl.tracks.size();
     const DeviceParams& P = pl.tracks[0].P;
     ImageSizes z;
-    z.head = FTGP_PARAMS_BYTES; z.wg = T > 1 ? sizeof(int32_t) * pl.wg.size() : 0; z.tasks = sizeof(int32_t) * pl.tasks.size();
+    z.head = FTGP_PARAMS_BYTES; z.wg = T > 1 ? sizeof(int32_t) * pl.wg.size() : 0; z.tasks = sizeof(int32_t) * (pl.tasks.size() + pl.tasks_win.size());
     z.params = z.head + z.wg + z.tasks + (T - 1) * z.head + 16;
     z.stage_head = (size_t)(P.off_cars - P.off_params);
     z.stage = z.stage_head + 2 * (size_t)P.stage_cover;
@@ -778,7 +835,8 @@ void layout_images(const Plan& pl, const DeviceAddrs& a, Images& im)
         for (size_t b = 0; b < wg.size(); b += 4) wg[b] = (int32_t)im.blocks[(size_t)wg[b + 3]];
         memcpy(im.params.data() + z.head, wg.data(), z.wg);
     }
-    memcpy(im.params.data() + z.head + z.wg, pl.tasks.data(), z.tasks);
+    memcpy(im.params.data() + z.head + z.wg, pl.tasks.data(), sizeof(int32_t) * pl.tasks.size());
+    memcpy(im.params.data() + z.head + z.wg + sizeof(int32_t) * pl.tasks.size(), pl.tasks_win.data(), sizeof(int32_t) * pl.tasks_win.size());
 }
 
 // nidc or fast, for every car or for some car of the roster

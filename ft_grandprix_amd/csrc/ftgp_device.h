@@ -88,7 +88,8 @@ struct DeviceParams {
     const double* edt;            // [height][width] exact Euclidean distance to the nearest wall pixel (0 on walls), pixels; null in RANGEFINDER mode
     const double* fan_dirs;       // [n_rays][2] body-frame fan directions, binary64
     double map_size;              // 20 * scale = 40 (custom.py:1382)
-    int32_t lidar_mode, pad_e;
+    int32_t lidar_mode;
+    int32_t win_tasks_per_car;    // tasks per car of the window-only table (task_tab's third); 0: FTGP_SCAN_EVERY_STEP, every step sweeps and stores every ray (a word that was spare)
     int32_t tasks_per_car;        // the sweep's work list per car (lidar_groups): groups of 64 consecutive rays, or pairs of opposite groups
     float group_cg, group_sg;     // cos / sin of the half-width of a ray group as mate_masks() needs it (cg < -1: no bound, e.g. a caller's fan)
     uint32_t dyn_table_hi;        // ... and its high half (two words that were spare: the block's layout is what it was)
@@ -132,6 +133,11 @@ struct DeviceParams {
                                   //   [2] byte offset of the car's row of ranges from the workgroup's first row
                                   //   [3] byte offset, in a scan buffer, at which sample j of the car sits when 4 j is added: row + ((eighth & 3) - eighth) floats
                                   // the second table is for launches whose drivers do not read the scan: window classes 0, no ray 0
+                                  // Behind the two, [cars_per_block * win_tasks_per_car][4]: the window-only table, for every step but the last of a launch whose
+                                  // drivers read the scan -- only the groups that hold a ray the drivers read (ranges[0], ranges[eighth : n - eighth]), in the first
+                                  // table's order and with its fields ([1]: the rank is still the group's in group_order), and in [0]
+                                  //   bit 25: some ray of the task is read by nobody before the next step overwrites it -- such a lane holds no ray
+                                  //   bit 26: a single group that is the opposite group of pair `rank`: its mate mask is the pair's second (mate_masks)
 };
 
 // Bytes of one parameter block in device memory.  Multi-track handles (ftgp_create_tracks): the workgroup table follows track 0's block,

@@ -389,7 +389,7 @@ __device__ __forceinline__ void march_all(float& s, uint32_t& w, float pu, float
 // a PAIR of groups, j0 .. j0 + 63 and the same rays turned round: the second group keeps the first one's |direction|, reciprocals and
 // slope slice (the two divisions and the sector search are half of a set-up) and only places its rays anew (ftgp_ray_place with
 // sector ^ 3).  Tasks are drawn long-first across the workgroup's cars (group_order), so that the waves end a sweep together.
-template <bool MULTI>
+template <bool MULTI, bool WINDOW>
 __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams G, const Lds& L, const LidarFrame* frames, const PairCull* pairs, const unsigned char* mmask,
                                              float* scan_rows, int* pool, int ncars_here, int ci0, bool scan_lds, bool second_half STAMP_ARG)
 {
@@ -397,14 +397,19 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
     typedef __attribute__((address_space(1))) unsigned char* global_u8w;
     struct alignas(16) Task { int32_t x, y, z, w; };
     typedef const __attribute__((address_space(4))) Task* ScalarTasks;
-    const int R = G->n_rays, half = R >> 1, ntasks = G->cars_per_block * G->tasks_per_car;
+    // WINDOW (implies scan_lds): a step whose ranges only the next step's drivers read -- every step of such a launch but its last.  The
+    // draws come from the third table (plan_window_table): the rays outside the drivers' window are not marched, and no range goes to HBM --
+    // the launch's last step writes every row.  An instantiation of its own: with WINDOW = false the code is exactly what it was.
+    constexpr bool window_only = WINDOW;
+    const int full_tasks = G->cars_per_block * G->tasks_per_car;
+    const int R = G->n_rays, half = R >> 1, ntasks = window_only ? G->cars_per_block * G->win_tasks_per_car : full_tasks;
     const int W = G->width, H = G->height, fstride = G->fstride;
     const uint32_t plane256 = G->plane256;
     const int eighth = G->eighth, win_floats = G->win_floats;
     const float isx = G->inv_px_x_f, isy = G->inv_px_y_f, thr = 0.5f - G->snap_eps, nsf = G->slice_factor;
     const float r0 = sgpr(L.veh->ring_radius_f);
     const void* field = G->field;
-    const ScalarTasks tasks = (ScalarTasks)G->task_tab + (scan_lds ? 0 : ntasks);      // (the second table: no ray goes to a scan window)
+    const ScalarTasks tasks = (ScalarTasks)G->task_tab + (window_only ? 2 * full_tasks : scan_lds ? 0 : full_tasks);      // (the second table: no ray goes to a scan window)
     const global_u8w ranges = (global_u8w)((global_f32)G->ranges + (size_t)ci0 * G->ranges_stride);      // the workgroup's first row
     const int mmask_stride = G->mmask_stride;
     const int lane = lane_here();
@@ -431,6 +436,12 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
         if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? half : 0); mine = (lane & 31) < half - j0; }
         else { j = j0 + lane; mine = j < (kind == 1 ? half : R); }
         mine = mine && c < ncars_here;               // (a ragged last workgroup draws tasks of cars it does not have)
+        bool first = mine;                           // the lanes that march a ray of the first group
+        if (WINDOW && (task.x & (1 << 25))) {        // window-only table: some ray of the task has no reader, and its lane holds no ray.  (A pair's set-up
+            asm volatile("");                        // runs on the lanes of either group: the second group's rays are the first one's turned round.)
+            first = mine && (j == 0 || (unsigned)(j - eighth) < (unsigned)(R - 2 * eighth));
+            mine = first || (kind == 1 && mine && (unsigned)(j + half - eighth) < (unsigned)(R - 2 * eighth));
+        }
         const LidarFrame* frame = reinterpret_cast<const LidarFrame*>(reinterpret_cast<const unsigned char*>(frames) + (task.y & 0xffff));
         FtgpRay ray;
         float du, dv, dxw, dyw, opu, opv;              // opu, opv: the ray's origin in pixels
@@ -450,8 +461,9 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
                 const PairCull* mates = pairs + c * FTGP_PAIR_STRIDE;
                 const int slot0 = sgpr(frame->slot0);
                 // ... and one byte per (car, group) says which mates the group's rays can see at all (mate_masks): mostly none
+                // (window-only table, bit 26: a single group that is the second group of pair kidx)
                 const int kidx = task.y >> 16;
-                uint32_t mm = (uint32_t)sgpr((int)mmask[c * mmask_stride + 2 * kidx + pass]);
+                uint32_t mm = (uint32_t)sgpr((int)mmask[c * mmask_stride + 2 * kidx + pass + (WINDOW ? (task.x >> 26) & 1 : 0)]);
                 while (mm) {
                     const int k = __builtin_ctz(mm); mm &= mm - 1u;
                     const float4 q = *reinterpret_cast<const float4*>(mates + k);
@@ -465,9 +477,10 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
                 }
             }
             // every range leaves for HBM now, 64 consecutive floats per wave (one 256-byte row segment); the window the on-device drivers
-            // read next step -- ranges[0] and ranges[eighth : n - eighth] -- is kept in LDS as well
+            // read next step -- ranges[0] and ranges[eighth : n - eighth] -- is kept in LDS as well.  (Not on a window-only step: nobody reads
+            // its rows before the launch's last step has written them again.)
             const uint32_t j4 = (uint32_t)j << 2;
-            *(global_f32)(ranges + (j4 + (uint32_t)task.z)) = r;
+            if (!window_only) *(global_f32)(ranges + (j4 + (uint32_t)task.z)) = r;
             // task.w: byte offset of the car's scan row + ((eighth & 3) - eighth) floats, so that sample j sits at task.w + 4 j.  Whether the
             // group's rays lie inside the window, outside it or across one of its ends is the task's to know (two bits per pass; all zero in
             // the table of a launch whose drivers do not read the scan).  The rare cases sit behind scalar branches that the optimiser is kept
@@ -506,8 +519,9 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
             }
         }
         STAMP(td); STAMP_ADD(8, td - ta);
-        finish(mine, 0);
+        finish(first, 0);
         if (kind == 1) {                 // the same rays turned round: ray j + n/2 = -(ray j), exactly
+            if (WINDOW && (task.x & (1 << 25))) { asm volatile(""); mine = mine && (unsigned)(j + half - eighth) < (unsigned)(R - 2 * eighth); }
             if (mine) {
                 j += half;
                 const float2 f2 = *reinterpret_cast<const float2*>(frame);
@@ -599,19 +613,20 @@ __device__ __forceinline__ void march_fake(double& x, double& y, double& dist, i
 // The FAKELIDAR sweep of one step for all cars of the workgroup: the task list, the draw and the delivery of lidar_groups() -- groups of 64
 // neighbouring rays of one car, long-first across the workgroup's cars, a pair's two groups one after the other -- around march_fake().
 // What depends on the car alone -- i_x, i_y (two binary64 divisions) and the heading -- comes with its LiDAR frame (frame_write).
-__device__ __forceinline__ void lidar_fake(ScalarParams G, const LidarFrame* frames, float* scan_rows, int* pool, int ncars_here, int ci0, bool scan_lds)
+__device__ __forceinline__ void lidar_fake(ScalarParams G, const LidarFrame* frames, float* scan_rows, int* pool, int ncars_here, int ci0, bool scan_lds, bool window_only)
 {
     typedef __attribute__((address_space(1))) float* global_f32;
     typedef __attribute__((address_space(1))) unsigned char* global_u8w;
     struct alignas(16) Task { int32_t x, y, z, w; };             // DeviceParams::task_tab (see lidar_groups)
     typedef const __attribute__((address_space(4))) Task* ScalarTasks;
-    const int R = G->n_rays, half = R >> 1, ntasks = G->cars_per_block * G->tasks_per_car;
+    const int full_tasks = G->cars_per_block * G->tasks_per_car;       // window_only: as in lidar_groups -- the third table, no unread ray marched, no range to HBM
+    const int R = G->n_rays, half = R >> 1, ntasks = window_only ? G->cars_per_block * G->win_tasks_per_car : full_tasks;
     const int W = G->width, H = G->height;
     const int eighth = G->eighth, win_floats = G->win_floats;
     const double s = G->map_size;
     const double* dt = G->edt;
     const double* __restrict__ fan = G->fan_dirs;
-    const ScalarTasks tasks = (ScalarTasks)G->task_tab + (scan_lds ? 0 : ntasks);
+    const ScalarTasks tasks = (ScalarTasks)G->task_tab + (window_only ? 2 * full_tasks : scan_lds ? 0 : full_tasks);
     const global_u8w ranges = (global_u8w)((global_f32)G->ranges + (size_t)ci0 * G->ranges_stride);
     const int lane = lane_here();
     for (;;) {
@@ -627,7 +642,7 @@ __device__ __forceinline__ void lidar_fake(ScalarParams G, const LidarFrame* fra
         mine = mine && c < ncars_here;
         const LidarFrame* f = reinterpret_cast<const LidarFrame*>(reinterpret_cast<const unsigned char*>(frames) + (task.y & 0xffff));
         for (int pass = 0; pass < (kind == 1 ? 2 : 1); ++pass, j += half) {
-            if (!mine) continue;
+            if (!mine || ((task.x & (1 << 25)) && j != 0 && (unsigned)(j - eighth) >= (unsigned)(R - 2 * eighth))) continue;
             float r = 0.0f;                                       // a finished car's rangefinders are switched off (custom.py:1436-1439): its scan reads 0
             if (!f->finished) {
                 const double ch = f->x, sh = f->y;                // FAKELIDAR frames: heading (cos, sin) in binary64 (frame_write)
@@ -639,7 +654,7 @@ __device__ __forceinline__ void lidar_fake(ScalarParams G, const LidarFrame* fra
                 r = bad ? -1.0f : (float)((distance / (double)W) * s);     // ranges /= original_width; ranges *= s (custom.py:1392-1393)
             }
             const uint32_t j4 = (uint32_t)j << 2;
-            *(global_f32)(ranges + (j4 + (uint32_t)task.z)) = r;
+            if (!window_only) *(global_f32)(ranges + (j4 + (uint32_t)task.z)) = r;
             const int wclass = (task.x >> (20 + 2 * pass)) & 3;   // the delivery of lidar_groups(): window classes from the task
             if (wclass) {
                 float* dst = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(scan_rows) + task.w + j4);
@@ -2083,9 +2098,17 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
             const LdsOffsets off = lds_offsets(G);
             const DeviceParams& P = *reinterpret_cast<const DeviceParams*>(lds + off.params);
             const Lds L = lds_view(off, lds);
-            if (FAKE) lidar_fake(G, L.frame + par * cpb, L.scan + par * cpb * G->win_floats, L.pool + par, ncars_here, ci0, need_scan);
-            else lidar_groups<MULTI>(P, G, L, L.frame + par * cpb, L.pairs + par * cpb * FTGP_PAIR_STRIDE, L.mmask + par * cpb * G->mmask_stride, L.scan + par * cpb * G->win_floats,
-                                     L.pool + par, ncars_here, ci0, need_scan, second_half STAMP_PASS);
+            // The ranges of a step inside a launch whose drivers read the scan have one reader: the next step's driver, through the LDS window.
+            // Whatever reads the rows in HBM runs after the launch and sees its last step.  So only that step sweeps the whole fan and stores
+            // it (FTGP_SCAN_EVERY_STEP: win_tasks_per_car = 0, every step does).  A launch whose drivers do not read the scan keeps the full sweep.
+            const bool window_only = need_scan && it != n_steps - 1 && G->win_tasks_per_car != 0;
+            if (FAKE) lidar_fake(G, L.frame + par * cpb, L.scan + par * cpb * G->win_floats, L.pool + par, ncars_here, ci0, need_scan, window_only);
+            else if (window_only)
+                lidar_groups<MULTI, true>(P, G, L, L.frame + par * cpb, L.pairs + par * cpb * FTGP_PAIR_STRIDE, L.mmask + par * cpb * G->mmask_stride, L.scan + par * cpb * G->win_floats,
+                                          L.pool + par, ncars_here, ci0, true, second_half STAMP_PASS);
+            else
+                lidar_groups<MULTI, false>(P, G, L, L.frame + par * cpb, L.pairs + par * cpb * FTGP_PAIR_STRIDE, L.mmask + par * cpb * G->mmask_stride, L.scan + par * cpb * G->win_floats,
+                                           L.pool + par, ncars_here, ci0, need_scan, second_half STAMP_PASS);
         }
         STAMP(t4);
         __syncthreads();

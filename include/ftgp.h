@@ -219,7 +219,8 @@ int ftgp_step(FtgpEnv *env, int n_steps);
 /*
  * Same loop with the driver evaluated on the device between progress and integrate:
  * per step: policy(ranges of the previous step) -> ctrl -> sensors -> integrate -> progress.
- * This is the throughput path; one launch covers all n_steps.
+ * This is the throughput path; one launch covers all n_steps.  The ranges a caller reads afterwards (ftgp_get_lidar and its kin) are
+ * those of the launch's last step; the steps before it leave no ranges but the ones their drivers read (FTGP_SCAN_EVERY_STEP=1: all).
  */
 int ftgp_rollout(FtgpEnv *env, int policy, int n_steps);
 

@@ -7,6 +7,7 @@
 static long g_fail = 0;
 static Fnv g_digest;
 #define CHECK(cond, ...) do { if (!(cond)) { ++g_fail; printf("FAIL %s: ", label); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "plan_window_check.h"
 
 // the binary32 fan is point-symmetric to the bit: ray j + n/2 is the negated ray j (both components, sign bits included)
 static bool point_symmetric(const std::vector<float>& ray, int R)
@@ -100,11 +101,16 @@ static int check(const FtgpConfig& cfg, const Switches& sw, const char* label)
         for (size_t i = 0; i < drawn.size(); ++i) bad += drawn[i] != times[i % R];
         CHECK(bad == 0, "table %d: %ld (car slot, ray) not drawn exactly once (or twice where counted above)", table, bad);
     }
+    check_window_table(pl, times, label, sw.scan_every_step);
     Images im;
     layout_images(pl, made_up_addrs(pl), im);
+    CHECK(im.params.size() >= FTGP_PARAMS_BYTES + sizeof(int32_t) * (pl.tasks.size() + pl.tasks_win.size()) &&
+          memcmp(im.params.data() + FTGP_PARAMS_BYTES, pl.tasks.data(), sizeof(int32_t) * pl.tasks.size()) == 0 &&
+          memcmp(im.params.data() + FTGP_PARAMS_BYTES + sizeof(int32_t) * pl.tasks.size(), pl.tasks_win.data(), sizeof(int32_t) * pl.tasks_win.size()) == 0,
+          "the parameter image: the two task tables, then the window-only table");
     digest_plan(g_digest, pl, im);
-    printf("%s: ok, %d x %d waves, %d B of LDS, %d sectors, %d tasks per car%s, %ld rays drawn twice\n", label, cpb, P.waves_per_block, P.lds_bytes, P.n_sectors,
-           P.tasks_per_car, pairs ? " (pairs)" : "", twice);
+    printf("%s: ok, %d x %d waves, %d B of LDS, %d sectors, %d tasks per car%s (%d window-only), %ld rays drawn twice\n", label, cpb, P.waves_per_block, P.lds_bytes, P.n_sectors,
+           P.tasks_per_car, pairs ? " (pairs)" : "", P.win_tasks_per_car, twice);
     return 0;
 }
 
@@ -160,6 +166,23 @@ int main()
         printf("rays 16385: rejected (%d): %s\n", rc, ftgp_last_error());
         const char* label = "rays 16385";
         CHECK(rc == FTGP_ERR_ARG && strcmp(ftgp_last_error(), "n_rays above 16384 is not supported") == 0, "rc %d", rc);
+    }
+    for (int R : { 36, 1080 }) {   // FTGP_SCAN_EVERY_STEP: no window-only table, the two others as ever (outside the matrix: not counted as a configuration)
+        FtgpConfig cfg{};
+        cfg.abi_version = FTGP_ABI_VERSION;
+        cfg.n_envs = 7; cfg.cars_per_env = 4; cfg.n_rays = R; cfg.spawn_mode = 1; cfg.dt = 0.01;
+        ftgp_default_vehicle(&cfg.vehicle);
+        cfg.track.width = W; cfg.track.height = H; cfg.track.words_per_row = wpr; cfg.track.bits = bits.data(); cfg.track.path = path.data();
+        cfg.track.px_size_x = cfg.track.px_size_y = 0.05;
+        Switches sw;
+        Plan every, usual;
+        const int rc0 = plan(cfg, &cfg.track, &cfg.n_envs, 1, 256, sw, usual);
+        sw.scan_every_step = true;
+        const int rc1 = plan(cfg, &cfg.track, &cfg.n_envs, 1, 256, sw, every);
+        char label[64]; snprintf(label, sizeof label, "rays %d scan_every_step", R);
+        CHECK(rc0 == 0 && rc1 == 0 && every.tasks == usual.tasks && every.tasks_win.empty() && every.tracks[0].P.win_tasks_per_car == 0 && usual.tracks[0].P.win_tasks_per_car > 0,
+              "rc %d / %d, %d window-only tasks per car", rc0, rc1, every.tracks[0].P.win_tasks_per_car);
+        printf("%s: %d window-only tasks per car, %d without the switch (of %d)\n", label, every.tracks[0].P.win_tasks_per_car, usual.tracks[0].P.win_tasks_per_car, usual.tracks[0].P.tasks_per_car);
     }
     printf("digest=%016llx\n", (unsigned long long)g_digest.h);
     printf("plan_check: %ld configs, %ld rejected, %ld failures\n", configs, rejected, g_fail);

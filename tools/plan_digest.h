@@ -32,7 +32,7 @@ static void digest_plan(Fnv& f, const Plan& pl, const Images& im)
         f.bytes(&t.P, sizeof t.P);
         f.vec(t.tab.bits); f.vec(t.tab.nearbits); f.vec(t.tab.runx); f.vec(t.tab.runy); f.vec(t.spawn);
     }
-    f.vec(pl.ray); f.vec(pl.fan); f.vec(pl.cover); f.vec(pl.veh); f.vec(pl.tasks);
+    f.vec(pl.ray); f.vec(pl.fan); f.vec(pl.cover); f.vec(pl.veh); f.vec(pl.tasks); f.vec(pl.tasks_win);
     if (T > 1) { f.vec(pl.wg); f.vec(pl.env_track); }      // (a one-track upload takes neither)
     f.bytes(&pl.n_wg, sizeof pl.n_wg);
     f.vec(im.params); f.vec(im.stage);

@@ -12,6 +12,7 @@
 static long g_fail = 0;
 static Fnv g_digest;
 #define CHECK(cond, ...) do { if (!(cond)) { ++g_fail; printf("FAIL %s: ", label); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "plan_window_check.h"
 
 // a W x H image walled at its border with a block in the middle, a centre-line on an ellipse
 struct SynthTrack {
@@ -53,12 +54,13 @@ static void check_layout(const Plan& pl, const Images& im, const DeviceAddrs& a,
 {
     const int T = (int)pl.tracks.size();
     const DeviceParams& P = pl.tracks[0].P;
-    const size_t head = FTGP_PARAMS_BYTES, wg_bytes = one ? 0 : sizeof(int32_t) * pl.wg.size(), tasks_bytes = sizeof(int32_t) * pl.tasks.size();
+    const size_t head = FTGP_PARAMS_BYTES, wg_bytes = one ? 0 : sizeof(int32_t) * pl.wg.size(), tasks_bytes = sizeof(int32_t) * (pl.tasks.size() + pl.tasks_win.size());      // (all three tables)
     const size_t stage_bytes = (size_t)(P.off_cars - P.off_params) + 2 * (size_t)P.stage_cover, stride = (size_t)P.cover_kmax + 1;
     CHECK(im.blocks.size() == (size_t)T && im.blocks[0] == 0, "block offsets: %zu of them, the first at %zu", im.blocks.size(), im.blocks.empty() ? (size_t)0 : im.blocks[0]);
     CHECK(im.params.size() == head + wg_bytes + tasks_bytes + (size_t)(T - 1) * head + 16 && im.stage.size() == stage_bytes * T, "image sizes %zu / %zu", im.params.size(), im.stage.size());
     CHECK(memcmp(&im.P0, im.params.data(), sizeof im.P0) == 0, "track 0's finished block is not the head of the image");
-    CHECK(memcmp(im.params.data() + head + wg_bytes, pl.tasks.data(), tasks_bytes) == 0, "the task tables do not sit behind %s", one ? "the block" : "the workgroup table");
+    CHECK(memcmp(im.params.data() + head + wg_bytes, pl.tasks.data(), sizeof(int32_t) * pl.tasks.size()) == 0, "the task tables do not sit behind %s", one ? "the block" : "the workgroup table");
+    CHECK(memcmp(im.params.data() + head + wg_bytes + sizeof(int32_t) * pl.tasks.size(), pl.tasks_win.data(), sizeof(int32_t) * pl.tasks_win.size()) == 0, "the window-only table does not sit behind the two task tables");
     if (one) CHECK(im.blocks == std::vector<size_t>{ 0 }, "one track: block offsets");
     else
         for (size_t b = 0; b < pl.wg.size(); b += 4) {       // the workgroup table: the plan's, each entry with its track's block offset
@@ -110,7 +112,7 @@ static int check(const FtgpConfig& cfg, const std::vector<FtgpTrack>& tr, const 
         CHECK(memcmp(&k.P, &k1.P, sizeof k.P) == 0, "track %d: the parameter block differs from its one-track plan's", t);
         CHECK(k.tab.bits == k1.tab.bits && k.tab.nearbits == k1.tab.nearbits && k.tab.runx == k1.tab.runx && k.tab.runy == k1.tab.runy, "track %d: tables differ", t);
         CHECK(k.spawn == k1.spawn && k.path == k1.path, "track %d: spawn table or centre-line differs", t);
-        CHECK(one.tasks == pb.tasks && one.ray == pb.ray, "track %d: the task tables or the fan differ", t);
+        CHECK(one.tasks == pb.tasks && one.tasks_win == pb.tasks_win && one.ray == pb.ray, "track %d: the task tables or the fan differ", t);
         CHECK(one.n_wg == (cfg.n_envs * cpe + cpb - 1) / cpb, "track %d: %d workgroups in its one-track plan", t, one.n_wg);
         if (t == 0) {       // a one-track handle's images: the block, then the task tables
             const DeviceAddrs a = made_up_addrs(one);
@@ -167,6 +169,19 @@ static int check(const FtgpConfig& cfg, const std::vector<FtgpTrack>& tr, const 
         }
     }
     for (const Plan* pl : { &pb, &px }) {
+        {   // the window-only table: every ray the drivers read drawn once, no other, ray 0 present (`times`: a single group split off a short
+            // pair runs on into the opposite half, as plan_check.cpp counts it)
+            const DeviceParams& P = pl->tracks[0].P;
+            const int R = P.n_rays, half = R / 2;
+            std::vector<int> times((size_t)R, 1);
+            bool pairs = false;
+            for (int k = 0; k < P.tasks_per_car; ++k) pairs = pairs || (P.group_order[k] >> 16) != 0 || (P.group_order[k] & 0xffff) % FTGP_WAVE != 0;
+            for (int k = 0; pairs && k < P.tasks_per_car; ++k) {
+                const int j0 = P.group_order[k] & 0xffff;
+                if ((P.group_order[k] >> 16) == 0 && j0 < half && j0 + FTGP_WAVE > half) for (int j = half; j < std::min(j0 + FTGP_WAVE, R); ++j) ++times[(size_t)j];
+            }
+            check_window_table(*pl, times, label);
+        }
         const DeviceAddrs a = made_up_addrs(*pl);
         Images im;
         layout_images(*pl, a, im);

@@ -131,7 +131,7 @@ int main(int argc, char** argv)
     if (getenv("HIST")) {          // iterations per ray, and per group of 64 consecutive rays (= the slowest ray of the group): lidar_groups
         std::vector<long> hr(64, 0), hg(64, 0); long sum_g = 0, ng = 0, sum_r = 0;
         std::vector<long> by_index(R, 0);
-        long alt_sum[4] = { 0, 0, 0, 0 }, nx_sum[5] = { 0, 0, 0, 0, 0 };
+        long alt_sum[4] = { 0, 0, 0, 0 }, nx_sum[5] = { 0, 0, 0, 0, 0 }, win_sum[2] = { 0, 0 }, win_groups[2] = { 0, 0 };
         for (int c = 0; c < n_cars; ++c) {
             const double* p = &pose[(size_t)c * 4];
             const double ch = 1.0 - 2.0 * (p[3] * p[3]), sh = 2.0 * (p[2] * p[3]);
@@ -165,6 +165,19 @@ int main(int argc, char** argv)
                 for (int k = 0; k < R; ++k) { m = std::max(m, cnt_of[idx[k]]); if ((k & 63) == 63 || k == R - 1) { sum += m; m = 0; } }
                 return sum;
             };
+            {   // the shipped task list (pairs of opposite groups, the short ends of both halves in one group) against the window-only list of
+                // a step whose ranges only the drivers read: ranges[0] and ranges[R/8 : R - R/8] (plan_window_tasks); a group costs its slowest ray
+                const int half = R / 2, e8 = R / 8;
+                auto live = [&](int j) { return j == 0 || (j >= e8 && j < R - e8); };
+                auto group = [&](int first, int n, bool window) { int m = 0; for (int j = first; j < first + n; ++j) if (!window || live(j)) m = std::max(m, cnt_of[j]); return m; };
+                for (int window = 0; window < 2; ++window)
+                    for (int j0 = 0; j0 < half; j0 += 64) {
+                        const int n = std::min(64, half - j0);
+                        const int a = group(j0, n, window), b = group(j0 + half, n, window);
+                        win_sum[window] += n <= 32 ? std::max(a, b) : a + b;
+                        win_groups[window] += n <= 32 ? (a || b) : (a > 0) + (b > 0);
+                    }
+            }
             alt_sum[0] += grouped([&](int j) { return (double)cnt_of[j]; });
             alt_sum[1] += grouped([&](int j) { return (double)range_of[j]; });
             alt_sum[2] += grouped([&](int j) { return floor((double)range_of[j] * 4.0); });
@@ -215,6 +228,8 @@ int main(int argc, char** argv)
         }
         printf("what-if, wave-iterations per car-step with groups of 64 after sorting a car's rays: by true count %.1f, by range %.1f, by range in 1/4-unit bins %.1f, in 1-unit bins %.1f\n",
                (double)alt_sum[0] / n_cars, (double)alt_sum[1] / n_cars, (double)alt_sum[2] / n_cars, (double)alt_sum[3] / n_cars);
+        printf("the shipped task list: %.1f wave-iterations in %.1f group-marches per car-step; window-only (ray 0 and rays n/8 .. n - n/8 - 1): %.1f in %.1f\n",
+               (double)win_sum[0] / n_cars, (double)win_groups[0] / n_cars, (double)win_sum[1] / n_cars, (double)win_groups[1] / n_cars);
         if (!pose_next.empty())
             printf("one step later: neighbours %.1f; sorted by the previous step's count %.1f, by that count clipped to 6: %.1f; pairs kept, sorted by the pair's larger count %.1f (neighbours in pairs %.1f)\n",
                    (double)nx_sum[0] / n_cars, (double)nx_sum[1] / n_cars, (double)nx_sum[2] / n_cars, (double)nx_sum[3] / n_cars, (double)nx_sum[4] / n_cars);
