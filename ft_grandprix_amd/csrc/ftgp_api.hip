@@ -17,6 +17,7 @@
 
 #include <hip/hip_ext.h>
 #include "ftgp_kernels.hip"
+#include "ftgp_window_cut.h"
 
 namespace {
 
@@ -479,14 +480,22 @@ void plan_fan(const FtgpConfig& cfg, std::vector<float>& ray, std::vector<double
     }
 }
 
-// the sweep's work list (lidar_groups): draw g -> (kidx = g / cars_per_block, car slot = g % cars_per_block), task = group_order[kidx]
-void plan_task_order(const FtgpConfig& cfg, const std::vector<float>& ray, const Switches& sw, DeviceParams& P)
+// a task may be a pair of opposite ray groups: the binary32 fan is point-symmetric to the bit (ray j + n/2 is the negated ray j), FTGP_NO_PAIRS unset
+bool fan_allows_pairs(const std::vector<float>& ray, int R, const Switches& sw)
 {
-    const int R = cfg.n_rays, halfR = R / 2;
+    const int halfR = R / 2;
     bool sym = R % 2 == 0 && !sw.no_pairs;
     for (int j = 0; sym && j < halfR; ++j)
         sym = ray[2 * (size_t)(j + halfR)] == -ray[2 * (size_t)j] && ray[2 * (size_t)(j + halfR) + 1] == -ray[2 * (size_t)j + 1] &&
               std::signbit(ray[2 * (size_t)(j + halfR)]) != std::signbit(ray[2 * (size_t)j]) && std::signbit(ray[2 * (size_t)(j + halfR) + 1]) != std::signbit(ray[2 * (size_t)j + 1]);
+    return sym;
+}
+
+// the sweep's work list (lidar_groups): draw g -> (kidx = g / cars_per_block, car slot = g % cars_per_block), task = group_order[kidx]
+void plan_task_order(const FtgpConfig& cfg, const std::vector<float>& ray, const Switches& sw, DeviceParams& P)
+{
+    const int R = cfg.n_rays, halfR = R / 2;
+    const bool sym = fan_allows_pairs(ray, R, sw);
     std::vector<int> tasks;
     if (!sym) for (int j0 = 0; j0 < R; j0 += FTGP_WAVE) tasks.push_back(j0);
     else {
@@ -551,52 +560,77 @@ int plan_task_table(const DeviceParams& P, std::vector<int32_t>& tt)
 // The window-only table (DeviceParams::task_tab's third; tt: the two tables of plan_task_table).  Inside a launch whose drivers read the scan, a range
 // of any step but the last has one reader, the next step's driver, and that reads ranges[0] and ranges[eighth : n - eighth]: every other ray of
 // such a step -- the rear quarter of the fan, where the rays look down the track and march longest -- is overwritten unread.  So those steps draw
-// from a list without them: the first table's tasks in its order (long first, the short singles of FTGP_PAIR_TAIL at the end), less the tasks that
-// hold no ray the drivers read; a pair of which one whole group is unread goes out as the other group alone (bit 26 where that is the second
-// one: its mate mask is the pair's second); a task that keeps unread rays says so (bit 25) and its lanes test their ray (lidar_groups).  Ray 0
-// stays lane 0 of its group.  The rank in [1] is still the group's in group_order: mate_masks() is what it was.  A fan without an unread ray
-// (n_rays < 8) gets the first table again.  FTGP_SCAN_EVERY_STEP: no such table, win_tasks_per_car = 0.
-void plan_window_table(const Switches& sw, const std::vector<int32_t>& tt, DeviceParams& P, std::vector<int32_t>& tw)
+// from a list of their own, cut from the live rays alone (ftgp_window_cut.h): pairs over the sideways zone, single groups over the forward cone,
+// and what is left of both, with ray 0, in GATHER tasks (kind 3) whose lanes take their rays from a few runs -- 13 full marches per car at 1080
+// rays where the first table's tasks, less their dead rays, took 15.  The list has its own order (win_group_order, the first table's key: |cos|
+// of the task's middle ray, for a gather the mean |cos| over its rays; FTGP_PAIR_TAIL splits its cheapest pairs) and its own ranks ([1]), so
+// mate_masks() is run on win_group_order for a step that draws from it.  Behind the draws, [gathers][4]: the runs of each gather task
+// (ftgp_device.h).  mmask_stride and group_order's size are the first table's, so the list never has more tasks than that: the tail's splits
+// give way first, and a list still longer (FTGP_PAIR_TAIL=0 at a few fan sizes) is dropped for the first table, as a fan without an unread
+// ray (n_rays < 8) gets it.  FTGP_SCAN_EVERY_STEP: no such table, win_tasks_per_car = 0.
+void plan_window_table(const Switches& sw, const std::vector<float>& ray, const std::vector<int32_t>& tt, DeviceParams& P, std::vector<int32_t>& tw)
 {
     const int cpb = P.cars_per_block, R = P.n_rays, halfR = R / 2;
     tw.clear();
     P.win_tasks_per_car = 0;
+    for (int k = 0; k < FTGP_MAX_GROUPS; ++k) P.win_group_order[k] = 0;
     if (sw.scan_every_step) {
         if (sw.verbose) fprintf(stderr, "ftgp_create: FTGP_SCAN_EVERY_STEP: every step of a launch sweeps and stores every ray\n");
         return;
     }
-    auto live = [&](int j) { return j == 0 || (j >= P.eighth && j < R - P.eighth); };
-    std::vector<std::pair<int, uint32_t>> list;      // (rank, [0] of car slot 0)
-    for (int k = 0; k < P.tasks_per_car; ++k) {
-        uint32_t x = (uint32_t)tt[4 * (size_t)k * cpb];
-        const int j0 = x & 0x3fff, kind = (x >> 14) & 3;
-        int n[2] = { 0, 0 }, l[2] = { 0, 0 };        // rays, and rays somebody reads, of the task's first / second group
-        for (int lane = 0; lane < FTGP_WAVE; ++lane) {
-            int j; bool mine;
-            if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? halfR : 0); mine = (lane & 31) < halfR - j0; }
-            else { j = j0 + lane; mine = j < (kind == 1 ? halfR : R); }
-            if (!mine) continue;
-            ++n[0]; l[0] += live(j) ? 1 : 0;
-            if (kind == 1) { ++n[1]; l[1] += live(j + halfR) ? 1 : 0; }
-        }
-        if (l[0] + l[1] == 0) continue;
-        if (kind == 1 && n[0] == FTGP_WAVE && (l[0] == 0 || l[1] == 0)) {      // (a pair of whole groups: either is a single group's 64 lanes)
-            if (l[0] == 0) { x = (uint32_t)(j0 + halfR) | ((x >> 22) & 3u) << 20 | 1u << 26; n[0] = n[1]; l[0] = l[1]; }
-            else x &= ~(3u << 14 | 3u << 22);
-            n[1] = l[1] = 0;
-        }
-        if (l[0] + l[1] < n[0] + n[1]) x |= 1u << 25;
-        list.push_back({ k, x });
+    const bool dead = P.eighth > 0;                  // some ray but ray 0 lies outside [eighth, R - eighth)
+    const FtgpWindowCut cut = ftgp_window_cut(R, P.eighth, fan_allows_pairs(ray, R, sw));
+    // longest first: |cos| of the angle between the car's axis and the task's middle ray; a gather: the mean over its rays
+    auto along = [&](double j) { return fabs(cos(2.0 * M_PI * j / (double)R)); };
+    struct Ent { double key; int ent, gather; };
+    std::vector<Ent> key;
+    for (int j0 : cut.pairs) key.push_back({ -along(j0 + 31.5), j0 | 1 << 16, -1 });
+    for (int j0 : cut.singles) key.push_back({ -along(j0 + 31.5), j0, -1 });
+    for (size_t q = 0; q < cut.gathers.size(); ++q) {
+        double sum = 0.0; int lanes = 0;
+        for (const FtgpWindowCut::Run& r : cut.gathers[q]) { for (int j = r.first; j < r.first + r.second; ++j) sum += along(j); lanes += r.second; }
+        key.push_back({ -sum / lanes, lanes | (int)q << 7 | 3 << 16, (int)q });
     }
-    P.win_tasks_per_car = (int)list.size();
+    if (sw.group_order_plain) for (Ent& k : key) k.key = 0.0;
+    std::stable_sort(key.begin(), key.end(), [](const Ent& a, const Ent& b) { return a.key < b.key; });
+    std::vector<int> order;
+    for (int tail = std::max(0, sw.pair_tail); ; --tail) {
+        order.clear();
+        for (size_t k = 0; k < key.size(); ++k) {
+            const int t = key[k].ent;
+            if ((t >> 16) == 1 && (int)(key.size() - k) <= tail) { order.push_back(t & 0xffff); order.push_back((t & 0xffff) + halfR); }
+            else order.push_back(t);
+        }
+        if ((int)order.size() <= P.tasks_per_car || tail == 0) break;
+    }
+    if (!dead || (int)order.size() > P.tasks_per_car || cut.gathers.size() > 127) {        // the first table again
+        P.win_tasks_per_car = P.tasks_per_car;
+        for (int k = 0; k < P.tasks_per_car; ++k) P.win_group_order[k] = P.group_order[k];
+        tw.assign(tt.begin(), tt.begin() + 4 * (size_t)cpb * P.tasks_per_car);
+        if (sw.verbose) fprintf(stderr, "ftgp_create: %d of them on the window-only steps of a launch\n", P.win_tasks_per_car);
+        return;
+    }
+    P.win_tasks_per_car = (int)order.size();
+    for (size_t k = 0; k < order.size(); ++k) P.win_group_order[k] = order[k];
     const int ntasks = cpb * P.win_tasks_per_car;
-    tw.assign(4 * (size_t)ntasks, 0);
+    tw.assign(4 * ((size_t)ntasks + cut.gathers.size()), 0);
     for (int g = 0; g < ntasks; ++g) {
-        const int c = g % cpb, kidx = list[(size_t)(g / cpb)].first;
-        const int32_t* a = &tt[4 * ((size_t)kidx * cpb + c)];
+        const int kidx = g / cpb, c = g % cpb, ent = order[(size_t)kidx], kind = ent >> 16;
+        const int32_t* a = &tt[4 * (size_t)c];           // the car slot's offsets: any draw of the first table has them
         int32_t* w = &tw[4 * (size_t)g];
-        w[0] = (int32_t)(list[(size_t)(g / cpb)].second | (uint32_t)c << 16);
-        w[1] = a[1]; w[2] = a[2]; w[3] = a[3];
+        bool zero = false;
+        if (kind == 3) for (const FtgpWindowCut::Run& r : cut.gathers[(size_t)((ent >> 7) & 127)]) zero = zero || r.first == 0;
+        // every ray of a pair or a single group lies in the window (class 1); a gather tests per ray (class 2: ray 0 goes to its own float)
+        w[0] = (int32_t)((uint32_t)(ent & 0x3fff) | (uint32_t)kind << 14 | (uint32_t)c << 16 | (kind == 3 ? 2u : 1u) << 20 | (kind == 1 ? 1u : 0u) << 22 | (zero ? 1u : 0u) << 24);
+        w[1] = (a[1] & 0xffff) | kidx << 16; w[2] = a[2]; w[3] = a[3];
+    }
+    for (size_t q = 0; q < cut.gathers.size(); ++q) {   // a gather's runs: (first ray - first lane) & 0xffff | first lane << 16; a run it does not have starts at lane 64
+        int32_t* w = &tw[4 * ((size_t)ntasks + q)];
+        int lane = 0;
+        for (size_t k = 0; k < 4; ++k) {
+            if (k < cut.gathers[q].size()) { w[k] = (int32_t)((uint32_t)((cut.gathers[q][k].first - lane) & 0xffff) | (uint32_t)lane << 16); lane += cut.gathers[q][k].second; }
+            else w[k] = (int32_t)(64u << 16);
+        }
     }
     if (sw.verbose) fprintf(stderr, "ftgp_create: %d of them on the window-only steps of a launch\n", P.win_tasks_per_car);
 }
@@ -736,7 +770,7 @@ int plan(const FtgpConfig& cfg, const FtgpTrack* tracks, const int32_t* envs_per
     plan_fan(cfg, pl.ray, pl.fan);
     plan_task_order(cfg, pl.ray, sw, P);
     if (int rc = plan_task_table(P, pl.tasks)) return rc;
-    plan_window_table(sw, pl.tasks, P, pl.tasks_win);
+    plan_window_table(sw, pl.ray, pl.tasks, P, pl.tasks_win);
     {   // cover-count thresholds: nidc (car_width 0.12, nidc.py:5) then fast (0.06, fast.py:4), each padded to the staged size
         const size_t stride = (size_t)P.cover_kmax + 1, padded = (size_t)pad16(sizeof(float) * stride) / sizeof(float);
         pl.cover.assign(stride + padded + 4, 0.0f);

@@ -126,6 +126,8 @@ struct DeviceParams {
                                   // track, sideways rays hit the corridor wall at once): first ray | kind << 16, kind 0 = one group of 64
                                   // consecutive rays, 1 = that group and the opposite one (first ray + n/2), 2 = the short ends of both halves in
                                   // one group (lanes 0..31 / 32..63); read with scalar loads
+    int32_t win_group_order[FTGP_MAX_GROUPS];  // right behind it, the window-only list's tasks in its order (plan_window_table), as group_order holds the first
+                                  // table's; kind 3, a gather: lanes | gather number << 7 in the low half (mate_masks looks at every mate for it, as for kind 2)
     const int32_t* task_tab;      // [2][cars_per_block * tasks_per_car][4] the sweep's draws, one 16-byte scalar load each (lidar_groups; behind this block in device memory):
                                   //   [0] first ray (14 bits) | kind << 14 | car slot << 16 | window class of the first / second group << 20 / 22 | (the first group holds ray 0) << 24
                                   //       (window class: 0 = no ray of the group lies in the drivers' scan window, 1 = every ray does, 2 = test per ray)
@@ -134,11 +136,17 @@ struct DeviceParams {
                                   //   [3] byte offset, in a scan buffer, at which sample j of the car sits when 4 j is added: row + ((eighth & 3) - eighth) floats
                                   // the second table is for launches whose drivers do not read the scan: window classes 0, no ray 0
                                   // Behind the two, [cars_per_block * win_tasks_per_car][4]: the window-only table, for every step but the last of a launch whose
-                                  // drivers read the scan -- only the groups that hold a ray the drivers read (ranges[0], ranges[eighth : n - eighth]), in the first
-                                  // table's order and with its fields ([1]: the rank is still the group's in group_order), and in [0]
-                                  //   bit 25: some ray of the task is read by nobody before the next step overwrites it -- such a lane holds no ray
-                                  //   bit 26: a single group that is the opposite group of pair `rank`: its mate mask is the pair's second (mate_masks)
+                                  // drivers read the scan -- the rays the drivers read (ranges[0], ranges[eighth : n - eighth]) and no other, in a cut and an
+                                  // order of their own (plan_window_table, win_group_order): pairs and single groups of 64 live rays each, first ray anywhere,
+                                  // window class 1, and
+                                  //   kind 3, a GATHER: [0]'s first-ray field holds lanes (7 bits) | gather number << 7; lane l < lanes marches ray l + d of the
+                                  //   run it lies in, window class 2 (a test per ray), the ray-0 flag where a run is ray 0.  The rank in [1] is the task's in
+                                  //   win_group_order; [2], [3] as in the first table.
+                                  // Behind those draws, [gathers][4]: the runs of each gather task, in lane order, one word each: (first ray - first lane) & 0xffff |
+                                  // first lane << 16; a run the task does not have starts at lane 64.  The same for every car slot.
 };
+
+static_assert(offsetof(DeviceParams, win_group_order) == offsetof(DeviceParams, group_order) + sizeof(int32_t) * FTGP_MAX_GROUPS, "win_group_order lies right behind group_order (dynamics_lanes)");
 
 // Bytes of one parameter block in device memory.  Multi-track handles (ftgp_create_tracks): the workgroup table follows track 0's block,
 // int4 per workgroup = (byte offset of its track's block from track 0's, first car, number of cars, track).

@@ -379,6 +379,23 @@ __device__ __forceinline__ void march_all(float& s, uint32_t& w, float pu, float
 #undef FTGP_MARCH_FIX
 }
 
+// A GATHER task of the window-only table (kind 3, plan_window_table): what a car's whole pairs and single groups leave over -- ray 0, the ends
+// of the sideways zone and of the forward cone -- marched together.  Its lanes hold a few runs of consecutive rays; the runs of gather q come
+// as ONE 16-byte scalar load from behind the table's draws (`gathers`), a word each: (first ray - first lane) & 0xffff | first lane << 16, a
+// run the task does not have starting at lane 64.  field: the draw's first-ray field, lanes | q << 7.  Shared by lidar_groups and lidar_fake.
+template <class ScalarTasksT>
+__device__ __forceinline__ void gather_lanes(ScalarTasksT gathers, int field, int lane, int& j, bool& mine)
+{
+    const uint32_t q = (uint32_t)field >> 7;
+    const int r0 = gathers[q].x, r1 = gathers[q].y, r2 = gathers[q].z, r3 = gathers[q].w;
+    int d = (int16_t)r0;
+    if (lane >= (r1 >> 16)) d = (int16_t)r1;
+    if (lane >= (r2 >> 16)) d = (int16_t)r2;
+    if (lane >= (r3 >> 16)) d = (int16_t)r3;
+    j = lane + d;
+    mine = lane < (field & 127);
+}
+
 // The sweep of one step for all cars of the workgroup, by every wave, in GROUPS of 64 consecutive rays of one car: a wave draws the
 // next task (one LDS atomic), sets its 64 rays up, marches them until all have finished (march_all), stores the 64 ranges, and draws
 // again.  Nothing is handed out ray by ray: no ranks, no per-lane bookkeeping, no partial refills -- the price is that a group
@@ -433,15 +450,10 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
         Task task; { const uint32_t gu = (uint32_t)g; task.x = tasks[gu].x; task.y = tasks[gu].y; task.z = tasks[gu].z; task.w = tasks[gu].w; }
         const int j0 = task.x & 0x3fff, kind = (task.x >> 14) & 3, c = (task.x >> 16) & 15;     // kind 0: one group; 1: a group and its opposite; 2: both halves in one group
         int j; bool mine;
-        if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? half : 0); mine = (lane & 31) < half - j0; }
+        if (WINDOW && kind == 3) { asm volatile(""); gather_lanes(tasks + ntasks, j0, lane, j, mine); }      // window-only table: a gather, lanes from runs
+        else if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? half : 0); mine = (lane & 31) < half - j0; }
         else { j = j0 + lane; mine = j < (kind == 1 ? half : R); }
         mine = mine && c < ncars_here;               // (a ragged last workgroup draws tasks of cars it does not have)
-        bool first = mine;                           // the lanes that march a ray of the first group
-        if (WINDOW && (task.x & (1 << 25))) {        // window-only table: some ray of the task has no reader, and its lane holds no ray.  (A pair's set-up
-            asm volatile("");                        // runs on the lanes of either group: the second group's rays are the first one's turned round.)
-            first = mine && (j == 0 || (unsigned)(j - eighth) < (unsigned)(R - 2 * eighth));
-            mine = first || (kind == 1 && mine && (unsigned)(j + half - eighth) < (unsigned)(R - 2 * eighth));
-        }
         const LidarFrame* frame = reinterpret_cast<const LidarFrame*>(reinterpret_cast<const unsigned char*>(frames) + (task.y & 0xffff));
         FtgpRay ray;
         float du, dv, dxw, dyw, opu, opv;              // opu, opv: the ray's origin in pixels
@@ -461,9 +473,9 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
                 const PairCull* mates = pairs + c * FTGP_PAIR_STRIDE;
                 const int slot0 = sgpr(frame->slot0);
                 // ... and one byte per (car, group) says which mates the group's rays can see at all (mate_masks): mostly none
-                // (window-only table, bit 26: a single group that is the second group of pair kidx)
+                // (kidx: the task's rank in the list this sweep draws from -- the masks were computed for that list)
                 const int kidx = task.y >> 16;
-                uint32_t mm = (uint32_t)sgpr((int)mmask[c * mmask_stride + 2 * kidx + pass + (WINDOW ? (task.x >> 26) & 1 : 0)]);
+                uint32_t mm = (uint32_t)sgpr((int)mmask[c * mmask_stride + 2 * kidx + pass]);
                 while (mm) {
                     const int k = __builtin_ctz(mm); mm &= mm - 1u;
                     const float4 q = *reinterpret_cast<const float4*>(mates + k);
@@ -519,9 +531,8 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
             }
         }
         STAMP(td); STAMP_ADD(8, td - ta);
-        finish(first, 0);
+        finish(mine, 0);
         if (kind == 1) {                 // the same rays turned round: ray j + n/2 = -(ray j), exactly
-            if (WINDOW && (task.x & (1 << 25))) { asm volatile(""); mine = mine && (unsigned)(j + half - eighth) < (unsigned)(R - 2 * eighth); }
             if (mine) {
                 j += half;
                 const float2 f2 = *reinterpret_cast<const float2*>(frame);
@@ -637,12 +648,13 @@ __device__ __forceinline__ void lidar_fake(ScalarParams G, const LidarFrame* fra
         Task task; { const uint32_t gu = (uint32_t)g; task.x = tasks[gu].x; task.y = tasks[gu].y; task.z = tasks[gu].z; task.w = tasks[gu].w; }
         const int j0 = task.x & 0x3fff, kind = (task.x >> 14) & 3, c = (task.x >> 16) & 15;
         int j; bool mine;
-        if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? half : 0); mine = (lane & 31) < half - j0; }
+        if (kind == 3) gather_lanes(tasks + ntasks, j0, lane, j, mine);      // (the window-only table alone has gathers)
+        else if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? half : 0); mine = (lane & 31) < half - j0; }
         else { j = j0 + lane; mine = j < (kind == 1 ? half : R); }
         mine = mine && c < ncars_here;
         const LidarFrame* f = reinterpret_cast<const LidarFrame*>(reinterpret_cast<const unsigned char*>(frames) + (task.y & 0xffff));
         for (int pass = 0; pass < (kind == 1 ? 2 : 1); ++pass, j += half) {
-            if (!mine || ((task.x & (1 << 25)) && j != 0 && (unsigned)(j - eighth) >= (unsigned)(R - 2 * eighth))) continue;
+            if (!mine) continue;
             float r = 0.0f;                                       // a finished car's rangefinders are switched off (custom.py:1436-1439): its scan reads 0
             if (!f->finished) {
                 const double ch = f->x, sh = f->y;                // FAKELIDAR frames: heading (cos, sin) in binary64 (frame_write)
@@ -960,7 +972,7 @@ __device__ __forceinline__ void mate_masks(const LidarFrame* frames, const PairC
         const int c = idx / slots, s = idx - c * slots;
         const int ent = order[s >> 1], j0 = ent & 0xffff, kind = ent >> 16;
         uint32_t m = 0;
-        if (kind == 2 || cg < -1.0f) m = (s & 1) ? 0u : 0xffu;                // both half-fans in one group, or a fan the bound does not cover: look at every mate
+        if (kind >= 2 || cg < -1.0f) m = (s & 1) ? 0u : 0xffu;                // both half-fans in one group, a gather (kind 3), or a fan the bound does not cover: look at every mate
         else if (!(s & 1) || kind == 1) {
             const int jc = min(j0 + 32, (kind == 1 ? (R >> 1) : R) - 1);
             const float2 bd = ray_tab[jc];
@@ -999,7 +1011,7 @@ __device__ __forceinline__ void quad_argmin_step(double& best, int& idx)
 // DYN: the table of per-car dynamics is on (ftgp_set_dynamics): the eight entries of the car's row and its wheel loads come from the car's
 // own record in LDS (`dyn`, FTGP_DYN_RECORD doubles per car slot: the car's four lanes read one address), everything else from L.veh as ever.
 template <bool MULTI, bool DYN>
-__device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds& L, LidarFrame* next_frames, PairCull* next_pairs, unsigned char* next_mmask, ScalarInts order,
+__device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds& L, LidarFrame* next_frames, PairCull* next_pairs, unsigned char* next_mmask, ScalarInts order, bool win_next,
                                                int* unsafe_next, int ncars_here, int ci0, const double* dyn)
 {
     const int lane = lane_here();
@@ -1216,7 +1228,8 @@ __device__ __forceinline__ void dynamics_lanes(const DeviceParams& P, const Lds&
             pair_cull_write(next_frames, next_pairs, c, r + 4, P.cars_per_env, cull, r0f);
         }
         wave_lds_sync();
-        mate_masks(next_frames, next_pairs, next_mmask, P.mmask_stride, order, L.ray, P.n_rays, P.tasks_per_car, P.cars_per_env, cull, P.group_cg, P.group_sg, ncars_here, lane, FTGP_WAVE);
+        // (win_next: the next step's sweep draws from the window-only list -- its order lies right behind group_order)
+        mate_masks(next_frames, next_pairs, next_mmask, P.mmask_stride, win_next ? order + FTGP_MAX_GROUPS : order, L.ray, P.n_rays, win_next ? P.win_tasks_per_car : P.tasks_per_car, P.cars_per_env, cull, P.group_cg, P.group_sg, ncars_here, lane, FTGP_WAVE);
     }
 }
 
@@ -2027,9 +2040,11 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
         for (int idx = (int)threadIdx.x; idx < ncars_here * FTGP_PAIR_STRIDE; idx += (int)blockDim.x)
             pair_cull_write(L.frame, L.pairs, idx / FTGP_PAIR_STRIDE, idx % FTGP_PAIR_STRIDE, P.cars_per_env, L.veh->cull_radius, (float)L.veh->v.lidar_ring_radius);
         __syncthreads();
-        if (wave == 0)
-            mate_masks(L.frame, L.pairs, L.mmask, P.mmask_stride, &scalar_view(Pt)->group_order[0], L.ray, P.n_rays, P.tasks_per_car, P.cars_per_env, L.veh->cull_radius, P.group_cg, P.group_sg,
-                       ncars_here, lane_here(), FTGP_WAVE);
+        if (wave == 0) {                 // for the list step 0's sweep draws from: the window-only one unless that step is the launch's last (see the step loop)
+            const bool win0 = need_scan && n_steps != 1 && P.win_tasks_per_car != 0;
+            mate_masks(L.frame, L.pairs, L.mmask, P.mmask_stride, win0 ? &scalar_view(Pt)->win_group_order[0] : &scalar_view(Pt)->group_order[0], L.ray, P.n_rays,
+                       win0 ? P.win_tasks_per_car : P.tasks_per_car, P.cars_per_env, L.veh->cull_radius, P.group_cg, P.group_sg, ncars_here, lane_here(), FTGP_WAVE);
+        }
     }
     }
     __syncthreads();
@@ -2084,8 +2099,10 @@ __global__ void __launch_bounds__(1024, FTGP_WAVES_PER_EU) ftgp_step_kernel(cons
                 STAMP(t1); STAMP_ADD(0, t1 - t0);
                 if (n == ncars_here - 1) {            // every driver of the workgroup has delivered its controls
                     if (lane_here() == 0) { L.pool[par ^ 1] = 0; L.pool[2 + (par ^ 1)] = 0; }     // the next step's counters (idle during this step)
+                    // (the masks of the next step's frames: for the list its sweep draws from, see window_only below)
+                    const bool win_next = need_scan && it + 1 != n_steps - 1 && G->win_tasks_per_car != 0;
                     if (FTGP_DIAG_RUN_K1)
-                        dynamics_lanes<MULTI, DYN>(P, L, next_frames, L.pairs + (par ^ 1) * cpb * FTGP_PAIR_STRIDE, L.mmask + (par ^ 1) * cpb * G->mmask_stride, &G->group_order[0],
+                        dynamics_lanes<MULTI, DYN>(P, L, next_frames, L.pairs + (par ^ 1) * cpb * FTGP_PAIR_STRIDE, L.mmask + (par ^ 1) * cpb * G->mmask_stride, &G->group_order[0], win_next,
                                                    L.pool + 4 + (par ^ 1), ncars_here, ci0, DYN ? reinterpret_cast<const double*>(lds + opaque(G->lds_bytes)) : nullptr);
                     STAMP(t2); STAMP_ADD(2, t2 - t1); STAMP_ADD(7, 1);
                 }

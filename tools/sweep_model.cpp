@@ -13,6 +13,7 @@
 #include <vector>
 #include "../include/ftgp.h"
 #include "../ft_grandprix_amd/csrc/ftgp_march.h"
+#include "../ft_grandprix_amd/csrc/ftgp_window_cut.h"
 
 struct Tables { std::vector<uint8_t> wall; std::vector<uint16_t> runx, runy; };
 static void build(const std::vector<uint32_t>& bits, int W, int H, int wpr, Tables& g)
@@ -132,6 +133,7 @@ int main(int argc, char** argv)
         std::vector<long> hr(64, 0), hg(64, 0); long sum_g = 0, ng = 0, sum_r = 0;
         std::vector<long> by_index(R, 0);
         long alt_sum[4] = { 0, 0, 0, 0 }, nx_sum[5] = { 0, 0, 0, 0, 0 }, win_sum[2] = { 0, 0 }, win_groups[2] = { 0, 0 };
+        long cut_sum[4] = { 0, 0, 0, 0 }, cut_groups[4] = { 0, 0, 0, 0 }, cut_gather = 0;      // the window-only steps' own cut (ftgp_window_cut.h), rests at low/low (shipped), low/high, high/low, high/high
         for (int c = 0; c < n_cars; ++c) {
             const double* p = &pose[(size_t)c * 4];
             const double ch = 1.0 - 2.0 * (p[3] * p[3]), sh = 2.0 * (p[2] * p[3]);
@@ -177,6 +179,13 @@ int main(int argc, char** argv)
                         win_sum[window] += n <= 32 ? std::max(a, b) : a + b;
                         win_groups[window] += n <= 32 ? (a || b) : (a > 0) + (b > 0);
                     }
+            }
+            for (int v = 0; v < 4; ++v) {     // the list plan_window_table makes (v = 0) and its what-ifs: a march costs its slowest ray, whatever group carries it
+                const FtgpWindowCut cut = ftgp_window_cut(R, R / 8, R % 2 == 0, (v & 2) == 0, (v & 1) == 0);
+                auto span = [&](int first, int n) { int m = 0; for (int j = first; j < first + n; ++j) m = std::max(m, cnt_of[j]); return m; };
+                for (int j0 : cut.pairs) { cut_sum[v] += span(j0, 64) + span(j0 + R / 2, 64); cut_groups[v] += 2; }
+                for (int j0 : cut.singles) { cut_sum[v] += span(j0, 64); ++cut_groups[v]; }
+                for (const auto& runs : cut.gathers) { int m = 0; for (const auto& r : runs) m = std::max(m, span(r.first, r.second)); cut_sum[v] += m; ++cut_groups[v]; if (v == 0) cut_gather += m; }
             }
             alt_sum[0] += grouped([&](int j) { return (double)cnt_of[j]; });
             alt_sum[1] += grouped([&](int j) { return (double)range_of[j]; });
@@ -230,6 +239,9 @@ int main(int argc, char** argv)
                (double)alt_sum[0] / n_cars, (double)alt_sum[1] / n_cars, (double)alt_sum[2] / n_cars, (double)alt_sum[3] / n_cars);
         printf("the shipped task list: %.1f wave-iterations in %.1f group-marches per car-step; window-only (ray 0 and rays n/8 .. n - n/8 - 1): %.1f in %.1f\n",
                (double)win_sum[0] / n_cars, (double)win_groups[0] / n_cars, (double)win_sum[1] / n_cars, (double)win_groups[1] / n_cars);
+        printf("the window-only steps' own cut (pairs over the sideways zone, single groups over the forward cone, the rest and ray 0 in gathers): %.1f wave-iterations in %.1f group-marches "
+               "(the gathers: %.1f); rests at the zones' other ends: low / high %.1f, high / low %.1f, high / high %.1f\n",
+               (double)cut_sum[0] / n_cars, (double)cut_groups[0] / n_cars, (double)cut_gather / n_cars, (double)cut_sum[1] / n_cars, (double)cut_sum[2] / n_cars, (double)cut_sum[3] / n_cars);
         if (!pose_next.empty())
             printf("one step later: neighbours %.1f; sorted by the previous step's count %.1f, by that count clipped to 6: %.1f; pairs kept, sorted by the pair's larger count %.1f (neighbours in pairs %.1f)\n",
                    (double)nx_sum[0] / n_cars, (double)nx_sum[1] / n_cars, (double)nx_sum[2] / n_cars, (double)nx_sum[3] / n_cars, (double)nx_sum[4] / n_cars);
