@@ -607,6 +607,7 @@ void plan_window_table(const Switches& sw, const std::vector<float>& ray, const 
         P.win_tasks_per_car = P.tasks_per_car;
         for (int k = 0; k < P.tasks_per_car; ++k) P.win_group_order[k] = P.group_order[k];
         tw.assign(tt.begin(), tt.begin() + 4 * (size_t)cpb * P.tasks_per_car);
+        for (size_t g = 0; g < (size_t)cpb * P.tasks_per_car; ++g) tw[4 * g] |= FTGP_TASK_MASKED;      // partial groups, every window class: no plain draw
         if (sw.verbose) fprintf(stderr, "ftgp_create: %d of them on the window-only steps of a launch\n", P.win_tasks_per_car);
         return;
     }
@@ -620,8 +621,10 @@ void plan_window_table(const Switches& sw, const std::vector<float>& ray, const 
         int32_t* w = &tw[4 * (size_t)g];
         bool zero = false;
         if (kind == 3) for (const FtgpWindowCut::Run& r : cut.gathers[(size_t)((ent >> 7) & 127)]) zero = zero || r.first == 0;
-        // every ray of a pair or a single group lies in the window (class 1); a gather tests per ray (class 2: ray 0 goes to its own float)
-        w[0] = (int32_t)((uint32_t)(ent & 0x3fff) | (uint32_t)kind << 14 | (uint32_t)c << 16 | (kind == 3 ? 2u : 1u) << 20 | (kind == 1 ? 1u : 0u) << 22 | (zero ? 1u : 0u) << 24);
+        // every ray of a pair or a single group lies in the window (class 1); a gather tests per ray (class 2: ray 0 goes to its own float).
+        // A pair or a single group is a PLAIN draw -- 64 live rays a group, no ray 0 (ftgp_window_cut.h) --, a gather is not (FTGP_TASK_MASKED).
+        w[0] = (int32_t)((uint32_t)(ent & 0x3fff) | (uint32_t)kind << 14 | (uint32_t)c << 16 | (kind == 3 ? 2u : 1u) << 20 | (kind == 1 ? 1u : 0u) << 22 | (zero ? 1u : 0u) << 24 |
+                           (kind == 3 ? (uint32_t)FTGP_TASK_MASKED : 0u));
         w[1] = (a[1] & 0xffff) | kidx << 16; w[2] = a[2]; w[3] = a[3];
     }
     for (size_t q = 0; q < cut.gathers.size(); ++q) {   // a gather's runs: (first ray - first lane) & 0xffff | first lane << 16; a run it does not have starts at lane 64

@@ -12,6 +12,7 @@
 
 #define FTGP_WAVE 64
 #define FTGP_MAX_GROUPS 256              // groups of 64 rays per car: n_rays <= 16384
+#define FTGP_TASK_MASKED (1 << 25)       // window-only table, word [0] of a draw: not a plain draw (DeviceParams::task_tab)
 #define FTGP_MAX_CARS_PER_BLOCK 16      // K1 / K3 run one car per lane group of a single wave: 16 cars x 4 lanes
 
 // Per-car state, array-of-structs in HBM.  The step kernel keeps CarCore in LDS for the whole launch.
@@ -142,6 +143,9 @@ struct DeviceParams {
                                   //   kind 3, a GATHER: [0]'s first-ray field holds lanes (7 bits) | gather number << 7; lane l < lanes marches ray l + d of the
                                   //   run it lies in, window class 2 (a test per ray), the ray-0 flag where a run is ray 0.  The rank in [1] is the task's in
                                   //   win_group_order; [2], [3] as in the first table.
+                                  //   FTGP_TASK_MASKED in [0]: the draw is not a plain one.  A PLAIN draw -- kind 0 or 1, 64 live rays per group, every group
+                                  //   wholly inside the window, no ray 0 -- runs through the window-only sweep without a lane mask and without a delivery test
+                                  //   (lidar_groups): the bit is set on every gather, and on every entry where this table is the first table again.
                                   // Behind those draws, [gathers][4]: the runs of each gather task, in lane order, one word each: (first ray - first lane) & 0xffff |
                                   // first lane << 16; a run the task does not have starts at lane 64.  The same for every car slot.
 };

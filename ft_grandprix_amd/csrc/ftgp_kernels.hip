@@ -155,8 +155,9 @@ __device__ __forceinline__ void rcp_abs2(float x, float y, float& rx, float& ry)
     float p = __builtin_amdgcn_rcpf(ax), q = __builtin_amdgcn_rcpf(ay);
     const float ep = fmaf(-ax, p, 1.0f), eq = fmaf(-ay, q, 1.0f);
     p = fmaf(p, ep, p); q = fmaf(q, eq, q);
-    const uint32_t lo1 = 0x0D800001u, span = 0x71800000u - 0x0D800001u;             // bit patterns of 2^-100 (+ 1) and 2^100
-    if (__any(((__float_as_uint(ax) - lo1) | (__float_as_uint(ay) - lo1)) >= span)) {
+    // (the patterns doubled: the shift drops the sign, so dropping it and subtracting is one shift-add per operand, not an AND and an add)
+    const uint32_t lo1 = 2u * 0x0D800001u, span = 2u * (0x71800000u - 0x0D800001u);             // bit patterns of 2^-100 (+ 1) and 2^100, twice
+    if (__any((((__float_as_uint(x) << 1) - lo1) | ((__float_as_uint(y) << 1) - lo1)) >= span)) {
         const bool oddx = !(ax > 0x1p-100f && ax < 0x1p100f), oddy = !(ay > 0x1p-100f && ay < 0x1p100f);      // also true for a NaN
         float zx = fabsf(1.0f / x), zy = fabsf(1.0f / y);
         if (CLAMP) { zx = zx < FTGP_IV_MAX ? zx : FTGP_IV_MAX; zy = zy < FTGP_IV_MAX ? zy : FTGP_IV_MAX; }
@@ -416,7 +417,8 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
     typedef const __attribute__((address_space(4))) Task* ScalarTasks;
     // WINDOW (implies scan_lds): a step whose ranges only the next step's drivers read -- every step of such a launch but its last.  The
     // draws come from the third table (plan_window_table): the rays outside the drivers' window are not marched, and no range goes to HBM --
-    // the launch's last step writes every row.  An instantiation of its own: with WINDOW = false the code is exactly what it was.
+    // the launch's last step writes every row.  An instantiation of its own, with a shell of its own for the table's plain draws (run_task below);
+    // with WINDOW = false there is the masked body alone, the full sweep as it was.
     constexpr bool window_only = WINDOW;
     const int full_tasks = G->cars_per_block * G->tasks_per_car;
     const int R = G->n_rays, half = R >> 1, ntasks = window_only ? G->cars_per_block * G->win_tasks_per_car : full_tasks;
@@ -430,7 +432,10 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
     const global_u8w ranges = (global_u8w)((global_f32)G->ranges + (size_t)ci0 * G->ranges_stride);      // the workgroup's first row
     const int mmask_stride = G->mmask_stride;
     const int lane = lane_here();
-    const bool all_safe = sgpr(pool[4]) == 0;        // every ray of this sweep starts on the image (frame_write): no test per ray
+    // every ray of this sweep starts on the image (frame_write): no test per ray.  (The window-only sweep tests the word itself, behind opaque() at
+    // each use: a bool hoisted out of the loop is kept as a lane mask and rebuilt with two vector instructions per set-up.)
+    const int unsafe = sgpr(pool[4]);
+    const bool all_safe = unsafe == 0;
     sweep_priority(second_half);
     for (;;) {                   // (ends: every draw moves the counter on)
         STAMP(ta);
@@ -446,14 +451,27 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
         // other.  Everything about the draw that ftgp_create can know -- first ray, kind, car slot, where the car's LiDAR frame, its row of
         // ranges and its scan window start, whether the group's rays lie in the drivers' window -- comes as ONE 16-byte scalar load
         // (ftgp_task_entry; round 5: a division by multiplication, a table read and three 32- and 64-bit address products per group used to
-        // stand here and in the delivery: a third of the kernel's scalar instructions).
-        Task task; { const uint32_t gu = (uint32_t)g; task.x = tasks[gu].x; task.y = tasks[gu].y; task.z = tasks[gu].z; task.w = tasks[gu].w; }
+        // stand here and in the delivery: a third of the kernel's scalar instructions).  The byte offset is formed in 32 bits -- a table is far
+        // below 4 GB --, so it goes into the scalar load as it is: no 64-bit shift and add; and the four words are read as one vector, so that
+        // they stay one load (field by field the compiler splits them and forms the address a second time).
+        typedef int32_t TaskWords __attribute__((ext_vector_type(4)));
+        Task task; { const TaskWords t = *(const __attribute__((address_space(4))) TaskWords*)((const __attribute__((address_space(4))) unsigned char*)tasks + ((uint32_t)g << 4)); task.x = t.x; task.y = t.y; task.z = t.z; task.w = t.w; }
         const int j0 = task.x & 0x3fff, kind = (task.x >> 14) & 3, c = (task.x >> 16) & 15;     // kind 0: one group; 1: a group and its opposite; 2: both halves in one group
-        int j; bool mine;
-        if (WINDOW && kind == 3) { asm volatile(""); gather_lanes(tasks + ntasks, j0, lane, j, mine); }      // window-only table: a gather, lanes from runs
-        else if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? half : 0); mine = (lane & 31) < half - j0; }
-        else { j = j0 + lane; mine = j < (kind == 1 ? half : R); }
-        mine = mine && c < ncars_here;               // (a ragged last workgroup draws tasks of cars it does not have)
+        if (WINDOW && c >= ncars_here) continue;     // (a ragged last workgroup draws tasks of cars it does not have; the counter has moved)
+        // The lanes of a draw that may be short of rays (every draw of the first two tables; of the window-only table the gathers, and all of it
+        // where it is the first table again): which ray a lane marches, and whether it has one.
+        auto masked_lanes = [&](int& j, bool& mine) __attribute__((always_inline)) {
+            if (WINDOW && kind == 3) { asm volatile(""); gather_lanes(tasks + ntasks, j0, lane, j, mine); }      // window-only table: a gather, lanes from runs
+            else if (kind == 2) { j = j0 + (lane & 31) + (lane >= 32 ? half : 0); mine = (lane & 31) < half - j0; }
+            else { j = j0 + lane; mine = j < (kind == 1 ? half : R); }
+            if (!WINDOW) mine = mine && c < ncars_here;               // (a ragged last workgroup draws tasks of cars it does not have)
+        };
+        // One task: set-up, march and delivery of its group, and of the opposite group where it has one.  MASKED = false: a PLAIN draw of the
+        // window-only table (FTGP_TASK_MASKED clear: kind 0 or 1, 64 live rays a group, all of them in the drivers' window, no ray 0) -- lane l
+        // marches ray j0 + l, there is no lane predicate and no exec region but march_all's own, and the delivery is one LDS store.
+        auto run_task = [&](auto masked_tag, int j, bool lanes) __attribute__((always_inline)) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        const bool mine = MASKED ? lanes : true;
         const LidarFrame* frame = reinterpret_cast<const LidarFrame*>(reinterpret_cast<const unsigned char*>(frames) + (task.y & 0xffff));
         FtgpRay ray;
         float du, dv, dxw, dyw, opu, opv;              // opu, opv: the ray's origin in pixels
@@ -492,6 +510,7 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
             // read next step -- ranges[0] and ranges[eighth : n - eighth] -- is kept in LDS as well.  (Not on a window-only step: nobody reads
             // its rows before the launch's last step has written them again.)
             const uint32_t j4 = (uint32_t)j << 2;
+            if (!MASKED) { *reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(scan_rows) + task.w + j4) = r; return; }      // (window class 1, no ray 0: see task.w below)
             if (!window_only) *(global_f32)(ranges + (j4 + (uint32_t)task.z)) = r;
             // task.w: byte offset of the car's scan row + ((eighth & 3) - eighth) floats, so that sample j sits at task.w + 4 j.  Whether the
             // group's rays lie inside the window, outside it or across one of its ends is the task's to know (two bits per pass; all zero in
@@ -523,7 +542,7 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
             ray.result = -1.0f;
             sector = ftgp_ray_sector(du, dv, ivx, ivy, nsf);
             ftgp_ray_place(ray, pu, pv, du, dv, ivx, ivy, sector, W, H, fstride, plane256, true, &P.sector_tab[0][0]);
-            if (!all_safe) {             // wave-uniform, rare: some car of the workgroup is near the image edge, off it, or has finished
+            if (WINDOW ? opaque(unsafe) != 0 : !all_safe) {             // wave-uniform, rare: some car of the workgroup is near the image edge, off it, or has finished
                 ftgp_ray_park_if_outside(ray, pu, pv, W, H);
                 // a finished car's rangefinders are switched off (custom.py:1436-1439): its frame carries u0 = -inf, so the ray is
                 // parked like any ray that starts off the image, and reads 0 instead of -1
@@ -532,7 +551,7 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
         }
         STAMP(td); STAMP_ADD(8, td - ta);
         finish(mine, 0);
-        if (kind == 1) {                 // the same rays turned round: ray j + n/2 = -(ray j), exactly
+        if (MASKED ? kind == 1 : (task.x & (1 << 14)) != 0) {                 // the same rays turned round: ray j + n/2 = -(ray j), exactly  (a plain draw is of kind 0 or 1)
             if (mine) {
                 j += half;
                 const float2 f2 = *reinterpret_cast<const float2*>(frame);
@@ -541,12 +560,20 @@ __device__ __forceinline__ void lidar_groups(const DeviceParams& P, ScalarParams
                 const float pv = fmaf(dv, -r0, f2.y);
                 opu = pu; opv = pv;
                 ftgp_ray_place(ray, pu, pv, du, dv, ray.ivx, ray.ivy, sector ^ 3u, W, H, fstride, plane256, true, &P.sector_tab[0][0]);
-                if (!all_safe) {
+                if (WINDOW ? opaque(unsafe) != 0 : !all_safe) {
                     ftgp_ray_park_if_outside(ray, pu, pv, W, H);
                     ray.result = (f2.x == -INFINITY) ? 0.0f : -1.0f;
                 }
             }
             finish(mine, 1);
+        }
+        };
+        if (WINDOW && !(task.x & FTGP_TASK_MASKED)) run_task(std::false_type(), j0 + lane, true);
+        else {
+            if (WINDOW) asm volatile("");        // (a scalar branch, not selects)
+            int j; bool mine;
+            masked_lanes(j, mine);
+            run_task(std::true_type(), j, mine);
         }
     }
 }

@@ -3,7 +3,9 @@
 // delivered ray's window class is right (1 only where every ray of the group lies in the window, else 2); a pair or a single group is whole --
 // 64 lanes, every one a live ray, a pair's on both sides; a gather's 64 entries (its runs expanded as gather_lanes does it) are rays below n or
 // the sentinel 0xffff, the lanes in use first; ranks ascend, every car slot of a rank together, and a draw is the task win_group_order names
-// at its rank; the list has no more tasks than the first table.  A fan without an unread ray has the first table again (and its order);
+// at its rank; the list has no more tasks than the first table.  FTGP_TASK_MASKED is clear exactly on the pairs and single groups -- the PLAIN draws,
+// which lidar_groups runs without a lane mask and delivers with one store: kind 0 or 1, never kind 2, 64 live rays a group, window class 1, no
+// ray 0 -- and set on every gather.  A fan without an unread ray has the first table again (and its order), every entry marked FTGP_TASK_MASKED;
 // first_table_ok: so may a fan whose own list would be longer than the first table (`times`: how often the first table draws a ray).
 // Shared by plan_check.cpp, plan_tracks_check.cpp and plan_window_fans.cpp (after their CHECK macro).
 #pragma once
@@ -20,7 +22,10 @@ static void check_window_table(const Plan& pl, const std::vector<int>& times, co
     bool dead = false;
     for (int j = 0; j < R; ++j) dead = dead || !live(j);
     CHECK(P.win_tasks_per_car >= 1 && P.win_tasks_per_car <= P.tasks_per_car, "%d window-only tasks per car of %d", P.win_tasks_per_car, P.tasks_per_car);
-    const bool is_first = ntasks == full && n_gathers == 0 && memcmp(pl.tasks_win.data(), pl.tasks.data(), sizeof(int32_t) * pl.tasks_win.size()) == 0;
+    // (the first table again: entry for entry, each marked FTGP_TASK_MASKED -- it has partial groups, kind 2 and every window class, so none of its
+    // draws may take the window-only sweep's unmasked path)
+    bool is_first = ntasks == full && n_gathers == 0;
+    for (size_t i = 0; is_first && i < pl.tasks_win.size(); ++i) is_first = pl.tasks_win[i] == (pl.tasks[i] | (i % 4 == 0 ? FTGP_TASK_MASKED : 0));
     if (!dead || (first_table_ok && is_first)) {
         CHECK(is_first && memcmp(P.win_group_order, P.group_order, sizeof(int32_t) * (size_t)P.tasks_per_car) == 0, "the window-only table should be the first table, and is not");
         return;
@@ -32,7 +37,13 @@ static void check_window_table(const Plan& pl, const std::vector<int>& times, co
         const uint32_t x = (uint32_t)d[0];
         const int field = x & 0x3fff, kind = (x >> 14) & 3, c = (x >> 16) & 15, rank = d[1] >> 16, w0 = (x >> 20) & 3, w1 = (x >> 22) & 3, flag = (x >> 24) & 1;
         // ranks ascend, the car slots of a rank together; the draw is the task win_group_order names
-        CHECK(c == g % cpb && rank == g / cpb && (x >> 25) == 0, "window draw %d: slot %d, rank %d, high bits %x", g, c, rank, x >> 25);
+        CHECK(c == g % cpb && rank == g / cpb && (x >> 26) == 0, "window draw %d: slot %d, rank %d, high bits %x", g, c, rank, x >> 26);
+        // a PLAIN draw (FTGP_TASK_MASKED clear) runs without a lane mask and delivers with one store: kind 0 or 1 -- never kind 2 --, every group
+        // wholly inside the window, no ray 0 (that all 64 lanes hold a live ray is checked lane by lane below); a gather is never plain
+        const bool plain = (x & (uint32_t)FTGP_TASK_MASKED) == 0;
+        CHECK(plain == (kind != 3) && kind != 2, "window draw %d: kind %d, plain %d", g, kind, (int)plain);
+        if (plain) CHECK(kind <= 1 && w0 == 1 && w1 == (kind == 1 ? 1 : 0) && !flag && field + FTGP_WAVE <= (kind == 1 ? half : R),
+                         "window draw %d: a plain draw of kind %d at ray %d with window classes %d / %d, ray-0 flag %d", g, kind, field, w0, w1, flag);
         if (!(c == g % cpb && rank == g / cpb)) continue;
         const int ent = P.win_group_order[rank];
         CHECK(kind == (ent >> 16) && field == (ent & 0xffff) && kind != 2, "window draw %d: kind %d, field %d, win_group_order[%d] = %x", g, kind, field, rank, ent);
