@@ -111,6 +111,7 @@ API_SYMBOLS = (
     "set_net", "set_net_device", "get_net", "set_net_frame", "get_net_frame", "set_net_rivals", "get_net_rivals",
     "collect_device",
     "set_net_population", "set_net_population_device", "get_net_population",
+    "set_value_net", "set_value_net_device", "get_value_net", "collect_values_device", "gae_device",
 )
 
 
@@ -204,6 +205,96 @@ def collect_args(n_decisions, slot=0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e3
     for k in range(2):
         c.std[k], c.lo[k], c.hi[k] = float(sd[k]), float(lim[k, 0]), float(lim[k, 1])
     return c
+
+
+class FtgpValueDesc(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("width", C.c_int32 * NET_MAX_LAYERS), ("hidden_act", C.c_int32), ("out_act", C.c_int32),
+                ("out_scale", C.c_float), ("out_offset", C.c_float), ("reserved", C.c_int32)]
+
+
+class FtgpCollectValues(C.Structure):
+    _fields_ = [("gamma", C.c_float), ("lam", C.c_float), ("value", C.c_void_p), ("next_value", C.c_void_p),
+                ("advantage", C.c_void_p), ("ret", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+def value_desc(layers, *, hidden_act="tanh", out_act="identity", out_scale=1.0, out_offset=0.0):
+    """(FtgpValueDesc, flat float32 parameters) of a value net given as a list of (W [n_out, n_in], b [n_out]) pairs, with every check
+    of ftgp_set_value_net that needs no handle (ValueError): 1 .. 4 layers, hidden widths 1 .. 128, a last width of exactly 1, the
+    activations, a finite output map, the shapes of the arrays.  The first layer's n_in must be the slot's; the handle knows it."""
+    try:
+        layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
+    except (TypeError, ValueError):
+        raise ValueError("layers: a list of (W [n_out, n_in], b [n_out]) pairs") from None
+    if not 1 <= len(layers) <= NET_MAX_LAYERS:
+        raise ValueError(f"a value net has 1 .. {NET_MAX_LAYERS} layers, got {len(layers)}")
+    for name, act in (("hidden_act", hidden_act), ("out_act", out_act)):
+        if act not in ACT_BY_NAME:
+            raise ValueError(f"{name}: one of {sorted(ACT_BY_NAME)}, got {act!r}")
+    try:
+        scale, offset = float(np.float32(out_scale)), float(np.float32(out_offset))
+    except (TypeError, ValueError):
+        raise ValueError(f"out_scale and out_offset: one finite number each, got {out_scale!r}, {out_offset!r}") from None
+    if not (np.isfinite(scale) and np.isfinite(offset)):
+        raise ValueError(f"out_scale and out_offset: one finite number each, got {out_scale!r}, {out_offset!r}")
+    d = FtgpValueDesc(n_layers=len(layers), hidden_act=ACT_BY_NAME[hidden_act], out_act=ACT_BY_NAME[out_act], out_scale=scale, out_offset=offset)
+    flat, width = [], None
+    for l, (W, b) in enumerate(layers):
+        last = l == len(layers) - 1
+        if W.ndim != 2 or W.shape[1] < 1 or (width is not None and W.shape[1] != width) or b.shape != (W.shape[0],):
+            raise ValueError(f"layer {l}: W [n_out, {width if width is not None else 'n_in'}] and b [n_out] (torch's nn.Linear layout), got {W.shape} and {b.shape}")
+        if last and W.shape[0] != 1:
+            raise ValueError(f"the last layer of a value net has exactly 1 output, got {W.shape[0]}")
+        if not last and not 1 <= W.shape[0] <= NET_MAX_HIDDEN:
+            raise ValueError(f"layer {l}: a hidden width is 1 .. {NET_MAX_HIDDEN}, got {W.shape[0]}")
+        d.width[l] = width = W.shape[0]
+        flat += [W.ravel(), b.ravel()]
+    if layers[0][0].shape[1] > NET_MAX_INPUTS:
+        raise ValueError(f"layer 0: at most {NET_MAX_INPUTS} inputs, got {layers[0][0].shape[1]}")
+    return d, np.ascontiguousarray(np.concatenate(flat), dtype=np.float32)
+
+
+def value_param_count(d: FtgpValueDesc, n_in: int) -> int:
+    n = 0
+    for l in range(d.n_layers):
+        n, n_in = n + d.width[l] * n_in + d.width[l], d.width[l]
+    return n
+
+
+def value_layers(d: FtgpValueDesc, flat: np.ndarray, n_in: int) -> list:
+    """The (W, b) pairs of a value net's flat parameter buffer on a slot of ``n_in`` inputs."""
+    out, o = [], 0
+    for l in range(d.n_layers):
+        n_out = d.width[l]
+        W = flat[o:o + n_out * n_in].reshape(n_out, n_in); o += n_out * n_in
+        out.append((W.copy(), flat[o:o + n_out].copy())); o += n_out
+        n_in = n_out
+    return out
+
+
+def check_discounts(gamma, lam):
+    """gamma and lam of ftgp_collect_values_device and ftgp_gae_device as binary32 (ValueError): finite, in [0, 1]."""
+    out = []
+    for name, v in (("gamma", gamma), ("lam", lam)):
+        try:
+            f = float(np.float32(v))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: a number in [0, 1], got {v!r}") from None
+        if isinstance(v, bool) or not (np.isfinite(f) and 0.0 <= f <= 1.0):
+            raise ValueError(f"{name}: finite and in [0, 1], got {v!r}")
+        out.append(f)
+    return tuple(out)
+
+
+def collect_values_args(gamma=0.99, lam=0.95, value: int = 0, next_value: int = 0, advantage: int = 0, ret: int = 0) -> "FtgpCollectValues":
+    """An FtgpCollectValues on integer device addresses with every check of ftgp_collect_values_device that needs no handle
+    (ValueError): gamma and lam finite and in [0, 1]; ``advantage`` and ``ret`` both or neither (0 = NULL)."""
+    g, l = check_discounts(gamma, lam)
+    if bool(advantage) != bool(ret):
+        raise ValueError("advantage and ret: both or neither" + (", got advantage without ret" if advantage else ", got ret without advantage"))
+    v = FtgpCollectValues(gamma=g, lam=l)
+    for name, a in (("value", value), ("next_value", next_value), ("advantage", advantage), ("ret", ret)):
+        setattr(v, name, a or None)
+    return v
 
 
 def net_frame(frame=False, lookahead=0, lookahead_stride=1) -> "FtgpNetFrame":
@@ -441,6 +532,11 @@ class CLib:
             "set_net_population": (i32, [vp, i32, i32, dp, dp]),
             "set_net_population_device": (i32, [vp, vp, i32, vp, vp]),
             "get_net_population": (i32, [vp, i32, C.POINTER(C.c_int32), dp, i32, dp]),
+            "set_value_net": (i32, [vp, i32, C.POINTER(FtgpValueDesc), dp]),
+            "set_value_net_device": (i32, [vp, vp, i32, vp]),
+            "get_value_net": (i32, [vp, i32, C.POINTER(FtgpValueDesc), dp]),
+            "collect_values_device": (i32, [vp, C.POINTER(FtgpCollect), C.POINTER(FtgpCollectValues)]),
+            "gae_device": (i32, [vp, vp, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -848,6 +944,66 @@ class Env:
                         ("reset_dynamics", reset_dynamics)):
             setattr(c, name, v or None)
         self._call("collect_device", C.byref(c))
+
+    # -- collected rollouts with values (include/ftgp.h: ftgp_set_value_net, ftgp_collect_values_device, ftgp_gae_device)
+    def set_value_net(self, slot: int, layers, *, hidden_act="tanh", out_act="identity", out_scale=1.0, out_offset=0.0):
+        """ftgp_set_value_net: ``layers`` = [(W [n_out, n_in], b [n_out]), ...] with one output becomes the value net of defined slot
+        ``slot`` -- it reads the slot's own input vector; ``layers=None`` clears it."""
+        if layers is None:
+            self._call("set_value_net", int(slot), None, None)
+            return
+        d, flat = value_desc(layers, hidden_act=hidden_act, out_act=out_act, out_scale=out_scale, out_offset=out_offset)
+        n_in = self._net_n_in(slot)            # (a slot that is not defined: the library's message)
+        if np.asarray(layers[0][0]).shape[1] != n_in:
+            raise ValueError(f"layer 0: the value net reads slot {int(slot)}'s {n_in} inputs, got W with {np.asarray(layers[0][0]).shape[1]} columns")
+        self._call("set_value_net", int(slot), C.byref(d), _ptr(flat))
+
+    def set_value_net_device(self, slot: int, address: int, stream: int = 0):
+        """ftgp_set_value_net_device: new parameters for a slot's value net from the integer device address of a float32 buffer in
+        the flat layout, ordered on ``stream``; only enqueues, never synchronises."""
+        self._call("set_value_net_device", stream or None, int(slot), address or None)
+
+    def _net_n_in(self, slot: int) -> int:
+        d, f, r = FtgpNetDesc(), FtgpNetFrame(), FtgpNetRivals()
+        self._call("get_net", int(slot), C.byref(d), None)
+        self._call("get_net_frame", int(slot), C.byref(f))
+        self._call("get_net_rivals", int(slot), C.byref(r))
+        return d.n_beams + (NET_STATE_INPUTS if d.use_state else 0) + net_frame_inputs(f) + net_rival_inputs(r)
+
+    def get_value_net(self, slot: int):
+        """(FtgpValueDesc, [(W, b), ...]): the description and the parameters in force of a slot's value net (ftgp_get_value_net)."""
+        d = FtgpValueDesc()
+        self._call("get_value_net", int(slot), C.byref(d), None)
+        n_in = self._net_n_in(slot)
+        flat = np.empty(value_param_count(d, n_in), dtype=np.float32)
+        self._call("get_value_net", int(slot), C.byref(d), _ptr(flat))
+        return d, value_layers(d, flat, n_in)
+
+    def collect_values_device(self, n_decisions: int, inputs: int, mean: int, action: int, reward: int, terminated: int, truncated: int,
+                              value: int, next_value: int, *, advantage: int = 0, ret: int = 0, gamma=0.99, lam=0.95,
+                              slot: int = 0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e30, 1e30)), noise: int = 0, next_inputs: int = 0,
+                              reset_dynamics: int = 0, stream: int = 0):
+        """One ftgp_collect_values_device call on integer device addresses: ``collect_device`` with the slot's value net evaluated
+        into ``value`` and ``next_value`` (float32 [T, n_envs, n_ext]) and, with ``advantage`` and ``ret`` (both or neither, 0 = NULL),
+        the advantage scan with ``gamma`` and ``lam`` behind the last decision.  Only enqueues."""
+        c = collect_args(n_decisions, slot, std, clip)
+        v = collect_values_args(gamma, lam, value, next_value, advantage, ret)
+        c.stream = stream or None
+        for name, a in (("noise", noise), ("inputs", inputs), ("mean", mean), ("action", action), ("reward", reward),
+                        ("terminated", terminated), ("truncated", truncated), ("next_inputs", next_inputs),
+                        ("reset_dynamics", reset_dynamics)):
+            setattr(c, name, a or None)
+        self._call("collect_values_device", C.byref(c), C.byref(v))
+
+    def gae_device(self, n_decisions: int, reward: int, value: int, next_value: int, terminated: int, truncated: int,
+                   advantage: int, ret: int, *, gamma=0.99, lam=0.95, stream: int = 0):
+        """ftgp_gae_device on integer device addresses: the advantage scan over ``n_decisions`` decisions of the handle's external
+        rows, ordered on ``stream``; only enqueues."""
+        if isinstance(n_decisions, bool) or not isinstance(n_decisions, (int, np.integer)) or not 1 <= int(n_decisions) < 2 ** 31:
+            raise ValueError(f"n_decisions: an integer >= 1, got {n_decisions!r}")
+        g, l = check_discounts(gamma, lam)
+        self._call("gae_device", stream or None, int(n_decisions), g, l, reward or None, value or None, next_value or None,
+                   terminated or None, truncated or None, advantage or None, ret or None)
 
     # -- env states on the device (include/ftgp.h: ftgp_save_envs_device)
     def env_state_bytes(self) -> int:

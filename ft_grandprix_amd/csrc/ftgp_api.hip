@@ -207,6 +207,12 @@ struct FtgpEnv {
     DevBuf<float> d_pop_params[FTGP_MAX_NETS];    // [n_members] parameter sets in the library's layout, net_member_stride(n_floats) floats apart
     DevBuf<int32_t> d_pop_map[FTGP_MAX_NETS];     // [n_envs] the member of every env
     bool last_net = false;            // the newest launch ran a NET instantiation
+    // value nets (ftgp_set_value_net): one per defined slot at most; read by the VALUE instantiations of ftgp_collect_act_kernel alone, so the
+    // records have a table of their own and the parameter blocks know nothing of them
+    DevBuf<NetDev> d_vnets;           // [FTGP_MAX_NETS] NetDev-shaped records: the layers, the output map in out_scale[0] / out_offset[0], params; allocated by the first setter call
+    NetDev vnets[FTGP_MAX_NETS] = {}; // their host mirror (defined = 0: none)
+    FtgpValueDesc vnet_desc[FTGP_MAX_NETS] = {};  // the descriptions as the caller gave them (ftgp_get_value_net)
+    DevBuf<float> d_vnet_params[FTGP_MAX_NETS];   // the parameters in the library's layout
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
     std::vector<uint64_t> track_fp;   // [n_tracks] the tracks' fingerprints (include/ftgp.h), folded at create
     DevBuf<EnvStateAux> d_state_aux;  // the handle's own dynamics record, the rejected counter, the fingerprints; allocated by the first save or load
@@ -1849,22 +1855,52 @@ static size_t collect_act_lds(const NetDev& N) { return 4 * ((size_t)N.n_beams *
 
 // ftgp_collect_act_kernel on the handle's stream for the rows of one decision: inputs, mean and action -- or, with mean == null, the
 // inputs alone (next_inputs)
-static int launch_collect_act(FtgpEnv* e, const FtgpCollect& c, const float* noise, float* inputs, float* mean, float* action)
+// (value != null: the VALUE instantiations, which also evaluate the slot's value net into value -- ftgp_collect_values_device)
+static int launch_collect_act(FtgpEnv* e, const FtgpCollect& c, const float* noise, float* inputs, float* mean, float* action, float* value = nullptr)
 {
-    CollectActArgs C{};
+    CollectValueArgs C{};
     C.noise = noise; C.inputs = inputs; C.mean = mean; C.action = action;
     for (int k = 0; k < 2; ++k) { C.std[k] = c.std[k]; C.lo[k] = c.lo[k]; C.hi[k] = c.hi[k]; }
     C.slot = c.slot; C.n_ext = e->ds.io.n_ext; C.n_rows = e->P.n_envs * e->ds.io.n_ext;
     for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) if (e->ds.io.ext_index[k] >= 0) C.ext_slot[e->ds.io.ext_index[k]] = k;
     C.env_track = e->d_env_track.get();
     const size_t lds = collect_act_lds(e->nets[c.slot]);
-    void (*kernel)(DeviceParams, CollectActArgs) = mean ? ftgp_collect_act_kernel<true> : ftgp_collect_act_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((C.n_rows + 3) / 4)), dim3(256), lds, e->stream.get(), e->P, C);
+    if (value) {
+        C.vnet = e->d_vnets.get() + c.slot; C.value = value;
+        void (*kernel)(DeviceParams, CollectValueArgs) = mean ? ftgp_collect_act_kernel<true, true> : ftgp_collect_act_kernel<false, true>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((C.n_rows + 3) / 4)), dim3(256), lds, e->stream.get(), e->P, C);
+    } else {
+        void (*kernel)(DeviceParams, CollectActArgs) = mean ? ftgp_collect_act_kernel<true> : ftgp_collect_act_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((C.n_rows + 3) / 4)), dim3(256), lds, e->stream.get(), e->P, static_cast<const CollectActArgs&>(C));
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int ftgp_collect_device(FtgpEnv* e, const FtgpCollect* c)
+// gamma and lam of ftgp_collect_values_device and ftgp_gae_device: finite, in [0, 1]
+static int check_discount(const char* entry, const char* name, float v)
+{
+    if (!std::isfinite(v) || v < 0.0f || v > 1.0f) return failf(FTGP_ERR_ARG, "%s: %s = %g must be finite and in [0, 1]", entry, name, (double)v);
+    return 0;
+}
+
+// ftgp_gae_kernel on the handle's stream: the advantage scan over T decisions of the handle's external rows (the buffers are checked)
+static int launch_gae(FtgpEnv* e, size_t T, float gamma, float lam, const float* reward, const float* value, const float* next_value,
+                      const uint8_t* terminated, const uint8_t* truncated, float* advantage, float* ret)
+{
+    GaeArgs G{};
+    G.reward = reward; G.value = value; G.next_value = next_value; G.terminated = terminated; G.truncated = truncated;
+    G.advantage = advantage; G.ret = ret;
+    G.gamma = gamma; G.gl = gamma * lam;
+    G.T = (int32_t)T; G.n_ext = e->ds.io.n_ext; G.n_envs = e->P.n_envs; G.n_rows = e->P.n_envs * e->ds.io.n_ext;
+    hipLaunchKernelGGL(ftgp_gae_kernel, dim3((unsigned)((G.n_rows + 255) / 256)), dim3(256), 0, e->stream.get(), G);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ftgp_collect_device(FtgpEnv* e, const FtgpCollect* c) { return ftgp_collect_values_device(e, c, nullptr); }
+
+int ftgp_collect_values_device(FtgpEnv* e, const FtgpCollect* c, const FtgpCollectValues* v)
 {
     if (!e || !c) return fail(FTGP_ERR_ARG, "null argument%s");
     FtgpEnv::DeviceStep& ds = e->ds;
@@ -1901,6 +1937,26 @@ int ftgp_collect_device(FtgpEnv* e, const FtgpCollect* c)
     if (int rc = checked(c->truncated, n_envs, "truncated")) return rc;
     if (c->next_inputs) if (int rc = checked(c->next_inputs, sizeof(float) * n_in * rows, "next_inputs")) return rc;
     if (c->reset_dynamics) if (int rc = checked(c->reset_dynamics, sizeof(double) * FTGP_DYN_DOUBLES * (size_t)e->P.n_cars, "reset_dynamics")) return rc;
+    if (v) {
+        auto refused_v = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_collect_values_device: %s", m.c_str()); return rc; };
+        auto checked_v = [&](const void* p, const char* name) {
+            size_t bytes = 0;
+            if (__builtin_mul_overflow(T, sizeof(float) * rows, &bytes)) return failf(FTGP_ERR_ARG, "ftgp_collect_values_device: %s is smaller than the layout needs", name);
+            return check_device_buffer(e, p, bytes, name) ? refused_v(FTGP_ERR_ARG) : 0;
+        };
+        if (!e->vnets[c->slot].defined) return failf(FTGP_ERR_STATE, "ftgp_collect_values_device: network slot %d has no value net (ftgp_set_value_net)", c->slot);
+        if (v->reserved[0] != 0 || v->reserved[1] != 0) return fail(FTGP_ERR_ARG, "ftgp_collect_values_device: reserved must be 0%s");
+        if (int rc = check_discount("ftgp_collect_values_device", "gamma", v->gamma)) return rc;
+        if (int rc = check_discount("ftgp_collect_values_device", "lam", v->lam)) return rc;
+        if ((v->advantage == nullptr) != (v->ret == nullptr))
+            return failf(FTGP_ERR_ARG, "ftgp_collect_values_device: %s is given without %s (both or neither)", v->advantage ? "advantage" : "ret", v->advantage ? "ret" : "advantage");
+        if (int rc = checked_v(v->value, "value")) return rc;
+        if (int rc = checked_v(v->next_value, "next_value")) return rc;
+        if (v->advantage) {
+            if (int rc = checked_v(v->advantage, "advantage")) return rc;
+            if (int rc = checked_v(v->ret, "ret")) return rc;
+        }
+    }
     // the obs rows of the device step are not part of the record: scratch of the handle's, at the widest row a signals setting gives
     if (!ds.d_collect_obs) HIP_TRY(dev_alloc(ds.d_collect_obs, sizeof(float) * (size_t)e->P.n_cars * (size_t)e->P.n_rays));
     const FtgpDeviceStep io{ c->stream, c->action, ds.d_collect_obs.get(), c->reward, c->terminated, c->truncated, nullptr };
@@ -1911,13 +1967,47 @@ int ftgp_collect_device(FtgpEnv* e, const FtgpCollect* c)
     if (int rc = handle_waits_for_caller(e, caller)) return rc;
     for (size_t t = 0; t < T; ++t) {
         float* action = c->action + t * rows * 2;
-        if (int rc = launch_collect_act(e, *c, c->noise ? c->noise + t * rows * 2 : nullptr, c->inputs + t * rows * n_in, c->mean + t * rows * 2, action)) return rc;
+        if (int rc = launch_collect_act(e, *c, c->noise ? c->noise + t * rows * 2 : nullptr, c->inputs + t * rows * n_in, c->mean + t * rows * 2, action,
+                                        v ? v->value + t * rows : nullptr)) return rc;
         plan.A.action = action; plan.A.reward = c->reward + t * rows; plan.A.terminated = c->terminated + t * n_envs; plan.A.truncated = c->truncated + t * n_envs;
-        if (int rc = enqueue_device_step(e, plan, [&] { return c->next_inputs ? launch_collect_act(e, *c, nullptr, c->next_inputs + t * rows * n_in, nullptr, nullptr) : 0; })) return rc;
+        // (step 3': with a value net the kernel runs whether or not next_inputs is given, and writes x down only where it is)
+        if (int rc = enqueue_device_step(e, plan, [&] {
+                if (v) return launch_collect_act(e, *c, nullptr, c->next_inputs ? c->next_inputs + t * rows * n_in : nullptr, nullptr, nullptr, v->next_value + t * rows);
+                return c->next_inputs ? launch_collect_act(e, *c, nullptr, c->next_inputs + t * rows * n_in, nullptr, nullptr) : 0; })) return rc;
         if (c->reset_dynamics)
             if (int rc = launch_dynamics(e, c->reset_dynamics + t * (size_t)e->P.n_cars * FTGP_DYN_DOUBLES, plan.A.terminated, plan.A.truncated)) return rc;
     }
+    if (v && v->advantage)
+        if (int rc = launch_gae(e, T, v->gamma, v->lam, c->reward, v->value, v->next_value, c->terminated, c->truncated, v->advantage, v->ret)) return rc;
     return caller_waits_for_handle(e, caller);
+}
+
+int ftgp_gae_device(FtgpEnv* e, void* stream, int n_decisions, float gamma, float lam, const float* reward, const float* value, const float* next_value,
+                    const uint8_t* terminated, const uint8_t* truncated, float* advantage, float* ret)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!e->ds.ready) return fail(FTGP_ERR_STATE, "ftgp_gae_device before ftgp_device_io_config%s");
+    if (n_decisions < 1) return failf(FTGP_ERR_ARG, "ftgp_gae_device: n_decisions = %d must be >= 1", n_decisions);
+    if (int rc = check_discount("ftgp_gae_device", "gamma", gamma)) return rc;
+    if (int rc = check_discount("ftgp_gae_device", "lam", lam)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t T = (size_t)n_decisions, n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)e->ds.io.n_ext;
+    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_gae_device: %s", m.c_str()); return rc; };
+    auto checked = [&](const void* p, size_t per_decision, const char* name) {
+        size_t bytes = 0;
+        if (__builtin_mul_overflow(T, per_decision, &bytes)) return failf(FTGP_ERR_ARG, "ftgp_gae_device: %s is smaller than the layout needs", name);
+        return check_device_buffer(e, p, bytes, name) ? refused(FTGP_ERR_ARG) : 0;
+    };
+    if (int rc = checked(reward, sizeof(float) * rows, "reward")) return rc;
+    if (int rc = checked(value, sizeof(float) * rows, "value")) return rc;
+    if (int rc = checked(next_value, sizeof(float) * rows, "next_value")) return rc;
+    if (int rc = checked(terminated, n_envs, "terminated")) return rc;
+    if (int rc = checked(truncated, n_envs, "truncated")) return rc;
+    if (int rc = checked(advantage, sizeof(float) * rows, "advantage")) return rc;
+    if (int rc = checked(ret, sizeof(float) * rows, "ret")) return rc;
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    if (int rc = launch_gae(e, T, gamma, lam, reward, value, next_value, terminated, truncated, advantage, ret)) return rc;
+    return caller_waits_for_handle(e, (hipStream_t)stream);
 }
 
 int ftgp_state_device(FtgpEnv* e, void* stream, float* state)
@@ -2221,6 +2311,7 @@ int ftgp_set_net_rivals(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftg
     e->net_rivals[slot] = (desc && rivals && rivals->enabled) ? *rivals : FtgpNetRivals{};
     e->d_net_params[slot] = std::move(buf);                   // (the old buffer goes: nothing reads it any more)
     e->pop_members[slot] = 0; e->d_pop_params[slot] = DevBuf<float>(); e->d_pop_map[slot] = DevBuf<int32_t>();      // ... and a population with it
+    e->vnets[slot] = NetDev{}; e->vnet_desc[slot] = FtgpValueDesc{}; e->d_vnet_params[slot] = DevBuf<float>();         // ... and a value net: the input width may have changed
     return 0;
 }
 
@@ -2366,6 +2457,114 @@ int ftgp_get_net_rivals(FtgpEnv* e, int slot, FtgpNetRivals* rivals_out)
     if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_rivals: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
     if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_rivals: network slot %d is not defined (ftgp_set_net)", slot);
     if (rivals_out) *rivals_out = e->net_rivals[slot];
+    return 0;
+}
+
+// ---- value nets: one critic per network slot (include/ftgp.h "Collected rollouts with values") ----
+// what ftgp_set_value_net checks of a description; the message names the field
+static int check_value_desc(const FtgpValueDesc& d)
+{
+    if (d.reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: reserved must be 0%s");
+    if (d.n_layers < 1 || d.n_layers > FTGP_NET_MAX_LAYERS) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: n_layers = %d outside 1 .. %d", d.n_layers, FTGP_NET_MAX_LAYERS);
+    for (int l = 0; l < FTGP_NET_MAX_LAYERS; ++l) {
+        const int w = d.width[l];
+        if (l >= d.n_layers) { if (w != 0) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: width[%d] = %d behind the last layer must be 0", l, w); }
+        else if (l == d.n_layers - 1) { if (w != 1) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: width[%d] = %d: the last layer has exactly 1 output", l, w); }
+        else if (w < 1 || w > FTGP_NET_MAX_HIDDEN) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: width[%d] = %d outside 1 .. %d", l, w, FTGP_NET_MAX_HIDDEN);
+    }
+    if (d.hidden_act < FTGP_ACT_IDENTITY || d.hidden_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: hidden_act = %d is no FTGP_ACT_*", d.hidden_act);
+    if (d.out_act < FTGP_ACT_IDENTITY || d.out_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: out_act = %d is no FTGP_ACT_*", d.out_act);
+    if (!std::isfinite(d.out_scale)) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: out_scale is not finite%s");
+    if (!std::isfinite(d.out_offset)) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: out_offset is not finite%s");
+    return 0;
+}
+
+// the record of a value net on a slot of n_in inputs: NetDev's layer fields as net_layers reads them, the output map in entry 0, no
+// scan, frame or rival fields (the inputs are the slot's) and no population
+static NetDev value_record(const FtgpValueDesc& d, int n_in)
+{
+    NetDev N{};
+    N.defined = 1; N.n_layers = d.n_layers; N.hidden_act = d.hidden_act; N.out_act = d.out_act;
+    N.width[0] = n_in;
+    int o = 0;
+    for (int l = 0; l < d.n_layers; ++l) {
+        N.width[l + 1] = d.width[l];
+        const int ld = (d.width[l] + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
+        N.w_off[l] = o; o += N.width[l] * ld;
+        N.b_off[l] = o; o += ld;
+    }
+    N.n_floats = o;
+    N.out_scale[0] = d.out_scale; N.out_offset[0] = d.out_offset;
+    return N;
+}
+
+int ftgp_set_value_net(FtgpEnv* e, int slot, const FtgpValueDesc* desc, const float* params)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_value_net: network slot %d is not defined (ftgp_set_net)", slot);
+    if (desc) {
+        if (int rc = check_value_desc(*desc)) return rc;
+        if (!params) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: params is NULL%s");
+    }
+    if (!desc && !e->vnets[slot].defined) return 0;              // there is none
+    HIP_TRY(hipSetDevice(e->device));
+    NetDev N{};
+    DevBuf<float> buf;
+    DevBuf<NetDev> table;
+    if (desc) {
+        N = value_record(*desc, e->nets[slot].width[0]);
+        std::vector<float> img;                               // the library's layout; the padding is zeros
+        if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_set_value_net")) return rc;
+        ftgp_net_population_to_library(N.n_layers, N.width, 1, params, img.data());
+        HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
+        N.params = buf.get();
+        if (!e->d_vnets) {                                    // the first value net of the handle: the records, every slot empty
+            HIP_TRY(dev_alloc(table, sizeof(NetDev) * FTGP_MAX_NETS));
+            HIP_TRY(hipMemset(table.get(), 0, sizeof(NetDev) * FTGP_MAX_NETS));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the record while it changes
+    NetDev* records = table ? table.get() : e->d_vnets.get();
+    HIP_TRY(hipMemcpy(records + slot, &N, sizeof N, hipMemcpyHostToDevice));
+    if (table) e->d_vnets = std::move(table);
+    e->vnets[slot] = N;
+    e->vnet_desc[slot] = desc ? *desc : FtgpValueDesc{};
+    e->d_vnet_params[slot] = std::move(buf);                  // (the old buffer goes: nothing reads it any more)
+    return 0;
+}
+
+int ftgp_set_value_net_device(FtgpEnv* e, void* stream, int slot, const float* params)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_value_net_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->vnets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_value_net_device: network slot %d has no value net (ftgp_set_value_net)", slot);
+    HIP_TRY(hipSetDevice(e->device));
+    const int n = (int)net_param_count(e->vnets[slot]);
+    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_value_net_device: %s", m.c_str()); return rc; };
+    if (int rc = check_device_buffer(e, params, sizeof(float) * (size_t)n, "params")) return refused(rc);
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream.get(), e->vnets[slot], params, e->d_vnet_params[slot].get(), n, 0, 1);
+    HIP_TRY(hipGetLastError());
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+int ftgp_get_value_net(FtgpEnv* e, int slot, FtgpValueDesc* desc_out, float* params_out)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_value_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    const NetDev& N = e->vnets[slot];
+    if (!N.defined) return failf(FTGP_ERR_STATE, "ftgp_get_value_net: network slot %d has no value net (ftgp_set_value_net)", slot);
+    if (desc_out) *desc_out = e->vnet_desc[slot];
+    if (!params_out) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<float> img;
+    if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_get_value_net")) return rc;
+    HIP_TRY(hipMemcpyAsync(img.data(), e->d_vnet_params[slot].get(), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), params_out);
     return 0;
 }
 

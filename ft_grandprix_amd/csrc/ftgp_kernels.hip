@@ -2264,7 +2264,7 @@ __global__ void ftgp_net_params_kernel(NetDev N, const float* __restrict__ src, 
 // step kernels stay where they were.)
 struct CollectActArgs {
     const float* noise;           // [n_rows][2] or null = zeros
-    float* inputs;                // [n_rows][n_in]
+    float* inputs;                // [n_rows][n_in]; the VALUE instantiations take null = not written down
     float* mean;                  // [n_rows][2]; unused, as noise and action, by the ACT = false instantiation
     float* action;                // [n_rows][2]
     float std[2], lo[2], hi[2];
@@ -2272,8 +2272,19 @@ struct CollectActArgs {
     int32_t ext_slot[FTGP_PAIR_STRIDE];      // index among the env's external cars -> car slot
     const int32_t* env_track;     // the track of every env; null with one track (frame inputs: the centre-line of the car's track)
 };
-template <bool ACT>
-__global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, CollectActArgs C)
+// VALUE (ftgp_collect_values_device, steps 1' and 3'): the wave keeps a copy of x, evaluates the slot's value net on it -- net_layers on a
+// NetDev-shaped record of the value net, one parameter set whatever the slot's population -- and lane 0 writes v.  For a finished car
+// too: its policy is not looked at, its value is.  With ACT = false the value is the only evaluation (next_value).  The record and the
+// row come behind CollectActArgs in an argument struct of the VALUE instantiations' own: the two instantiations without it take the
+// arguments they took and hold the code they held.
+struct CollectValueArgs : CollectActArgs {
+    const NetDev* vnet;           // the value record of the slot (FtgpEnv::d_vnets + slot)
+    float* value;                 // [n_rows]
+};
+template <bool VALUE> struct CollectArgsOf { typedef CollectActArgs type; };
+template <> struct CollectArgsOf<true> { typedef CollectValueArgs type; };
+template <bool ACT, bool VALUE = false>
+__global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, typename CollectArgsOf<VALUE>::type C)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int lane = lane_id();
@@ -2298,10 +2309,19 @@ __global__ void __launch_bounds__(256) ftgp_collect_act_kernel(DeviceParams P, C
                                  return NetEnv{ P.path + (size_t)(C.env_track ? C.env_track[env] : 0) * 2 * FTGP_PATH_POINTS, P.cars + (size_t)env * P.cars_per_env,
                                                 (int)sizeof(CarState), ci - env * P.cars_per_env, P.cars_per_env }; }, x);
     const int n_in = N->width[0];
-    float* in_row = C.inputs + (size_t)row * n_in;
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) if (r * FTGP_WAVE + lane < n_in) in_row[r * FTGP_WAVE + lane] = x[r];
-    if (!ACT) return;
+    if (!VALUE || C.inputs) {                                    // (next_value without next_inputs: x is not written down)
+        float* in_row = C.inputs + (size_t)row * n_in;
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) if (r * FTGP_WAVE + lane < n_in) in_row[r * FTGP_WAVE + lane] = x[r];
+    }
+    if (!ACT && !VALUE) return;
+    if constexpr (VALUE) {
+        const ScalarNet V = scalar_net(C.vnet, 0);
+        float xv[4] = { x[0], x[1], x[2], x[3] };
+        net_layers(V, [] { return 0; }, xv);                     // (a value record has no env_member: the env is never asked for)
+        if (lane == 0) C.value[row] = ftgp_net_value(xv[0], V->out_scale[0], V->out_offset[0]);
+        if (!ACT) return;
+    }
     const int k = lane & 1;
     float m = 0.0f, a = 0.0f;
     if (!sgpr(st->finished)) {                                   // a finished car: (0, 0) before the network is looked at
@@ -3425,5 +3445,36 @@ __global__ void __launch_bounds__(FTGP_METRIC_THREADS) ftgp_metrics_kernel(Devic
         }
         out[0] = r[0]; out[1] = (double)P.n_cars; out[2] = r[1]; out[3] = r[2];
         out[4] = r[3]; out[5] = r[4]; out[6] = r[5]; out[7] = r[6];
+    }
+}
+
+// =============================================================================================
+// Collected rollouts with values (include/ftgp.h: ftgp_collect_values_device, ftgp_gae_device).  Behind every other kernel of the file, so
+// that the code object keeps the others where they were.
+// =============================================================================================
+template __global__ void ftgp_collect_act_kernel<true, true>(DeviceParams, CollectValueArgs);
+template __global__ void ftgp_collect_act_kernel<false, true>(DeviceParams, CollectValueArgs);
+
+// The advantage scan: one thread per row (env, external car), t descending, so that a wave's loads of one t are contiguous; the element
+// step is ftgp_gae_step of ftgp_net.h, which tools/collect_values_check.cpp compiles for the CPU.
+struct GaeArgs {
+    const float* reward; const float* value; const float* next_value;      // [T][n_rows]
+    const uint8_t* terminated; const uint8_t* truncated;                   // [T][n_envs]
+    float* advantage; float* ret;                                          // [T][n_rows]
+    float gamma, gl;              // gl = gamma * lam, rounded once on the host
+    int32_t T, n_rows, n_ext, n_envs;
+};
+__global__ void __launch_bounds__(256) ftgp_gae_kernel(GaeArgs G)
+{
+    const int row = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (row >= G.n_rows) return;
+    const int env = row / G.n_ext;
+    float a = 0.0f;
+    for (int t = G.T - 1; t >= 0; --t) {
+        const size_t at = (size_t)t * (size_t)G.n_rows + (size_t)row, ae = (size_t)t * (size_t)G.n_envs + (size_t)env;
+        const float v = G.value[at];
+        a = ftgp_gae_step(G.gamma, G.gl, G.reward[at], v, G.next_value[at], G.terminated[ae] != 0, G.truncated[ae] != 0, t == G.T - 1, a);
+        G.advantage[at] = a;
+        G.ret[at] = ftgp_gae_return(a, v);
     }
 }

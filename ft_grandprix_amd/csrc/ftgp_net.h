@@ -85,6 +85,18 @@ FTGP_HD bool ftgp_net_finite(float a) { return a - a == 0.0f; }
 // the guard: both components, or neither
 FTGP_HD float ftgp_net_guarded(float a, bool both_finite) { return both_finite ? a : 0.0f; }
 
+// ---- collected values (include/ftgp.h "Collected rollouts with values"): the value element and one element step of the advantage scan
+// (tools/collect_values_check.cpp compiles these for the CPU; tests/collect_values_model.py restates the header's text)
+FTGP_HD float ftgp_net_value(float y, float scale, float offset) { return fmaf(y, scale, offset); }          // no guard: a diverged critic shows
+// the advantage at t from the one at t + 1 (a_next; not looked at where last, term or trunc); gl = gamma * lam, rounded once on the host
+FTGP_HD float ftgp_gae_step(float gamma, float gl, float reward, float value, float next_value, bool term, bool trunc, bool last, float a_next)
+{
+    const float nv = term ? 0.0f : next_value;
+    const float d = fmaf(gamma, nv, reward) - value;
+    return (last || term || trunc) ? d : fmaf(gl, a_next, d);
+}
+FTGP_HD float ftgp_gae_return(float advantage, float value) { return advantage + value; }
+
 // ---- shapes: what ftgp_set_net checks, and the sizes that follow from a description ----
 FTGP_HD int ftgp_net_inputs(const FtgpNetDesc* d) { return d->n_beams + (d->use_state ? FTGP_NET_STATE_INPUTS : 0); }
 // the frame entries behind them (ftgp_set_net_frame): none without the struct or with enabled == 0

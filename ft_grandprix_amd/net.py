@@ -132,6 +132,106 @@ def stack_params(specs) -> np.ndarray:
     return np.stack([s.flat_params() for s in specs])
 
 
+def _torch_layers(module, who: str):
+    """(layers, activation names) of an ``nn.Sequential(Linear, act, ..., Linear[, act])``: the module rules of ``from_torch``."""
+    import torch.nn as nn
+    if not isinstance(module, nn.Sequential):
+        raise TypeError(f"{who} takes an nn.Sequential of Linear / ReLU / Tanh / Identity, got {type(module).__name__}")
+    names = {nn.ReLU: "relu", nn.Tanh: "tanh", nn.Identity: "identity"}
+    layers, acts = [], []
+    for i, m in enumerate(module):
+        if isinstance(m, nn.Linear):
+            if m.bias is None:
+                raise ValueError(f"module {i}: a Linear without bias is not supported (give it a zero bias)")
+            layers.append((m.weight.detach().cpu().numpy().astype(np.float32), m.bias.detach().cpu().numpy().astype(np.float32)))
+            acts.append("identity")
+        elif type(m) in names:
+            if not layers or acts[-1] != "identity":
+                raise ValueError(f"module {i}: {type(m).__name__} must follow a Linear, one activation per layer")
+            acts[-1] = names[type(m)]
+        else:
+            raise TypeError(f"module {i}: {type(m).__name__} is not supported: Linear, ReLU, Tanh and Identity only")
+    if not layers:
+        raise ValueError("the module has no Linear layer")
+    if len(set(acts[:-1])) > 1:
+        raise ValueError(f"every hidden layer must use the same activation, got {acts[:-1]}")
+    return layers, acts
+
+
+@dataclass
+class ValueSpec:
+    """Everything ``ftgp_set_value_net`` takes: the layers of a critic in torch's ``nn.Linear`` layout -- the first one as wide as the
+    input vector of the slot it is set on, the last one with a single output --, the two activations and the output map
+    ``v = y * out_scale + out_offset``."""
+    layers: list                      # [(W float32 [n_out, n_in], b float32 [n_out]), ...]
+    hidden_act: str = "tanh"
+    out_act: str = "identity"
+    out_scale: float = 1.0
+    out_offset: float = 0.0
+    _flat: np.ndarray = field(default=None, repr=False, compare=False)
+
+    def __post_init__(self):
+        self.layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in self.layers]
+        self.out_scale, self.out_offset = float(self.out_scale), float(self.out_offset)
+        _, self._flat = capi.value_desc(self.layers, **self.fields())         # every check that needs no handle
+
+    def fields(self) -> dict:
+        return dict(hidden_act=self.hidden_act, out_act=self.out_act, out_scale=self.out_scale, out_offset=self.out_offset)
+
+    @property
+    def n_in(self) -> int:
+        return int(self.layers[0][0].shape[1])
+
+    @property
+    def widths(self) -> tuple:
+        return (self.n_in,) + tuple(W.shape[0] for W, _ in self.layers)
+
+    def flat_params(self) -> np.ndarray:
+        """float32, ftgp_set_value_net's layout: per layer W[n_out][n_in], then b[n_out]."""
+        return self._flat.copy()
+
+    @property
+    def param_count(self) -> int:
+        return int(self._flat.size)
+
+    def with_params(self, flat) -> "ValueSpec":
+        """A spec of the same shape and fields with the parameters of one flat float32 row in ``flat_params``' layout."""
+        flat = np.asarray(flat.detach().cpu().numpy() if hasattr(flat, "detach") else flat)
+        if flat.dtype != np.float32 or flat.shape != (self.param_count,):
+            raise ValueError(f"flat: float32 [{self.param_count}], got {flat.dtype} {flat.shape}")
+        layers, o = [], 0
+        for W, b in self.layers:
+            layers.append((flat[o:o + W.size].reshape(W.shape), flat[o + W.size:o + W.size + b.size]))
+            o += W.size + b.size
+        return ValueSpec(layers, **self.fields())
+
+    def save(self, path):
+        arrays = {}
+        for l, (W, b) in enumerate(self.layers):
+            arrays[f"W{l}"], arrays[f"b{l}"] = W, b
+        np.savez(path, value_net=1, n_layers=len(self.layers), hidden_act=self.hidden_act, out_act=self.out_act,
+                 out_scale=np.float32(self.out_scale), out_offset=np.float32(self.out_offset), **arrays)
+
+    @staticmethod
+    def load(path) -> "ValueSpec":
+        with np.load(path, allow_pickle=False) as z:
+            if "value_net" not in z.files:
+                raise ValueError(f"{path}: not a value net's file (ValueSpec.save)")
+            layers = [(z[f"W{l}"], z[f"b{l}"]) for l in range(int(z["n_layers"]))]
+            return ValueSpec(layers, hidden_act=str(z["hidden_act"]), out_act=str(z["out_act"]), out_scale=float(z["out_scale"]),
+                             out_offset=float(z["out_offset"]))
+
+
+def value_from_torch(module, out_scale=1.0, out_offset=0.0) -> ValueSpec:
+    """Freeze a critic ``nn.Sequential(Linear, act, ..., Linear[, act])`` under ``from_torch``'s module rules; the last Linear must have
+    one output."""
+    layers, acts = _torch_layers(module, "value_from_torch")
+    if layers[-1][0].shape[0] != 1:
+        raise ValueError(f"the last Linear of a value net has exactly 1 output, got {layers[-1][0].shape[0]}")
+    hidden = set(acts[:-1])
+    return ValueSpec(layers, hidden_act=hidden.pop() if hidden else "tanh", out_act=acts[-1], out_scale=out_scale, out_offset=out_offset)
+
+
 def from_torch(module, **input_fields) -> NetSpec:
     """Freeze ``nn.Sequential(Linear, act, Linear, act, ..., Linear[, act])`` with act in ReLU / Tanh / Identity.  Every hidden layer
     must use the same activation; a Linear without one behind it has the identity.  ``input_fields``: pool, max_range, beam_first,

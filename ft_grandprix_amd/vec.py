@@ -80,11 +80,15 @@ class Rollout:
     ``inputs`` float32 [T, n_envs, n_agents, n_in] what the network saw, ``mean`` and ``action`` [T, n_envs, n_agents, 2] what it
     proposed and what was applied, ``reward`` [T, n_envs, n_agents], ``terminated`` / ``truncated`` bool [T, n_envs],
     ``next_inputs`` as ``inputs`` (the state after decision t's steps, before any reset; None unless asked for) and ``noise`` the
-    draws that were used (None without exploration)."""
+    draws that were used (None without exploration).  With ``collect(values=True)``: ``value`` and ``next_value`` float32
+    [T, n_envs, n_agents], the slot's value net at what ``inputs`` and ``next_inputs`` hold (``next_value`` whether or not
+    ``next_inputs`` was recorded), and ``advantage`` / ``returns`` of the advantage scan; None otherwise."""
 
-    def __init__(self, inputs, mean, action, reward, terminated, truncated, next_inputs=None, noise=None):
+    def __init__(self, inputs, mean, action, reward, terminated, truncated, next_inputs=None, noise=None, *, value=None, next_value=None,
+                 advantage=None, returns=None):
         self.inputs, self.mean, self.action, self.reward = inputs, mean, action, reward
         self.terminated, self.truncated, self.next_inputs, self.noise = terminated, truncated, next_inputs, noise
+        self.value, self.next_value, self.advantage, self.returns = value, next_value, advantage, returns
 
 
 class DeviceVecEnv:
@@ -328,6 +332,7 @@ class DeviceVecEnv:
             self.env.set_spawn_rule(True, **self.start_rule)
         self._nets = {}                              # slot -> (shape key, the device tensor of the parameters last handed over)
         self._pops = {}                              # slot -> (n_members, the device tensors last handed over): slots with a population
+        self._vnets = {}                             # slot -> (widths of its value net, the device tensor of the parameters last handed over)
         for slot, spec in net_specs.items():
             self.set_net(slot, spec)
         z = dict(device=self.device)
@@ -457,6 +462,7 @@ class DeviceVecEnv:
             self.env.set_net(slot, None)
             self._nets.pop(slot, None)
             self._pops.pop(slot, None)
+            self._value_nets().pop(slot, None)
             return
         spec = self._net_spec(spec_or_module, self.n_rays, **input_fields)
         key = spec.shape_key()
@@ -466,9 +472,89 @@ class DeviceVecEnv:
                 self.env.set_net_device(slot, params.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
             self._nets[slot] = (key, params)         # (kept until the next one: the library reads it in stream order)
             return
-        self.env.set_net(slot, spec.layers, **spec.input_fields())      # (defines the slot without a population)
+        self.env.set_net(slot, spec.layers, **spec.input_fields())      # (defines the slot without a population and without a value net)
         self._nets[slot] = (key, None)
         self._pops.pop(slot, None)
+        self._value_nets().pop(slot, None)
+
+    # -- value nets (include/ftgp.h: ftgp_set_value_net)
+    def _value_nets(self) -> dict:
+        """slot -> (widths of the value net, the device tensor of the parameters last handed over)"""
+        if not hasattr(self, "_vnets"):
+            self._vnets = {}
+        return self._vnets
+
+    def set_value_net(self, slot, spec_or_module, **fields):
+        """Give defined slot ``slot`` a value net (a critic over the slot's own input vector): a ``net.ValueSpec`` or an
+        ``nn.Sequential`` (``net.value_from_torch``; ``fields``: out_scale, out_offset).  ``None`` clears it.  Synchronises; the
+        per-iteration refresh is ``set_value_params``.  ``set_net`` with another shape clears the value net."""
+        from . import net
+        slot = self._check_net_slot(slot)
+        if spec_or_module is None:
+            self.env.set_value_net(slot, None)
+            self._value_nets().pop(slot, None)
+            return
+        if slot not in self._nets:
+            raise ValueError(f"network slot {slot} is not defined: set_net first")
+        spec = spec_or_module if isinstance(spec_or_module, net.ValueSpec) else net.value_from_torch(spec_or_module, **fields)
+        if isinstance(spec_or_module, net.ValueSpec) and fields:
+            raise TypeError(f"a ValueSpec carries its own fields, got {sorted(fields)} as well")
+        n_in = self._nets[slot][0][0][0]
+        if spec.n_in != n_in:
+            raise ValueError(f"the value net reads slot {slot}'s {n_in} inputs, its first layer has {spec.n_in} columns")
+        self.env.set_value_net(slot, spec.layers, **spec.fields())
+        self._value_nets()[slot] = (spec.widths, None)
+
+    def set_value_params(self, slot, params):
+        """New parameters for a slot's value net from a float32 tensor on the env's device in the flat layout
+        (``ValueSpec.flat_params``), on torch's current stream, without a synchronisation: once per learner iteration."""
+        slot = self._check_net_slot(slot)
+        if slot not in self._value_nets():
+            raise ValueError(f"network slot {slot} has no value net: set_value_net first")
+        widths = self._vnets[slot][0]
+        count = sum(widths[l + 1] * widths[l] + widths[l + 1] for l in range(len(widths) - 1))
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() \
+                or tuple(params.shape) != (count,):
+            raise ValueError(f"params: a contiguous float32 tensor [{count}] on {self.device}")
+        self.env.set_value_net_device(slot, params.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        self._vnets[slot] = (widths, params)           # (kept until the next one: the library reads it in stream order)
+
+    def value_net(self, slot):
+        """The slot's value net as the library holds it (synchronises): a ``net.ValueSpec``."""
+        from . import net
+        slot = self._check_net_slot(slot)
+        d, layers = self.env.get_value_net(slot)
+        names = {v: k for k, v in capi.ACT_BY_NAME.items()}
+        return net.ValueSpec(layers, hidden_act=names[d.hidden_act], out_act=names[d.out_act], out_scale=d.out_scale, out_offset=d.out_offset)
+
+    def gae(self, reward, value, next_value, terminated, truncated, gamma=0.99, lam=0.95, out=None):
+        """(advantage, returns) float32 [T, n_envs, n_agents] of the advantage scan (ftgp_gae_device) over tensors shaped as a
+        ``Rollout``'s, on torch's current stream; only enqueues.  ``out``: a pair of tensors to write into.  After rescaling the
+        rewards of a rollout, ``gae(scaled, r.value, r.next_value, r.terminated, r.truncated, ...)`` gives the advantages again."""
+        g, l = capi.check_discounts(gamma, lam)
+        if not isinstance(reward, torch.Tensor) or reward.dim() != 3 or tuple(reward.shape[1:]) != (self.n_envs, self.n_agents) or reward.shape[0] < 1:
+            raise ValueError(f"reward: a float32 tensor [T, {self.n_envs}, {self.n_agents}] on {self.device}")
+        T = int(reward.shape[0])
+        lead = (T, self.n_envs, self.n_agents)
+        def check(name, t, shape, dtype):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous {dtype} tensor {shape} on {self.device}")
+        for name, t in (("reward", reward), ("value", value), ("next_value", next_value)):
+            check(name, t, lead, torch.float32)
+        for name, t in (("terminated", terminated), ("truncated", truncated)):
+            check(name, t, (T, self.n_envs), torch.bool)
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise ValueError("out: a pair (advantage, returns) of tensors")
+            check("out[0]", out[0], lead, torch.float32)
+            check("out[1]", out[1], lead, torch.float32)
+        with self._device_guard():
+            adv, ret = out if out is not None else (torch.empty(lead, dtype=torch.float32, device=self.device),
+                                                    torch.empty(lead, dtype=torch.float32, device=self.device))
+            self._gae_keep = (reward, value, next_value, terminated, truncated, adv, ret)
+            self.env.gae_device(T, reward.data_ptr(), value.data_ptr(), next_value.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                                adv.data_ptr(), ret.data_ptr(), gamma=g, lam=l, stream=self._stream())
+        return adv, ret
 
     def set_net_params(self, slot, params):
         """New parameters for a defined slot from a float32 tensor on the env's device in ftgp_set_net's flat layout (``NetSpec.flat_params``),
@@ -599,7 +685,8 @@ class DeviceVecEnv:
         self._draw_dynamics(self._dyn_mask)
 
     # -- collected rollouts (include/ftgp.h: ftgp_collect_device)
-    def collect(self, n_decisions, slot=0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e30, 1e30)), noise=None, next_inputs=False, out=None):
+    def collect(self, n_decisions, slot=0, std=(0.0, 0.0), clip=((-1e30, 1e30), (-1e30, 1e30)), noise=None, next_inputs=False, out=None, *,
+                values=False, gamma=0.99, lam=0.95):
         """``n_decisions`` = T decisions of network slot ``slot`` for every agent, in one call that only enqueues, on torch's current
         stream: a ``Rollout`` of what the network saw, proposed, what was applied and what came back (ftgp_collect_device).
         action = clip(mean + std * noise) per component, ``clip`` = ((lo, hi) of the speed, (lo, hi) of the steering angle).  ``noise``:
@@ -608,11 +695,19 @@ class DeviceVecEnv:
         ``Rollout`` of an earlier call with the same T, slot and ``next_inputs``, whose tensors are written again (with ``noise=True``
         its noise tensor too: drawn into in place).  With
         ``randomize_dynamics`` the T row sets are drawn up front and an env takes decision t's rows when its episode ends there.
-        ``obs`` and the optional rows are evaluated again at the state the call leaves, so ``step`` and ``collect`` may alternate."""
+        ``obs`` and the optional rows are evaluated again at the state the call leaves, so ``step`` and ``collect`` may alternate.
+        ``values=True`` (ftgp_collect_values_device; the slot needs a value net, ``set_value_net``): the ``Rollout`` also holds
+        ``value``, ``next_value`` -- the bootstrap of a truncation, with or without ``next_inputs`` -- and ``advantage`` / ``returns`` of
+        the advantage scan with ``gamma`` and ``lam``."""
         c = capi.collect_args(n_decisions, slot, std, clip)
         T, slot = c.n_decisions, c.slot
         if slot not in self._nets:
             raise ValueError(f"network slot {slot} is not defined: set_net first")
+        v = None
+        if values:
+            v = capi.collect_values_args(gamma, lam)
+            if slot not in self._value_nets():
+                raise ValueError(f"network slot {slot} has no value net: set_value_net first")
         n_in = self._nets[slot][0][0][0]
         lead = (T, self.n_envs, self.n_agents)
         if noise is not None and noise is not True:
@@ -623,6 +718,8 @@ class DeviceVecEnv:
                       truncated=(T, self.n_envs))
         if next_inputs:
             shapes["next_inputs"] = lead + (n_in,)
+        if values:
+            shapes.update(value=lead, next_value=lead, advantage=lead, returns=lead)
         if out is not None:
             if not isinstance(out, Rollout):
                 raise ValueError("out: a Rollout of an earlier collect")
@@ -630,13 +727,15 @@ class DeviceVecEnv:
                 t = getattr(out, name)
                 want = torch.bool if name in ("terminated", "truncated") else torch.float32
                 if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != want or t.device != self.device or not t.is_contiguous():
-                    raise ValueError(f"out.{name}: a contiguous {want} tensor {shape} on {self.device} (same T, slot and next_inputs)")
+                    raise ValueError(f"out.{name}: a contiguous {want} tensor {shape} on {self.device} (same T, slot, next_inputs and values)")
         with self._device_guard():
             if out is None:
                 out = Rollout(**{name: torch.zeros(shape, dtype=torch.bool if name in ("terminated", "truncated") else torch.float32,
                                                    device=self.device) for name, shape in shapes.items()})
             if not next_inputs:
                 out.next_inputs = None
+            if not values:
+                out.value = out.next_value = out.advantage = out.returns = None
             if noise is True:                            # drawn into the tensor an earlier call left in `out`, if it fits
                 kept = out.noise
                 fits = isinstance(kept, torch.Tensor) and tuple(kept.shape) == lead + (2,) and kept.dtype == torch.float32 and \
@@ -660,7 +759,11 @@ class DeviceVecEnv:
             c.next_inputs = out.next_inputs.data_ptr() if next_inputs else None
             c.reset_dynamics = None if rows is None else rows.data_ptr()
             self._collect_keep = (out, noise, rows)      # (the library reads and writes them in stream order)
-            rc = self.env.lib.fn("collect_device")(self.env.h, ctypes.byref(c))
+            if v is not None:
+                v.value, v.next_value, v.advantage, v.ret = out.value.data_ptr(), out.next_value.data_ptr(), out.advantage.data_ptr(), out.returns.data_ptr()
+                rc = self.env.lib.fn("collect_values_device")(self.env.h, ctypes.byref(c), ctypes.byref(v))
+            else:
+                rc = self.env.lib.fn("collect_device")(self.env.h, ctypes.byref(c))
             if rc:
                 self.env.lib.check(rc)
             if rows is not None:                         # the mirror: the rows of the last decision at which an env ended, if any

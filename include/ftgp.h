@@ -959,6 +959,88 @@ typedef struct FtgpCollect {
 } FtgpCollect;
 int ftgp_collect_device(FtgpEnv *env, const FtgpCollect *c);
 
+/* ---- Collected rollouts with values: a value net per slot, bootstrap values and advantages (no reference counterpart) ------------------
+ * What an actor-critic learner needs next to a collected rollout, without a pass through the caller's framework: the critic's value at
+ * every decision, its value at the state the decision led to (before any reset: the bootstrap of a truncation), and the advantages
+ * and returns of generalised advantage estimation.
+ *
+ * Everything here is binary32 with one rounding per written operation; fmaf is the fused multiply-add with one rounding; nothing else is
+ * contracted.  Comparisons with a NaN are false.
+ *
+ * The value net of slot s.  A defined network slot may carry one value net.  It reads the slot's own input vector x -- beams, state,
+ * frame and rival entries exactly as the slot defines them, at the slot's true n_in -- and its layers are the "Layers" text of "Network
+ * drivers" verbatim: acc = b[j], then one fmaf per k ascending, the same three activations and the same TANH; hidden widths
+ * 1 .. FTGP_NET_MAX_HIDDEN, the last width exactly 1.  With y the single output of the last layer,
+ *     v = fmaf(y, out_scale, out_offset)
+ * and there is no guard: a diverged critic shows as a NaN or an infinity in the record.  Parameters: torch's nn.Linear layout in one
+ * flat buffer, as ftgp_set_net takes them (the first layer has n_in columns); the count is the sum over the layers of n_out*n_in + n_out.
+ * A value net has ONE parameter set: on a slot with a population (ftgp_set_net_population) every env uses that one set, whatever its
+ * member; per-member critics are not provided.
+ * The value net is evaluated by ftgp_collect_values_device alone -- never by the step kernel, ftgp_rollout or ftgp_policy_eval --, and
+ * launches that name no value net run the kernels they ran before there was one, with the arguments they got.
+ *
+ * ftgp_set_value_net (host buffers; may synchronise) gives defined slot `slot` a value net or replaces it; desc = NULL clears it.
+ * Everything is checked before anything changes and a refused call leaves the slot as it was.  FTGP_ERR_ARG names the field: a slot
+ * outside 0 .. 3; n_layers outside 1 .. FTGP_NET_MAX_LAYERS; a hidden width outside 1 .. FTGP_NET_MAX_HIDDEN, the last width != 1, a
+ * width behind the last layer != 0; an unknown activation; out_scale or out_offset not finite; reserved != 0; params = NULL.
+ * FTGP_ERR_STATE for a slot that is not defined.
+ * ftgp_set_value_net_device replaces the parameters of a value net that is there, from device memory on the handle's device in the
+ * same layout; it only enqueues and never synchronises, ordered on `stream` exactly as ftgp_set_net_device (the handle's stream waits
+ * for `stream`, and `stream` for the work): a critic changes at every iteration of its learner.  A host pointer or a buffer too small
+ * is FTGP_ERR_ARG before anything is enqueued; a slot without a value net is FTGP_ERR_STATE.
+ * ftgp_get_value_net (host, synchronous) mirrors ftgp_get_net: the description and the parameters in force, in the caller's layout;
+ * either pointer may be NULL; FTGP_ERR_STATE for a slot without a value net.
+ * With the other entries: ftgp_set_net, ftgp_set_net_frame and ftgp_set_net_rivals on a slot clear its value net (the input width may
+ * change).  ftgp_set_net_device, ftgp_set_net_population and its device form, ftgp_reset, auto-reset, the spawn rule, the dynamics
+ * table, the ftgp_device_io_* setters and the env-state calls leave it alone. */
+typedef struct FtgpValueDesc {
+    int32_t n_layers;                       /* 1 .. FTGP_NET_MAX_LAYERS */
+    int32_t width[FTGP_NET_MAX_LAYERS];     /* hidden 1 .. FTGP_NET_MAX_HIDDEN, width[n_layers - 1] exactly 1, the rest 0 */
+    int32_t hidden_act, out_act;            /* FTGP_ACT_* */
+    float   out_scale, out_offset;          /* finite */
+    int32_t reserved;                       /* 0 */
+} FtgpValueDesc;
+int ftgp_set_value_net(FtgpEnv *env, int slot, const FtgpValueDesc *desc, const float *params);
+int ftgp_set_value_net_device(FtgpEnv *env, void *stream, int slot, const float *params);
+int ftgp_get_value_net(FtgpEnv *env, int slot, FtgpValueDesc *desc_out, float *params_out);
+
+/* ftgp_collect_values_device: ftgp_collect_device with the slot's value net evaluated along the way.  v == NULL is ftgp_collect_device
+ * to the letter.  Otherwise everything ftgp_collect_device documents holds unchanged -- every buffer of c and the handle afterwards are
+ * to the bit what ftgp_collect_device with the same c leaves -- and in addition, for decision t:
+ *   1'. value[t][e][i] = the slot's value net on step 1's x, for every external car, finished or not: a finished car's policy is not
+ *       looked at, its value is.
+ *   3'. next_value[t][e][i] = the value net on step 3's x -- the state after the decision's physics steps and before any reset --
+ *       whether or not c->next_inputs is given: the bootstrap of a truncation needs no next_inputs.
+ *   5.  If advantage is given, the advantage scan below runs after decision T-1 over the call's own reward, value, next_value,
+ *       terminated and truncated, and writes advantage and ret.
+ * Ordering and buffers as ftgp_collect_device.  Errors, all before anything is enqueued: those of ftgp_collect_device for c;
+ * FTGP_ERR_STATE for a slot without a value net; FTGP_ERR_ARG, naming the field, for gamma or lam not finite or outside [0, 1], for
+ * reserved != 0, for one of advantage and ret given without the other, and for a buffer that is NULL (the optional pair may be), not
+ * device memory on the handle's device or too small.
+ *
+ * The advantage scan (ftgp_gae_device, and step 5 above).  Rows are the n_envs * n_ext external cars of a device-io handle; reward,
+ * value, next_value, advantage and ret are float32[T][n_envs][n_ext], terminated and truncated uint8[T][n_envs], T = n_decisions.
+ * gl = gamma * lam, rounded once on the host.  For each row, for t = T-1 down to 0, with term and trunc the bytes of the row's env at t:
+ *     nv = term ? 0.0f : next_value[t]
+ *     d  = fmaf(gamma, nv, reward[t]) - value[t]
+ *     A  = (t == T-1 || term || trunc) ? d : fmaf(gl, A_next, d)
+ *     advantage[t] = A;  ret[t] = A + value[t];  A_next = A
+ * Non-finite values pass through as the arithmetic gives them.  ftgp_gae_device only enqueues, ordered on `stream` like
+ * ftgp_state_device: a learner that rescales or reshapes rewards after collection recomputes its advantages with it.  FTGP_ERR_STATE
+ * before ftgp_device_io_config; FTGP_ERR_ARG, naming the field, for n_decisions < 1, gamma or lam not finite or outside [0, 1], and a
+ * buffer that is NULL, not device memory on the handle's device or too small. */
+typedef struct FtgpCollectValues {
+    float gamma, lam;            /* finite, in [0, 1] */
+    float *value;                /* float32[T][n_envs][n_ext] */
+    float *next_value;           /* float32[T][n_envs][n_ext] */
+    float *advantage, *ret;      /* optional, both or neither: float32[T][n_envs][n_ext] */
+    int32_t reserved[2];         /* 0 */
+} FtgpCollectValues;
+int ftgp_collect_values_device(FtgpEnv *env, const FtgpCollect *c, const FtgpCollectValues *v);
+int ftgp_gae_device(FtgpEnv *env, void *stream, int n_decisions, float gamma, float lam,
+                    const float *reward, const float *value, const float *next_value,
+                    const uint8_t *terminated, const uint8_t *truncated, float *advantage, float *ret);
+
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 
 /* float[n_cars][n_rays]; replaces data.sensordata[vehicle_state.sensors] (custom.py:1395; drive.py:81).
