@@ -1123,6 +1123,8 @@ int oracle_get_race_steps(OracleEnv *e, int64_t *out)
     for (int i = 0; i < e->n_cars; ++i) { out[2 * i] = e->cars[i].start; out[2 * i + 1] = e->cars[i].finished ? e->cars[i].finish_step : -1; }
     return 0;
 }
+/* ftgp_get_centre_dist2: distances[closest] (squared) as the progress block stored it last */
+int oracle_get_centre_dist2(OracleEnv *e, double *out) { for (int i = 0; i < e->n_cars; ++i) out[i] = e->cars[i].dist2; return 0; }
 
 int oracle_metrics_local(OracleEnv *e, double *out)
 {

@@ -236,33 +236,53 @@ def drive_g4_table(lib):
         assert not p[:, 5].any() and not p[:, 4].any(), (p[:, 5], p[:, 4])                          # never off-track, never finished
 
 
-def replay_progress_trace(lib, trace):
-    """Replay a G5 trace through a full env: set_pose + eval_progress at steps == s (K3 path incl. its own argmin)."""
+def replay_progress_trace(lib, trace, n_envs=1):
+    """Replay a G5 trace through a full env: set_pose + eval_progress at steps == 0, then set_pose + step(1) (K3 incl. its own argmin)
+    with the cars at rest and zero controls.  n_envs: so many envs, every one posed alike at the fixture's car count (more cars per
+    workgroup: the in-step search's other lane layout); the traced car of every env must give the fixture's rows.
+
+    Twice: on the `track` asset, where a wall or an env-mate nudges the traced car on a few steps before K3 sees it (the rows hold all
+    the same; its centre_dist2() must be the fixture's distances[closest], squared, wherever pose() says it stood still); and on a
+    wall-free field with the same centre-line and the env-mates parked far off it, where no car moves (asserted) and centre_dist2() must
+    be the fixture's at every step, bit for bit, off the track included."""
+    import dataclasses
     g = np.load(golden("g5_progress.npz"))
     t = load_track("track")
     np.testing.assert_array_equal(t.path, g["path"])
-    xy, ref = g[f"{trace}_xy"], g[f"{trace}_out"]
+    xy, ref, d2 = g[f"{trace}_xy"], g[f"{trace}_out"], g[f"{trace}_d2"]
     offset, target = [int(x) for x in g[f"{trace}_params"]]
     cars = offset // 2 - 5 + 1   # reference spawn: car i gets offset (i+5)*2 (custom.py:1112)
-    ci = cars - 1
-    with capi.Env(lib, t, n_envs=1, cars_per_env=cars, n_rays=8, lap_target=target) as e:
-        pose = e.pose()
-        pose[:, 7:] = 0.0
-        got = np.zeros((len(xy), 7), dtype=np.int64)
-        for s in range(len(xy)):
-            pose[ci, 0:2] = xy[s]
-            e.set_pose(pose)
-            if s == 0:
-                e.eval_progress()    # steps == 0
-            else:
-                e.step(1)            # cars at rest, zero ctrl: nothing moves; steps -> s; progress at xy[s]
-            p = e.progress()[ci]
-            cnt, times = e.lap_times()
-            got[s] = [p[0], p[1], p[7], cnt[ci], p[4], p[8], p[5]]
-        np.testing.assert_array_equal(e.steps(), [len(xy) - 1])
-        np.testing.assert_array_equal(got, ref)
-        n = int(ref[-1, 3])
-        np.testing.assert_allclose(times[ci, :n], g[f"{trace}_times"], rtol=0, atol=1e-15)
+    ci = np.arange(n_envs) * cars + cars - 1
+    for free in (False, True):
+        track = dataclasses.replace(open_field(200), path=t.path, name="track-path") if free else t
+        with capi.Env(lib, track, n_envs=n_envs, cars_per_env=cars, n_rays=8, lap_target=target) as e:
+            pose = e.pose()
+            pose[:, 7:] = 0.0
+            if free:
+                for k in range(cars - 1):                    # the env-mates: 15 units and more from the centre-line, 3 apart
+                    pose[k::cars, 0], pose[k::cars, 1] = 2.0 + 3.0 * k, -2.0
+            got = np.zeros((n_envs, len(xy), 7), dtype=np.int64)
+            got_d2, still = np.zeros((n_envs, len(xy))), np.zeros((n_envs, len(xy)), dtype=bool)
+            for s in range(len(xy)):
+                pose[ci, 0:2] = xy[s]
+                e.set_pose(pose)
+                if s == 0:
+                    e.eval_progress()    # steps == 0
+                else:
+                    e.step(1)            # steps -> s; progress at xy[s]
+                p = e.progress()[ci]
+                cnt, times = e.lap_times()
+                got[:, s] = np.stack([p[:, 0], p[:, 1], p[:, 7], cnt[ci], p[:, 4], p[:, 8], p[:, 5]], axis=1)
+                got_d2[:, s] = e.centre_dist2()[ci]
+                still[:, s] = (e.pose()[ci, 0:2] == xy[s]).all(axis=1)
+            np.testing.assert_array_equal(e.steps(), [len(xy) - 1] * n_envs)
+            n = int(ref[-1, 3])
+            assert still.all() or not free, f"{trace}: a car moved on the wall-free field, steps {np.nonzero(~still.all(axis=0))[0]}"
+            assert still.mean() > 0.5, still.mean()             # (the `track` leg: a nudged step is the exception)
+            for k in range(n_envs):
+                np.testing.assert_array_equal(got[k], ref, err_msg=f"env {k}")
+                np.testing.assert_array_equal(got_d2[k][still[k]], d2[still[k]], err_msg=f"env {k}: centre_dist2 against the fixture's distances[closest]")
+                np.testing.assert_allclose(times[ci[k], :n], g[f"{trace}_times"], rtol=0, atol=1e-15)
 
 
 def laps_by_teleport(lib, n_laps=37):
