@@ -112,6 +112,7 @@ API_SYMBOLS = (
     "collect_device",
     "set_net_population", "set_net_population_device", "get_net_population",
     "set_value_net", "set_value_net_device", "get_value_net", "collect_values_device", "gae_device",
+    "train_begin", "train_end", "train_grad_device", "train_adam_device", "train_get",
 )
 
 
@@ -295,6 +296,79 @@ def collect_values_args(gamma=0.99, lam=0.95, value: int = 0, next_value: int = 
     for name, a in (("value", value), ("next_value", next_value), ("advantage", advantage), ("ret", ret)):
         setattr(v, name, a or None)
     return v
+
+
+TRAIN_STATS = 8
+TRAIN_GRAD, TRAIN_M, TRAIN_V, TRAIN_RAW_GRAD, TRAIN_RAW_PARAMS = 0, 1, 2, 3, 4
+
+
+class FtgpTrainDesc(C.Structure):
+    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("reserved", C.c_int32)]
+
+
+class FtgpTrainBatch(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("slot", C.c_int32), ("n_rows", C.c_int32), ("n_batch", C.c_int32), ("first_row", C.c_int32),
+                ("index", C.c_void_p), ("inputs", C.c_void_p), ("mean", C.c_void_p), ("noise", C.c_void_p), ("advantage", C.c_void_p),
+                ("ret", C.c_void_p), ("weight", C.c_void_p), ("std", C.c_float * 2), ("clip", C.c_float), ("value_coef", C.c_float),
+                ("stats", C.c_void_p), ("new_mean", C.c_void_p), ("new_value", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+def _f32(name, v, what, ok):
+    try:
+        f = float(np.float32(v))
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: {what}, got {v!r}") from None
+    if isinstance(v, bool) or not (np.isfinite(f) and ok(f)):
+        raise ValueError(f"{name}: {what}, got {v!r}")
+    return f
+
+
+def _train_slot(slot):
+    if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < MAX_NETS:
+        raise ValueError(f"network slot: 0 .. {MAX_NETS - 1}, got {slot!r}")
+    return int(slot)
+
+
+def train_desc(betas=(0.9, 0.999), eps=1e-8) -> "FtgpTrainDesc":
+    """The FtgpTrainDesc of ftgp_train_begin with its checks (ValueError): two betas, finite and in [0, 1); eps finite and > 0."""
+    try:
+        b1, b2 = betas
+    except (TypeError, ValueError):
+        raise ValueError(f"betas: two numbers in [0, 1), got {betas!r}") from None
+    return FtgpTrainDesc(beta1=_f32("beta1", b1, "finite and in [0, 1)", lambda f: 0.0 <= f < 1.0),
+                         beta2=_f32("beta2", b2, "finite and in [0, 1)", lambda f: 0.0 <= f < 1.0),
+                         eps=_f32("eps", eps, "finite and > 0", lambda f: f > 0.0))
+
+
+def train_batch(n_rows, n_batch, *, slot=0, first_row=0, index: int = 0, inputs: int = 0, mean: int = 0, noise: int = 0, advantage: int = 0,
+                ret: int = 0, weight: int = 0, std=(1.0, 1.0), clip=0.2, value_coef=0.5, stats: int = 0, new_mean: int = 0, new_value: int = 0,
+                stream: int = 0) -> "FtgpTrainBatch":
+    """An FtgpTrainBatch on integer device addresses (0 = NULL) with every check of ftgp_train_grad_device that needs no handle
+    (ValueError): n_rows and n_batch >= 1, the range of first_row (without an index), std finite and > 0, clip and value_coef finite and
+    >= 0, the required buffers given."""
+    for name, v in (("n_rows", n_rows), ("n_batch", n_batch)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) < 2 ** 31:
+            raise ValueError(f"{name}: an integer >= 1, got {v!r}")
+    if isinstance(first_row, bool) or not isinstance(first_row, (int, np.integer)):
+        raise ValueError(f"first_row: an integer, got {first_row!r}")
+    if not index and not 0 <= int(first_row) <= int(n_rows) - int(n_batch):
+        raise ValueError(f"first_row = {first_row} with n_batch = {n_batch} leaves the {n_rows} rows")
+    try:
+        s0, s1 = std
+    except (TypeError, ValueError):
+        raise ValueError(f"std: two finite numbers > 0, got {std!r}") from None
+    b = FtgpTrainBatch(slot=_train_slot(slot), n_rows=int(n_rows), n_batch=int(n_batch), first_row=int(first_row) if not index else 0,
+                       clip=_f32("clip", clip, "finite and >= 0", lambda f: f >= 0.0),
+                       value_coef=_f32("value_coef", value_coef, "finite and >= 0", lambda f: f >= 0.0))
+    b.std[0] = _f32("std[0]", s0, "finite and > 0", lambda f: f > 0.0)
+    b.std[1] = _f32("std[1]", s1, "finite and > 0", lambda f: f > 0.0)
+    for name, a in (("inputs", inputs), ("mean", mean), ("advantage", advantage), ("ret", ret)):
+        if not a:
+            raise ValueError(f"{name}: a device address, got {a!r}")
+    for name, a in (("stream", stream), ("index", index), ("inputs", inputs), ("mean", mean), ("noise", noise), ("advantage", advantage),
+                    ("ret", ret), ("weight", weight), ("stats", stats), ("new_mean", new_mean), ("new_value", new_value)):
+        setattr(b, name, a or None)
+    return b
 
 
 def net_frame(frame=False, lookahead=0, lookahead_stride=1) -> "FtgpNetFrame":
@@ -537,6 +611,11 @@ class CLib:
             "get_value_net": (i32, [vp, i32, C.POINTER(FtgpValueDesc), dp]),
             "collect_values_device": (i32, [vp, C.POINTER(FtgpCollect), C.POINTER(FtgpCollectValues)]),
             "gae_device": (i32, [vp, vp, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp]),
+            "train_begin": (i32, [vp, i32, C.POINTER(FtgpTrainDesc)]),
+            "train_end": (i32, [vp, i32]),
+            "train_grad_device": (i32, [vp, C.POINTER(FtgpTrainBatch)]),
+            "train_adam_device": (i32, [vp, vp, i32, C.c_float]),
+            "train_get": (i32, [vp, i32, i32, dp, dp, C.POINTER(C.c_int64)]),
             "create_tracks": (i32, [C.POINTER(FtgpConfig), C.POINTER(FtgpTrack), dp, i32, C.POINTER(vp)]),
             "get_track_distance_field": (i32, [vp, i32, dp]),
         }
@@ -1004,6 +1083,57 @@ class Env:
         g, l = check_discounts(gamma, lam)
         self._call("gae_device", stream or None, int(n_decisions), g, l, reward or None, value or None, next_value or None,
                    terminated or None, truncated or None, advantage or None, ret or None)
+
+    # -- training on the device (include/ftgp.h: ftgp_train_begin, ftgp_train_grad_device, ftgp_train_adam_device)
+    def train_begin(self, slot: int = 0, betas=(0.9, 0.999), eps=1e-8):
+        """ftgp_train_begin: a trainer for defined slot ``slot`` (it needs a value net and no population): zeroed gradient and moments, t = 0."""
+        d = train_desc(betas, eps)
+        self._call("train_begin", _train_slot(slot), C.byref(d))
+
+    def train_end(self, slot: int = 0):
+        self._call("train_end", _train_slot(slot))
+
+    def train_grad_device(self, batch: "FtgpTrainBatch"):
+        """ftgp_train_grad_device on a ``train_batch``: the PPO gradient of the batch rows into the trainer's gradient; only enqueues."""
+        self._call("train_grad_device", C.byref(batch))
+
+    def train_adam_device(self, slot: int = 0, lr=3e-4, stream: int = 0):
+        """ftgp_train_adam_device: one Adam step on the slot's policy and value parameters in place; only enqueues."""
+        self._call("train_adam_device", stream or None, _train_slot(slot), _f32("lr", lr, "finite and >= 0", lambda f: f >= 0.0))
+
+    def train_get(self, slot: int = 0, what: int = TRAIN_GRAD):
+        """(policy float32 [count], value float32 [count], t): the gradient (TRAIN_GRAD) or a moment (TRAIN_M, TRAIN_V) of both nets in
+        ftgp_get_net's flat layout, and the Adam steps taken (synchronous)."""
+        slot = _train_slot(slot)
+        vd = FtgpValueDesc()
+        self._call("get_value_net", slot, C.byref(vd), None)
+        pol = np.empty(self._net_count(slot), dtype=np.float32)
+        val = np.empty(value_param_count(vd, self._net_n_in(slot)), dtype=np.float32)
+        t = C.c_int64(0)
+        self._call("train_get", slot, int(what), _ptr(pol), _ptr(val), C.byref(t))
+        return pol, val, int(t.value)
+
+    def train_get_raw(self, slot: int = 0, what: int = TRAIN_RAW_GRAD):
+        """(policy, value): per net a list of (Wt float32 [n_in, ld], b float32 [ld]) per layer -- the gradient (TRAIN_RAW_GRAD) or the
+        parameters in force (TRAIN_RAW_PARAMS) as they lie in device memory, ld = n_out rounded up to 64: a debug read for tests, which
+        look at the padding (synchronous)."""
+        slot = _train_slot(slot)
+        d, vd = FtgpNetDesc(), FtgpValueDesc()
+        self._call("get_net", slot, C.byref(d), None)
+        self._call("get_value_net", slot, C.byref(vd), None)
+        n_in = self._net_n_in(slot)
+        out = []
+        shapes = [[n_in] + list(x.width[:x.n_layers]) for x in (d, vd)]
+        bufs = [np.full(sum((i + 1) * ((o + 63) // 64 * 64) for i, o in zip(w[:-1], w[1:])), np.nan, dtype=np.float32) for w in shapes]
+        self._call("train_get", slot, int(what), _ptr(bufs[0]), _ptr(bufs[1]), None)
+        for w, buf in zip(shapes, bufs):
+            layers, at = [], 0
+            for i, o in zip(w[:-1], w[1:]):
+                ld = (o + 63) // 64 * 64
+                layers.append((buf[at:at + i * ld].reshape(i, ld), buf[at + i * ld:at + (i + 1) * ld]))
+                at += (i + 1) * ld
+            out.append(layers)
+        return tuple(out)
 
     # -- env states on the device (include/ftgp.h: ftgp_save_envs_device)
     def env_state_bytes(self) -> int:

@@ -213,6 +213,17 @@ struct FtgpEnv {
     NetDev vnets[FTGP_MAX_NETS] = {}; // their host mirror (defined = 0: none)
     FtgpValueDesc vnet_desc[FTGP_MAX_NETS] = {};  // the descriptions as the caller gave them (ftgp_get_value_net)
     DevBuf<float> d_vnet_params[FTGP_MAX_NETS];   // the parameters in the library's layout
+    // trainers (ftgp_train_begin): one per slot at most; nothing of it exists on a handle that never asked for one
+    struct Trainer {
+        bool on = false;
+        FtgpTrainDesc desc{};
+        int64_t t = 0;                    // Adam steps taken
+        int n[2] = { 0, 0 };              // n_floats of the policy and of the value net (the library's layout)
+        DevBuf<float> grad, m, v;         // [n[0] + n[1]] the policy's, then the value net's
+        DevBuf<float> part;               // [FTGP_TRAIN_MAX_WG][n[0] + n[1]] the workgroups' partial sums
+        DevBuf<float> stats;              // [FTGP_TRAIN_MAX_WG + 1][FTGP_TRAIN_STATS] the workgroups' partial stats, then the stats of the newest gradient
+        DevBuf<int32_t> sync;             // the gradient's non-finite flag, the reduce kernel's ticket
+    } trainers[FTGP_MAX_NETS];
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
     std::vector<uint64_t> track_fp;   // [n_tracks] the tracks' fingerprints (include/ftgp.h), folded at create
     DevBuf<EnvStateAux> d_state_aux;  // the handle's own dynamics record, the rejected counter, the fingerprints; allocated by the first save or load
@@ -2312,6 +2323,7 @@ int ftgp_set_net_rivals(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftg
     e->d_net_params[slot] = std::move(buf);                   // (the old buffer goes: nothing reads it any more)
     e->pop_members[slot] = 0; e->d_pop_params[slot] = DevBuf<float>(); e->d_pop_map[slot] = DevBuf<int32_t>();      // ... and a population with it
     e->vnets[slot] = NetDev{}; e->vnet_desc[slot] = FtgpValueDesc{}; e->d_vnet_params[slot] = DevBuf<float>();         // ... and a value net: the input width may have changed
+    e->trainers[slot] = FtgpEnv::Trainer{};                   // ... and a trainer (the stream is idle)
     return 0;
 }
 
@@ -2386,6 +2398,7 @@ int ftgp_set_net_population(FtgpEnv* e, int slot, int n_members, const float* pa
     HIP_TRY(hipMemcpy(e->d_nets.get() + slot, &N, sizeof N, hipMemcpyHostToDevice));
     e->nets[slot] = N;
     e->pop_members[slot] = n_members;
+    if (n_members > 0) e->trainers[slot] = FtgpEnv::Trainer{};      // a trainer steps the slot's single set: it ends with it
     e->d_pop_params[slot] = std::move(buf);                   // (the old buffers go: nothing reads them any more)
     e->d_pop_map[slot] = std::move(map);
     return 0;
@@ -2531,6 +2544,7 @@ int ftgp_set_value_net(FtgpEnv* e, int slot, const FtgpValueDesc* desc, const fl
     e->vnets[slot] = N;
     e->vnet_desc[slot] = desc ? *desc : FtgpValueDesc{};
     e->d_vnet_params[slot] = std::move(buf);                  // (the old buffer goes: nothing reads it any more)
+    e->trainers[slot] = FtgpEnv::Trainer{};                   // a trainer ends with the value net it stepped
     return 0;
 }
 
@@ -2565,6 +2579,186 @@ int ftgp_get_value_net(FtgpEnv* e, int slot, FtgpValueDesc* desc_out, float* par
     HIP_TRY(hipMemcpyAsync(img.data(), e->d_vnet_params[slot].get(), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), params_out);
+    return 0;
+}
+
+// ---- training on the device (include/ftgp.h "Training on the device") ----
+static bool train_fraction(float b) { return std::isfinite(b) && b >= 0.0f && b < 1.0f; }
+
+int ftgp_train_begin(FtgpEnv* e, int slot, const FtgpTrainDesc* desc)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_begin: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!desc) return fail(FTGP_ERR_ARG, "ftgp_train_begin: desc is NULL%s");
+    if (!train_fraction(desc->beta1)) return fail(FTGP_ERR_ARG, "ftgp_train_begin: beta1 is not finite or outside [0, 1)%s");
+    if (!train_fraction(desc->beta2)) return fail(FTGP_ERR_ARG, "ftgp_train_begin: beta2 is not finite or outside [0, 1)%s");
+    if (!std::isfinite(desc->eps) || !(desc->eps > 0.0f)) return fail(FTGP_ERR_ARG, "ftgp_train_begin: eps is not finite or <= 0%s");
+    if (desc->reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_train_begin: reserved must be 0%s");
+    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d is not defined (ftgp_set_net)", slot);
+    if (!e->vnets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d has no value net (ftgp_set_value_net)", slot);
+    if (e->pop_members[slot]) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d carries a population of %d members", slot, e->pop_members[slot]);
+    if (e->trainers[slot].on) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d has a trainer already (ftgp_train_end)", slot);
+    HIP_TRY(hipSetDevice(e->device));
+    FtgpEnv::Trainer T;
+    T.desc = *desc;
+    T.n[0] = e->nets[slot].n_floats; T.n[1] = e->vnets[slot].n_floats;
+    const size_t total = (size_t)T.n[0] + (size_t)T.n[1];
+    HIP_TRY(dev_zeros(T.grad, sizeof(float) * total, e->stream.get()));
+    HIP_TRY(dev_zeros(T.m, sizeof(float) * total, e->stream.get()));
+    HIP_TRY(dev_zeros(T.v, sizeof(float) * total, e->stream.get()));
+    HIP_TRY(dev_zeros(T.part, sizeof(float) * total * FTGP_TRAIN_MAX_WG, e->stream.get()));
+    HIP_TRY(dev_zeros(T.stats, sizeof(float) * FTGP_TRAIN_STATS * (FTGP_TRAIN_MAX_WG + 1), e->stream.get()));
+    HIP_TRY(dev_zeros(T.sync, sizeof(int32_t) * 2, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    T.on = true;
+    e->trainers[slot] = std::move(T);
+    return 0;
+}
+
+int ftgp_train_end(FtgpEnv* e, int slot)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_end: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!e->trainers[slot].on) return failf(FTGP_ERR_STATE, "ftgp_train_end: network slot %d has no trainer (ftgp_train_begin)", slot);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is using the buffers while they go
+    e->trainers[slot] = FtgpEnv::Trainer{};
+    return 0;
+}
+
+// one of a slot's nets as the train kernels read it; x_off: where the layers' outputs sit in an LDS row (the input at 0)
+static TrainNet train_net(const NetDev& N, const float* params, int g_off)
+{
+    TrainNet t{};
+    t.n_layers = N.n_layers; t.hidden_act = N.hidden_act; t.out_act = N.out_act; t.n_floats = N.n_floats;
+    int x = 0;
+    for (int l = 0; l <= N.n_layers; ++l) {
+        t.width[l] = N.width[l]; t.x_off[l] = x; x += (N.width[l] + 3) & ~3;
+        if (l < N.n_layers) { t.w_off[l] = N.w_off[l]; t.b_off[l] = N.b_off[l]; }
+    }
+    for (int k = 0; k < 2; ++k) { t.out_scale[k] = N.out_scale[k]; t.out_offset[k] = N.out_offset[k]; }
+    t.params = params; t.g_off = g_off;
+    return t;
+}
+
+int ftgp_train_grad_device(FtgpEnv* e, const FtgpTrainBatch* b)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (!b) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: the batch is NULL%s");
+    if (b->slot < 0 || b->slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: slot = %d outside 0 .. %d", b->slot, FTGP_MAX_NETS - 1);
+    FtgpEnv::Trainer& R = e->trainers[b->slot];
+    if (!R.on) return failf(FTGP_ERR_STATE, "ftgp_train_grad_device: network slot %d has no trainer (ftgp_train_begin)", b->slot);
+    if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: reserved must be 0%s");
+    if (b->n_rows < 1) return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: n_rows = %d must be >= 1", b->n_rows);
+    if (b->n_batch < 1) return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: n_batch = %d must be >= 1", b->n_batch);
+    if (!b->index && (b->first_row < 0 || (int64_t)b->first_row + (int64_t)b->n_batch > (int64_t)b->n_rows))
+        return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: first_row = %d with n_batch = %d leaves the %d rows", b->first_row, b->n_batch, b->n_rows);
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(b->std[k]) || !(b->std[k] > 0.0f)) return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: std[%d] is not finite or <= 0", k);
+    if (!std::isfinite(b->clip) || b->clip < 0.0f) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: clip is not finite or < 0%s");
+    if (!std::isfinite(b->value_coef) || b->value_coef < 0.0f) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: value_coef is not finite or < 0%s");
+    HIP_TRY(hipSetDevice(e->device));
+    const NetDev& N = e->nets[b->slot]; const NetDev& V = e->vnets[b->slot];
+    const size_t rows = (size_t)b->n_rows, B = (size_t)b->n_batch, n_in = (size_t)N.width[0];
+    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_train_grad_device: %s", m.c_str()); return rc; };
+    auto checked = [&](const void* p, size_t bytes, const char* name) { return check_device_buffer(e, p, bytes, name) ? refused(FTGP_ERR_ARG) : 0; };
+    if (b->index) if (int rc = checked(b->index, sizeof(int32_t) * B, "index")) return rc;
+    if (int rc = checked(b->inputs, sizeof(float) * rows * n_in, "inputs")) return rc;
+    if (int rc = checked(b->mean, sizeof(float) * rows * 2, "mean")) return rc;
+    if (b->noise) if (int rc = checked(b->noise, sizeof(float) * rows * 2, "noise")) return rc;
+    if (int rc = checked(b->advantage, sizeof(float) * rows, "advantage")) return rc;
+    if (int rc = checked(b->ret, sizeof(float) * rows, "ret")) return rc;
+    if (b->weight) if (int rc = checked(b->weight, sizeof(float) * rows, "weight")) return rc;
+    if (b->stats) if (int rc = checked(b->stats, sizeof(float) * FTGP_TRAIN_STATS, "stats")) return rc;
+    if (b->new_mean) if (int rc = checked(b->new_mean, sizeof(float) * B * 2, "new_mean")) return rc;
+    if (b->new_value) if (int rc = checked(b->new_value, sizeof(float) * B, "new_value")) return rc;
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+
+    TrainArgs T{};
+    T.net[0] = train_net(N, e->d_net_params[b->slot].get(), 0);
+    T.net[1] = train_net(V, e->d_vnet_params[b->slot].get(), R.n[0]);
+    int act_floats = 0, ld_max = FTGP_WAVE;
+    for (int w = 0; w < 2; ++w) {
+        const TrainNet& t = T.net[w];
+        act_floats = std::max(act_floats, t.x_off[t.n_layers] + ((t.width[t.n_layers] + 3) & ~3));
+        for (int l = 1; l <= t.n_layers; ++l) ld_max = std::max(ld_max, (t.width[l] + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1));
+    }
+    T.d_off[0] = act_floats; T.d_off[1] = act_floats + ld_max;
+    T.row_floats = act_floats + 2 * ld_max;                   // a multiple of 4 ...
+    if ((T.row_floats / 4) % 2 == 0) T.row_floats += 4;       // ... and an odd one: rows a thread apart fall into different banks
+    const int tile = (size_t)32 * (size_t)T.row_floats * sizeof(float) <= 63 * 1024 ? 32 : 16;
+    T.n_rows = b->n_rows; T.n_batch = b->n_batch; T.first_row = b->first_row;
+    T.n_tiles = (int)((B + (size_t)tile - 1) / (size_t)tile);
+    T.n_total = R.n[0] + R.n[1];
+    T.index = b->index; T.inputs = b->inputs; T.mean = b->mean; T.noise = b->noise; T.advantage = b->advantage; T.ret = b->ret; T.weight = b->weight;
+    T.std[0] = b->std[0]; T.std[1] = b->std[1]; T.clip = b->clip; T.value_coef = b->value_coef;
+    T.new_mean = b->new_mean; T.new_value = b->new_value;
+    T.part = R.part.get(); T.part_stats = R.stats.get();
+    const int G = std::min(T.n_tiles, FTGP_TRAIN_MAX_WG);
+    const size_t lds = (size_t)tile * (size_t)T.row_floats * sizeof(float);
+
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)b->stream)) return rc;
+    if (tile == 32) hipLaunchKernelGGL(ftgp_train_grad_kernel<32>, dim3((unsigned)G), dim3(FTGP_TRAIN_THREADS), lds, e->stream.get(), T);
+    else hipLaunchKernelGGL(ftgp_train_grad_kernel<16>, dim3((unsigned)G), dim3(FTGP_TRAIN_THREADS), lds, e->stream.get(), T);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(R.sync.get(), 0, sizeof(int32_t) * 2, e->stream.get()));
+    TrainReduceArgs A{};
+    A.part = R.part.get(); A.part_stats = R.stats.get(); A.G = G; A.n_total = T.n_total;
+    A.grad = R.grad.get(); A.sync = R.sync.get(); A.stats = R.stats.get() + (size_t)FTGP_TRAIN_MAX_WG * FTGP_TRAIN_STATS; A.stats_out = b->stats;
+    hipLaunchKernelGGL(ftgp_train_reduce_kernel, dim3((unsigned)((T.n_total + 255) / 256)), dim3(256), 0, e->stream.get(), A);
+    HIP_TRY(hipGetLastError());
+    return caller_waits_for_handle(e, (hipStream_t)b->stream);
+}
+
+int ftgp_train_adam_device(FtgpEnv* e, void* stream, int slot, float lr)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_adam_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (!std::isfinite(lr) || lr < 0.0f) return fail(FTGP_ERR_ARG, "ftgp_train_adam_device: lr is not finite or < 0%s");
+    FtgpEnv::Trainer& R = e->trainers[slot];
+    if (!R.on) return failf(FTGP_ERR_STATE, "ftgp_train_adam_device: network slot %d has no trainer (ftgp_train_begin)", slot);
+    HIP_TRY(hipSetDevice(e->device));
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
+    R.t += 1;
+    float s[6];
+    ftgp_adam_scalars(R.desc.beta1, R.desc.beta2, lr, R.t, s);
+    TrainAdamArgs A{};
+    A.p[0] = e->d_net_params[slot].get(); A.p[1] = e->d_vnet_params[slot].get(); A.n[0] = R.n[0]; A.n[1] = R.n[1];
+    A.grad = R.grad.get(); A.m = R.m.get(); A.v = R.v.get(); A.sync = R.sync.get();
+    A.b1 = s[0]; A.b2 = s[1]; A.omb1 = s[2]; A.omb2 = s[3]; A.a = s[4]; A.r = s[5]; A.eps = R.desc.eps;
+    hipLaunchKernelGGL(ftgp_train_adam_kernel, dim3((unsigned)((R.n[0] + R.n[1] + 255) / 256)), dim3(256), 0, e->stream.get(), A);
+    HIP_TRY(hipGetLastError());
+    return caller_waits_for_handle(e, (hipStream_t)stream);
+}
+
+int ftgp_train_get(FtgpEnv* e, int slot, int what, float* policy_out, float* value_out, int64_t* steps_out)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_get: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (what < FTGP_TRAIN_GRAD || what > FTGP_TRAIN_RAW_PARAMS) return failf(FTGP_ERR_ARG, "ftgp_train_get: what = %d is no FTGP_TRAIN_*", what);
+    FtgpEnv::Trainer& R = e->trainers[slot];
+    if (!R.on) return failf(FTGP_ERR_STATE, "ftgp_train_get: network slot %d has no trainer (ftgp_train_begin)", slot);
+    if (steps_out) *steps_out = R.t;
+    if (!policy_out && !value_out) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    if (what >= FTGP_TRAIN_RAW_GRAD) {                         // the library's layout as it lies in device memory, padding included
+        const bool g = what == FTGP_TRAIN_RAW_GRAD;
+        if (policy_out) HIP_TRY(hipMemcpyAsync(policy_out, g ? R.grad.get() : e->d_net_params[slot].get(), sizeof(float) * (size_t)R.n[0], hipMemcpyDeviceToHost, e->stream.get()));
+        if (value_out) HIP_TRY(hipMemcpyAsync(value_out, g ? R.grad.get() + R.n[0] : e->d_vnet_params[slot].get(), sizeof(float) * (size_t)R.n[1], hipMemcpyDeviceToHost, e->stream.get()));
+        HIP_TRY(hipStreamSynchronize(e->stream.get()));
+        return 0;
+    }
+    std::vector<float> img;
+    if (int rc = net_host_buffer(img, (size_t)R.n[0] + (size_t)R.n[1], "ftgp_train_get")) return rc;
+    const float* src = what == FTGP_TRAIN_GRAD ? R.grad.get() : what == FTGP_TRAIN_M ? R.m.get() : R.v.get();
+    HIP_TRY(hipMemcpyAsync(img.data(), src, sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    const NetDev& N = e->nets[slot]; const NetDev& V = e->vnets[slot];
+    if (policy_out) ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), policy_out);
+    if (value_out) ftgp_net_population_from_library(V.n_layers, V.width, 1, img.data() + R.n[0], value_out);
     return 0;
 }
 

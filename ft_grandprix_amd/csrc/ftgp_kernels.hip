@@ -3478,3 +3478,9 @@ __global__ void __launch_bounds__(256) ftgp_gae_kernel(GaeArgs G)
         G.ret[at] = ftgp_gae_return(a, v);
     }
 }
+
+// =============================================================================================
+// Training on the device (include/ftgp.h: ftgp_train_grad_device, ftgp_train_adam_device).  Behind every other kernel of the file, so that
+// the code object keeps the others where they were.
+// =============================================================================================
+#include "ftgp_train.h"

@@ -97,6 +97,27 @@ FTGP_HD float ftgp_gae_step(float gamma, float gl, float reward, float value, fl
 }
 FTGP_HD float ftgp_gae_return(float advantage, float value) { return advantage + value; }
 
+// ---- training (include/ftgp.h "Training on the device"): the scalars of one Adam step and its element step
+// (tools/train_check.cpp compiles these for the CPU; tests/train_model.py restates the header's text)
+// out = b1, b2, 1 - b1, 1 - b2, a = lr / (1 - beta1^t), r = 1 / sqrt(1 - beta2^t): binary64 (libm's pow and sqrt), each rounded once
+static inline void ftgp_adam_scalars(float beta1, float beta2, float lr, int64_t t, float out[6])
+{
+    const double b1 = (double)beta1, b2 = (double)beta2;
+    out[0] = beta1; out[1] = beta2;
+    out[2] = (float)(1.0 - b1); out[3] = (float)(1.0 - b2);
+    out[4] = (float)((double)lr / (1.0 - pow(b1, (double)t)));
+    out[5] = (float)(1.0 / sqrt(1.0 - pow(b2, (double)t)));
+}
+// one parameter: torch's Adam without weight decay; sqrtf and / are IEEE
+FTGP_HD void ftgp_adam_step(float* p, float* m, float* v, float g, float b1, float b2, float omb1, float omb2, float a, float r, float eps)
+{
+    const float m1 = fmaf(b1, *m, omb1 * g);
+    const float v1 = fmaf(b2, *v, omb2 * (g * g));
+    const float d = fmaf(sqrtf(v1), r, eps);
+    *p = fmaf(-a, m1 / d, *p);
+    *m = m1; *v = v1;
+}
+
 // ---- shapes: what ftgp_set_net checks, and the sizes that follow from a description ----
 FTGP_HD int ftgp_net_inputs(const FtgpNetDesc* d) { return d->n_beams + (d->use_state ? FTGP_NET_STATE_INPUTS : 0); }
 // the frame entries behind them (ftgp_set_net_frame): none without the struct or with enabled == 0

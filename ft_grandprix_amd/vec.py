@@ -556,6 +556,73 @@ class DeviceVecEnv:
                                 adv.data_ptr(), ret.data_ptr(), gamma=g, lam=l, stream=self._stream())
         return adv, ret
 
+    # -- training on the device (include/ftgp.h: ftgp_train_begin, ftgp_train_grad_device, ftgp_train_adam_device)
+    def train_begin(self, slot=0, betas=(0.9, 0.999), eps=1e-8):
+        """Give slot ``slot`` (defined, with a value net, without a population) a trainer: zeroed Adam moments and a step count of 0
+        (ftgp_train_begin).  ``set_net`` / ``set_value_net`` on the slot end it; ``set_net_params`` / ``set_value_params`` do not."""
+        slot = self._check_net_slot(slot)
+        d = capi.train_desc(betas, eps)
+        if slot not in self._nets:
+            raise ValueError(f"network slot {slot} is not defined: set_net first")
+        if slot not in self._value_nets():
+            raise ValueError(f"network slot {slot} has no value net: set_value_net first")
+        if slot in self._pops:
+            raise ValueError(f"network slot {slot} carries a population: a trainer steps a single parameter set")
+        self.env._call("train_begin", slot, ctypes.byref(d))
+
+    def train_end(self, slot=0):
+        self.env.train_end(self._check_net_slot(slot))
+
+    def ppo_update(self, roll, slot=0, epochs=4, minibatches=4, lr=3e-4, clip=0.2, value_coef=0.5, std=(1.0, 1.0), weight=None,
+                   normalize_advantage=True, generator=None):
+        """Clipped-PPO epochs over a ``collect(values=True)`` rollout on the device: per epoch one ``torch.randperm`` of the rollout's
+        rows (int32, on the device, from ``generator``), cut into ``minibatches`` chunks, and per chunk one ftgp_train_grad_device and
+        one ftgp_train_adam_device on slot ``slot``'s policy and value net in place (``train_begin`` first).  Only enqueues, on torch's
+        current stream; every tensor handed over is kept alive until the next call.  Returns the stats of every chunk, float32
+        [epochs * minibatches, 8] on the device (include/ftgp.h: S, policy loss, value loss, approximate KL, clipped fraction, the
+        non-finite flag, rows refused, 0).  ``std``: the exploration std the rollout was collected with.  ``weight``: float32
+        [T, n_envs, n_agents] >= 0 or None.  ``normalize_advantage``: ONE weighted mean / std over the whole rollout, once per call
+        (tools/ppo.py's torch path normalises per minibatch instead)."""
+        slot = self._check_net_slot(slot)
+        for name, v in (("epochs", epochs), ("minibatches", minibatches)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name}: an integer >= 1, got {v!r}")
+        if not isinstance(roll, Rollout) or roll.advantage is None or roll.returns is None:
+            raise ValueError("roll: a Rollout of collect(values=True)")
+        n_rows = int(roll.advantage.numel())
+        if minibatches > n_rows:
+            raise ValueError(f"minibatches = {minibatches} exceeds the rollout's {n_rows} rows")
+        if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != self.device
+                                   or tuple(weight.shape) != tuple(roll.advantage.shape) or not weight.is_contiguous()):
+            raise ValueError(f"weight: None or a contiguous float32 tensor {tuple(roll.advantage.shape)} on {self.device}")
+        probe = capi.train_batch(n_rows, 1, slot=slot, inputs=1, mean=1, advantage=1, ret=1, std=std, clip=clip, value_coef=value_coef)
+        with self._device_guard():
+            adv = roll.advantage
+            if normalize_advantage:
+                w = weight if weight is not None else torch.ones_like(adv)
+                s = w.sum().clamp_min(1e-12)
+                mu = (w * adv).sum() / s
+                var = (w * (adv - mu) ** 2).sum() / s
+                adv = ((adv - mu) / (var.sqrt() + 1e-8)).contiguous()
+            stats = torch.zeros((epochs * minibatches, capi.TRAIN_STATS), dtype=torch.float32, device=self.device)
+            stream = self._stream()
+            perms = []
+            edges = [n_rows * k // minibatches for k in range(minibatches + 1)]
+            for ep in range(epochs):
+                perm = torch.randperm(n_rows, device=self.device, generator=generator).to(torch.int32)
+                perms.append(perm)
+                for k in range(minibatches):
+                    b = capi.train_batch(n_rows, edges[k + 1] - edges[k], slot=slot, index=perm.data_ptr() + 4 * edges[k],
+                                         inputs=roll.inputs.data_ptr(), mean=roll.mean.data_ptr(),
+                                         noise=0 if roll.noise is None else roll.noise.data_ptr(), advantage=adv.data_ptr(),
+                                         ret=roll.returns.data_ptr(), weight=0 if weight is None else weight.data_ptr(),
+                                         std=(probe.std[0], probe.std[1]), clip=probe.clip, value_coef=probe.value_coef,
+                                         stats=stats.data_ptr() + 4 * capi.TRAIN_STATS * (ep * minibatches + k), stream=stream)
+                    self.env.train_grad_device(b)
+                    self.env.train_adam_device(slot, lr, stream)
+            self._train_keep = (roll, adv, weight, perms, stats)        # (the library reads and writes them in stream order)
+        return stats
+
     def set_net_params(self, slot, params):
         """New parameters for a defined slot from a float32 tensor on the env's device in ftgp_set_net's flat layout (``NetSpec.flat_params``),
         on torch's current stream, without leaving the device."""

@@ -892,6 +892,7 @@ int ftgp_get_net_rivals(FtgpEnv *env, int slot, FtgpNetRivals *rivals_out);
  * a member outside [0, n_members) with params_out set is FTGP_ERR_ARG.
  *
  * With the other entries: ftgp_set_net, ftgp_set_net_frame and ftgp_set_net_rivals (re)define a slot without a population.
+ * A call that gives a slot a population ends the slot's trainer (ftgp_train_begin).
  * ftgp_set_net_device on a slot with a population is FTGP_ERR_STATE (use ftgp_set_net_population_device).  ftgp_get_net keeps returning
  * the description and the slot's single set.  ftgp_reset, auto-reset, the spawn rule, the dynamics table and the ftgp_device_io_*
  * setters leave the population and the map alone, and so do the env-state calls: an env that loads another env's state keeps its own
@@ -991,7 +992,7 @@ int ftgp_collect_device(FtgpEnv *env, const FtgpCollect *c);
  * ftgp_get_value_net (host, synchronous) mirrors ftgp_get_net: the description and the parameters in force, in the caller's layout;
  * either pointer may be NULL; FTGP_ERR_STATE for a slot without a value net.
  * With the other entries: ftgp_set_net, ftgp_set_net_frame and ftgp_set_net_rivals on a slot clear its value net (the input width may
- * change).  ftgp_set_net_device, ftgp_set_net_population and its device form, ftgp_reset, auto-reset, the spawn rule, the dynamics
+ * change) and end its trainer (ftgp_train_begin), as ftgp_set_value_net itself does.  ftgp_set_net_device, ftgp_set_net_population and its device form, ftgp_reset, auto-reset, the spawn rule, the dynamics
  * table, the ftgp_device_io_* setters and the env-state calls leave it alone. */
 typedef struct FtgpValueDesc {
     int32_t n_layers;                       /* 1 .. FTGP_NET_MAX_LAYERS */
@@ -1040,6 +1041,105 @@ int ftgp_collect_values_device(FtgpEnv *env, const FtgpCollect *c, const FtgpCol
 int ftgp_gae_device(FtgpEnv *env, void *stream, int n_decisions, float gamma, float lam,
                     const float *reward, const float *value, const float *next_value,
                     const uint8_t *terminated, const uint8_t *truncated, float *advantage, float *ret);
+
+/* ---- Training on the device: PPO gradients of a slot's two nets and an Adam step (no reference counterpart) -----------------------------
+ * What closes a learner's loop behind ftgp_collect_values_device without a pass through the caller's framework: the gradient of the
+ * clipped-PPO objective on rows of a collected rollout, with respect to every weight and bias of the slot's policy and of its value net,
+ * and an Adam step on both in place -- in the buffers ftgp_set_net_device and ftgp_set_value_net_device write, so that the next launch
+ * that names the slot runs the new network.
+ *
+ * The trainer of slot s.  ftgp_train_begin (host; may synchronise) gives a defined slot that has a value net and no population a
+ * trainer: a gradient buffer and two moment buffers for each of the two nets, zeroed, a step count t = 0, and the scratch memory for
+ * partial sums (256 sets of both gradients in the library's layout).  FTGP_ERR_STATE for a slot that is not defined, has no value net,
+ * carries a population or has a trainer already; FTGP_ERR_ARG, naming the field, for a slot outside 0 .. 3, desc == NULL, beta1, beta2
+ * or eps not finite, a beta outside [0, 1), eps <= 0, reserved != 0 -- everything is checked before anything changes.  ftgp_train_end
+ * frees it (FTGP_ERR_STATE without one).  So do ftgp_destroy and the host setters that can change a shape: ftgp_set_net,
+ * ftgp_set_net_frame, ftgp_set_net_rivals and ftgp_set_value_net on that slot, and a ftgp_set_net_population that gives it a population.
+ * ftgp_set_net_device and ftgp_set_value_net_device replace parameters and leave the moments and t alone.  A handle that never calls
+ * ftgp_train_begin allocates and launches exactly what it did before there were trainers.
+ *
+ * ftgp_train_grad_device only enqueues, ordered on `stream` exactly as ftgp_set_net_device.  It overwrites the trainer's gradient with
+ * the gradient of L below at the parameters in force.  Batch row i = 0 .. n_batch-1 is row index[i] of the buffers, or first_row + i
+ * with index == NULL; its weight w is weight[row], or 1; S = the sum of w over the batch rows.  A row number outside [0, n_rows)
+ * contributes nothing, is counted in stats[6] and is never dereferenced; its new_mean and new_value entries are 0.
+ * Per row, with x the row of inputs:
+ *   y  = the slot's layers on x ("Layers" of "Network drivers", verbatim);  m_k = fmaf(y_k, out_scale[k], out_offset[k]);
+ *        new_mean[i] = (m_0, m_1)
+ *   yv = the value net's layers on x, likewise;  v = fmaf(yv, out_scale, out_offset);  new_value[i] = v
+ *   p_k = std[k]*noise[row][k] + mean[row][k] (the action before the clip, step 1 of "Collected rollouts");  z_k = (p_k - m_k) / std[k]
+ *   logp = -(z_0^2 + z_1^2)/2;  logq = -(noise_0^2 + noise_1^2)/2;  rho = exp(logp - logq)
+ *   A = advantage[row];  s = min(rho*A, clamp(rho, 1-c, 1+c)*A), c = clip;
+ *   ds/drho = A where (A >= 0 and rho <= 1+c) or (A < 0 and rho >= 1-c), else 0 -- evaluated as "0 where (A >= 0 and rho > 1+c) or
+ *             (A < 0 and rho < 1-c), else A": comparisons with a NaN are false, so a NaN advantage or ratio is not clipped away, reaches
+ *             the gradient and sets stats[5]
+ *   L = -(1/S) sum w*s + value_coef * (1/S) sum w*(v - ret[row])^2/2
+ * The derivative of an activation is taken from the layer's stored output o: identity 1; relu o > 0; tanh 1 - o*o, hence 0 where a
+ * clamp of TANH binds.  With S = 0 (or not > 0) the gradient and the stats are zeros.
+ * To the bit: the two forward passes, that is new_mean and new_value -- with unchanged parameters new_mean equals the mean
+ * ftgp_collect_device recorded for an unfinished car and new_value the value.  Everything else is binary32 as the implementation orders
+ * it, with these promises: z_k is evaluated as noise[row][k] + (mean[row][k] - m_k) / std[k], so that at unchanged parameters z_k is the
+ * noise, rho is exactly 1 and stats[3] and stats[4] are exactly 0; and the result is deterministic -- the same call on the same buffers
+ * gives the same bits on any stream at any load: no floating-point atomics reach the gradient or the stats, and the number and the
+ * order of the partial sums follow from the shapes alone (rows in tiles of 32, or of 16 for the widest nets; tile g, g + G, .. to
+ * workgroup g of G = min(tiles, 256); the workgroups' sums added g ascending, then divided by S).
+ * stats: [0] S; [1] -sum w*s / S; [2] sum w*(v - ret)^2/2 / S; [3] sum w*(logq - logp) / S; [4] sum w*[|rho - 1| > c] / S; [5] 1 if an
+ * element of either gradient is not finite, else 0; [6] the rows refused; [7] 0.
+ * Errors, all before anything is enqueued: FTGP_ERR_STATE for a slot without a trainer; FTGP_ERR_ARG, naming the field, for a slot
+ * outside 0 .. 3, n_batch < 1 or n_rows < 1, first_row < 0 or first_row + n_batch > n_rows (with index == NULL), std not finite or
+ * <= 0, clip or value_coef not finite or < 0, reserved != 0, and a buffer that is NULL (index, noise, weight, stats, new_mean and
+ * new_value may be), not device memory on the handle's device or too small.
+ *
+ * ftgp_train_adam_device only enqueues, with the same ordering.  The host advances t and rounds once from binary64: b1 = beta1,
+ * b2 = beta2, omb1 = 1 - beta1, omb2 = 1 - beta2, a = lr / (1 - beta1^t), r = 1 / sqrt(1 - beta2^t).  Then per parameter p with
+ * gradient g and moments m and v, binary32 with one rounding per written operation (sqrtf and / are IEEE):
+ *     m = fmaf(b1, m, omb1 * g);  v = fmaf(b2, v, omb2 * (g * g));  d = fmaf(sqrtf(v), r, eps);  p = fmaf(-a, m / d, p)
+ * -- torch's Adam without weight decay (ftgp_adam_step of csrc/ftgp_net.h) -- over the slot's policy and value parameters.  If the
+ * gradient's non-finite flag (stats[5]) is set, p, m and v of both nets stay exactly as they were; t still advances.  The zero padding
+ * of the library's layout stays zero.  lr not finite or < 0 is FTGP_ERR_ARG, no trainer FTGP_ERR_STATE.
+ *
+ * ftgp_train_get (host, synchronous): the gradient (FTGP_TRAIN_GRAD) or a moment (FTGP_TRAIN_M, FTGP_TRAIN_V) of both nets in the
+ * caller's flat layout -- the counts of ftgp_get_net and ftgp_get_value_net -- and t.  Any pointer may be NULL.  FTGP_ERR_STATE without a
+ * trainer, FTGP_ERR_ARG for an unknown `what`.  FTGP_TRAIN_RAW_GRAD and FTGP_TRAIN_RAW_PARAMS are debug reads for tests: the gradient,
+ * or the parameters in force, of both nets exactly as they lie in device memory -- the library's layout of "Network populations": per
+ * layer Wt[n_in][ld] with ld = n_out rounded up to 64, then b[ld]; (n_in + 1) * ld floats per layer -- so that the padding can be seen
+ * to be zeros.
+ * Memory: a trainer holds three copies of both nets in the library's layout and 256 more as partial sums -- about 28 MB for an
+ * 85 -> 64 -> 64 pair, about 150 MB for the largest shape (256 -> 128 x 3) -- until ftgp_train_end. */
+#define FTGP_TRAIN_STATS 8
+typedef struct FtgpTrainDesc {           /* the optimiser of one slot */
+    float beta1, beta2, eps;             /* finite; 0 <= beta < 1; eps > 0 */
+    int32_t reserved;                    /* 0 */
+} FtgpTrainDesc;
+int ftgp_train_begin(FtgpEnv *env, int slot, const FtgpTrainDesc *desc);
+int ftgp_train_end(FtgpEnv *env, int slot);
+
+typedef struct FtgpTrainBatch {
+    void *stream;                 /* as ftgp_set_net_device */
+    int32_t slot;
+    int32_t n_rows;               /* rows in the buffers below: T * n_envs * n_ext of the rollout */
+    int32_t n_batch;              /* B >= 1 rows of this minibatch */
+    int32_t first_row;            /* used when index == NULL: rows first_row .. first_row + B - 1 */
+    const int32_t *index;         /* optional int32[B] row numbers, any order, repeats allowed */
+    const float *inputs;          /* float32[n_rows][n_in] */
+    const float *mean;            /* float32[n_rows][2]   Rollout.mean */
+    const float *noise;           /* optional float32[n_rows][2]; NULL = zeros */
+    const float *advantage, *ret; /* float32[n_rows] */
+    const float *weight;          /* optional float32[n_rows] >= 0; NULL = ones */
+    float std[2];                 /* > 0, finite */
+    float clip;                   /* c >= 0, finite */
+    float value_coef;             /* >= 0, finite */
+    float *stats;                 /* optional float32[FTGP_TRAIN_STATS] */
+    float *new_mean, *new_value;  /* optional float32[B][2], float32[B]: the forward pass on the batch rows */
+    int32_t reserved[2];          /* 0 */
+} FtgpTrainBatch;
+int ftgp_train_grad_device(FtgpEnv *env, const FtgpTrainBatch *b);
+int ftgp_train_adam_device(FtgpEnv *env, void *stream, int slot, float lr);
+#define FTGP_TRAIN_GRAD 0
+#define FTGP_TRAIN_M    1
+#define FTGP_TRAIN_V    2
+#define FTGP_TRAIN_RAW_GRAD   3   /* for tests: the gradient as it lies in device memory, the library's layout, padding included */
+#define FTGP_TRAIN_RAW_PARAMS 4   /* for tests: likewise the slot's parameters in force */
+int ftgp_train_get(FtgpEnv *env, int slot, int what, float *policy_out, float *value_out, int64_t *steps_out);
 
 /* Read-backs (host buffers).  All are synchronous with respect to earlier calls on the handle. */
 

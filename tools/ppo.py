@@ -3,7 +3,7 @@
 
     python tools/ppo.py [--track circle] [--envs 1024] [--rays 1080] [--decisions 32] [--iterations 20] [--epochs 4] [--minibatches 4]
                         [--repeat 4] [--gamma 0.99] [--lam 0.95] [--clip 0.2] [--lr 3e-4] [--std 0.3,0.1] [--hidden 64] [--seed 0]
-                        [--save policy.npz]
+                        [--save policy.npz] [--device-update]
 
 One DeviceVecEnv of --envs envs with one agent each; slot 0 holds the policy and its value net.  Per iteration:
 
@@ -13,6 +13,10 @@ One DeviceVecEnv of --envs envs with one agent each; slot 0 holds the policy and
     --epochs passes of --minibatches minibatches: torch autograd on roll.inputs with the clipped surrogate on roll.advantage (normalised
     per minibatch) and the squared error to roll.returns; Adam
     env.set_net_params(0, flat policy), env.set_value_params(0, flat critic)      the refresh, on torch's stream, no synchronisation
+
+With --device-update the update never enters torch's autograd: env.train_begin(0) once, and per iteration env.ppo_update(roll, ...)
+(ftgp_train_grad_device and ftgp_train_adam_device per minibatch, on the slot's parameters in place; one advantage normalisation over
+the whole rollout instead of one per minibatch).  The torch path stays the default, and the comparison.
 
 and one JSON line: the iteration, the mean reward per decision, the mean return, the losses, the seconds of the collect and of the
 update.  torch's tanh differs from the library's in the seventh digit, so the ratio of the first minibatch is 1 to that precision.
@@ -59,6 +63,7 @@ def main():
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save", default=None, help="write the policy of the last iteration as an .npz (net.load reads it)")
+    ap.add_argument("--device-update", action="store_true", help="the update on the device (DeviceVecEnv.ppo_update) instead of torch autograd + Adam")
     a = ap.parse_args()
     eighth = int(a.rays / 8.0)
     first = -(-eighth // a.pool)
@@ -72,6 +77,8 @@ def main():
     env = DeviceVecEnv(a.track, n_envs=a.envs, n_rays=a.rays, roster=["agent"], nets={0: net.from_torch(policy, **fields)},
                        action_repeat=a.repeat, max_episode_steps=a.episode, terminate_off_track=True, spawn_mode=1, seed=a.seed)
     env.set_value_net(0, critic)
+    if a.device_update:
+        env.train_begin(0)
     env.reset()
     dev = env.device
     policy, critic = policy.to(dev), critic.to(dev)
@@ -84,6 +91,15 @@ def main():
         roll = env.collect(T, std=tuple(std.tolist()), clip=((0.0, 6.0), (-0.6, 0.6)), noise=True, values=True, gamma=a.gamma, lam=a.lam, out=roll)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
+        if a.device_update:
+            stats = env.ppo_update(roll, 0, epochs=a.epochs, minibatches=a.minibatches, lr=a.lr, clip=a.clip, value_coef=0.5, std=tuple(std.tolist()))
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            print(json.dumps({"iteration": iteration, "update": "device", "reward_per_decision": float(roll.reward.mean()),
+                              "return_mean": float(roll.returns.mean()), "value_mean": float(roll.value.mean()), "loss_pi": float(stats[-1, 1]),
+                              "loss_v": float(stats[-1, 2]), "ends": int((roll.terminated | roll.truncated).sum()), "envs": a.envs, "decisions": T,
+                              "collect_s": t1 - t0, "update_s": t2 - t1}), flush=True)
+            continue
         x = roll.inputs.reshape(-1, n_in)
         z = roll.noise.reshape(-1, 2)
         proposed = roll.mean.reshape(-1, 2) + std * z                  # the action before the clip: what the behaviour policy drew
@@ -106,11 +122,13 @@ def main():
         env.set_value_params(0, flat(critic))
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        print(json.dumps({"iteration": iteration, "reward_per_decision": float(roll.reward.mean()), "return_mean": float(ret.mean()),
+        print(json.dumps({"iteration": iteration, "update": "torch", "reward_per_decision": float(roll.reward.mean()), "return_mean": float(ret.mean()),
                           "value_mean": float(roll.value.mean()), "loss_pi": float(loss_pi), "loss_v": float(loss_v),
                           "ends": int((roll.terminated | roll.truncated).sum()), "envs": a.envs, "decisions": T,
                           "collect_s": t1 - t0, "update_s": t2 - t1}), flush=True)
-    if a.save:
+    if a.save and a.device_update:
+        net.NetSpec(env.env.net(0)[1], hidden_act="tanh", out_act="tanh", **fields).save(a.save)
+    elif a.save:
         net.from_torch(policy.cpu(), **fields).save(a.save)
     env.close()
 
