@@ -221,7 +221,7 @@ struct FtgpEnv {
         int n[2] = { 0, 0 };              // n_floats of the policy and of the value net (the library's layout)
         DevBuf<float> grad, m, v;         // [n[0] + n[1]] the policy's, then the value net's
         DevBuf<float> part;               // [FTGP_TRAIN_MAX_WG][n[0] + n[1]] the workgroups' partial sums
-        DevBuf<float> stats;              // [FTGP_TRAIN_MAX_WG + 1][FTGP_TRAIN_STATS] the workgroups' partial stats, then the stats of the newest gradient
+        DevBuf<float> stats;              // [2 * FTGP_TRAIN_MAX_WG + 1][FTGP_TRAIN_STATS] the workgroups' partial stats, the stats of the newest gradient, the workgroups' binary64 sums (four doubles each)
         DevBuf<int32_t> sync;             // the gradient's non-finite flag, the reduce kernel's ticket
     } trainers[FTGP_MAX_NETS];
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
@@ -2607,7 +2607,8 @@ int ftgp_train_begin(FtgpEnv* e, int slot, const FtgpTrainDesc* desc)
     HIP_TRY(dev_zeros(T.m, sizeof(float) * total, e->stream.get()));
     HIP_TRY(dev_zeros(T.v, sizeof(float) * total, e->stream.get()));
     HIP_TRY(dev_zeros(T.part, sizeof(float) * total * FTGP_TRAIN_MAX_WG, e->stream.get()));
-    HIP_TRY(dev_zeros(T.stats, sizeof(float) * FTGP_TRAIN_STATS * (FTGP_TRAIN_MAX_WG + 1), e->stream.get()));
+    // (the workgroups' stats, the trainer's own, then the workgroups' binary64 sums: four doubles each)
+    HIP_TRY(dev_zeros(T.stats, sizeof(float) * FTGP_TRAIN_STATS * (2 * FTGP_TRAIN_MAX_WG + 1), e->stream.get()));
     HIP_TRY(dev_zeros(T.sync, sizeof(int32_t) * 2, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     T.on = true;
@@ -2695,6 +2696,8 @@ int ftgp_train_grad_device(FtgpEnv* e, const FtgpTrainBatch* b)
     T.std[0] = b->std[0]; T.std[1] = b->std[1]; T.clip = b->clip; T.value_coef = b->value_coef;
     T.new_mean = b->new_mean; T.new_value = b->new_value;
     T.part = R.part.get(); T.part_stats = R.stats.get();
+    static_assert(((FTGP_TRAIN_MAX_WG + 1) * FTGP_TRAIN_STATS * sizeof(float)) % alignof(double) == 0 && 4 * sizeof(double) <= FTGP_TRAIN_STATS * sizeof(float), "the binary64 sums behind the stats");
+    T.part_wide = reinterpret_cast<double*>(R.stats.get() + (size_t)(FTGP_TRAIN_MAX_WG + 1) * FTGP_TRAIN_STATS);      // [FTGP_TRAIN_MAX_WG][4]
     const int G = std::min(T.n_tiles, FTGP_TRAIN_MAX_WG);
     const size_t lds = (size_t)tile * (size_t)T.row_floats * sizeof(float);
 
@@ -2704,7 +2707,7 @@ int ftgp_train_grad_device(FtgpEnv* e, const FtgpTrainBatch* b)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(R.sync.get(), 0, sizeof(int32_t) * 2, e->stream.get()));
     TrainReduceArgs A{};
-    A.part = R.part.get(); A.part_stats = R.stats.get(); A.G = G; A.n_total = T.n_total;
+    A.part = R.part.get(); A.part_stats = R.stats.get(); A.part_wide = T.part_wide; A.G = G; A.n_total = T.n_total;
     A.grad = R.grad.get(); A.sync = R.sync.get(); A.stats = R.stats.get() + (size_t)FTGP_TRAIN_MAX_WG * FTGP_TRAIN_STATS; A.stats_out = b->stats;
     hipLaunchKernelGGL(ftgp_train_reduce_kernel, dim3((unsigned)((T.n_total + 255) / 256)), dim3(256), 0, e->stream.get(), A);
     HIP_TRY(hipGetLastError());

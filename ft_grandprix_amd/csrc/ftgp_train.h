@@ -13,7 +13,8 @@
 // the result dealt to the four waves (train_dw, train_dx); the forward stays a plain fmaf chain, which the specification allows.
 // A workgroup adds its tiles, in the order it takes them, into ITS OWN partial sums part[g] (the library's layout, the padding zeros);
 // ftgp_train_reduce_kernel adds the partial sums g = 0, 1, .. in that order and divides by S.  No floating-point atomics anywhere: the
-// number and the order of the sums follow from the shapes alone.
+// number and the order of the sums follow from the shapes alone.  The numerators of stats [1] .. [4] take the same path in binary64
+// (part_wide) and are rounded once, after the division by S: their error does not grow with the batch.
 #pragma once
 #include "ftgp_net.h"
 
@@ -39,6 +40,7 @@ struct TrainArgs {
     float* new_mean; float* new_value;
     float* part;                     // [G][n_total] the workgroups' partial sums
     float* part_stats;               // [G][FTGP_TRAIN_STATS]
+    double* part_wide;               // [G][4]: the binary64 sums of columns 1 .. 4
 };
 
 typedef float train_f32x16 __attribute__((ext_vector_type(16)));      // the accumulator of v_mfma_f32_32x32x2_f32
@@ -177,7 +179,12 @@ __global__ void __launch_bounds__(FTGP_TRAIN_THREADS) ftgp_train_grad_kernel(Tra
     const int tid = (int)threadIdx.x, lane = tid & (FTGP_WAVE - 1), wave = tid >> 6;
     const int S = T.row_floats;
     float* __restrict__ P = T.part + (size_t)blockIdx.x * (size_t)T.n_total;
-    float stat = 0.0f;                       // thread t < FTGP_TRAIN_ROWSTATS: the workgroup's sum of column t
+    // thread t < FTGP_TRAIN_ROWSTATS: the workgroup's sum of column t.  Columns 0 (w: S divides the gradient) and 5 (the rows refused) are
+    // binary32 sums; columns 1 .. 4, the numerators of stats [1] .. [4], are carried in binary64, so that what a stat loses does not grow
+    // with the number of rows
+    float stat = 0.0f;
+    double wide = 0.0;
+    const bool is_wide = tid >= 1 && tid <= 4;
     bool first = true;
     for (int tile = (int)blockIdx.x; tile < T.n_tiles; tile += (int)gridDim.x, first = false) {
         // ---- the tile's rows: a row number outside [0, n_rows) is counted and never dereferenced
@@ -269,15 +276,26 @@ __global__ void __launch_bounds__(FTGP_TRAIN_THREADS) ftgp_train_grad_kernel(Tra
             }
         }
         if (tid < FTGP_TRAIN_ROWSTATS) {
-            float s = 0.0f;
-            for (int r = 0; r < R; ++r) s += rowstat[r][tid];
-            stat += s;
+            if (is_wide) {
+                double s = 0.0;
+                for (int r = 0; r < R; ++r) s += (double)rowstat[r][tid];
+                wide += s;
+            } else {
+                float s = 0.0f;
+                for (int r = 0; r < R; ++r) s += rowstat[r][tid];
+                stat += s;
+            }
         }
         __syncthreads();
     }
     if (tid < FTGP_TRAIN_ROWSTATS) {
         float* mine = T.part_stats + (size_t)blockIdx.x * FTGP_TRAIN_STATS;
-        mine[tid == FTGP_TRAIN_ROWSTATS - 1 ? 6 : tid] = stat;             // stats[6]: the rows refused
+        if (is_wide) {
+            mine[tid] = (float)wide;                                       // (not read: the reduce takes the binary64 sum)
+            T.part_wide[(size_t)blockIdx.x * 4 + (tid - 1)] = wide;
+        } else {
+            mine[tid == FTGP_TRAIN_ROWSTATS - 1 ? 6 : tid] = stat;         // stats[6]: the rows refused
+        }
         if (tid == 0) { mine[5] = 0.0f; mine[7] = 0.0f; }
     }
 }
@@ -290,11 +308,19 @@ template __global__ void ftgp_train_grad_kernel<16>(TrainArgs);
 struct TrainReduceArgs {
     const float* part; const float* part_stats; int32_t G, n_total;
     float* grad; int32_t* sync; float* stats; float* stats_out;       // stats: the trainer's own; stats_out: the caller's, or null
+    const double* part_wide;
 };
 __device__ __forceinline__ float train_sum_stat(const TrainReduceArgs& A, int q)
 {
     float s = 0.0f;
     for (int g = 0; g < A.G; ++g) s += A.part_stats[(size_t)g * FTGP_TRAIN_STATS + q];
+    return s;
+}
+// columns 1 .. 4: the workgroups' binary64 sums, g ascending, in binary64
+__device__ __forceinline__ double train_sum_stat_wide(const TrainReduceArgs& A, int q)
+{
+    double s = 0.0;
+    for (int g = 0; g < A.G; ++g) s += A.part_wide[(size_t)g * 4 + (q - 1)];
     return s;
 }
 __global__ void __launch_bounds__(256) ftgp_train_reduce_kernel(TrainReduceArgs A)
@@ -333,7 +359,7 @@ __global__ void __launch_bounds__(256) ftgp_train_reduce_kernel(TrainReduceArgs 
         const int q = (int)threadIdx.x;
         float v = 0.0f;
         if (q == 0) v = S > 0.0f ? S : 0.0f;
-        else if (q >= 1 && q <= 4) v = S > 0.0f ? train_sum_stat(A, q) / S : 0.0f;
+        else if (q >= 1 && q <= 4) v = S > 0.0f ? (float)(train_sum_stat_wide(A, q) / (double)S) : 0.0f;     // one rounding
         else if (q == 5) v = atomicOr(A.sync, 0) ? 1.0f : 0.0f;
         else if (q == 6) v = train_sum_stat(A, 6);
         A.stats[q] = v;

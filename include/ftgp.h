@@ -1081,7 +1081,9 @@ int ftgp_gae_device(FtgpEnv *env, void *stream, int n_decisions, float gamma, fl
  * noise, rho is exactly 1 and stats[3] and stats[4] are exactly 0; and the result is deterministic -- the same call on the same buffers
  * gives the same bits on any stream at any load: no floating-point atomics reach the gradient or the stats, and the number and the
  * order of the partial sums follow from the shapes alone (rows in tiles of 32, or of 16 for the widest nets; tile g, g + G, .. to
- * workgroup g of G = min(tiles, 256); the workgroups' sums added g ascending, then divided by S).
+ * workgroup g of G = min(tiles, 256); the workgroups' sums added g ascending, then divided by S).  The sums behind stats [1] .. [4] are
+ * carried in binary64 along that order (each row's term is binary32) and rounded to binary32 once, after the division by S, so that what
+ * a stat loses does not grow with n_batch; S and the gradient are binary32 sums.
  * stats: [0] S; [1] -sum w*s / S; [2] sum w*(v - ret)^2/2 / S; [3] sum w*(logq - logp) / S; [4] sum w*[|rho - 1| > c] / S; [5] 1 if an
  * element of either gradient is not finite, else 0; [6] the rows refused; [7] 0.
  * Errors, all before anything is enqueued: FTGP_ERR_STATE for a slot without a trainer; FTGP_ERR_ARG, naming the field, for a slot

@@ -8,7 +8,9 @@ text (tests/train_model.py), bit for bit; the model's gradient against central d
 GPU: every scenario runs in a fresh child process (tests/train_child.py), one at a time, each under a time limit (tests/children.py).
 The forward pass and Adam are compared to the bit; the gradient and the stats within 4 * rel_ref of the binary64 model, rel_ref being
 what the same model in binary32, rows accumulated one after the other, loses against it -- the factor covers another order of the sums
-and the device's exp.
+and the device's exp.  Where a batch has more tiles than workgroups, a workgroup adds several tiles into its partial sums: a batch that
+is zeros but for one or two tiles is compared exactly with a call on those tiles' rows alone (`turns`).  The CPU side restates the
+host's LDS row rule (train_model.row_layout) and pins the tile size and the number of tiles of every case that is there for a path.
 """
 import ctypes
 import functools
@@ -276,6 +278,86 @@ def test_the_gradient_cases_meet_their_conditions():
         assert len(case["rows"]) == tm.CASES[name][6]
     a = tm.make_case("a")
     assert np.unique(a["rows"]).size < len(a["rows"]) and (a["weight"] == 0).any()
+    for name in ("turns32", "turns16"):
+        c = tm.make_case(name)
+        assert np.unique(c["rows"]).size < len(c["rows"]) and (c["weight"] == 0).any()
+
+
+def test_row_layout_written_out_by_hand():
+    """The host's row rule on shapes added up by hand.  d: 33 -> 65 -> 2 and -> 1: 36 + 68 + 4 = 108 floats of outputs, two delta
+    buffers of 128: 364 = 4 * 91, odd.  a: 88 + 64 + 64 + 4 = 220, + 2 * 64 = 348 = 4 * 87.  c: 256 + 3 * 128 + 4 = 644, + 256 = 900
+    = 4 * 225; 32 * 900 * 4 bytes are more than 63 KiB.  A net of (8, 2) and (8, 1): 12 + 128 = 140 = 4 * 35."""
+    assert tm.row_layout((33, 65, 2), (33, 65, 1)) == (364, 32)
+    assert tm.row_layout((85, 64, 64, 2), (85, 64, 64, 1)) == (348, 32)
+    assert tm.row_layout((256, 128, 128, 128, 2), (256, 128, 128, 128, 1)) == (900, 16)
+    assert tm.row_layout((8, 2), (8, 1)) == (140, 32)
+    # the bump: 4 + 4 + 128 = 136 = 4 * 34, even: four more
+    assert tm.row_layout((4, 2), (4, 1)) == (140, 32)
+    # the longer net sets the outputs, the widest layer of either the delta buffers: (33, 2) against (33, 100, 7, 33, 1)
+    # (36 + 100 + 8 + 36 + 4 = 184, + 2 * 128 = 440 = 4 * 110, even: 444)
+    assert tm.row_layout((33, 2), (33, 100, 7, 33, 1)) == (444, 32)
+    assert tm.row_layout((33, 100, 7, 33, 2), (33, 1)) == (444, 32)
+
+
+def test_the_gradient_cases_take_the_paths_they_are_meant_to():
+    """The tile size and the number of tiles of the cases that are there for a path of the launch: a change to a case cannot move it off
+    its path unseen."""
+    rows = {name: tm.row_layout(*tm.case_widths(name))[1] for name in tm.CASES}
+    floats = {name: tm.row_layout(*tm.case_widths(name))[0] for name in tm.CASES}
+    assert rows["turns32"] == 32 and rows["edge32"] == 32 and rows["mixed"] == 32 and rows["mixed2"] == 32
+    assert rows["turns16"] == 16 and rows["edge16"] == 16 and rows["c"] == 16
+    # more tiles than workgroups, by two: workgroups 0 and 1 take a second tile, and the last tile is ragged
+    for name in ("turns32", "turns16"):
+        assert tm.n_tiles(name) == tm.MAX_WG + 2 and tm.CASES[name][6] % rows[name] != 0
+    assert all(tm.n_tiles(name) <= tm.MAX_WG for name in tm.CASES if not name.startswith("turns"))
+    # the edge of the tile-size rule: the largest row that takes 32 rows, and the next one (rows grow by 8 floats: an odd number of float4)
+    assert floats["edge32"] == 500 and 32 * 500 * 4 <= 63 * 1024 < 32 * 508 * 4 and floats["edge16"] == 508
+    # widths that are no multiple of 8 into the input delta (layers l > 0), a bias row inside a 32-row tile of k, nets of unlike shape
+    dx_widths = {n for name in tm.CASES for w in tm.case_widths(name) for n in w[2:]}
+    assert {7, 31, 33, 65, 97, 100} <= {n for name in ("mixed", "mixed2", "edge32") for w in tm.case_widths(name) for n in w[1:-1]}
+    assert {1, 2, 7, 33, 64, 65, 97, 128} <= dx_widths
+    assert {7, 31, 97, 100} <= {n for name in ("mixed", "mixed2") for w in tm.case_widths(name) for n in w[:-1]}
+    for name in ("mixed", "mixed2"):
+        pw, vw = tm.case_widths(name)
+        assert len(pw) != len(vw) and max(pw[1:]) != max(vw[1:])
+    # uneven: at layer 1 the weight gradient has (n_in + 1 tiles of 32) x (ld / 32) = 3 x 2 tiles, no multiple of the four waves; the
+    # delta it reads is the second buffer (the buffers alternate from the last layer down), the one it writes is 128 columns wide
+    n_in, n_out = tm.case_widths("uneven")[0][1:3]
+    ld = lambda n: (n + 63) & ~63                                     # noqa: E731
+    assert len(tm.case_widths("uneven")[0]) == 4 and ((n_in + 1 + 31) // 32) * (ld(n_out) // 32) % 4 != 0 and ld(n_in) == 128 and ld(n_out) == 64
+    assert rows["uneven"] == 32
+
+
+@pytest.mark.parametrize("name", ["turns32", "turns16"])
+def test_the_turns_scenario_makes_no_nan_of_its_own(name):
+    """tests/train_child.py `turns` gives most rows a weight of 0.  0 * infinity is a NaN, so every row of the buffers -- any of them may
+    be named by an index -- has a finite ratio in the binary32 model, |logp - logq| < 80 (exp overflows binary32 at 88.7), and a finite
+    value; the live rows are distinct, the dead ones are the rest, and only the live ones have a weight."""
+    case = tm.make_case(name)
+    span, finite = tm.ratio_span(case)
+    assert finite and span < 80.0, (span, finite)
+    R = tm.row_layout(*tm.case_widths(name))[1]
+    tail = tm.turns_tail(name)
+    assert 0 < tail < R
+    live, dead, weight = tm.turns_rows(case, R, tail)
+    assert live.size == 2 * R and np.unique(live).size == 2 * R and not np.intersect1d(live, dead).size and live.size + dead.size == case["n_rows"]
+    assert (weight[live] >= 0.5).all() and not weight[dead].any() and np.isfinite(case["advantage"]).all() and np.isfinite(case["ret"]).all()
+    index = tm.turns_index(dead, 5 * R, [(2 * R, live[:R])])
+    assert index.dtype == np.int32 and (index[2 * R:3 * R] == live[:R]).all() and np.isin(np.delete(index, np.s_[2 * R:3 * R]), dead).all()
+    # the clip leaves live rows free in each live tile: their gradient is not a zero
+    t = tm.loss_terms(dict(case, rows=live, weight=weight))
+    assert t["active"][R:].any() and t["active"][:tail].any()
+
+
+def test_the_case_without_noise_meets_what_conditions_it_can():
+    """noise = None: logq = 0 and rho = exp(logp) <= 1, so the clip cannot bind above 1 + clip for any seed; every other condition is
+    asked as of the other cases (the clip binds below on 5 % of the weighted rows, 40 % are free, no row at an edge)."""
+    case = tm.make_case("d", with_noise=False)
+    assert case["noise"] is None and tm.conditions(case, high_side=False) is None
+    assert "binds" in tm.conditions(case)                             # (the full conditions do name the high side)
+    assert tm.loss_terms(case)["rho"].max() <= 1.0
+    with_noise = tm.make_case("d")
+    assert with_noise["noise"] is not None and tm.conditions(with_noise) is None
 
 
 # ---------------------------------------------------------------------------------------------------------------------- GPU
@@ -284,8 +366,38 @@ def test_the_gradient_cases_meet_their_conditions():
 def test_gradient_and_forward(case):
     """a: 85 -> 64 -> 64 at 517 rows through an index with repeats and zero weights; b: 1 -> 3, relu, 63 rows; c: 256 -> 128 x 3, 300
     rows from first_row 27 (tiles of 16 rows); d: hidden 65 (padding inside ld = 128), 257 rows; e: one-layer nets at 1 and at 64 rows.
-    Each case also reads the gradient, and after an Adam step the parameters, as raw library-layout memory: the padding is zero bits."""
+    turns32: 17 -> 8, 8229 rows through an index: 258 tiles of 32 rows on 256 workgroups, so workgroups 0 and 1 take a second tile, the
+    last one of 5 rows; turns16: 256 -> 128, 4115 rows: 258 tiles of 16 (rel_ref grows with the rows added up, to about 4e-6: these two are
+    coarse, the sharp check of a second turn is test_a_tiles_share_does_not_depend_on_whose_turn_it_is).  mixed: a policy 33 -> 31 -> 97
+    -> 2 next to a critic 33 -> 64 -> 1, relu; mixed2: a one-layer policy next to a critic 33 -> 100 -> 7 -> 33 -> 1 -- the nets share the
+    LDS row, and widths that are no multiple of 8 go through the input delta, bias rows inside a 32-row tile of k through the weight
+    gradient.  edge32 / edge16: 104 and 108 -> 65 -> 65: LDS rows of 500 and 508 floats, the largest that takes tiles of 32 rows (64000
+    bytes) and the first that takes 16.  uneven: 33 -> 80 -> 24: waves that finish the middle layer's weight gradient early write the next
+    delta while the others still read this one.
+    Each case also reads the gradient, and after an Adam step the parameters, as raw library-layout memory: the padding is zero bits.
+    stats [0], [2] and [4] (S, the value loss, the clipped fraction) are also compared to the bit with sums in the order the header
+    gives -- a tile's rows, a workgroup's tiles, the workgroups -- S in binary32, the other two carried in binary64 and rounded once
+    (tm.ordered_stats).
+    (turns32 is the case that found the stats' sums wanting: added up in binary32 in that order, 8229 rows left stats [2] and [4] at
+    4.0e-7 and 5.5e-7 of their scale, 9.27 times rel_ref = 5.92e-8, where 4 are allowed; the device now carries them in binary64.)"""
     assert f"gradient {case} ok" in run_child("gradient", only=case)
+
+
+@pytest.mark.gpu
+def test_gradient_without_noise():
+    """Case d with noise = NULL (n = 0, logq = 0), in the model and in the call: the same criterion."""
+    assert "gradient d without noise ok" in run_child("gradient", only="d", noise=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,rows", [("turns32", 32), ("turns16", 16)])
+def test_a_tiles_share_does_not_depend_on_whose_turn_it_is(case, rows):
+    """All weights 0 but for one or two tiles' rows; every comparison exact (values: +0 and -0 may differ), against a call on the live
+    rows alone (one tile, one workgroup).  258 tiles with the live one at 0, 255 (first turns), 256 (the second turn of workgroup 0) and
+    257 (ragged); 769 tiles with the live one at 512 (a third turn behind a second turn of zeros); tiles 3 and 259 live, both workgroup
+    3's, against a call of those two tiles on two workgroups; row numbers -1 and n_rows inside the live tile of a second turn; and a
+    call with stats, new_mean and new_value NULL.  new_mean and new_value of every batch position to the bit against the model."""
+    assert f"turns {case} ok" in run_child("turns", only=case, rows=rows)
 
 
 @pytest.mark.gpu

@@ -5,8 +5,10 @@ ft_grandprix_amd/vec.py).  Exit status 0 = the scenario held; anything else fail
 
 The criteria (include/ftgp.h "Training on the device"): new_mean and new_value equal tests/net_model.py to the bit; the gradient and the
 stats lie within four times the distance of the binary32 model from the binary64 one (tests/train_model.py: tolerance); Adam equals the
-model's element step to the bit on the gradients read back.
+model's element step to the bit on the gradients read back; a batch whose rows have weight 0 but for one or two tiles gives exactly the
+gradient and the stats of those tiles' rows alone, whichever workgroup's whichever turn they fall on (turns).
 """
+import functools
 import json
 import os
 import subprocess
@@ -30,7 +32,7 @@ DEV = "cuda"
 F = np.float32
 # the slot description that gives a net n_in inputs: (n_rays, pool, max_range, beam_first, n_beams, use_state)
 INPUTS = {85: (1080, 10, 10.0, 14, 80, True), 1: (64, 4, 3.0, 2, 1, False), 256: (1344, 4, 8.0, 42, 251, True), 33: (1080, 10, 10.0, 14, 28, True),
-          17: (64, 4, 3.0, 2, 12, True)}
+          17: (64, 4, 3.0, 2, 12, True), 104: (1344, 4, 8.0, 42, 99, True), 108: (1344, 4, 8.0, 42, 103, True)}
 
 
 def dev(a):
@@ -95,7 +97,9 @@ def forward_bits(what, case, b):
     want = nm.fmaf(y, np.asarray(p["out_scale"], dtype=F)[None, :], np.asarray(p["out_offset"], dtype=F)[None, :])
     cmod.assert_same_bits(b.new_mean.cpu().numpy(), want, f"{what}: new_mean against the model")
     yv = nm.forward(x, v["layers"], v["hidden_act"], v["out_act"])
-    cmod.assert_same_bits(b.new_value.cpu().numpy(), nm.fmaf(yv[:, 0], F(v["out_scale"]), F(v["out_offset"])), f"{what}: new_value against the model")
+    want_value = nm.fmaf(yv[:, 0], F(v["out_scale"]), F(v["out_offset"]))
+    cmod.assert_same_bits(b.new_value.cpu().numpy(), want_value, f"{what}: new_value against the model")
+    return want, want_value
 
 
 def padding_is_zero(what, env, which, caller):
@@ -116,14 +120,24 @@ def padding_is_zero(what, env, which, caller):
 
 
 def gradient(opt):
-    """Cases a - e: the gradient and the stats within 4 * rel_ref of the binary64 model, the forward pass to the bit."""
+    """Every case of tm.CASES: the gradient and the stats within 4 * rel_ref of the binary64 model, the forward pass to the bit.
+    noise = false: the case with noise = None in the model and NULL in the call."""
     name = opt["only"]
-    case = tm.make_case(name)
+    with_noise = opt.get("noise", True)
+    case = tm.make_case(name, with_noise=with_noise)
+    if not with_noise:
+        assert case["noise"] is None and tm.conditions(case, high_side=False) is None
+        name += " without noise"
     gp, gv, st, rel_p, rel_v, rel_s, scales = tm.tolerance(case)
     env = make_env(case)
     b = Batch(case)
     stats = b.grad(env)
-    forward_bits(name, case, b)
+    _, value32 = forward_bits(name, case, b)
+    # S, the value loss and the clipped fraction: binary32 sums in the order the header gives, to the bit
+    R = tm.row_layout(widths_of(case["policy"]), widths_of(case["value"]))[1]
+    ordered = tm.ordered_stats(case, R, value32)
+    print(f"case {name}: stats [0], [2], [4] = {[float(stats[q]) for q in (0, 2, 4)]} against the sums in the device's order {[float(x) for x in ordered]}")
+    cmod.assert_same_bits(stats[[0, 2, 4]], np.array(ordered, dtype=F), f"{name}: stats [0], [2] and [4] against the binary32 sums in the device's order")
     dp, dv, t = grads_of(env, case)
     assert t == 0
     worst = {}
@@ -150,6 +164,89 @@ def gradient(opt):
     assert not np.array_equal(tm.flat(pl), tm.flat(case["policy"]["layers"])), "Adam moved the parameters"
     env.close()
     print(f"gradient {name} ok")
+
+
+def turns(opt):
+    """What a tile adds to the gradient does not depend on whose turn it is: the nets of turns32 (tiles of 32 rows) or turns16 (of 16),
+    one handle, every comparison exact.  Only the rows tm.turns_rows calls live have a weight; every other batch position names a
+    real row whose weight is 0.  Such a row's deltas are +-0, and adding +-0 to a partial sum, in a workgroup or across workgroups, is
+    exact: a batch of hundreds of tiles must give the values of a batch of its live rows alone."""
+    name = opt["only"]
+    case = tm.make_case(name)
+    R = tm.row_layout(*tm.case_widths(name))[1]
+    G = tm.MAX_WG
+    B = tm.CASES[name][6]
+    tail = tm.turns_tail(name)                                         # the live rows of the ragged last tile
+    assert opt["rows"] == R and tm.n_tiles(name) == G + 2 and 0 < tail < R and B == (G + 1) * R + tail
+    span, finite = tm.ratio_span(case)
+    assert finite and span < 80.0, f"{name}: a row of weight 0 would make a NaN of the test's own: {span}, {finite}"
+    live, dead, weight = tm.turns_rows(case, R, tail)
+    a, pair = live[:R], live
+    env = make_env(case)
+    # the forward pass of every row of the buffers, once
+    p, v = case["policy"], case["value"]
+    y = nm.forward(case["inputs"], p["layers"], p["hidden_act"], p["out_act"])
+    mean_of = nm.fmaf(y, np.asarray(p["out_scale"], dtype=F)[None, :], np.asarray(p["out_offset"], dtype=F)[None, :])
+    yv = nm.forward(case["inputs"], v["layers"], v["hidden_act"], v["out_act"])
+    value_of = nm.fmaf(yv[:, 0], F(v["out_scale"]), F(v["out_offset"]))
+
+    def run(what, index, null=False):
+        """(stats, policy gradient, value gradient) of one call on `index`; new_mean and new_value against the model to the bit."""
+        index = np.asarray(index, dtype=np.int32)
+        b = Batch(dict(case, index=index, rows=index, weight=weight, first_row=0))
+        stats = b.grad(env, **(dict(stats=0, new_mean=0, new_value=0) if null else {}))
+        g = env.train_get(0)
+        if null:
+            assert (stats == -7.0).all() and (b.new_mean.cpu().numpy() == -7.0).all() and (b.new_value.cpu().numpy() == -7.0).all()
+            return None, g[0], g[1]
+        ok = (index >= 0) & (index < case["n_rows"])
+        rows = np.where(ok, index, 0)
+        cmod.assert_same_bits(b.new_mean.cpu().numpy(), np.where(ok[:, None], mean_of[rows], F(0.0)), f"{name} {what}: new_mean against the model")
+        cmod.assert_same_bits(b.new_value.cpu().numpy(), np.where(ok, value_of[rows], F(0.0)), f"{name} {what}: new_value against the model")
+        assert stats[5] == 0 and stats[6] == np.count_nonzero(~ok) and stats[7] == 0, (what, stats)
+        return stats, g[0], g[1]
+
+    def same(what, got, want):
+        if got[0] is not None:
+            assert np.array_equal(got[0][:5], want[0][:5]), f"{name} {what}: stats {got[0]} against {want[0]}"
+        for net, g, w in (("policy", got[1], want[1]), ("value", got[2], want[2])):
+            assert np.array_equal(g, w), f"{name} {what}: the {net} gradient differs in {np.count_nonzero(g != w)} of {g.size} elements, by up to {np.abs(g - w).max():.3e}"
+        print(f"{name} {what}: equal")
+
+    def batch(n_batch, placed, seed=0):
+        return tm.turns_index(dead, n_batch, placed, seed)
+
+    ref = run("the live tile alone", a)
+    ref_tail = run("the ragged tile's live rows alone", a[:tail])
+    ref_pair = run("two live tiles alone", pair)
+    for r in (ref, ref_tail, ref_pair):
+        assert r[0][0] > 0 and np.abs(r[1]).max() > 0 and np.abs(r[2]).max() > 0 and np.isfinite(r[1]).all() and np.isfinite(r[2]).all()
+    # (stats[0] = S: a tile's weights added one after the other in binary32, then the tiles)
+    one_by_one = lambda w: functools.reduce(lambda s, x: F(s + x), w, F(0.0))          # noqa: E731
+    assert ref[0][0] == one_by_one(weight[a]) and ref_tail[0][0] == one_by_one(weight[a[:tail]])
+    assert ref_pair[0][0] == F(one_by_one(weight[a]) + one_by_one(weight[live[R:]]))
+    assert not np.array_equal(ref[1], ref_tail[1]) and not np.array_equal(ref[1], ref_pair[1]) and not np.array_equal(ref[2], ref_pair[2])
+    # 1. 258 tiles, the only live rows in tile t: the first turn of workgroup 0 and of the last workgroup, the second turn of workgroup 0,
+    #    the ragged last tile
+    for t in (0, G - 1, G, G + 1):
+        rows = a if t <= G else a[:tail]
+        same(f"live tile {t} of {G + 2}", run(f"tile {t}", batch(B, [(t * R, rows)], t)), ref if t <= G else ref_tail)
+    # 2. a third turn, behind a second turn of zeros
+    same(f"live tile {2 * G} of {3 * G + 1}", run(f"tile {2 * G}", batch((3 * G + 1) * R, [(2 * G * R, a)])), ref)
+    # 3. two live tiles of one workgroup: a, then += b, against a + b of the reduce over two workgroups -- the same one rounding
+    same(f"live tiles 3 and {G + 3} of {G + 4}", run("tiles 3 and 259", batch((G + 4) * R, [(3 * R, a), ((G + 3) * R, live[R:])])), ref_pair)
+    # 4. row numbers -1 and n_rows inside the live tile of a second turn: counted, and the batch that has dead rows in their place
+    holed = a.copy(); holed[[R // 4, R - 3]] = dead[:2]
+    refused = holed.copy(); refused[[R // 4, R - 3]] = (-1, case["n_rows"])
+    with_dead = run("dead rows at two positions", batch(B, [(G * R, holed)], 4))
+    with_refused = run("row numbers -1 and n_rows", batch(B, [(G * R, refused)], 4))
+    assert with_refused[0][6] == 2 and with_dead[0][6] == 0
+    same(f"row numbers -1 and n_rows in tile {G}", with_refused, with_dead)
+    assert not np.array_equal(with_dead[2], ref[2])
+    # 5. stats, new_mean and new_value NULL (behind a call with another gradient): the same gradient
+    same(f"live tile {G} with stats, new_mean and new_value NULL", run("NULL outputs", batch(B, [(G * R, a)], G), null=True), ref)
+    env.close()
+    print(f"turns {name} ok")
 
 
 def collected(opt):
@@ -462,5 +559,5 @@ def ppo_tool(opt):
 if __name__ == "__main__":
     scenario = sys.argv[1]
     options = json.loads(sys.argv[2]) if len(sys.argv) > 2 else {}
-    {"gradient": gradient, "collected": collected, "adam": adam, "determinism": determinism, "guards": guards, "optimises": optimises,
+    {"gradient": gradient, "turns": turns, "collected": collected, "adam": adam, "determinism": determinism, "guards": guards, "optimises": optimises,
      "wrapper": wrapper, "ppo_tool": ppo_tool}[scenario](options)

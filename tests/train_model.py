@@ -5,6 +5,9 @@ must reproduce), the stats and Adam's element step.
 loss_and_grad(case, dtype): binary64 is the reference (np.tanh: the derivative 1 - o*o is then exact calculus); binary32 is "the same
 model in binary32" -- the specified TANH, numpy's float32 products, the batch rows accumulated one after the other -- whose distance from
 the reference sets the tolerance of the device (tests/test_train.py).
+
+CASES: the gradient cases (a - e, turns32 / turns16, mixed / mixed2, edge32 / edge16, uneven); row_layout restates how the host cuts an LDS row and
+chooses 32 or 16 rows a tile, from ftgp_train_grad_device's text; turns_rows / turns_index build the batches of the `turns` scenario.
 """
 import numpy as np
 
@@ -146,15 +149,19 @@ def loss_and_grad(case, dtype=np.float64):
     return gp, gv, stats
 
 
-def conditions(case):
+def conditions(case, high_side=True):
     """What a gradient case must offer, from the binary64 model: the clip binds on both sides and leaves rows free, no row sits at the
-    clip's edge, no relu pre-activation at 0.  A string that names the first miss, or None."""
+    clip's edge, no relu pre-activation at 0.  A string that names the first miss, or None.
+    high_side=False is for a case without noise alone: there logq = 0 and rho = exp(logp) <= 1, so no ratio can pass 1 + clip, whatever
+    the seed; the clip is then asked to bind on the low side only, and every ratio is asserted to be <= 1."""
     t = loss_terms(case, np.float64)
     w, S = t["w"], t["S"]
     off_hi = (w * (~t["active"] & (t["A"] >= 0))).sum() / S
     off_lo = (w * (~t["active"] & (t["A"] < 0))).sum() / S
     on = (w * t["active"]).sum() / S
-    if off_hi < 0.05 or off_lo < 0.05:
+    if not high_side:
+        assert case["noise"] is None and (t["rho"] <= 1).all() and off_hi == 0
+    if (high_side and off_hi < 0.05) or off_lo < 0.05:
         return f"the clip binds on {off_hi:.3f} / {off_lo:.3f} of the weighted rows"
     if on < 0.40:
         return f"only {on:.3f} of the weighted rows are free"
@@ -182,13 +189,133 @@ CASES = {
     "d": (33, (65,), (65,), "tanh", "tanh", 300, 257, "contiguous"),
     "e1": (33, (), (), "tanh", "tanh", 40, 1, "contiguous"),
     "e64": (33, (), (), "tanh", "tanh", 90, 64, "contiguous"),
+    # more tiles than workgroups (258 tiles of 32 and of 16 rows, the last one ragged): workgroups 0 and 1 take a second tile
+    "turns32": (17, (8,), (8,), "tanh", "tanh", 700, 8229, "index"),
+    "turns16": (256, (128,), (128,), "tanh", "tanh", 500, 4115, "index"),
+    # the two nets differ in depth and width; widths that are no multiple of 8 below the last layer; a bias row inside a 32-row tile of k
+    "mixed": (33, (31, 97), (64,), "relu", "tanh", 300, 130, "contiguous"),
+    "mixed2": (33, (), (100, 7, 33), "tanh", "identity", 300, 97, "contiguous"),
+    # the two sides of the tile-size rule: an LDS row of 500 floats (32 rows: 64000 bytes) and of 508 (16 rows)
+    "edge32": (104, (65, 65), (65, 65), "tanh", "tanh", 200, 70, "contiguous"),
+    "edge16": (108, (65, 65), (65, 65), "tanh", "tanh", 200, 70, "contiguous"),
+    # the middle layer 80 -> 24 has 3 x 2 tiles of the weight gradient for four waves: two waves reach the input delta, whose 128 columns
+    # fill a whole delta buffer, while the other two still read the delta in hand -- the two buffers must not share a float
+    "uneven": (33, (80, 24), (80, 24), "tanh", "tanh", 300, 70, "contiguous"),
 }
 LOOSE = ("e1",)      # one row cannot bind the clip on both sides: the conditions are not asked of it
+MAX_WG = 256         # FTGP_TRAIN_MAX_WG: a launch has min(n_tiles, MAX_WG) workgroups, workgroup g takes the tiles g, g + G, ..
 
 
-def make_case(name, seed=0):
+def case_widths(name):
+    """(policy widths, value widths) of a case, inputs and outputs included."""
+    n_in, ph, vh = CASES[name][:3]
+    return (n_in, *ph, 2), (n_in, *vh, 1)
+
+
+def row_layout(policy_widths, value_widths):
+    """(row_floats, tile_rows) as ftgp_train_grad_device lays out an LDS row: every layer's outputs (the input among them) padded to 4
+    floats, the longer of the two nets; two delta buffers of ld_max floats, the widest layer output rounded up to 64; four floats more
+    where the row would be an even number of float4; 32 rows a tile where they fit 63 KiB, 16 otherwise."""
+    act_floats, ld_max = 0, 64
+    for widths in (policy_widths, value_widths):
+        act_floats = max(act_floats, sum((n + 3) & ~3 for n in widths))
+        ld_max = max([ld_max] + [(n + 63) & ~63 for n in widths[1:]])
+    row_floats = act_floats + 2 * ld_max
+    if (row_floats // 4) % 2 == 0:
+        row_floats += 4
+    return row_floats, 32 if 32 * row_floats * 4 <= 63 * 1024 else 16
+
+
+def n_tiles(name):
+    B = CASES[name][6]
+    R = row_layout(*case_widths(name))[1]
+    return (B + R - 1) // R
+
+
+def ordered_sum(terms, R, G=MAX_WG, wide=False):
+    """The sum of one binary32 term per batch row in the order include/ftgp.h gives for the device: a tile's R rows one after the
+    other; tile g, g + G, .. into workgroup g of G = min(tiles, 256), in the order it takes them; the workgroups' sums g ascending.
+    In binary32, or (wide) carried in binary64 all the way, with a binary64 result.
+    (A batch position past the batch adds +0, which changes nothing.)"""
+    T = np.float64 if wide else F
+    terms = np.asarray(terms, dtype=F)
+    tiles = (terms.size + R - 1) // R
+    t = np.zeros(tiles * R, dtype=F)
+    t[:terms.size] = terms
+    t = t.reshape(tiles, R).astype(T)
+    tile_sum = np.zeros(tiles, dtype=T)
+    for r in range(R):
+        tile_sum = (tile_sum + t[:, r]).astype(T)
+    G = min(tiles, G)
+    group = np.zeros(G, dtype=T)
+    for first in range(0, tiles, G):
+        turn = tile_sum[first:first + G]
+        group[:turn.size] = (group[:turn.size] + turn).astype(T)
+    total = T(0.0)
+    for g in range(G):
+        total = T(total + group[g])
+    return total
+
+
+def ordered_stats(case, R, value32):
+    """stats [0], [2] and [4] to the bit: the three whose terms binary32 fixes -- w; w * (0.5 * (e * e)) with e = v - ret on the value
+    the forward pass gives to the bit (value32, one per batch row); w where |rho - 1| > clip, which conditions() keeps 1e-4 clear of a
+    tie.  S is the binary32 ordered_sum of w; the other two are added up in binary64 along the same order, divided by S in binary64 and
+    rounded once.  ([1] and [3] carry the device's exp.)"""
+    rows = case["rows"]
+    w = (case["weight"][rows] if case["weight"] is not None else np.ones(len(rows))).astype(F)
+    e = (np.asarray(value32, dtype=F) - case["ret"][rows]).astype(F)
+    t = loss_terms(case, np.float64)
+    S = ordered_sum(w, R)
+    half_sq = (F(0.5) * (e * e).astype(F)).astype(F)
+    over_S = lambda terms: F(ordered_sum(terms, R, wide=True) / np.float64(S))          # noqa: E731
+    return S, over_S((w * half_sq).astype(F)), over_S(np.where(np.abs(t["rho"] - 1) > t["c"], w, F(0.0)))
+
+
+def ratio_span(case):
+    """(largest |logp - logq|, whether every rho is finite) over EVERY row of the case's buffers, in the binary32 model: what a test
+    that gives rows a weight of 0 needs, since 0 * infinity would be a NaN of its own making."""
+    every = dict(case, rows=np.arange(case["n_rows"]), weight=None)
+    t = loss_terms(every, np.float32)
+    return float(np.abs(t["logp"] - t["logq"]).max()), bool(np.isfinite(t["rho"]).all() and np.isfinite(t["v"]).all())
+
+
+def turns_tail(name):
+    """The rows of the last tile of a turns* case, two tiles past the workgroups."""
+    R = row_layout(*case_widths(name))[1]
+    return CASES[name][6] - (MAX_WG + 1) * R
+
+
+def turns_rows(case, R, tail):
+    """For the `turns` scenario: (live, dead, weight).  live: 2 * R distinct rows of the buffers, the only ones with a weight (in
+    [0.5, 1.5)); dead: every other row, weight 0.  Redrawn until the clip leaves a row free among the first `tail` live rows and in the
+    second R of them: every group of live rows a call is made on has a policy gradient that is not zeros."""
+    for attempt in range(200):
+        rng = np.random.default_rng([7, R, attempt])
+        perm = rng.permutation(case["n_rows"]).astype(np.int32)
+        live, dead = perm[:2 * R], perm[2 * R:]
+        weight = np.zeros(case["n_rows"], dtype=F)
+        weight[live] = rng.uniform(0.5, 1.5, 2 * R).astype(F)
+        active = loss_terms(dict(case, rows=live, weight=weight))["active"]
+        if active[:tail].any() and active[R:].any():
+            return live, dead, weight
+    raise AssertionError("no draw of live rows left the clip free where it is needed")
+
+
+def turns_index(dead, B, placed, seed=0):
+    """An index of B batch positions: dead rows drawn at random everywhere, but rows[k] at position at + k for every (at, rows) of
+    `placed`."""
+    index = np.random.default_rng([11, seed, B]).choice(dead, B).astype(np.int32)
+    for at, rows in placed:
+        assert 0 <= at and at + len(rows) <= B
+        index[at:at + len(rows)] = rows
+    return index
+
+
+def make_case(name, seed=0, with_noise=True):
     """A gradient case: nets, buffers of n_rows rows and the batch rows.  `mean` comes from a copy of the policy perturbed by
-    0.03 * N(0, 1), so that the clip binds; the seed is redrawn until conditions() holds (not for LOOSE)."""
+    0.03 * N(0, 1), so that the clip binds; the seed is redrawn until conditions() holds (not for LOOSE).  with_noise=False: the case
+    with noise = None (the draws are made all the same), its seed redrawn until conditions(high_side=False) holds."""
     n_in, ph, vh, hidden, out_act, n_rows, B, how = CASES[name]
     for attempt in range(200):
         rng = np.random.default_rng([seed, attempt, sum(map(ord, name))])
@@ -211,11 +338,12 @@ def make_case(name, seed=0):
         else:
             first_row = n_rows - B - 3 if name != "b" else 5
             rows, index = np.arange(first_row, first_row + B, dtype=np.int32), None
-        case = dict(name=name, policy=policy, value=value, inputs=inputs, mean=mean, noise=noise, advantage=advantage, ret=ret, weight=weight,
-                    rows=rows, index=index, first_row=first_row, n_rows=n_rows, std=(F(0.3), F(0.1)), clip=F(0.2), value_coef=F(0.5))
-        if name in LOOSE or conditions(case) is None:
+        case = dict(name=name, policy=policy, value=value, inputs=inputs, mean=mean, noise=noise if with_noise else None, advantage=advantage,
+                    ret=ret, weight=weight, rows=rows, index=index, first_row=first_row, n_rows=n_rows, std=(F(0.3), F(0.1)), clip=F(0.2),
+                    value_coef=F(0.5))
+        if name in LOOSE or conditions(case, high_side=with_noise) is None:
             return case
-    raise AssertionError(f"case {name}: no seed met the batch conditions: {conditions(case)}")
+    raise AssertionError(f"case {name}: no seed met the batch conditions: {conditions(case, high_side=with_noise)}")
 
 
 def stat_scales(case):
