@@ -141,8 +141,11 @@ typedef struct FtgpConfig {
                                          march    raycast.py:5-21 on the exact Euclidean distance transform of the wall image (the recipe of
                                                   custom.py:1149-1153 / raycast.py:24-27, built at ftgp_create: integer squared distances, one sqrt)
                                          range    (scan / width) * map_size (custom.py:1392-1393), stored as binary32
-                                       int() truncates toward zero and negative indices wrap like numpy's; a lookup past the right / bottom edge -- the
-                                       reference's IndexError -- ends the ray with range -1.  The rays see walls only (no other cars), as there. */
+                                       int() truncates toward zero and negative indices wrap like numpy's: an index is valid iff -width <= int(x) < width
+                                       and -height <= int(y) < height.  A lookup past the right / bottom edge, or below -width / -height -- the reference's
+                                       IndexError either way -- ends the ray with range -1, whatever it had accumulated.  A ray whose lookup was valid
+                                       ends without error, with the distance it has, once x < 0 or y < 0 (the loop condition, tested after the lookup).
+                                       The rays see walls only (no other cars), as there. */
     int32_t reserved2;
     double map_size;                /* FAKELIDAR: world size of the map, 20 * scale = 40 (custom.py:1155,1382; mushr.em.xml:16-18); <= 0 means 40 */
     const double *fan_dirs;         /* optional [n_rays][2]: body-frame unit directions of the rangefinder fan; NULL = the sites of
@@ -1245,8 +1248,9 @@ int ftgp_metrics_allgather_end(FtgpEnv *env, double *out);
  *   scan      double[n_origins][rangefinders]        accumulated distance per ray (pixels)
  *   points    double[n_origins][rangefinders][2]     end point per ray
  * Same loop as the reference: while dt[int(y), int(x)] > eps and 0 <= x <= W and 0 <= y <= H: advance by dt.
- * int() truncates toward zero and negative indices wrap like numpy's; an index past the end is the reference's
- * IndexError and is reported as FTGP_ERR_ARG.  Standalone: needs no FtgpEnv.
+ * int() truncates toward zero and negative indices wrap like numpy's; an index past the end (>= W / H) or below -W / -H
+ * is the reference's IndexError and is reported as FTGP_ERR_ARG.  A ray whose lookup was valid ends without error once
+ * x < 0 or y < 0.  Standalone: needs no FtgpEnv.
  */
 int ftgp_fakelidar(int device_id, const double *dt, int H, int W, int n_origins, const double *origins, int rangefinders,
                    const double *cosines, const double *sines, double eps, double *scan, double *points);

@@ -24,6 +24,9 @@ Fixtures (data only -- inputs and the reference's outputs):
   g9_reference_drivers.npz / .json  the reference's nidc / fast / drivers.template objects driving closed loops through the host
                    path (ft_grandprix_amd.sim) on the CPU oracle: template/cars/cars.json (the roster itself is stored) for 250 steps,
                    nidc and fast alone for 300, the template driver for 50 (every value it returned, and its arity)
+  g10_fakelidar_edges.npz  raycast.fakelidar at the image's edges, one ray per call (a ray whose call raises IndexError reads -1): five small
+                   and ragged synthetic images, 64 poses each on and off the image, the default fan at R = 72 and 37, every ray's class
+                   (normal, left / top exit, IndexError, zero range); and whole calls on two images with walls on the right and bottom only
 
 custom.py imports mujoco / dearpygui / empy / svg.path, which are not installed; they are replaced by
 MagicMock entries in sys.modules for the import only -- none of the functions
@@ -433,7 +436,109 @@ def gen_g9():
     print("g9: ok")
 
 
+# ----------------------------------------------------------------------------- G10
+G10_IMAGES = ((1, 1, 1.0), (7, 45, 0.02), (33, 5, 0.1), (61, 127, 0.001), (200, 333, 0.0005))      # (H, W, wall density)
+G10_L_IMAGES = ((61, 127), (96, 64))
+G10_RAYS = (72, 37)
+G10_NORMAL, G10_LEFT_TOP, G10_INDEX_ERROR, G10_ZERO = 0, 1, 2, 3
+
+
+def gen_g10():
+    """FAKELIDAR at the image's edges: small and ragged synthetic images, car poses on and off the image (beyond -W and -H included), the
+    default fan at an even and an odd R.  raycast.fakelidar raises IndexError for a whole call, so it is called one ray at a time: a ray
+    that raises reads -1, the others (scan / W) * 40 as binary32 (custom.py:1392-1393).  Inputs as in G8; everything from
+    `fakelidar(...)` on is the reference's own code.  Plus two images with walls on the right and bottom only, whole calls from inside:
+    nothing raises there, and nearly half the rays leave through the left / top edge."""
+    from scipy.ndimage import distance_transform_edt
+    from tests.helpers import draw_walls, pack_walls
+    rng = np.random.default_rng(2)
+    data = {}
+    s = 20 * 2.0
+    fans = {}
+    for R in G10_RAYS:
+        phi = ((360.0 / R) * np.arange(R) - 90.0) * (np.pi / 180.0)         # mushr.em.xml:112-117
+        fans[R] = data[f"fan_{R}"] = np.stack([np.sin(phi), -np.cos(phi)], axis=1)
+    for k, (H, W, p) in enumerate(G10_IMAGES):
+        wall = draw_walls(rng, H, W, p)
+        dt = distance_transform_edt(~wall)
+        n = 64
+        uv = np.concatenate([rng.uniform(0.05, 0.95, (n // 2, 2)), rng.uniform(-0.1, 1.1, (n // 2, 2))])
+        xy = np.stack([uv[:, 0] * s, -uv[:, 1] * s], axis=1)
+        yaw = rng.uniform(-np.pi, np.pi, n)
+        qw0, qz0 = np.cos(yaw / 2), np.sin(yaw / 2)
+        nrm = np.sqrt(qw0 * qw0 + qz0 * qz0)                                # ftgp_set_pose normalises the quaternion
+        qw, qz = qw0 / nrm, qz0 / nrm
+        ch, sh = 1.0 - 2.0 * (qz * qz), 2.0 * (qw * qz)
+        i_x = (xy[:, 0] / s) * W                                            # custom.py:1383
+        i_y = -(xy[:, 1] / s) * H                                           # custom.py:1384
+        data[f"img{k}_shape"] = np.array([H, W], dtype=np.int64)
+        data[f"img{k}_bits"] = pack_walls(wall)
+        data[f"img{k}_xy"], data[f"img{k}_quat"] = xy, np.stack([qw0, qz0], axis=1)
+        for R in G10_RAYS:
+            fan = fans[R]
+            rngs = np.zeros((n, R), dtype=np.float32); cls = np.zeros((n, R), dtype=np.uint8)
+            for c in range(n):
+                dxw = ch[c] * fan[:, 0] - sh[c] * fan[:, 1]
+                dyw = sh[c] * fan[:, 0] + ch[c] * fan[:, 1]
+                for j in range(R):
+                    try:
+                        ranges, pts = raycast.fakelidar(i_x[c], i_y[c], dt, 1, dxw[j:j + 1], -dyw[j:j + 1])
+                    except IndexError:
+                        rngs[c, j], cls[c, j] = -1.0, G10_INDEX_ERROR
+                        continue
+                    d = ranges[0]
+                    ranges = ranges.copy()
+                    ranges /= W                                             # custom.py:1392 (original_width)
+                    ranges *= s                                             # custom.py:1393
+                    rngs[c, j] = ranges.astype(np.float32)[0]
+                    cls[c, j] = G10_ZERO if d == 0 else G10_LEFT_TOP if (pts[0, 0] < 0 or pts[0, 1] < 0) else G10_NORMAL
+            data[f"img{k}_{R}_ranges"], data[f"img{k}_{R}_class"] = rngs, cls
+            share = np.bincount(cls.ravel(), minlength=4) / cls.size
+            print(f"g10: {H} x {W}, R = {R}: normal / left-top / IndexError / zero = {np.round(share, 3)}")
+            if R == 72 and (H, W) != (1, 1):
+                assert share.min() >= 0.05, (H, W, share)
+    for k, (H, W) in enumerate(G10_L_IMAGES):
+        wall = np.zeros((H, W), dtype=bool)
+        wall[:, W - 2:] = True
+        wall[H - 2:, :] = True
+        dt = distance_transform_edt(~wall)
+        n, R = 32, 36
+        origins = np.stack([rng.uniform(1.0, W - 4.0, n), rng.uniform(1.0, H - 4.0, n)], axis=1)
+        yaw = rng.uniform(-np.pi, np.pi, n)
+        scan = np.zeros((n, R)); pts = np.zeros((n, R, 2)); angs = np.zeros((n, R))
+        for c in range(n):
+            angs[c] = np.linspace(yaw[c] + np.pi, yaw[c] - np.pi, R, endpoint=False)      # custom.py:1387
+            scan[c], pts[c] = raycast.fakelidar(origins[c, 0], origins[c, 1], dt, R, np.cos(angs[c]), np.sin(angs[c]))      # no call may raise
+        left = ((pts[..., 0] < 0) | (pts[..., 1] < 0)).mean()
+        print(f"g10: L-wall {H} x {W}: {left:.3f} of the rays end left of / above the image")
+        assert left >= 0.2, (H, W, left)
+        data[f"L{k}_shape"] = np.array([H, W], dtype=np.int64)
+        data[f"L{k}_bits"] = pack_walls(wall)
+        data[f"L{k}_origins"], data[f"L{k}_angles"], data[f"L{k}_scan"], data[f"L{k}_points"] = origins, angs, scan, pts
+    # single rays on a constant 64 x 64 table: (fill, orig_x, orig_y, dx, dy) -> does the call raise, and what it returns if not
+    cases = np.array([[10.0, 60.0, 32.0, 1.0, 0.0],          # past the right edge
+                      [10.0, 32.0, 60.0, 0.0, 1.0],          # past the bottom edge
+                      [100.0, 10.0, 32.0, -1.0, 0.0],        # one jump to int(x) = -90 < -W
+                      [100.0, 32.0, 10.0, 0.0, -1.0],        # ... to int(y) = -90 < -H
+                      [20.0, 10.0, 32.0, -1.0, 0.0],         # int(x) = -10 wraps: a valid look-up, then x < 0 ends the ray
+                      [20.0, 32.0, 10.0, 0.0, -1.0]])
+    raises = np.zeros(len(cases), dtype=bool); e_scan = np.full(len(cases), np.nan); e_pts = np.full((len(cases), 2), np.nan)
+    for c, (fill, ox, oy, dx, dy) in enumerate(cases):
+        try:
+            sc, pt = raycast.fakelidar(ox, oy, np.full((64, 64), fill), 1, np.array([dx]), np.array([dy]))
+            e_scan[c], e_pts[c] = sc[0], pt[0]
+        except IndexError:
+            raises[c] = True
+    assert raises.tolist() == [True, True, True, True, False, False], raises
+    data["single_cases"], data["single_raises"], data["single_scan"], data["single_points"] = cases, raises, e_scan, e_pts
+    np.savez_compressed(os.path.join(HERE, "g10_fakelidar_edges.npz"), **data)
+    print("g10: ok")
+
+
 if __name__ == "__main__":
+    if "--only-g10" in sys.argv:
+        gen_g10()
+        raise SystemExit(0)
     if "--only-g8" in sys.argv:
         gen_g8()
         raise SystemExit(0)
@@ -443,6 +548,7 @@ if __name__ == "__main__":
     gen_g6()
     gen_g7()
     gen_g8()
+    gen_g10()
     if "--only-new" in sys.argv:
         raise SystemExit(0)
     gen_g1()

@@ -90,6 +90,160 @@ def g2_fakelidar(track):
     return np.load(golden(f"g2_fakelidar_{track}.npz"))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Fixture G10 (FAKELIDAR at the image's edges): tests/test_fakelidar_mode.py on the oracle, tests/fakelidar_edges_child.py on the GPU.
+G10_IMAGES = ((1, 1), (7, 45), (33, 5), (61, 127), (200, 333))            # (H, W) of img0 .. img4
+G10_L_IMAGES = ((61, 127), (96, 64))
+G10_RAYS = (72, 37)
+G10_NORMAL, G10_LEFT_TOP, G10_INDEX_ERROR, G10_ZERO = 0, 1, 2, 3          # a ray's class (tests/golden/make_golden.py: gen_g10)
+MAP_SIZE = 40.0                                                            # 20 * scale, custom.py:1155,1382
+
+
+def g10():
+    return np.load(golden("g10_fakelidar_edges.npz"))
+
+
+def pack_walls(wall):
+    """bool [H, W] -> the Track's bits: uint32 [H, ceil(W / 32)], bit x & 31 of word x >> 5."""
+    W = wall.shape[1]
+    return np.ascontiguousarray(np.packbits(np.pad(wall, ((0, 0), (0, (-W) % 32))), axis=1, bitorder="little").view(np.uint32))
+
+
+def draw_walls(rng, H, W, p):
+    """A random wall image of density p, bool [H, W], with one wall pixel forced if none was drawn."""
+    wall = rng.uniform(size=(H, W)) < p
+    if not wall.any():
+        wall[rng.integers(H), rng.integers(W)] = True
+    return wall
+
+
+ODD_IMAGES = ((1, 1, 1.0), (7, 45, 0.02), (33, 5, 0.1), (61, 127, 0.001), (40, 40, 0.5), (19, 70, 0.0))       # (H, W, wall density)
+
+
+def odd_walls():
+    """Ragged shapes, a single wall pixel, walls on the border, a wall-free column set: the images of the distance transform's tests, the
+    same for the oracle and the GPU."""
+    rng = np.random.default_rng(3)
+    return [draw_walls(rng, H, W, p) for (H, W, p) in ODD_IMAGES]
+
+
+def image_track(bits, H, W):
+    """A Track of a synthetic H x W wall image on the 40 x 40 map; the centre-line (it only places the spawn and feeds K3) is
+    `small-circle`'s."""
+    import dataclasses
+    return dataclasses.replace(load_track("small-circle"), name=f"image-{H}x{W}", width=int(W), height=int(H), bits=np.ascontiguousarray(bits, dtype=np.uint32),
+                               px_size_x=MAP_SIZE / W, px_size_y=MAP_SIZE / H)
+
+
+def g10_track(g, key):
+    H, W = (int(v) for v in g[f"{key}_shape"])
+    return image_track(g[f"{key}_bits"], H, W)
+
+
+def fakelidar_step(lib, track, xy, quat, R, fan=None, cars_per_env=1, envs_per_track=None):
+    """One ftgp_step in FAKELIDAR mode with car i posed at (xy[i], quat[i]) and at rest: the scans the drivers would be handed,
+    float32 [n_cars, R].  track: a Track, or a list of them with envs_per_track (a multi-track handle)."""
+    n = len(xy)
+    assert n % cars_per_env == 0
+    with capi.Env(lib, track, n_envs=n // cars_per_env, cars_per_env=cars_per_env, n_rays=R, lidar_mode="fakelidar", fan_dirs=fan,
+                  envs_per_track=envs_per_track) as e:
+        pose = e.pose()
+        pose[:, 0:2] = xy
+        pose[:, 3], pose[:, 6] = quat[:, 0], quat[:, 1]
+        pose[:, 7:] = 0.0
+        e.set_pose(pose)
+        e.step(1)                       # sensors are evaluated at the pose the step starts from
+        return e.lidar()
+
+
+def g10_style_poses(rng, n):
+    """The pose recipe of G10: world x = u * 40, y = -v * 40 with u, v in [0.05, 0.95] for the first half and in [-0.1, 1.1] for the
+    other (starts off the image on every side), yaw uniform.  Returns (xy [n, 2], (qw, qz) [n, 2])."""
+    uv = np.concatenate([rng.uniform(0.05, 0.95, (n // 2, 2)), rng.uniform(-0.1, 1.1, (n - n // 2, 2))])
+    yaw = rng.uniform(-np.pi, np.pi, n)
+    return np.stack([uv[:, 0] * MAP_SIZE, -uv[:, 1] * MAP_SIZE], axis=1), np.stack([np.cos(yaw / 2), np.sin(yaw / 2)], axis=1)
+
+
+G10_LOOPS = ((1, "nidc", 72), (3, "fast", 37), (2, "nidc", 1080))         # (cars per env, policy, R) of the closed loops on the 200 x 333 image
+
+
+def g10_closed_loop(g, o, what):
+    """Two handles on the 200 x 333 image of G10, the cars put on G10-style poses: rollouts of 1, 3 and 40 steps, scans and progress bit
+    for bit, poses to 1e-12.  Every scan holds rays that read -1, rays that read 0 and positive ranges: the drivers (window-only tables in
+    the multi-step launches) are handed all three."""
+    xy, quat = g10_style_poses(np.random.default_rng(11), g.n_cars)
+    for e in (g, o):
+        pose = e.pose()
+        pose[:, 0:2] = xy
+        pose[:, 3], pose[:, 6] = quat[:, 0], quat[:, 1]
+        pose[:, 7:] = 0.0
+        e.set_pose(pose)
+    for n in (1, 3, 40):
+        g.rollout(what, n); o.rollout(what, n)
+        r = g.lidar()
+        kinds = [int((r == -1.0).sum()), int((r == 0.0).sum()), int((r > 0).sum())]
+        print(f"{what}, {g.cars_per_env} cars, R = {g.n_rays}, after {n} steps: -1 / 0 / positive = {kinds} of {r.size}")
+        assert min(kinds) > 0 and sum(kinds) == r.size, kinds
+        np.testing.assert_array_equal(r, o.lidar(), err_msg=f"scans after the rollout of {n}")
+        np.testing.assert_array_equal(g.progress(), o.progress(), err_msg=f"progress after the rollout of {n}")
+        np.testing.assert_allclose(g.pose(), o.pose(), rtol=0, atol=1e-12, err_msg=f"poses after the rollout of {n}")
+        np.testing.assert_array_equal(g.metrics_local(), o.metrics_local())
+
+
+def check_g10_classes(g):
+    """What the generator asserted of the fixture: on every image but 1 x 1 each class holds at least 5 % of the rays at R = 72; and
+    the classes say what the ranges are."""
+    for k, (H, W) in enumerate(G10_IMAGES):
+        assert tuple(g[f"img{k}_shape"]) == (H, W)
+        for R in G10_RAYS:
+            cls, r = g[f"img{k}_{R}_class"], g[f"img{k}_{R}_ranges"]
+            assert cls.shape == r.shape == (64, R) and r.dtype == np.float32
+            np.testing.assert_array_equal(cls == G10_INDEX_ERROR, r == -1.0)
+            np.testing.assert_array_equal(cls == G10_ZERO, r == 0.0)
+            assert (r[(cls == G10_NORMAL) | (cls == G10_LEFT_TOP)] > 0).all()
+        share = np.bincount(g[f"img{k}_72_class"].ravel(), minlength=4) / (64 * 72)
+        print(f"G10 {H} x {W}: normal / left-top / IndexError / zero = {np.round(share, 3)}")
+        if (H, W) != (1, 1):
+            assert share.min() >= 0.05, (H, W, share)
+
+
+def check_g10_steps(lib, g, images=range(5), cars_per_env=1):
+    """One ftgp_step from the G10 poses, default fan, every image and both R: the fixture's ranges bit for bit.  cars_per_env = 3: 22
+    envs, the first 66 poses of the cyclic sequence (the rays see walls only, so a pose gives its row whoever stands beside it)."""
+    n = 64 if cars_per_env == 1 else 66
+    idx = np.arange(n) % 64
+    for k in images:
+        t = g10_track(g, f"img{k}")
+        for R in G10_RAYS:
+            got = fakelidar_step(lib, t, g[f"img{k}_xy"][idx], g[f"img{k}_quat"][idx], R, None, cars_per_env)
+            np.testing.assert_array_equal(got, g[f"img{k}_{R}_ranges"][idx], err_msg=f"G10 image {k} ({t.height} x {t.width}), R = {R}, {cars_per_env} cars per env")
+
+
+def check_g10_standalone(lib, g):
+    """raycast.fakelidar's whole calls on the L-wall images (nothing raises, nearly half the rays leave through the left / top edge),
+    and six single rays of which four raise: the stand-alone entry, scan and points bit for bit."""
+    from scipy.ndimage import distance_transform_edt
+    for k, (H, W) in enumerate(G10_L_IMAGES):
+        t = g10_track(g, f"L{k}")
+        assert (t.height, t.width) == (H, W)
+        dt = distance_transform_edt(~t.wall_mask())
+        ang, pts = g[f"L{k}_angles"], g[f"L{k}_points"]
+        assert ((pts[..., 0] < 0) | (pts[..., 1] < 0)).mean() >= 0.2
+        scan, points = capi.fakelidar(lib, dt, g[f"L{k}_origins"], np.cos(ang), np.sin(ang), eps=2.0)
+        np.testing.assert_array_equal(scan, g[f"L{k}_scan"], err_msg=f"L-wall image {H} x {W}: scan")
+        np.testing.assert_array_equal(points, pts, err_msg=f"L-wall image {H} x {W}: points")
+    for (fill, ox, oy, dx, dy), raises, want, want_pt in zip(g["single_cases"], g["single_raises"], g["single_scan"], g["single_points"]):
+        call = lambda: capi.fakelidar(lib, np.full((64, 64), fill), [[ox, oy]], [[dx]], [[dy]])
+        if raises:
+            try:
+                call()
+            except capi.FtgpError:
+                continue
+            raise AssertionError(f"no error for the ray ({ox}, {oy}) + t ({dx}, {dy}) on a table of {fill}: the reference raises IndexError")
+        scan, points = call()
+        assert scan[0, 0] == want and tuple(points[0, 0]) == tuple(want_pt), (scan, points, want, want_pt)
+
+
 def oracle_policy(lib, policy, scan_f32, last_steer=0.0):
     import ctypes as C
     s = np.ascontiguousarray(scan_f32, dtype=np.float32)

@@ -9,16 +9,26 @@ Pins (fixtures produced by RUNNING the reference, tests/golden/make_golden.py):
   the distance transform itself: built without scipy (exact integer squared distances, one sqrt), compared with
       scipy.ndimage.distance_transform_edt (the reference's recipe, custom.py:1152-1153) here and by SHA-256 in G8
 
-CPU: the oracle; `-m gpu`: libftgp.so through the C-ABI, and closed loops GPU against oracle.
+  G10 raycast.fakelidar at the image's edges, one ray per call (a ray whose call raises IndexError reads -1): small and ragged synthetic
+      images, poses on and off the image, R = 72 and 37 -- equal bit for bit to one ftgp_step; whole calls on images walled on the right
+      and bottom only (half the rays leave through the left / top edge, none raises) -- equal bit for bit to the stand-alone entry
+
+CPU: the oracle; `-m gpu`: libftgp.so through the C-ABI, and closed loops GPU against oracle.  The G10 scenarios run on the GPU one per
+fresh process (tests/fakelidar_edges_child.py).
 """
+import functools
 import hashlib
+import os
+import re
 
 import numpy as np
 import pytest
 
 from ft_grandprix_amd import capi
 from ft_grandprix_amd.track import load_track
-from tests.helpers import g2_fakelidar, golden
+from tests import children
+from tests.helpers import (check_g10_classes, check_g10_standalone, check_g10_steps, fakelidar_step, g10, g10_track, g2_fakelidar, golden, image_track,
+                           odd_walls, pack_walls)
 
 TRACKS = ["track", "circle", "small-circle", "inkscape"]
 MAP = 40.0            # 20 * scale, custom.py:1155,1382
@@ -104,18 +114,10 @@ def test_oracle_distance_transform_is_scipys(oracle, name):
 
 def test_oracle_distance_transform_on_odd_images(oracle):
     """Ragged shapes, a single wall pixel, walls on the border, a wall-free column set: against scipy."""
-    import dataclasses
     from scipy.ndimage import distance_transform_edt
-    from ft_grandprix_amd.track import Track
-    rng = np.random.default_rng(3)
-    base = load_track("small-circle")
-    for (H, W, p) in ((1, 1, 1.0), (7, 45, 0.02), (33, 5, 0.1), (61, 127, 0.001), (40, 40, 0.5), (19, 70, 0.0)):
-        wall = rng.uniform(size=(H, W)) < p
-        if not wall.any():
-            wall[rng.integers(H), rng.integers(W)] = True
-        bits = np.packbits(np.pad(wall, ((0, 0), (0, (-W) % 32))), axis=1, bitorder="little").view(np.uint32)
-        t = dataclasses.replace(base, width=W, height=H, bits=np.ascontiguousarray(bits), px_size_x=MAP / W, px_size_y=MAP / H)
-        with capi.Env(oracle, t, n_envs=1, n_rays=8, lidar_mode="fakelidar") as e:
+    for wall in odd_walls():
+        H, W = wall.shape
+        with capi.Env(oracle, image_track(pack_walls(wall), H, W), n_envs=1, n_rays=8, lidar_mode="fakelidar") as e:
             dt = np.empty((H, W))
             assert oracle.dll.oracle_get_distance_field(e.h, dt.ctypes.data) == 0
         np.testing.assert_array_equal(dt, distance_transform_edt(~wall), err_msg=f"{H}x{W}")
@@ -143,6 +145,28 @@ def test_oracle_rays_that_leave_the_image_read_minus_one_and_negative_indices_wr
         e.step(1)
         r = e.lidar()[0]
     assert (r == -1.0).any() and (r >= 0).any()
+
+
+def test_g10_holds_every_class_of_ray():
+    """The generator's condition, from the fixture: on every image but 1 x 1 each of normal, left / top exit, IndexError and zero range
+    holds at least 5 % of the rays at R = 72."""
+    check_g10_classes(g10())
+
+
+@pytest.mark.parametrize("image", range(5))
+def test_oracle_step_reproduces_the_reference_at_the_image_edges_g10(oracle, image):
+    """Poses on and off small and ragged images, R = 72 and 37: raycast.fakelidar called one ray at a time, a raising ray reads -1."""
+    g = g10()
+    check_g10_steps(oracle, g, images=[image])
+    t = g10_track(g, f"img{image}")                      # the stored fan is the default one
+    got = fakelidar_step(oracle, t, g[f"img{image}_xy"], g[f"img{image}_quat"], 37, g["fan_37"])
+    np.testing.assert_array_equal(got, g[f"img{image}_37_ranges"])
+
+
+def test_oracle_standalone_fakelidar_wraps_negative_indices_g10(oracle):
+    """Whole calls from inside images walled on the right and bottom only: about half the rays end left of or above the image, none
+    raises; and single rays that do raise, past either pair of edges."""
+    check_g10_standalone(oracle, g10())
 
 
 def test_fakelidar_mode_is_refused_where_it_does_not_apply(oracle):
@@ -194,6 +218,48 @@ def test_gpu_closed_loop_in_fakelidar_mode_matches_the_oracle(product, oracle, n
             np.testing.assert_allclose(g.pose(), o.pose(), rtol=0, atol=1e-12)
             np.testing.assert_array_equal(g.metrics_local(), o.metrics_local())
         assert g.kernel_name().endswith(", true>")
+
+
+# ------------------------------------------------------------------------------------------------ GPU: the image's edges (G10)
+# One scenario per fresh process (tests/fakelidar_edges_child.py), each under a time limit.
+run_child = functools.partial(children.run_child, os.path.join(children.ROOT, "tests", "fakelidar_edges_child.py"), timeout=120)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cars_per_env,cars_per_block,cars", [(1, None, 1), (1, 5, 5), (3, 12, 12)])
+def test_gpu_step_reproduces_the_reference_at_the_image_edges_g10(cars_per_env, cars_per_block, cars):
+    """march_fake()'s `bad` lane, both wrap adds, the 0 > x and 0 > y exits and the delivery of -1: every G10 image at R = 72 and 37
+    (an odd R: unpaired sweep tasks).  64 envs of one car in workgroups of one car and of five (13 workgroups, the last with four); 22
+    envs of three in workgroups of twelve (the MULTI kernel, the last workgroup with six cars)."""
+    out = run_child("edges", cars_per_env=cars_per_env, cars_per_block=cars_per_block)
+    shapes = [int(a) for a in re.findall(r"ftgp_create: (\d+) cars x \d+ waves per workgroup", out)]
+    assert shapes and set(shapes) == {cars}, out[-2000:]
+
+
+@pytest.mark.gpu
+def test_gpu_step_at_the_image_edges_on_a_two_track_handle_g10():
+    """The 61 x 127 and the 200 x 333 image in one handle, 40 + 24 envs: every env marches its own track's table with its own W and H;
+    and each track's distance transform is scipy's."""
+    run_child("edges_tracks")
+
+
+@pytest.mark.gpu
+def test_gpu_distance_transform_on_odd_images_is_scipys():
+    """ftgp_edt_kernel's wall-free columns (g == 65535), its k * k >= best cut and the image borders: as arrays against scipy."""
+    run_child("edt")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config", range(3))
+def test_gpu_closed_loop_from_poses_off_the_image_matches_the_oracle(config):
+    """The drivers are handed -1, 0 and positive ranges, in multi-step launches through the window-only tables."""
+    run_child("loop", config=config)
+
+
+@pytest.mark.gpu
+def test_gpu_standalone_fakelidar_wraps_negative_indices_g10():
+    """ftgp_fakelidar_kernel's `xi += W` / `yi += H`, and the IndexError past either pair of edges."""
+    run_child("standalone")
 
 
 @pytest.mark.gpu
