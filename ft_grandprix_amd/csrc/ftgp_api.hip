@@ -195,25 +195,13 @@ struct FtgpEnv {
     bool dyn_on = false;              // step launches run the DYN instantiations
     DynArgs dyn{};                    // the handle's own row and the wheel-load rule (the buffers are filled in per call)
     DevBuf<double> d_dyn_rows;        // [n_cars][FTGP_DYN_DOUBLES] landing buffer of the host setter, allocated on first use
-    // network drivers (ftgp_set_net)
-    DevBuf<NetDev> d_nets;            // [FTGP_MAX_NETS] the records the kernels read; allocated by the first setter call (ensure_nets)
-    NetDev nets[FTGP_MAX_NETS] = {};  // their host mirror (defined = 0: an empty slot)
-    FtgpNetDesc net_desc[FTGP_MAX_NETS] = {};     // the descriptions as the caller gave them (ftgp_get_net)
-    FtgpNetFrame net_frame[FTGP_MAX_NETS] = {};   // ... and the frame inputs (ftgp_get_net_frame); zeros = none
-    FtgpNetRivals net_rivals[FTGP_MAX_NETS] = {}; // ... and the rival inputs (ftgp_get_net_rivals); zeros = none
-    DevBuf<float> d_net_params[FTGP_MAX_NETS];    // the slots' parameters in the library's layout
-    // populations (ftgp_set_net_population): pop_members[s] > 0 = slot s carries one, and its record's params and env_member point here
-    int pop_members[FTGP_MAX_NETS] = {};
-    DevBuf<float> d_pop_params[FTGP_MAX_NETS];    // [n_members] parameter sets in the library's layout, net_member_stride(n_floats) floats apart
-    DevBuf<int32_t> d_pop_map[FTGP_MAX_NETS];     // [n_envs] the member of every env
+    // network drivers (ftgp_set_net): the two tables the kernels read, and one NetSlot per slot with everything else (below)
+    DevBuf<NetDev> d_nets;            // [FTGP_MAX_NETS] the policies' records; allocated by the first setter call (ensure_nets)
     bool last_net = false;            // the newest launch ran a NET instantiation
-    // value nets (ftgp_set_value_net): one per defined slot at most; read by the VALUE instantiations of ftgp_collect_act_kernel alone, so the
-    // records have a table of their own and the parameter blocks know nothing of them
-    DevBuf<NetDev> d_vnets;           // [FTGP_MAX_NETS] NetDev-shaped records: the layers, the output map in out_scale[0] / out_offset[0], params; allocated by the first setter call
-    NetDev vnets[FTGP_MAX_NETS] = {}; // their host mirror (defined = 0: none)
-    FtgpValueDesc vnet_desc[FTGP_MAX_NETS] = {};  // the descriptions as the caller gave them (ftgp_get_value_net)
-    DevBuf<float> d_vnet_params[FTGP_MAX_NETS];   // the parameters in the library's layout
-    // trainers (ftgp_train_begin): one per slot at most; nothing of it exists on a handle that never asked for one
+    // the value nets' records are read by the VALUE instantiations of ftgp_collect_act_kernel alone, so they have a table of their own and the
+    // parameter blocks know nothing of them
+    DevBuf<NetDev> d_vnets;           // [FTGP_MAX_NETS] NetDev-shaped records: the layers, the output map in out_scale[0] / out_offset[0], params; allocated by the first ftgp_set_value_net
+    // a trainer (ftgp_train_begin): nothing of it exists on a handle that never asked for one
     struct Trainer {
         bool on = false;
         FtgpTrainDesc desc{};
@@ -223,7 +211,30 @@ struct FtgpEnv {
         DevBuf<float> part;               // [FTGP_TRAIN_MAX_WG][n[0] + n[1]] the workgroups' partial sums
         DevBuf<float> stats;              // [2 * FTGP_TRAIN_MAX_WG + 1][FTGP_TRAIN_STATS] the workgroups' partial stats, the stats of the newest gradient, the workgroups' binary64 sums (four doubles each)
         DevBuf<int32_t> sync;             // the gradient's non-finite flag, the reduce kernel's ticket
-    } trainers[FTGP_MAX_NETS];
+    };
+    // One network slot: the policy (ftgp_set_net), and what hangs on it -- a population (ftgp_set_net_population), a value net
+    // (ftgp_set_value_net), a trainer (ftgp_train_begin).
+    struct NetSlot {
+        NetDev net{};                     // host mirror of the slot's record in d_nets (defined = 0: an empty slot)
+        FtgpNetDesc desc{};               // the description as the caller gave it (ftgp_get_net)
+        FtgpNetFrame frame{};             // ... and the frame inputs (ftgp_get_net_frame); zeros = none
+        FtgpNetRivals rivals{};           // ... and the rival inputs (ftgp_get_net_rivals); zeros = none
+        DevBuf<float> d_params;           // the slot's single parameter set in the library's layout
+        int pop_members = 0;              // > 0: the slot carries a population, and its record's params and env_member point here
+        DevBuf<float> d_pop_params;       // [pop_members] parameter sets in the library's layout, net_member_stride(n_floats) floats apart
+        DevBuf<int32_t> d_pop_map;        // [n_envs] the member of every env
+        NetDev vnet{};                    // host mirror of the value net's record in d_vnets (defined = 0: none)
+        FtgpValueDesc vdesc{};            // its description as the caller gave it (ftgp_get_value_net)
+        DevBuf<float> d_vparams;          // its parameters in the library's layout
+        Trainer trainer;
+        // What ends with what.  A trainer steps the slot's single parameter set and its value net, so it ends when a population takes the
+        // set's place and whenever the value net is set or cleared.  The value net reads the policy's inputs, and a population is sets of the
+        // policy's shape, so both end -- and the trainer with them -- when the policy is defined anew or cleared.  Each call releases device
+        // buffers: the setters make it once the stream is idle and the slot's new record is on the device.
+        void end_trainer() { trainer = Trainer{}; }
+        void end_value() { vnet = NetDev{}; vdesc = FtgpValueDesc{}; d_vparams.reset(); end_trainer(); }
+        void end_population() { pop_members = 0; d_pop_params.reset(); d_pop_map.reset(); }
+    } slots[FTGP_MAX_NETS];
     // env states (ftgp_save_envs_device / ftgp_load_envs_device)
     std::vector<uint64_t> track_fp;   // [n_tracks] the tracks' fingerprints (include/ftgp.h), folded at create
     DevBuf<EnvStateAux> d_state_aux;  // the handle's own dynamics record, the rejected counter, the fingerprints; allocated by the first save or load
@@ -1000,7 +1011,26 @@ unsigned nets_named(const FtgpEnv* e, int policy, bool device_io)
 int check_nets_defined(const FtgpEnv* e, unsigned named)
 {
     for (int s = 0; s < FTGP_MAX_NETS; ++s)
-        if ((named >> s & 1u) && !e->nets[s].defined) return failf(FTGP_ERR_STATE, "FTGP_POLICY_NET%d: network slot %d is not defined (ftgp_set_net)", s, s);
+        if ((named >> s & 1u) && !e->slots[s].net.defined) return failf(FTGP_ERR_STATE, "FTGP_POLICY_NET%d: network slot %d is not defined (ftgp_set_net)", s, s);
+    return 0;
+}
+
+// The preamble of every entry that names a network slot: the handle, the slot's range, and what the entry needs of the slot, looked at in
+// this order; S is the slot, or the call is refused in the entry's name.  An entry that checks other arguments between two of these calls
+// it twice.  instead: the entry to call on a slot that carries a population.
+enum : unsigned { kSlotDefined = 1, kSlotValue = 2, kSlotPopulation = 4, kSlotNoPopulation = 8, kSlotTrainer = 16, kSlotNoTrainer = 32 };
+int net_slot(FtgpEnv* e, const char* entry, int slot, unsigned needs, FtgpEnv::NetSlot*& S, const char* instead = nullptr)
+{
+    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
+    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "%s: slot = %d outside 0 .. %d", entry, slot, FTGP_MAX_NETS - 1);
+    S = &e->slots[slot];
+    if ((needs & kSlotDefined) && !S->net.defined) return failf(FTGP_ERR_STATE, "%s: network slot %d is not defined (ftgp_set_net)", entry, slot);
+    if ((needs & kSlotValue) && !S->vnet.defined) return failf(FTGP_ERR_STATE, "%s: network slot %d has no value net (ftgp_set_value_net)", entry, slot);
+    if ((needs & kSlotPopulation) && !S->pop_members) return failf(FTGP_ERR_STATE, "%s: network slot %d carries no population (ftgp_set_net_population)", entry, slot);
+    if ((needs & kSlotNoPopulation) && S->pop_members)
+        return failf(FTGP_ERR_STATE, "%s: network slot %d carries a population of %d members%s%s%s", entry, slot, S->pop_members, instead ? " (" : "", instead ? instead : "", instead ? ")" : "");
+    if ((needs & kSlotTrainer) && !S->trainer.on) return failf(FTGP_ERR_STATE, "%s: network slot %d has no trainer (ftgp_train_begin)", entry, slot);
+    if ((needs & kSlotNoTrainer) && S->trainer.on) return failf(FTGP_ERR_STATE, "%s: network slot %d has a trainer already (ftgp_train_end)", entry, slot);
     return 0;
 }
 
@@ -1073,29 +1103,38 @@ int sync_rows_to_host(FtgpEnv* e)
     return 0;
 }
 
-// A buffer of ftgp_step_device: `bytes` of device memory on the handle's device from p on (hipPointerGetAttributes, and the extent of the
-// allocation from hipMemGetAddressRange).  Buffers found valid are remembered, so that the steady state asks the runtime nothing.
-int check_device_buffer(FtgpEnv* e, const void* p, size_t bytes, const char* name)
+// A caller's buffer of entry `entry`: `bytes` of device memory on the handle's device from p on (hipPointerGetAttributes, and the extent of
+// the allocation from hipMemGetAddressRange); a refusal names the entry and the buffer.  Buffers found valid are remembered, so that the
+// steady state asks the runtime nothing.
+int check_device_buffer(FtgpEnv* e, const char* entry, const void* p, size_t bytes, const char* name)
 {
-    if (!p) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is NULL", name);
+    if (!p) return failf(FTGP_ERR_ARG, "%s: %s is NULL", entry, name);
     auto& ds = e->ds;
     for (const auto& c : ds.checked) if (c.p == p && c.bytes >= bytes) return 0;
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is not device memory", name);
+        return failf(FTGP_ERR_ARG, "%s: %s is not device memory", entry, name);
     }
-    if (a.type != hipMemoryTypeDevice || a.device != e->device) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is not device memory on the handle's device", name);
+    if (a.type != hipMemoryTypeDevice || a.device != e->device) return failf(FTGP_ERR_ARG, "%s: %s is not device memory on the handle's device", entry, name);
     hipDeviceptr_t base = nullptr; size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(FTGP_ERR_ARG, "ftgp_step_device: the allocation of %s is unknown to the runtime", name);
+        return failf(FTGP_ERR_ARG, "%s: the allocation of %s is unknown to the runtime", entry, name);
     }
     const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
-    if (q < b || q - b + bytes > size) return fail(FTGP_ERR_ARG, "ftgp_step_device: %s is smaller than the layout needs", name);
+    if (q < b || q - b + bytes > size) return failf(FTGP_ERR_ARG, "%s: %s is smaller than the layout needs", entry, name);
     ds.checked[ds.checked_next] = { p, bytes };
     ds.checked_next = (ds.checked_next + 1) % (int)(sizeof ds.checked / sizeof ds.checked[0]);
     return 0;
+}
+
+// ... of `count` elements of `each` bytes, in size_t: a product that does not fit is a buffer too small
+int check_device_buffer(FtgpEnv* e, const char* entry, const void* p, size_t count, size_t each, const char* name)
+{
+    size_t bytes = 0;
+    if (__builtin_mul_overflow(count, each, &bytes)) return failf(FTGP_ERR_ARG, "%s: %s is smaller than the layout needs", entry, name);
+    return check_device_buffer(e, entry, p, bytes, name);
 }
 
 // the signals of the device step as the finish kernel takes them (ftgp_device_io_signals has checked s)
@@ -1213,22 +1252,31 @@ int stream_waits_for(hipStream_t behind, hipStream_t ahead, const Event& ev)
     return 0;
 }
 
-// the two fences of an entry that works on the handle's stream for a caller's: one before the work, one behind it
-int handle_waits_for_caller(FtgpEnv* e, hipStream_t caller) { return stream_waits_for(e->stream.get(), caller, e->ds.ev_in); }
-int caller_waits_for_handle(FtgpEnv* e, hipStream_t caller) { return stream_waits_for(caller, e->stream.get(), e->ds.ev_out); }
+// The fence of every entry that works on the handle's stream for a caller's: the handle's stream waits for what the caller's holds, `work`
+// enqueues on the handle's stream, and the caller's stream waits for that.  Safe as a handle's first call: the two events are made here.
+// An entry validates before it comes here, so nothing is enqueued for a refused call; if `work` fails, its code is returned without the
+// closing fence.
+template <class Work>
+int on_handle_stream(FtgpEnv* e, void* caller_stream, Work work)
+{
+    hipStream_t caller = (hipStream_t)caller_stream;
+    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
+    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (int rc = stream_waits_for(e->stream.get(), caller, e->ds.ev_in)) return rc;
+    if (int rc = work()) return rc;
+    return stream_waits_for(caller, e->stream.get(), e->ds.ev_out);
+}
 
-// ftgp_state_device, ftgp_contacts_device, ftgp_frame_device, ftgp_rivals_device (`entry`): the external agents' rows of `floats` floats, written by `launch`
-// on the handle's stream to the caller's buffer `out` (`name` in a refusal)
+// ftgp_state_device, ftgp_contacts_device, ftgp_frame_device, ftgp_rivals_device, ftgp_obs_device (`entry`): the external agents' rows of `floats` floats,
+// written by `launch` on the handle's stream to the caller's buffer `out` (`name` in a refusal)
 template <class Launch>
 int rows_to_device(FtgpEnv* e, const char* entry, void* stream, size_t floats, float* out, const char* name, Launch launch)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     if (!e->ds.ready) return fail(FTGP_ERR_STATE, "%s before ftgp_device_io_config", entry);
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc = check_device_buffer(e, out, sizeof(float) * floats * (size_t)e->P.n_envs * (size_t)e->ds.io.n_ext, name)) return rc;
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    if (int rc = launch()) return rc;
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    if (int rc = check_device_buffer(e, entry, out, sizeof(float) * floats * (size_t)e->P.n_envs * (size_t)e->ds.io.n_ext, name)) return rc;
+    return on_handle_stream(e, stream, launch);
 }
 
 // The first setter call of a handle: the DYN kernels may use the LDS the others may, the records are allocated (zeroed, the counter with
@@ -1289,8 +1337,6 @@ size_t env_state_bytes(const DeviceParams& P)
 // A handle's first save or load: the handle's own dynamics record, a zeroed counter and the fingerprints go to device memory.
 int ensure_env_state(FtgpEnv* e)
 {
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
     if (e->d_state_aux) return 0;
     EnvStateAux a{};
     memcpy(a.own, e->dyn.base, sizeof e->dyn.base);
@@ -1491,15 +1537,15 @@ int plan_device_step(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDeviceStepE
     S.state = st.out; S.final_state = st.final_out;
     plan.signals = !ds.sig_default || S.state || S.final_state || ds.con_on || ds.frame_on || ds.rivals_on;
     const size_t n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)A.n_ext, obs_bytes = sizeof(float) * rows * (size_t)S.n_beams;
-    if (int rc = check_device_buffer(e, io->action, sizeof(float) * 2 * rows, "action")) return rc;
-    if (int rc = check_device_buffer(e, io->obs, obs_bytes, "obs")) return rc;
-    if (int rc = check_device_buffer(e, io->reward, sizeof(float) * rows, "reward")) return rc;
-    if (int rc = check_device_buffer(e, io->terminated, n_envs, "terminated")) return rc;
-    if (int rc = check_device_buffer(e, io->truncated, n_envs, "truncated")) return rc;
-    if (io->final_obs) if (int rc = check_device_buffer(e, io->final_obs, obs_bytes, "final_obs")) return rc;
+    if (int rc = check_device_buffer(e, "ftgp_step_device", io->action, sizeof(float) * 2 * rows, "action")) return rc;
+    if (int rc = check_device_buffer(e, "ftgp_step_device", io->obs, obs_bytes, "obs")) return rc;
+    if (int rc = check_device_buffer(e, "ftgp_step_device", io->reward, sizeof(float) * rows, "reward")) return rc;
+    if (int rc = check_device_buffer(e, "ftgp_step_device", io->terminated, n_envs, "terminated")) return rc;
+    if (int rc = check_device_buffer(e, "ftgp_step_device", io->truncated, n_envs, "truncated")) return rc;
+    if (io->final_obs) if (int rc = check_device_buffer(e, "ftgp_step_device", io->final_obs, obs_bytes, "final_obs")) return rc;
     for (const Rows* r : { &st, &ct, &fr, &rv }) {
-        if (r->out) if (int rc = check_device_buffer(e, r->out, sizeof(float) * r->floats * rows, r->name)) return rc;
-        if (r->final_out) if (int rc = check_device_buffer(e, r->final_out, sizeof(float) * r->floats * rows, r->final_name)) return rc;
+        if (r->out) if (int rc = check_device_buffer(e, "ftgp_step_device", r->out, sizeof(float) * r->floats * rows, r->name)) return rc;
+        if (r->final_out) if (int rc = check_device_buffer(e, "ftgp_step_device", r->final_out, sizeof(float) * r->floats * rows, r->final_name)) return rc;
     }
     plan.dense = ds.frame_on && ds.frame.dense_progress != 0;
     if (ds.frame_on) {
@@ -1759,8 +1805,6 @@ int ftgp_device_io_config(FtgpEnv* e, const FtgpDeviceIoConfig* cfg)
         e->table_on_device = 0;
     }
     if (!e->ds.d_prev_abs) HIP_TRY(dev_alloc(e->ds.d_prev_abs, sizeof(int32_t) * (size_t)e->P.n_cars));
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
     // a workgroup holds whole envs, so its car slot c runs entry c % cars_per_env (as ftgp_set_car_policies)
     for (int c = 0; c < FTGP_MAX_CARS_PER_BLOCK; ++c) e->h_tables.get()[FTGP_MAX_CARS_PER_BLOCK + c] = slot[c % cpe];
     if (e->table_on_device == 1) e->table_on_device = -1;
@@ -1855,10 +1899,7 @@ int ftgp_step_device_rivals(FtgpEnv* e, const FtgpDeviceStep* io, const FtgpDevi
 {
     DeviceStepPlan plan;
     if (int rc = plan_device_step(e, io, extra, contacts, frame, rivals, plan)) return rc;       // (before anything is enqueued)
-    hipStream_t caller = (hipStream_t)io->stream;
-    if (int rc = handle_waits_for_caller(e, caller)) return rc;
-    if (int rc = enqueue_device_step(e, plan, [] { return 0; })) return rc;
-    return caller_waits_for_handle(e, caller);
+    return on_handle_stream(e, io->stream, [&] { return enqueue_device_step(e, plan, [] { return 0; }); });
 }
 
 // LDS of a workgroup of ftgp_collect_act_kernel: four waves, each the rays its network's beams cover and the car's record
@@ -1875,7 +1916,7 @@ static int launch_collect_act(FtgpEnv* e, const FtgpCollect& c, const float* noi
     C.slot = c.slot; C.n_ext = e->ds.io.n_ext; C.n_rows = e->P.n_envs * e->ds.io.n_ext;
     for (int k = 0; k < FTGP_PAIR_STRIDE; ++k) if (e->ds.io.ext_index[k] >= 0) C.ext_slot[e->ds.io.ext_index[k]] = k;
     C.env_track = e->d_env_track.get();
-    const size_t lds = collect_act_lds(e->nets[c.slot]);
+    const size_t lds = collect_act_lds(e->slots[c.slot].net);
     if (value) {
         C.vnet = e->d_vnets.get() + c.slot; C.value = value;
         void (*kernel)(DeviceParams, CollectValueArgs) = mean ? ftgp_collect_act_kernel<true, true> : ftgp_collect_act_kernel<false, true>;
@@ -1917,8 +1958,8 @@ int ftgp_collect_values_device(FtgpEnv* e, const FtgpCollect* c, const FtgpColle
     FtgpEnv::DeviceStep& ds = e->ds;
     if (!ds.ready) return fail(FTGP_ERR_STATE, "ftgp_collect_device before ftgp_device_io_config%s");
     if (c->reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_collect_device: reserved must be 0%s");
-    if (c->slot < 0 || c->slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_collect_device: slot = %d outside 0 .. %d", c->slot, FTGP_MAX_NETS - 1);
-    if (!e->nets[c->slot].defined) return failf(FTGP_ERR_STATE, "ftgp_collect_device: network slot %d is not defined (ftgp_set_net)", c->slot);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_collect_device", c->slot, kSlotDefined, S)) return rc;
     if (c->n_decisions < 1) return failf(FTGP_ERR_ARG, "ftgp_collect_device: n_decisions = %d must be >= 1", c->n_decisions);
     for (int k = 0; k < 2; ++k) {
         if (!nonneg_finite(c->std[k])) return failf(FTGP_ERR_ARG, "ftgp_collect_device: std[%d] = %g must be >= 0 and finite", k, (double)c->std[k]);
@@ -1928,17 +1969,12 @@ int ftgp_collect_values_device(FtgpEnv* e, const FtgpCollect* c, const FtgpColle
     }
     // (a FTGP_LIDAR_FAKELIDAR handle, where ftgp_set_dynamics is FTGP_ERR_STATE, has no defined slot: ftgp_set_net refuses it)
     if (c->reset_dynamics && !ds.io.auto_reset) return fail(FTGP_ERR_STATE, "ftgp_collect_device: reset_dynamics while auto_reset is off (ftgp_device_io_config)%s");
-    if (collect_act_lds(e->nets[c->slot]) > 64 * 1024)
-        return failf(FTGP_ERR_ARG, "ftgp_collect_device: slot %d: the %d rays of its beams (n_beams * pool) do not fit LDS four cars to a workgroup", c->slot, e->nets[c->slot].n_beams * e->nets[c->slot].pool);
+    if (collect_act_lds(S->net) > 64 * 1024)
+        return failf(FTGP_ERR_ARG, "ftgp_collect_device: slot %d: the %d rays of its beams (n_beams * pool) do not fit LDS four cars to a workgroup", c->slot, S->net.n_beams * S->net.pool);
     HIP_TRY(hipSetDevice(e->device));
-    // every buffer at its full T-fold size, in size_t (a product that does not fit is a buffer too small)
-    const size_t T = (size_t)c->n_decisions, n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)ds.io.n_ext, n_in = (size_t)e->nets[c->slot].width[0];
-    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_collect_device: %s", m.c_str()); return rc; };
-    auto checked = [&](const void* p, size_t per_decision, const char* name) {
-        size_t bytes = 0;
-        if (__builtin_mul_overflow(T, per_decision, &bytes)) return failf(FTGP_ERR_ARG, "ftgp_collect_device: %s is smaller than the layout needs", name);
-        return check_device_buffer(e, p, bytes, name) ? refused(FTGP_ERR_ARG) : 0;
-    };
+    // every buffer at its full T-fold size
+    const size_t T = (size_t)c->n_decisions, n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)ds.io.n_ext, n_in = (size_t)S->net.width[0];
+    auto checked = [&](const void* p, size_t per_decision, const char* name) { return check_device_buffer(e, "ftgp_collect_device", p, T, per_decision, name); };
     if (c->noise) if (int rc = checked(c->noise, sizeof(float) * 2 * rows, "noise")) return rc;
     if (int rc = checked(c->inputs, sizeof(float) * n_in * rows, "inputs")) return rc;
     if (int rc = checked(c->mean, sizeof(float) * 2 * rows, "mean")) return rc;
@@ -1949,13 +1985,8 @@ int ftgp_collect_values_device(FtgpEnv* e, const FtgpCollect* c, const FtgpColle
     if (c->next_inputs) if (int rc = checked(c->next_inputs, sizeof(float) * n_in * rows, "next_inputs")) return rc;
     if (c->reset_dynamics) if (int rc = checked(c->reset_dynamics, sizeof(double) * FTGP_DYN_DOUBLES * (size_t)e->P.n_cars, "reset_dynamics")) return rc;
     if (v) {
-        auto refused_v = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_collect_values_device: %s", m.c_str()); return rc; };
-        auto checked_v = [&](const void* p, const char* name) {
-            size_t bytes = 0;
-            if (__builtin_mul_overflow(T, sizeof(float) * rows, &bytes)) return failf(FTGP_ERR_ARG, "ftgp_collect_values_device: %s is smaller than the layout needs", name);
-            return check_device_buffer(e, p, bytes, name) ? refused_v(FTGP_ERR_ARG) : 0;
-        };
-        if (!e->vnets[c->slot].defined) return failf(FTGP_ERR_STATE, "ftgp_collect_values_device: network slot %d has no value net (ftgp_set_value_net)", c->slot);
+        auto checked_v = [&](const void* p, const char* name) { return check_device_buffer(e, "ftgp_collect_values_device", p, T, sizeof(float) * rows, name); };
+        if (int rc = net_slot(e, "ftgp_collect_values_device", c->slot, kSlotValue, S)) return rc;
         if (v->reserved[0] != 0 || v->reserved[1] != 0) return fail(FTGP_ERR_ARG, "ftgp_collect_values_device: reserved must be 0%s");
         if (int rc = check_discount("ftgp_collect_values_device", "gamma", v->gamma)) return rc;
         if (int rc = check_discount("ftgp_collect_values_device", "lam", v->lam)) return rc;
@@ -1974,23 +2005,23 @@ int ftgp_collect_values_device(FtgpEnv* e, const FtgpCollect* c, const FtgpColle
     DeviceStepPlan plan;
     if (int rc = plan_device_step(e, &io, nullptr, nullptr, nullptr, nullptr, plan)) return rc;
     if (c->reset_dynamics) if (int rc = ensure_dynamics(e)) return rc;
-    hipStream_t caller = (hipStream_t)c->stream;
-    if (int rc = handle_waits_for_caller(e, caller)) return rc;
-    for (size_t t = 0; t < T; ++t) {
-        float* action = c->action + t * rows * 2;
-        if (int rc = launch_collect_act(e, *c, c->noise ? c->noise + t * rows * 2 : nullptr, c->inputs + t * rows * n_in, c->mean + t * rows * 2, action,
-                                        v ? v->value + t * rows : nullptr)) return rc;
-        plan.A.action = action; plan.A.reward = c->reward + t * rows; plan.A.terminated = c->terminated + t * n_envs; plan.A.truncated = c->truncated + t * n_envs;
-        // (step 3': with a value net the kernel runs whether or not next_inputs is given, and writes x down only where it is)
-        if (int rc = enqueue_device_step(e, plan, [&] {
-                if (v) return launch_collect_act(e, *c, nullptr, c->next_inputs ? c->next_inputs + t * rows * n_in : nullptr, nullptr, nullptr, v->next_value + t * rows);
-                return c->next_inputs ? launch_collect_act(e, *c, nullptr, c->next_inputs + t * rows * n_in, nullptr, nullptr) : 0; })) return rc;
-        if (c->reset_dynamics)
-            if (int rc = launch_dynamics(e, c->reset_dynamics + t * (size_t)e->P.n_cars * FTGP_DYN_DOUBLES, plan.A.terminated, plan.A.truncated)) return rc;
-    }
-    if (v && v->advantage)
-        if (int rc = launch_gae(e, T, v->gamma, v->lam, c->reward, v->value, v->next_value, c->terminated, c->truncated, v->advantage, v->ret)) return rc;
-    return caller_waits_for_handle(e, caller);
+    return on_handle_stream(e, c->stream, [&] {
+        for (size_t t = 0; t < T; ++t) {
+            float* action = c->action + t * rows * 2;
+            if (int rc = launch_collect_act(e, *c, c->noise ? c->noise + t * rows * 2 : nullptr, c->inputs + t * rows * n_in, c->mean + t * rows * 2, action,
+                                            v ? v->value + t * rows : nullptr)) return rc;
+            plan.A.action = action; plan.A.reward = c->reward + t * rows; plan.A.terminated = c->terminated + t * n_envs; plan.A.truncated = c->truncated + t * n_envs;
+            // (step 3': with a value net the kernel runs whether or not next_inputs is given, and writes x down only where it is)
+            if (int rc = enqueue_device_step(e, plan, [&] {
+                    if (v) return launch_collect_act(e, *c, nullptr, c->next_inputs ? c->next_inputs + t * rows * n_in : nullptr, nullptr, nullptr, v->next_value + t * rows);
+                    return c->next_inputs ? launch_collect_act(e, *c, nullptr, c->next_inputs + t * rows * n_in, nullptr, nullptr) : 0; })) return rc;
+            if (c->reset_dynamics)
+                if (int rc = launch_dynamics(e, c->reset_dynamics + t * (size_t)e->P.n_cars * FTGP_DYN_DOUBLES, plan.A.terminated, plan.A.truncated)) return rc;
+        }
+        if (v && v->advantage)
+            if (int rc = launch_gae(e, T, v->gamma, v->lam, c->reward, v->value, v->next_value, c->terminated, c->truncated, v->advantage, v->ret)) return rc;
+        return 0;
+    });
 }
 
 int ftgp_gae_device(FtgpEnv* e, void* stream, int n_decisions, float gamma, float lam, const float* reward, const float* value, const float* next_value,
@@ -2003,12 +2034,7 @@ int ftgp_gae_device(FtgpEnv* e, void* stream, int n_decisions, float gamma, floa
     if (int rc = check_discount("ftgp_gae_device", "lam", lam)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     const size_t T = (size_t)n_decisions, n_envs = (size_t)e->P.n_envs, rows = n_envs * (size_t)e->ds.io.n_ext;
-    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_gae_device: %s", m.c_str()); return rc; };
-    auto checked = [&](const void* p, size_t per_decision, const char* name) {
-        size_t bytes = 0;
-        if (__builtin_mul_overflow(T, per_decision, &bytes)) return failf(FTGP_ERR_ARG, "ftgp_gae_device: %s is smaller than the layout needs", name);
-        return check_device_buffer(e, p, bytes, name) ? refused(FTGP_ERR_ARG) : 0;
-    };
+    auto checked = [&](const void* p, size_t per_decision, const char* name) { return check_device_buffer(e, "ftgp_gae_device", p, T, per_decision, name); };
     if (int rc = checked(reward, sizeof(float) * rows, "reward")) return rc;
     if (int rc = checked(value, sizeof(float) * rows, "value")) return rc;
     if (int rc = checked(next_value, sizeof(float) * rows, "next_value")) return rc;
@@ -2016,9 +2042,7 @@ int ftgp_gae_device(FtgpEnv* e, void* stream, int n_decisions, float gamma, floa
     if (int rc = checked(truncated, n_envs, "truncated")) return rc;
     if (int rc = checked(advantage, sizeof(float) * rows, "advantage")) return rc;
     if (int rc = checked(ret, sizeof(float) * rows, "ret")) return rc;
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    if (int rc = launch_gae(e, T, gamma, lam, reward, value, next_value, terminated, truncated, advantage, ret)) return rc;
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    return on_handle_stream(e, stream, [&] { return launch_gae(e, T, gamma, lam, reward, value, next_value, terminated, truncated, advantage, ret); });
 }
 
 int ftgp_state_device(FtgpEnv* e, void* stream, float* state)
@@ -2134,15 +2158,9 @@ int ftgp_set_dynamics_device(FtgpEnv* e, void* stream, const double* rows, const
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_dynamics_device: not on a FTGP_LIDAR_FAKELIDAR handle%s");
     HIP_TRY(hipSetDevice(e->device));
-    // (check_device_buffer words its refusals for the device step: put this entry's name in front)
-    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_dynamics_device: %s", m.c_str()); return rc; };
-    if (int rc = check_device_buffer(e, rows, sizeof(double) * FTGP_DYN_DOUBLES * (size_t)e->P.n_cars, "rows")) return refused(rc);
-    if (env_mask) if (int rc = check_device_buffer(e, env_mask, (size_t)e->P.n_envs, "env_mask")) return refused(rc);
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    if (int rc = launch_dynamics(e, rows, env_mask)) return rc;
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    if (int rc = check_device_buffer(e, "ftgp_set_dynamics_device", rows, sizeof(double) * FTGP_DYN_DOUBLES * (size_t)e->P.n_cars, "rows")) return rc;
+    if (env_mask) if (int rc = check_device_buffer(e, "ftgp_set_dynamics_device", env_mask, (size_t)e->P.n_envs, "env_mask")) return rc;
+    return on_handle_stream(e, stream, [&] { return launch_dynamics(e, rows, env_mask); });
 }
 
 int ftgp_get_dynamics(FtgpEnv* e, double* rows_out, int64_t* rejected_out)
@@ -2166,10 +2184,26 @@ int ftgp_get_dynamics(FtgpEnv* e, double* rows_out, int64_t* rejected_out)
 }
 
 // ---- network drivers ----
-// what ftgp_set_net checks of a description (include/ftgp.h); the message names the field
-static int check_net_desc(const FtgpEnv* e, const FtgpNetDesc& d)
+// What the description of a policy and of a value net share (`entry`: the setter in the message): n_layers, width[] with `last` outputs on the
+// last layer, the two activations.
+static int check_layers(const char* entry, int last, int n_layers, const int32_t* width, int hidden_act, int out_act)
 {
-    const int R = e->P.n_rays, eighth = e->P.eighth;
+    if (n_layers < 1 || n_layers > FTGP_NET_MAX_LAYERS) return failf(FTGP_ERR_ARG, "%s: n_layers = %d outside 1 .. %d", entry, n_layers, FTGP_NET_MAX_LAYERS);
+    for (int l = 0; l < FTGP_NET_MAX_LAYERS; ++l) {
+        const int w = width[l];
+        if (l >= n_layers) { if (w != 0) return failf(FTGP_ERR_ARG, "%s: width[%d] = %d behind the last layer must be 0", entry, l, w); }
+        else if (l == n_layers - 1) { if (w != last) return failf(FTGP_ERR_ARG, "%s: width[%d] = %d: the last layer has exactly %d output%s", entry, l, w, last, last == 1 ? "" : "s"); }
+        else if (w < 1 || w > FTGP_NET_MAX_HIDDEN) return failf(FTGP_ERR_ARG, "%s: width[%d] = %d outside 1 .. %d", entry, l, w, FTGP_NET_MAX_HIDDEN);
+    }
+    if (hidden_act < FTGP_ACT_IDENTITY || hidden_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "%s: hidden_act = %d is no FTGP_ACT_*", entry, hidden_act);
+    if (out_act < FTGP_ACT_IDENTITY || out_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "%s: out_act = %d is no FTGP_ACT_*", entry, out_act);
+    return 0;
+}
+
+// what ftgp_set_net checks of a description on a handle of R rays whose drivers read rays [eighth, R - eighth) (include/ftgp.h); the message
+// names the field
+static int check_net_desc(int R, int eighth, const FtgpNetDesc& d)
+{
     if (d.reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_set_net: reserved must be 0%s");
     if (d.pool < 1 || R % d.pool != 0) return failf(FTGP_ERR_ARG, "ftgp_set_net: pool = %d must be >= 1 and divide n_rays = %d", d.pool, R);
     if (!(d.max_range > 0.0f) || std::isinf(d.max_range)) return failf(FTGP_ERR_ARG, "ftgp_set_net: max_range = %g must be finite and > 0", (double)d.max_range);
@@ -2179,16 +2213,10 @@ static int check_net_desc(const FtgpEnv* e, const FtgpNetDesc& d)
         return failf(FTGP_ERR_ARG, "ftgp_set_net: beams %d .. %d of pool %d leave the drivers' scan window, rays [%d, %d) of %d (beam_first, n_beams)", d.beam_first,
                      d.beam_first + d.n_beams - 1, d.pool, eighth, R - eighth, R);
     if (d.use_state != 0 && d.use_state != 1) return failf(FTGP_ERR_ARG, "ftgp_set_net: use_state = %d must be 0 or 1", d.use_state);
-    if (d.n_layers < 1 || d.n_layers > FTGP_NET_MAX_LAYERS) return failf(FTGP_ERR_ARG, "ftgp_set_net: n_layers = %d outside 1 .. %d", d.n_layers, FTGP_NET_MAX_LAYERS);
-    if (ftgp_net_inputs(&d) > FTGP_NET_MAX_INPUTS) return failf(FTGP_ERR_ARG, "ftgp_set_net: n_beams + 5 use_state = %d inputs, at most %d", ftgp_net_inputs(&d), FTGP_NET_MAX_INPUTS);
-    for (int l = 0; l < FTGP_NET_MAX_LAYERS; ++l) {
-        const int w = d.width[l];
-        if (l >= d.n_layers) { if (w != 0) return failf(FTGP_ERR_ARG, "ftgp_set_net: width[%d] = %d behind the last layer must be 0", l, w); }
-        else if (l == d.n_layers - 1) { if (w != 2) return failf(FTGP_ERR_ARG, "ftgp_set_net: width[%d] = %d: the last layer has exactly 2 outputs", l, w); }
-        else if (w < 1 || w > FTGP_NET_MAX_HIDDEN) return failf(FTGP_ERR_ARG, "ftgp_set_net: width[%d] = %d outside 1 .. %d", l, w, FTGP_NET_MAX_HIDDEN);
-    }
-    if (d.hidden_act < FTGP_ACT_IDENTITY || d.hidden_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_net: hidden_act = %d is no FTGP_ACT_*", d.hidden_act);
-    if (d.out_act < FTGP_ACT_IDENTITY || d.out_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_net: out_act = %d is no FTGP_ACT_*", d.out_act);
+    // (the input width has always been looked at behind n_layers and before width[]: a description wrong in two ways keeps its message)
+    const bool count_ok = d.n_layers >= 1 && d.n_layers <= FTGP_NET_MAX_LAYERS;
+    if (count_ok && ftgp_net_inputs(&d) > FTGP_NET_MAX_INPUTS) return failf(FTGP_ERR_ARG, "ftgp_set_net: n_beams + 5 use_state = %d inputs, at most %d", ftgp_net_inputs(&d), FTGP_NET_MAX_INPUTS);
+    if (int rc = check_layers("ftgp_set_net", 2, d.n_layers, d.width, d.hidden_act, d.out_act)) return rc;
     for (int k = 0; k < 2; ++k) {
         if (!std::isfinite(d.out_scale[k])) return failf(FTGP_ERR_ARG, "ftgp_set_net: out_scale[%d] is not finite", k);
         if (!std::isfinite(d.out_offset[k])) return failf(FTGP_ERR_ARG, "ftgp_set_net: out_offset[%d] is not finite", k);
@@ -2224,7 +2252,7 @@ static int check_net_rivals(const FtgpNetDesc& d, const FtgpNetFrame* f, const F
     return 0;
 }
 
-// floats of a slot's parameters in the caller's layout: per layer W[n_out][n_in], then b[n_out], with the slot's true n_in
+// floats of a record's parameters in the caller's layout: per layer W[n_out][n_in], then b[n_out], with the slot's true n_in
 static size_t net_param_count(const NetDev& N)
 {
     size_t n = 0;
@@ -2232,23 +2260,30 @@ static size_t net_param_count(const NetDev& N)
     return n;
 }
 
-// the record of a description: the library's layout (NetDev) without the buffer's address; f = null: no frame inputs, r = null: no rival inputs
-static NetDev net_record(const FtgpNetDesc& d, const FtgpNetFrame* f, const FtgpNetRivals* r)
+// the layers of a record in the library's layout: n_in inputs, then width[l] outputs of layer l; where Wt and b of each layer sit, and
+// the floats of the whole set
+static void lay_out_layers(NetDev& N, int n_in, int n_layers, const int32_t* width)
 {
-    NetDev N{};
-    N.defined = 1; N.pool = d.pool; N.beam_first = d.beam_first; N.n_beams = d.n_beams; N.use_state = d.use_state; N.n_layers = d.n_layers;
-    N.hidden_act = d.hidden_act; N.out_act = d.out_act;
-    N.width[0] = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f) + ftgp_net_rival_inputs(r);
-    if (f && f->enabled) { N.frame_first = ftgp_net_inputs(&d); N.frame_shape = f->n_ahead | f->stride << 8; }
-    if (r && r->enabled) { N.rival_first = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f); N.rival_shape = 1 | r->n_rivals << 8; }
+    N.n_layers = n_layers; N.width[0] = n_in;
     int o = 0;
-    for (int l = 0; l < d.n_layers; ++l) {
-        N.width[l + 1] = d.width[l];
-        const int ld = (d.width[l] + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
+    for (int l = 0; l < n_layers; ++l) {
+        N.width[l + 1] = width[l];
+        const int ld = (width[l] + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
         N.w_off[l] = o; o += N.width[l] * ld;
         N.b_off[l] = o; o += ld;
     }
     N.n_floats = o;
+}
+
+// the record of a description: the library's layout (NetDev) without the buffer's address; f = null: no frame inputs, r = null: no rival inputs
+static NetDev net_record(const FtgpNetDesc& d, const FtgpNetFrame* f, const FtgpNetRivals* r)
+{
+    NetDev N{};
+    N.defined = 1; N.pool = d.pool; N.beam_first = d.beam_first; N.n_beams = d.n_beams; N.use_state = d.use_state;
+    N.hidden_act = d.hidden_act; N.out_act = d.out_act;
+    if (f && f->enabled) { N.frame_first = ftgp_net_inputs(&d); N.frame_shape = f->n_ahead | f->stride << 8; }
+    if (r && r->enabled) { N.rival_first = ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f); N.rival_shape = 1 | r->n_rivals << 8; }
+    lay_out_layers(N, ftgp_net_inputs(&d) + ftgp_net_frame_inputs(f) + ftgp_net_rival_inputs(r), d.n_layers, d.width);
     N.max_range = d.max_range; N.inv_max_range = 1.0f / d.max_range;
     for (int k = 0; k < 2; ++k) { N.out_scale[k] = d.out_scale[k]; N.out_offset[k] = d.out_offset[k]; }
     return N;
@@ -2262,6 +2297,38 @@ template <class T> static int net_host_buffer(std::vector<T>& v, size_t n, const
     catch (const std::bad_alloc&) { return failf(FTGP_ERR_HIP, "%s: no host memory for %zu bytes", entry, n * sizeof(T)); }
     return 0;
 }
+}
+
+// The three ways of a parameter set of record N's shape between a caller and the library's layout.
+// in from the host: n_members sets in the caller's layout (a slot's single set: 1) -> the library's layout, `floats` floats with the padding
+// zeros -> a new device buffer
+static int upload_params(const char* entry, const NetDev& N, int n_members, size_t floats, const float* params, DevBuf<float>& buf)
+{
+    std::vector<float> img;
+    if (int rc = net_host_buffer(img, floats, entry)) return rc;
+    ftgp_net_population_to_library(N.n_layers, N.width, n_members, params, img.data());
+    HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
+    return 0;
+}
+// out to the host: one set in the library's layout at `src` on the device -> the caller's layout; the handle's stream is synchronised
+static int download_params(FtgpEnv* e, const char* entry, const NetDev& N, const float* src, float* out)
+{
+    std::vector<float> img;
+    if (int rc = net_host_buffer(img, (size_t)N.n_floats, entry)) return rc;
+    HIP_TRY(hipMemcpyAsync(img.data(), src, sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
+    HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), out);
+    return 0;
+}
+// in from the device: ftgp_net_params_kernel on the handle's stream, n_members sets of a caller's device buffer in the caller's layout -> the
+// library's layout at dst, `stride` floats apart (a slot's single set: 1 member, stride 0)
+static int launch_net_params(FtgpEnv* e, const NetDev& N, const float* params, float* dst, int stride, int n_members)
+{
+    const int n = (int)net_param_count(N);
+    hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min(n_members, FTGP_NET_PARAMS_GRID_Y)), dim3(256), 0, e->stream.get(), N, params,
+                       dst, n, stride, n_members);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // The first setter call of a handle: the NET kernels may use the LDS the others may, the records are allocated (zeroed: every slot
@@ -2292,11 +2359,11 @@ int ftgp_set_net_frame(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftgp
 
 int ftgp_set_net_rivals(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const FtgpNetFrame* frame, const FtgpNetRivals* rivals, const float* params)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_net: not on a FTGP_LIDAR_FAKELIDAR handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    if (e && e->P.lidar_mode == FTGP_LIDAR_FAKELIDAR) return fail(FTGP_ERR_STATE, "ftgp_set_net: not on a FTGP_LIDAR_FAKELIDAR handle%s");
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_set_net", slot, 0, S)) return rc;
     if (desc) {
-        if (int rc = check_net_desc(e, *desc)) return rc;
+        if (int rc = check_net_desc(e->P.n_rays, e->P.eighth, *desc)) return rc;
         if (frame) if (int rc = check_net_frame(*desc, *frame)) return rc;
         if (rivals) if (int rc = check_net_rivals(*desc, frame, *rivals)) return rc;
         if (!params) return fail(FTGP_ERR_ARG, "ftgp_set_net: params is NULL%s");
@@ -2308,66 +2375,45 @@ int ftgp_set_net_rivals(FtgpEnv* e, int slot, const FtgpNetDesc* desc, const Ftg
     DevBuf<float> buf;
     if (desc) {
         N = net_record(*desc, frame, rivals);
-        std::vector<float> img;                               // the library's layout; the padding is zeros
-        if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_set_net")) return rc;
-        ftgp_net_population_to_library(N.n_layers, N.width, 1, params, img.data());
-        HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
+        if (int rc = upload_params("ftgp_set_net", N, 1, (size_t)N.n_floats, params, buf)) return rc;
         N.params = buf.get();
     }
     HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the slot while it changes
     HIP_TRY(hipMemcpy(e->d_nets.get() + slot, &N, sizeof N, hipMemcpyHostToDevice));
-    e->nets[slot] = N;
-    e->net_desc[slot] = desc ? *desc : FtgpNetDesc{};
-    e->net_frame[slot] = (desc && frame && frame->enabled) ? *frame : FtgpNetFrame{};
-    e->net_rivals[slot] = (desc && rivals && rivals->enabled) ? *rivals : FtgpNetRivals{};
-    e->d_net_params[slot] = std::move(buf);                   // (the old buffer goes: nothing reads it any more)
-    e->pop_members[slot] = 0; e->d_pop_params[slot] = DevBuf<float>(); e->d_pop_map[slot] = DevBuf<int32_t>();      // ... and a population with it
-    e->vnets[slot] = NetDev{}; e->vnet_desc[slot] = FtgpValueDesc{}; e->d_vnet_params[slot] = DevBuf<float>();         // ... and a value net: the input width may have changed
-    e->trainers[slot] = FtgpEnv::Trainer{};                   // ... and a trainer (the stream is idle)
+    S->net = N;
+    S->desc = desc ? *desc : FtgpNetDesc{};
+    S->frame = (desc && frame && frame->enabled) ? *frame : FtgpNetFrame{};
+    S->rivals = (desc && rivals && rivals->enabled) ? *rivals : FtgpNetRivals{};
+    S->d_params = std::move(buf);                             // (the old buffer goes: nothing reads it any more)
+    S->end_population();
+    S->end_value();
     return 0;
 }
 
 int ftgp_set_net_device(FtgpEnv* e, void* stream, int slot, const float* params)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_device: network slot %d is not defined (ftgp_set_net)", slot);
-    if (e->pop_members[slot]) return failf(FTGP_ERR_STATE, "ftgp_set_net_device: network slot %d carries a population of %d members (ftgp_set_net_population_device)", slot, e->pop_members[slot]);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_set_net_device", slot, kSlotDefined | kSlotNoPopulation, S, "ftgp_set_net_population_device")) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    const int n = (int)net_param_count(e->nets[slot]);
-    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_net_device: %s", m.c_str()); return rc; };
-    if (int rc = check_device_buffer(e, params, sizeof(float) * (size_t)n, "params")) return refused(rc);
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream.get(), e->nets[slot], params, e->d_net_params[slot].get(), n, 0, 1);
-    HIP_TRY(hipGetLastError());
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    if (int rc = check_device_buffer(e, "ftgp_set_net_device", params, sizeof(float) * net_param_count(S->net), "params")) return rc;
+    return on_handle_stream(e, stream, [&] { return launch_net_params(e, S->net, params, S->d_params.get(), 0, 1); });
 }
 
 int ftgp_get_net(FtgpEnv* e, int slot, FtgpNetDesc* desc_out, float* params_out)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    const NetDev& N = e->nets[slot];
-    if (!N.defined) return failf(FTGP_ERR_STATE, "ftgp_get_net: network slot %d is not defined (ftgp_set_net)", slot);
-    if (desc_out) *desc_out = e->net_desc[slot];
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_get_net", slot, kSlotDefined, S)) return rc;
+    if (desc_out) *desc_out = S->desc;
     if (!params_out) return 0;
     HIP_TRY(hipSetDevice(e->device));
-    std::vector<float> img;
-    if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_get_net")) return rc;
-    HIP_TRY(hipMemcpyAsync(img.data(), e->d_net_params[slot].get(), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
-    HIP_TRY(hipStreamSynchronize(e->stream.get()));
-    ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), params_out);
-    return 0;
+    return download_params(e, "ftgp_get_net", S->net, S->d_params.get(), params_out);
 }
 
 // ---- network populations: one parameter set per env (include/ftgp.h "Network populations") ----
 int ftgp_set_net_population(FtgpEnv* e, int slot, int n_members, const float* params, const int32_t* env_member)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_population: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_population: network slot %d is not defined (ftgp_set_net)", slot);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_set_net_population", slot, kSlotDefined, S)) return rc;
     const int n_envs = e->P.n_envs;
     if (n_members < 0 || n_members > n_envs) return failf(FTGP_ERR_ARG, "ftgp_set_net_population: n_members = %d outside 0 .. n_envs = %d", n_members, n_envs);
     if (n_members > 0 && !params) return fail(FTGP_ERR_ARG, "ftgp_set_net_population: params is NULL%s");
@@ -2376,100 +2422,84 @@ int ftgp_set_net_population(FtgpEnv* e, int slot, int n_members, const float* pa
             if (env_member[i] < 0 || env_member[i] >= n_members)
                 return failf(FTGP_ERR_ARG, "ftgp_set_net_population: env_member[%d] = %d outside [0, n_members = %d)", i, env_member[i], n_members);
     HIP_TRY(hipSetDevice(e->device));
-    NetDev N = e->nets[slot];
+    NetDev N = S->net;
     DevBuf<float> buf;
     DevBuf<int32_t> map;
     if (n_members > 0) {
-        const size_t stride = (size_t)net_member_stride(N.n_floats);
-        std::vector<float> img;                               // the library's layout; the padding is zeros
         std::vector<int32_t> members;
-        if (int rc = net_host_buffer(img, (size_t)n_members * stride, "ftgp_set_net_population")) return rc;
         if (int rc = net_host_buffer(members, (size_t)n_envs, "ftgp_set_net_population")) return rc;
-        ftgp_net_population_to_library(N.n_layers, N.width, n_members, params, img.data());
         for (int i = 0; i < n_envs; ++i) members[(size_t)i] = env_member ? env_member[i] : i % n_members;
-        HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
+        if (int rc = upload_params("ftgp_set_net_population", N, n_members, (size_t)n_members * (size_t)net_member_stride(N.n_floats), params, buf)) return rc;
         HIP_TRY(dev_upload(map, members.data(), sizeof(int32_t) * members.size()));
         N.params = buf.get(); N.env_member = map.get();
     } else {
-        if (!e->pop_members[slot]) return 0;                     // there is none
-        N.params = e->d_net_params[slot].get(); N.env_member = nullptr;        // the slot's single set is in force again
+        if (!S->pop_members) return 0;                        // there is none
+        N.params = S->d_params.get(); N.env_member = nullptr; // the slot's single set is in force again
     }
     HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is reading the slot while it changes
     HIP_TRY(hipMemcpy(e->d_nets.get() + slot, &N, sizeof N, hipMemcpyHostToDevice));
-    e->nets[slot] = N;
-    e->pop_members[slot] = n_members;
-    if (n_members > 0) e->trainers[slot] = FtgpEnv::Trainer{};      // a trainer steps the slot's single set: it ends with it
-    e->d_pop_params[slot] = std::move(buf);                   // (the old buffers go: nothing reads them any more)
-    e->d_pop_map[slot] = std::move(map);
+    S->net = N;
+    if (n_members > 0) {
+        S->end_trainer();
+        S->pop_members = n_members;
+        S->d_pop_params = std::move(buf);                     // (the old buffers go: nothing reads them any more)
+        S->d_pop_map = std::move(map);
+    } else S->end_population();
     return 0;
 }
 
 int ftgp_set_net_population_device(FtgpEnv* e, void* stream, int slot, const float* params, const int32_t* env_member)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_net_population_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_net_population_device: network slot %d is not defined (ftgp_set_net)", slot);
-    const int M = e->pop_members[slot], n_envs = e->P.n_envs;
-    if (!M) return failf(FTGP_ERR_STATE, "ftgp_set_net_population_device: network slot %d carries no population (ftgp_set_net_population)", slot);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_set_net_population_device", slot, kSlotDefined | kSlotPopulation, S)) return rc;
+    const int M = S->pop_members, n_envs = e->P.n_envs;
     HIP_TRY(hipSetDevice(e->device));
-    const NetDev& N = e->nets[slot];
-    const int n = (int)net_param_count(N);
-    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_net_population_device: %s", m.c_str()); return rc; };
-    if (params) if (int rc = check_device_buffer(e, params, sizeof(float) * (size_t)n * (size_t)M, "params")) return refused(rc);
-    if (env_member) if (int rc = check_device_buffer(e, env_member, sizeof(int32_t) * (size_t)n_envs, "env_member")) return refused(rc);
+    const NetDev& N = S->net;
+    if (params) if (int rc = check_device_buffer(e, "ftgp_set_net_population_device", params, sizeof(float) * net_param_count(N) * (size_t)M, "params")) return rc;
+    if (env_member) if (int rc = check_device_buffer(e, "ftgp_set_net_population_device", env_member, sizeof(int32_t) * (size_t)n_envs, "env_member")) return rc;
     if (!params && !env_member) return 0;
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    if (params) {
-        hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min(M, FTGP_NET_PARAMS_GRID_Y)), dim3(256), 0, e->stream.get(), N, params,
-                           e->d_pop_params[slot].get(), n, net_member_stride(N.n_floats), M);
-        HIP_TRY(hipGetLastError());
-    }
-    if (env_member) {
-        hipLaunchKernelGGL(ftgp_net_map_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, e->stream.get(), env_member, e->d_pop_map[slot].get(), n_envs, M);
-        HIP_TRY(hipGetLastError());
-    }
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    return on_handle_stream(e, stream, [&] {
+        if (params) if (int rc = launch_net_params(e, N, params, S->d_pop_params.get(), net_member_stride(N.n_floats), M)) return rc;
+        if (env_member) {
+            hipLaunchKernelGGL(ftgp_net_map_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, e->stream.get(), env_member, S->d_pop_map.get(), n_envs, M);
+            HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    });
 }
 
 int ftgp_get_net_population(FtgpEnv* e, int slot, int32_t* n_members_out, int32_t* env_member_out, int member, float* params_out)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_population: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    const NetDev& N = e->nets[slot];
-    if (!N.defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_population: network slot %d is not defined (ftgp_set_net)", slot);
-    const int M = e->pop_members[slot];
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_get_net_population", slot, kSlotDefined, S)) return rc;
+    const int M = S->pop_members;
     if (n_members_out) *n_members_out = M;
     if (!env_member_out && !params_out) return 0;
-    if (!M) return failf(FTGP_ERR_STATE, "ftgp_get_net_population: network slot %d carries no population (ftgp_set_net_population)", slot);
+    if (int rc = net_slot(e, "ftgp_get_net_population", slot, kSlotPopulation, S)) return rc;
     if (params_out && (member < 0 || member >= M)) return failf(FTGP_ERR_ARG, "ftgp_get_net_population: member = %d outside [0, n_members = %d)", member, M);
     HIP_TRY(hipSetDevice(e->device));
-    std::vector<float> img;
-    if (int rc = net_host_buffer(img, params_out ? (size_t)N.n_floats : 0, "ftgp_get_net_population")) return rc;
-    if (env_member_out) HIP_TRY(hipMemcpyAsync(env_member_out, e->d_pop_map[slot].get(), sizeof(int32_t) * (size_t)e->P.n_envs, hipMemcpyDeviceToHost, e->stream.get()));
     if (params_out)
-        HIP_TRY(hipMemcpyAsync(img.data(), e->d_pop_params[slot].get() + (size_t)member * (size_t)net_member_stride(N.n_floats), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
-    HIP_TRY(hipStreamSynchronize(e->stream.get()));
-    if (params_out) ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), params_out);
+        if (int rc = download_params(e, "ftgp_get_net_population", S->net, S->d_pop_params.get() + (size_t)member * (size_t)net_member_stride(S->net.n_floats), params_out)) return rc;
+    if (env_member_out) {
+        HIP_TRY(hipMemcpyAsync(env_member_out, S->d_pop_map.get(), sizeof(int32_t) * (size_t)e->P.n_envs, hipMemcpyDeviceToHost, e->stream.get()));
+        HIP_TRY(hipStreamSynchronize(e->stream.get()));
+    }
     return 0;
 }
 
 int ftgp_get_net_frame(FtgpEnv* e, int slot, FtgpNetFrame* frame_out)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_frame: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_frame: network slot %d is not defined (ftgp_set_net)", slot);
-    if (frame_out) *frame_out = e->net_frame[slot];
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_get_net_frame", slot, kSlotDefined, S)) return rc;
+    if (frame_out) *frame_out = S->frame;
     return 0;
 }
 
 int ftgp_get_net_rivals(FtgpEnv* e, int slot, FtgpNetRivals* rivals_out)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_net_rivals: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_get_net_rivals: network slot %d is not defined (ftgp_set_net)", slot);
-    if (rivals_out) *rivals_out = e->net_rivals[slot];
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_get_net_rivals", slot, kSlotDefined, S)) return rc;
+    if (rivals_out) *rivals_out = S->rivals;
     return 0;
 }
 
@@ -2478,15 +2508,7 @@ int ftgp_get_net_rivals(FtgpEnv* e, int slot, FtgpNetRivals* rivals_out)
 static int check_value_desc(const FtgpValueDesc& d)
 {
     if (d.reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: reserved must be 0%s");
-    if (d.n_layers < 1 || d.n_layers > FTGP_NET_MAX_LAYERS) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: n_layers = %d outside 1 .. %d", d.n_layers, FTGP_NET_MAX_LAYERS);
-    for (int l = 0; l < FTGP_NET_MAX_LAYERS; ++l) {
-        const int w = d.width[l];
-        if (l >= d.n_layers) { if (w != 0) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: width[%d] = %d behind the last layer must be 0", l, w); }
-        else if (l == d.n_layers - 1) { if (w != 1) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: width[%d] = %d: the last layer has exactly 1 output", l, w); }
-        else if (w < 1 || w > FTGP_NET_MAX_HIDDEN) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: width[%d] = %d outside 1 .. %d", l, w, FTGP_NET_MAX_HIDDEN);
-    }
-    if (d.hidden_act < FTGP_ACT_IDENTITY || d.hidden_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: hidden_act = %d is no FTGP_ACT_*", d.hidden_act);
-    if (d.out_act < FTGP_ACT_IDENTITY || d.out_act > FTGP_ACT_TANH) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: out_act = %d is no FTGP_ACT_*", d.out_act);
+    if (int rc = check_layers("ftgp_set_value_net", 1, d.n_layers, d.width, d.hidden_act, d.out_act)) return rc;
     if (!std::isfinite(d.out_scale)) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: out_scale is not finite%s");
     if (!std::isfinite(d.out_offset)) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: out_offset is not finite%s");
     return 0;
@@ -2497,40 +2519,28 @@ static int check_value_desc(const FtgpValueDesc& d)
 static NetDev value_record(const FtgpValueDesc& d, int n_in)
 {
     NetDev N{};
-    N.defined = 1; N.n_layers = d.n_layers; N.hidden_act = d.hidden_act; N.out_act = d.out_act;
-    N.width[0] = n_in;
-    int o = 0;
-    for (int l = 0; l < d.n_layers; ++l) {
-        N.width[l + 1] = d.width[l];
-        const int ld = (d.width[l] + FTGP_WAVE - 1) & ~(FTGP_WAVE - 1);
-        N.w_off[l] = o; o += N.width[l] * ld;
-        N.b_off[l] = o; o += ld;
-    }
-    N.n_floats = o;
+    N.defined = 1; N.hidden_act = d.hidden_act; N.out_act = d.out_act;
+    lay_out_layers(N, n_in, d.n_layers, d.width);
     N.out_scale[0] = d.out_scale; N.out_offset[0] = d.out_offset;
     return N;
 }
 
 int ftgp_set_value_net(FtgpEnv* e, int slot, const FtgpValueDesc* desc, const float* params)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_value_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_value_net: network slot %d is not defined (ftgp_set_net)", slot);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_set_value_net", slot, kSlotDefined, S)) return rc;
     if (desc) {
         if (int rc = check_value_desc(*desc)) return rc;
         if (!params) return fail(FTGP_ERR_ARG, "ftgp_set_value_net: params is NULL%s");
     }
-    if (!desc && !e->vnets[slot].defined) return 0;              // there is none
+    if (!desc && !S->vnet.defined) return 0;                  // there is none
     HIP_TRY(hipSetDevice(e->device));
     NetDev N{};
     DevBuf<float> buf;
     DevBuf<NetDev> table;
     if (desc) {
-        N = value_record(*desc, e->nets[slot].width[0]);
-        std::vector<float> img;                               // the library's layout; the padding is zeros
-        if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_set_value_net")) return rc;
-        ftgp_net_population_to_library(N.n_layers, N.width, 1, params, img.data());
-        HIP_TRY(dev_upload(buf, img.data(), sizeof(float) * img.size()));
+        N = value_record(*desc, S->net.width[0]);
+        if (int rc = upload_params("ftgp_set_value_net", N, 1, (size_t)N.n_floats, params, buf)) return rc;
         N.params = buf.get();
         if (!e->d_vnets) {                                    // the first value net of the handle: the records, every slot empty
             HIP_TRY(dev_alloc(table, sizeof(NetDev) * FTGP_MAX_NETS));
@@ -2541,45 +2551,28 @@ int ftgp_set_value_net(FtgpEnv* e, int slot, const FtgpValueDesc* desc, const fl
     NetDev* records = table ? table.get() : e->d_vnets.get();
     HIP_TRY(hipMemcpy(records + slot, &N, sizeof N, hipMemcpyHostToDevice));
     if (table) e->d_vnets = std::move(table);
-    e->vnets[slot] = N;
-    e->vnet_desc[slot] = desc ? *desc : FtgpValueDesc{};
-    e->d_vnet_params[slot] = std::move(buf);                  // (the old buffer goes: nothing reads it any more)
-    e->trainers[slot] = FtgpEnv::Trainer{};                   // a trainer ends with the value net it stepped
+    S->end_value();                                           // (the old buffer goes: nothing reads it any more)
+    if (desc) { S->vnet = N; S->vdesc = *desc; S->d_vparams = std::move(buf); }
     return 0;
 }
 
 int ftgp_set_value_net_device(FtgpEnv* e, void* stream, int slot, const float* params)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_set_value_net_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->vnets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_set_value_net_device: network slot %d has no value net (ftgp_set_value_net)", slot);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_set_value_net_device", slot, kSlotValue, S)) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    const int n = (int)net_param_count(e->vnets[slot]);
-    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_set_value_net_device: %s", m.c_str()); return rc; };
-    if (int rc = check_device_buffer(e, params, sizeof(float) * (size_t)n, "params")) return refused(rc);
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    hipLaunchKernelGGL(ftgp_net_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream.get(), e->vnets[slot], params, e->d_vnet_params[slot].get(), n, 0, 1);
-    HIP_TRY(hipGetLastError());
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    if (int rc = check_device_buffer(e, "ftgp_set_value_net_device", params, sizeof(float) * net_param_count(S->vnet), "params")) return rc;
+    return on_handle_stream(e, stream, [&] { return launch_net_params(e, S->vnet, params, S->d_vparams.get(), 0, 1); });
 }
 
 int ftgp_get_value_net(FtgpEnv* e, int slot, FtgpValueDesc* desc_out, float* params_out)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_get_value_net: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    const NetDev& N = e->vnets[slot];
-    if (!N.defined) return failf(FTGP_ERR_STATE, "ftgp_get_value_net: network slot %d has no value net (ftgp_set_value_net)", slot);
-    if (desc_out) *desc_out = e->vnet_desc[slot];
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_get_value_net", slot, kSlotValue, S)) return rc;
+    if (desc_out) *desc_out = S->vdesc;
     if (!params_out) return 0;
     HIP_TRY(hipSetDevice(e->device));
-    std::vector<float> img;
-    if (int rc = net_host_buffer(img, (size_t)N.n_floats, "ftgp_get_value_net")) return rc;
-    HIP_TRY(hipMemcpyAsync(img.data(), e->d_vnet_params[slot].get(), sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
-    HIP_TRY(hipStreamSynchronize(e->stream.get()));
-    ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), params_out);
-    return 0;
+    return download_params(e, "ftgp_get_value_net", S->vnet, S->d_vparams.get(), params_out);
 }
 
 // ---- training on the device (include/ftgp.h "Training on the device") ----
@@ -2587,21 +2580,18 @@ static bool train_fraction(float b) { return std::isfinite(b) && b >= 0.0f && b 
 
 int ftgp_train_begin(FtgpEnv* e, int slot, const FtgpTrainDesc* desc)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_begin: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_train_begin", slot, 0, S)) return rc;
     if (!desc) return fail(FTGP_ERR_ARG, "ftgp_train_begin: desc is NULL%s");
     if (!train_fraction(desc->beta1)) return fail(FTGP_ERR_ARG, "ftgp_train_begin: beta1 is not finite or outside [0, 1)%s");
     if (!train_fraction(desc->beta2)) return fail(FTGP_ERR_ARG, "ftgp_train_begin: beta2 is not finite or outside [0, 1)%s");
     if (!std::isfinite(desc->eps) || !(desc->eps > 0.0f)) return fail(FTGP_ERR_ARG, "ftgp_train_begin: eps is not finite or <= 0%s");
     if (desc->reserved != 0) return fail(FTGP_ERR_ARG, "ftgp_train_begin: reserved must be 0%s");
-    if (!e->nets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d is not defined (ftgp_set_net)", slot);
-    if (!e->vnets[slot].defined) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d has no value net (ftgp_set_value_net)", slot);
-    if (e->pop_members[slot]) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d carries a population of %d members", slot, e->pop_members[slot]);
-    if (e->trainers[slot].on) return failf(FTGP_ERR_STATE, "ftgp_train_begin: network slot %d has a trainer already (ftgp_train_end)", slot);
+    if (int rc = net_slot(e, "ftgp_train_begin", slot, kSlotDefined | kSlotValue | kSlotNoPopulation | kSlotNoTrainer, S)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     FtgpEnv::Trainer T;
     T.desc = *desc;
-    T.n[0] = e->nets[slot].n_floats; T.n[1] = e->vnets[slot].n_floats;
+    T.n[0] = S->net.n_floats; T.n[1] = S->vnet.n_floats;
     const size_t total = (size_t)T.n[0] + (size_t)T.n[1];
     HIP_TRY(dev_zeros(T.grad, sizeof(float) * total, e->stream.get()));
     HIP_TRY(dev_zeros(T.m, sizeof(float) * total, e->stream.get()));
@@ -2612,18 +2602,17 @@ int ftgp_train_begin(FtgpEnv* e, int slot, const FtgpTrainDesc* desc)
     HIP_TRY(dev_zeros(T.sync, sizeof(int32_t) * 2, e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     T.on = true;
-    e->trainers[slot] = std::move(T);
+    S->trainer = std::move(T);
     return 0;
 }
 
 int ftgp_train_end(FtgpEnv* e, int slot)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_end: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
-    if (!e->trainers[slot].on) return failf(FTGP_ERR_STATE, "ftgp_train_end: network slot %d has no trainer (ftgp_train_begin)", slot);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_train_end", slot, kSlotTrainer, S)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream.get()));           // no launch is using the buffers while they go
-    e->trainers[slot] = FtgpEnv::Trainer{};
+    S->end_trainer();
     return 0;
 }
 
@@ -2646,9 +2635,10 @@ int ftgp_train_grad_device(FtgpEnv* e, const FtgpTrainBatch* b)
 {
     if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
     if (!b) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: the batch is NULL%s");
-    if (b->slot < 0 || b->slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: slot = %d outside 0 .. %d", b->slot, FTGP_MAX_NETS - 1);
-    FtgpEnv::Trainer& R = e->trainers[b->slot];
-    if (!R.on) return failf(FTGP_ERR_STATE, "ftgp_train_grad_device: network slot %d has no trainer (ftgp_train_begin)", b->slot);
+    static const char* const entry = "ftgp_train_grad_device";
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, entry, b->slot, kSlotTrainer, S)) return rc;
+    FtgpEnv::Trainer& R = S->trainer;
     if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: reserved must be 0%s");
     if (b->n_rows < 1) return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: n_rows = %d must be >= 1", b->n_rows);
     if (b->n_batch < 1) return failf(FTGP_ERR_ARG, "ftgp_train_grad_device: n_batch = %d must be >= 1", b->n_batch);
@@ -2659,26 +2649,22 @@ int ftgp_train_grad_device(FtgpEnv* e, const FtgpTrainBatch* b)
     if (!std::isfinite(b->clip) || b->clip < 0.0f) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: clip is not finite or < 0%s");
     if (!std::isfinite(b->value_coef) || b->value_coef < 0.0f) return fail(FTGP_ERR_ARG, "ftgp_train_grad_device: value_coef is not finite or < 0%s");
     HIP_TRY(hipSetDevice(e->device));
-    const NetDev& N = e->nets[b->slot]; const NetDev& V = e->vnets[b->slot];
+    const NetDev& N = S->net; const NetDev& V = S->vnet;
     const size_t rows = (size_t)b->n_rows, B = (size_t)b->n_batch, n_in = (size_t)N.width[0];
-    auto refused = [](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "ftgp_train_grad_device: %s", m.c_str()); return rc; };
-    auto checked = [&](const void* p, size_t bytes, const char* name) { return check_device_buffer(e, p, bytes, name) ? refused(FTGP_ERR_ARG) : 0; };
-    if (b->index) if (int rc = checked(b->index, sizeof(int32_t) * B, "index")) return rc;
-    if (int rc = checked(b->inputs, sizeof(float) * rows * n_in, "inputs")) return rc;
-    if (int rc = checked(b->mean, sizeof(float) * rows * 2, "mean")) return rc;
-    if (b->noise) if (int rc = checked(b->noise, sizeof(float) * rows * 2, "noise")) return rc;
-    if (int rc = checked(b->advantage, sizeof(float) * rows, "advantage")) return rc;
-    if (int rc = checked(b->ret, sizeof(float) * rows, "ret")) return rc;
-    if (b->weight) if (int rc = checked(b->weight, sizeof(float) * rows, "weight")) return rc;
-    if (b->stats) if (int rc = checked(b->stats, sizeof(float) * FTGP_TRAIN_STATS, "stats")) return rc;
-    if (b->new_mean) if (int rc = checked(b->new_mean, sizeof(float) * B * 2, "new_mean")) return rc;
-    if (b->new_value) if (int rc = checked(b->new_value, sizeof(float) * B, "new_value")) return rc;
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
+    if (b->index) if (int rc = check_device_buffer(e, entry, b->index, sizeof(int32_t) * B, "index")) return rc;
+    if (int rc = check_device_buffer(e, entry, b->inputs, sizeof(float) * rows * n_in, "inputs")) return rc;
+    if (int rc = check_device_buffer(e, entry, b->mean, sizeof(float) * rows * 2, "mean")) return rc;
+    if (b->noise) if (int rc = check_device_buffer(e, entry, b->noise, sizeof(float) * rows * 2, "noise")) return rc;
+    if (int rc = check_device_buffer(e, entry, b->advantage, sizeof(float) * rows, "advantage")) return rc;
+    if (int rc = check_device_buffer(e, entry, b->ret, sizeof(float) * rows, "ret")) return rc;
+    if (b->weight) if (int rc = check_device_buffer(e, entry, b->weight, sizeof(float) * rows, "weight")) return rc;
+    if (b->stats) if (int rc = check_device_buffer(e, entry, b->stats, sizeof(float) * FTGP_TRAIN_STATS, "stats")) return rc;
+    if (b->new_mean) if (int rc = check_device_buffer(e, entry, b->new_mean, sizeof(float) * B * 2, "new_mean")) return rc;
+    if (b->new_value) if (int rc = check_device_buffer(e, entry, b->new_value, sizeof(float) * B, "new_value")) return rc;
 
     TrainArgs T{};
-    T.net[0] = train_net(N, e->d_net_params[b->slot].get(), 0);
-    T.net[1] = train_net(V, e->d_vnet_params[b->slot].get(), R.n[0]);
+    T.net[0] = train_net(N, S->d_params.get(), 0);
+    T.net[1] = train_net(V, S->d_vparams.get(), R.n[0]);
     int act_floats = 0, ld_max = FTGP_WAVE;
     for (int w = 0; w < 2; ++w) {
         const TrainNet& t = T.net[w];
@@ -2701,67 +2687,62 @@ int ftgp_train_grad_device(FtgpEnv* e, const FtgpTrainBatch* b)
     const int G = std::min(T.n_tiles, FTGP_TRAIN_MAX_WG);
     const size_t lds = (size_t)tile * (size_t)T.row_floats * sizeof(float);
 
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)b->stream)) return rc;
-    if (tile == 32) hipLaunchKernelGGL(ftgp_train_grad_kernel<32>, dim3((unsigned)G), dim3(FTGP_TRAIN_THREADS), lds, e->stream.get(), T);
-    else hipLaunchKernelGGL(ftgp_train_grad_kernel<16>, dim3((unsigned)G), dim3(FTGP_TRAIN_THREADS), lds, e->stream.get(), T);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(R.sync.get(), 0, sizeof(int32_t) * 2, e->stream.get()));
-    TrainReduceArgs A{};
-    A.part = R.part.get(); A.part_stats = R.stats.get(); A.part_wide = T.part_wide; A.G = G; A.n_total = T.n_total;
-    A.grad = R.grad.get(); A.sync = R.sync.get(); A.stats = R.stats.get() + (size_t)FTGP_TRAIN_MAX_WG * FTGP_TRAIN_STATS; A.stats_out = b->stats;
-    hipLaunchKernelGGL(ftgp_train_reduce_kernel, dim3((unsigned)((T.n_total + 255) / 256)), dim3(256), 0, e->stream.get(), A);
-    HIP_TRY(hipGetLastError());
-    return caller_waits_for_handle(e, (hipStream_t)b->stream);
+    return on_handle_stream(e, b->stream, [&] {
+        if (tile == 32) hipLaunchKernelGGL(ftgp_train_grad_kernel<32>, dim3((unsigned)G), dim3(FTGP_TRAIN_THREADS), lds, e->stream.get(), T);
+        else hipLaunchKernelGGL(ftgp_train_grad_kernel<16>, dim3((unsigned)G), dim3(FTGP_TRAIN_THREADS), lds, e->stream.get(), T);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(R.sync.get(), 0, sizeof(int32_t) * 2, e->stream.get()));
+        TrainReduceArgs A{};
+        A.part = R.part.get(); A.part_stats = R.stats.get(); A.part_wide = T.part_wide; A.G = G; A.n_total = T.n_total;
+        A.grad = R.grad.get(); A.sync = R.sync.get(); A.stats = R.stats.get() + (size_t)FTGP_TRAIN_MAX_WG * FTGP_TRAIN_STATS; A.stats_out = b->stats;
+        hipLaunchKernelGGL(ftgp_train_reduce_kernel, dim3((unsigned)((T.n_total + 255) / 256)), dim3(256), 0, e->stream.get(), A);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 int ftgp_train_adam_device(FtgpEnv* e, void* stream, int slot, float lr)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_adam_device: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_train_adam_device", slot, 0, S)) return rc;
     if (!std::isfinite(lr) || lr < 0.0f) return fail(FTGP_ERR_ARG, "ftgp_train_adam_device: lr is not finite or < 0%s");
-    FtgpEnv::Trainer& R = e->trainers[slot];
-    if (!R.on) return failf(FTGP_ERR_STATE, "ftgp_train_adam_device: network slot %d has no trainer (ftgp_train_begin)", slot);
+    if (int rc = net_slot(e, "ftgp_train_adam_device", slot, kSlotTrainer, S)) return rc;
+    FtgpEnv::Trainer& R = S->trainer;
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->ds.ev_in) HIP_TRY(make_event(e->ds.ev_in, hipEventDisableTiming));
-    if (!e->ds.ev_out) HIP_TRY(make_event(e->ds.ev_out, hipEventDisableTiming));
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    R.t += 1;
-    float s[6];
-    ftgp_adam_scalars(R.desc.beta1, R.desc.beta2, lr, R.t, s);
-    TrainAdamArgs A{};
-    A.p[0] = e->d_net_params[slot].get(); A.p[1] = e->d_vnet_params[slot].get(); A.n[0] = R.n[0]; A.n[1] = R.n[1];
-    A.grad = R.grad.get(); A.m = R.m.get(); A.v = R.v.get(); A.sync = R.sync.get();
-    A.b1 = s[0]; A.b2 = s[1]; A.omb1 = s[2]; A.omb2 = s[3]; A.a = s[4]; A.r = s[5]; A.eps = R.desc.eps;
-    hipLaunchKernelGGL(ftgp_train_adam_kernel, dim3((unsigned)((R.n[0] + R.n[1] + 255) / 256)), dim3(256), 0, e->stream.get(), A);
-    HIP_TRY(hipGetLastError());
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    return on_handle_stream(e, stream, [&] {
+        R.t += 1;
+        float s[6];
+        ftgp_adam_scalars(R.desc.beta1, R.desc.beta2, lr, R.t, s);
+        TrainAdamArgs A{};
+        A.p[0] = S->d_params.get(); A.p[1] = S->d_vparams.get(); A.n[0] = R.n[0]; A.n[1] = R.n[1];
+        A.grad = R.grad.get(); A.m = R.m.get(); A.v = R.v.get(); A.sync = R.sync.get();
+        A.b1 = s[0]; A.b2 = s[1]; A.omb1 = s[2]; A.omb2 = s[3]; A.a = s[4]; A.r = s[5]; A.eps = R.desc.eps;
+        hipLaunchKernelGGL(ftgp_train_adam_kernel, dim3((unsigned)((R.n[0] + R.n[1] + 255) / 256)), dim3(256), 0, e->stream.get(), A);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 int ftgp_train_get(FtgpEnv* e, int slot, int what, float* policy_out, float* value_out, int64_t* steps_out)
 {
-    if (!e) return fail(FTGP_ERR_ARG, "null handle%s");
-    if (slot < 0 || slot >= FTGP_MAX_NETS) return failf(FTGP_ERR_ARG, "ftgp_train_get: slot = %d outside 0 .. %d", slot, FTGP_MAX_NETS - 1);
+    FtgpEnv::NetSlot* S;
+    if (int rc = net_slot(e, "ftgp_train_get", slot, 0, S)) return rc;
     if (what < FTGP_TRAIN_GRAD || what > FTGP_TRAIN_RAW_PARAMS) return failf(FTGP_ERR_ARG, "ftgp_train_get: what = %d is no FTGP_TRAIN_*", what);
-    FtgpEnv::Trainer& R = e->trainers[slot];
-    if (!R.on) return failf(FTGP_ERR_STATE, "ftgp_train_get: network slot %d has no trainer (ftgp_train_begin)", slot);
+    if (int rc = net_slot(e, "ftgp_train_get", slot, kSlotTrainer, S)) return rc;
+    FtgpEnv::Trainer& R = S->trainer;
     if (steps_out) *steps_out = R.t;
     if (!policy_out && !value_out) return 0;
     HIP_TRY(hipSetDevice(e->device));
     if (what >= FTGP_TRAIN_RAW_GRAD) {                         // the library's layout as it lies in device memory, padding included
         const bool g = what == FTGP_TRAIN_RAW_GRAD;
-        if (policy_out) HIP_TRY(hipMemcpyAsync(policy_out, g ? R.grad.get() : e->d_net_params[slot].get(), sizeof(float) * (size_t)R.n[0], hipMemcpyDeviceToHost, e->stream.get()));
-        if (value_out) HIP_TRY(hipMemcpyAsync(value_out, g ? R.grad.get() + R.n[0] : e->d_vnet_params[slot].get(), sizeof(float) * (size_t)R.n[1], hipMemcpyDeviceToHost, e->stream.get()));
+        if (policy_out) HIP_TRY(hipMemcpyAsync(policy_out, g ? R.grad.get() : S->d_params.get(), sizeof(float) * (size_t)R.n[0], hipMemcpyDeviceToHost, e->stream.get()));
+        if (value_out) HIP_TRY(hipMemcpyAsync(value_out, g ? R.grad.get() + R.n[0] : S->d_vparams.get(), sizeof(float) * (size_t)R.n[1], hipMemcpyDeviceToHost, e->stream.get()));
         HIP_TRY(hipStreamSynchronize(e->stream.get()));
         return 0;
     }
-    std::vector<float> img;
-    if (int rc = net_host_buffer(img, (size_t)R.n[0] + (size_t)R.n[1], "ftgp_train_get")) return rc;
     const float* src = what == FTGP_TRAIN_GRAD ? R.grad.get() : what == FTGP_TRAIN_M ? R.m.get() : R.v.get();
-    HIP_TRY(hipMemcpyAsync(img.data(), src, sizeof(float) * img.size(), hipMemcpyDeviceToHost, e->stream.get()));
-    HIP_TRY(hipStreamSynchronize(e->stream.get()));
-    const NetDev& N = e->nets[slot]; const NetDev& V = e->vnets[slot];
-    if (policy_out) ftgp_net_population_from_library(N.n_layers, N.width, 1, img.data(), policy_out);
-    if (value_out) ftgp_net_population_from_library(V.n_layers, V.width, 1, img.data() + R.n[0], value_out);
+    if (policy_out) if (int rc = download_params(e, "ftgp_train_get", S->net, src, policy_out)) return rc;
+    if (value_out) if (int rc = download_params(e, "ftgp_train_get", S->vnet, src + R.n[0], value_out)) return rc;
     return 0;
 }
 
@@ -2775,13 +2756,11 @@ int ftgp_env_state_bytes(FtgpEnv* e, size_t* bytes_per_env)
 // the checks ftgp_save_envs_device and ftgp_load_envs_device (`entry`) share; `need_all`: row e of every env must exist
 static int env_state_checks(FtgpEnv* e, const char* entry, const void* rows, int64_t n_rows, bool need_all, const void* per_env, size_t per_env_bytes, const char* per_env_name)
 {
-    // (check_device_buffer words its refusals for the device step: put this entry's name in front)
-    auto refused = [entry](int rc) { const std::string m(g_err); snprintf(g_err, sizeof g_err, "%s: %s", entry, m.c_str()); return rc; };
     if (n_rows < 1 || n_rows > 0x7fffffffll) return failf(FTGP_ERR_ARG, "%s: n_rows = %lld, not in 1 .. 2^31 - 1", entry, (long long)n_rows);
     if (need_all && n_rows < e->P.n_envs) return failf(FTGP_ERR_ARG, "%s: n_rows = %lld, fewer than the handle's %d envs", entry, (long long)n_rows, e->P.n_envs);
-    if (int rc = check_device_buffer(e, rows, env_state_bytes(e->P) * (size_t)n_rows, "rows")) return refused(rc);
+    if (int rc = check_device_buffer(e, entry, rows, env_state_bytes(e->P) * (size_t)n_rows, "rows")) return rc;
     if ((uintptr_t)rows % 16 != 0) return failf(FTGP_ERR_ARG, "%s: rows is not 16-byte aligned", entry);
-    if (per_env) if (int rc = check_device_buffer(e, per_env, per_env_bytes, per_env_name)) return refused(rc);
+    if (per_env) if (int rc = check_device_buffer(e, entry, per_env, per_env_bytes, per_env_name)) return rc;
     return 0;
 }
 
@@ -2793,10 +2772,11 @@ int ftgp_save_envs_device(FtgpEnv* e, void* stream, void* rows, int64_t n_rows, 
     if (int rc = ensure_env_state(e)) return rc;
     EnvStateArgs A = env_state_args(e, rows, n_rows);
     A.env_mask = env_mask;
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    hipLaunchKernelGGL(ftgp_env_save_kernel, dim3(env_state_blocks(e)), dim3(FTGP_ENV_STATE_THREADS), 0, e->stream.get(), e->P, A);
-    HIP_TRY(hipGetLastError());
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    return on_handle_stream(e, stream, [&] {
+        hipLaunchKernelGGL(ftgp_env_save_kernel, dim3(env_state_blocks(e)), dim3(FTGP_ENV_STATE_THREADS), 0, e->stream.get(), e->P, A);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 int ftgp_load_envs_device(FtgpEnv* e, void* stream, const void* rows, int64_t n_rows, const int32_t* src_row)
@@ -2807,11 +2787,12 @@ int ftgp_load_envs_device(FtgpEnv* e, void* stream, const void* rows, int64_t n_
     if (int rc = ensure_env_state(e)) return rc;
     EnvStateArgs A = env_state_args(e, const_cast<void*>(rows), n_rows);
     A.src_row = src_row;
-    if (int rc = handle_waits_for_caller(e, (hipStream_t)stream)) return rc;
-    hipLaunchKernelGGL(ftgp_env_load_kernel, dim3(env_state_blocks(e)), dim3(FTGP_ENV_STATE_THREADS), 0, e->stream.get(), e->P, A);
-    HIP_TRY(hipGetLastError());
-    e->rows_valid = false; e->launch_metrics_valid = false;
-    return caller_waits_for_handle(e, (hipStream_t)stream);
+    return on_handle_stream(e, stream, [&] {
+        hipLaunchKernelGGL(ftgp_env_load_kernel, dim3(env_state_blocks(e)), dim3(FTGP_ENV_STATE_THREADS), 0, e->stream.get(), e->P, A);
+        HIP_TRY(hipGetLastError());
+        e->rows_valid = false; e->launch_metrics_valid = false;
+        return 0;
+    });
 }
 
 int ftgp_get_env_state_rejected(FtgpEnv* e, int64_t* rejected)

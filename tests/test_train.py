@@ -431,5 +431,12 @@ def test_device_vec_env_ppo_update():
 
 
 @pytest.mark.gpu
+def test_what_ends_with_what_on_a_slot():
+    """ftgp_set_net, ftgp_set_net_population, ftgp_set_value_net and ftgp_train_end at every edge of a slot's lifetime rules; the
+    stream-ordered setters as a handle's first stream-ordered call."""
+    assert "lifecycle ok" in run_child("lifecycle")
+
+
+@pytest.mark.gpu
 def test_the_ppo_tool_with_the_device_update():
     assert "ppo tool ok" in run_child("ppo_tool")

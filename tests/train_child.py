@@ -545,6 +545,158 @@ def wrapper(opt):
     print("wrapper ok")
 
 
+def lifecycle(opt):
+    """What ends with what on a network slot (include/ftgp.h), edge by edge through capi alone on 2 envs of 1 car and 36 rays: after every
+    setter, what must be gone is refused with its code and its words, what must have survived reads back with the bits that went in, and
+    slot 0 -- a policy, a value net and a trainer one Adam step old -- is untouched by everything done to slot 1.  Then each stream-ordered
+    entry that needs no ftgp_device_io_config, as the first stream-ordered call of a fresh handle, on a stream of the caller's.
+    (A slot cannot hold a population and a trainer at once -- either refuses the other --, so ftgp_set_net meets them in two steps.)"""
+    lib, track = capi.load(), load_track("small-circle")
+    rng = np.random.default_rng(23)
+    N_IN, KW = 8, dict(pool=1, max_range=3.0, beam_first=4, n_beams=8)       # the drivers' window of 36 rays: [4, 32)
+
+    def mlp(*widths):
+        return [(rng.standard_normal((o, i)).astype(F), rng.standard_normal(o).astype(F)) for i, o in zip(widths[:-1], widths[1:])]
+
+    def fresh():
+        return capi.Env(lib, track, n_envs=2, cars_per_env=1, n_rays=36, spawn_mode=1, seed=3)
+
+    def gone(call, code, *words):
+        try:
+            call()
+        except capi.FtgpError as x:
+            assert x.code == code and all(w in str(x) for w in words), (code, words, str(x))
+        else:
+            raise AssertionError(f"accepted: what should be refused with {code} {words}")
+
+    def bits(what, got, want):
+        cmod.assert_same_bits(tm.flat(got), tm.flat(want), what)
+
+    env = fresh()
+
+    def policy_is(what, slot, layers):
+        bits(f"{what}: slot {slot}'s policy", env.net(slot)[1], layers)
+
+    def value_is(what, slot, layers):
+        bits(f"{what}: slot {slot}'s value net", env.get_value_net(slot)[1], layers)
+
+    def no_trainer(slot):
+        gone(lambda: env._call("train_get", slot, capi.TRAIN_GRAD, None, None, None), ERR_STATE, "train_get", "trainer")
+        gone(lambda: env.train_adam_device(slot, 1e-3), ERR_STATE, "train_adam_device", "trainer")
+        gone(lambda: env.train_end(slot), ERR_STATE, "train_end", "trainer")
+
+    def no_value(slot, defined=True):
+        gone(lambda: env._call("get_value_net", slot, None, None), ERR_STATE, "get_value_net", "value net")
+        gone(lambda: env.train_begin(slot), ERR_STATE, "train_begin", "value net" if defined else "not defined")
+
+    def no_population(slot):
+        assert env.get_net_population(slot) == (0, None)
+        gone(lambda: env.set_net_population_device(slot, 0, 0), ERR_STATE, "set_net_population_device", "population")
+        gone(lambda: env.get_net_population(slot, 0), ERR_STATE, "get_net_population", "population")
+
+    # slot 0: everything a slot can hold beside a population, and one Adam step on a zero gradient (t = 1, the parameters as they were)
+    P0, V0 = mlp(N_IN, 4, 2), mlp(N_IN, 4, 1)
+    env.set_net(0, P0, **KW); env.set_value_net(0, V0); env.train_begin(0); env.train_adam_device(0, 1e-3)
+
+    def slot0_untouched(what):
+        policy_is(what, 0, P0); value_is(what, 0, V0)
+        pol, val, t = env.train_get(0, capi.TRAIN_M)
+        assert t == 1 and not pol.any() and not val.any(), (what, t)
+        assert env.get_net_population(0) == (0, None), what
+    slot0_untouched("at the start")
+
+    P1, V1, P1b, V1b = mlp(N_IN, 4, 2), mlp(N_IN, 4, 1), mlp(N_IN, 5, 2), mlp(N_IN, 3, 1)
+    members, env_member = np.stack([tm.flat(mlp(N_IN, 4, 2)) for _ in range(2)]), np.array([1, 0], dtype=np.int32)
+
+    def population_is(what):
+        n, m = env.get_net_population(1)
+        assert n == 2 and (m == env_member).all(), (what, n, m)
+        for k in range(2):
+            cmod.assert_same_bits(env.get_net_population(1, k), members[k], f"{what}: member {k}")
+        gone(lambda: env.set_net_device(1, 0), ERR_STATE, "set_net_device", "population", "member")
+
+    # ftgp_set_net_population with members on a slot with a value net and a trainer: the trainer is gone, the value net stays
+    env.set_net(1, P1, **KW); env.set_value_net(1, V1); env.train_begin(1)
+    assert env.train_get(1)[2] == 0
+    env.set_net_population(1, members, env_member)
+    what = "a population installed"
+    no_trainer(1); population_is(what); policy_is(what, 1, P1); value_is(what, 1, V1); slot0_untouched(what)
+    gone(lambda: env.train_begin(1), ERR_STATE, "train_begin", "population", "member")
+    # ftgp_set_net with a new description on a slot with a population and a value net: both are gone, the slot is defined
+    env.set_net(1, P1b, **KW)
+    what = "set_net on a population and a value net"
+    policy_is(what, 1, P1b); no_population(1); no_value(1); no_trainer(1); slot0_untouched(what)
+    # ... and on a slot with a value net and a trainer
+    env.set_value_net(1, V1b); env.train_begin(1)
+    env.set_net(1, P1, **KW)
+    what = "set_net on a value net and a trainer"
+    policy_is(what, 1, P1); no_population(1); no_value(1); no_trainer(1); slot0_untouched(what)
+    # ftgp_set_net(NULL): the slot is undefined
+    env.set_net(1, None)
+    for call, entry in ((lambda: env.net(1), "get_net"), (lambda: env.net_frame(1), "get_net_frame"), (lambda: env.net_rivals(1), "get_net_rivals"),
+                        (lambda: env.get_net_population(1), "get_net_population"), (lambda: env.set_value_net(1, V1), "get_net"),
+                        (lambda: env.set_net_population(1, None), "set_net_population"), (lambda: env.set_net_device(1, 0), "set_net_device")):
+        gone(call, ERR_STATE, entry, "slot 1", "not defined")
+    no_value(1, defined=False); no_trainer(1); slot0_untouched("set_net(NULL)")
+    gone(lambda: env.rollout("net1", 1), ERR_STATE, "slot 1", "not defined")
+    # ftgp_set_net_population with 0 members: the single set is in force again, bit for bit, and the value net stays
+    env.set_net(1, P1, **KW); env.set_value_net(1, V1); env.set_net_population(1, members, env_member)
+    population_is("a population again")
+    env.set_net_population(1, None)
+    what = "the population removed"
+    no_population(1); policy_is(what, 1, P1); value_is(what, 1, V1); no_trainer(1); slot0_untouched(what)
+    same = dev(tm.flat(P1))
+    env.set_net_device(1, same.data_ptr()); torch.cuda.synchronize()        # accepted again: no population
+    policy_is(what + ", set_net_device", 1, P1)
+    # ftgp_set_value_net with a description, then with NULL, on a slot with a trainer: the trainer is gone each time, the policy stays
+    env.train_begin(1)
+    env.set_value_net(1, V1b)
+    what = "set_value_net on a trainer"
+    no_trainer(1); policy_is(what, 1, P1); value_is(what, 1, V1b); no_population(1); slot0_untouched(what)
+    env.train_begin(1)
+    env.set_value_net(1, None)
+    what = "set_value_net(NULL) on a trainer"
+    no_trainer(1); no_value(1); policy_is(what, 1, P1); no_population(1); slot0_untouched(what)
+    # ftgp_train_end: both nets stay
+    env.set_value_net(1, V1); env.train_begin(1)
+    env.train_end(1)
+    what = "train_end"
+    no_trainer(1); policy_is(what, 1, P1); value_is(what, 1, V1); no_population(1); slot0_untouched(what)
+    env.train_begin(1)                                           # ... and a new trainer starts at t = 0
+    assert env.train_get(1)[2] == 0
+    env.close()
+
+    # each stream-ordered entry as a fresh handle's first stream-ordered call, on a stream of the caller's
+    stream = torch.cuda.Stream()
+    new = dev(tm.flat(P1))
+    torch.cuda.synchronize()
+    env = fresh(); env.set_net(0, P0, **KW)
+    env.set_net_device(0, new.data_ptr(), stream=stream.cuda_stream); stream.synchronize()
+    policy_is("set_net_device first", 0, P1)
+    env.close()
+    new = dev(tm.flat(V1))
+    torch.cuda.synchronize()
+    env = fresh(); env.set_net(0, P0, **KW); env.set_value_net(0, V0)
+    env.set_value_net_device(0, new.data_ptr(), stream=stream.cuda_stream); stream.synchronize()
+    value_is("set_value_net_device first", 0, V1); policy_is("set_value_net_device first", 0, P0)
+    env.close()
+    env = fresh(); env.set_net(0, P0, **KW); env.set_value_net(0, V0); env.train_begin(0)
+    env.train_adam_device(0, 1e-3, stream=stream.cuda_stream); stream.synchronize()
+    assert env.train_get(0)[2] == 1
+    policy_is("train_adam_device first", 0, P0); value_is("train_adam_device first", 0, V0)      # (a zero gradient moves nothing)
+    env.close()
+    env = fresh()
+    n = env.env_state_bytes() * 2
+    rows, again = (torch.full((n,), 0xAA, dtype=torch.uint8, device=DEV) for _ in range(2))
+    torch.cuda.synchronize()
+    env.save_envs_device(rows.data_ptr(), 2, stream=stream.cuda_stream); stream.synchronize()
+    env.save_envs_device(again.data_ptr(), 2, stream=stream.cuda_stream)
+    env.load_envs_device(rows.data_ptr(), 2, stream=stream.cuda_stream); stream.synchronize()
+    assert (rows.cpu().numpy() != 0xAA).any() and rows.cpu().numpy().tobytes() == again.cpu().numpy().tobytes() and env.env_state_rejected() == 0
+    env.close()
+    print("lifecycle ok")
+
+
 def ppo_tool(opt):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ppo.py"), "--device-update", "--envs", "64", "--iterations", "2"],
                        cwd=ROOT, capture_output=True, text=True, timeout=240)
@@ -560,4 +712,4 @@ if __name__ == "__main__":
     scenario = sys.argv[1]
     options = json.loads(sys.argv[2]) if len(sys.argv) > 2 else {}
     {"gradient": gradient, "turns": turns, "collected": collected, "adam": adam, "determinism": determinism, "guards": guards, "optimises": optimises,
-     "wrapper": wrapper, "ppo_tool": ppo_tool}[scenario](options)
+     "wrapper": wrapper, "lifecycle": lifecycle, "ppo_tool": ppo_tool}[scenario](options)
